@@ -9,7 +9,10 @@ so accumulation frames may go out several at a time (--batch B, rvpt_hip_dispatc
 B frames x pixels, bit-identical to B dispatches).  Default for brute force: B = 64, the ABI's maximum — the K steps go out as few
 launches as that allows (20 steps: one launch; 200: 4 x 50), which measured best at every N.  K steps are always K frames of the same work.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N>1: launched by torch.distributed.run)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]          (N>1: launched by torch.distributed.run)
+
+A plain run measures the headline only; --full adds the CPU oracle legs and the one-dispatch-per-frame leg.  --dump-outputs DIR writes
+the finished frame of the last timed step; the same arguments give the same frame in every run.
 
 N ranks tile-partition the SAME image (strong scaling); the only collective is one RCCL gather of per-tile
 radiance to rank 0 when the finished frame is requested after the K-th step; it is timed separately (`frame_request`),
@@ -90,10 +93,39 @@ def parse():
     ap.add_argument("--serial-launches", action="store_true",
                     help="diagnostic (tools/gpu_profile.sh's kernel-trace pass): wait for every launch of the timed region before the next goes out, so "
                          "that a profiler's per-launch durations are durations of ONE kernel and not of three queued behind each other")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-one-frame-leg", action="store_true", help="skip the one-dispatch-per-frame measurement after the timed region (profiling runs: every dispatch of the process then has the same shape)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the oracle sample")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU oracle legs (cpu_baseline*) and the one-dispatch-per-frame leg "
+                         "(value_one_frame_per_launch); a plain run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle legs")
+    ap.add_argument("--no-one-frame-leg", action="store_true", help="with --full: skip the one-dispatch-per-frame measurement after the timed region (profiling runs: every dispatch of the process then has the same shape)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: target CPU time of the oracle sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the finished frame of the last step (what gather_frame / read_frame return) as DIR/frame.npy, float32 "
+                         "[H, W, 4]; a frame over 64 MB as a fixed, seeded sample of its pixels (DIR/frame_sample.npy + DIR/frame_sample_index.npy)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.emulate_world > 1:
+        ap.error("--dump-outputs: an emulated rank's share is not a frame")
+    return args
+
+
+DUMP_BYTES = 64 * 10 ** 6  # at most this much in all under --dump-outputs
+
+
+def dump_outputs(dirname, frame, limit=DUMP_BYTES):
+    """--dump-outputs: the finished frame [H, W, 4] float32 as DIR/frame.npy, or, when that exceeds `limit`, a fixed sample of its pixels (all four channels,
+    pixels picked by a generator seeded with 0, in row-major order) as DIR/frame_sample.npy [n, 4] float32 and their row-major indices as
+    DIR/frame_sample_index.npy float64 — the same pixels for the same shape in every run."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= limit:
+        np.save(d / "frame.npy", frame)
+        return
+    px = frame.reshape(-1, frame.shape[-1])
+    n = limit // (px.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+    np.save(d / "frame_sample.npy", px[idx])
+    np.save(d / "frame_sample_index.npy", idx.astype(np.float64))
 
 
 def cpu_baseline(args, tris, mats, nodes, cam, target_s, traversal=None, size=None):
@@ -337,6 +369,9 @@ def main():
     # the W warm-up steps follow the ramp without a gap and run right up to the opening barrier: a GPU that sat idle for a few
     # hundred microseconds (a host-side wait, a sysfs read) starts the timed region below its sustained clock — over 20 frames
     # that was 6 200-6 370 against 6 440-6 640 Msamples/s with a busy run-up
+    # The warm-up starts a fresh accumulation (frame 0, as RVPT::update does after a camera move): the ramp above runs for a time, not a number
+    # of frames, and without the reset the frames of the timed region — and the frame --dump-outputs writes — would depend on how many it got through.
+    r.local._previous_key = None
     run(args.warmup)
 
     # the timed region: EXACTLY K steps of the hot path between two barriers
@@ -363,7 +398,7 @@ def main():
 
     # One dispatch per frame — the reference's own shape (RVPT::draw: one compute pass per frame, rvpt.cpp:346-354; a moving camera leaves nothing to batch) — timed
     # the same way over 20 .. 300 frames (about a quarter of a second), after the timed region (so that `value` is untouched): what a caller that cannot batch gets (VERDICT r5 #2d)
-    one_n = 0 if args.no_one_frame_leg else max(20, min(300, int(0.25 / max(elapsed / args.steps, 1e-9))))  # ~a quarter of a second of frames, 20 .. 300
+    one_n = 0 if (args.no_one_frame_leg or not args.full) else max(20, min(300, int(0.25 / max(elapsed / args.steps, 1e-9))))  # ~a quarter of a second of frames, 20 .. 300
     # (the counters above were read with the GPU idle: a burst of ~300 launches first — the launch shape's buffers, the shader clock back out of idle, as the ramp and the
     # warm-up steps do for `value` — then five repetitions of one_n frames, each between two barriers; the MEDIAN is reported, as tools/one_frame_per_launch.py does)
     one_reps = []
@@ -630,7 +665,7 @@ def main():
                                                      "what a moving camera gets), wall clock between two barriers, median of five repetitions after a burst of 300 untimed launches, measured after the timed region; `value` batches K still-camera "
                                                      "frames per launch (rvpt_hip_dispatch_frames)"}
         out["clocks"] = {"profiled_clock_mhz": (prof or {}).get("profiled_clock_mhz"), "ramp_seconds": args.ramp_seconds, "ramp_frames_untimed": ramp_frames}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # Three legs inside the same budget (--cpu-seconds, default 12 s of oracle time): the workload's own traversal (the algorithm the GPU path
             # runs), the reference's LIVE algorithm when that is a different one (the BVH walk; the headline's brute force has no reference
             # counterpart: like-for-like against the reference is cpu_baseline_bvh), and BASELINE config 1 (256 x 256, both traversals).
@@ -645,6 +680,8 @@ def main():
             c1 = {t: cpu_baseline(*scene_args, args.cpu_seconds * 0.05, traversal=t, size=(256, 256)) for t in dict.fromkeys([args.traversal, "bvh"])}
             out["cpu_baseline_c1"] = {"config": "BASELINE config 1: 256x256, 1 spp", **{t: {k: v[k] for k in ("value", "unit", "cores", "kind", "min", "max", "sample")} for t, v in c1.items()}}
         line = json.dumps(out)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame.cpu().numpy())
     else:
         line = None
     r.shutdown()

@@ -26,6 +26,12 @@ def build() -> None:
     subprocess.run(["make", "-C", str(_HERE)], check=True, capture_output=True)
 
 
+def can_build() -> bool:
+    """The recipe's input (the reference's compiled shader, named by the Makefile alone) is readable here: a dry run of the recipe succeeds.
+    False where the reference tree is absent or belongs to another user."""
+    return subprocess.run(["make", "-n", "-C", str(_HERE)], capture_output=True).returncode == 0
+
+
 def lib(fused=False) -> C.CDLL:
     """fused: False = no contraction, True = the build's contraction rule; or a variant name: "ieee" / "fused_ieee" (the one
     OpFDiv(OpDot, OpDot) as C's `/`), "libm" (a different admissible driver: libm sin/cos/tan, plain dot and normalize)."""

@@ -1776,7 +1776,7 @@ def test_bench_under_torchrun_with_ranks_sharing_one_gpu(native, world):
     env = dict(os.environ, RVPT_BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(port),
            str(ROOT / "bench.py"), "--gpus", str(world), "--steps", "20" if world == 8 else "6", "--warmup", "5" if world == 8 else "2", "--width", "640", "--height", "360",
-           "--no-cpu-baseline", "--ramp-seconds", "0"]
+           "--full", "--no-cpu-baseline", "--ramp-seconds", "0"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
@@ -1788,6 +1788,31 @@ def test_bench_under_torchrun_with_ranks_sharing_one_gpu(native, world):
     # the collective describes itself: ranks sharing one GPU cannot form an RCCL communicator, and the line says so instead of passing for RCCL
     assert line["collective"]["path"] == "host-staged" and line["collective"]["rccl_ranks"] == 0 and line["collective"]["gather_ms"] > 0
     assert line["value_one_frame_per_launch"]["value"] > 0 and line["value_one_frame_per_launch"]["frames"] >= 20
+
+
+def test_bench_dump_outputs_is_the_timed_frame(native, oracle, tmp_path):
+    """bench.py --dump-outputs DIR: the finished frame of the last timed step as DIR/frame.npy — the same bits whatever the time-bounded ramp got
+    through (the warm-up starts a fresh accumulation), and the oracle's chain over the W + K frames since.  A plain run carries no CPU leg and
+    no one-frame leg."""
+    import json
+    import subprocess
+    import sys
+    from rvpt_amd import Camera
+    W, H, K, warm = 128, 64, 3, 2
+    dumps = []
+    for ramp in ("0", "0.2"):
+        out = tmp_path / f"ramp{ramp}"
+        res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", str(K), "--warmup", str(warm), "--width", str(W), "--height", str(H),
+                              "--ramp-seconds", ramp, "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads(res.stdout.strip().splitlines()[-1])
+        assert line["steps"] == K and line["ms_per_step"] > 0 and "cpu_baseline" not in line and line["value_one_frame_per_launch"] is None
+        assert sorted(p.name for p in out.iterdir()) == ["frame.npy"]
+        dumps.append(np.load(out / "frame.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (H, W, 4)
+    assert np.array_equal(dumps[0].view(np.uint32), dumps[1].view(np.uint32))
+    ref, _ = oracle_frames(oracle, scene_by_name("default"), Camera(W / H).get_data(), W, H, "brute", range(warm + K))
+    assert_parity(dumps[0], ref[-1], "bench.py --dump-outputs")
 
 
 def test_bench_with_gpus_n_fans_out_by_itself_or_fails(native):

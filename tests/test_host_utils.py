@@ -203,11 +203,36 @@ def test_bench_cli_defaults_and_cpu_baseline_leg(oracle, default_scene):
         sys.argv = argv
     assert a.gpus == 1 and 0 < a.steps <= 1000 and 0 <= a.warmup <= 100 and (a.width, a.height, a.aa, a.bounces) == (1920, 1080, 1, 8)
     assert a.traversal == "brute" and a.scene == "default"
+    assert not a.full and a.dump_outputs is None  # a plain run measures the headline only and writes nothing
     tris, mats, nodes = default_scene
     a.width, a.height = 64, 32
     from _util import identity_camera
     out = bench.cpu_baseline(a, tris, mats, nodes, identity_camera(2.0), 0.3)
     assert out["kind"] == "port" and out["unit"] == "Msamples/s" and out["value"] > 0 and out["cores"] >= 1 and "64x32" in out["sample"]
+
+
+def test_bench_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path):
+    """bench.dump_outputs: a frame within the limit as frame.npy (float32, unchanged); a larger one as the same seeded sample of pixels in every call,
+    float32 values and float64 row-major indices, within the limit in all."""
+    import importlib.util
+    from pathlib import Path
+    spec = importlib.util.spec_from_file_location("bench_module", Path(__file__).resolve().parent.parent / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    frame = np.random.default_rng(5).random((30, 40, 4), dtype=np.float32)
+    bench.dump_outputs(tmp_path / "whole", frame)
+    assert sorted(p.name for p in (tmp_path / "whole").iterdir()) == ["frame.npy"]
+    got = np.load(tmp_path / "whole" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    limit = 4000
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, frame, limit=limit)
+        assert sorted(p.name for p in (tmp_path / d).iterdir()) == ["frame_sample.npy", "frame_sample_index.npy"]
+        assert sum(p.stat().st_size - 128 for p in (tmp_path / d).iterdir()) <= limit  # (128: the .npy header)
+    vals, idx = np.load(tmp_path / "a" / "frame_sample.npy"), np.load(tmp_path / "a" / "frame_sample_index.npy")
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == (idx.size, 4) and idx.size > 0
+    assert np.all(np.diff(idx) > 0) and np.array_equal(vals, frame.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_sample_index.npy"))
 
 
 def test_bench_gpus_n_without_devices_fails_with_the_reason():

@@ -4,7 +4,7 @@
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/config_table.jsonl
 : > $OUT
-run() { echo "## $*" >&2; python $REPO/bench.py "$@" 2>/dev/null | tail -1 >> $OUT; }
+run() { echo "## $*" >&2; python $REPO/bench.py --full "$@" 2>/dev/null | tail -1 >> $OUT; }
 CPU="--cpu-seconds 6"
 run --width 256 --height 256 --steps 400 --warmup 40 $CPU
 run --width 256 --height 256 --steps 400 --warmup 40 --traversal bvh $CPU

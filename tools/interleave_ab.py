@@ -46,7 +46,7 @@ def bench():
     for g in groups:
         env = {"RVPT_HIP_PACKETS_INTERLEAVE": g}
         k20 = [line(["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-one-frame-leg"], env).get("value") for _ in range(3)]
-        d = line(["--steps", "200", "--warmup", "20", "--no-cpu-baseline"], env)
+        d = line(["--steps", "200", "--warmup", "20", "--full", "--no-cpu-baseline"], env)
         sh = [line(["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-one-frame-leg", "--emulate-world", "8", "--emulate-rank", r], env) for r in ("3", "5")]
         one = subprocess.run([py, str(ROOT / "tools" / "one_frame_per_launch.py")], env={**os.environ, **env}, capture_output=True, text=True).stdout.strip()
         print(f"interleave {g}: k20 {k20} k200 {d.get('value')} one-frame leg {d.get('value_one_frame_per_launch', {}).get('value')} share-of-8 ms/frame {[s.get('ms_per_frame_wall') for s in sh]} kernel ms {[s.get('kernel_ms') for s in sh]}")

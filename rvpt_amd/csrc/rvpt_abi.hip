@@ -109,12 +109,9 @@ struct rvpt_hip_ctx {
     size_t cap_wideq = 0, cap_leaf_box = 0;
     bool has_quant = false;
     float slab_extent = 0.0f;
-    int bvh_quant = 0;               // RVPT_HIP_BVH_QUANT=1: the 64-byte quantised nodes (bit-exact, measured SLOWER: profiles/EXPERIMENTS.md 5.16)
     float4 *d_wide8 = nullptr;       // the 8-wide form (rvpt_bvh8.hip; RVPT_HIP_BVH_WIDE8=1): 256-byte nodes
     size_t n_wide8 = 0, cap_wide8 = 0;
     uint32_t wide8_stack_levels = 0;
-    int bvh_wide8 = 0;
-    int bvh_wide = 1;                // policy: BVH contexts, lean configuration, reference order, HBM-resident scene: the wide kernel (RVPT_HIP_BVH_WIDE=0 / RVPT_HIP_BVH_PER_LANE: binary)
     uint32_t bvh_head_shift = 0;  // see FrameParams::head_shift
     size_t cap_tris = 0, cap_prep = 0, cap_mat_index = 0, cap_mats = 0, cap_nodes = 0;  // allocated elements
     bool have_scene = false;
@@ -135,25 +132,16 @@ struct rvpt_hip_ctx {
     std::vector<rvpt_hip_ctx *> local_group;  // single-process form (comm_init_all): every rank's context, index == rank
     uint32_t *d_stack_overflow[kMaxSlots] = {};  // HBM-resident BVH kernel: stack levels beyond the LDS ones, per launch in flight
     size_t stack_overflow_cap[kMaxSlots] = {};   // in words
-    int brute_packets_policy = 1;             // LDS-resident brute force, lean configuration: the packet kernel (default; RVPT_HIP_BRUTE_MIXED_PACKETS or
-                                              // RVPT_HIP_BRUTE_PACKETS=0 select round 2's trace_brute_resident)
-    // screen rectangles of the triangles for the packet kernel's camera rounds (rvpt_rect.h), one buffer per launch slot: rewritten (camera_rects, on the
-    // slot's own stream, in front of the frame kernel) only when the camera, the image size or the scene differ from what the slot's buffer was made for
     int debug_checks = 0;                     // RVPT_HIP_DEBUG=1: rvpt_hip_wait reads the kernels' error words (traversal-stack overflow) and fails loudly
-    int force_stack_levels = 0;               // RVPT_HIP_BVH_FORCE_STACK_LEVELS (tests of the above): lie to the kernels about the stack the tree needs
-    int packets_cull = 1;                     // RVPT_HIP_PACKETS_CULL=0: no rectangles (A/B)
     // the bounce cull's table (bounce_visibility, once per upload of a scene the packet kernel can hold): 2 n rows of ceil(n / 32) words
-    int packets_bounce_cull = 1;              // RVPT_HIP_PACKETS_BOUNCE_CULL=0: off (A/B)
     uint32_t *d_vis = nullptr;
     size_t vis_cap = 0;                       // in words
     float4 *d_leaf_boxes = nullptr;           // the leaf boxes of the bounce rounds (rvpt_vis.h), made with the table; two float4 per kLeafTris triangles
     size_t leaf_boxes_cap = 0;                // in float4
-    int packets_box_cull = 1;                 // RVPT_HIP_PACKETS_BOX_CULL=0: off (A/B)
-    int packets_lean_instance = 1;            // (laboratory build: RVPT_HIP_PACKETS_LEAN_INSTANCE=0 keeps the general instances — A/B)
-    int packets_interleave = 1;               // RVPT_HIP_PACKETS_INTERLEAVE=g: launches of fewer than four frames deal groups of g (1, 2, 4, 8) blocks from all over the frame; 0 = tile-linear order (A/B)
-    int packets_interleave_all = 0;           // ... =-g: launches of any size (measured slower for the batched ones: profiles/r06_interleave.txt)
     uint32_t vis_words = 0;                   // 0: no table for this scene
     double scene_scale = 0.0;                 // largest |coordinate| + largest extent of the uploaded triangles: what float errors of positions scale with
+    // screen rectangles of the triangles for the packet kernel's camera rounds (rvpt_rect.h), one buffer per launch slot: rewritten (camera_rects, on the
+    // slot's own stream, in front of the frame kernel) only when the camera, the image size or the scene differ from what the slot's buffer was made for
     uint2 *d_rects[kMaxSlots] = {};
     float4 *d_cam_records[kMaxSlots] = {};   // the camera records of the packet kernel (rvpt_early_out.h), made with the slot's rectangles: 16 B per triangle
     size_t rects_cap[kMaxSlots] = {};         // in triangles
@@ -167,7 +155,6 @@ struct rvpt_hip_ctx {
     void *d_quant = nullptr;                  // rank 0: width*height*4 B, rgba8 of a gathered frame
     unsigned long long *d_timeline = nullptr;  // RVPT_HIP_TIMELINE=<file>: per-wave timestamps of the last frame
     size_t timeline_words = 0;
-    std::string timeline_path;
 
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, spare;
@@ -176,16 +163,30 @@ struct rvpt_hip_ctx {
     uint64_t n_timed = 0;
     uint32_t last_grid = 0, last_lds = 0, last_variant = 0;
     uint32_t last_cull = 0;  // rvpt_hip_get_cull_info: what the last launch rode with
-    // tuning knobs, read from the environment once at create (0 = use the built-in policy)
-    struct {
-        int blocks_per_cu = 0, first_units = 0, claim_units = 0, bvh_refill = 0, bvh_leaf_batch = 0;
-        int bvh_top_nodes = -1;  // -1 = the built-in 256
-        int bvh_stack_lds = 0;   // stack levels kept in LDS by the HBM-resident BVH kernel (0 = built-in 8)
-        int bvh_wide_resident = 1;  // RVPT_HIP_BVH_WIDE_RESIDENT=0: LDS-resident scenes on the binary camera-packet kernel instead of the wide tree (trace_bvh4_resident)
-        int bvh_no_resident = 0; // RVPT_HIP_BVH_NO_RESIDENT: never the LDS-resident BVH instances
-        int bvh_cam_min = 0;     // camera packets: lanes that must start a camera ray together (0 = built-in)
-        int bvh_detach = -1;     // camera packets: the lanes of a node leave the packet at this many or fewer (-1 = built-in)
-    } tune;
+    // The policy knobs, read once at create (read_knobs); the release library reads only the culls' and the interleave's, the others keep these defaults there
+    struct Knobs {
+        bool bvh_wide = true;             // BVH contexts, lean configuration, reference order: the wide kernels (RVPT_HIP_BVH_PER_LANE / RVPT_HIP_BVH_WIDE=0: binary)
+        bool bvh_wide8 = false;           // RVPT_HIP_BVH_WIDE8=1: the 8-wide walk (rvpt_bvh8.hip) on HBM-resident scenes
+        bool bvh_quant = false;           // RVPT_HIP_BVH_QUANT=1: the 64-byte quantised nodes (bit-exact, measured SLOWER: profiles/EXPERIMENTS.md 5.16)
+        bool bvh_wide_resident = true;    // RVPT_HIP_BVH_WIDE_RESIDENT=0: LDS-resident scenes on the binary camera-packet kernel instead of the wide tree (trace_bvh4_resident)
+        bool bvh_no_resident = false;     // RVPT_HIP_BVH_NO_RESIDENT=1: never the LDS-resident BVH instances
+        bool bvh_no_packed_heads = false; // RVPT_HIP_BVH_NO_PACKED_HEADS (set): the stack keeps node indices and the walk fetches (first, count) at the pop (FrameParams::head_shift = 0)
+        bool bvh_caller_layout = false;   // RVPT_HIP_BVH_CALLER_LAYOUT (set): the device keeps the uploaded node order (no breadth-first layout, no wide forms)
+        bool brute_packets = true;        // LDS-resident brute force, lean configuration: the packet kernel (RVPT_HIP_BRUTE_MIXED_PACKETS / RVPT_HIP_BRUTE_PACKETS=0: trace_brute_resident)
+        int force_stack_levels = 0;       // RVPT_HIP_BVH_FORCE_STACK_LEVELS (tests of RVPT_HIP_DEBUG): lie to the kernels about the stack the tree needs
+        bool packets_cull = true, packets_bounce_cull = true, packets_box_cull = true;  // RVPT_HIP_PACKETS_CULL / _BOUNCE_CULL / _BOX_CULL=0: each cull off (A/B)
+        bool packets_lean_instance = true;  // RVPT_HIP_PACKETS_LEAN_INSTANCE=0: the general instances only (A/B)
+        int packets_interleave = 1;       // RVPT_HIP_PACKETS_INTERLEAVE=g: launches of < 4 frames deal groups of g (1, 2, 4, 8) blocks from all over the frame; 0 = tile-linear (A/B)
+        bool packets_interleave_all = false;  // ... =-g: launches of any size (measured slower for the batched ones: profiles/r06_interleave.txt)
+        std::string timeline_path;        // RVPT_HIP_TIMELINE=<file>: the last frame's per-wave timestamps, written at destroy
+        int blocks_per_cu = 0;            // RVPT_HIP_BLOCKS_PER_CU: work-groups per CU of the persistent kernels (0 / -1 here and below: the built-in policy)
+        int first_units = 0, claim_units = 0;  // RVPT_HIP_FIRST_UNITS, RVPT_HIP_CLAIM_UNITS: the work plan's static chunk and claim size (plan_work)
+        int bvh_refill = 0, bvh_leaf_batch = 0;  // RVPT_HIP_BVH_REFILL, RVPT_HIP_BVH_LEAF_BATCH: FrameParams::bvh_refill, bvh_leaf_batch
+        int bvh_top_nodes = -1;           // RVPT_HIP_BVH_TOP_NODES: nodes of the tree's top in LDS (HBM-resident scenes; 0 = no LDS copy)
+        int bvh_stack_lds = 0;            // RVPT_HIP_BVH_STACK_LDS: stack levels kept in LDS where the rest goes to global memory
+        int bvh_cam_min = 0;              // RVPT_HIP_BVH_CAM_MIN: camera packets: lanes that must start a camera ray together
+        int bvh_detach = -1;              // RVPT_HIP_BVH_DETACH: camera packets: the lanes of a node leave the packet at this many or fewer
+    } knobs;
     const void *occ_kernel = nullptr;  // cached occupancy query (kernel, lds) -> work-groups per CU
     size_t occ_lds = 0;
     int occ_per_cu = 0;
@@ -200,17 +201,49 @@ namespace {
 
 thread_local std::string g_err;  // for calls that fail before a context exists
 
-// Knobs of the laboratory build (librvpt_hip_debug.so, -DRVPT_HIP_LAB=1: rvpt_amd/build.py): the sweeps of rounds 1-5 found each of them flat around its
-// default (profiles/r05_bvh_thresholds.txt, EXPERIMENTS.md), so the release library reads none of them — there they are the constants of the built-in policy.
-inline const char *lab_env(const char *name)
+// A context's knobs, from its create flags and the environment (rvpt_hip_ctx::Knobs).
+rvpt_hip_ctx::Knobs read_knobs(uint32_t flags)
 {
+    auto set_flag = [](bool &knob, const char *e) { knob = e ? atoi(e) > 0 : knob; };
+    auto set_int = [](int &knob, const char *e, int lo, int hi) { knob = e ? std::max(lo, std::min(hi, atoi(e))) : knob; };
+    rvpt_hip_ctx::Knobs k;
+    k.bvh_wide = (flags & RVPT_HIP_BVH_PER_LANE) == 0;
+    k.brute_packets = (flags & RVPT_HIP_BRUTE_MIXED_PACKETS) == 0;
+    set_flag(k.packets_cull, getenv("RVPT_HIP_PACKETS_CULL"));
+    set_flag(k.packets_bounce_cull, getenv("RVPT_HIP_PACKETS_BOUNCE_CULL"));
+    set_flag(k.packets_box_cull, getenv("RVPT_HIP_PACKETS_BOX_CULL"));
+    if (const char *e = getenv("RVPT_HIP_PACKETS_INTERLEAVE")) {
+        const int g = std::abs(atoi(e));
+        k.packets_interleave_all = atoi(e) < 0;
+        k.packets_interleave = (g == 1 || g == 2 || g == 4 || g == 8) ? g : 0;
+    }
 #if RVPT_HIP_LAB
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
+    // Knobs of the laboratory build (librvpt_hip_debug.so, -DRVPT_HIP_LAB=1: rvpt_amd/build.py): the sweeps of rounds 1-5 found each of them flat around its
+    // default (profiles/r05_bvh_thresholds.txt, EXPERIMENTS.md), so the release library reads none of them — there they are the constants of the built-in policy.
+    set_flag(k.bvh_wide, getenv("RVPT_HIP_BVH_WIDE"));  // experiments: A/B a whole run
+    set_flag(k.bvh_wide8, getenv("RVPT_HIP_BVH_WIDE8"));
+    set_flag(k.bvh_quant, getenv("RVPT_HIP_BVH_QUANT"));
+    set_flag(k.bvh_wide_resident, getenv("RVPT_HIP_BVH_WIDE_RESIDENT"));
+    set_flag(k.bvh_no_resident, getenv("RVPT_HIP_BVH_NO_RESIDENT"));
+    k.bvh_no_packed_heads = getenv("RVPT_HIP_BVH_NO_PACKED_HEADS") != nullptr;
+    k.bvh_caller_layout = getenv("RVPT_HIP_BVH_CALLER_LAYOUT") != nullptr;
+    set_flag(k.brute_packets, getenv("RVPT_HIP_BRUTE_PACKETS"));
+    set_int(k.force_stack_levels, getenv("RVPT_HIP_BVH_FORCE_STACK_LEVELS"), 0, INT32_MAX);
+    set_flag(k.packets_lean_instance, getenv("RVPT_HIP_PACKETS_LEAN_INSTANCE"));
+    if (const char *e = getenv("RVPT_HIP_TIMELINE")) k.timeline_path = e;
+    set_int(k.blocks_per_cu, getenv("RVPT_HIP_BLOCKS_PER_CU"), 1, 8);
+    set_int(k.first_units, getenv("RVPT_HIP_FIRST_UNITS"), 1, 1 << 20);
+    set_int(k.claim_units, getenv("RVPT_HIP_CLAIM_UNITS"), 1, 1 << 20);
+    set_int(k.bvh_refill, getenv("RVPT_HIP_BVH_REFILL"), 1, 64);
+    set_int(k.bvh_leaf_batch, getenv("RVPT_HIP_BVH_LEAF_BATCH"), 1, 64);
+    set_int(k.bvh_top_nodes, getenv("RVPT_HIP_BVH_TOP_NODES"), 0, 2048);
+    set_int(k.bvh_stack_lds, getenv("RVPT_HIP_BVH_STACK_LDS"), 1, 64);
+    set_int(k.bvh_cam_min, getenv("RVPT_HIP_BVH_CAM_MIN"), 1, 65);  // 65 = never
+    set_int(k.bvh_detach, getenv("RVPT_HIP_BVH_DETACH"), 0, 64);
 #endif
+    return k;
 }
+
 void drop_comm(rvpt_hip_ctx *ctx);  // defined with the collective, used by destroy
 
 // RCCL entry points, resolved on first use: a single-GPU host needs no RCCL at all, and inside a torch process the
@@ -334,19 +367,30 @@ int sync_all(rvpt_hip_ctx *ctx)
 uint32_t owned_tiles(uint32_t n_tiles, uint32_t rank, uint32_t world) { return (n_tiles > rank) ? (n_tiles - rank + world - 1) / world : 0; }
 
 using Kernel = void (*)(const rv::FrameParams);
+
+// The kernel paths of a launch, by the number rvpt_hip_get_launch_info reports (bench.py and the tests compare against these numbers).  Retired: 9, the streamed
+// packet kernel of round 4, measured no faster (profiles/r04_exp_stream_packets.patch); 4, 5, the wavefront pipelines of round 3 (profiles/r04_exp_wavefront_pipelines.patch)
+enum class Variant : uint32_t {
+    BruteResident = 0, BruteStream = 1,  // brute force, scene in LDS (mixed packets: trace_brute_resident) / streamed through LDS
+    Bvh = 2, BvhResident = 3,            // binary tree, scene in HBM / in LDS
+    BrutePackets = 6,                    // brute force, scene in LDS: the packet kernel (rvpt_packets.hip)
+    Wide = 10, WideResident = 11,        // the 4-wide tree (rvpt_bvh4.hip), scene in HBM / in LDS with camera packets
+    Wide8 = 12, WideQuant = 13,          // laboratory: the 8-wide walk (RVPT_HIP_BVH_WIDE8=1) / the 4-wide one over 64-byte quantised nodes (RVPT_HIP_BVH_QUANT=1)
+};
+
+// the paths that keep the levels of the traversal stack beyond the LDS ones in global memory (FrameParams::stack_overflow)
+bool has_global_stack(Variant v) { return v == Variant::Bvh || v == Variant::Wide || v == Variant::WideResident || v == Variant::Wide8 || v == Variant::WideQuant; }
+
+// rvpt_hip_get_cull_info bits (native.cull_info, tools/fuzz_culls.py): the screen rectangles (FrameParams::rects), the bounce table (vis), camera rounds
+// aligned to 16 x 4 blocks, the leaf boxes of the bounce rounds (leaf_boxes), the interleaved claim order (perm_*), the packet instance without the uncull'd walks
+constexpr uint32_t kCullRects = 1u, kCullBounce = 2u, kCullBlockRounds = 4u, kCullLeafBoxes = 16u, kCullClaimOrder = 32u, kCullLeanInstance = 64u;
+
 struct Launch {
     Kernel kernel;
-    size_t lds;        // dynamic LDS bytes per work-group
-    uint32_t grid;     // work-groups
-    uint32_t variant;  // 0 brute/LDS-resident (mixed packets), 1 brute/LDS-streamed, 2 bvh, 3 bvh/LDS-resident, 6 brute/LDS-resident packet kernel,
-                       // 10 bvh over the 4-wide tree, 11 the same with the scene in LDS and camera packets, 12 the 8-wide walk (RVPT_HIP_BVH_WIDE8=1),
-                       // 13 the 4-wide walk over 64-byte quantised nodes (RVPT_HIP_BVH_QUANT=1) (9: the streamed packet kernel of round 4,
-                       // measured no faster and retired: profiles/r04_exp_stream_packets.patch)
-                       // (4, 5: the wavefront pipelines of round 3, retired in ABI 5 — profiles/r04_exp_wavefront_pipelines.patch)
-    bool regen;
-    int slots = 3;     // launches in flight this launch rotates over (slots_for)
-    bool lone = false; // no launch of this context is in flight when this one goes out
-    bool cull = false; // packet kernel: the screen rectangles of the triangles ride along (FrameParams::rects)
+    Variant variant;
+    size_t lds;          // dynamic LDS bytes per work-group
+    uint32_t grid;       // work-groups
+    uint32_t cull_bits;  // kCull*: kCullRects = the packet kernel's screen rectangles of the triangles ride along (FrameParams::rects)
 };
 
 // scene pointers, image geometry, the settings/camera blocks of this frame (compute_pass.comp:28-54)
@@ -399,14 +443,21 @@ void fill_frame_params(const rvpt_hip_ctx *ctx, int slot, rv::FrameParams &p, in
     for (int r = 0; r < 3; ++r) p.cam[9 + r] = ctx->camera.matrix[12 + r];
 }
 
-// LDS-resident BVH scenes (nodes + triangles + materials + the whole stack within 64 KiB) run their own kernel instance
-bool bvh_scene_fits_lds(const rvpt_hip_ctx *ctx, uint32_t stack_levels)
+constexpr size_t kLdsBudget = 64 * 1024;  // LDS bytes a work-group gets without opting in to more
+
+// a BVH context with triangles, hence a tree (upload_scene); an empty scene's frames run the brute-force instances over zero triangles
+bool is_bvh(const rvpt_hip_ctx *ctx, size_t n_tris) { return (ctx->flags & RVPT_HIP_TRAVERSAL_MASK) != RVPT_HIP_TRAVERSAL_BRUTE && n_tris > 0; }
+// the binary walk's stack: at most one push per inner level of the path from the root
+uint32_t bvh_stack_levels(const rvpt_hip_ctx *ctx) { return std::max<uint32_t>(1, std::min<uint32_t>(rv::kBvhStackDepth, ctx->bvh_height)); }
+size_t stack_lds_bytes(uint32_t levels) { return static_cast<size_t>(levels) * rv::kBlock * 2 * sizeof(uint32_t); }  // a work-group's stack: two words per slot
+size_t index_bytes(const rvpt_hip_ctx *ctx) { return ((ctx->n_tris + 3) & ~size_t(3)) * 4; }
+size_t bvh_scene_bytes(const rvpt_hip_ctx *ctx) { return ctx->n_nodes * 32 + ctx->n_tris * 64 + index_bytes(ctx) + ctx->n_mats * 48; }
+
+// LDS-resident BVH scenes (nodes + triangles + materials + the whole stack within 64 KiB) run their own kernel instances (unless RVPT_HIP_BVH_NO_RESIDENT)
+bool bvh_scene_fits_lds(const rvpt_hip_ctx *ctx)
 {
-    if (ctx->tune.bvh_no_resident) return false;  // experiments (RVPT_HIP_BVH_NO_RESIDENT): small scenes through the HBM-resident kernels
-    const size_t index_bytes = ((ctx->n_tris + 3) & ~size_t(3)) * 4;
-    const size_t bvh_scene_bytes = ctx->n_nodes * 32 + ctx->n_tris * 64 + index_bytes + ctx->n_mats * 48;
-    const size_t full_stack_bytes = static_cast<size_t>(stack_levels) * rv::kBlock * 2 * sizeof(uint32_t);  // two words per slot
-    return bvh_scene_bytes <= rv::kBvhResidentBytes && bvh_scene_bytes + full_stack_bytes <= 64 * 1024;
+    const size_t bytes = bvh_scene_bytes(ctx);
+    return !ctx->knobs.bvh_no_resident && bytes <= rv::kBvhResidentBytes && bytes + stack_lds_bytes(bvh_stack_levels(ctx)) <= kLdsBudget;
 }
 
 // How many launches in flight.  Three, except for SHORT launches of the HBM-resident BVH kernel (one frame of a large scene,
@@ -417,204 +468,14 @@ int slots_for(const rvpt_hip_ctx *ctx, uint32_t n_frames)
 {
     if (!ctx->overlap) return 1;
     if (ctx->slots_fixed) return ctx->n_slots;
-    const bool bvh = (ctx->flags & RVPT_HIP_TRAVERSAL_MASK) != RVPT_HIP_TRAVERSAL_BRUTE && ctx->n_nodes > 0;
-    const uint32_t levels = std::max<uint32_t>(1, std::min<uint32_t>(rv::kBvhStackDepth, ctx->bvh_height));
-    const bool hbm_bvh = bvh && !bvh_scene_fits_lds(ctx, levels);
+    const bool hbm_bvh = is_bvh(ctx, ctx->n_tris) && !bvh_scene_fits_lds(ctx);
     const uint64_t samples = static_cast<uint64_t>(ctx->n_work) * n_frames * static_cast<uint64_t>(std::max(1, ctx->settings.aa));
     const bool short_launch = samples <= 10ull * 1000 * 1000;
     return std::min(ctx->n_slots, (hbm_bvh && short_launch) ? 6 : 3);
 }
 
-// which kernel instance, how much LDS, how many work-groups
-int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, Launch &l)
-{
-    const bool bvh = (ctx->flags & RVPT_HIP_TRAVERSAL_MASK) != RVPT_HIP_TRAVERSAL_BRUTE && ctx->n_nodes > 0;  // no tree = empty scene
-    const bool ordered = bvh && (ctx->flags & RVPT_HIP_TRAVERSAL_MASK) == RVPT_HIP_TRAVERSAL_BVH_ORDERED;
-    l.regen = (ctx->flags & RVPT_HIP_KERNEL_SIMPLE) == 0;
-    // the lean kernels cover the default configuration (Kajiya everywhere, pinhole); anything else runs the GENERIC ones
-    const bool generic = p.camera_mode != 0 || p.modes[0] != 9 || p.modes[1] != 9 || p.modes[2] != 9 || p.modes[3] != 9;
-    const size_t index_bytes = ((ctx->n_tris + 3) & ~size_t(3)) * 4;
-    // brute force keeps the whole scene in LDS when it fits the 64 KiB a work-group gets without opting in to more
-    const size_t resident_bytes = ctx->n_tris * 64 + index_bytes + (ctx->n_mats <= rv::kResidentMaxMats ? ctx->n_mats * 48 : 0) +
-                                  (rv::kBlock / 64) * 64 * sizeof(uint32_t);
-    const bool resident = !bvh && ctx->n_tris <= rv::kResidentMaxTris && resident_bytes <= 64 * 1024;
-    // BVH: traversal stack sized from the tree; nodes + triangles + materials in LDS too when everything fits 64 KiB
-    // at most one push per inner level of the path from the root
-    p.stack_levels = std::max<uint32_t>(1, std::min<uint32_t>(rv::kBvhStackDepth, ctx->bvh_height));
-    p.head_shift = lab_env("RVPT_HIP_BVH_NO_PACKED_HEADS") ? 0u : ctx->bvh_head_shift;
-    const size_t bvh_scene_bytes = ctx->n_nodes * 32 + ctx->n_tris * 64 + index_bytes + ctx->n_mats * 48;
-    const bool bvh_resident = bvh && bvh_scene_fits_lds(ctx, p.stack_levels);
-    // HBM-resident scenes keep only the first stack levels in LDS (the rest overflows to global memory, rarely touched) so
-    // that the top of the tree fits beside them at full occupancy; LDS-resident scenes keep the whole stack
-    const uint32_t lds_levels_want = ctx->tune.bvh_stack_lds > 0 ? static_cast<uint32_t>(ctx->tune.bvh_stack_lds) : 8u;
-    p.stack_lds_levels = bvh_resident ? p.stack_levels : std::min(p.stack_levels, lds_levels_want);
-    const size_t stack_bytes = static_cast<size_t>(p.stack_lds_levels) * rv::kBlock * 2 * sizeof(uint32_t);
-    // short LDS-resident traversals: let the whole packet finish before refilling (64); long HBM traversals: refill once
-    // half of the packet waits, run the parked leaves in batches of 16 lanes, 3 work-groups per CU (swept on the Cornell and
-    // 1M-triangle scenes, both traversal orders, frames dispatched in batches: profiles/r01_bvh_knob_sweeps.txt)
-    p.bvh_refill = ctx->tune.bvh_refill ? static_cast<uint32_t>(ctx->tune.bvh_refill) : (bvh_resident ? 64u : 32u);
-    p.bvh_leaf_batch = ctx->tune.bvh_leaf_batch ? static_cast<uint32_t>(ctx->tune.bvh_leaf_batch) : 16u;
-    // top of the tree in LDS (HBM-resident scenes): 256 nodes = 8 KiB by default (with 8 two-word stack levels in LDS: 24 KiB per
-    // work-group, six per CU — what the registers allow anyway; swept: tools/archive/sweep_bvh_top.sh, profiles/r02_sweeps.txt), never more than the tree has (even count: sibling pairs)
-    const uint32_t top_want = ctx->tune.bvh_top_nodes >= 0 ? static_cast<uint32_t>(ctx->tune.bvh_top_nodes) : 256u;
-    p.bvh_top_nodes = (bvh && !bvh_resident) ? std::max(2u, std::min<uint32_t>(top_want, static_cast<uint32_t>(ctx->n_nodes)) & ~1u) : 0u;  // at least the root's line
-
-    const int bvh_per_cu = ctx->tune.blocks_per_cu ? ctx->tune.blocks_per_cu : 3;
-    l.lds = bvh ? stack_bytes + (bvh_resident ? bvh_scene_bytes : static_cast<size_t>(p.bvh_top_nodes) * 32) : (resident ? resident_bytes : static_cast<size_t>(rv::kBlock / 64) * (rv::kStreamDepth * rv::kWaveChunk * 64 + 64 * sizeof(uint32_t)));
-    l.variant = bvh ? (bvh_resident ? 3u : 2u) : (resident ? 0u : 1u);
-    const int sel = (l.regen ? 0 : 1) | (generic ? 2 : 0);
-    static const Kernel table[4][4] = {
-        {rv::trace_brute_resident<true, false>, rv::trace_brute_resident<false, false>, rv::trace_brute_resident<true, true>,
-         rv::trace_brute_resident<false, true>},
-        {rv::trace_brute_stream<true, false>, rv::trace_brute_stream<false, false>, rv::trace_brute_stream<true, true>,
-         rv::trace_brute_stream<false, true>},
-        {rv::trace_bvh<true, false, false, false>, rv::trace_bvh<false, false, false, false>, rv::trace_bvh<true, false, true, false>,
-         rv::trace_bvh<false, false, true, false>},
-        {rv::trace_bvh<true, true, false, false>, rv::trace_bvh<false, true, false, false>, rv::trace_bvh<true, true, true, false>,
-         rv::trace_bvh<false, true, true, false>},
-    };
-    static const Kernel ordered_table[2][4] = {
-        {rv::trace_bvh<true, false, false, true>, rv::trace_bvh<false, false, false, true>, rv::trace_bvh<true, false, true, true>,
-         rv::trace_bvh<false, false, true, true>},
-        {rv::trace_bvh<true, true, false, true>, rv::trace_bvh<false, true, false, true>, rv::trace_bvh<true, true, true, true>,
-         rv::trace_bvh<false, true, true, true>},
-    };
-    l.kernel = ordered ? ordered_table[bvh_resident ? 1 : 0][sel] : table[l.variant][sel];
-    // camera packets (trace_bvh4_resident: lanes that start camera rays together walk the tree as one wave-uniform packet in the reference's fixed child
-    // order): at least bvh_cam_min lanes must start a camera ray at once; the lanes of a node leave the packet when at most bvh_detach of them are in it
-    // (LDS-resident scenes: nobody leaves measured best; the binary-tree form of round 4, +5 % resident / +-0 HBM-resident, is profiles/r04_exp_campack_binary.patch)
-    p.bvh_cam_min = ctx->tune.bvh_cam_min ? static_cast<uint32_t>(ctx->tune.bvh_cam_min) : 24u;
-    p.bvh_detach = ctx->tune.bvh_detach >= 0 ? static_cast<uint32_t>(ctx->tune.bvh_detach) : 0u;
-    // the 4-wide form of the tree (rvpt_bvh4.hip): scenes that do not fit LDS, lean configuration, reference order; half the dependent steps per ray
-    const bool wide = bvh && !bvh_resident && !ordered && l.regen && ctx->n_wide > 0 && ctx->bvh_wide == 1 && p.head_shift != 0;
-    if (wide) {
-        l.variant = 10u;
-#if RVPT_HIP_LAB
-        const bool quant = !generic && ctx->has_quant && ctx->bvh_quant == 1;
-        if (quant) l.variant = 13u;
-        l.kernel = generic ? rv::trace_bvh4_generic : (quant ? rv::trace_bvh4q : rv::trace_bvh4);
-#else
-        const bool quant = false;
-        l.kernel = generic ? rv::trace_bvh4_generic : rv::trace_bvh4;
-#endif
-        p.leaf_box = quant ? ctx->d_leaf_box : nullptr;
-        p.slab_extent = ctx->slab_extent;
-        p.wide = quant ? ctx->d_wideq : ctx->d_wide;
-        p.n_wide = static_cast<uint32_t>(ctx->n_wide);
-        p.stack_levels = std::max<uint32_t>(1, ctx->wide_stack_levels);
-        p.stack_lds_levels = std::min(p.stack_levels, lds_levels_want);
-        const uint32_t node_bytes = quant ? 64u : rv::kWideTopQuads * 16u;  // one node in the LDS copy of the tree top
-        const uint32_t wide_top_want = ctx->tune.bvh_top_nodes >= 0 ? static_cast<uint32_t>(ctx->tune.bvh_top_nodes) : (quant ? 128u : 64u);  // 8 KiB, as the binary kernel's 256 nodes
-        // (the knob counts NODES, and a wide node is four binary ones: whatever it asks for, the stack levels + the root record + the top nodes stay within
-        // the 64 KiB a work-group can have — ADVICE r4: RVPT_HIP_BVH_TOP_NODES=2048 used to ask for 256 KiB and fail at launch)
-        const size_t wide_fixed = static_cast<size_t>(p.stack_lds_levels) * rv::kBlock * 2 * sizeof(uint32_t) + 2 * sizeof(float4);
-        const uint32_t wide_top_fit = static_cast<uint32_t>((64 * 1024 - std::min<size_t>(wide_fixed, 64 * 1024)) / node_bytes);
-        p.wide_top_nodes = std::min<uint32_t>({wide_top_want, p.n_wide, wide_top_fit});
-        l.lds = static_cast<size_t>(p.stack_lds_levels) * rv::kBlock * 2 * sizeof(uint32_t) + 2 * sizeof(float4) + static_cast<size_t>(p.wide_top_nodes) * node_bytes;
-    }
-#if RVPT_HIP_LAB
-    // the 8-wide form (rvpt_bvh8.hip): half the steps of the 4-wide walk again on scenes whose rays see few boxes per level
-    if (wide && !generic && ctx->bvh_wide8 == 1 && ctx->n_wide8 > 0) {
-        l.variant = 12u;
-        l.kernel = rv::trace_bvh8;
-        p.wide = ctx->d_wide8;
-        p.n_wide = static_cast<uint32_t>(ctx->n_wide8);
-        p.stack_levels = std::max<uint32_t>(1, ctx->wide8_stack_levels);
-        p.stack_lds_levels = std::min(p.stack_levels, lds_levels_want);
-        const uint32_t top8_want = ctx->tune.bvh_top_nodes >= 0 ? static_cast<uint32_t>(ctx->tune.bvh_top_nodes) : 32u;  // 8 KiB
-        const size_t fixed8 = static_cast<size_t>(p.stack_lds_levels + 1u) * rv::kBlock * 2 * sizeof(uint32_t) + 2 * sizeof(float4);
-        p.wide_top_nodes = std::min<uint32_t>({top8_want, p.n_wide, static_cast<uint32_t>((64 * 1024 - std::min<size_t>(fixed8, 64 * 1024)) / 256)});
-        l.lds = static_cast<size_t>(p.stack_lds_levels + 1u) * rv::kBlock * 2 * sizeof(uint32_t) + 2 * sizeof(float4) + static_cast<size_t>(p.wide_top_nodes) * 256;
-    }
-#endif
-    // ... and its LDS-resident instance, with camera packets over the wide nodes: every wide node, the prepared triangles, material indices and materials
-    // beside FOUR stack levels (the rest of a lane's stack in its global column: a work-group then takes 27 KB for the default scene and five fit a CU;
-    // with eight levels 22 700, with four 25 100 Msamples/s; with camera packets 26 100-26 350 against the binary camera-packet kernel's 23 100:
-    // tools/archive/ab_wide_resident.sh, profiles/r04_ab_wide_resident.txt)
-    const uint32_t wr_levels_want = ctx->tune.bvh_stack_lds > 0 ? static_cast<uint32_t>(ctx->tune.bvh_stack_lds) : 4u;
-    const size_t wide_resident_bytes = static_cast<size_t>(wr_levels_want) * rv::kBlock * 2 * sizeof(uint32_t) + 2 * sizeof(float4) + ctx->n_wide * rv::kWideTopQuads * 16 +
-                                       ctx->n_tris * 64 + index_bytes + ctx->n_mats * 48;
-    const bool wide_resident = bvh && bvh_resident && !ordered && l.regen && ctx->n_wide > 0 && ctx->bvh_wide == 1 && p.head_shift != 0 &&
-                               ctx->tune.bvh_wide_resident == 1 && wide_resident_bytes <= 64 * 1024;
-    if (wide_resident) {
-        l.variant = 11u;
-        l.kernel = generic ? rv::trace_bvh4_resident_generic : rv::trace_bvh4_resident;
-        p.wide = ctx->d_wide;
-        p.n_wide = static_cast<uint32_t>(ctx->n_wide);
-        p.wide_top_nodes = p.n_wide;
-        p.stack_levels = std::max<uint32_t>(1, ctx->wide_stack_levels);
-        p.stack_lds_levels = std::min(p.stack_levels, wr_levels_want);
-        l.lds = static_cast<size_t>(p.stack_lds_levels) * rv::kBlock * 2 * sizeof(uint32_t) + 2 * sizeof(float4) + ctx->n_wide * rv::kWideTopQuads * 16 + ctx->n_tris * 64 +
-                index_bytes + ctx->n_mats * 48;
-    }
-    // the packet form of the resident brute-force kernel (rvpt_packets.hip): full packets of one kind per round, camera rays with the
-    // packet-uniform early-out; the lean configuration only
-    // (one sample per pixel — the headline's configuration — has an instance of its own: 15-word queue entries, six work-groups per CU instead of five)
-    const uint32_t queue_words = (p.aa == 1) ? rv::kPacketQueueWordsAA1 : rv::kPacketQueueWords;
-    const size_t packets_bytes = ctx->n_tris * 64 + index_bytes + ctx->n_mats * 48 + (rv::kBlock / 64) * queue_words * 64 * sizeof(uint32_t);
-    const bool packets = !bvh && resident && ctx->n_tris > 0 && !generic && l.regen && p.max_bounces >= 1 && p.max_bounces <= 1023 &&
-                         p.aa <= 1023 && ctx->n_mats <= rv::kResidentMaxMats && ctx->brute_packets_policy == 1 && packets_bytes <= 64 * 1024;
-    if (packets) {
-        l.variant = 6u;
-        l.kernel = (p.aa == 1) ? rv::trace_brute_packets_aa1 : rv::trace_brute_packets;
-        l.lds = packets_bytes;
-        // + the screen rectangles (8 B per triangle, padded to 16) when they fit beside the rest
-        const size_t rect_bytes = ((ctx->n_tris + 1) & ~size_t(1)) * 8;
-        l.cull = ctx->packets_cull == 1 && l.lds + rect_bytes <= 64 * 1024;
-        if (l.cull) l.lds += rect_bytes;
-        // the bounce cull's premise: positions carry float errors of at most 2^-13 of the scene's scale — true while the camera (the origin of the first
-        // segment) is no further than 64 scene scales from the world origin (rvpt_packets.hip: bounce_visibility; DESIGN.md 5.1)
-        const float *o = ctx->camera.matrix + 12;
-        const double far = rv::kBounceCameraScales * ctx->scene_scale;
-        if (ctx->packets_bounce_cull == 1 && ctx->vis_words > 0 && std::fabs(o[0]) <= far && std::fabs(o[1]) <= far && std::fabs(o[2]) <= far) {
-            p.vis = ctx->d_vis;
-            p.vis_words = ctx->vis_words;
-            p.vis_stride = (ctx->vis_words + 3u) & ~3u;
-            if (ctx->packets_box_cull == 1 && ctx->d_leaf_boxes) p.leaf_boxes = ctx->d_leaf_boxes;
-        }
-    }
-    if (bvh && ctx->force_stack_levels > 0) {  // tests: a stack smaller than the tree needs — the kernels clamp and report (RVPT_HIP_DEBUG)
-        p.stack_levels = static_cast<uint32_t>(ctx->force_stack_levels);
-        p.stack_lds_levels = std::min(p.stack_lds_levels, p.stack_levels);
-    }
-    const uint32_t blocks_needed = (p.n_work + rv::kBlock - 1) / rv::kBlock;
-    l.grid = blocks_needed;  // one-pixel-per-lane kernel: one wave per 64 pixels
-    if (l.regen) {           // persistent work-groups
-        if (ctx->occ_kernel != reinterpret_cast<const void *>(l.kernel) || ctx->occ_lds != l.lds) {
-            int q = 0;
-            HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void *>(l.kernel), rv::kBlock, l.lds));
-            ctx->occ_kernel = reinterpret_cast<const void *>(l.kernel);
-            ctx->occ_lds = l.lds;
-            ctx->occ_per_cu = q;
-        }
-        int per_cu = std::max(1, std::min(ctx->occ_per_cu, 8));
-        // With frames overlapped in flight a frame kernel takes only 2 work-groups per CU: the kernels of consecutive
-        // frames then co-reside (2 + 2 waves per SIMD) and a frame's tail hides under the next frame's body (swept on
-        // MI355X: profiles/README.md).  The HBM-resident BVH kernels take 3-4 per CU: the register file holds 7 waves
-        // per SIMD in all, so the kernels of the frames in flight fill the CU between them either way, and larger
-        // per-group shares balance better (swept: profiles/r01_bvh_knob_sweeps.txt).
-        // (LDS-resident BVH with several frames per launch: 3 measured 6 % better than 2; one frame per launch: 2.)
-        // Brute force with several frames per launch (>= 4): a launch is long against its own ramp-up and drain, so it takes
-        // the register file's five work-groups per CU and consecutive launches overlap only at their ends (swept on MI355X,
-        // tools/archive/sweep_batch_bpc.sh: 8 frames per launch x 5 per CU = 6 080 / 6 500 Msamples/s over 20 / 200 frames against
-        // 5 670 / 6 410 for one frame per launch x 2 per CU x 3 launches in flight).
-        const bool batched = p.n_work >= 4 * p.n_work_frame;
-        const int small_per_cu = batched ? (bvh ? 3 : 8) : 2;  // (brute force, batched: what LDS and registers allow — five work-groups per CU, six for the aa == 1 instance)
-        if (ctx->overlap) per_cu = std::min(per_cu, (bvh && !bvh_resident) ? (ctx->tune.blocks_per_cu ? bvh_per_cu : (l.slots > 3 ? 2 : bvh_per_cu)) : small_per_cu);
-        // ... which assumes that launches overlap.  A LONE launch of the HBM-resident BVH kernel — nothing of this context in flight when it goes
-        // out: a rank's 20-step share sent as one launch, the first launch of a burst — has nobody to share the CU with and takes what the registers
-        // allow (six per CU): rank 2's share of an 8-way partition as one 20-frame launch, C4 geometry 0.132 -> 0.079 ms per frame, C3 0.675 -> 0.519
-        // (tools/archive/sweep_share_shapes.sh, profiles/r04_share_shapes.txt); launches that follow while it runs keep the overlapping shape
-        // Only launches of >= 16 frames: a caller that sends such a launch has batched what it had; the first of a stream of SMALLER launches must
-        // leave room for the next (measured: C3 at 8 frames per launch 3 240 -> 3 110 Msamples/s when the first launch took the whole CU).
-        if (ctx->overlap && bvh && !bvh_resident && !ctx->tune.blocks_per_cu && l.lone && p.n_work >= 16u * p.n_work_frame)
-            per_cu = std::max(1, std::min(ctx->occ_per_cu, 8));
-        if (ctx->tune.blocks_per_cu) per_cu = ctx->tune.blocks_per_cu;
-        l.grid = std::min<uint32_t>(blocks_needed, static_cast<uint32_t>(ctx->num_cus) * static_cast<uint32_t>(per_cu));
-    }
-    p.n_waves = l.grid * (rv::kBlock / 64);
-    return 0;
-}
+// every chunk of the work plan is whole 64-item blocks
+bool whole_blocks(const rv::FrameParams &p) { return p.first_units % 4u == 0u && p.claim_units % 4u == 0u && p.dyn_base % 4u == 0u && p.shard_len % 4u == 0u; }
 
 // work distribution of the launch (kernels: WavePool): a static first chunk per wave, then sharded claims
 // align_units > 1 (the packet kernel: 4 units = the 64 work items of a camera round): chunks start at multiples of it wherever the launch is large enough for
@@ -636,8 +497,8 @@ void plan_work(const rvpt_hip_ctx *ctx, bool regen, rv::FrameParams &p, uint32_t
         if (align_units == 4u) p.claim_units = 32u;
         // a static chunk of 5-7 units (images of 131-229 k pixels) would start most camera rounds off a block boundary and lose them the rectangles
         if (align_units > 1 && p.first_units > align_units) p.first_units = p.first_units / align_units * align_units;
-        if (ctx->tune.first_units) p.first_units = static_cast<uint32_t>(ctx->tune.first_units);
-        if (ctx->tune.claim_units) p.claim_units = static_cast<uint32_t>(ctx->tune.claim_units);
+        if (ctx->knobs.first_units) p.first_units = static_cast<uint32_t>(ctx->knobs.first_units);
+        if (ctx->knobs.claim_units) p.claim_units = static_cast<uint32_t>(ctx->knobs.claim_units);
     }
     p.dyn_base = static_cast<uint32_t>(std::min<uint64_t>(p.n_units, static_cast<uint64_t>(p.first_units) * p.n_waves));
     p.shard_len = (p.n_units - p.dyn_base + rv::kClaimShards - 1) / rv::kClaimShards;
@@ -690,15 +551,193 @@ void plan_interleave(const rvpt_hip_ctx *ctx, rv::FrameParams &p)
     p.perm_stride = 1;
     p.perm_shift = 0;
     p.div_perm_groups = rv::fast_div_make(1);
-    const uint32_t g = static_cast<uint32_t>(ctx->packets_interleave);
-    if (g == 0 || p.first_units % 4u || p.claim_units % 4u || p.dyn_base % 4u || p.shard_len % 4u) return;
-    if (!ctx->packets_interleave_all && p.n_work >= 4u * p.n_work_frame) return;
+    const uint32_t g = static_cast<uint32_t>(ctx->knobs.packets_interleave);
+    if (g == 0 || !whole_blocks(p)) return;
+    if (!ctx->knobs.packets_interleave_all && p.n_work >= 4u * p.n_work_frame) return;
     uint32_t groups, stride, shift;
     if (!plan_claim_order(p.n_work_frame, g, groups, stride, shift)) return;
     p.perm_groups = groups;
     p.perm_stride = stride;
     p.perm_shift = shift;
     p.div_perm_groups = rv::fast_div_make(groups);
+}
+
+// The whole decision for one launch: the kernel path, its LDS and FrameParams, the grid, the work plan and the culls.  `p` comes filled by
+// fill_frame_params, with p.n_work the launch's work items; `lone`: nothing of this context is in flight; `slots`: launches in flight (slots_for).
+int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, Launch &l)
+{
+    const rvpt_hip_ctx::Knobs &k = ctx->knobs;
+    const bool bvh = is_bvh(ctx, ctx->n_tris);  // no tree = empty scene
+    const bool ordered = bvh && (ctx->flags & RVPT_HIP_TRAVERSAL_MASK) == RVPT_HIP_TRAVERSAL_BVH_ORDERED;
+    const bool regen = (ctx->flags & RVPT_HIP_KERNEL_SIMPLE) == 0;  // persistent work-groups (KERNEL_SIMPLE: one pixel per lane, one wave per 64 pixels)
+    // the lean kernels cover the default configuration (Kajiya everywhere, pinhole); anything else runs the GENERIC ones
+    const bool generic = p.camera_mode != 0 || p.modes[0] != 9 || p.modes[1] != 9 || p.modes[2] != 9 || p.modes[3] != 9;
+    p.head_shift = k.bvh_no_packed_heads ? 0u : ctx->bvh_head_shift;
+
+    // 1. The path.
+    // brute force keeps the whole scene in LDS when it fits the 64 KiB a work-group gets without opting in to more
+    const size_t resident_bytes = ctx->n_tris * 64 + index_bytes(ctx) + (ctx->n_mats <= rv::kResidentMaxMats ? ctx->n_mats * 48 : 0) +
+                                  (rv::kBlock / 64) * 64 * sizeof(uint32_t);
+    const bool resident = ctx->n_tris <= rv::kResidentMaxTris && resident_bytes <= kLdsBudget;
+    // the packet form of the resident brute-force kernel (rvpt_packets.hip): full packets of one kind per round, camera rays with the
+    // packet-uniform early-out; the lean configuration only
+    // (one sample per pixel — the headline's configuration — has an instance of its own: 15-word queue entries, six work-groups per CU instead of five)
+    const size_t packets_bytes = ctx->n_tris * 64 + index_bytes(ctx) + ctx->n_mats * 48 +
+                                 (rv::kBlock / 64) * (p.aa == 1 ? rv::kPacketQueueWordsAA1 : rv::kPacketQueueWords) * 64 * sizeof(uint32_t);
+    const bool packets = resident && ctx->n_tris > 0 && !generic && regen && p.max_bounces >= 1 && p.max_bounces <= 1023 && p.aa <= 1023 &&
+                         ctx->n_mats <= rv::kResidentMaxMats && k.brute_packets && packets_bytes <= kLdsBudget;
+    const bool bvh_resident = bvh && bvh_scene_fits_lds(ctx);
+    // the 4-wide form of the tree (rvpt_bvh4.hip): lean configuration, reference order; half the dependent steps per ray
+    const bool wide = bvh && !ordered && regen && ctx->n_wide > 0 && k.bvh_wide && p.head_shift != 0;
+    // ... and its LDS-resident instance, with camera packets over the wide nodes: every wide node, the prepared triangles, material indices and materials
+    // beside FOUR stack levels (the rest of a lane's stack in its global column: a work-group then takes 27 KB for the default scene and five fit a CU;
+    // with eight levels 22 700, with four 25 100 Msamples/s; with camera packets 26 100-26 350 against the binary camera-packet kernel's 23 100:
+    // tools/archive/ab_wide_resident.sh, profiles/r04_ab_wide_resident.txt)
+    const uint32_t wr_levels_want = k.bvh_stack_lds > 0 ? static_cast<uint32_t>(k.bvh_stack_lds) : 4u;
+    auto wide_resident_bytes = [&](uint32_t levels) { return stack_lds_bytes(levels) + 2 * sizeof(float4) + ctx->n_wide * rv::kWideTopQuads * 16 + ctx->n_tris * 64 + index_bytes(ctx) + ctx->n_mats * 48; };
+    const bool quant = !generic && ctx->has_quant && k.bvh_quant;  // (the laboratory build's trees only)
+    // the 8-wide form (laboratory build; rvpt_bvh8.hip): half the steps of the 4-wide walk again on scenes whose rays see few boxes per level
+    const bool wide8 = wide && !bvh_resident && !generic && k.bvh_wide8 && ctx->n_wide8 > 0;
+    const Variant v = l.variant = !bvh ? (packets ? Variant::BrutePackets : resident ? Variant::BruteResident : Variant::BruteStream)
+                                : bvh_resident ? (wide && k.bvh_wide_resident && wide_resident_bytes(wr_levels_want) <= kLdsBudget ? Variant::WideResident : Variant::BvhResident)
+                                : !wide ? Variant::Bvh : wide8 ? Variant::Wide8 : quant ? Variant::WideQuant : Variant::Wide;
+    // 2. Its LDS and FrameParams.
+    // BVH: traversal stack sized from the tree.  HBM-resident scenes keep only the first stack levels in LDS (the rest overflows to global memory, rarely
+    // touched) so that the top of the tree fits beside them at full occupancy; LDS-resident scenes keep the whole stack
+    const uint32_t lds_levels_want = k.bvh_stack_lds > 0 ? static_cast<uint32_t>(k.bvh_stack_lds) : 8u;
+    p.stack_levels = bvh_stack_levels(ctx);
+    p.stack_lds_levels = bvh_resident ? p.stack_levels : std::min(p.stack_levels, lds_levels_want);
+    // short LDS-resident traversals: let the whole packet finish before refilling (64); long HBM traversals: refill once
+    // half of the packet waits, run the parked leaves in batches of 16 lanes, 3 work-groups per CU (swept on the Cornell and
+    // 1M-triangle scenes, both traversal orders, frames dispatched in batches: profiles/r01_bvh_knob_sweeps.txt)
+    p.bvh_refill = k.bvh_refill ? static_cast<uint32_t>(k.bvh_refill) : (bvh_resident ? 64u : 32u);
+    p.bvh_leaf_batch = k.bvh_leaf_batch ? static_cast<uint32_t>(k.bvh_leaf_batch) : 16u;
+    // top of the tree in LDS (HBM-resident scenes): 256 nodes = 8 KiB by default (with 8 two-word stack levels in LDS: 24 KiB per
+    // work-group, six per CU — what the registers allow anyway; swept: tools/archive/sweep_bvh_top.sh, profiles/r02_sweeps.txt), never more than the tree has (even count: sibling pairs)
+    const uint32_t top_want = k.bvh_top_nodes >= 0 ? static_cast<uint32_t>(k.bvh_top_nodes) : 256u;
+    p.bvh_top_nodes = (bvh && !bvh_resident) ? std::max(2u, std::min<uint32_t>(top_want, static_cast<uint32_t>(ctx->n_nodes)) & ~1u) : 0u;  // at least the root's line
+    // camera packets (trace_bvh4_resident: lanes that start camera rays together walk the tree as one wave-uniform packet in the reference's fixed child
+    // order): at least bvh_cam_min lanes must start a camera ray at once; the lanes of a node leave the packet when at most bvh_detach of them are in it
+    // (LDS-resident scenes: nobody leaves measured best; the binary-tree form of round 4, +5 % resident / +-0 HBM-resident, is profiles/r04_exp_campack_binary.patch)
+    p.bvh_cam_min = k.bvh_cam_min ? static_cast<uint32_t>(k.bvh_cam_min) : 24u;
+    p.bvh_detach = k.bvh_detach >= 0 ? static_cast<uint32_t>(k.bvh_detach) : 0u;
+    const int sel = (regen ? 0 : 1) | (generic ? 2 : 0);
+    bool cull = false;  // packet kernel: the screen rectangles of the triangles ride along
+    if (v == Variant::BruteResident || v == Variant::BruteStream) {
+        static const Kernel kernels[2][4] = {  // [streamed][sel]
+            {rv::trace_brute_resident<true, false>, rv::trace_brute_resident<false, false>, rv::trace_brute_resident<true, true>, rv::trace_brute_resident<false, true>},
+            {rv::trace_brute_stream<true, false>, rv::trace_brute_stream<false, false>, rv::trace_brute_stream<true, true>, rv::trace_brute_stream<false, true>}};
+        l.kernel = kernels[v == Variant::BruteStream ? 1 : 0][sel];
+        l.lds = v == Variant::BruteResident ? resident_bytes : static_cast<size_t>(rv::kBlock / 64) * (rv::kStreamDepth * rv::kWaveChunk * 64 + 64 * sizeof(uint32_t));
+    } else if (v == Variant::Bvh || v == Variant::BvhResident) {
+        static const Kernel kernels[2][2][4] = {  // [ordered][resident][sel]
+            {{rv::trace_bvh<true, false, false, false>, rv::trace_bvh<false, false, false, false>, rv::trace_bvh<true, false, true, false>, rv::trace_bvh<false, false, true, false>},
+             {rv::trace_bvh<true, true, false, false>, rv::trace_bvh<false, true, false, false>, rv::trace_bvh<true, true, true, false>, rv::trace_bvh<false, true, true, false>}},
+            {{rv::trace_bvh<true, false, false, true>, rv::trace_bvh<false, false, false, true>, rv::trace_bvh<true, false, true, true>, rv::trace_bvh<false, false, true, true>},
+             {rv::trace_bvh<true, true, false, true>, rv::trace_bvh<false, true, false, true>, rv::trace_bvh<true, true, true, true>, rv::trace_bvh<false, true, true, true>}}};
+        l.kernel = kernels[ordered ? 1 : 0][bvh_resident ? 1 : 0][sel];
+        l.lds = stack_lds_bytes(p.stack_lds_levels) + (bvh_resident ? bvh_scene_bytes(ctx) : static_cast<size_t>(p.bvh_top_nodes) * 32);
+    } else if (v == Variant::Wide || v == Variant::WideQuant || v == Variant::Wide8) {
+#if RVPT_HIP_LAB
+        l.kernel = wide8 ? rv::trace_bvh8 : quant ? rv::trace_bvh4q : generic ? rv::trace_bvh4_generic : rv::trace_bvh4;
+#else
+        l.kernel = generic ? rv::trace_bvh4_generic : rv::trace_bvh4;
+#endif
+        p.leaf_box = quant ? ctx->d_leaf_box : nullptr;
+        p.slab_extent = ctx->slab_extent;
+        p.wide = wide8 ? ctx->d_wide8 : quant ? ctx->d_wideq : ctx->d_wide;
+        p.n_wide = static_cast<uint32_t>(wide8 ? ctx->n_wide8 : ctx->n_wide);
+        p.stack_levels = std::max<uint32_t>(1, wide8 ? ctx->wide8_stack_levels : ctx->wide_stack_levels);
+        p.stack_lds_levels = std::min(p.stack_levels, lds_levels_want);
+        // one node in the LDS copy of the tree top, and how many by default: 8 KiB, as the binary kernel's 256 nodes (the 8-wide walk keeps one stack level more)
+        const uint32_t node_bytes = wide8 ? 256u : quant ? 64u : rv::kWideTopQuads * 16u;
+        const uint32_t wide_top_want = k.bvh_top_nodes >= 0 ? static_cast<uint32_t>(k.bvh_top_nodes) : (wide8 ? 32u : quant ? 128u : 64u);
+        // (the knob counts NODES, and a wide node is four binary ones: whatever it asks for, the stack levels + the root record + the top nodes stay within
+        // the 64 KiB a work-group can have — ADVICE r4: RVPT_HIP_BVH_TOP_NODES=2048 used to ask for 256 KiB and fail at launch)
+        const size_t fixed = stack_lds_bytes(p.stack_lds_levels + (wide8 ? 1u : 0u)) + 2 * sizeof(float4);
+        const uint32_t wide_top_fit = static_cast<uint32_t>((kLdsBudget - std::min(fixed, kLdsBudget)) / node_bytes);
+        p.wide_top_nodes = std::min<uint32_t>({wide_top_want, p.n_wide, wide_top_fit});
+        l.lds = fixed + static_cast<size_t>(p.wide_top_nodes) * node_bytes;
+    } else if (v == Variant::WideResident) {
+        l.kernel = generic ? rv::trace_bvh4_resident_generic : rv::trace_bvh4_resident;
+        p.wide = ctx->d_wide;
+        p.n_wide = static_cast<uint32_t>(ctx->n_wide);
+        p.wide_top_nodes = p.n_wide;
+        p.stack_levels = std::max<uint32_t>(1, ctx->wide_stack_levels);
+        p.stack_lds_levels = std::min(p.stack_levels, wr_levels_want);
+        l.lds = wide_resident_bytes(p.stack_lds_levels);
+    } else {  // Variant::BrutePackets
+        l.kernel = (p.aa == 1) ? rv::trace_brute_packets_aa1 : rv::trace_brute_packets;
+        // + the screen rectangles (8 B per triangle, padded to 16) when they fit beside the rest
+        const size_t rect_bytes = ((ctx->n_tris + 1) & ~size_t(1)) * 8;
+        cull = k.packets_cull && packets_bytes + rect_bytes <= kLdsBudget;
+        l.lds = packets_bytes + (cull ? rect_bytes : 0);
+        // the bounce cull's premise: positions carry float errors of at most 2^-13 of the scene's scale — true while the camera (the origin of the first
+        // segment) is no further than 64 scene scales from the world origin (rvpt_packets.hip: bounce_visibility; DESIGN.md 5.1)
+        const float *o = ctx->camera.matrix + 12;
+        const double far = rv::kBounceCameraScales * ctx->scene_scale;
+        if (k.packets_bounce_cull && ctx->vis_words > 0 && std::fabs(o[0]) <= far && std::fabs(o[1]) <= far && std::fabs(o[2]) <= far) {
+            p.vis = ctx->d_vis;
+            p.vis_words = ctx->vis_words;
+            p.vis_stride = (ctx->vis_words + 3u) & ~3u;
+            if (k.packets_box_cull && ctx->d_leaf_boxes) p.leaf_boxes = ctx->d_leaf_boxes;
+        }
+    }
+    if (bvh && k.force_stack_levels > 0) {  // tests: a stack smaller than the tree needs — the kernels clamp and report (RVPT_HIP_DEBUG)
+        p.stack_levels = static_cast<uint32_t>(k.force_stack_levels);
+        p.stack_lds_levels = std::min(p.stack_lds_levels, p.stack_levels);
+    }
+    // 3. The grid, from the occupancy of the general instance of the path.
+    const uint32_t blocks_needed = (p.n_work + rv::kBlock - 1) / rv::kBlock;
+    l.grid = blocks_needed;  // one-pixel-per-lane kernel: one wave per 64 pixels
+    if (regen) {             // persistent work-groups
+        if (ctx->occ_kernel != reinterpret_cast<const void *>(l.kernel) || ctx->occ_lds != l.lds) {
+            int q = 0;
+            HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void *>(l.kernel), rv::kBlock, l.lds));
+            ctx->occ_kernel = reinterpret_cast<const void *>(l.kernel);
+            ctx->occ_lds = l.lds;
+            ctx->occ_per_cu = q;
+        }
+        const int occ = std::max(1, std::min(ctx->occ_per_cu, 8));
+        // With frames overlapped in flight a frame kernel takes only 2 work-groups per CU: the kernels of consecutive
+        // frames then co-reside (2 + 2 waves per SIMD) and a frame's tail hides under the next frame's body (swept on
+        // MI355X: profiles/README.md).  The HBM-resident BVH kernels take 3-4 per CU: the register file holds 7 waves
+        // per SIMD in all, so the kernels of the frames in flight fill the CU between them either way, and larger
+        // per-group shares balance better (swept: profiles/r01_bvh_knob_sweeps.txt).
+        // (LDS-resident BVH with several frames per launch: 3 measured 6 % better than 2; one frame per launch: 2.)
+        // Brute force with several frames per launch (>= 4): a launch is long against its own ramp-up and drain, so it takes
+        // the register file's five work-groups per CU and consecutive launches overlap only at their ends (swept on MI355X,
+        // tools/archive/sweep_batch_bpc.sh: 8 frames per launch x 5 per CU = 6 080 / 6 500 Msamples/s over 20 / 200 frames against
+        // 5 670 / 6 410 for one frame per launch x 2 per CU x 3 launches in flight).
+        const bool batched = p.n_work >= 4 * p.n_work_frame;
+        const bool hbm_bvh = bvh && !bvh_resident;
+        const int small_per_cu = batched ? (bvh ? 3 : 8) : 2;  // (brute force, batched: what LDS and registers allow — five work-groups per CU, six for the aa == 1 instance)
+        int per_cu = ctx->overlap ? std::min(occ, hbm_bvh ? (slots > 3 ? 2 : 3) : small_per_cu) : occ;
+        // ... which assumes that launches overlap.  A LONE launch of the HBM-resident BVH kernel — nothing of this context in flight when it goes
+        // out: a rank's 20-step share sent as one launch, the first launch of a burst — has nobody to share the CU with and takes what the registers
+        // allow (six per CU): rank 2's share of an 8-way partition as one 20-frame launch, C4 geometry 0.132 -> 0.079 ms per frame, C3 0.675 -> 0.519
+        // (tools/archive/sweep_share_shapes.sh, profiles/r04_share_shapes.txt); launches that follow while it runs keep the overlapping shape
+        // Only launches of >= 16 frames: a caller that sends such a launch has batched what it had; the first of a stream of SMALLER launches must
+        // leave room for the next (measured: C3 at 8 frames per launch 3 240 -> 3 110 Msamples/s when the first launch took the whole CU).
+        if (ctx->overlap && hbm_bvh && lone && p.n_work >= 16u * p.n_work_frame) per_cu = occ;
+        if (k.blocks_per_cu) per_cu = k.blocks_per_cu;  // (RVPT_HIP_BLOCKS_PER_CU: instead of all of the above)
+        l.grid = std::min<uint32_t>(blocks_needed, static_cast<uint32_t>(ctx->num_cus) * static_cast<uint32_t>(per_cu));
+    }
+    p.n_waves = l.grid * (rv::kBlock / 64);
+    // 4. The work plan (the packet kernel: camera rounds of whole 16 x 4 blocks) and the packet kernel's claim order.
+    plan_work(ctx, regen, p, v == Variant::BrutePackets ? 4u : 1u);
+    if (v == Variant::BrutePackets) plan_interleave(ctx, p);
+    // 5. The lean packet instances, for launches with all three culls on and every chunk of the plan whole blocks (the default for a scene with a table): no
+    // uncull'd walks — fewer registers to keep alive (SGPR spills 54 -> 19 for one sample per pixel; every spill is a v_readlane / v_writelane the VALU issues) —
+    // with or without the interleaved claim order of short launches (its scalars cost the batched launches' kernel eleven spills more).  LAST, because it depends
+    // on the work plan (whole_blocks), which depends on the grid (p.n_waves); the grid is the general instance's, which needs no fewer resources (tests/test_abi_exports.py).
+    const bool lean = v == Variant::BrutePackets && cull && p.vis && p.leaf_boxes && p.sample_out && whole_blocks(p) && k.packets_lean_instance;
+    if (lean)
+        l.kernel = p.perm_groups != 0u ? ((p.aa == 1) ? rv::trace_brute_packets_aa1_culls_order : rv::trace_brute_packets_culls_order)
+                                       : ((p.aa == 1) ? rv::trace_brute_packets_aa1_culls : rv::trace_brute_packets_culls);
+    l.cull_bits = (cull ? kCullRects : 0u) | (p.vis ? kCullBounce : 0u) | ((v == Variant::BrutePackets && p.first_units % 4u == 0u) ? kCullBlockRounds : 0u) |
+                  (p.leaf_boxes ? kCullLeafBoxes : 0u) | (p.perm_groups != 0u ? kCullClaimOrder : 0u) | (lean ? kCullLeanInstance : 0u);
+    return 0;
 }
 
 }  // namespace
@@ -804,44 +843,13 @@ int rvpt_hip_create(rvpt_hip_ctx **out, int device_id, uint32_t width, uint32_t 
             }
         }
     }
-    if (const char *tl = lab_env("RVPT_HIP_TIMELINE")) ctx->timeline_path = tl;
-    ctx->bvh_wide = (flags & RVPT_HIP_BVH_PER_LANE) ? 0 : 1;
-    if (const char *e = lab_env("RVPT_HIP_BVH_WIDE")) ctx->bvh_wide = atoi(e) > 0 ? 1 : 0;  // experiments: A/B a whole run
-    if (const char *e = lab_env("RVPT_HIP_BVH_WIDE8")) ctx->bvh_wide8 = atoi(e) > 0 ? 1 : 0;
-    if (const char *e = lab_env("RVPT_HIP_BVH_QUANT")) ctx->bvh_quant = atoi(e) > 0 ? 1 : 0;
-    ctx->brute_packets_policy = (flags & RVPT_HIP_BRUTE_MIXED_PACKETS) ? 0 : 1;
-    if (const char *e = lab_env("RVPT_HIP_BRUTE_PACKETS")) ctx->brute_packets_policy = atoi(e) > 0 ? 1 : 0;
+    ctx->knobs = read_knobs(flags);
     if (const char *e = getenv("RVPT_HIP_DEBUG")) ctx->debug_checks = atoi(e) > 0 ? 1 : 0;
     if (ctx->debug_checks && !RV_REPORT_STACK_OVERFLOW) {  // never a silent no-op: the release kernels only clamp, nothing would ever set the word
         fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "RVPT_HIP_DEBUG=1 needs the kernels' internal checks, which this build of the library does not carry "
                                             "(rvpt_hip_build_flags() bit 1): load librvpt_hip_debug.so");
         return bail(RVPT_HIP_ERR_UNSUPPORTED);
     }
-    if (const char *e = lab_env("RVPT_HIP_BVH_FORCE_STACK_LEVELS")) ctx->force_stack_levels = std::max(0, atoi(e));
-    if (const char *e = getenv("RVPT_HIP_PACKETS_CULL")) ctx->packets_cull = atoi(e) > 0 ? 1 : 0;
-    if (const char *e = getenv("RVPT_HIP_PACKETS_BOUNCE_CULL")) ctx->packets_bounce_cull = atoi(e) > 0 ? 1 : 0;
-    if (const char *e = getenv("RVPT_HIP_PACKETS_BOX_CULL")) ctx->packets_box_cull = atoi(e) > 0 ? 1 : 0;
-    if (const char *e = lab_env("RVPT_HIP_PACKETS_LEAN_INSTANCE")) ctx->packets_lean_instance = atoi(e) > 0 ? 1 : 0;
-    if (const char *e = getenv("RVPT_HIP_PACKETS_INTERLEAVE")) {
-        const int g = atoi(e);
-        ctx->packets_interleave_all = g < 0 ? 1 : 0;
-        ctx->packets_interleave = (std::abs(g) == 1 || std::abs(g) == 2 || std::abs(g) == 4 || std::abs(g) == 8) ? std::abs(g) : 0;
-    }
-    auto env_int = [](const char *name, int lo, int hi) {
-        const char *e = lab_env(name);
-        return e ? std::max(lo, std::min(hi, atoi(e))) : 0;
-    };
-    ctx->tune.blocks_per_cu = env_int("RVPT_HIP_BLOCKS_PER_CU", 1, 8);
-    ctx->tune.first_units = env_int("RVPT_HIP_FIRST_UNITS", 1, 1 << 20);
-    ctx->tune.claim_units = env_int("RVPT_HIP_CLAIM_UNITS", 1, 1 << 20);
-    ctx->tune.bvh_refill = env_int("RVPT_HIP_BVH_REFILL", 1, 64);
-    ctx->tune.bvh_leaf_batch = env_int("RVPT_HIP_BVH_LEAF_BATCH", 1, 64);
-    ctx->tune.bvh_stack_lds = env_int("RVPT_HIP_BVH_STACK_LDS", 1, 64);
-    if (const char *e = lab_env("RVPT_HIP_BVH_WIDE_RESIDENT")) ctx->tune.bvh_wide_resident = atoi(e) > 0 ? 1 : 0;
-    ctx->tune.bvh_no_resident = env_int("RVPT_HIP_BVH_NO_RESIDENT", 0, 1);
-    ctx->tune.bvh_cam_min = env_int("RVPT_HIP_BVH_CAM_MIN", 1, 65);  // 65 = never
-    if (const char *e = lab_env("RVPT_HIP_BVH_DETACH")) ctx->tune.bvh_detach = std::max(0, std::min(64, atoi(e)));
-    if (const char *e = lab_env("RVPT_HIP_BVH_TOP_NODES")) ctx->tune.bvh_top_nodes = std::max(0, std::min(2048, atoi(e)));  // 0 = no LDS copy
     CREATE_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_stats), rv::kStatStripes * rv::kStatStride * sizeof(unsigned long long)));
     CREATE_TRY(hipMemsetAsync(ctx->d_stats, 0, rv::kStatStripes * rv::kStatStride * sizeof(unsigned long long), ctx->stream));
     CREATE_TRY(hipStreamSynchronize(ctx->stream));
@@ -873,10 +881,10 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     for (int i = 0; i < rvpt_hip_ctx::kMaxSlots; ++i)
         if (ctx->trace_stream[i]) (void)hipStreamSynchronize(ctx->trace_stream[i]);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->d_timeline && !ctx->timeline_path.empty()) {  // debugging aid: dump the last frame's wave timeline
+    if (ctx->d_timeline && !ctx->knobs.timeline_path.empty()) {  // debugging aid: dump the last frame's wave timeline
         std::vector<unsigned long long> h(ctx->timeline_words);
         if (hipMemcpy(h.data(), ctx->d_timeline, ctx->timeline_words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (FILE *f = fopen(ctx->timeline_path.c_str(), "wb")) {
+            if (FILE *f = fopen(ctx->knobs.timeline_path.c_str(), "wb")) {
                 fwrite(h.data(), 8, h.size(), f);
                 fclose(f);
             }
@@ -916,7 +924,7 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     if (n_tris > 0x3FFFFFFFull) return fail(ctx, RVPT_HIP_ERR_INVALID, "too many triangles");
     // an EMPTY scene has no tree (RVPT::initialize with no triangles): every ray misses whatever the traversal, and the
     // frame kernels of a BVH context then run the brute-force instance over zero triangles (choose_launch)
-    const bool bvh = (ctx->flags & RVPT_HIP_TRAVERSAL_MASK) != RVPT_HIP_TRAVERSAL_BRUTE && n_tris > 0;
+    const bool bvh = is_bvh(ctx, n_tris);
     uint32_t bvh_height_tmp = 0;
     // materials[int(mat_id.x)] (intersection.glsl:398) must stay inside the buffer
     for (size_t i = 0; i < n_tris; ++i) {
@@ -974,7 +982,7 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     if (bvh) {
         // Device layout of the tree (traversal order and results are unchanged): breadth-first, root at 0, slot 1
         // unused, every sibling pair on an even index = one 64-byte line, upper levels first.
-        if (lab_env("RVPT_HIP_BVH_CALLER_LAYOUT")) {
+        if (ctx->knobs.bvh_caller_layout) {
             device_nodes.assign(nodes, nodes + n_nodes);
             if (device_nodes.size() < 2) device_nodes.resize(2);  // the kernels copy at least the root's 64-byte line into LDS
         } else {
@@ -1020,7 +1028,7 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     }
     ctx->n_wide = 0;
     ctx->wide_stack_levels = 0;
-    if (bvh && !lab_env("RVPT_HIP_BVH_CALLER_LAYOUT")) {  // the 4-wide form of the tree (breadth-first device layout: children of node i at first, first + 1)
+    if (bvh && !ctx->knobs.bvh_caller_layout) {  // the 4-wide form of the tree (breadth-first device layout: children of node i at first, first + 1)
         uint32_t need = 0;
         const std::vector<float> wide = rv::build_wide_nodes(device_nodes.data(), device_nodes.size(), ctx->bvh_head_shift, need);
         if (!wide.empty() && need <= 4096u && wide.size() / 32 < rv::kWideMaxNodes) {
@@ -1032,7 +1040,7 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
         }
         ctx->has_quant = false;
 #if RVPT_HIP_LAB
-        if (ctx->n_wide > 0 && ctx->bvh_quant == 1) {
+        if (ctx->n_wide > 0 && ctx->knobs.bvh_quant) {
             float extent = 0.0f, box_extent = 0.0f;
             const std::vector<uint32_t> quant = rv::build_quant_nodes(wide, extent);
             const std::vector<float> boxes = quant.empty() ? std::vector<float>() : rv::build_leaf_boxes(device_nodes.data(), device_nodes.size(), n_tris, box_extent);
@@ -1046,7 +1054,7 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
             }
         }
         ctx->n_wide8 = 0;
-        if (ctx->bvh_wide8 == 1) {
+        if (ctx->knobs.bvh_wide8) {
             uint32_t need8 = 0;
             const std::vector<float> wide8 = rv::build_wide8_nodes(device_nodes.data(), device_nodes.size(), ctx->bvh_head_shift, need8);
             if (!wide8.empty() && need8 <= 4096u && wide8.size() / 64 < (rv::kWideMaxNodes >> 1)) {
@@ -1137,22 +1145,18 @@ static int dispatch_launch(rvpt_hip_ctx *ctx, uint32_t n_frames)
     rv::FrameParams p{};
     fill_frame_params(ctx, slot, p, buf);
     p.n_work = n_frames * ctx->n_work;
-    Launch launch{};
-    launch.slots = slots;
     // is anything of this context still running?  (a finished or never used stream answers hipSuccess)  Only the HBM-resident BVH launches of >= 16 frames act on the
-    // answer (choose_launch); a one-frame brute-force launch does not pay six stream queries for it
-    const bool lone_matters = (ctx->flags & RVPT_HIP_TRAVERSAL_MASK) != RVPT_HIP_TRAVERSAL_BRUTE && ctx->n_nodes > 0 && n_frames >= 16u;
-    if (ctx->overlap && lone_matters) {
-        launch.lone = true;
-        for (int i = 0; i < ctx->n_slots && launch.lone; ++i)
-            if (ctx->slot_used[i] && hipStreamQuery(ctx->trace_stream[i]) != hipSuccess) launch.lone = false;
+    // answer (choose_launch); a one-frame brute-force launch does not pay six stream queries for it.  (After the growth above: its drain makes the answer "idle".)
+    bool lone = false;
+    if (ctx->overlap && is_bvh(ctx, ctx->n_tris) && n_frames >= 16u) {
+        lone = true;
+        for (int i = 0; i < ctx->n_slots && lone; ++i)
+            if (ctx->slot_used[i] && hipStreamQuery(ctx->trace_stream[i]) != hipSuccess) lone = false;
         (void)hipGetLastError();  // hipErrorNotReady is an answer, not an error
     }
-    if (int rc = choose_launch(ctx, p, launch)) return rc;
-    plan_work(ctx, launch.regen, p, launch.variant == 6u ? 4u : 1u);
-    if (launch.variant == 6u) plan_interleave(ctx, p);
-    bool lean = false;  // packet kernel: the instances for launches with all three culls (below)
-    if (launch.variant == 6u) {  // the camera records and the rectangles for this camera: made on the slot's stream, in front of the frame kernel, when the slot's buffers hold another camera's
+    Launch launch{};
+    if (int rc = choose_launch(ctx, p, lone, slots, launch)) return rc;
+    if (launch.variant == Variant::BrutePackets) {  // the camera records and the rectangles for this camera: made on the slot's stream, in front of the frame kernel, when the slot's buffers hold another camera's
         if (ctx->n_tris > ctx->rects_cap[slot]) {
             HIP_TRY(ctx, hipStreamSynchronize(tstream));
             if (ctx->d_rects[slot]) HIP_TRY(ctx, hipFree(ctx->d_rects[slot]));
@@ -1175,17 +1179,10 @@ static int dispatch_launch(rvpt_hip_ctx *ctx, uint32_t n_frames)
             ctx->rects_key[slot] = key;
             ctx->rects_valid[slot] = true;
         }
-        if (launch.cull) p.rects = ctx->d_rects[slot];
+        if (launch.cull_bits & kCullRects) p.rects = ctx->d_rects[slot];
         p.cam_records = ctx->d_cam_records[slot];
-        // all three culls on and every chunk of the plan whole blocks (the default for a scene with a table): the instances without the uncull'd walks — fewer
-        // registers to keep alive (SGPR spills 54 -> 19 for one sample per pixel; every spill is a v_readlane / v_writelane the VALU issues), same LDS, same occupancy
-        const bool whole_blocks = p.first_units % 4u == 0u && p.claim_units % 4u == 0u && p.dyn_base % 4u == 0u && p.shard_len % 4u == 0u;
-        lean = p.rects != nullptr && p.vis != nullptr && p.leaf_boxes != nullptr && p.sample_out != nullptr && whole_blocks && ctx->packets_lean_instance;
-        if (lean)  // ... and with or without the interleaved claim order of short launches (its scalars cost the batched launches' kernel eleven spills more)
-            launch.kernel = p.perm_groups != 0u ? ((p.aa == 1) ? rv::trace_brute_packets_aa1_culls_order : rv::trace_brute_packets_culls_order)
-                                                : ((p.aa == 1) ? rv::trace_brute_packets_aa1_culls : rv::trace_brute_packets_culls);
     }
-    if ((launch.variant == 2 || launch.variant == 10 || launch.variant == 11 || launch.variant == 12 || launch.variant == 13) && p.stack_levels > p.stack_lds_levels) {  // global part of the traversal stack, one column per thread and level
+    if (has_global_stack(launch.variant) && p.stack_levels > p.stack_lds_levels) {  // global part of the traversal stack, one column per thread and level
         const size_t words = static_cast<size_t>(2) * (p.stack_levels - p.stack_lds_levels) * launch.grid * rv::kBlock;
         if (words > ctx->stack_overflow_cap[slot]) {
             HIP_TRY(ctx, hipStreamSynchronize(tstream));
@@ -1197,7 +1194,7 @@ static int dispatch_launch(rvpt_hip_ctx *ctx, uint32_t n_frames)
         }
         p.stack_overflow = ctx->d_stack_overflow[slot];
     }
-    if (!ctx->timeline_path.empty()) {
+    if (!ctx->knobs.timeline_path.empty()) {
         const size_t words = static_cast<size_t>(p.n_waves) * 16;  // 8 per wave + 8 more for the instrumented BVH build's load counts
         if (words > ctx->timeline_words) {
             if (ctx->d_timeline) HIP_TRY(ctx, hipFree(ctx->d_timeline));
@@ -1209,8 +1206,8 @@ static int dispatch_launch(rvpt_hip_ctx *ctx, uint32_t n_frames)
     }
     ctx->last_grid = launch.grid;
     ctx->last_lds = static_cast<uint32_t>(launch.lds);
-    ctx->last_variant = launch.variant;
-    ctx->last_cull = (p.rects != nullptr ? 1u : 0u) | (p.vis != nullptr ? 2u : 0u) | ((launch.variant == 6u && p.first_units % 4u == 0u) ? 4u : 0u) | (p.leaf_boxes != nullptr ? 16u : 0u) | (p.perm_groups != 0u ? 32u : 0u) | (lean ? 64u : 0u);
+    ctx->last_variant = static_cast<uint32_t>(launch.variant);
+    ctx->last_cull = launch.cull_bits;
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (ctx->timing) {

@@ -78,6 +78,21 @@ def test_the_release_library_reads_no_laboratory_knob():
     assert set(found) - macros <= allowed, sorted(set(found) - macros - allowed)
 
 
+def test_the_lean_packet_instances_need_no_more_than_the_general_ones():
+    """rvpt_abi.hip: choose_launch sizes a packet launch's grid from the occupancy of the general instance (trace_brute_packets[_aa1]) and then may launch a
+    lean one (*_culls, *_culls_order) on that grid: it fits only while the lean instance needs no more registers, scratch or static LDS."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_resources", ROOT / "tools" / "kernel_resources.py")
+    kr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kr)
+    res = kr.kernel_resources(["rvpt_packets.hip"])
+    for aa in ("", "_aa1"):
+        general = res[f"trace_brute_packets{aa}"]
+        for lean in (f"trace_brute_packets{aa}_culls", f"trace_brute_packets{aa}_culls_order"):
+            for key in ("vgpr", "sgpr", "scratch_bytes", "static_lds_bytes"):
+                assert res[lean][key] <= general[key], (lean, key, res[lean][key], general[key])
+
+
 def test_abi_version(lib):
     assert lib.rvpt_hip_abi_version() == 8
 

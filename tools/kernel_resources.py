@@ -21,14 +21,21 @@ sys.path.insert(0, str(ROOT))
 from rvpt_amd import build  # noqa: E402
 
 
-def main():
-    rnd = sys.argv[1] if len(sys.argv) > 1 else "r03"
-    flags = [f for f in build.FLAGS if f not in ("-fPIC", "-shared")]
+KERNEL_FILES = ("rvpt_kernels.hip", "rvpt_packets.hip", "rvpt_bvh4.hip", "rvpt_bvh8.hip")
+
+
+def device_flags():
+    return [f for f in build.FLAGS if f not in ("-fPIC", "-shared")]
+
+
+def kernel_resources(sources=KERNEL_FILES):
+    """{kernel: {vgpr, sgpr, scratch_bytes, static_lds_bytes, waves_per_simd_by_vgpr}} of every kernel the files `sources` (under rvpt_amd/csrc/) define,
+    compiled device-only with the library's flags."""
     text = ""
     with tempfile.TemporaryDirectory() as d:
-        for src in ("rvpt_kernels.hip", "rvpt_packets.hip", "rvpt_bvh4.hip", "rvpt_bvh8.hip"):
+        for src in sources:
             out = Path(d) / "k.s"
-            subprocess.run([build.hipcc(), *flags, "-S", "--cuda-device-only", str(ROOT / "rvpt_amd" / "csrc" / src), "-o", str(out)],
+            subprocess.run([build.hipcc(), *device_flags(), "-S", "--cuda-device-only", str(ROOT / "rvpt_amd" / "csrc" / src), "-o", str(out)],
                            check=True, capture_output=True)
             text += out.read_text()
     demangle = lambda n: subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip() or n
@@ -40,8 +47,14 @@ def main():
         res[demangle(m.group(1)).replace("(rv::FrameParams)", "").replace("rv::", "").replace("void ", "")] = {
             "vgpr": vg, "sgpr": g("next_free_sgpr"), "scratch_bytes": g("private_segment_fixed_size"), "static_lds_bytes": g("group_segment_fixed_size"),
             "waves_per_simd_by_vgpr": min(8, 512 // (((vg + 7) // 8) * 8))}
+    return res
+
+
+def main():
+    rnd = sys.argv[1] if len(sys.argv) > 1 else "r03"
+    res = kernel_resources()
     dst = ROOT / "profiles" / f"{rnd}_kernel_resources.json"
-    dst.write_text(json.dumps({"flags": flags, "kernels": res}, indent=1) + "\n")
+    dst.write_text(json.dumps({"flags": device_flags(), "kernels": res}, indent=1) + "\n")
     for k, v in res.items():
         print(f"{k[:72]:72s} {v}")
 

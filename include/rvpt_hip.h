@@ -40,7 +40,7 @@ extern "C" {
                                      unknown flag bits are an error;
                                   6: + rvpt_camera_rects, rvpt_hip_selftest_camera_rects (the screen rectangles of the packet kernel's camera rounds), rvpt_hip_selftest_bounce_cull;
                                   7: + rvpt_bvh_quant_form (the 64-byte quantised wide nodes, RVPT_HIP_BVH_QUANT=1);
-                                  8: the release library exports the 31 entry points of THIS header only — what a caller of `class RVPT` needs; the
+                                  8: the release library exports the 30 entry points of THIS header only — what a caller of `class RVPT` needs; the
                                      selftests, the host-side forms of the device data (rvpt_camera_rects, rvpt_bounce_rows, rvpt_bvh_wide_form,
                                      rvpt_bvh_quant_form), the opt-in walks that measured slower (8-wide, quantised) and the tuning knobs live in the
                                      laboratory build librvpt_hip_debug.so (include/rvpt_hip_lab.h); + rvpt_hip_build_flags, rvpt_hip_get_cull_info,
@@ -269,8 +269,7 @@ int rvpt_hip_get_stats(rvpt_hip_ctx *ctx, uint64_t stats[2]);
 /* Launch shape of the last dispatched frame kernel: work-groups, dynamic LDS bytes per work-group,
  * kernel variant (0 brute/LDS-resident with mixed packets, 1 brute/LDS-streamed, 2 bvh: binary per-lane walk, 3 the same with the scene in LDS,
  * 6 brute/LDS-resident packet kernel, 10 bvh over the 4-wide regrouping of the tree, 11 the same with the scene in LDS (and camera packets in the lean
- * configuration), 12 / 13 the opt-in 8-wide walk / 4-wide walk over 64-byte quantised nodes (RVPT_HIP_BVH_WIDE8=1 / RVPT_HIP_BVH_QUANT=1: bit-exact, measured
- * slower); 6, 10 and 11 are the defaults; 4, 5, 7, 8 and 9 were experiments of rounds 3-4 and are retired), and how many frames the context
+ * configuration); 6, 10 and 11 are the defaults; 4, 5, 7, 8 and 9 were experiments of rounds 3-4, 12 and 13 of round 5, all retired), and how many frames the context
  * keeps in flight (the reference: MAX_FRAMES_IN_FLIGHT = 2, rvpt.h:25).  Any out pointer may be NULL. */
 int rvpt_hip_get_launch_info(rvpt_hip_ctx *ctx, uint32_t *grid_blocks, uint32_t *lds_bytes,
                              uint32_t *kernel_variant, uint32_t *frames_in_flight);

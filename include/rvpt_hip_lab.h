@@ -3,9 +3,7 @@
  * -DRV_REPORT_STACK_OVERFLOW=1, rvpt_amd/build.py) exports beside the C ABI of rvpt_hip.h.  None of it has a counterpart in the reference; a caller of
  * `class RVPT` needs none of it; the parity tests, tools/fuzz_culls.py and the experiments do:
  *   - diagnostics of the arithmetic specification and of the packet kernel's exact culls (rvpt_hip_selftest_*),
- *   - the host-side forms of data the kernels consume, GPU-free (rvpt_camera_rects, rvpt_bounce_rows, rvpt_claim_order, rvpt_bvh_wide_form, rvpt_bvh_quant_form),
- *   - the kernels that were built, are bit-exact and measured SLOWER (profiles/EXPERIMENTS.md): the 8-wide walk (RVPT_HIP_BVH_WIDE8=1) and the walk over
- *     64-byte quantised nodes (RVPT_HIP_BVH_QUANT=1),
+ *   - the host-side forms of data the kernels consume, GPU-free (rvpt_camera_rects, rvpt_bounce_rows, rvpt_claim_order, rvpt_bvh_wide_form),
  *   - the tuning knobs the sweeps of rounds 1-5 found flat (RVPT_HIP_BVH_WIDE, _WIDE_RESIDENT, _NO_RESIDENT, _NO_PACKED_HEADS, _CALLER_LAYOUT, _TOP_NODES,
  *     _STACK_LDS, _REFILL, _LEAF_BATCH, _CAM_MIN, _DETACH, _FORCE_STACK_LEVELS, RVPT_HIP_BRUTE_PACKETS, RVPT_HIP_PACKETS_LEAN_INSTANCE, _BLOCKS_PER_CU, _FIRST_UNITS, _CLAIM_UNITS,
  *     RVPT_HIP_TIMELINE): the release library reads none of them,
@@ -89,17 +87,6 @@ int rvpt_claim_order(uint32_t n_work_frame, uint32_t group_blocks, uint32_t *ord
  * the most slots a depth-first walk of the wide tree holds at once.  RVPT_HIP_ERR_SIZE if wide_capacity (in nodes) is too small.  No GPU needed. */
 int rvpt_bvh_wide_form(const rvpt_bvh_node *nodes, size_t n_nodes, uint32_t head_shift, float *wide_out, size_t wide_capacity, size_t *n_wide_out,
                        uint32_t *stack_need_out);
-
-/* The 64-byte QUANTISED form of those wide nodes (rvpt_bvh4.hip: trace_bvh4q, opt-in with RVPT_HIP_BVH_QUANT=1; profiles/EXPERIMENTS.md 5.16) and the exact
- * leaf boxes that go with it.  Under containment inner boxes only cull (intersection.glsl:361-413 visits a node iff its OWN box passes), so a child box may
- * be any superset as long as a leaf's exact box is tested at its visit.  quant_out: 16 words per wide node — origin x y z (float), scale x y z (float, a
- * power of two), qminx qmaxx qminy qmaxy qminz qmaxz (byte k = child k; [origin + qmin scale, origin + qmax scale] contains the child's exact box), the
- * four heads of the 128-byte form.  leaf_boxes_out (may be NULL): 8 floats per TRIANGLE index, at [8 first] the box of the leaf that starts at `first`
- * (minx maxx miny maxy minz maxz 0 0).  *extent_out: the largest |coordinate| of the tree (the margin of the kernel's conservative test).
- * *n_quant_out = 0 when the tree has no quantised form (no wide form; an inner node that does not contain a child; two leaves starting at one triangle;
- * a non-finite bound): the exact nodes serve it.  No GPU needed. */
-int rvpt_bvh_quant_form(const rvpt_bvh_node *nodes, size_t n_nodes, uint32_t head_shift, size_t n_tris, uint32_t *quant_out, size_t quant_capacity,
-                        size_t *n_quant_out, float *leaf_boxes_out, float *extent_out);
 
 #ifdef __cplusplus
 }

@@ -103,15 +103,6 @@ struct rvpt_hip_ctx {
     float4 *d_wide = nullptr;
     size_t n_wide = 0, cap_wide = 0;
     uint32_t wide_stack_levels = 0;  // most slots a depth-first walk of the wide tree can hold at once
-    // the 64-byte quantised form of the wide nodes + the exact leaf boxes by first triangle (trace_bvh4q; build_quant_nodes, build_leaf_boxes): trees every
-    // inner node of which contains its children
-    float4 *d_wideq = nullptr, *d_leaf_box = nullptr;
-    size_t cap_wideq = 0, cap_leaf_box = 0;
-    bool has_quant = false;
-    float slab_extent = 0.0f;
-    float4 *d_wide8 = nullptr;       // the 8-wide form (rvpt_bvh8.hip; RVPT_HIP_BVH_WIDE8=1): 256-byte nodes
-    size_t n_wide8 = 0, cap_wide8 = 0;
-    uint32_t wide8_stack_levels = 0;
     uint32_t bvh_head_shift = 0;  // see FrameParams::head_shift
     size_t cap_tris = 0, cap_prep = 0, cap_mat_index = 0, cap_mats = 0, cap_nodes = 0;  // allocated elements
     bool have_scene = false;
@@ -166,8 +157,6 @@ struct rvpt_hip_ctx {
     // The policy knobs, read once at create (read_knobs); the release library reads only the culls' and the interleave's, the others keep these defaults there
     struct Knobs {
         bool bvh_wide = true;             // BVH contexts, lean configuration, reference order: the wide kernels (RVPT_HIP_BVH_PER_LANE / RVPT_HIP_BVH_WIDE=0: binary)
-        bool bvh_wide8 = false;           // RVPT_HIP_BVH_WIDE8=1: the 8-wide walk (rvpt_bvh8.hip) on HBM-resident scenes
-        bool bvh_quant = false;           // RVPT_HIP_BVH_QUANT=1: the 64-byte quantised nodes (bit-exact, measured SLOWER: profiles/EXPERIMENTS.md 5.16)
         bool bvh_wide_resident = true;    // RVPT_HIP_BVH_WIDE_RESIDENT=0: LDS-resident scenes on the binary camera-packet kernel instead of the wide tree (trace_bvh4_resident)
         bool bvh_no_resident = false;     // RVPT_HIP_BVH_NO_RESIDENT=1: never the LDS-resident BVH instances
         bool bvh_no_packed_heads = false; // RVPT_HIP_BVH_NO_PACKED_HEADS (set): the stack keeps node indices and the walk fetches (first, count) at the pop (FrameParams::head_shift = 0)
@@ -221,8 +210,6 @@ rvpt_hip_ctx::Knobs read_knobs(uint32_t flags)
     // Knobs of the laboratory build (librvpt_hip_debug.so, -DRVPT_HIP_LAB=1: rvpt_amd/build.py): the sweeps of rounds 1-5 found each of them flat around its
     // default (profiles/r05_bvh_thresholds.txt, EXPERIMENTS.md), so the release library reads none of them — there they are the constants of the built-in policy.
     set_flag(k.bvh_wide, getenv("RVPT_HIP_BVH_WIDE"));  // experiments: A/B a whole run
-    set_flag(k.bvh_wide8, getenv("RVPT_HIP_BVH_WIDE8"));
-    set_flag(k.bvh_quant, getenv("RVPT_HIP_BVH_QUANT"));
     set_flag(k.bvh_wide_resident, getenv("RVPT_HIP_BVH_WIDE_RESIDENT"));
     set_flag(k.bvh_no_resident, getenv("RVPT_HIP_BVH_NO_RESIDENT"));
     k.bvh_no_packed_heads = getenv("RVPT_HIP_BVH_NO_PACKED_HEADS") != nullptr;
@@ -369,17 +356,18 @@ uint32_t owned_tiles(uint32_t n_tiles, uint32_t rank, uint32_t world) { return (
 using Kernel = void (*)(const rv::FrameParams);
 
 // The kernel paths of a launch, by the number rvpt_hip_get_launch_info reports (bench.py and the tests compare against these numbers).  Retired: 9, the streamed
-// packet kernel of round 4, measured no faster (profiles/r04_exp_stream_packets.patch); 4, 5, the wavefront pipelines of round 3 (profiles/r04_exp_wavefront_pipelines.patch)
+// packet kernel of round 4, measured no faster (profiles/r04_exp_stream_packets.patch); 4, 5, the wavefront pipelines of round 3 (profiles/r04_exp_wavefront_pipelines.patch);
+// 12, 13, the 8-wide walk and the 4-wide walk over 64-byte quantised nodes of round 5, both bit-exact and measured slower (profiles/r07_exp_bvh8_walk.patch,
+// profiles/r07_exp_bvh4_quant_nodes.patch)
 enum class Variant : uint32_t {
     BruteResident = 0, BruteStream = 1,  // brute force, scene in LDS (mixed packets: trace_brute_resident) / streamed through LDS
     Bvh = 2, BvhResident = 3,            // binary tree, scene in HBM / in LDS
     BrutePackets = 6,                    // brute force, scene in LDS: the packet kernel (rvpt_packets.hip)
     Wide = 10, WideResident = 11,        // the 4-wide tree (rvpt_bvh4.hip), scene in HBM / in LDS with camera packets
-    Wide8 = 12, WideQuant = 13,          // laboratory: the 8-wide walk (RVPT_HIP_BVH_WIDE8=1) / the 4-wide one over 64-byte quantised nodes (RVPT_HIP_BVH_QUANT=1)
 };
 
 // the paths that keep the levels of the traversal stack beyond the LDS ones in global memory (FrameParams::stack_overflow)
-bool has_global_stack(Variant v) { return v == Variant::Bvh || v == Variant::Wide || v == Variant::WideResident || v == Variant::Wide8 || v == Variant::WideQuant; }
+bool has_global_stack(Variant v) { return v == Variant::Bvh || v == Variant::Wide || v == Variant::WideResident; }
 
 // rvpt_hip_get_cull_info bits (native.cull_info, tools/fuzz_culls.py): the screen rectangles (FrameParams::rects), the bounce table (vis), camera rounds
 // aligned to 16 x 4 blocks, the leaf boxes of the bounce rounds (leaf_boxes), the interleaved claim order (perm_*), the packet instance without the uncull'd walks
@@ -595,12 +583,9 @@ int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, L
     // tools/archive/ab_wide_resident.sh, profiles/r04_ab_wide_resident.txt)
     const uint32_t wr_levels_want = k.bvh_stack_lds > 0 ? static_cast<uint32_t>(k.bvh_stack_lds) : 4u;
     auto wide_resident_bytes = [&](uint32_t levels) { return stack_lds_bytes(levels) + 2 * sizeof(float4) + ctx->n_wide * rv::kWideTopQuads * 16 + ctx->n_tris * 64 + index_bytes(ctx) + ctx->n_mats * 48; };
-    const bool quant = !generic && ctx->has_quant && k.bvh_quant;  // (the laboratory build's trees only)
-    // the 8-wide form (laboratory build; rvpt_bvh8.hip): half the steps of the 4-wide walk again on scenes whose rays see few boxes per level
-    const bool wide8 = wide && !bvh_resident && !generic && k.bvh_wide8 && ctx->n_wide8 > 0;
     const Variant v = l.variant = !bvh ? (packets ? Variant::BrutePackets : resident ? Variant::BruteResident : Variant::BruteStream)
                                 : bvh_resident ? (wide && k.bvh_wide_resident && wide_resident_bytes(wr_levels_want) <= kLdsBudget ? Variant::WideResident : Variant::BvhResident)
-                                : !wide ? Variant::Bvh : wide8 ? Variant::Wide8 : quant ? Variant::WideQuant : Variant::Wide;
+                                : wide ? Variant::Wide : Variant::Bvh;
     // 2. Its LDS and FrameParams.
     // BVH: traversal stack sized from the tree.  HBM-resident scenes keep only the first stack levels in LDS (the rest overflows to global memory, rarely
     // touched) so that the top of the tree fits beside them at full occupancy; LDS-resident scenes keep the whole stack
@@ -637,24 +622,18 @@ int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, L
              {rv::trace_bvh<true, true, false, true>, rv::trace_bvh<false, true, false, true>, rv::trace_bvh<true, true, true, true>, rv::trace_bvh<false, true, true, true>}}};
         l.kernel = kernels[ordered ? 1 : 0][bvh_resident ? 1 : 0][sel];
         l.lds = stack_lds_bytes(p.stack_lds_levels) + (bvh_resident ? bvh_scene_bytes(ctx) : static_cast<size_t>(p.bvh_top_nodes) * 32);
-    } else if (v == Variant::Wide || v == Variant::WideQuant || v == Variant::Wide8) {
-#if RVPT_HIP_LAB
-        l.kernel = wide8 ? rv::trace_bvh8 : quant ? rv::trace_bvh4q : generic ? rv::trace_bvh4_generic : rv::trace_bvh4;
-#else
+    } else if (v == Variant::Wide) {
         l.kernel = generic ? rv::trace_bvh4_generic : rv::trace_bvh4;
-#endif
-        p.leaf_box = quant ? ctx->d_leaf_box : nullptr;
-        p.slab_extent = ctx->slab_extent;
-        p.wide = wide8 ? ctx->d_wide8 : quant ? ctx->d_wideq : ctx->d_wide;
-        p.n_wide = static_cast<uint32_t>(wide8 ? ctx->n_wide8 : ctx->n_wide);
-        p.stack_levels = std::max<uint32_t>(1, wide8 ? ctx->wide8_stack_levels : ctx->wide_stack_levels);
+        p.wide = ctx->d_wide;
+        p.n_wide = static_cast<uint32_t>(ctx->n_wide);
+        p.stack_levels = std::max<uint32_t>(1, ctx->wide_stack_levels);
         p.stack_lds_levels = std::min(p.stack_levels, lds_levels_want);
-        // one node in the LDS copy of the tree top, and how many by default: 8 KiB, as the binary kernel's 256 nodes (the 8-wide walk keeps one stack level more)
-        const uint32_t node_bytes = wide8 ? 256u : quant ? 64u : rv::kWideTopQuads * 16u;
-        const uint32_t wide_top_want = k.bvh_top_nodes >= 0 ? static_cast<uint32_t>(k.bvh_top_nodes) : (wide8 ? 32u : quant ? 128u : 64u);
+        // one node in the LDS copy of the tree top, and how many by default: 8 KiB, as the binary kernel's 256 nodes
+        const uint32_t node_bytes = rv::kWideTopQuads * 16u;
+        const uint32_t wide_top_want = k.bvh_top_nodes >= 0 ? static_cast<uint32_t>(k.bvh_top_nodes) : 64u;
         // (the knob counts NODES, and a wide node is four binary ones: whatever it asks for, the stack levels + the root record + the top nodes stay within
         // the 64 KiB a work-group can have — ADVICE r4: RVPT_HIP_BVH_TOP_NODES=2048 used to ask for 256 KiB and fail at launch)
-        const size_t fixed = stack_lds_bytes(p.stack_lds_levels + (wide8 ? 1u : 0u)) + 2 * sizeof(float4);
+        const size_t fixed = stack_lds_bytes(p.stack_lds_levels) + 2 * sizeof(float4);
         const uint32_t wide_top_fit = static_cast<uint32_t>((kLdsBudget - std::min(fixed, kLdsBudget)) / node_bytes);
         p.wide_top_nodes = std::min<uint32_t>({wide_top_want, p.n_wide, wide_top_fit});
         l.lds = fixed + static_cast<size_t>(p.wide_top_nodes) * node_bytes;
@@ -872,9 +851,6 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     }
     if (ctx->d_vis) (void)hipFree(ctx->d_vis);
     if (ctx->d_leaf_boxes) (void)hipFree(ctx->d_leaf_boxes);
-    if (ctx->d_wide8) (void)hipFree(ctx->d_wide8);
-    if (ctx->d_leaf_box) (void)hipFree(ctx->d_leaf_box);
-    if (ctx->d_wideq) (void)hipFree(ctx->d_wideq);
     if (ctx->d_gather) (void)hipFree(ctx->d_gather);
     if (ctx->d_barrier) (void)hipFree(ctx->d_barrier);
     if (ctx->d_quant) (void)hipFree(ctx->d_quant);
@@ -1038,34 +1014,6 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
             ctx->n_wide = n_wide;
             ctx->wide_stack_levels = need;
         }
-        ctx->has_quant = false;
-#if RVPT_HIP_LAB
-        if (ctx->n_wide > 0 && ctx->knobs.bvh_quant) {
-            float extent = 0.0f, box_extent = 0.0f;
-            const std::vector<uint32_t> quant = rv::build_quant_nodes(wide, extent);
-            const std::vector<float> boxes = quant.empty() ? std::vector<float>() : rv::build_leaf_boxes(device_nodes.data(), device_nodes.size(), n_tris, box_extent);
-            if (!quant.empty() && !boxes.empty()) {
-                if ((rc = grow(ctx, ctx->d_wideq, ctx->cap_wideq, ctx->n_wide * 4, sizeof(float4)))) return rc;
-                if ((rc = grow(ctx, ctx->d_leaf_box, ctx->cap_leaf_box, n_tris * 2, sizeof(float4)))) return rc;
-                HIP_TRY(ctx, hipMemcpy(ctx->d_wideq, quant.data(), quant.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                HIP_TRY(ctx, hipMemcpy(ctx->d_leaf_box, boxes.data(), boxes.size() * sizeof(float), hipMemcpyHostToDevice));
-                ctx->has_quant = true;
-                ctx->slab_extent = std::max(extent, box_extent);
-            }
-        }
-        ctx->n_wide8 = 0;
-        if (ctx->knobs.bvh_wide8) {
-            uint32_t need8 = 0;
-            const std::vector<float> wide8 = rv::build_wide8_nodes(device_nodes.data(), device_nodes.size(), ctx->bvh_head_shift, need8);
-            if (!wide8.empty() && need8 <= 4096u && wide8.size() / 64 < (rv::kWideMaxNodes >> 1)) {
-                const size_t n8 = wide8.size() / 64;
-                if ((rc = grow(ctx, ctx->d_wide8, ctx->cap_wide8, n8 * 16, sizeof(float4)))) return rc;
-                HIP_TRY(ctx, hipMemcpy(ctx->d_wide8, wide8.data(), wide8.size() * sizeof(float), hipMemcpyHostToDevice));
-                ctx->n_wide8 = n8;
-                ctx->wide8_stack_levels = need8;
-            }
-        }
-#endif
     }
     // the bounce cull's table, for scenes the packet kernel can hold (brute-force contexts, <= kResidentMaxTris triangles)
     ctx->vis_words = 0;

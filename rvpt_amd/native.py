@@ -37,7 +37,7 @@ EXPORTS = [
 # ... and what the laboratory build librvpt_hip_debug.so adds (include/rvpt_hip_lab.h)
 LAB_EXPORTS = [
     "rvpt_hip_selftest_div", "rvpt_hip_selftest_rcp", "rvpt_hip_selftest_pretest", "rvpt_hip_selftest_camera_rects", "rvpt_hip_selftest_bounce_cull",
-    "rvpt_hip_selftest_fast_div", "rvpt_camera_rects", "rvpt_bounce_rows", "rvpt_bounce_leaf_boxes", "rvpt_bvh_wide_form", "rvpt_bvh_quant_form", "rvpt_claim_order",
+    "rvpt_hip_selftest_fast_div", "rvpt_camera_rects", "rvpt_bounce_rows", "rvpt_bounce_leaf_boxes", "rvpt_bvh_wide_form", "rvpt_claim_order",
 ]
 
 
@@ -92,7 +92,6 @@ def _bind(L, lab: bool):
     names = list(EXPORTS)
     if lab:
         L.rvpt_bvh_wide_form.argtypes = [vp, sz, C.c_uint32, vp, sz, C.POINTER(sz), C.POINTER(C.c_uint32)]
-        L.rvpt_bvh_quant_form.argtypes = [vp, sz, C.c_uint32, sz, vp, sz, C.POINTER(sz), vp, C.POINTER(C.c_float)]
         L.rvpt_hip_selftest_div.argtypes = [i32, vp, vp, vp, sz]
         L.rvpt_hip_selftest_rcp.argtypes = [i32, vp]
         L.rvpt_hip_selftest_pretest.argtypes = [i32, vp, vp, vp, vp, sz]
@@ -223,18 +222,6 @@ def wide_form(nodes: np.ndarray, head_shift: int):
     n_wide, need = C.c_size_t(0), C.c_uint32(0)
     _check(load_lab().rvpt_bvh_wide_form(_ptr(nodes), n, int(head_shift), _ptr(out), out.shape[0], C.byref(n_wide), C.byref(need)), None, load_lab())
     return out[: n_wide.value].copy(), int(need.value)
-
-
-def quant_form(nodes: np.ndarray, head_shift: int, n_tris: int):
-    """rvpt_bvh_quant_form: the 64-byte quantised wide nodes (RVPT_HIP_BVH_QUANT=1) of a binary tree.  Returns (quant uint32[n, 16], leaf boxes
-    float32[n_tris, 8], extent); n == 0 when the tree has no quantised form."""
-    nodes = np.ascontiguousarray(nodes).view(np.uint32).reshape(-1, 8)
-    n = nodes.shape[0]
-    out = np.zeros((max(n, 1), 16), dtype=np.uint32)
-    boxes = np.zeros((max(int(n_tris), 1), 8), dtype=np.float32)
-    n_q, extent = C.c_size_t(0), C.c_float(0.0)
-    _check(load_lab().rvpt_bvh_quant_form(_ptr(nodes), n, int(head_shift), int(n_tris), _ptr(out), out.shape[0], C.byref(n_q), _ptr(boxes), C.byref(extent)), None, load_lab())
-    return out[: n_q.value].copy(), boxes, float(extent.value)
 
 
 def fast_div(x: np.ndarray, divisor: int) -> np.ndarray:

@@ -39,7 +39,7 @@ RELEASE_ABI = [
     "rvpt_hip_upload_scene", "rvpt_hip_wait", "rvpt_hip_wait_for", "rvpt_hip_write_accum",
 ]
 LAB_ABI = [
-    "rvpt_bounce_leaf_boxes", "rvpt_bounce_rows", "rvpt_bvh_quant_form", "rvpt_bvh_wide_form", "rvpt_camera_rects", "rvpt_claim_order", "rvpt_hip_selftest_bounce_cull", "rvpt_hip_selftest_camera_rects",
+    "rvpt_bounce_leaf_boxes", "rvpt_bounce_rows", "rvpt_bvh_wide_form", "rvpt_camera_rects", "rvpt_claim_order", "rvpt_hip_selftest_bounce_cull", "rvpt_hip_selftest_camera_rects",
     "rvpt_hip_selftest_div", "rvpt_hip_selftest_fast_div", "rvpt_hip_selftest_pretest", "rvpt_hip_selftest_rcp",
 ]
 
@@ -50,6 +50,8 @@ def test_the_release_library_exports_the_c_abi_and_nothing_else(lib):
     names = declared_functions()
     assert names == RELEASE_ABI
     assert sorted(native.EXPORTS) == names
+    history = re.search(r"the release library exports the (\d+) entry points", (ROOT / "include" / "rvpt_hip.h").read_text())
+    assert history and int(history.group(1)) == len(native.EXPORTS)  # the header's ABI-8 history line counts them too
     assert exported_functions(build.LIB_PATH) == names
     for n in names:
         assert hasattr(lib, n), n
@@ -57,7 +59,7 @@ def test_the_release_library_exports_the_c_abi_and_nothing_else(lib):
     assert lib.rvpt_hip_build_flags() == 0
 
 
-def test_the_laboratory_library_adds_the_diagnostics(lib):
+def test_the_laboratory_library_adds_the_diagnostics_and_host_forms(lib):
     """include/rvpt_hip_lab.h == native.LAB_EXPORTS == what librvpt_hip_debug.so defines beside the release ABI."""
     from rvpt_amd import build, native
     build.build_native_debug()

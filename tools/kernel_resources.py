@@ -21,7 +21,7 @@ sys.path.insert(0, str(ROOT))
 from rvpt_amd import build  # noqa: E402
 
 
-KERNEL_FILES = ("rvpt_kernels.hip", "rvpt_packets.hip", "rvpt_bvh4.hip", "rvpt_bvh8.hip")
+KERNEL_FILES = ("rvpt_kernels.hip", "rvpt_packets.hip", "rvpt_bvh4.hip")
 
 
 def device_flags():

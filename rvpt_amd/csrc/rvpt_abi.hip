@@ -141,7 +141,14 @@ struct rvpt_hip_ctx {
         uint64_t scene_gen;
     } rects_key[kMaxSlots] = {};
     bool rects_valid[kMaxSlots] = {};
-    uint64_t scene_gen = 0;                   // bumped by every upload_scene
+    // the SKY blocks of the slot's camera (rvpt_packets.hip: sky_blocks, sky_list — made with the slot's rectangles, for batched launches): a bit per block, the
+    // ascending list of the other blocks and its count, copied into pinned host memory behind them (sky_ready); choose_launch takes the listed path only once it is there
+    uint32_t *d_sky_bits[kMaxSlots] = {}, *d_sky_list[kMaxSlots] = {}, *d_sky_count[kMaxSlots] = {};
+    uint32_t *h_sky_count = nullptr;          // kMaxSlots counts (hipHostMalloc)
+    hipEvent_t sky_ready[kMaxSlots] = {}, sky_read[kMaxSlots] = {};  // the count has arrived / the last blend that read the slot's sky bits is done
+    bool sky_valid[kMaxSlots] = {};           // made for rects_key[slot]
+    bool sky_read_used[kMaxSlots] = {};
+    uint64_t scene_gen = 0;                  // bumped by every upload_scene
     float4 *d_gather = nullptr;               // rank 0: tile_world slots of slot_quads
     void *d_quant = nullptr;                  // rank 0: width*height*4 B, rgba8 of a gathered frame
     unsigned long long *d_timeline = nullptr;  // RVPT_HIP_TIMELINE=<file>: per-wave timestamps of the last frame
@@ -167,6 +174,8 @@ struct rvpt_hip_ctx {
         bool packets_lean_instance = true;  // RVPT_HIP_PACKETS_LEAN_INSTANCE=0: the general instances only (A/B)
         int packets_interleave = 1;       // RVPT_HIP_PACKETS_INTERLEAVE=g: launches of < 4 frames deal groups of g (1, 2, 4, 8) blocks from all over the frame; 0 = tile-linear (A/B)
         bool packets_interleave_all = false;  // ... =-g: launches of any size (measured slower for the batched ones: profiles/r06_interleave.txt)
+        int packets_sky_list = 1;         // RVPT_HIP_PACKETS_SKY_LIST (laboratory build): batched launches claim only the blocks that are not sky (0 = off, 1 = once the
+                                          // slot's list has arrived, 2 = wait for the list on first use: tests/test_sky_list.py)
         std::string timeline_path;        // RVPT_HIP_TIMELINE=<file>: the last frame's per-wave timestamps, written at destroy
         int blocks_per_cu = 0;            // RVPT_HIP_BLOCKS_PER_CU: work-groups per CU of the persistent kernels (0 / -1 here and below: the built-in policy)
         int first_units = 0, claim_units = 0;  // RVPT_HIP_FIRST_UNITS, RVPT_HIP_CLAIM_UNITS: the work plan's static chunk and claim size (plan_work)
@@ -227,6 +236,7 @@ rvpt_hip_ctx::Knobs read_knobs(uint32_t flags)
     set_int(k.bvh_stack_lds, getenv("RVPT_HIP_BVH_STACK_LDS"), 1, 64);
     set_int(k.bvh_cam_min, getenv("RVPT_HIP_BVH_CAM_MIN"), 1, 65);  // 65 = never
     set_int(k.bvh_detach, getenv("RVPT_HIP_BVH_DETACH"), 0, 64);
+    set_int(k.packets_sky_list, getenv("RVPT_HIP_PACKETS_SKY_LIST"), 0, 2);
 #endif
     return k;
 }
@@ -371,7 +381,8 @@ bool has_global_stack(Variant v) { return v == Variant::Bvh || v == Variant::Wid
 
 // rvpt_hip_get_cull_info bits (native.cull_info, tools/fuzz_culls.py): the screen rectangles (FrameParams::rects), the bounce table (vis), camera rounds
 // aligned to 16 x 4 blocks, the leaf boxes of the bounce rounds (leaf_boxes), the interleaved claim order (perm_*), the packet instance without the uncull'd walks
-constexpr uint32_t kCullRects = 1u, kCullBounce = 2u, kCullBlockRounds = 4u, kCullLeafBoxes = 16u, kCullClaimOrder = 32u, kCullLeanInstance = 64u;
+// ... and the batched launch that claims only the blocks that are not sky (trace_brute_packets_aa1_culls_listed + blend_accumulate_sky)
+constexpr uint32_t kCullRects = 1u, kCullBounce = 2u, kCullBlockRounds = 4u, kCullLeafBoxes = 16u, kCullClaimOrder = 32u, kCullLeanInstance = 64u, kCullSkyList = 128u;
 
 struct Launch {
     Kernel kernel;
@@ -379,6 +390,9 @@ struct Launch {
     size_t lds;          // dynamic LDS bytes per work-group
     uint32_t grid;       // work-groups
     uint32_t cull_bits;  // kCull*: kCullRects = the packet kernel's screen rectangles of the triangles ride along (FrameParams::rects)
+    bool sky_wanted;     // the lean batched instance with one sample per pixel: the slot's sky list is made for its camera (dispatch_launch)
+    bool listed;         // ... and this launch takes the listed path over `work` (kernel = the listed instance)
+    rv::ListedWork work;
 };
 
 // scene pointers, image geometry, the settings/camera blocks of this frame (compute_pass.comp:28-54)
@@ -483,6 +497,8 @@ void plan_work(const rvpt_hip_ctx *ctx, bool regen, rv::FrameParams &p, uint32_t
         // Msamples/s at the driver's command, 36 169 -> 46 338 over 200 steps; an eighth of the image 0.0164 -> 0.0131 ms per frame; 16 / 32 / 64 counters
         // instead of 8 help only the small claims (tools/archive/r05_claims.sh, profiles/r05_claims.txt)
         if (align_units == 4u) p.claim_units = 32u;
+        // (the listed path of round 7 — only the blocks that are not sky, about six claims per wave in 20 frames where there were thirteen — keeps the same rule:
+        // 16- and 8-unit claims measured 6 % and 10 % slower, a smaller static chunk within noise: profiles/r07_sky_list.txt)
         // a static chunk of 5-7 units (images of 131-229 k pixels) would start most camera rounds off a block boundary and lose them the rectangles
         if (align_units > 1 && p.first_units > align_units) p.first_units = p.first_units / align_units * align_units;
         if (ctx->knobs.first_units) p.first_units = static_cast<uint32_t>(ctx->knobs.first_units);
@@ -551,8 +567,8 @@ void plan_interleave(const rvpt_hip_ctx *ctx, rv::FrameParams &p)
 }
 
 // The whole decision for one launch: the kernel path, its LDS and FrameParams, the grid, the work plan and the culls.  `p` comes filled by
-// fill_frame_params, with p.n_work the launch's work items; `lone`: nothing of this context is in flight; `slots`: launches in flight (slots_for).
-int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, Launch &l)
+// fill_frame_params, with p.n_work the launch's work items; `lone`: nothing of this context is in flight; `slots`: launches in flight (slots_for); `slot`: this launch's.
+int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, int slot, Launch &l)
 {
     const rvpt_hip_ctx::Knobs &k = ctx->knobs;
     const bool bvh = is_bvh(ctx, ctx->n_tris);  // no tree = empty scene
@@ -707,15 +723,46 @@ int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, L
     plan_work(ctx, regen, p, v == Variant::BrutePackets ? 4u : 1u);
     if (v == Variant::BrutePackets) plan_interleave(ctx, p);
     // 5. The lean packet instances, for launches with all three culls on and every chunk of the plan whole blocks (the default for a scene with a table): no
-    // uncull'd walks — fewer registers to keep alive (SGPR spills 54 -> 19 for one sample per pixel; every spill is a v_readlane / v_writelane the VALU issues) —
+    // uncull'd walks — fewer registers to keep alive (SGPR spills 54 -> 19 for one sample per pixel when measured in round 6, 22 with today's compiler, 20 for the listed instance; every spill is a v_readlane / v_writelane the VALU issues) —
     // with or without the interleaved claim order of short launches (its scalars cost the batched launches' kernel eleven spills more).  LAST, because it depends
     // on the work plan (whole_blocks), which depends on the grid (p.n_waves); the grid is the general instance's, which needs no fewer resources (tests/test_abi_exports.py).
     const bool lean = v == Variant::BrutePackets && cull && p.vis && p.leaf_boxes && p.sample_out && whole_blocks(p) && k.packets_lean_instance;
     if (lean)
         l.kernel = p.perm_groups != 0u ? ((p.aa == 1) ? rv::trace_brute_packets_aa1_culls_order : rv::trace_brute_packets_culls_order)
                                        : ((p.aa == 1) ? rv::trace_brute_packets_aa1_culls : rv::trace_brute_packets_culls);
+    // 6. The listed path (round 7): a batched launch of the lean one-sample instance whose camera leaves SKY blocks — no triangle's rectangle holds them, so their camera
+    // round walks nothing, every ray misses and the path ends there — claims only the other blocks; blend_accumulate_sky makes the sky's samples from the RNG.  Only
+    // with the slot's list for THIS camera already on the host (a moving camera, the first launch after a camera or scene change: the path above), never waited for.
+    l.sky_wanted = lean && p.aa == 1 && p.perm_groups == 0u && p.n_work >= 4u * p.n_work_frame && k.packets_sky_list > 0;
+    l.listed = false;
+    uint32_t n_listed = 0;
+    if (l.sky_wanted && ctx->sky_valid[slot] && ctx->rects_valid[slot] && std::memcmp(&ctx->rects_key[slot].camera, &ctx->camera, sizeof(ctx->camera)) == 0 &&
+        ctx->rects_key[slot].scene_gen == ctx->scene_gen) {
+        const hipError_t arrived = hipEventQuery(ctx->sky_ready[slot]);
+        if (arrived == hipErrorNotReady) (void)hipGetLastError();  // (an answer, not an error)
+        if (arrived == hipSuccess) {
+            const uint32_t n_blocks = p.n_work_frame / 64u;
+            n_listed = ctx->h_sky_count[slot];
+            if (n_listed < n_blocks && n_listed > 0u) {
+                const uint32_t n_work = p.n_work;
+                p.n_work = p.n_work / p.n_work_frame * n_listed * 64u;
+                plan_work(ctx, regen, p, 4u);
+                l.listed = whole_blocks(p);  // (a list too short for whole-block chunks: the path above)
+                if (!l.listed) {
+                    p.n_work = n_work;
+                    plan_work(ctx, regen, p, 4u);
+                }
+            }
+        }
+    }
+    if (l.listed) {
+        l.kernel = nullptr;  // (dispatch_launch launches the listed instance)
+        l.work.list = ctx->d_sky_list[slot];
+        l.work.n_listed_frame = 64u * n_listed;
+        l.work.div_listed_frame = rv::fast_div_make(64u * n_listed);
+    }
     l.cull_bits = (cull ? kCullRects : 0u) | (p.vis ? kCullBounce : 0u) | ((v == Variant::BrutePackets && p.first_units % 4u == 0u) ? kCullBlockRounds : 0u) |
-                  (p.leaf_boxes ? kCullLeafBoxes : 0u) | (p.perm_groups != 0u ? kCullClaimOrder : 0u) | (lean ? kCullLeanInstance : 0u);
+                  (p.leaf_boxes ? kCullLeafBoxes : 0u) | (p.perm_groups != 0u ? kCullClaimOrder : 0u) | (lean ? kCullLeanInstance : 0u) | (l.listed ? kCullSkyList : 0u);
     return 0;
 }
 
@@ -857,6 +904,14 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     for (int i = 0; i < rvpt_hip_ctx::kMaxSlots; ++i)
         if (ctx->trace_stream[i]) (void)hipStreamSynchronize(ctx->trace_stream[i]);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    for (int i = 0; i < rvpt_hip_ctx::kMaxSlots; ++i) {  // (after the drain: a blend_accumulate_sky on the main stream reads the bits)
+        if (ctx->d_sky_bits[i]) (void)hipFree(ctx->d_sky_bits[i]);
+        if (ctx->d_sky_list[i]) (void)hipFree(ctx->d_sky_list[i]);
+        if (ctx->d_sky_count[i]) (void)hipFree(ctx->d_sky_count[i]);
+        if (ctx->sky_ready[i]) (void)hipEventDestroy(ctx->sky_ready[i]);
+        if (ctx->sky_read[i]) (void)hipEventDestroy(ctx->sky_read[i]);
+    }
+    if (ctx->h_sky_count) (void)hipHostFree(ctx->h_sky_count);
     if (ctx->d_timeline && !ctx->knobs.timeline_path.empty()) {  // debugging aid: dump the last frame's wave timeline
         std::vector<unsigned long long> h(ctx->timeline_words);
         if (hipMemcpy(h.data(), ctx->d_timeline, ctx->timeline_words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1060,6 +1115,65 @@ int rvpt_hip_set_frame(rvpt_hip_ctx *ctx, const rvpt_render_settings *s, const r
 
 namespace {
 
+// The packet kernel's camera records and screen rectangles for this camera: made on the slot's stream, in front of the frame kernel, when the slot's buffers hold another
+// camera's.  With `sky`, the slot's sky bits, list and count for the same camera too (sky_blocks, sky_list), the count copied to the host behind them (sky_ready).
+static int update_rects(rvpt_hip_ctx *ctx, int slot, hipStream_t tstream, const rv::FrameParams &p, bool sky)
+{
+    if (ctx->n_tris > ctx->rects_cap[slot]) {
+        HIP_TRY(ctx, hipStreamSynchronize(tstream));
+        if (ctx->d_rects[slot]) HIP_TRY(ctx, hipFree(ctx->d_rects[slot]));
+        if (ctx->d_cam_records[slot]) HIP_TRY(ctx, hipFree(ctx->d_cam_records[slot]));
+        ctx->d_rects[slot] = nullptr;
+        ctx->d_cam_records[slot] = nullptr;
+        ctx->rects_cap[slot] = 0;
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_rects[slot]), ctx->n_tris * sizeof(uint2)));
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_cam_records[slot]), ctx->n_tris * sizeof(float4)));
+        ctx->rects_cap[slot] = ctx->n_tris;
+        ctx->rects_valid[slot] = false;
+    }
+    rvpt_hip_ctx::RectKey key{};
+    key.camera = ctx->camera;
+    key.scene_gen = ctx->scene_gen;
+    if (!ctx->rects_valid[slot] || std::memcmp(&key, &ctx->rects_key[slot], sizeof(key)) != 0) {
+        const uint32_t n = static_cast<uint32_t>(ctx->n_tris);
+        hipLaunchKernelGGL(rv::camera_rects, dim3((n + 63) / 64), dim3(64), 0, tstream, p, ctx->d_rects[slot], ctx->d_cam_records[slot]);
+        HIP_TRY(ctx, hipGetLastError());
+        ctx->rects_key[slot] = key;
+        ctx->rects_valid[slot] = true;
+        ctx->sky_valid[slot] = false;
+    }
+    if (sky && !ctx->sky_valid[slot]) {
+        const uint32_t n_blocks = ctx->n_work / 64u;  // (n_work: whole 16 x 16 tiles)
+        if (!ctx->d_sky_bits[slot]) {  // (all five made, then published together: a failure part way leaves the slot without a list, never with half of one)
+            uint32_t *bits = nullptr, *list = nullptr, *count = nullptr;
+            hipEvent_t ready = nullptr, read = nullptr;
+            hipError_t e = hipMalloc(reinterpret_cast<void **>(&bits), static_cast<size_t>((n_blocks + 31u) / 32u) * sizeof(uint32_t));
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&list), static_cast<size_t>(n_blocks) * sizeof(uint32_t));
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&count), sizeof(uint32_t));
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&ready, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&read, hipEventDisableTiming);
+            if (e != hipSuccess) {
+                if (bits) (void)hipFree(bits);
+                if (list) (void)hipFree(list);
+                if (count) (void)hipFree(count);
+                if (ready) (void)hipEventDestroy(ready);
+                return fail(ctx, RVPT_HIP_ERR_HIP, "sky list buffers -> %s", hipGetErrorString(e));
+            }
+            ctx->d_sky_bits[slot] = bits, ctx->d_sky_list[slot] = list, ctx->d_sky_count[slot] = count;
+            ctx->sky_ready[slot] = ready, ctx->sky_read[slot] = read;
+        }
+        if (!ctx->h_sky_count) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_sky_count), rvpt_hip_ctx::kMaxSlots * sizeof(uint32_t)));
+        if (ctx->sky_read_used[slot]) HIP_TRY(ctx, hipStreamWaitEvent(tstream, ctx->sky_read[slot], 0));  // the last blend that reads the slot's old bits
+        hipLaunchKernelGGL(rv::sky_blocks, dim3((n_blocks + 255u) / 256u), dim3(256), 0, tstream, p, ctx->d_rects[slot], n_blocks, ctx->d_sky_bits[slot]);
+        hipLaunchKernelGGL(rv::sky_list, dim3(1), dim3(1024), 0, tstream, ctx->d_sky_bits[slot], n_blocks, ctx->d_sky_list[slot], ctx->d_sky_count[slot]);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_sky_count + slot, ctx->d_sky_count[slot], sizeof(uint32_t), hipMemcpyDeviceToHost, tstream));
+        HIP_TRY(ctx, hipEventRecord(ctx->sky_ready[slot], tstream));
+        ctx->sky_valid[slot] = true;
+    }
+    return 0;
+}
+
 // one launch covering n_frames consecutive frames starting at settings.current_frame
 static int dispatch_launch(rvpt_hip_ctx *ctx, uint32_t n_frames)
 {
@@ -1102,31 +1216,15 @@ static int dispatch_launch(rvpt_hip_ctx *ctx, uint32_t n_frames)
             if (ctx->slot_used[i] && hipStreamQuery(ctx->trace_stream[i]) != hipSuccess) lone = false;
         (void)hipGetLastError();  // hipErrorNotReady is an answer, not an error
     }
+    // the knob's test form (RVPT_HIP_PACKETS_SKY_LIST=2): the slot's rectangles and sky list for this camera first, waited for, so that a first batched launch takes the listed path
+    if (ctx->knobs.packets_sky_list == 2 && n_frames >= 4u && ctx->settings.aa == 1 && !is_bvh(ctx, ctx->n_tris) && ctx->n_tris > 0 && ctx->n_tris <= rv::kResidentMaxTris) {
+        if (int rc = update_rects(ctx, slot, tstream, p, true)) return rc;
+        HIP_TRY(ctx, hipEventSynchronize(ctx->sky_ready[slot]));
+    }
     Launch launch{};
-    if (int rc = choose_launch(ctx, p, lone, slots, launch)) return rc;
-    if (launch.variant == Variant::BrutePackets) {  // the camera records and the rectangles for this camera: made on the slot's stream, in front of the frame kernel, when the slot's buffers hold another camera's
-        if (ctx->n_tris > ctx->rects_cap[slot]) {
-            HIP_TRY(ctx, hipStreamSynchronize(tstream));
-            if (ctx->d_rects[slot]) HIP_TRY(ctx, hipFree(ctx->d_rects[slot]));
-            if (ctx->d_cam_records[slot]) HIP_TRY(ctx, hipFree(ctx->d_cam_records[slot]));
-            ctx->d_rects[slot] = nullptr;
-            ctx->d_cam_records[slot] = nullptr;
-            ctx->rects_cap[slot] = 0;
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_rects[slot]), ctx->n_tris * sizeof(uint2)));
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_cam_records[slot]), ctx->n_tris * sizeof(float4)));
-            ctx->rects_cap[slot] = ctx->n_tris;
-            ctx->rects_valid[slot] = false;
-        }
-        rvpt_hip_ctx::RectKey key{};
-        key.camera = ctx->camera;
-        key.scene_gen = ctx->scene_gen;
-        if (!ctx->rects_valid[slot] || std::memcmp(&key, &ctx->rects_key[slot], sizeof(key)) != 0) {
-            const uint32_t n = static_cast<uint32_t>(ctx->n_tris);
-            hipLaunchKernelGGL(rv::camera_rects, dim3((n + 63) / 64), dim3(64), 0, tstream, p, ctx->d_rects[slot], ctx->d_cam_records[slot]);
-            HIP_TRY(ctx, hipGetLastError());
-            ctx->rects_key[slot] = key;
-            ctx->rects_valid[slot] = true;
-        }
+    if (int rc = choose_launch(ctx, p, lone, slots, slot, launch)) return rc;
+    if (launch.variant == Variant::BrutePackets) {
+        if (int rc = update_rects(ctx, slot, tstream, p, launch.sky_wanted)) return rc;
         if (launch.cull_bits & kCullRects) p.rects = ctx->d_rects[slot];
         p.cam_records = ctx->d_cam_records[slot];
     }
@@ -1177,7 +1275,10 @@ static int dispatch_launch(rvpt_hip_ctx *ctx, uint32_t n_frames)
     ctx->buf_used[buf] = true;
     ctx->slot_used[slot] = true;
     if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev0, tstream));
-    hipLaunchKernelGGL(launch.kernel, dim3(launch.grid), dim3(rv::kBlock), launch.lds, tstream, p);
+    if (launch.listed)
+        hipLaunchKernelGGL(rv::trace_brute_packets_aa1_culls_listed, dim3(launch.grid), dim3(rv::kBlock), launch.lds, tstream, p, launch.work);
+    else
+        hipLaunchKernelGGL(launch.kernel, dim3(launch.grid), dim3(rv::kBlock), launch.lds, tstream, p);
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->timing) {
         HIP_TRY(ctx, hipEventRecord(ev1, tstream));
@@ -1186,8 +1287,15 @@ static int dispatch_launch(rvpt_hip_ctx *ctx, uint32_t n_frames)
     if (ctx->overlap) {  // the temporal blend of this frame, after its samples and after every earlier blend
         HIP_TRY(ctx, hipEventRecord(ctx->trace_done[slot], tstream));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->trace_done[slot], 0));
-        hipLaunchKernelGGL(rv::blend_accumulate, dim3((ctx->n_work + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_samples[buf],
-                           ctx->d_accum, ctx->n_work, n_frames, p.frame, p.quantize);
+        if (launch.listed) {  // (the sky's samples were never made: the blend makes them)
+            hipLaunchKernelGGL(rv::blend_accumulate_sky, dim3((ctx->n_work + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_samples[buf], n_frames, ctx->d_sky_bits[slot], p);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipEventRecord(ctx->sky_read[slot], ctx->stream));
+            ctx->sky_read_used[slot] = true;
+        } else {
+            hipLaunchKernelGGL(rv::blend_accumulate, dim3((ctx->n_work + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_samples[buf],
+                               ctx->d_accum, ctx->n_work, n_frames, p.frame, p.quantize);
+        }
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipEventRecord(ctx->blend_done[buf], ctx->stream));
     }

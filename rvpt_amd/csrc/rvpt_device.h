@@ -240,6 +240,15 @@ struct ShadeSrc {
     const float4 *unit_n;  // FrameParams::unit_n (HBM; a 16-byte gather per hit through the vector cache — the table is n_tris x 16 B)
 };
 
+// integrator_Kajiya's miss: the path ends with the background of its direction (shade's first branch)
+__device__ __forceinline__ f3 miss_radiance(const Lane &L)
+{
+    const float s = fma_(L.d.y, 0.5f, 0.5f);
+    const float oms = 1.0f - s;
+    const f3 bg = mk(fma_(0.2f, s, oms), fma_(0.3f, s, oms), fma_(0.7f, s, oms));
+    return fma3(L.thr, bg, L.col);
+}
+
 // One iteration of integrator_Kajiya's loop body after the closest hit is known
 // (integrators.glsl:576-671, intersect_scene's normalisation intersection.glsl:511-513).
 // Returns true when the path ended; `radiance` is then its value.
@@ -252,10 +261,7 @@ __device__ __forceinline__ bool shade(Lane &L, const FrameParams &p, const Shade
                                       f3 &radiance, uint32_t *leave = nullptr)
 {
     if (hit == 0xFFFFFFFFu) {
-        const float s = fma_(L.d.y, 0.5f, 0.5f);
-        const float oms = 1.0f - s;
-        const f3 bg = mk(fma_(0.2f, s, oms), fma_(0.3f, s, oms), fma_(0.7f, s, oms));
-        radiance = fma3(L.thr, bg, L.col);
+        radiance = miss_radiance(L);
         return true;
     }
     // the hit triangle's unit normal: normalize(n) of its prepared record, computed by prepare_triangles (one IEEE sqrt and divide per TRIANGLE instead of per hit: the
@@ -663,6 +669,25 @@ __device__ __forceinline__ bool decode_work(const FrameParams &p, const uint32_t
     return (gx < p.width) & (gy < p.height);
 }
 
+// the RNG state a pixel's first sample starts from in frame p.frame + frame_offset (util.glsl:35-36)
+__device__ __forceinline__ uint32_t camera_seed(const FrameParams &p, const uint32_t gx, const uint32_t gy, const uint32_t frame_offset)
+{
+    return wang_hash(gx + gy * p.width) + (p.frame + frame_offset);
+}
+
+// The one-sample mean of a pixel whose camera ray provably hits nothing (a SKY block: no triangle's screen rectangle holds it, rvpt_packets.hip: sky_blocks) in
+// frame p.frame + frame_offset, Kajiya / pinhole: what the packet kernel's camera round makes of it — the seed, begin_sample, shade's miss, L.sum = 0 + radiance —
+// by the same functions, so that blend_accumulate_sky makes it instead of reading it back (same bits)
+__device__ __forceinline__ f3 sky_sample(const FrameParams &p, const uint32_t gx, const uint32_t gy, const uint32_t frame_offset)
+{
+    Lane L{};
+    L.gx = gx;
+    L.gy = gy;
+    L.rng = camera_seed(p, gx, gy, frame_offset);
+    begin_sample(L, p);
+    return mk(0.0f, 0.0f, 0.0f) + miss_radiance(L);
+}
+
 // Per-wave pool of claimed work indices + the ballot/mbcnt hand-out to lanes that need a pixel.
 //
 // Work is dealt in units of kUnit consecutive tile-linear indices (one 16-pixel tile row):
@@ -759,7 +784,7 @@ __device__ __forceinline__ void regenerate(WavePool &pool, const FrameParams &p,
                 L.work = work;
                 L.gx = gx;
                 L.gy = gy;
-                L.rng = wang_hash(gx + gy * p.width) + (p.frame + frame_offset);  // util.glsl:35-36
+                L.rng = camera_seed(p, gx, gy, frame_offset);
                 L.sample = 0;
                 L.sum = mk(0.0f, 0.0f, 0.0f);
                 if (GENERIC) L.mode = select_mode(p, gx, gy);

@@ -195,6 +195,8 @@ __global__ void trace_bvh4_generic(const FrameParams p);           // ... every 
 __global__ void trace_bvh4_resident_generic(const FrameParams p);
 __global__ void blend_accumulate(const SampleRGB *__restrict__ samples, float4 *__restrict__ accum, uint32_t n, uint32_t n_frames,
                                  uint32_t frame0, uint32_t quantize);
+// ... after a LISTED launch: the sky blocks (bit b of sky_bits) make their samples instead of reading them (p: the launch's, frame0 = p.frame, n = p.n_work_frame)
+__global__ void blend_accumulate_sky(const SampleRGB *__restrict__ samples, uint32_t n_frames, const uint32_t *__restrict__ sky_bits, const FrameParams p);
 #if RVPT_HIP_LAB
 __global__ void selftest_div_dots(const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ out, uint32_t n);
 __global__ void selftest_rcp_sweep(unsigned long long *__restrict__ mismatches);

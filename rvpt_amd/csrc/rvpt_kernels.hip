@@ -621,6 +621,48 @@ __global__ void blend_accumulate(const SampleRGB *__restrict__ samples, float4 *
     accum[i] = make_float4(prev.x, prev.y, prev.z, 0.0f);
 }
 
+// The same after a LISTED launch of the packet kernel (rvpt_packets.hip), which never claimed the SKY blocks: a work-group of 256 items is four 64-item blocks, so
+// a wave's block is sky or not as a whole.  A wave that is not folds the samples as blend_accumulate; a sky wave makes each frame's sample with the trace kernel's
+// own functions (rvpt_device.h: sky_sample) — a pixel outside the image folds the zero its never-written slot holds — and, when the launch counts, adds the one
+// segment and one sample per frame of each pixel inside that the trace kernel would have counted.
+__global__ void blend_accumulate_sky(const SampleRGB *__restrict__ samples, uint32_t n_frames, const uint32_t *__restrict__ sky_bits, const FrameParams p)
+{
+    const uint32_t n = p.n_work_frame;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;  // (n is a multiple of 256: whole waves)
+    const uint32_t b = i >> 6;
+    const bool sky = ((sky_bits[b >> 5] >> (b & 31u)) & 1u) != 0u;
+    f3 prev = mk(0.0f, 0.0f, 0.0f);
+    if (p.frame != 0u) {
+        const float4 a = p.accum[i];
+        prev = mk(a.x, a.y, a.z);
+    }
+    uint32_t gx = 0, gy = 0;
+    const bool inside = sky && decode_work(p, i, gx, gy);
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        const uint32_t frame = p.frame + k;
+        f3 sampled = mk(0.0f, 0.0f, 0.0f);
+        if (!sky) {
+            const SampleRGB sv = samples[static_cast<size_t>(k) * n + i];
+            sampled = mk(sv.x, sv.y, sv.z);
+        } else if (inside) {
+            sampled = sky_sample(p, gx, gy, k);
+        }
+        const float cf = static_cast<float>(frame);
+        const float inv_cf = 1.0f / static_cast<float>(frame + 1u);
+        prev = store_format(fma3(prev, cf, sampled) * inv_cf, p.quantize);
+    }
+    p.accum[i] = make_float4(prev.x, prev.y, prev.z, 0.0f);
+    if (sky && p.stats != nullptr) {
+        const unsigned long long counted = static_cast<unsigned long long>(__builtin_popcountll(ballot(inside))) * n_frames;
+        if (lane_id() == 0 && counted != 0ull) {
+            unsigned long long *stripe = p.stats + kStatStride * (b % kStatStripes);
+            atomicAdd(&stripe[0], counted);
+            atomicAdd(&stripe[1], counted);
+        }
+    }
+}
+
 #if RVPT_HIP_LAB
 // ------------------------------------------------------------------------------------------------
 // diagnostics of the arithmetic specification (rvpt_hip_selftest_*): div_dots on operand arrays, and the refined hardware

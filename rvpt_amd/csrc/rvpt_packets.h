@@ -15,6 +15,14 @@ __global__ void trace_brute_packets_culls(const FrameParams p);      // the same
 __global__ void trace_brute_packets_aa1_culls(const FrameParams p);  // (the walks without a cull are not in them; nor the interleaved claim order of short launches:)
 __global__ void trace_brute_packets_culls_order(const FrameParams p);
 __global__ void trace_brute_packets_aa1_culls_order(const FrameParams p);
+// The LISTED instance (batched launches of a still camera, one sample per pixel): the claims count only the blocks of a frame that are not SKY (sky_blocks below), 64
+// work items per block of `list` (ascending frame-local block indices) per frame — n_listed_frame items per frame; blend_accumulate_sky makes the sky blocks' samples
+struct ListedWork {
+    const uint32_t *list;
+    uint32_t n_listed_frame;  // 64 x the blocks of the list
+    FastDiv div_listed_frame;
+};
+__global__ void trace_brute_packets_aa1_culls_listed(const FrameParams p, const ListedWork w);
 #if RVPT_HIP_LAB
 // diagnostics (rvpt_hip_selftest_pretest): per element, bit 0 = the division-free pre-test of a camera round lets the pair through, bit 1 = the
 // quotient's own condition 0 < t < closest holds; the numerator goes through the camera record's rule (not safe -> NaN -> always through)
@@ -24,6 +32,11 @@ __global__ void selftest_camera_pretest(const float *__restrict__ a, const float
 
 // the screen rectangles of the prepared triangles for the camera of `p` (rvpt_rect.h): rects[i] = (x0 | x1 << 16, y0 | y1 << 16); one thread per triangle
 __global__ void camera_rects(const FrameParams p, uint2 *__restrict__ rects, float4 *__restrict__ records);  // (+ the camera records, 16 B per triangle, or nullptr)
+// the SKY blocks of a frame for the same camera: bit b of sky_bits (ceil(n_blocks / 32) words) = no rectangle holds the frame's 16 x 4 block b (work items 64 b ..) or
+// the block lies wholly outside the image; one thread per block, 256 per work-group
+__global__ void sky_blocks(const FrameParams p, const uint2 *__restrict__ rects, uint32_t n_blocks, uint32_t *__restrict__ sky_bits);
+// ... and the blocks that are not, in ascending order, and their count: ONE work-group of 1024 threads
+__global__ void sky_list(const uint32_t *__restrict__ sky_bits, uint32_t n_blocks, uint32_t *__restrict__ list, uint32_t *__restrict__ count);
 // the bounce cull's table for `n` prepared triangles: out[(2 A + s) * words + w] bit b = 0 only when triangle B = 32 w + b lies wholly behind the plane of A as
 // seen from side s (s = 0: the side A's normal cross(e0, e1) points to), by more than `margin`, and both triangles are well shaped; bits >= n are 0
 __global__ void bounce_visibility(const float4 *__restrict__ prep, uint32_t n, double margin, uint32_t words, uint32_t stride, uint32_t *__restrict__ out);

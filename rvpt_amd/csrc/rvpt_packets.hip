@@ -120,8 +120,10 @@ __device__ __forceinline__ void intersect_listed(const v4f *src, const uint32_t 
 // without a cull (split mode, the packet-uniform early-out over every triangle, the plain loop) are not in it
 // ORDER (CULLS only): the instance carries the interleaved claim order of short launches (FrameParams::perm_*); the batched launches' instance does not — the
 // map's six scalars cost eleven SGPR spills in a kernel that never uses them
-template <bool AA1, bool CULLS, bool ORDER = true>
-__device__ __forceinline__ void packets_body(const FrameParams &p)
+// LISTED (AA1, CULLS, batched, no claim order): pool.next counts the items of the sky-less work list `lw` (rvpt_packets.h: ListedWork); a camera round maps its 64 to
+// (frame, lw.list[b]) and L.work stays the launch's uncompacted index frame * n_work_frame + pixel (sample slot, seed and statistics as without the list)
+template <bool AA1, bool CULLS, bool ORDER = true, bool LISTED = false>
+__device__ __forceinline__ void packets_body(const FrameParams &p, const ListedWork &lw = ListedWork{})
 {
     constexpr uint32_t kPathWords = AA1 ? kPacketQueueWordsAA1 : kPacketQueueWords;
     // LDS: [prepared triangles][material index per triangle][materials][camera records: (n, dot(v0 - o, n)) per triangle][per wave: the queue of parked paths]
@@ -202,10 +204,18 @@ __device__ __forceinline__ void packets_body(const FrameParams &p)
                 first = uniform(f * p.n_work_frame + ((claim_order_block(in_frame >> 6, p.perm_groups, p.perm_stride, p.perm_shift, p.div_perm_groups) << 6) | (in_frame & 63u)));
             }
             const bool in_chunk = pool.next + lane < pool.end;
-            const uint32_t work = first + lane;
+            uint32_t work = first + lane;
             pool.next += 64u;
             uint32_t frame_offset = 0, pixel = work;
-            if (p.n_work_frame != p.n_work) {
+            if (LISTED) {  // item `first` of the list's launch: frame f, the list's block b (one scalar load: wave-uniform)
+                typedef const __attribute__((address_space(4))) uint32_t *ConstWords;
+                const uint32_t f = uniform(fast_div(first, lw.div_listed_frame));
+                const uint32_t b = uniform((first - f * lw.n_listed_frame) >> 6);
+                const uint32_t block = ((ConstWords)(reinterpret_cast<uintptr_t>(lw.list)))[b];
+                frame_offset = f;
+                pixel = (block << 6) | lane;
+                work = f * p.n_work_frame + pixel;
+            } else if (p.n_work_frame != p.n_work) {
                 frame_offset = fast_div(work, p.div_work_frame);
                 pixel = work - frame_offset * p.n_work_frame;
             }
@@ -220,7 +230,7 @@ __device__ __forceinline__ void packets_body(const FrameParams &p)
                 L.work = work;
                 L.gx = gx;
                 L.gy = gy;
-                L.rng = wang_hash(gx + gy * p.width) + (p.frame + frame_offset);  // util.glsl:35-36
+                L.rng = camera_seed(p, gx, gy, frame_offset);
                 L.sample = 0;
                 L.sum = mk(0.0f, 0.0f, 0.0f);
                 begin_sample(L, p);
@@ -433,6 +443,65 @@ __global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_pack
 __global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_packets_aa1_culls(const FrameParams p) { packets_body<true, true, false>(p); }
 __global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_packets_culls_order(const FrameParams p) { packets_body<false, true, true>(p); }
 __global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_packets_aa1_culls_order(const FrameParams p) { packets_body<true, true, true>(p); }
+__global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_packets_aa1_culls_listed(const FrameParams p, const ListedWork w) { packets_body<true, true, false, true>(p, w); }
+
+__global__ void sky_blocks(const FrameParams p, const uint2 *__restrict__ rects, uint32_t n_blocks, uint32_t *__restrict__ sky_bits)
+{
+    __shared__ uint2 lds_rect[kResidentMaxTris];  // (the packet kernel's scenes: n_tris <= kResidentMaxTris)
+    for (uint32_t i = threadIdx.x; i < p.n_tris; i += blockDim.x) lds_rect[i] = rects[i];
+    __syncthreads();
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    bool sky = true;
+    uint32_t gx, gy;
+    if (b < n_blocks && decode_work(p, b << 6, gx, gy)) {  // (the block's first pixel: outside the image = the whole block outside)
+        // the camera round's predicate (packets_body): a candidate is a triangle whose rectangle holds the block; none = the walk is empty and every ray misses
+        const uint32_t bx = gx >> 4, by = gy >> 2;
+        for (uint32_t j = 0; j < p.n_tris && sky; ++j) {
+            const uint2 r = lds_rect[j];
+            sky = !rect_holds(r.x, r.y, bx, by);
+        }
+    }
+    const uint64_t m = ballot(sky);  // a wave's 64 blocks start at a multiple of 64: two whole words
+    const uint32_t w = (b - lane_id()) >> 5, n_words = (n_blocks + 31u) >> 5;
+    if (lane_id() == 0 && w < n_words) sky_bits[w] = static_cast<uint32_t>(m);
+    if (lane_id() == 0 && w + 1u < n_words) sky_bits[w + 1u] = static_cast<uint32_t>(m >> 32);
+}
+
+__global__ void sky_list(const uint32_t *__restrict__ sky_bits, uint32_t n_blocks, uint32_t *__restrict__ list, uint32_t *__restrict__ count)
+{
+    __shared__ uint32_t wave_total[16];
+    const uint32_t n_words = (n_blocks + 31u) >> 5;
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6, n_wave = blockDim.x >> 6;
+    uint32_t base = 0;
+    for (uint32_t w0 = 0; w0 < n_words; w0 += blockDim.x) {  // a word (32 blocks) per thread, the words in order
+        const uint32_t w = w0 + threadIdx.x;
+        uint32_t keep = 0;
+        if (w < n_words) {
+            keep = ~sky_bits[w];
+            if (32u * w + 32u > n_blocks) keep &= (1u << (n_blocks - 32u * w)) - 1u;
+        }
+        // exclusive prefix of the counts over the work-group: within the wave, then the waves before
+        uint32_t incl = static_cast<uint32_t>(__builtin_popcount(keep));
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint32_t y = __shfl_up(incl, off, 64);
+            incl += lane >= off ? y : 0u;
+        }
+        if (lane == 63u) wave_total[wave] = incl;
+        __syncthreads();
+        uint32_t pos = base + incl - static_cast<uint32_t>(__builtin_popcount(keep)), all = 0;
+        for (uint32_t k = 0; k < n_wave; ++k) {
+            pos += k < wave ? wave_total[k] : 0u;
+            all += wave_total[k];
+        }
+        while (keep != 0u) {
+            list[pos++] = 32u * w + static_cast<uint32_t>(__builtin_ctz(keep));
+            keep &= keep - 1u;
+        }
+        base += all;
+        __syncthreads();  // (wave_total is rewritten by the next chunk)
+    }
+    if (threadIdx.x == 0) *count = base;
+}
 
 __global__ void bounce_visibility(const float4 *__restrict__ prep, uint32_t n, double margin, uint32_t words, uint32_t stride, uint32_t *__restrict__ out)
 {

@@ -44,7 +44,8 @@ extern "C" {
                                      selftests, the host-side forms of the device data (rvpt_camera_rects, rvpt_bounce_rows, rvpt_bvh_wide_form,
                                      rvpt_bvh_quant_form), the opt-in walks that measured slower (8-wide, quantised) and the tuning knobs live in the
                                      laboratory build librvpt_hip_debug.so (include/rvpt_hip_lab.h); + rvpt_hip_build_flags, rvpt_hip_get_cull_info,
-                                     rvpt_hip_comm_info */
+                                     rvpt_hip_comm_info.  Still 8, no new symbol: rvpt_hip_upload_scene called with triangles but without nodes and without
+                                     materials — until then always an error — is a GEOMETRY UPDATE (moved vertices, the tree refitted on the device) */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -165,7 +166,33 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
 
 /* Replaces the three scene memcpys the reference repeats every frame (rvpt.cpp:124-126).
  * Call when the scene changes.  `nodes` may be NULL for brute-force contexts.  Triangles must
- * already be in BVH-leaf order (Bvh::permute_primitives, bvh.h:72-79) for BVH contexts. */
+ * already be in BVH-leaf order (Bvh::permute_primitives, bvh.h:72-79) for BVH contexts.
+ *
+ * GEOMETRY UPDATE — the form for a mesh whose vertices move while its topology stays (what the reference's
+ * per-frame triangle copy, rvpt.cpp:124, is for):
+ *
+ *     rvpt_hip_upload_scene(ctx, NULL, 0, tris, n_tris, NULL, 0);      n_tris > 0
+ *
+ * - Legal only after a successful full upload on this context and only with the same n_tris; otherwise
+ *   RVPT_HIP_ERR_INVALID, rvpt_hip_last_error says which, and the stored scene is untouched.  (Without triangles
+ *   the call is what it always was: a full upload of the empty scene.)
+ * - Only the twelve floats vert0..vert2 of every triangle are taken, in the leaf order of the full upload.  The
+ *   stored mat_id rows, the materials and the topology of the tree (every node's first / count words) are kept.
+ * - Every box of the tree is REFITTED on the device: a leaf's box becomes the component-wise min / max over the
+ *   vertices of its triangles, an inner node's box the min / max of its two children's boxes.  min / max of
+ *   floats is exact, so this is the same tree a host refit gives (rvpt_amd/scene.py: refit_bvh), and the context
+ *   renders exactly what a full upload of (refitted nodes, tris, mats) would: images, statistics and tile buffers
+ *   are bit-identical.  A caller's tree with LOOSE boxes therefore becomes TIGHT at the first update, even one
+ *   that moves nothing.  A refit keeps the tree valid, not good: after large deformations a rebuilt tree
+ *   traverses faster (DESIGN.md has the measurement) — rebuild and upload in full now and then.
+ * - Frames in flight finish on the old geometry; `tris` may be freed on return; the accumulate / reset rule stays
+ *   with the caller as for any scene change (set current_frame = 0).  Non-finite vertices are the caller's problem.
+ * - On BVH contexts `tris` may also be DEVICE memory of the context's GPU (a buffer a simulation or a torch
+ *   tensor lives in): the vertices then never visit the host.  The caller makes sure that whatever wrote the
+ *   buffer has finished.  Brute-force contexts compute their scene scale and leaf boxes on the host: a device
+ *   pointer there is RVPT_HIP_ERR_INVALID.
+ * Cost, 1 M triangles: about the 48 MB host-to-device copy; rvpt_bvh_build + a full upload is two orders of
+ * magnitude more. */
 int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes,
                           const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats,
                           size_t n_mats);

@@ -9,7 +9,8 @@ from pathlib import Path
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "librvpt_hip.so"
 SOURCES = [_PKG / "csrc" / n for n in ("rvpt_kernels.hip", "rvpt_packets.hip", "rvpt_bvh4.hip", "rvpt_abi.hip", "bvh_builder.cpp", "bvh_wide.cpp")]
-HEADERS = [_PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
+SOURCES.append(_PKG / "csrc" / "rvpt_refit.hip")  # the geometry update's kernels: no frame kernels, hence not among KERNEL_SOURCES below (kernel_sha stands)
+HEADERS = [_PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
            _PKG / "csrc" / "rvpt_vis.h", _PKG.parent / "include" / "rvpt_hip.h", _PKG.parent / "include" / "rvpt_hip_lab.h"]
 
 # -ffp-contract=off: the arithmetic specification fixes where FMAs happen; applies to the

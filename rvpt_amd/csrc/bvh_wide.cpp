@@ -125,9 +125,10 @@ uint32_t head_of(const Regrouped &r, const rvpt_bvh_node *nodes, uint32_t binary
 // Device layout, width 4: 8 quads (128 B) per wide node — minx[4] maxx[4] miny[4] maxy[4] minz[4] maxz[4] head[4] pad — breadth first (upper levels
 // first: the kernel keeps the first nodes in LDS); head = first | count << head_shift for a leaf (count > 0), the wide index of an inner child (count 0),
 // kWideEmpty for an unused slot.  Returns the wide nodes (empty: no wide form — single-leaf tree, heads that do not pack, not a tree) and the stack need.
-std::vector<float> build_wide_nodes(const rvpt_bvh_node *nodes, size_t n_nodes, uint32_t head_shift, uint32_t &stack_need)
+std::vector<float> build_wide_nodes(const rvpt_bvh_node *nodes, size_t n_nodes, uint32_t head_shift, uint32_t &stack_need, std::vector<uint32_t> *kid_map)
 {
     stack_need = 0;
+    if (kid_map) kid_map->clear();
     std::vector<float> out;
     const Regrouped r = regroup(nodes, n_nodes, head_shift, 4);
     if (!r.ok) return out;
@@ -144,6 +145,11 @@ std::vector<float> build_wide_nodes(const rvpt_bvh_node *nodes, size_t n_nodes, 
             if (hd == kWideFormEmpty) return std::vector<float>();  // (cannot happen below 2^31 nodes; the marker must stay unambiguous)
             heads[i] = hd;
         }
+    }
+    if (kid_map) {
+        kid_map->resize(r.queue.size() * 4);
+        for (size_t w = 0; w < r.queue.size(); ++w)
+            for (int i = 0; i < 4; ++i) (*kid_map)[4 * w + i] = r.kids[w][i];  // (0xFFFFFFFF == kWideFormEmpty: an unused slot)
     }
     stack_need = r.stack_need;
     return out;

@@ -27,6 +27,7 @@
 #include "../../include/rvpt_hip_lab.h"
 #include "rvpt_kernels.h"
 #include "bvh_wide.h"
+#include "rvpt_refit.h"
 #include "rvpt_packets.h"
 #include "rvpt_math.h"
 #include "rvpt_rect.h"
@@ -104,6 +105,12 @@ struct rvpt_hip_ctx {
     size_t n_wide = 0, cap_wide = 0;
     uint32_t wide_stack_levels = 0;  // most slots a depth-first walk of the wide tree can hold at once
     uint32_t bvh_head_shift = 0;  // see FrameParams::head_shift
+    // what a geometry update (upload_scene's update form: same topology, moved vertices) needs from the last full upload: the levels of the breadth-first device
+    // layout as index ranges [begin, end) of d_nodes, root level first (at most kBvhStackDepth of them; empty: no tree, or the caller's layout was kept), and the
+    // binary node behind every child slot of the wide form (4 words per wide node: build_wide_nodes' kid_map)
+    std::vector<std::pair<uint32_t, uint32_t>> refit_levels;
+    uint32_t *d_wide_map = nullptr;
+    size_t cap_wide_map = 0;
     size_t cap_tris = 0, cap_prep = 0, cap_mat_index = 0, cap_mats = 0, cap_nodes = 0;  // allocated elements
     bool have_scene = false;
 
@@ -939,7 +946,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
         }
         if (ctx->trace_stream[i]) (void)hipStreamDestroy(ctx->trace_stream[i]);
     }
-    void *bufs[] = {ctx->d_tris, ctx->d_prep, ctx->d_mats, ctx->d_nodes, ctx->d_wide, ctx->d_mat_index, ctx->d_unit_n, ctx->d_accum,
+    void *bufs[] = {ctx->d_tris, ctx->d_prep, ctx->d_mats, ctx->d_nodes, ctx->d_wide, ctx->d_wide_map, ctx->d_mat_index, ctx->d_unit_n, ctx->d_accum,
                     ctx->d_rowmajor, ctx->d_counter, ctx->d_stats};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -947,12 +954,116 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     delete ctx;
 }
 
+namespace {
+
+// What upload_scene derives from the vertex positions in d_tris, shared by the full upload and the geometry update.
+// The prepared records, the material indices and the hit normals of the n_tris triangles in d_tris (on ctx->stream, behind the copy that filled d_tris):
+static int launch_prepare_triangles(rvpt_hip_ctx *ctx, size_t n_tris)
+{
+    if (n_tris == 0) return 0;
+    const uint32_t n = static_cast<uint32_t>(n_tris);
+    hipLaunchKernelGGL(rv::prepare_triangles, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_tris, n, ctx->d_prep, ctx->d_mat_index, ctx->d_unit_n);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// ... and the bounce cull's table with its scene scale and leaf boxes, for scenes the packet kernel can hold (brute-force contexts, <= kResidentMaxTris triangles);
+// `tris` is the caller's HOST array (only its vertices are read), d_prep already holds its prepared records
+static int derive_bounce_state(rvpt_hip_ctx *ctx, bool bvh, const rvpt_triangle *tris, size_t n_tris)
+{
+    int rc;
+    ctx->vis_words = 0;
+    ctx->scene_scale = 0.0;
+    if (!bvh && n_tris > 0 && n_tris <= rv::kResidentMaxTris) {
+        const double scale = rv::bounce_scene_scale(reinterpret_cast<const float *>(tris), n_tris);
+        if (scale > 0.0) {
+            const uint32_t n = static_cast<uint32_t>(n_tris), words = (n + 31u) / 32u;
+            const uint32_t stride = (words + 3u) & ~3u;  // rows 16-byte aligned and a multiple of four words apart: a bounce round loads four words of a lane's row at once
+            const size_t total = static_cast<size_t>(2) * n * stride;
+            if ((rc = grow(ctx, ctx->d_vis, ctx->vis_cap, total, sizeof(uint32_t)))) return rc;
+            hipLaunchKernelGGL(rv::bounce_visibility, dim3(static_cast<uint32_t>((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_prep, n, rv::kBounceMarginScales * scale, words,
+                               stride, ctx->d_vis);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            ctx->vis_words = words;
+            ctx->scene_scale = scale;
+            // ... and the leaf boxes of the same triangles (host arithmetic on the caller's array; rvpt_vis.h)
+            // (a whole word's boxes — 32 / kLeafTris of them — are requested together: the array is padded to whole words, the padding's triangles do not exist)
+            const size_t n_leaves = static_cast<size_t>(words) * (32u / rv::kLeafTris);
+            std::vector<float> boxes(8 * n_leaves, 0.0f);
+            rv::bounce_leaf_boxes(reinterpret_cast<const float *>(tris), n_tris, scale, boxes.data());
+            if ((rc = grow(ctx, ctx->d_leaf_boxes, ctx->leaf_boxes_cap, 2 * n_leaves, sizeof(float4)))) return rc;
+            HIP_TRY(ctx, hipMemcpy(ctx->d_leaf_boxes, boxes.data(), boxes.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+    }
+    return 0;
+}
+
+// is `p` device memory (hipMalloc: a torch tensor's storage, say)?  Plain host memory is unknown to the runtime, which answers with an error and keeps it as
+// the thread's last error: cleared here.  Pinned and managed memory can be read on the host and count as host memory.
+static bool is_device_pointer(const void *p)
+{
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return attr.type == hipMemoryTypeDevice;
+}
+
+// The update form of rvpt_hip_upload_scene (include/rvpt_hip.h): same triangle count and tree topology as the last full upload, new vertex positions.  Takes the
+// twelve floats vert0..vert2 of every triangle (the stored mat_id rows, the materials and the tree's (first, count) words stay) and recomputes what depends on
+// positions: prepared records and hit normals, the boxes of the binary nodes (level by level, deepest first) and their copies in the wide nodes, the bounce
+// cull's table, scale and leaf boxes.  What depends on topology alone — bvh_height, bvh_head_shift, n_wide, wide_stack_levels, hence the launch choice — stays.
+static int update_geometry(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t n_tris)
+{
+    if (!ctx->have_scene)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "geometry update (no nodes, no materials) before any full upload_scene on this context: there is no scene to update");
+    if (n_tris != ctx->n_tris)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "geometry update with %zu triangles, the uploaded scene has %zu: a full upload_scene changes the count", n_tris, ctx->n_tris);
+    const bool bvh = is_bvh(ctx, n_tris);
+    if (bvh && ctx->refit_levels.empty())  // (the laboratory's knob only: the release library always makes the breadth-first layout and names no laboratory knob)
+#if RVPT_HIP_LAB
+        return fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "geometry update needs the breadth-first device layout of the tree: RVPT_HIP_BVH_CALLER_LAYOUT keeps the caller's, which has no level ranges");
+#else
+        return fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "geometry update needs the level ranges of the tree's device layout, which this context does not hold");
+#endif
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!bvh && is_device_pointer(tris))
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "geometry update of a brute-force context from a device pointer: its scene scale and leaf boxes are computed on the host, pass a host array");
+    if (int rc0 = sync_all(ctx)) return rc0;  // frames in flight finish on the old geometry
+    // 48 of every 64 bytes: the mat_id row of d_tris stays (no index to validate); the source may be host or device memory
+    HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_tris, sizeof(rvpt_triangle), tris, sizeof(rvpt_triangle), offsetof(rvpt_triangle, mat_id), n_tris, hipMemcpyDefault, ctx->stream));
+    if (int rc = launch_prepare_triangles(ctx, n_tris)) return rc;
+    if (bvh) {
+        const uint32_t n_nodes = static_cast<uint32_t>(ctx->n_nodes);
+        for (size_t l = ctx->refit_levels.size(); l-- > 0;) {
+            const auto [begin, end] = ctx->refit_levels[l];
+            hipLaunchKernelGGL(rv::refit_level, dim3((end - begin + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_nodes, begin, end, n_nodes, ctx->d_tris, static_cast<uint32_t>(n_tris));
+        }
+        if (ctx->n_wide) {
+            const uint32_t n_slots = static_cast<uint32_t>(ctx->n_wide * 4);
+            hipLaunchKernelGGL(rv::refit_wide_gather, dim3((n_slots + 255u) / 256u), dim3(256), 0, ctx->stream, reinterpret_cast<float *>(ctx->d_wide), ctx->d_wide_map, n_slots,
+                               ctx->d_nodes, n_nodes);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // caller may free its array on return
+    if (int rc = derive_bounce_state(ctx, bvh, tris, n_tris)) return rc;
+    ctx->scene_gen += 1;  // the slots' screen rectangles and sky lists belong to the old geometry
+    return RVPT_HIP_OK;
+}
+
+}  // namespace
+
 int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes, const rvpt_triangle *tris,
                           size_t n_tris, const rvpt_material *mats, size_t n_mats)
 {
     if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
     if ((n_tris && !tris) || (n_mats && !mats)) return fail(ctx, RVPT_HIP_ERR_INVALID, "NULL scene array");
     if (n_tris > 0x3FFFFFFFull) return fail(ctx, RVPT_HIP_ERR_INVALID, "too many triangles");
+    // the UPDATE FORM: triangles without nodes and without materials (as a full upload it could never succeed: no material index fits n_mats == 0)
+    if (n_tris > 0 && !nodes && n_nodes == 0 && !mats && n_mats == 0) return update_geometry(ctx, tris, n_tris);
     // an EMPTY scene has no tree (RVPT::initialize with no triangles): every ray misses whatever the traversal, and the
     // frame kernels of a BVH context then run the brute-force instance over zero triangles (choose_launch)
     const bool bvh = is_bvh(ctx, n_tris);
@@ -1010,6 +1121,7 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     }
     std::vector<rvpt_bvh_node> device_nodes;  // must outlive the async copy below (stream is synchronised before return)
     size_t n_device_nodes = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> levels;  // the levels of the breadth-first layout as device index ranges (rvpt_hip_ctx::refit_levels)
     if (bvh) {
         // Device layout of the tree (traversal order and results are unchanged): breadth-first, root at 0, slot 1
         // unused, every sibling pair on an even index = one 64-byte line, upper levels first.
@@ -1023,7 +1135,12 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
             queue.reserve(n_nodes);
             queue.emplace_back(0u, 0u);
             uint32_t next_pair = 2;
+            size_t level_end = 0;  // queue entries below this belong to the levels recorded so far
             for (size_t head = 0; head < queue.size(); ++head) {
+                if (head == level_end) {  // the level above has been expanded: what the queue holds from here on is exactly the next level
+                    levels.emplace_back(queue[head].second, queue.back().second + 1u);
+                    level_end = queue.size();
+                }
                 const auto [src, dst] = queue[head];
                 rvpt_bvh_node nd = nodes[src];
                 if (nd.primitive_count == 0) {
@@ -1040,16 +1157,13 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
         if ((rc = grow(ctx, ctx->d_nodes, ctx->cap_nodes, n_device_nodes, sizeof(rvpt_bvh_node)))) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_nodes, device_nodes.data(), n_device_nodes * sizeof(rvpt_bvh_node), hipMemcpyHostToDevice, ctx->stream));
     }
-    if (n_tris) {
-        const uint32_t n = static_cast<uint32_t>(n_tris);
-        hipLaunchKernelGGL(rv::prepare_triangles, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_tris, n, ctx->d_prep, ctx->d_mat_index, ctx->d_unit_n);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    if ((rc = launch_prepare_triangles(ctx, n_tris))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // caller may free its arrays on return
     ctx->n_tris = n_tris;
     ctx->n_mats = n_mats;
     ctx->n_nodes = bvh ? n_device_nodes : 0;
     ctx->bvh_height = bvh_height_tmp;
+    ctx->refit_levels = std::move(levels);
     ctx->bvh_head_shift = 0;
     if (bvh) {  // can a node's (first, count) pair ride in one stack word?  indices below 2^shift, leaf sizes below 2^(32 - shift)
         uint32_t shift = 1, max_count = 0;
@@ -1061,40 +1175,19 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     ctx->wide_stack_levels = 0;
     if (bvh && !ctx->knobs.bvh_caller_layout) {  // the 4-wide form of the tree (breadth-first device layout: children of node i at first, first + 1)
         uint32_t need = 0;
-        const std::vector<float> wide = rv::build_wide_nodes(device_nodes.data(), device_nodes.size(), ctx->bvh_head_shift, need);
+        std::vector<uint32_t> kid_map;
+        const std::vector<float> wide = rv::build_wide_nodes(device_nodes.data(), device_nodes.size(), ctx->bvh_head_shift, need, &kid_map);
         if (!wide.empty() && need <= 4096u && wide.size() / 32 < rv::kWideMaxNodes) {
             const size_t n_wide = wide.size() / 32;
             if ((rc = grow(ctx, ctx->d_wide, ctx->cap_wide, n_wide * 8, sizeof(float4)))) return rc;
             HIP_TRY(ctx, hipMemcpy(ctx->d_wide, wide.data(), wide.size() * sizeof(float), hipMemcpyHostToDevice));
+            if ((rc = grow(ctx, ctx->d_wide_map, ctx->cap_wide_map, kid_map.size(), sizeof(uint32_t)))) return rc;
+            HIP_TRY(ctx, hipMemcpy(ctx->d_wide_map, kid_map.data(), kid_map.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
             ctx->n_wide = n_wide;
             ctx->wide_stack_levels = need;
         }
     }
-    // the bounce cull's table, for scenes the packet kernel can hold (brute-force contexts, <= kResidentMaxTris triangles)
-    ctx->vis_words = 0;
-    ctx->scene_scale = 0.0;
-    if (!bvh && n_tris > 0 && n_tris <= rv::kResidentMaxTris) {
-        const double scale = rv::bounce_scene_scale(reinterpret_cast<const float *>(tris), n_tris);
-        if (scale > 0.0) {
-            const uint32_t n = static_cast<uint32_t>(n_tris), words = (n + 31u) / 32u;
-            const uint32_t stride = (words + 3u) & ~3u;  // rows 16-byte aligned and a multiple of four words apart: a bounce round loads four words of a lane's row at once
-            const size_t total = static_cast<size_t>(2) * n * stride;
-            if ((rc = grow(ctx, ctx->d_vis, ctx->vis_cap, total, sizeof(uint32_t)))) return rc;
-            hipLaunchKernelGGL(rv::bounce_visibility, dim3(static_cast<uint32_t>((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_prep, n, rv::kBounceMarginScales * scale, words,
-                               stride, ctx->d_vis);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            ctx->vis_words = words;
-            ctx->scene_scale = scale;
-            // ... and the leaf boxes of the same triangles (host arithmetic on the caller's array; rvpt_vis.h)
-            // (a whole word's boxes — 32 / kLeafTris of them — are requested together: the array is padded to whole words, the padding's triangles do not exist)
-            const size_t n_leaves = static_cast<size_t>(words) * (32u / rv::kLeafTris);
-            std::vector<float> boxes(8 * n_leaves, 0.0f);
-            rv::bounce_leaf_boxes(reinterpret_cast<const float *>(tris), n_tris, scale, boxes.data());
-            if ((rc = grow(ctx, ctx->d_leaf_boxes, ctx->leaf_boxes_cap, 2 * n_leaves, sizeof(float4)))) return rc;
-            HIP_TRY(ctx, hipMemcpy(ctx->d_leaf_boxes, boxes.data(), boxes.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-    }
+    if ((rc = derive_bounce_state(ctx, bvh, tris, n_tris))) return rc;
     ctx->scene_gen += 1;  // the slots' screen rectangles belong to the old scene
     ctx->have_scene = true;
     return RVPT_HIP_OK;

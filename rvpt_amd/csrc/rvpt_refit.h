@@ -1,0 +1,15 @@
+// rvpt_refit.h — the geometry update's kernels (rvpt_refit.hip), launched by rvpt_hip_upload_scene's update form (rvpt_abi.hip: update_geometry).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace rv {
+
+// the boxes of the binary nodes [begin, end) — one level of the breadth-first device layout — from their triangles (leaves) or their two children (inner
+// nodes); launched level by level, deepest first.  tris: the reference Triangle records (four quads each), nodes: two quads each
+__global__ void refit_level(float4 *__restrict__ nodes, uint32_t begin, uint32_t end, uint32_t n_nodes, const float4 *__restrict__ tris, uint32_t n_tris);
+// ... then the wide nodes' copies of those boxes: map = 4 words per wide node (bvh_wide.h: build_wide_nodes' kid_map), n_slots = 4 x wide nodes
+__global__ void refit_wide_gather(float *__restrict__ wide, const uint32_t *__restrict__ map, uint32_t n_slots, const float4 *__restrict__ nodes, uint32_t n_nodes);
+
+}  // namespace rv

@@ -158,6 +158,32 @@ int main(int argc, char **argv)
     CHECK(g_frames.back().frame == 2 && r.render_settings.current_frame == 6 && g_batched_frames == 5);
     CHECK(step() == 7);
 
+    // moving geometry: update_triangles goes out as the update form (no nodes, no materials), in leaf order, and restarts the accumulation; bvh_nodes() is the refit
+    {
+        RVPT rm(32, 32, opt, fake);
+        std::vector<Triangle> added;
+        for (int k = 0; k < 40; ++k) added.emplace_back(Triangle({float(k), 0, 1}, {float(k) + 1, 0, 1}, {float(k), 1, 1}, 0));
+        for (const Triangle &x : added) rm.add_triangle(x);
+        rm.add_material(m);
+        CHECK(!rm.update_triangles(added));  // before initialize()
+        CHECK(rm.initialize() && g_uploaded_tris == 40 && g_uploaded_nodes >= 3);
+        const std::vector<rvpt_bvh_node> built = rm.bvh_nodes();
+        rm.update(); rm.draw(); rm.update(); rm.draw();
+        CHECK(rm.render_settings.current_frame == 1);
+        CHECK(rm.update_triangles(added) && g_uploaded_tris == 40 && g_uploaded_nodes == 0 && g_uploaded_mats == 0);
+        CHECK(std::memcmp(built.data(), rm.bvh_nodes().data(), built.size() * sizeof(rvpt_bvh_node)) == 0);  // same vertices: the builder's boxes, byte for byte
+        rm.update();
+        CHECK(rm.render_settings.current_frame == 0);
+        std::vector<Triangle> moved = added;
+        for (Triangle &x : moved) x.vertex0[1] -= 2.f, x.vertex1[2] += 3.f;
+        CHECK(rm.update_triangles(moved));
+        const rvpt_bvh_node &root = rm.bvh_nodes()[0];
+        CHECK(root.bounds[2] == -2.f && root.bounds[3] == 1.f && root.bounds[5] == 4.f && root.bounds[0] == 0.f && root.bounds[1] == 40.f);
+        CHECK(rm.sorted_triangles().size() == 40 && rm.bvh_nodes().size() == built.size());
+        moved.pop_back();
+        CHECK(!rm.update_triangles(moved) && !rm.last_error().empty());
+    }
+
     // launch_sizes: as few launches as `batch` allows, near-equal sizes
     {
         using V = std::vector<uint32_t>;

@@ -160,9 +160,12 @@ bool RVPT::initialize()
     // top_level_bvh = bvh_builder.build_bvh(triangles); sorted_triangles = permute_primitives(triangles)  (rvpt.cpp:83-86)
     sorted_.clear();
     nodes_.clear();
+    nodes_stale_ = false;
+    order_.clear();
     if (!triangles_.empty()) {
         nodes_.resize(2 * triangles_.size() - 1);
-        std::vector<uint32_t> order(triangles_.size());
+        std::vector<uint32_t> &order = order_;
+        order.resize(triangles_.size());
         size_t n_nodes = 0;
         if (!check(backend_.bvh_build(reinterpret_cast<const rvpt_triangle *>(triangles_.data()), triangles_.size(), nodes_.data(), &n_nodes,
                                       order.data()),
@@ -181,6 +184,53 @@ bool RVPT::initialize()
                                        reinterpret_cast<const rvpt_triangle *>(sorted_.data()), sorted_.size(),
                                        reinterpret_cast<const rvpt_material *>(materials_.data()), materials_.size()),
                  "rvpt_hip_upload_scene");
+}
+
+bool RVPT::update_triangles(const std::vector<Triangle> &triangles)
+{
+    if (!ctx_) {
+        error_ = "update_triangles before initialize()";
+        return false;
+    }
+    if (triangles.size() != order_.size()) {
+        error_ = "update_triangles: " + std::to_string(triangles.size()) + " triangles given, the scene has " + std::to_string(order_.size());
+        return false;
+    }
+    if (triangles.empty()) return true;
+    std::vector<Triangle> moved;
+    moved.reserve(triangles.size());
+    for (uint32_t i : order_) moved.push_back(triangles[i]);  // leaf order (Bvh::permute_primitives)
+    if (!check(backend_.upload_scene(ctx_, nullptr, 0, reinterpret_cast<const rvpt_triangle *>(moved.data()), moved.size(), nullptr, 0), "rvpt_hip_upload_scene (geometry update)"))
+        return false;
+    triangles_ = triangles;
+    sorted_.swap(moved);
+    nodes_stale_ = true;
+    previous_.valid = false;  // a new scene: nothing accumulated so far belongs to it
+    return true;
+}
+
+// The refit the device made, on the host: leaf boxes from the triangles, inner boxes from the two children.  rvpt_bvh_build puts children behind their parent,
+// so one pass from the last node to the first sees every child before its parent.
+const std::vector<rvpt_bvh_node> &RVPT::bvh_nodes() const
+{
+    if (nodes_stale_) {
+        for (size_t i = nodes_.size(); i-- > 0;) {
+            rvpt_bvh_node &n = nodes_[i];
+            float lo[3], hi[3];
+            if (n.primitive_count > 0) {
+                for (int k = 0; k < 3; ++k) lo[k] = hi[k] = sorted_[n.first_child_or_primitive].vertex0[k];
+                for (uint32_t t = n.first_child_or_primitive; t < n.first_child_or_primitive + n.primitive_count; ++t)
+                    for (const float *v : {sorted_[t].vertex0, sorted_[t].vertex1, sorted_[t].vertex2})
+                        for (int k = 0; k < 3; ++k) lo[k] = std::fmin(lo[k], v[k]), hi[k] = std::fmax(hi[k], v[k]);
+            } else {
+                const rvpt_bvh_node &l = nodes_[n.first_child_or_primitive], &r = nodes_[n.first_child_or_primitive + 1];
+                for (int k = 0; k < 3; ++k) lo[k] = std::fmin(l.bounds[2 * k], r.bounds[2 * k]), hi[k] = std::fmax(l.bounds[2 * k + 1], r.bounds[2 * k + 1]);
+            }
+            for (int k = 0; k < 3; ++k) n.bounds[2 * k] = lo[k], n.bounds[2 * k + 1] = hi[k];
+        }
+        nodes_stale_ = false;
+    }
+    return nodes_;
 }
 
 bool RVPT::update()

@@ -123,6 +123,10 @@ public:
 
     void add_material(Material material);  // rvpt.cpp:1041
     void add_triangle(Triangle triangle);  // rvpt.cpp:1043
+    // Moving geometry — what the per-frame triangle copy of rvpt.cpp:124 is for: `triangles` (in the order they were ADDED, same count) replace the scene's.  The
+    // tree keeps its topology and is refitted on the device (the update form of rvpt_hip_upload_scene: no nodes, no materials), no rebuild; the next update()
+    // restarts the accumulation.  After initialize() only.
+    bool update_triangles(const std::vector<Triangle> &triangles);
 
     // RGBA32F (width*height*4 floats) or RGBA8 (width*height*4 bytes), row-major, top row first
     std::vector<float> read_frame();
@@ -136,7 +140,7 @@ public:
     RenderSettings render_settings;
 
     // what initialize() derived (rvpt.h:175-179: top_level_bvh, sorted_triangles)
-    const std::vector<rvpt_bvh_node> &bvh_nodes() const { return nodes_; }
+    const std::vector<rvpt_bvh_node> &bvh_nodes() const;  // (after update_triangles: refitted on the host when first asked for)
     const std::vector<Triangle> &sorted_triangles() const { return sorted_; }
     const std::vector<Material> &materials() const { return materials_; }
 
@@ -148,7 +152,9 @@ private:
     rvpt_hip_ctx *ctx_ = nullptr;
     std::vector<Triangle> triangles_, sorted_;
     std::vector<Material> materials_;
-    std::vector<rvpt_bvh_node> nodes_;
+    mutable std::vector<rvpt_bvh_node> nodes_;
+    mutable bool nodes_stale_ = false;  // update_triangles moved the geometry under nodes_' boxes
+    std::vector<uint32_t> order_;       // primitive indices of the build: sorted_[i] = triangles_[order_[i]]
     // PreviousFrameState (rvpt.h:211-219, rvpt.cpp:21-29); empty camera data never compares equal
     struct Previous {
         bool valid = false;

@@ -300,7 +300,9 @@ class Context:
         self._L = load_lab() if self.lab else load()
         self._h = C.c_void_p(None)
         self.width, self.height = int(width), int(height)
+        self.device = int(device)
         self.tile_rank, self.tile_world, self.flags = int(tile_rank), int(tile_world), int(flags)
+        self._scene_tris = None  # triangles of the last successful full upload (update_triangles)
         _check(self._L.rvpt_hip_create(C.byref(self._h), device, width, height, tile_rank, tile_world, flags), None, self._L)
 
     def close(self) -> None:
@@ -319,6 +321,37 @@ class Context:
             n_nodes = nodes.nbytes // 32
         _check(self._L.rvpt_hip_upload_scene(self._h, _ptr(nodes), n_nodes, _ptr(tris), tris.shape[0], _ptr(mats),
                                              mats.shape[0]), self._h, self._L)
+        self._scene_tris = tris.shape[0]
+
+    def update_triangles(self, tris) -> None:
+        """The update form of rvpt_hip_upload_scene (include/rvpt_hip.h): the scene's triangles have moved — same count, same leaf order, same tree topology as
+        the last upload_scene.  Only vert0..vert2 are taken; material rows, materials and the tree's structure stay, every box of the tree is refitted on the
+        device (scene.refit_bvh is the same on the host).  Frames in flight finish on the old geometry; restarting the accumulation is the caller's business.
+        tris: float32[n, 16], a numpy array or — BVH contexts — a contiguous torch tensor on this context's device, which never visits the host."""
+        ptr = None
+        if not isinstance(tris, np.ndarray) and hasattr(tris, "data_ptr"):  # a torch tensor
+            import torch
+            if tris.dtype != torch.float32 or tris.dim() != 2 or tris.shape[1] != 16 or not tris.is_contiguous():
+                raise NativeError(ERR_INVALID, f"update_triangles: a contiguous float32 tensor [n, 16] is needed, got {tris.dtype} {tuple(tris.shape)}")
+            if tris.is_cuda:
+                if tris.device.index != self.device:
+                    raise NativeError(ERR_INVALID, f"update_triangles: the tensor lives on device {tris.device.index}, the context on {self.device}")
+                torch.cuda.current_stream(tris.device).synchronize()  # the library copies on its own stream: what produced the tensor must have finished
+                ptr, n, keep = C.c_void_p(tris.data_ptr()), int(tris.shape[0]), tris
+            else:
+                tris = tris.numpy()
+        if ptr is None:
+            tris = np.asarray(tris)
+            if tris.dtype != np.float32 or tris.ndim != 2 or tris.shape[1] != 16:
+                raise NativeError(ERR_INVALID, f"update_triangles: float32[n, 16] is needed, got {tris.dtype} {tris.shape}")
+            keep = tris = np.ascontiguousarray(tris)
+            ptr, n = _ptr(tris), tris.shape[0]
+        if n == 0:  # (in the C form a call without triangles is a full upload of the empty scene)
+            if self._scene_tris != 0:
+                raise NativeError(ERR_INVALID, "update_triangles: no triangles given" + (" before any upload_scene" if self._scene_tris is None else f", the uploaded scene has {self._scene_tris}"))
+            return
+        _check(self._L.rvpt_hip_upload_scene(self._h, None, 0, ptr, n, None, 0), self._h, self._L)
+        del keep
 
     def set_frame(self, settings: np.ndarray, camera: np.ndarray) -> None:
         settings = np.ascontiguousarray(settings)

@@ -15,7 +15,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import native
+from . import native, scene
 from .camera import Camera
 
 
@@ -78,7 +78,8 @@ class RVPT:
         self.render_settings = RenderSettings()
         self.triangles: list[np.ndarray] = []
         self.materials: list[np.ndarray] = []
-        self.bvh_nodes: np.ndarray | None = None
+        self._bvh_nodes: np.ndarray | None = None
+        self._nodes_stale = False  # update_triangles moved the geometry: bvh_nodes is refitted when it is next asked for
         self.primitive_indices: np.ndarray | None = None
         self.sorted_triangles: np.ndarray | None = None
         self._previous_key = None  # default-constructed PreviousFrameState never compares equal (empty camera data)
@@ -93,6 +94,33 @@ class RVPT:
 
     def add_triangles(self, triangles) -> None:
         self.triangles.append(np.asarray(triangles, dtype=np.float32).reshape(-1, 16))
+
+    @property
+    def bvh_nodes(self):
+        """top_level_bvh (rvpt.h:175): the tree initialize() built; after update_triangles its refit (scene.refit_bvh), made when first asked for."""
+        if self._nodes_stale:
+            self._bvh_nodes = scene.refit_bvh(self._bvh_nodes, self.sorted_triangles)
+            self._nodes_stale = False
+        return self._bvh_nodes
+
+    @bvh_nodes.setter
+    def bvh_nodes(self, nodes) -> None:
+        self._bvh_nodes, self._nodes_stale = nodes, False
+
+    def update_triangles(self, triangles) -> None:
+        """Moving geometry — what the per-frame triangle copy of rvpt.cpp:124 is for: `triangles` (float32[n, 16], in the order they were ADDED, same count) replace
+        the scene's; the tree keeps its topology and is refitted on the device (Context.update_triangles), no rebuild.  The next update() restarts the accumulation."""
+        tris = np.asarray(triangles, dtype=np.float32).reshape(-1, 16)
+        if self._ctx is None or self.primitive_indices is None:
+            raise RuntimeError("update_triangles before initialize()")
+        if tris.shape[0] != self.primitive_indices.shape[0]:
+            raise native.NativeError(native.ERR_INVALID, f"update_triangles: {tris.shape[0]} triangles given, the scene has {self.primitive_indices.shape[0]}")
+        sorted_tris = tris[self.primitive_indices]  # leaf order (Bvh::permute_primitives)
+        self._ctx.update_triangles(sorted_tris)
+        self.triangles = [tris.copy()]
+        self.sorted_triangles = sorted_tris
+        self._nodes_stale = self._bvh_nodes is not None
+        self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
 
     # -- lifecycle -----------------------------------------------------------------------------------------
     def initialize(self) -> bool:

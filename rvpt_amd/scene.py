@@ -43,6 +43,73 @@ def make_material(albedo, emission, mtype: int) -> np.ndarray:
     return m
 
 
+NODE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("bounds", "<f4", (6,))])  # rvpt_bvh_node (== native.NODE_DTYPE)
+
+
+def refit_bvh(nodes, tris) -> np.ndarray:
+    """The normative refit of a tree whose triangles moved (the host statement of what rvpt_hip_upload_scene's update form does on the device): topology
+    (`first`, `count`) kept, a leaf's box = component-wise min / max over the vertices of its triangles, an inner node's box = min / max of its two
+    children's boxes.  min / max of floats is exact, so the result does not depend on the order of evaluation (up to the sign of a zero) and a tree whose
+    boxes were tight comes back byte for byte; loose boxes become tight.
+
+    nodes: uint32[n, 8] (native.build_bvh) or NODE_DTYPE records, root at 0, children of an inner node at first, first + 1, leaf iff count > 0;
+    tris: float32[m, 16] in the leaf order the tree indexes.  Returns a new array in the form of `nodes`; nodes the root does not reach are left as they are.
+    Iterative (level by level), a few seconds for the 1.5 M nodes of the 1 M-triangle terrain."""
+    src = np.ascontiguousarray(nodes)
+    out = src.copy()
+    rec = out.view(NODE_DTYPE).reshape(-1)
+    n = rec.shape[0]
+    v = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 4, 4)[:, :3, :3]
+    first, count = rec["first"].astype(np.int64), rec["count"].astype(np.int64)
+    if n == 0:
+        return out
+    # the levels of the tree, root first
+    levels, frontier, seen = [], np.zeros(1, dtype=np.int64), 1
+    while frontier.size:
+        levels.append(frontier)
+        inner = frontier[count[frontier] == 0]
+        if inner.size and int(first[inner].max()) + 1 >= n:
+            raise ValueError("refit_bvh: child index outside the node array")
+        frontier = np.stack([first[inner], first[inner] + 1], axis=1).reshape(-1)
+        seen += frontier.size
+        if seen > n:
+            raise ValueError("refit_bvh: not a tree (a node is reachable twice)")
+    lo = np.empty((n, 3), dtype=np.float32)
+    hi = np.empty((n, 3), dtype=np.float32)
+    leaves = np.concatenate([l[count[l] > 0] for l in levels])
+    if leaves.size:
+        if int((first[leaves] + count[leaves]).max()) > v.shape[0]:
+            raise ValueError("refit_bvh: leaf range outside the triangle array")
+        tlo, thi = v.min(axis=1), v.max(axis=1)
+        lo[leaves], hi[leaves] = tlo[first[leaves]], thi[first[leaves]]
+        for k in range(1, int(count[leaves].max())):  # the k-th triangle of every leaf that has one
+            more = leaves[count[leaves] > k]
+            lo[more] = np.minimum(lo[more], tlo[first[more] + k])
+            hi[more] = np.maximum(hi[more], thi[first[more] + k])
+    for level in reversed(levels):
+        inner = level[count[level] == 0]
+        lo[inner] = np.minimum(lo[first[inner]], lo[first[inner] + 1])
+        hi[inner] = np.maximum(hi[first[inner]], hi[first[inner] + 1])
+    reached = np.concatenate(levels)
+    b = rec["bounds"]
+    b[reached, 0::2], b[reached, 1::2] = lo[reached], hi[reached]
+    return out
+
+
+def wobble(tris, phase: float, amplitude: float) -> np.ndarray:
+    """A smooth deformation for moving-geometry demos, tests and tools/refit_bench.py: every vertex is displaced by a function of its own position and `phase`
+    alone (three sines of the other two coordinates), so vertices that coincide stay welded; |displacement| <= amplitude * sqrt(3).  The .w lanes and the
+    material row are kept.  float32[n, 16] -> float32[n, 16]."""
+    t = np.array(tris, dtype=np.float32).reshape(-1, 16)
+    p = t.reshape(-1, 4, 4)[:, :3, :3].astype(np.float64)
+    ext = float(np.ptp(p.reshape(-1, 3), axis=0).max()) or 1.0
+    k = 2.0 * np.pi / ext
+    d = np.stack([np.sin(1.3 * k * p[..., 1] + 0.7 * k * p[..., 2] + phase), np.sin(0.9 * k * p[..., 2] + 1.1 * k * p[..., 0] + 1.7 * phase),
+                  np.sin(1.2 * k * p[..., 0] + 0.8 * k * p[..., 1] + 2.3 * phase)], axis=-1)
+    t.reshape(-1, 4, 4)[:, :3, :3] = (p + amplitude * d).astype(np.float32)
+    return t
+
+
 def load_obj_positions(path) -> np.ndarray:
     """Minimal Wavefront OBJ reader: `v` records and `f` records (v, v/vt, v/vt/vn, v//vn, negative
     indices); polygons are fan-triangulated (tinyobjloader's default `triangulate=true`, which is

@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Run on the GPU box: what a pose change of the 1 M-triangle terrain costs (BVH context, 1920x1080) by the update form of rvpt_hip_upload_scene against the
+only route there was before it — rvpt_bvh_build + a full upload_scene — and against the floor, a bare host-to-device copy of the same 48 MB; then what
+traversal pays on a refitted tree against a freshly built one.  -> stdout (profiles/refit_update.txt)
+usage: tools/refit_bench.py [all|updates]     (updates: one upload and a few updates, nothing else — the run to put under rocprofv3 --kernel-trace --stats)"""
+import statistics, sys, time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+from rvpt_amd import Camera, RenderSettings, native, scene  # noqa: E402
+
+what = sys.argv[1] if len(sys.argv) > 1 else "all"
+W, H = 1920, 1080
+
+
+def spread(xs):
+    return f"median {statistics.median(xs) * 1e3:9.3f} ms   min {min(xs) * 1e3:9.3f}   max {max(xs) * 1e3:9.3f}   n {len(xs)}"
+
+
+def timed(fn, reps, warm=1):
+    for _ in range(warm):
+        fn()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        out.append(time.perf_counter() - t0)
+    return out
+
+
+def frame_rate(ctx, cam, frames=24, reps=5):
+    """Msamples/s of one-frame launches (a moving mesh leaves nothing to batch), wall clock over `frames` frames, best-of and median of `reps`"""
+    def run():
+        for f in range(frames):
+            ctx.set_frame(RenderSettings(current_frame=f).pack(), cam)
+            ctx.dispatch()
+        ctx.wait()
+    ts = timed(run, reps)
+    return [W * H * frames / t / 1e6 for t in ts]
+
+
+tris0, mats = scene.heightfield_scene()
+ext = float(np.ptp(tris0.reshape(-1, 4, 4)[:, :3, :3].reshape(-1, 3), axis=0).max())
+t0 = time.perf_counter()
+nodes, idx = native.build_bvh(tris0)
+print(f"scene: {tris0.shape[0]} triangles, {nodes.shape[0]} nodes, extent {ext:.2f}; first rvpt_bvh_build {(time.perf_counter() - t0) * 1e3:.0f} ms (cold)")
+tris = tris0[idx]
+c = Camera(W / H)
+c.translation = np.array([0.0, 2.5, -5.0])
+c.rotation = np.array([0.0, 25.0, 0.0])
+cam = c.get_data()
+poses = [scene.wobble(tris, 0.5 + 0.9 * k, 0.02 * ext) for k in range(4)]  # in leaf order
+ctx = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BVH)
+ctx.upload_scene(nodes, tris, mats)
+
+if what == "updates":
+    for k in range(8):
+        ctx.update_triangles(poses[k % 4])
+    ctx.close()
+    print("8 updates done")
+    sys.exit(0)
+
+print("\n== cost of a pose change (wall clock, host call to return; the caller's array may be freed on return) ==")
+k = [0]
+def update():
+    ctx.update_triangles(poses[k[0] % 4]); k[0] += 1
+upd = timed(update, 20, warm=3)
+print(f"update form (host numpy array)        {spread(upd)}")
+
+import torch  # noqa: E402
+dev_poses = [torch.from_numpy(p).to("cuda:0") for p in poses[:2]]
+def update_dev():
+    ctx.update_triangles(dev_poses[k[0] % 2]); k[0] += 1
+upd_dev = timed(update_dev, 20, warm=3)
+print(f"update form (torch tensor on device)  {spread(upd_dev)}    <- prepare_triangles + level sweep + wide gather + a device copy")
+
+unsorted = [tris0.copy() for _ in range(2)]
+for u, p in zip(unsorted, poses):
+    u[idx] = p  # the pose in the order the triangles were added: what a caller without the update form starts from
+def rebuild():
+    u = unsorted[k[0] % 2]; k[0] += 1
+    n2, i2 = native.build_bvh(u)
+    ctx.upload_scene(n2, u[i2], mats)
+def rebuild_parts():
+    u = unsorted[k[0] % 2]; k[0] += 1
+    a = time.perf_counter(); n2, i2 = native.build_bvh(u)
+    b = time.perf_counter(); s = u[i2]
+    c_ = time.perf_counter(); ctx.upload_scene(n2, s, mats)
+    return b - a, c_ - b, time.perf_counter() - c_
+base = timed(rebuild, 5, warm=1)
+parts = [rebuild_parts() for _ in range(3)]
+print(f"baseline: rvpt_bvh_build + upload     {spread(base)}")
+print("          of which build / permute / upload_scene (ms): " + "; ".join(f"{a * 1e3:.0f} / {b * 1e3:.0f} / {c_ * 1e3:.0f}" for a, b, c_ in parts))
+def refit_route():
+    p = poses[k[0] % 4]; k[0] += 1
+    ctx.upload_scene(scene.refit_bvh(nodes, p), p, mats)
+print(f"numpy refit_bvh + full upload         {spread(timed(refit_route, 3, warm=0))}")
+
+dst48 = torch.empty(tris.shape[0] * 48, dtype=torch.uint8, device="cuda:0")
+dst64 = torch.empty(tris.shape[0] * 64, dtype=torch.uint8, device="cuda:0")
+src48 = torch.from_numpy(np.frombuffer(np.random.RandomState(1).bytes(tris.shape[0] * 48), dtype=np.uint8).copy())  # pageable, like a numpy array
+src64 = torch.from_numpy(poses[0].view(np.uint8).reshape(-1))
+def copy48():
+    dst48.copy_(src48); torch.cuda.synchronize()
+def copy64():
+    dst64.copy_(src64); torch.cuda.synchronize()
+fl48, fl64 = timed(copy48, 20, warm=3), timed(copy64, 20, warm=3)
+print(f"floor: flat H2D copy of 48 MB         {spread(fl48)}    (pageable host memory, {tris.shape[0] * 48 / 1e6 / statistics.median(fl48) / 1e3:.1f} GB/s)")
+print(f"       flat H2D copy of 64 MB         {spread(fl64)}")
+m_u, m_d, m_b, m_f = (statistics.median(x) for x in (upd, upd_dev, base, fl48))
+print(f"summary: update {m_u * 1e3:.2f} ms = {m_b / m_u:.0f} x faster than rebuild + upload ({m_b * 1e3:.0f} ms), {m_u / m_f:.2f} x the 48 MB copy floor ({m_f * 1e3:.2f} ms); "
+      f"the device-side part (device source) {m_d * 1e3:.2f} ms, so the strided host copy holds about {(m_u - m_d) * 1e3:.2f} ms")
+
+print("\n== what refitting costs in traversal: the same deformed geometry on the refitted tree and on a freshly built one (one-frame launches, Msamples/s) ==")
+ctx.upload_scene(nodes, tris, mats)
+r0 = frame_rate(ctx, cam)
+print(f"undeformed, built tree                     median {statistics.median(r0):8.0f}   min {min(r0):8.0f}   max {max(r0):8.0f}")
+for amp in (0.02, 0.1):
+    pose = scene.wobble(tris, 1.4, amp * ext)
+    ctx.upload_scene(nodes, tris, mats)
+    ctx.update_triangles(pose)
+    a = frame_rate(ctx, cam)
+    u = tris0.copy(); u[idx] = pose
+    n2, i2 = native.build_bvh(u)
+    ctx.upload_scene(n2, u[i2], mats)
+    b = frame_rate(ctx, cam)
+    print(f"amplitude {amp:4.2f} x extent: refitted tree    median {statistics.median(a):8.0f}   min {min(a):8.0f}   max {max(a):8.0f}")
+    print(f"                         rebuilt tree     median {statistics.median(b):8.0f}   min {min(b):8.0f}   max {max(b):8.0f}    refit / rebuilt = {statistics.median(a) / statistics.median(b):.3f}")
+ctx.close()

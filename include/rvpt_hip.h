@@ -45,7 +45,9 @@ extern "C" {
                                      rvpt_bvh_quant_form), the opt-in walks that measured slower (8-wide, quantised) and the tuning knobs live in the
                                      laboratory build librvpt_hip_debug.so (include/rvpt_hip_lab.h); + rvpt_hip_build_flags, rvpt_hip_get_cull_info,
                                      rvpt_hip_comm_info.  Still 8, no new symbol: rvpt_hip_upload_scene called with triangles but without nodes and without
-                                     materials — until then always an error — is a GEOMETRY UPDATE (moved vertices, the tree refitted on the device) */
+                                     materials — until then always an error — is a GEOMETRY UPDATE (moved vertices, the tree refitted on the device).  Still 8,
+                                     no new symbol: on a BVH context, no nodes and the count RVPT_HIP_NODES_BUILD — until then the "needs nodes" error —
+                                     is the BUILD FORM (the library builds the tree on the device from the triangles alone) */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -192,7 +194,31 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  *   buffer has finished.  Brute-force contexts compute their scene scale and leaf boxes on the host: a device
  *   pointer there is RVPT_HIP_ERR_INVALID.
  * Cost, 1 M triangles: about the 48 MB host-to-device copy; rvpt_bvh_build + a full upload is two orders of
- * magnitude more. */
+ * magnitude more.
+ *
+ * BUILD FORM — the library builds the tree, on the device, from the triangles alone:
+ *
+ *     rvpt_hip_upload_scene(ctx, NULL, RVPT_HIP_NODES_BUILD, tris, n_tris, mats, n_mats);
+ *
+ * - BVH contexts: a full upload whose tree is an LBVH made on the GPU (30-bit Morton codes of the centroids, a radix
+ *   sort, leaves of at most two triangles; rvpt_amd/csrc/rvpt_build.h holds the definition, rvpt_amd/scene.py:
+ *   build_lbvh is the same tree in numpy).  Brute-force contexts ignore nodes and n_nodes as they always have: there
+ *   the call is the ordinary upload.  n_tris == 0 is the empty scene.
+ * - `tris` arrive in the CALLER'S order, any order.  The library sorts its own copy and keeps the permutation.
+ * - On BVH contexts `tris` may be device memory of the context's GPU, as in the update form; the material indices
+ *   are then validated by a kernel.  A bad index is RVPT_HIP_ERR_INVALID naming the first offending triangle and
+ *   leaves the stored scene untouched, for host and device sources alike.
+ * - A second build-form call is a rebuild.  Frames in flight finish on the old scene.
+ * - Only a bad material index is atomic.  Any other failure of a build (a HIP error, an allocation that fails, a tree
+ *   higher than the traversal stack — which the definition rules out below 2^30 triangles) leaves the context WITHOUT a
+ *   scene: the next call must be a full upload or another build form.
+ * - The UPDATE FORM after a build form takes the triangles in that same caller's order (the vertex rows are gathered
+ *   through the stored permutation); after an ordinary full upload it takes the leaf order of that upload, as above.
+ * An LBVH is quick to build and traverses slower than the binned-SAH tree of rvpt_bvh_build: measured on one MI355X
+ * (profiles/device_build.txt), 1 M triangles build in 4.5 ms from a host array and 1.8 ms from device memory against
+ * 338 ms for rvpt_bvh_build + a full upload, and one-frame launches at 1080p run at 0.54 - 0.72 of the SAH tree's rate
+ * — the number a caller chooses by (DESIGN.md 5.6 has the table and the frame counts at which a host build pays). */
+#define RVPT_HIP_NODES_BUILD ((size_t)-1)
 int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes,
                           const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats,
                           size_t n_mats);

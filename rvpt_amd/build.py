@@ -10,7 +10,8 @@ _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "librvpt_hip.so"
 SOURCES = [_PKG / "csrc" / n for n in ("rvpt_kernels.hip", "rvpt_packets.hip", "rvpt_bvh4.hip", "rvpt_abi.hip", "bvh_builder.cpp", "bvh_wide.cpp")]
 SOURCES.append(_PKG / "csrc" / "rvpt_refit.hip")  # the geometry update's kernels: no frame kernels, hence not among KERNEL_SOURCES below (kernel_sha stands)
-HEADERS = [_PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
+SOURCES.append(_PKG / "csrc" / "rvpt_build.hip")  # the device BVH build's kernels (upload_scene's build form): likewise outside KERNEL_SOURCES
+HEADERS = [_PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
            _PKG / "csrc" / "rvpt_vis.h", _PKG.parent / "include" / "rvpt_hip.h", _PKG.parent / "include" / "rvpt_hip_lab.h"]
 
 # -ffp-contract=off: the arithmetic specification fixes where FMAs happen; applies to the
@@ -88,14 +89,26 @@ def build_native_debug(force: bool = False) -> Path:
     return DEBUG_LIB_PATH
 
 
+def build_leaf_variant(leaf_tris: int) -> Path:
+    """The release library with another leaf size of the device BVH build (-DRVPT_LBVH_LEAF_TRIS, rvpt_build.h): rvpt_amd/librvpt_hip_leaf<L>.so, for the
+    leaf-size sweep of tools/build_bench.py (RVPT_HIP_LIB=<that file> LEAF_TRIS=<L> tools/build_bench.py traversal)."""
+    out = _PKG / f"librvpt_hip_leaf{int(leaf_tris)}.so"
+    cmd = [hipcc(), *FLAGS, f"-DRVPT_LBVH_LEAF_TRIS={int(leaf_tris)}", *map(str, SOURCES), "-o", str(out)]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + res.stdout + res.stderr)
+    return out
+
+
 HOST_DIR = _PKG / "host"
 HOST_BIN_DIR = _PKG / "bin"  # git-ignored build outputs (travel to the GPU box with the snapshot)
-HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selftest": ["host_selftest.cpp", "rvpt_host.cpp"]}
+HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selftest": ["host_selftest.cpp", "rvpt_host.cpp"],
+                "host_selftest_build": ["host_selftest_build.cpp", "rvpt_host.cpp"]}
 
 
 def build_host(force: bool = False) -> Path:
     """Compile the C++ host layer (rvpt_amd/host/: the mirror of the reference's class RVPT above the C ABI) with
-    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`."""
+    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest` and `host_selftest_build`."""
     build_native()
     HOST_BIN_DIR.mkdir(exist_ok=True)
     srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h"]
@@ -112,7 +125,9 @@ def build_host(force: bool = False) -> Path:
     return HOST_BIN_DIR
 
 
-if __name__ == "__main__":
+if __name__ == "__main__" and len(__import__("sys").argv) > 2 and __import__("sys").argv[1] == "--leaf-variant":
+    print(build_leaf_variant(int(__import__("sys").argv[2])))  # python -m rvpt_amd.build --leaf-variant 4
+elif __name__ == "__main__":
     print(build_native(force=True, verbose=True))
     print(build_native_debug(force=True))
     print(build_host(force=True))

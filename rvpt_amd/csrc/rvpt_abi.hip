@@ -28,6 +28,7 @@
 #include "rvpt_kernels.h"
 #include "bvh_wide.h"
 #include "rvpt_refit.h"
+#include "rvpt_build.h"
 #include "rvpt_packets.h"
 #include "rvpt_math.h"
 #include "rvpt_rect.h"
@@ -112,6 +113,15 @@ struct rvpt_hip_ctx {
     uint32_t *d_wide_map = nullptr;
     size_t cap_wide_map = 0;
     size_t cap_tris = 0, cap_prep = 0, cap_mat_index = 0, cap_mats = 0, cap_nodes = 0;  // allocated elements
+    // the BUILD FORM of upload_scene (rvpt_build.h; build_scene_on_device below): the permutation it sorted the caller's triangles by (perm[j] = caller's index of
+    // leaf-order triangle j; have_perm: the stored scene came from a build form, so the update form takes the caller's order), the scratch of the level loops
+    // (keys, ranges, flags, offsets: 32 bytes per triangle), rocPRIM's temporary storage, eight counters and their pinned host copy
+    uint32_t *d_perm = nullptr;
+    size_t cap_perm = 0;
+    bool have_perm = false;
+    unsigned char *d_build = nullptr, *d_build_temp = nullptr;
+    size_t cap_build = 0, cap_build_temp = 0;
+    uint32_t *d_build_counters = nullptr, *h_build_words = nullptr;
     bool have_scene = false;
 
     rvpt_render_settings settings{};
@@ -919,6 +929,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
         if (ctx->sky_read[i]) (void)hipEventDestroy(ctx->sky_read[i]);
     }
     if (ctx->h_sky_count) (void)hipHostFree(ctx->h_sky_count);
+    if (ctx->h_build_words) (void)hipHostFree(ctx->h_build_words);
     if (ctx->d_timeline && !ctx->knobs.timeline_path.empty()) {  // debugging aid: dump the last frame's wave timeline
         std::vector<unsigned long long> h(ctx->timeline_words);
         if (hipMemcpy(h.data(), ctx->d_timeline, ctx->timeline_words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -947,7 +958,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
         if (ctx->trace_stream[i]) (void)hipStreamDestroy(ctx->trace_stream[i]);
     }
     void *bufs[] = {ctx->d_tris, ctx->d_prep, ctx->d_mats, ctx->d_nodes, ctx->d_wide, ctx->d_wide_map, ctx->d_mat_index, ctx->d_unit_n, ctx->d_accum,
-                    ctx->d_rowmajor, ctx->d_counter, ctx->d_stats};
+                    ctx->d_rowmajor, ctx->d_counter, ctx->d_stats, ctx->d_perm, ctx->d_build, ctx->d_build_temp, ctx->d_build_counters};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1033,7 +1044,16 @@ static int update_geometry(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t 
         return fail(ctx, RVPT_HIP_ERR_INVALID, "geometry update of a brute-force context from a device pointer: its scene scale and leaf boxes are computed on the host, pass a host array");
     if (int rc0 = sync_all(ctx)) return rc0;  // frames in flight finish on the old geometry
     // 48 of every 64 bytes: the mat_id row of d_tris stays (no index to validate); the source may be host or device memory
-    HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_tris, sizeof(rvpt_triangle), tris, sizeof(rvpt_triangle), offsetof(rvpt_triangle, mat_id), n_tris, hipMemcpyDefault, ctx->stream));
+    if (ctx->have_perm) {  // the stored scene came from a build form: `tris` are in the CALLER'S order and go through the permutation the build kept
+        const float4 *src = reinterpret_cast<const float4 *>(tris);
+        if (!is_device_pointer(tris)) {  // staged in d_prep, which prepare_triangles rewrites below
+            HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_prep, sizeof(rvpt_triangle), tris, sizeof(rvpt_triangle), offsetof(rvpt_triangle, mat_id), n_tris, hipMemcpyHostToDevice, ctx->stream));
+            src = ctx->d_prep;
+        }
+        HIP_TRY(ctx, rv::build_gather_vertices(ctx->stream, src, ctx->d_perm, static_cast<uint32_t>(n_tris), ctx->d_tris));
+    } else {
+        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_tris, sizeof(rvpt_triangle), tris, sizeof(rvpt_triangle), offsetof(rvpt_triangle, mat_id), n_tris, hipMemcpyDefault, ctx->stream));
+    }
     if (int rc = launch_prepare_triangles(ctx, n_tris)) return rc;
     if (bvh) {
         const uint32_t n_nodes = static_cast<uint32_t>(ctx->n_nodes);
@@ -1054,6 +1074,175 @@ static int update_geometry(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t 
     return RVPT_HIP_OK;
 }
 
+// The BUILD FORM of rvpt_hip_upload_scene (include/rvpt_hip.h; BVH contexts): triangles in the caller's order and materials, no nodes — the tree is built on
+// the device (rvpt_build.h: the specification of the tree and the stages).  It is born in the breadth-first layout the full upload makes on the host, with its
+// level table, its height and its 4-wide form; the host reads one word per level.  `tris` may be host memory or device memory of the context's GPU.
+static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats, size_t n_mats)
+{
+    int rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t n = static_cast<uint32_t>(n_tris);
+    const bool device_source = is_device_pointer(tris);
+    size_t cap_counters = ctx->d_build_counters ? rv::kBuildCounters : 0;
+    if ((rc = grow(ctx, ctx->d_build_counters, cap_counters, rv::kBuildCounters, sizeof(uint32_t)))) return rc;
+    if (!ctx->h_build_words) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_build_words), rv::kBuildCounters * sizeof(uint32_t)));
+    uint32_t *const h = ctx->h_build_words;
+    auto read_word = [&](uint32_t &out, const uint32_t *dev) {  // one word behind everything queued on the stream
+        hipError_t e = hipMemcpyAsync(h, dev, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        out = h[0];
+        return e;
+    };
+    // materials[int(mat_id.x)] must stay inside the buffer: validated BEFORE anything of the stored scene is touched, on the host or by a kernel
+    if (!device_source) {
+        for (size_t i = 0; i < n_tris; ++i) {
+            const float m = tris[i].mat_id[0];
+            if (!(m >= 0.0f) || static_cast<size_t>(static_cast<int>(m)) >= n_mats)
+                return fail(ctx, RVPT_HIP_ERR_INVALID, "triangle %zu: material index %g outside [0,%zu)", i, static_cast<double>(m), n_mats);
+        }
+    } else {
+        uint32_t bad = 0;
+        HIP_TRY(ctx, rv::build_validate_materials(ctx->stream, reinterpret_cast<const float4 *>(tris), n, static_cast<uint32_t>(std::min<size_t>(n_mats, 0x80000000u)), ctx->d_build_counters));
+        HIP_TRY(ctx, read_word(bad, ctx->d_build_counters + rv::kBuildFirstBad));
+        if (bad != 0xFFFFFFFFu) {
+            float m = 0.0f;
+            HIP_TRY(ctx, hipMemcpy(&m, &tris[bad].mat_id[0], sizeof m, hipMemcpyDeviceToHost));
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "triangle %zu: material index %g outside [0,%zu)", static_cast<size_t>(bad), static_cast<double>(m), n_mats);
+        }
+    }
+    if (int rc0 = sync_all(ctx)) return rc0;  // frames in flight still read the old scene
+    // scratch of the level loops, in bytes per region: keys / ranges A / wide heads (8 n), sorted keys / wide heads (8 n), ranges B / the two wide queues (8 n),
+    // then three arrays of n + 1 words (flags A, flags B, offsets)
+    const size_t words = ((static_cast<size_t>(n) + 1u) * 4u + 15u) & ~size_t(15);
+    const size_t scratch_bytes = 24u * static_cast<size_t>(n) + 3u * words;
+    size_t temp_bytes = 0;
+    HIP_TRY(ctx, rv::build_temp_bytes(n, &temp_bytes));
+    const size_t node_cap = 2u * static_cast<size_t>(n) + 2u;  // 2 leaves - 1 nodes and the unused slot 1, leaves <= triangles
+    if ((rc = grow(ctx, ctx->d_tris, ctx->cap_tris, n_tris, sizeof(rvpt_triangle)))) return rc;
+    if ((rc = grow(ctx, ctx->d_prep, ctx->cap_prep, n_tris, sizeof(rvpt_triangle)))) return rc;
+    if ((rc = grow(ctx, ctx->d_mat_index, ctx->cap_mat_index, n_tris, sizeof(uint32_t)))) return rc;
+    if ((rc = grow(ctx, ctx->d_unit_n, ctx->cap_unit_n, n_tris, sizeof(float4)))) return rc;
+    if ((rc = grow(ctx, ctx->d_mats, ctx->cap_mats, n_mats, sizeof(rvpt_material)))) return rc;
+    if ((rc = grow(ctx, ctx->d_perm, ctx->cap_perm, n_tris, sizeof(uint32_t)))) return rc;
+    if ((rc = grow(ctx, ctx->d_nodes, ctx->cap_nodes, node_cap, sizeof(rvpt_bvh_node)))) return rc;
+    if ((rc = grow(ctx, ctx->d_build, ctx->cap_build, scratch_bytes, 1))) return rc;
+    if ((rc = grow(ctx, ctx->d_build_temp, ctx->cap_build_temp, temp_bytes, 1))) return rc;
+    unsigned char *const base = ctx->d_build;
+    uint64_t *const keys = reinterpret_cast<uint64_t *>(base), *const sorted = reinterpret_cast<uint64_t *>(base + 8u * static_cast<size_t>(n));
+    uint2 *ranges = reinterpret_cast<uint2 *>(base), *ranges_next = reinterpret_cast<uint2 *>(base + 16u * static_cast<size_t>(n));
+    uint32_t *flags = reinterpret_cast<uint32_t *>(base + 24u * static_cast<size_t>(n)), *flags_next = reinterpret_cast<uint32_t *>(base + 24u * static_cast<size_t>(n) + words);
+    uint32_t *const offs = reinterpret_cast<uint32_t *>(base + 24u * static_cast<size_t>(n) + 2u * words);
+    ctx->have_scene = false;  // from here on the stored scene is being replaced: an error below leaves none
+    if (n_mats) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mats, mats, n_mats * sizeof(rvpt_material), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(rv::prepare_materials, dim3((static_cast<uint32_t>(n_mats) + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_mats, static_cast<uint32_t>(n_mats));
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    const float4 *src = reinterpret_cast<const float4 *>(tris);
+    if (!device_source) {  // a host array is staged in d_prep, which prepare_triangles rewrites at the end
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_prep, tris, n_tris * sizeof(rvpt_triangle), hipMemcpyHostToDevice, ctx->stream));
+        src = ctx->d_prep;
+    }
+    // stages 1-3: keys, sort, gather
+    HIP_TRY(ctx, rv::build_keys(ctx->stream, src, n, ctx->d_build_counters, keys));
+    HIP_TRY(ctx, rv::build_sort_keys(ctx->stream, ctx->d_build_temp, temp_bytes, keys, sorted, n));
+    HIP_TRY(ctx, rv::build_gather(ctx->stream, src, sorted, n, ctx->d_tris, ctx->d_perm));
+    // stage 4: the topology, level by level, straight into the device layout (root at 0, slot 1 unused, sibling pairs on even indices, upper levels first)
+    std::vector<std::pair<uint32_t, uint32_t>> levels;
+    HIP_TRY(ctx, rv::build_root(ctx->stream, n, ranges, flags, ctx->d_nodes));
+    for (uint32_t begin = 0, count = 1, next_begin = 2;;) {
+        // rvpt_build.h: at most 30 + ceil(log2 n) + 1 <= 61 levels for n <= 2^30 triangles; counted, not clamped
+        if (levels.size() >= rv::kBvhStackDepth)
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "device BVH build: the tree is higher than the %u levels the traversal stack can walk", rv::kBvhStackDepth);
+        levels.emplace_back(begin, begin + count);
+        HIP_TRY(ctx, rv::build_level(ctx->stream, ctx->d_build_temp, temp_bytes, sorted, ranges, flags, offs, begin, count, next_begin, ranges_next, flags_next, ctx->d_nodes,
+                                     static_cast<uint32_t>(node_cap), ctx->d_build_counters));
+        uint32_t inner = 0;
+        HIP_TRY(ctx, read_word(inner, offs + count));
+        if (inner == 0) break;
+        if (static_cast<size_t>(next_begin) + 2u * inner > node_cap) return fail(ctx, RVPT_HIP_ERR_HIP, "device BVH build: a level of %u pairs does not fit the node buffer", inner);
+        begin = next_begin, count = 2u * inner, next_begin = begin + count;
+        std::swap(ranges, ranges_next);
+        std::swap(flags, flags_next);
+    }
+    const size_t n_device_nodes = std::max<size_t>(2, levels.back().second);
+    // stage 5: boxes, deepest level first
+    for (size_t l = levels.size(); l-- > 0;) {
+        const auto [begin, end] = levels[l];
+        hipLaunchKernelGGL(rv::refit_level, dim3((end - begin + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_nodes, begin, end, static_cast<uint32_t>(n_device_nodes), ctx->d_tris, n);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    // stage 6: can a node's (first, count) pair ride in one stack word?  (the rule of the full upload)
+    uint32_t max_count = 0, head_shift = 0;
+    HIP_TRY(ctx, read_word(max_count, ctx->d_build_counters + rv::kBuildMaxLeaf));
+    {
+        uint32_t shift = 1;
+        while (shift < 31 && (1ull << shift) <= std::max(n_device_nodes, n_tris)) shift += 1;
+        if (static_cast<uint64_t>(max_count) < (1ull << (32 - shift))) head_shift = shift;
+    }
+    // stage 7: the 4-wide form (bvh_wide.cpp: regroup as a level loop); no wide form for a single-leaf tree, heads that do not pack, need > 4096, kWideMaxNodes
+    size_t n_wide_kept = 0;
+    uint32_t wide_need_kept = 0;
+    const size_t n_inner = (n_device_nodes - 2u) / 2u;
+    // (the laboratory's caller-layout knob does not apply: there is no caller's layout — the tree is born breadth first, with its level table)
+    const uint64_t wide_limit = std::min<uint64_t>(rv::kWideMaxNodes, 1ull << head_shift);  // a wide index must address 128-byte nodes in 32 bits and fit below a head's count bits
+    if (levels.size() > 1 && head_shift != 0) {
+        if ((rc = grow(ctx, ctx->d_wide_map, ctx->cap_wide_map, n_inner * 4u, sizeof(uint32_t)))) return rc;
+        uint32_t *const heads = reinterpret_cast<uint32_t *>(base);  // 16 bytes per wide node, <= 16 (n - 1)
+        uint32_t *bin = reinterpret_cast<uint32_t *>(base + 16u * static_cast<size_t>(n)), *bin_next = bin + n;
+        uint32_t *const cnt = flags, *const need = flags_next;
+        std::vector<std::pair<uint32_t, uint32_t>> wide_levels;  // (first wide index, count)
+        HIP_TRY(ctx, rv::build_wide_root(ctx->stream, bin));
+        uint32_t wbase = 0, count = 1;
+        for (;;) {
+            if (wide_levels.size() >= levels.size()) return fail(ctx, RVPT_HIP_ERR_HIP, "device BVH build: the wide form has more levels than the binary tree");
+            wide_levels.emplace_back(wbase, count);
+            HIP_TRY(ctx, rv::build_wide_level(ctx->stream, ctx->d_build_temp, temp_bytes, ctx->d_nodes, static_cast<uint32_t>(n_device_nodes), bin, wbase, count, head_shift, cnt, offs,
+                                              ctx->d_wide_map, heads, static_cast<uint32_t>(n_inner), bin_next));
+            uint32_t next = 0;
+            HIP_TRY(ctx, read_word(next, offs + count));
+            if (next == 0) break;
+            // (wide_pick / wide_emit write nothing beyond n_inner rows and leave a level partly written when it would not fit: this check is what makes that safe)
+            if (static_cast<size_t>(wbase) + count + next > n_inner) return fail(ctx, RVPT_HIP_ERR_HIP, "device BVH build: more wide nodes than inner nodes");
+            wbase += count, count = next;
+            if (static_cast<uint64_t>(wbase) + count >= wide_limit) break;  // no wide form for this tree: the levels below need not be made
+            std::swap(bin, bin_next);
+        }
+        const size_t n_wide = static_cast<size_t>(wbase) + count;
+        if (n_wide < wide_limit) {
+            if ((rc = grow(ctx, ctx->d_wide, ctx->cap_wide, n_wide * 8, sizeof(float4)))) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_wide, 0, n_wide * 128u, ctx->stream));  // unused slots and padding are zero, as build_wide_nodes leaves them
+            HIP_TRY(ctx, rv::build_wide_heads(ctx->stream, heads, static_cast<uint32_t>(n_wide), reinterpret_cast<float *>(ctx->d_wide)));
+            const uint32_t n_slots = static_cast<uint32_t>(n_wide * 4);
+            hipLaunchKernelGGL(rv::refit_wide_gather, dim3((n_slots + 255u) / 256u), dim3(256), 0, ctx->stream, reinterpret_cast<float *>(ctx->d_wide), ctx->d_wide_map, n_slots, ctx->d_nodes,
+                               static_cast<uint32_t>(n_device_nodes));
+            HIP_TRY(ctx, hipGetLastError());
+            for (size_t l = wide_levels.size(); l-- > 0;)  // the same bottom-up maximum as need[] in bvh_wide.cpp
+                HIP_TRY(ctx, rv::build_wide_need(ctx->stream, reinterpret_cast<const float *>(ctx->d_wide), wide_levels[l].first, wide_levels[l].second, static_cast<uint32_t>(n_wide), head_shift, need));
+            uint32_t root_need = 0;
+            HIP_TRY(ctx, read_word(root_need, need));
+            root_need = std::max(1u, root_need);
+            if (root_need <= 4096u) n_wide_kept = n_wide, wide_need_kept = root_need;
+        }
+    }
+    // stage 8: what the full upload derives from d_tris
+    if ((rc = launch_prepare_triangles(ctx, n_tris))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // caller may free its arrays on return
+    ctx->n_tris = n_tris;
+    ctx->n_mats = n_mats;
+    ctx->n_nodes = n_device_nodes;
+    ctx->bvh_height = static_cast<uint32_t>(levels.size());
+    ctx->refit_levels = std::move(levels);
+    ctx->bvh_head_shift = head_shift;
+    ctx->n_wide = n_wide_kept;
+    ctx->wide_stack_levels = wide_need_kept;
+    ctx->have_perm = true;
+    if ((rc = derive_bounce_state(ctx, true, nullptr, n_tris))) return rc;
+    ctx->scene_gen += 1;  // the slots' screen rectangles belong to the old scene
+    ctx->have_scene = true;
+    return RVPT_HIP_OK;
+}
+
 }  // namespace
 
 int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes, const rvpt_triangle *tris,
@@ -1064,6 +1253,11 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     if (n_tris > 0x3FFFFFFFull) return fail(ctx, RVPT_HIP_ERR_INVALID, "too many triangles");
     // the UPDATE FORM: triangles without nodes and without materials (as a full upload it could never succeed: no material index fits n_mats == 0)
     if (n_tris > 0 && !nodes && n_nodes == 0 && !mats && n_mats == 0) return update_geometry(ctx, tris, n_tris);
+    // the BUILD FORM: no nodes and the sentinel count.  BVH contexts build the tree on the device; brute-force contexts ignore nodes and n_nodes as ever
+    if (!nodes && n_nodes == RVPT_HIP_NODES_BUILD) {
+        if (is_bvh(ctx, n_tris)) return build_scene_on_device(ctx, tris, n_tris, mats, n_mats);
+        n_nodes = 0;
+    }
     // an EMPTY scene has no tree (RVPT::initialize with no triangles): every ray misses whatever the traversal, and the
     // frame kernels of a BVH context then run the brute-force instance over zero triangles (choose_launch)
     const bool bvh = is_bvh(ctx, n_tris);
@@ -1173,6 +1367,7 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     }
     ctx->n_wide = 0;
     ctx->wide_stack_levels = 0;
+    ctx->have_perm = false;  // the triangles are in the leaf order of the caller's tree: the update form takes that order
     if (bvh && !ctx->knobs.bvh_caller_layout) {  // the 4-wide form of the tree (breadth-first device layout: children of node i at first, first + 1)
         uint32_t need = 0;
         std::vector<uint32_t> kid_map;

@@ -1,0 +1,68 @@
+// rvpt_build.h — the device BVH build (rvpt_build.hip), launched by rvpt_hip_upload_scene's BUILD FORM (rvpt_abi.hip: build_scene_on_device): triangles in the
+// caller's order in, the binary tree in its breadth-first device layout, its level table and its 4-wide form out.  Nothing derived from the triangles visits
+// the host except a few counters.
+//
+// THE TREE (one specification, written twice: here for the device, rvpt_amd/scene.py: build_lbvh in numpy — the two give the same topology, which is what
+// tests/test_device_build.py compares bit for bit):
+//   key of triangle i (caller's index):  c = (v0 + v1 + v2) * (1.0f / 3.0f) per axis, float32, left to right, no contraction (as bvh_builder.cpp);
+//       lo, hi = min, max of the centroids per axis (exact; NaN centroids take no part);
+//       q = clamp((int)((c - lo) * (1024.0f / (hi - lo))), 0, 1023) with the IEEE float32 divide — evaluated as f >= 1023 ? 1023 : f >= 0 ? (int)f : 0, so that
+//       a NaN (every comparison fails) gives 0 and an infinity 1023 without leaning on an undefined conversion; q = 0 on an axis whose extent is not > 0;
+//       code = 30-bit Morton code, x the highest bit of each triple; key = code << 32 | i.  Keys are unique: the ascending sort is unique.
+//   nodes: a node is a range [a, b] of the sorted keys; a leaf iff b - a + 1 <= kLbvhLeafTris; otherwise p = the highest bit in which key[a] and key[b]
+//       differ and the right child starts at the first s in (a, b] whose bit p is set (the keys are sorted: bit p is 0 .. 0 1 .. 1 over the range).
+//   height: a split on a code bit can happen at most 30 times along a path, a split on an index bit at most ceil(log2 n) times (p strictly falls), then the
+//       leaf: at most 30 + ceil(log2 n) + 1 <= 61 levels for n <= 2^30 triangles, so every such tree fits rv::kBvhStackDepth (64).  The build counts the
+//       levels it makes and fails with a message rather than clamp.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace rv {
+
+// Triangles per leaf at most.  Started at 4; settled at 2 by the traversal measurement of DESIGN.md §5.6 (profiles/device_build.txt): one-frame launches at 1080p
+// on leaves of <= 2 against <= 4 are a tie on the 1 M-triangle terrain (3 229 against 3 253 Msamples/s, inside the spread) and 11 % faster on Cornell + 9 k
+// (1 821 against 1 642); leaves of <= 8 are 14 % and 30 % slower; the default scene cannot tell.  Morton order pairs neighbours, not good leaves: the fewer
+// triangles a visited leaf drags in, the better.  (tools/build_bench.py traversal on a library built with -DRVPT_LBVH_LEAF_TRIS=4 / 8 is the comparison.)
+#ifndef RVPT_LBVH_LEAF_TRIS
+#define RVPT_LBVH_LEAF_TRIS 2
+#endif
+constexpr uint32_t kLbvhLeafTris = RVPT_LBVH_LEAF_TRIS;
+
+// counters the build keeps on the device (one small buffer; read back a few words at a time)
+enum BuildCounter : uint32_t { kBuildFirstBad = 0, kBuildMaxLeaf = 1, kBuildBounds = 2 /* .. 7: lo xyz, hi xyz as ordered integers */, kBuildCounters = 8 };
+
+// Every function below enqueues on `stream` and returns the launch's error; none of them waits.
+// src: reference Triangle records (four quads each) in the caller's order, DEVICE memory.
+
+// the first triangle whose material index is outside [0, n_mats) -> counters[kBuildFirstBad] (0xFFFFFFFF: none); resets the counters
+hipError_t build_validate_materials(hipStream_t stream, const float4 *src, uint32_t n_tris, uint32_t n_mats, uint32_t *counters);
+// stage 1: centroid bounds (counters[kBuildBounds ..]) and the keys
+hipError_t build_keys(hipStream_t stream, const float4 *src, uint32_t n_tris, uint32_t *counters, uint64_t *keys);
+// stage 2: rocPRIM's radix sort of the keys (62 bits) and the exclusive scans of the level loops share one temporary buffer of this many bytes
+hipError_t build_temp_bytes(uint32_t n_tris, size_t *bytes);
+hipError_t build_sort_keys(hipStream_t stream, void *temp, size_t temp_bytes, const uint64_t *keys_in, uint64_t *keys_out, uint32_t n_tris);
+// stage 3: the 64-byte records gathered into leaf order, the permutation kept (perm[j] = caller's index of leaf-order triangle j)
+hipError_t build_gather(hipStream_t stream, const float4 *src, const uint64_t *sorted_keys, uint32_t n_tris, float4 *tris_out, uint32_t *perm_out);
+// the update form after a build form: vert0..vert2 (48 of every 64 bytes) of the caller's-order records gathered through the stored permutation
+hipError_t build_gather_vertices(hipStream_t stream, const float4 *src, const uint32_t *perm, uint32_t n_tris, float4 *tris);
+// stage 4, per level (root level first): ranges / flags describe the level's `count` nodes at device indices begin .. begin + count - 1 (flags[j] = the node
+// splits; flags[count] = 0); the children go to next_begin + 2 * (number of splitting nodes before j) with their ranges / flags in ranges_next / flags_next.
+// offs[count] = the number of splitting nodes when the stream gets there.  node_cap: quads-pairs d_nodes can hold (nothing is written beyond)
+hipError_t build_root(hipStream_t stream, uint32_t n_tris, uint2 *ranges, uint32_t *flags, float4 *nodes);
+hipError_t build_level(hipStream_t stream, void *temp, size_t temp_bytes, const uint64_t *sorted_keys, const uint2 *ranges, const uint32_t *flags, uint32_t *offs,
+                       uint32_t begin, uint32_t count, uint32_t next_begin, uint2 *ranges_next, uint32_t *flags_next, float4 *nodes, uint32_t node_cap, uint32_t *counters);
+// stage 7, the 4-wide form (bvh_wide.cpp: regroup, as a level loop): per wide level, `bin` = the binary inner nodes that become the wide nodes wbase .. wbase +
+// count - 1.  Writes the d_wide_map rows, the leaf heads (heads: 4 words per wide node) and, behind the scan, the inner children's wide indices and bin_next.
+// offs[count] = wide nodes of the next level.
+hipError_t build_wide_root(hipStream_t stream, uint32_t *bin);
+hipError_t build_wide_level(hipStream_t stream, void *temp, size_t temp_bytes, const float4 *nodes, uint32_t n_nodes, const uint32_t *bin, uint32_t wbase, uint32_t count,
+                            uint32_t head_shift, uint32_t *cnt, uint32_t *offs, uint32_t *wide_map, uint32_t *heads, uint32_t wide_cap, uint32_t *bin_next);
+// ... the head quads of the finished wide nodes (boxes: refit_wide_gather, on a zeroed buffer)
+hipError_t build_wide_heads(hipStream_t stream, const uint32_t *heads, uint32_t n_wide, float *wide);
+// ... and the stack need, per wide level, deepest first: need[w] = max over children i of (children - 1 - i) + need[inner child]
+hipError_t build_wide_need(hipStream_t stream, const float *wide, uint32_t wbase, uint32_t count, uint32_t n_wide, uint32_t head_shift, uint32_t *need);
+
+}  // namespace rv

@@ -3,7 +3,7 @@
 // window's event loop, and writes the accumulated frame as a PFM image.
 //
 //   rvpt_render (--obj model.obj [--material-id 1] | --scene scene.obj) [--width 1024 --height 512] [--spp 1] [--bounces 8] [--frames 16] [--batch 1]
-//               [--traversal bvh|bvh_ordered|brute] [--translate x y z] [--rotate x y z] [--fov 90] [--mode 9] [--camera-mode 0]
+//               [--traversal bvh|bvh_ordered|brute] [--build host|device] [--translate x y z] [--rotate x y z] [--fov 90] [--mode 9] [--camera-mode 0]
 //               [--out frame.pfm] [--dump-prefix path]   (dump: camera block, sorted triangles, nodes, materials)
 #include <algorithm>
 #include <chrono>
@@ -43,7 +43,7 @@ int main(int argc, char **argv)
     // before the first HIP call: the context's seven streams (six for launches in flight + one main) must not share hardware queues; the library
     // itself leaves the environment alone
     setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    std::string obj, scene_obj, out = "frame.pfm", dump_prefix, traversal = "bvh";
+    std::string obj, scene_obj, out = "frame.pfm", dump_prefix, traversal = "bvh", build = "host";
     uint32_t width = 1024, height = 512;  // Window::Settings, main.cpp:95-98
     int spp = 1, bounces = 8, frames = 16, batch = 1, material_id = 1, mode = 9, camera_mode = 0, gpus = 1;
     bool force_collective = false;
@@ -57,6 +57,7 @@ int main(int argc, char **argv)
         else if (a == "--out") out = next();
         else if (a == "--dump-prefix") dump_prefix = next();
         else if (a == "--traversal") traversal = next();
+        else if (a == "--build") build = next();  // who builds the tree of a BVH traversal: rvpt_bvh_build on the host, or the library on the device
         else if (a == "--width") width = static_cast<uint32_t>(std::atoi(next()));
         else if (a == "--height") height = static_cast<uint32_t>(std::atoi(next()));
         else if (a == "--spp") spp = std::atoi(next());
@@ -73,6 +74,8 @@ int main(int argc, char **argv)
         else if (a == "--rotate") { rotate.x = static_cast<float>(std::atof(next())); rotate.y = static_cast<float>(std::atof(next())); rotate.z = static_cast<float>(std::atof(next())); }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
+    if (build != "host" && build != "device") { std::fprintf(stderr, "--build host|device\n"); return 2; }
+    if (build == "device" && !dump_prefix.empty()) { std::fprintf(stderr, "--dump-prefix needs --build host: a device-built tree has no host copy\n"); return 2; }
     if (obj.empty() && scene_obj.empty()) { std::fprintf(stderr, "usage: rvpt_render (--obj model.obj | --scene scene.obj) [options]\n"); return 2; }
     if (gpus > 1) {  // --gpus N means N devices: never a silent run on fewer (a figure labelled "gpus": N must be N GPUs' work)
         int visible = 0;
@@ -93,6 +96,7 @@ int main(int argc, char **argv)
         opt.tile_world = static_cast<uint32_t>(gpus);
         opt.bvh_traversal = traversal != "brute";
         opt.ordered_children = traversal == "bvh_ordered";
+        opt.device_build = build == "device";
         ranks.emplace_back(new rvpt::RVPT(width, height, opt));
         rvpt::RVPT &rvpt = *ranks.back();
         if (!scene_obj.empty()) {  // OBJ + MTL scene description: materials come from the file

@@ -162,7 +162,8 @@ bool RVPT::initialize()
     nodes_.clear();
     nodes_stale_ = false;
     order_.clear();
-    if (!triangles_.empty()) {
+    device_built_ = options_.device_build && options_.bvh_traversal && !triangles_.empty();
+    if (!triangles_.empty() && !device_built_) {
         nodes_.resize(2 * triangles_.size() - 1);
         std::vector<uint32_t> &order = order_;
         order.resize(triangles_.size());
@@ -180,6 +181,10 @@ bool RVPT::initialize()
     const uint32_t flags = traversal | options_.extra_flags;
     if (!check(backend_.create(&ctx_, options_.device, width_, height_, options_.tile_rank, options_.tile_world, flags), "rvpt_hip_create"))
         return false;
+    if (device_built_)  // the build form: no nodes, the sentinel count, the triangles in the order they were added
+        return check(backend_.upload_scene(ctx_, nullptr, RVPT_HIP_NODES_BUILD, reinterpret_cast<const rvpt_triangle *>(triangles_.data()), triangles_.size(),
+                                           reinterpret_cast<const rvpt_material *>(materials_.data()), materials_.size()),
+                     "rvpt_hip_upload_scene (build form)");
     return check(backend_.upload_scene(ctx_, options_.bvh_traversal ? nodes_.data() : nullptr, options_.bvh_traversal ? nodes_.size() : 0,
                                        reinterpret_cast<const rvpt_triangle *>(sorted_.data()), sorted_.size(),
                                        reinterpret_cast<const rvpt_material *>(materials_.data()), materials_.size()),
@@ -192,11 +197,18 @@ bool RVPT::update_triangles(const std::vector<Triangle> &triangles)
         error_ = "update_triangles before initialize()";
         return false;
     }
-    if (triangles.size() != order_.size()) {
-        error_ = "update_triangles: " + std::to_string(triangles.size()) + " triangles given, the scene has " + std::to_string(order_.size());
+    if (triangles.size() != triangles_.size()) {
+        error_ = "update_triangles: " + std::to_string(triangles.size()) + " triangles given, the scene has " + std::to_string(triangles_.size());
         return false;
     }
     if (triangles.empty()) return true;
+    if (device_built_) {  // the device gathers through the permutation it kept
+        if (!check(backend_.upload_scene(ctx_, nullptr, 0, reinterpret_cast<const rvpt_triangle *>(triangles.data()), triangles.size(), nullptr, 0), "rvpt_hip_upload_scene (geometry update)"))
+            return false;
+        triangles_ = triangles;
+        previous_.valid = false;
+        return true;
+    }
     std::vector<Triangle> moved;
     moved.reserve(triangles.size());
     for (uint32_t i : order_) moved.push_back(triangles[i]);  // leaf order (Bvh::permute_primitives)

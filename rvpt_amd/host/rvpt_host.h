@@ -103,6 +103,10 @@ public:
         int device = 0;
         bool bvh_traversal = true;  // the reference's live path; false = LDS-staged brute force
         bool ordered_children = false;  // with bvh_traversal: nearer child first (RVPT_HIP_TRAVERSAL_BVH_ORDERED)
+        // with bvh_traversal: who builds the tree.  false: rvpt_bvh_build (binned SAH) on the host and a full upload; true: the library builds an LBVH on the
+        // GPU from the triangles as they were added (the build form of rvpt_hip_upload_scene) — the tree then lives on the device only: bvh_nodes() and
+        // sorted_triangles() are empty
+        bool device_build = false;
         uint32_t tile_rank = 0, tile_world = 1;
         uint32_t extra_flags = 0;   // RVPT_HIP_TIMING, RVPT_HIP_ACCUM_UNORM8, ...
     };
@@ -125,7 +129,7 @@ public:
     void add_triangle(Triangle triangle);  // rvpt.cpp:1043
     // Moving geometry — what the per-frame triangle copy of rvpt.cpp:124 is for: `triangles` (in the order they were ADDED, same count) replace the scene's.  The
     // tree keeps its topology and is refitted on the device (the update form of rvpt_hip_upload_scene: no nodes, no materials), no rebuild; the next update()
-    // restarts the accumulation.  After initialize() only.
+    // restarts the accumulation.  After initialize() only.  (After a device build the device keeps the permutation: the triangles go down as they are.)
     bool update_triangles(const std::vector<Triangle> &triangles);
 
     // RGBA32F (width*height*4 floats) or RGBA8 (width*height*4 bytes), row-major, top row first
@@ -155,6 +159,7 @@ private:
     mutable std::vector<rvpt_bvh_node> nodes_;
     mutable bool nodes_stale_ = false;  // update_triangles moved the geometry under nodes_' boxes
     std::vector<uint32_t> order_;       // primitive indices of the build: sorted_[i] = triangles_[order_[i]]
+    bool device_built_ = false;         // the scene went up by the build form: no nodes_, sorted_, order_ on the host
     // PreviousFrameState (rvpt.h:211-219, rvpt.cpp:21-29); empty camera data never compares equal
     struct Previous {
         bool valid = false;

@@ -25,6 +25,7 @@ FORMAT_RGBA32F, FORMAT_RGBA8_UNORM = 0, 1
 CULL_SKY_LIST = 0x80  # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
 TILE = 16
 TILE_SHIFT = 3  # RVPT_HIP_TILE_SHIFT: every row of the tile grid is rotated by this many more tiles than the one above (tile ownership)
+NODES_BUILD = C.c_size_t(-1).value  # RVPT_HIP_NODES_BUILD: upload_scene's node count for the build form (Context.build_scene)
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_SIZE, ERR_COMM = -1, -2, -3, -4, -5, -6
 
 # the C ABI of include/rvpt_hip.h: what librvpt_hip.so exports, all of it and nothing else (tests/test_abi_exports.py)
@@ -323,29 +324,44 @@ class Context:
                                              mats.shape[0]), self._h, self._L)
         self._scene_tris = tris.shape[0]
 
-    def update_triangles(self, tris) -> None:
-        """The update form of rvpt_hip_upload_scene (include/rvpt_hip.h): the scene's triangles have moved — same count, same leaf order, same tree topology as
-        the last upload_scene.  Only vert0..vert2 are taken; material rows, materials and the tree's structure stay, every box of the tree is refitted on the
-        device (scene.refit_bvh is the same on the host).  Frames in flight finish on the old geometry; restarting the accumulation is the caller's business.
-        tris: float32[n, 16], a numpy array or — BVH contexts — a contiguous torch tensor on this context's device, which never visits the host."""
-        ptr = None
+    def _triangle_source(self, tris, what: str):
+        """(pointer, count, object to keep alive) of float32[n, 16] triangles in a numpy array or a torch tensor; a tensor on this context's device is passed as
+        device memory once the stream that produced it has finished (the library copies on its own stream)."""
         if not isinstance(tris, np.ndarray) and hasattr(tris, "data_ptr"):  # a torch tensor
             import torch
             if tris.dtype != torch.float32 or tris.dim() != 2 or tris.shape[1] != 16 or not tris.is_contiguous():
-                raise NativeError(ERR_INVALID, f"update_triangles: a contiguous float32 tensor [n, 16] is needed, got {tris.dtype} {tuple(tris.shape)}")
+                raise NativeError(ERR_INVALID, f"{what}: a contiguous float32 tensor [n, 16] is needed, got {tris.dtype} {tuple(tris.shape)}")
             if tris.is_cuda:
                 if tris.device.index != self.device:
-                    raise NativeError(ERR_INVALID, f"update_triangles: the tensor lives on device {tris.device.index}, the context on {self.device}")
+                    raise NativeError(ERR_INVALID, f"{what}: the tensor lives on device {tris.device.index}, the context on {self.device}")
                 torch.cuda.current_stream(tris.device).synchronize()  # the library copies on its own stream: what produced the tensor must have finished
-                ptr, n, keep = C.c_void_p(tris.data_ptr()), int(tris.shape[0]), tris
-            else:
-                tris = tris.numpy()
-        if ptr is None:
-            tris = np.asarray(tris)
-            if tris.dtype != np.float32 or tris.ndim != 2 or tris.shape[1] != 16:
-                raise NativeError(ERR_INVALID, f"update_triangles: float32[n, 16] is needed, got {tris.dtype} {tris.shape}")
-            keep = tris = np.ascontiguousarray(tris)
-            ptr, n = _ptr(tris), tris.shape[0]
+                return C.c_void_p(tris.data_ptr()), int(tris.shape[0]), tris
+            tris = tris.numpy()
+        tris = np.asarray(tris)
+        if tris.dtype != np.float32 or tris.ndim != 2 or tris.shape[1] != 16:
+            raise NativeError(ERR_INVALID, f"{what}: float32[n, 16] is needed, got {tris.dtype} {tris.shape}")
+        tris = np.ascontiguousarray(tris)
+        return _ptr(tris), tris.shape[0], tris
+
+    def build_scene(self, tris, mats) -> None:
+        """The build form of rvpt_hip_upload_scene (include/rvpt_hip.h): a full upload without nodes — on a BVH context the library builds the tree on the
+        device (scene.build_lbvh is the same tree in numpy).  tris: float32[n, 16] in ANY order, a numpy array or — BVH contexts — a contiguous torch tensor on
+        this context's device, which never visits the host; update_triangles afterwards takes the same order.  Brute-force contexts: the ordinary upload."""
+        ptr, n, keep = self._triangle_source(tris, "build_scene")
+        if not isinstance(keep, np.ndarray) and (self.flags & (TRAVERSAL_BVH | TRAVERSAL_BVH_ORDERED)) == 0:
+            raise NativeError(ERR_INVALID, "build_scene: a brute-force context reads the triangles on the host, pass a host array")
+        mats = np.ascontiguousarray(mats, dtype=np.float32).reshape(-1, 12)
+        _check(self._L.rvpt_hip_upload_scene(self._h, None, NODES_BUILD, ptr, n, _ptr(mats), mats.shape[0]), self._h, self._L)
+        self._scene_tris = n
+        del keep
+
+    def update_triangles(self, tris) -> None:
+        """The update form of rvpt_hip_upload_scene (include/rvpt_hip.h): the scene's triangles have moved — same count, same tree topology as the last full
+        upload, in the order that upload took them: the leaf order after upload_scene, the caller's own order after build_scene.
+        Only vert0..vert2 are taken; material rows, materials and the tree's structure stay, every box of the tree is refitted on the
+        device (scene.refit_bvh is the same on the host).  Frames in flight finish on the old geometry; restarting the accumulation is the caller's business.
+        tris: float32[n, 16], a numpy array or — BVH contexts — a contiguous torch tensor on this context's device, which never visits the host."""
+        ptr, n, keep = self._triangle_source(tris, "update_triangles")
         if n == 0:  # (in the C form a call without triangles is a full upload of the empty scene)
             if self._scene_tris != 0:
                 raise NativeError(ERR_INVALID, "update_triangles: no triangles given" + (" before any upload_scene" if self._scene_tris is None else f", the uploaded scene has {self._scene_tris}"))

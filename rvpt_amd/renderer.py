@@ -66,9 +66,15 @@ def launch_sizes(frames: int, batch: int, in_flight: int = 3) -> list[int]:
 
 class RVPT:
     def __init__(self, width: int, height: int, device: int = 0, traversal: str = "brute", tile_rank: int = 0,
-                 tile_world: int = 1, flags: int = 0):
+                 tile_world: int = 1, flags: int = 0, build: str = "host"):
+        """build: who makes the tree of a BVH traversal — "host": rvpt_bvh_build (binned SAH, the reference's builder class) and a full upload; "device": the
+        library builds an LBVH on the GPU from the triangles as they were added (Context.build_scene): two orders of magnitude quicker to build, slower to
+        traverse."""
         if traversal not in ("brute", "bvh", "bvh_ordered"):
             raise ValueError("traversal must be 'brute', 'bvh' (the reference's visiting order) or 'bvh_ordered'")
+        if build not in ("host", "device"):
+            raise ValueError("build must be 'host' or 'device'")
+        self.build = build
         self.width, self.height = int(width), int(height)
         self.device, self.traversal = device, traversal
         self.tile_rank, self.tile_world = tile_rank, tile_world
@@ -80,10 +86,14 @@ class RVPT:
         self.materials: list[np.ndarray] = []
         self._bvh_nodes: np.ndarray | None = None
         self._nodes_stale = False  # update_triangles moved the geometry: bvh_nodes is refitted when it is next asked for
-        self.primitive_indices: np.ndarray | None = None
-        self.sorted_triangles: np.ndarray | None = None
+        self._primitive_indices: np.ndarray | None = None
+        self._sorted_triangles: np.ndarray | None = None
+        self._built_from: np.ndarray | None = None  # build="device": the triangles the device built its tree from, until the host statement is asked for
+        self._current_triangles: np.ndarray | None = None  # ... and the triangles the scene holds now, in the order they were added
         self._previous_key = None  # default-constructed PreviousFrameState never compares equal (empty camera data)
         self._ctx: native.Context | None = None
+        self._n_triangles: int | None = None
+        self._device_built = False
 
     # -- scene -------------------------------------------------------------------------------------------
     def add_material(self, material) -> None:
@@ -97,7 +107,9 @@ class RVPT:
 
     @property
     def bvh_nodes(self):
-        """top_level_bvh (rvpt.h:175): the tree initialize() built; after update_triangles its refit (scene.refit_bvh), made when first asked for."""
+        """top_level_bvh (rvpt.h:175): the tree initialize() built; after update_triangles its refit (scene.refit_bvh), made when first asked for.  With
+        build="device" the tree lives on the GPU: what is returned is the same tree stated on the host (scene.build_lbvh), made when first asked for."""
+        self._host_statement()
         if self._nodes_stale:
             self._bvh_nodes = scene.refit_bvh(self._bvh_nodes, self.sorted_triangles)
             self._nodes_stale = False
@@ -107,32 +119,72 @@ class RVPT:
     def bvh_nodes(self, nodes) -> None:
         self._bvh_nodes, self._nodes_stale = nodes, False
 
+    def _host_statement(self) -> None:
+        """build="device": bvh_nodes, primitive_indices and sorted_triangles of the device-built tree, from scene.build_lbvh on the triangles it was built from"""
+        if self._built_from is not None:
+            built_from, self._built_from = self._built_from, None
+            self._bvh_nodes, self._primitive_indices = scene.build_lbvh(built_from)
+            self._sorted_triangles = self._current_triangles[self._primitive_indices]
+            self._nodes_stale = self._current_triangles is not built_from  # moved since: the boxes are refitted when the nodes are asked for
+
+    @property
+    def primitive_indices(self):
+        self._host_statement()
+        return self._primitive_indices
+
+    @primitive_indices.setter
+    def primitive_indices(self, idx) -> None:
+        self._primitive_indices = idx
+
+    @property
+    def sorted_triangles(self):
+        self._host_statement()
+        return self._sorted_triangles
+
+    @sorted_triangles.setter
+    def sorted_triangles(self, tris) -> None:
+        self._sorted_triangles = tris
+
     def update_triangles(self, triangles) -> None:
         """Moving geometry — what the per-frame triangle copy of rvpt.cpp:124 is for: `triangles` (float32[n, 16], in the order they were ADDED, same count) replace
         the scene's; the tree keeps its topology and is refitted on the device (Context.update_triangles), no rebuild.  The next update() restarts the accumulation."""
         tris = np.asarray(triangles, dtype=np.float32).reshape(-1, 16)
-        if self._ctx is None or self.primitive_indices is None:
+        if self._ctx is None or self._n_triangles is None:
             raise RuntimeError("update_triangles before initialize()")
-        if tris.shape[0] != self.primitive_indices.shape[0]:
-            raise native.NativeError(native.ERR_INVALID, f"update_triangles: {tris.shape[0]} triangles given, the scene has {self.primitive_indices.shape[0]}")
-        sorted_tris = tris[self.primitive_indices]  # leaf order (Bvh::permute_primitives)
-        self._ctx.update_triangles(sorted_tris)
-        self.triangles = [tris.copy()]
-        self.sorted_triangles = sorted_tris
-        self._nodes_stale = self._bvh_nodes is not None
+        if tris.shape[0] != self._n_triangles:
+            raise native.NativeError(native.ERR_INVALID, f"update_triangles: {tris.shape[0]} triangles given, the scene has {self._n_triangles}")
+        if self._device_built:  # the device keeps the permutation: the caller's order goes down as it is
+            self._ctx.update_triangles(tris)
+            self._current_triangles = tris.copy()
+            self.triangles = [self._current_triangles]
+            if self._built_from is None:
+                self._sorted_triangles = tris[self._primitive_indices]
+                self._nodes_stale = True
+        else:
+            sorted_tris = tris[self.primitive_indices]  # leaf order (Bvh::permute_primitives)
+            self._ctx.update_triangles(sorted_tris)
+            self.triangles = [tris.copy()]
+            self.sorted_triangles = sorted_tris
+            self._nodes_stale = self._bvh_nodes is not None
         self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
 
     # -- lifecycle -----------------------------------------------------------------------------------------
     def initialize(self) -> bool:
         tris = np.concatenate(self.triangles) if self.triangles else np.zeros((0, 16), np.float32)
         mats = np.stack(self.materials) if self.materials else np.zeros((0, 12), np.float32)
+        self._n_triangles = tris.shape[0]
+        self._device_built = self.build == "device" and self.traversal != "brute" and tris.shape[0] > 0
+        self._ctx = native.Context(self.width, self.height, self.device, self.tile_rank, self.tile_world, self._flags)
+        if self._device_built:
+            self._ctx.build_scene(tris, mats)
+            self._built_from = self._current_triangles = tris
+            return True
         if tris.shape[0]:
             # top_level_bvh = bvh_builder.build_bvh(triangles); sorted_triangles = permute_primitives (rvpt.cpp:83-86)
             self.bvh_nodes, self.primitive_indices = native.build_bvh(tris)
             self.sorted_triangles = tris[self.primitive_indices]
         else:
             self.bvh_nodes, self.primitive_indices, self.sorted_triangles = None, np.zeros(0, np.uint32), tris
-        self._ctx = native.Context(self.width, self.height, self.device, self.tile_rank, self.tile_world, self._flags)
         self._ctx.upload_scene(self.bvh_nodes if self.traversal != "brute" else None, self.sorted_triangles, mats)
         return True
 

@@ -96,6 +96,88 @@ def refit_bvh(nodes, tris) -> np.ndarray:
     return out
 
 
+LBVH_LEAF_TRIS = 2  # == rv::kLbvhLeafTris (rvpt_amd/csrc/rvpt_build.h)
+
+
+def lbvh_keys(tris) -> np.ndarray:
+    """The 64-bit sort keys of the device BVH build (rvpt_amd/csrc/rvpt_build.h has the definition): per triangle i of the CALLER'S order, the 30-bit Morton code
+    of its centroid quantised to 10 bits per axis over the centroid bounds (x the highest bit of each triple), shifted above the index i.  uint64[n]."""
+    v = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 4, 4)[:, :3, :3]
+    n = v.shape[0]
+    third = np.float32(1.0) / np.float32(3.0)
+    with np.errstate(all="ignore"):
+        c = ((v[:, 0] + v[:, 1]) + v[:, 2]) * third  # float32, left to right
+        code = np.zeros(n, dtype=np.uint64)
+        for ax in range(3):
+            ca = c[:, ax]
+            lo, hi = (np.fmin.reduce(ca), np.fmax.reduce(ca)) if n else (np.float32(0), np.float32(0))  # NaN centroids take no part
+            ext = np.float32(hi - lo)
+            q = np.zeros(n, dtype=np.uint64)
+            if ext > 0:
+                f = (ca - lo) * (np.float32(1024.0) / ext)
+                inside = (f >= 0) & (f < 1023)  # false for a NaN
+                q[inside] = f[inside].astype(np.int32).astype(np.uint64)
+                q[f >= 1023] = 1023
+            s = np.zeros(n, dtype=np.uint64)
+            for bit in range(10):  # bit b of q -> bit 3 b (+ 2 for x, + 1 for y) of the code
+                s |= ((q >> np.uint64(bit)) & np.uint64(1)) << np.uint64(3 * bit + (2 - ax))
+            code |= s
+    return (code << np.uint64(32)) | np.arange(n, dtype=np.uint64)
+
+
+def _top_bit(x) -> np.ndarray:
+    """index of the highest set bit of every element of uint64 x (all non-zero)"""
+    hi = (x >> np.uint64(32)).astype(np.uint32)
+    lo = (x & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    word = np.where(hi > 0, hi, lo).astype(np.float64)  # exact: 32 bits fit a double, and floor(log2) of one is exact
+    return (np.floor(np.log2(word)).astype(np.int64) + np.where(hi > 0, 32, 0)).astype(np.uint64)
+
+
+def build_lbvh(tris, leaf_tris: int = LBVH_LEAF_TRIS):
+    """The tree rvpt_hip_upload_scene's BUILD FORM makes on the device, in numpy (the second statement of the one specification in
+    rvpt_amd/csrc/rvpt_build.h): sort the keys (lbvh_keys; unique, so the order is unique), a node is a range [a, b] of the sorted keys, a leaf iff it holds
+    <= leaf_tris of them, else split in front of the first key whose bit p is set, p = the highest bit in which key[a] and key[b] differ.  Boxes: refit_bvh.
+
+    tris: float32[n, 16] in the CALLER'S order, n >= 1.  Returns (nodes NODE_DTYPE[m] in the reference layout: root 0, children of an inner node adjacent at
+    first, first + 1, leaf iff count > 0, breadth first; perm uint32[n]: leaf-order triangle j is the caller's triangle perm[j]), so that
+    upload_scene(nodes, tris[perm], mats) is the scene the build form uploads.  Vectorised per level; a few seconds for 1 M triangles."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    n = t.shape[0]
+    if n == 0:
+        raise ValueError("build_lbvh: no triangles")
+    keys = np.sort(lbvh_keys(t))
+    perm = (keys & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    firsts, counts = [], []
+    a, b = np.zeros(1, dtype=np.int64), np.full(1, n - 1, dtype=np.int64)
+    next_index, height = 1, 0
+    while a.size:
+        height += 1
+        if height > 64:
+            raise ValueError("build_lbvh: the tree is higher than 64 levels")
+        inner = (b - a + 1) > leaf_tris
+        ia, ib = a[inner], b[inner]
+        p = _top_bit(keys[ia] ^ keys[ib])
+        lo, hi = ia.copy(), ib.copy()  # bit p of key[lo] is 0, of key[hi] 1
+        while True:
+            open_ = (hi - lo) > 1
+            if not open_.any():
+                break
+            mid = lo + (hi - lo) // 2
+            bit = ((keys[mid] >> p) & np.uint64(1)).astype(bool)
+            hi = np.where(open_ & bit, mid, hi)
+            lo = np.where(open_ & ~bit, mid, lo)
+        first = a.copy()
+        first[inner] = next_index + 2 * np.arange(ia.size, dtype=np.int64)
+        firsts.append(first)
+        counts.append(np.where(inner, 0, b - a + 1))
+        next_index += 2 * ia.size
+        a = np.stack([ia, hi], axis=1).reshape(-1)
+        b = np.stack([hi - 1, ib], axis=1).reshape(-1)
+    nodes = np.zeros(next_index, dtype=NODE_DTYPE)
+    nodes["first"], nodes["count"] = np.concatenate(firsts), np.concatenate(counts)
+    return refit_bvh(nodes, t[perm]), perm
+
+
 def wobble(tris, phase: float, amplitude: float) -> np.ndarray:
     """A smooth deformation for moving-geometry demos, tests and tools/refit_bench.py: every vertex is displaced by a function of its own position and `phase`
     alone (three sines of the other two coordinates), so vertices that coincide stay welded; |displacement| <= amplitude * sqrt(3).  The .w lanes and the

@@ -47,7 +47,8 @@ extern "C" {
                                      rvpt_hip_comm_info.  Still 8, no new symbol: rvpt_hip_upload_scene called with triangles but without nodes and without
                                      materials — until then always an error — is a GEOMETRY UPDATE (moved vertices, the tree refitted on the device).  Still 8,
                                      no new symbol: on a BVH context, no nodes and the count RVPT_HIP_NODES_BUILD — until then the "needs nodes" error —
-                                     is the BUILD FORM (the library builds the tree on the device from the triangles alone) */
+                                     is the BUILD FORM (the library builds the tree on the device from the triangles alone).  Still 8, no new symbol: the
+                                     count RVPT_HIP_NODES_BUILD_PLOC — until then the "needs nodes" error too — is the build form with a PLOC tree */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -217,8 +218,25 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  * An LBVH is quick to build and traverses slower than the binned-SAH tree of rvpt_bvh_build: measured on one MI355X
  * (profiles/device_build.txt), 1 M triangles build in 4.5 ms from a host array and 1.8 ms from device memory against
  * 338 ms for rvpt_bvh_build + a full upload, and one-frame launches at 1080p run at 0.54 - 0.72 of the SAH tree's rate
- * — the number a caller chooses by (DESIGN.md 5.6 has the table and the frame counts at which a host build pays). */
+ * — the number a caller chooses by (DESIGN.md 5.6 has the table and the frame counts at which a host build pays).
+ *
+ * BUILD FORM, PLOC TREE — the same call with the count RVPT_HIP_NODES_BUILD_PLOC:
+ *
+ *     rvpt_hip_upload_scene(ctx, NULL, RVPT_HIP_NODES_BUILD_PLOC, tris, n_tris, mats, n_mats);
+ *
+ * - The tree is made by parallel locally-ordered clustering (Meister & Bittner 2018) over the same sorted Morton order:
+ *   bottom-up merging of nearest neighbours within 16 positions, leaves of one triangle (rvpt_amd/csrc/rvpt_build.h
+ *   holds the definition, tie rule included; rvpt_amd/scene.py: build_ploc is the same tree in numpy).
+ * - Everything said above holds: the caller's order, device pointers, the rebuild, the atomicity rule, the update
+ *   form afterwards, brute-force contexts ignoring the count.  The two counts may alternate on one context.
+ * - PLOC promises neither a height nor an iteration count.  A tree higher than 62 levels, or one not finished after
+ *   256 iterations, is dropped and the call uploads the LBVH tree of RVPT_HIP_NODES_BUILD instead.  That is not an
+ *   error: the call returns RVPT_HIP_OK, and rvpt_hip_last_error then holds a sentence that says so (after a PLOC tree
+ *   it is empty).
+ * By SAH cost the PLOC tree is at 0.65 - 0.84 of the LBVH's on the scenes of DESIGN.md 5.7; its build time and traversal
+ * rate on an MI355X have not been measured yet (DESIGN.md 5.7 says what is open). */
 #define RVPT_HIP_NODES_BUILD ((size_t)-1)
+#define RVPT_HIP_NODES_BUILD_PLOC ((size_t)-2)
 int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes,
                           const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats,
                           size_t n_mats);

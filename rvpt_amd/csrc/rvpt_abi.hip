@@ -1077,7 +1077,8 @@ static int update_geometry(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t 
 // The BUILD FORM of rvpt_hip_upload_scene (include/rvpt_hip.h; BVH contexts): triangles in the caller's order and materials, no nodes — the tree is built on
 // the device (rvpt_build.h: the specification of the tree and the stages).  It is born in the breadth-first layout the full upload makes on the host, with its
 // level table, its height and its 4-wide form; the host reads one word per level.  `tris` may be host memory or device memory of the context's GPU.
-static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats, size_t n_mats)
+// `ploc`: the PLOC tree (RVPT_HIP_NODES_BUILD_PLOC) instead of the LBVH between stage 3 and stage 5, with the fallback rule of rvpt_build.h.
+static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats, size_t n_mats, bool ploc)
 {
     int rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1114,7 +1115,8 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     // scratch of the level loops, in bytes per region: keys / ranges A / wide heads (8 n), sorted keys / wide heads (8 n), ranges B / the two wide queues (8 n),
     // then three arrays of n + 1 words (flags A, flags B, offsets)
     const size_t words = ((static_cast<size_t>(n) + 1u) * 4u + 15u) & ~size_t(15);
-    const size_t scratch_bytes = 24u * static_cast<size_t>(n) + 3u * words;
+    const size_t lbvh_bytes = 24u * static_cast<size_t>(n) + 3u * words;  // (a multiple of 8: the PLOC regions behind it hold 8-byte pairs)
+    const size_t scratch_bytes = lbvh_bytes + (ploc ? rv::ploc_scratch_bytes(n) : 0u);
     size_t temp_bytes = 0;
     HIP_TRY(ctx, rv::build_temp_bytes(n, &temp_bytes));
     const size_t node_cap = 2u * static_cast<size_t>(n) + 2u;  // 2 leaves - 1 nodes and the unused slot 1, leaves <= triangles
@@ -1149,8 +1151,55 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     HIP_TRY(ctx, rv::build_gather(ctx->stream, src, sorted, n, ctx->d_tris, ctx->d_perm));
     // stage 4: the topology, level by level, straight into the device layout (root at 0, slot 1 unused, sibling pairs on even indices, upper levels first)
     std::vector<std::pair<uint32_t, uint32_t>> levels;
-    HIP_TRY(ctx, rv::build_root(ctx->stream, n, ranges, flags, ctx->d_nodes));
-    for (uint32_t begin = 0, count = 1, next_begin = 2;;) {
+    const char *fell_back = nullptr;
+    if (ploc) {  // the PLOC tree in place of stage 4 (rvpt_build.h); the sorted keys stay as they are for the fallback
+        unsigned char *const scratch = base + lbvh_bytes;
+        uint32_t m = n, parity = 0, iterations = 0;
+        HIP_TRY(ctx, rv::ploc_begin(ctx->stream, reinterpret_cast<const float4 *>(ctx->d_tris), n, scratch));
+        while (m > rv::kPlocTailClusters && iterations < rv::kPlocMaxIterations) {
+            HIP_TRY(ctx, rv::ploc_iteration(ctx->stream, ctx->d_build_temp, temp_bytes, scratch, n, m, parity, flags, offs));
+            uint32_t left = 0;
+            HIP_TRY(ctx, read_word(left, offs + m));
+            if (left == 0 || left >= m) return fail(ctx, RVPT_HIP_ERR_HIP, "device BVH build: a PLOC iteration left %u of %u clusters", left, m);
+            m = left, parity ^= 1u, iterations += 1u;
+        }
+        uint32_t root_and_iterations[2] = {0u, 0xFFFFFFFFu};
+        if (m <= rv::kPlocTailClusters) {
+            HIP_TRY(ctx, rv::ploc_finish(ctx->stream, scratch, n, m, parity, iterations, ctx->d_build_counters));
+            HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_build_counters + rv::kPlocRoot, 2u * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            root_and_iterations[0] = h[0], root_and_iterations[1] = h[1];
+        }
+        if (root_and_iterations[1] == 0xFFFFFFFFu) {
+            fell_back = "it was not finished within the iterations allowed";
+        } else {  // the layout: the level loop of stage 4 over the provisional nodes (the dead unsorted keys' region holds the two level arrays)
+            uint32_t *cur = reinterpret_cast<uint32_t *>(base), *cur_next = cur + n;
+            uint32_t *fl = flags, *fl_next = flags_next;
+            HIP_TRY(ctx, rv::ploc_layout_root(ctx->stream, ctx->d_build_counters, n, cur, fl, ctx->d_nodes));
+            for (uint32_t begin = 0, count = 1, next_begin = 2;;) {
+                if (levels.size() >= rv::kPlocMaxHeight) {
+                    fell_back = "it is higher than the levels allowed";
+                    levels.clear();
+                    break;
+                }
+                levels.emplace_back(begin, begin + count);
+                HIP_TRY(ctx, rv::ploc_layout_level(ctx->stream, ctx->d_build_temp, temp_bytes, scratch, n, cur, fl, offs, begin, count, next_begin, cur_next, fl_next, ctx->d_nodes,
+                                                   static_cast<uint32_t>(node_cap)));
+                uint32_t inner = 0;
+                HIP_TRY(ctx, read_word(inner, offs + count));
+                if (inner == 0) break;
+                if (static_cast<size_t>(next_begin) + 2u * inner > node_cap) return fail(ctx, RVPT_HIP_ERR_HIP, "device BVH build: a level of %u pairs does not fit the node buffer", inner);
+                begin = next_begin, count = 2u * inner, next_begin = begin + count;
+                std::swap(cur, cur_next);
+                std::swap(fl, fl_next);
+            }
+            if (!fell_back && levels.back().second != (n == 1u ? 1u : 2u * n))
+                return fail(ctx, RVPT_HIP_ERR_HIP, "device BVH build: the PLOC tree of %u triangles came out with %u node slots", n, levels.back().second);
+        }
+    }
+    const bool lbvh_tree = levels.empty();
+    if (lbvh_tree) HIP_TRY(ctx, rv::build_root(ctx->stream, n, ranges, flags, ctx->d_nodes));
+    for (uint32_t begin = 0, count = 1, next_begin = 2; lbvh_tree;) {
         // rvpt_build.h: at most 30 + ceil(log2 n) + 1 <= 61 levels for n <= 2^30 triangles; counted, not clamped
         if (levels.size() >= rv::kBvhStackDepth)
             return fail(ctx, RVPT_HIP_ERR_INVALID, "device BVH build: the tree is higher than the %u levels the traversal stack can walk", rv::kBvhStackDepth);
@@ -1174,7 +1223,8 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     HIP_TRY(ctx, hipGetLastError());
     // stage 6: can a node's (first, count) pair ride in one stack word?  (the rule of the full upload)
     uint32_t max_count = 0, head_shift = 0;
-    HIP_TRY(ctx, read_word(max_count, ctx->d_build_counters + rv::kBuildMaxLeaf));
+    if (lbvh_tree) HIP_TRY(ctx, read_word(max_count, ctx->d_build_counters + rv::kBuildMaxLeaf));
+    else max_count = 1;  // PLOC leaves hold one triangle
     {
         uint32_t shift = 1;
         while (shift < 31 && (1ull << shift) <= std::max(n_device_nodes, n_tris)) shift += 1;
@@ -1240,6 +1290,10 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     if ((rc = derive_bounce_state(ctx, true, nullptr, n_tris))) return rc;
     ctx->scene_gen += 1;  // the slots' screen rectangles belong to the old scene
     ctx->have_scene = true;
+    if (ploc) {  // which tree this was: the one fact a PLOC build reports beside its return code
+        if (fell_back) fail(ctx, RVPT_HIP_OK, "device BVH build: the PLOC tree was dropped (%s), the scene holds the LBVH tree", fell_back);
+        else ctx->err.clear();
+    }
     return RVPT_HIP_OK;
 }
 
@@ -1254,8 +1308,8 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     // the UPDATE FORM: triangles without nodes and without materials (as a full upload it could never succeed: no material index fits n_mats == 0)
     if (n_tris > 0 && !nodes && n_nodes == 0 && !mats && n_mats == 0) return update_geometry(ctx, tris, n_tris);
     // the BUILD FORM: no nodes and the sentinel count.  BVH contexts build the tree on the device; brute-force contexts ignore nodes and n_nodes as ever
-    if (!nodes && n_nodes == RVPT_HIP_NODES_BUILD) {
-        if (is_bvh(ctx, n_tris)) return build_scene_on_device(ctx, tris, n_tris, mats, n_mats);
+    if (!nodes && (n_nodes == RVPT_HIP_NODES_BUILD || n_nodes == RVPT_HIP_NODES_BUILD_PLOC)) {
+        if (is_bvh(ctx, n_tris)) return build_scene_on_device(ctx, tris, n_tris, mats, n_mats, n_nodes == RVPT_HIP_NODES_BUILD_PLOC);
         n_nodes = 0;
     }
     // an EMPTY scene has no tree (RVPT::initialize with no triangles): every ray misses whatever the traversal, and the

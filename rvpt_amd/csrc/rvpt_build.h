@@ -14,6 +14,22 @@
 //   height: a split on a code bit can happen at most 30 times along a path, a split on an index bit at most ceil(log2 n) times (p strictly falls), then the
 //       leaf: at most 30 + ceil(log2 n) + 1 <= 61 levels for n <= 2^30 triangles, so every such tree fits rv::kBvhStackDepth (64).  The build counts the
 //       levels it makes and fails with a message rather than clamp.
+//
+// THE PLOC TREE (RVPT_HIP_NODES_BUILD_PLOC; rvpt_ploc.hip on the device, rvpt_amd/scene.py: build_ploc in numpy — the same topology, compared bit for bit by
+// tests/test_device_build_ploc.py): parallel locally-ordered clustering (Meister & Bittner 2018), bottom-up merging over the order above.
+//   order: keys, sort and perm are exactly the LBVH's; triangle j of the leaf order is sorted key j.
+//   start: one cluster per sorted triangle, its box the exact min / max of its nine vertex coordinates (fminf / fmaxf: a NaN coordinate takes no part).
+//   one iteration over the m clusters in array order: cluster i takes, among the j != i with |i - j| <= kPlocRadius, the minimum of the triple
+//       (d(i, j), i xor j, min(i, j)).  d = the half-area of the union box in double: e = (double)hi - (double)lo per axis, (ex ey + ey ez) + ez ex, no
+//       contraction; a d that is not finite counts as +inf.  The triple is symmetric in (i, j) and totally ordered, so the globally smallest pair is mutual
+//       and every iteration merges at least one pair.  The xor term makes runs of equal distances pair up as buddies (0-1, 2-3, ..): by min(i, j) alone only
+//       the first pair of such a run would be mutual, one merge per iteration, a chain.  Every mutual pair i < j becomes one inner node at position i (left
+//       child cluster i, right child cluster j, box = min / max of the two); position j is removed; the array is compacted in order.  Until one cluster is left.
+//   layout: the finished tree is laid out from the root, level by level: root at 0, slot 1 unused, the children of the k-th inner node of a level (in node
+//       index order) at next_begin + 2 k and + 2 k + 1; a leaf is count = 1, first = its sorted position.  Boxes: refit_level, as after the LBVH.
+//   bounds on trouble: PLOC promises neither a height nor an iteration count.  A tree of more than kPlocMaxHeight levels (62: the depth the BVH checks of the
+//       tests allow, inside the 64 the traversal stack walks), or one that is not finished after kPlocMaxIterations iterations, is dropped and the call
+//       builds the LBVH tree above from the same sorted keys.  A rule, not an error: rvpt_hip_last_error then says so (and is empty after a PLOC tree).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,7 +48,23 @@ namespace rv {
 constexpr uint32_t kLbvhLeafTris = RVPT_LBVH_LEAF_TRIS;
 
 // counters the build keeps on the device (one small buffer; read back a few words at a time)
-enum BuildCounter : uint32_t { kBuildFirstBad = 0, kBuildMaxLeaf = 1, kBuildBounds = 2 /* .. 7: lo xyz, hi xyz as ordered integers */, kBuildCounters = 8 };
+enum BuildCounter : uint32_t {
+    kBuildFirstBad = 0,
+    kBuildMaxLeaf = 1,
+    kBuildBounds = 2 /* .. 7: lo xyz, hi xyz as ordered integers */,
+    kPlocRoot = 8 /* the provisional node of the PLOC tree's root */,
+    kPlocIterations = 9 /* iterations in all; 0xFFFFFFFF: not finished within kPlocMaxIterations */,
+    kBuildCounters = 12
+};
+
+// The PLOC tree's constants (each stated a second time in rvpt_amd/scene.py).  Radius: 16 against 8 is profiles/EXPERIMENTS.md's entry.
+#ifndef RVPT_PLOC_RADIUS
+#define RVPT_PLOC_RADIUS 16
+#endif
+constexpr uint32_t kPlocRadius = RVPT_PLOC_RADIUS;
+constexpr uint32_t kPlocMaxIterations = 256;
+constexpr uint32_t kPlocMaxHeight = 62;
+constexpr uint32_t kPlocTailClusters = 1024;  // not part of the tree: at most this many clusters are finished by one work-group in LDS (rvpt_ploc.hip: ploc_tail)
 
 // Every function below enqueues on `stream` and returns the launch's error; none of them waits.
 // src: reference Triangle records (four quads each) in the caller's order, DEVICE memory.
@@ -64,5 +96,21 @@ hipError_t build_wide_level(hipStream_t stream, void *temp, size_t temp_bytes, c
 hipError_t build_wide_heads(hipStream_t stream, const uint32_t *heads, uint32_t n_wide, float *wide);
 // ... and the stack need, per wide level, deepest first: need[w] = max over children i of (children - 1 - i) + need[inner child]
 hipError_t build_wide_need(hipStream_t stream, const float *wide, uint32_t wbase, uint32_t count, uint32_t n_wide, uint32_t head_shift, uint32_t *need);
+
+
+// The PLOC tree (rvpt_ploc.hip), between stage 3 and stage 5.  scratch: ploc_scratch_bytes(n) bytes, 8-byte aligned, kept until the layout is done.
+size_t ploc_scratch_bytes(uint32_t n_tris);
+// one cluster per leaf-order triangle (tris: the gathered records of stage 3) into half 0 of the double-buffered cluster array
+hipError_t ploc_begin(hipStream_t stream, const float4 *tris, uint32_t n_tris, unsigned char *scratch);
+// one iteration over the m clusters of half `parity`: nearest neighbours, keep flags, their scan (pos[m] = clusters left when the stream gets there), merge and
+// compaction into the other half.  keep, pos: m + 1 words each
+hipError_t ploc_iteration(hipStream_t stream, void *temp, size_t temp_bytes, unsigned char *scratch, uint32_t n_tris, uint32_t m, uint32_t parity, uint32_t *keep, uint32_t *pos);
+// the last m <= kPlocTailClusters clusters of half `parity`, all remaining iterations in one work-group; `iterations` = those made so far.
+// counters[kPlocRoot], counters[kPlocIterations] when the stream gets there
+hipError_t ploc_finish(hipStream_t stream, unsigned char *scratch, uint32_t n_tris, uint32_t m, uint32_t parity, uint32_t iterations, uint32_t *counters);
+// the layout, per level (root level first), the shape of build_root / build_level: cur = the provisional nodes of the level's `count` nodes, flags[j] = inner
+hipError_t ploc_layout_root(hipStream_t stream, const uint32_t *counters, uint32_t n_tris, uint32_t *cur, uint32_t *flags, float4 *nodes);
+hipError_t ploc_layout_level(hipStream_t stream, void *temp, size_t temp_bytes, const unsigned char *scratch, uint32_t n_tris, const uint32_t *cur, const uint32_t *flags, uint32_t *offs,
+                             uint32_t begin, uint32_t count, uint32_t next_begin, uint32_t *cur_next, uint32_t *flags_next, float4 *nodes, uint32_t node_cap);
 
 }  // namespace rv

@@ -107,6 +107,8 @@ public:
         // GPU from the triangles as they were added (the build form of rvpt_hip_upload_scene) — the tree then lives on the device only: bvh_nodes() and
         // sorted_triangles() are empty
         bool device_build = false;
+        // with device_build: the PLOC tree (RVPT_HIP_NODES_BUILD_PLOC) instead of the LBVH; false: the build form as it always was
+        bool device_build_ploc = false;
         uint32_t tile_rank = 0, tile_world = 1;
         uint32_t extra_flags = 0;   // RVPT_HIP_TIMING, RVPT_HIP_ACCUM_UNORM8, ...
     };

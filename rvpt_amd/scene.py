@@ -178,6 +178,100 @@ def build_lbvh(tris, leaf_tris: int = LBVH_LEAF_TRIS):
     return refit_bvh(nodes, t[perm]), perm
 
 
+PLOC_RADIUS = 16           # == rv::kPlocRadius (rvpt_amd/csrc/rvpt_build.h)
+PLOC_MAX_ITERATIONS = 256  # == rv::kPlocMaxIterations
+PLOC_MAX_HEIGHT = 62       # == rv::kPlocMaxHeight: the depth check_bvh allows, inside the 64 levels the traversal stack walks
+
+
+def _ploc_nearest(lo, hi, radius):
+    """nn[i] = the j != i, |i - j| <= radius, with the smallest triple (d(i, j), i xor j, min(i, j)); d = half-area of the union box in double, +inf if not finite"""
+    m = lo.shape[0]
+    best_d = np.full(m, np.inf)
+    best_x = np.full(m, np.iinfo(np.int64).max, dtype=np.int64)
+    best_m = np.full(m, np.iinfo(np.int64).max, dtype=np.int64)
+    nn = np.full(m, -1, dtype=np.int64)
+    idx = np.arange(m, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for s in range(1, min(radius, m - 1) + 1):
+            e = np.fmax(hi[:-s], hi[s:]).astype(np.float64) - np.fmin(lo[:-s], lo[s:]).astype(np.float64)
+            d = (e[:, 0] * e[:, 1] + e[:, 1] * e[:, 2]) + e[:, 2] * e[:, 0]
+            d = np.where(np.isfinite(d), d, np.inf)
+            i, j = idx[:-s], idx[s:]
+            x = i ^ j
+            for me, other in ((i, j), (j, i)):  # the pair (i, i + s) is a candidate of both members; min(i, j) = i
+                better = (d < best_d[me]) | ((d == best_d[me]) & ((x < best_x[me]) | ((x == best_x[me]) & (i < best_m[me]))))
+                w = me[better]
+                best_d[w], best_x[w], best_m[w], nn[w] = d[better], x[better], i[better], other[better]
+    return nn
+
+
+def build_ploc(tris, radius: int = PLOC_RADIUS, info: dict | None = None):
+    """The tree rvpt_hip_upload_scene's PLOC BUILD FORM (RVPT_HIP_NODES_BUILD_PLOC) makes on the device, in numpy — the second statement of the specification in
+    rvpt_amd/csrc/rvpt_build.h: parallel locally-ordered clustering (Meister & Bittner 2018) over build_lbvh's leaf order.  One cluster per sorted triangle;
+    per iteration every cluster picks its nearest neighbour within `radius` positions by the triple (half-area of the union box in double, i xor j, min(i, j)),
+    every mutual pair i < j becomes an inner node at position i (left i, right j), the array is compacted in order; until one cluster is left.  The tree is then
+    laid out level by level in the reference layout, leaves of one triangle; boxes: refit_bvh.
+
+    If the tree would be higher than PLOC_MAX_HEIGHT levels or needs more than PLOC_MAX_ITERATIONS iterations, the result is build_lbvh's tree (a rule of the
+    specification, not an error).  `info`, when given, is filled with tree ("ploc" | "lbvh"), iterations and height (of the PLOC tree, None if it was not
+    finished).  Same contract as build_lbvh: returns (nodes, perm), and upload_scene(nodes, tris[perm], mats) is the scene the form uploads."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    n = t.shape[0]
+    if n == 0:
+        raise ValueError("build_ploc: no triangles")
+    keys = np.sort(lbvh_keys(t))
+    perm = (keys & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    v = t[perm].reshape(-1, 4, 4)[:, :3, :3]
+    with np.errstate(all="ignore"):
+        lo, hi = np.fmin.reduce(v, axis=1), np.fmax.reduce(v, axis=1)  # a NaN coordinate takes no part (fminf / fmaxf)
+    ids = np.arange(n, dtype=np.int64)  # provisional node of every cluster: < n a leaf (its sorted position), else inner node ids - n of `children`
+    children = np.zeros((max(n - 1, 1), 2), dtype=np.int64)
+    made, iterations = 0, 0
+    if info is not None:
+        info.update(tree="lbvh", iterations=None, height=None)
+    while ids.size > 1:
+        if iterations >= PLOC_MAX_ITERATIONS:
+            return build_lbvh(t)
+        iterations += 1
+        m = ids.size
+        nn = _ploc_nearest(lo, hi, radius)
+        idx = np.arange(m, dtype=np.int64)
+        mutual = nn[nn] == idx
+        left = np.flatnonzero(mutual & (idx < nn))
+        right = nn[left]
+        new = n + made + np.arange(left.size, dtype=np.int64)
+        children[new - n, 0], children[new - n, 1] = ids[left], ids[right]
+        made += left.size
+        with np.errstate(all="ignore"):
+            lo[left], hi[left] = np.fmin(lo[left], lo[right]), np.fmax(hi[left], hi[right])
+        ids[left] = new
+        keep = np.ones(m, dtype=bool)
+        keep[right] = False
+        lo, hi, ids = lo[keep], hi[keep], ids[keep]
+    if info is not None:
+        info["iterations"] = iterations
+    # the layout: level by level from the root, the children of the k-th inner node of a level at next_begin + 2 k, + 2 k + 1
+    firsts, counts = [], []
+    cur, next_index, height = ids[:1].copy(), 1, 0
+    while cur.size:
+        height += 1
+        if height > PLOC_MAX_HEIGHT:
+            return build_lbvh(t)
+        inner = cur >= n
+        first = cur.copy()
+        k = int(inner.sum())
+        first[inner] = next_index + 2 * np.arange(k, dtype=np.int64)
+        firsts.append(first)
+        counts.append(np.where(inner, 0, 1))
+        next_index += 2 * k
+        cur = children[cur[inner] - n].reshape(-1)
+    if info is not None:
+        info.update(tree="ploc", height=height)
+    nodes = np.zeros(next_index, dtype=NODE_DTYPE)
+    nodes["first"], nodes["count"] = np.concatenate(firsts), np.concatenate(counts)
+    return refit_bvh(nodes, t[perm]), perm
+
+
 def wobble(tris, phase: float, amplitude: float) -> np.ndarray:
     """A smooth deformation for moving-geometry demos, tests and tools/refit_bench.py: every vertex is displaced by a function of its own position and `phase`
     alone (three sines of the other two coordinates), so vertices that coincide stay welded; |displacement| <= amplitude * sqrt(3).  The .w lanes and the

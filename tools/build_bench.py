@@ -2,7 +2,9 @@
 """Run on the GPU box: what a REBUILD of the 1 M-triangle terrain's tree costs (BVH context, 1920x1080) by the build form of rvpt_hip_upload_scene against the
 only route there was before it — rvpt_bvh_build + permute + a full upload_scene — and against the floor, a bare host-to-device copy of the same 64 MB; then
 what traversal pays on the device-built LBVH against the binned-SAH tree of rvpt_bvh_build and against a refitted tree.  -> stdout (profiles/device_build.txt)
-usage: tools/build_bench.py [all|builds|traversal|stages <kernel_stats.csv> [n_builds]]
+usage: tools/build_bench.py [--method lbvh|ploc] [all|builds|traversal|stages <kernel_stats.csv> [n_builds]]
+    --method ploc: the PLOC tree of the build form (DESIGN.md 5.7, profiles/device_build_ploc.txt).  all: its build time beside the LBVH's in the same run;
+        builds: PLOC builds; traversal: three trees interleaved on one box — PLOC, LBVH, rvpt_bvh_build's — one context each, a repetition of each in turn
     builds: one upload and a few device builds from a device tensor, nothing else — the run to put under rocprofv3 --kernel-trace --stats
     traversal: the traversal table only (what the leaf-size sweep runs per library)
     stages: no GPU — the per-stage table of profiles/device_build.txt from the kernel_stats.csv of such a rocprofv3 run
@@ -20,7 +22,16 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
-STAGES = {"validate_materials": "validate", "reset_counters": "keys", "centroid_bounds": "keys", "make_keys": "keys", "gather_records": "gather", "root_level": "topology",
+METHOD = "lbvh"
+if "--method" in sys.argv:
+    at = sys.argv.index("--method")
+    METHOD = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
+    if METHOD not in ("lbvh", "ploc"):
+        sys.exit("--method lbvh|ploc")
+
+STAGES = {"ploc_init": "PLOC clusters", "ploc_nearest": "PLOC nearest neighbour", "ploc_keep": "PLOC merge + compaction", "ploc_merge": "PLOC merge + compaction", "ploc_tail": "PLOC tail (one work-group)",
+          "layout_root": "topology", "layout_level": "topology", "validate_materials": "validate", "reset_counters": "keys", "centroid_bounds": "keys", "make_keys": "keys", "gather_records": "gather", "root_level": "topology",
           "emit_level": "topology", "refit_level": "boxes", "wide_root": "wide form", "wide_pick": "wide form", "wide_emit": "wide form", "wide_heads": "wide form",
           "wide_need": "wide form", "refit_wide_gather": "wide form", "prepare_triangles": "prepare", "prepare_materials": "prepare",
           "copyBuffer": "copies (read-backs of one word, materials)", "fillBuffer": "memset"}
@@ -104,9 +115,9 @@ if what == "builds":
     import torch
     dev = [torch.from_numpy(p).to("cuda:0") for p in poses]
     for k in range(8):
-        ctx.build_scene(dev[k % 2], mats)
+        ctx.build_scene(dev[k % 2], mats, method=METHOD)
     ctx.close()
-    print("8 device builds done")
+    print(f"8 device builds ({METHOD}) done")
     sys.exit(0)
 
 if what == "all":
@@ -151,14 +162,55 @@ if what == "all":
         dst64.copy_(src64); torch.cuda.synchronize()
     fl = timed(copy64, 20, warm=3)
     print(f"floor: flat H2D copy of 64 MB          {spread(fl)}    (pageable host memory, {tris0.shape[0] * 64 / 1e6 / statistics.median(fl) / 1e3:.1f} GB/s)")
+    if METHOD == "ploc":
+        def ploc_host():
+            ctx.build_scene(poses[k[0] % 2], mats, method="ploc"); k[0] += 1
+        def ploc_dev():
+            ctx.build_scene(dev[k[0] % 2], mats, method="ploc"); k[0] += 1
+        ph = timed(ploc_host, 20, warm=3)
+        print(f"PLOC build form (host numpy array)     {spread(ph)}")
+        pd = timed(ploc_dev, 20, warm=3)
+        print(f"PLOC build form (torch tensor)         {spread(pd)}")
+        print(f"PLOC / LBVH build time: host array {statistics.median(ph) / statistics.median(bh):.2f}, device tensor {statistics.median(pd) / statistics.median(bd):.2f}")
     m_b, m_h, m_d, m_f = (statistics.median(x) for x in (base, bh, bd, fl))
     print(f"summary: build form from a host array {m_h * 1e3:.2f} ms = {m_b / m_h:.1f} x faster than rvpt_bvh_build + upload ({m_b * 1e3:.0f} ms), {m_h / m_f:.2f} x the 64 MB copy floor "
           f"({m_f * 1e3:.2f} ms); from a device tensor {m_d * 1e3:.2f} ms")
     assert m_h < m_b, "the build form from a host array must take less wall time than the host route"
     del dev, dst64
 
-print(f"\n== traversal: the device-built LBVH (leaves of <= {os.environ.get('LEAF_TRIS', scene.LBVH_LEAF_TRIS)}) against rvpt_bvh_build's binned-SAH tree (one-frame launches, Msamples/s) ==")
+if METHOD == "ploc":
+    print(f"\n== traversal: the PLOC tree (radius {scene.PLOC_RADIUS}, leaves of 1) against the LBVH (leaves of <= {scene.LBVH_LEAF_TRIS}) and rvpt_bvh_build's binned-SAH tree (one-frame launches, Msamples/s) ==")
+else:
+    print(f"\n== traversal: the device-built LBVH (leaves of <= {os.environ.get('LEAF_TRIS', scene.LBVH_LEAF_TRIS)}) against rvpt_bvh_build's binned-SAH tree (one-frame launches, Msamples/s) ==")
+def compare_three(name, tris, ms, c, w, h, amps=()):
+    """PLOC, LBVH and the host's binned-SAH tree of one pose, a context each; five rounds, every round one repetition of each tree in turn"""
+    e = float(np.ptp(tris.reshape(-1, 4, 4)[:, :3, :3].reshape(-1, 3), axis=0).max())
+    for amp in (0.0,) + tuple(amps):
+        pose = scene.wobble(tris, 1.4, amp * e) if amp else tris
+        cxs = {k_: native.Context(w, h, 0, 0, 1, native.TRAVERSAL_BVH) for k_ in ("ploc", "lbvh", "host")}
+        t0 = time.perf_counter(); tree = cxs["ploc"].build_scene(pose, ms, method="ploc"); t_ploc = time.perf_counter() - t0
+        t0 = time.perf_counter(); cxs["lbvh"].build_scene(pose, ms); t_lbvh = time.perf_counter() - t0
+        t0 = time.perf_counter(); n2, i2 = native.build_bvh(pose); cxs["host"].upload_scene(n2, pose[i2], ms); t_host = time.perf_counter() - t0
+        got = {k_: [] for k_ in cxs}
+        for _ in range(5):
+            for k_, cx in cxs.items():
+                got[k_] += frame_rate(cx, c, w, h, reps=1)
+        for cx in cxs.values():
+            cx.close()
+        med = {k_: statistics.median(v) for k_, v in got.items()}
+        pad = f"{'':{len(name) + 18}}"
+        line = (f"{name}, amplitude {amp:4.2f}: PLOC ({tree})  {rates(got['ploc'])}\n{pad}LBVH         {rates(got['lbvh'])}\n{pad}host-built   {rates(got['host'])}\n"
+                f"{pad}PLOC / LBVH = {med['ploc'] / med['lbvh']:.3f}   PLOC / host = {med['ploc'] / med['host']:.3f}   LBVH / host = {med['lbvh'] / med['host']:.3f}")
+        for label, t_dev, r in (("PLOC", t_ploc, med["ploc"]), ("LBVH", t_lbvh, med["lbvh"])):
+            per_dev, per_host = w * h / r / 1e6, w * h / med["host"] / 1e6
+            line += f"\n{pad}rebuild {t_dev * 1e3:.1f} ms ({label}, first call of a context) vs {t_host * 1e3:.1f} ms (host): "
+            line += f"the host rebuild overtakes after {(t_host - t_dev) / (per_dev - per_host):.0f} one-frame launches" if per_dev > per_host and t_host > t_dev else "the host rebuild never overtakes" if t_host > t_dev else "the host route is no slower to build at this size"
+        print(line, flush=True)
+
+
 def compare(name, tris, ms, c, w, h, amps=()):
+    if METHOD == "ploc":
+        return compare_three(name, tris, ms, c, w, h, amps)
     cx = native.Context(w, h, 0, 0, 1, native.TRAVERSAL_BVH)
     e = float(np.ptp(tris.reshape(-1, 4, 4)[:, :3, :3].reshape(-1, 3), axis=0).max())
     nodes, idx = native.build_bvh(tris)

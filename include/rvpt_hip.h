@@ -48,7 +48,9 @@ extern "C" {
                                      materials — until then always an error — is a GEOMETRY UPDATE (moved vertices, the tree refitted on the device).  Still 8,
                                      no new symbol: on a BVH context, no nodes and the count RVPT_HIP_NODES_BUILD — until then the "needs nodes" error —
                                      is the BUILD FORM (the library builds the tree on the device from the triangles alone).  Still 8, no new symbol: the
-                                     count RVPT_HIP_NODES_BUILD_PLOC — until then the "needs nodes" error too — is the build form with a PLOC tree */
+                                     count RVPT_HIP_NODES_BUILD_PLOC — until then the "needs nodes" error too — is the build form with a PLOC tree.  Still 8, no
+                                     new symbol: the count RVPT_HIP_NODES_BUILD_SAH — until then the "needs nodes" error as well — is the build form with the
+                                     binned-SAH tree of rvpt_bvh_build, made on the device */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -234,9 +236,25 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  *   error: the call returns RVPT_HIP_OK, and rvpt_hip_last_error then holds a sentence that says so (after a PLOC tree
  *   it is empty).
  * By SAH cost the PLOC tree is at 0.65 - 0.84 of the LBVH's on the scenes of DESIGN.md 5.7; its build time and traversal
- * rate on an MI355X have not been measured yet (DESIGN.md 5.7 says what is open). */
+ * rate on an MI355X have not been measured yet (DESIGN.md 5.7 says what is open).
+ *
+ * BUILD FORM, SAH TREE — the same call with the count RVPT_HIP_NODES_BUILD_SAH:
+ *
+ *     rvpt_hip_upload_scene(ctx, NULL, RVPT_HIP_NODES_BUILD_SAH, tris, n_tris, mats, n_mats);
+ *
+ * - The tree is rvpt_bvh_build's: the top-down binned-SAH build (16 bins per axis over the centroid bounds, leaves of
+ *   2 .. 8 triangles, median splits from depth 30 on) run level by level on the device.  Node for node the triangle
+ *   sets and the boxes are those of rvpt_bvh_build; only the order of triangles inside a leaf may differ
+ *   (rvpt_amd/csrc/rvpt_build.h: THE SAH TREE holds the definition with every tie rule; rvpt_amd/scene.py: build_sah
+ *   is the same tree in numpy).  The traversal cost is 0: the device ignores RVPT_BVH_TRAVERSAL_COST.
+ * - Everything said above holds: the caller's order, device pointers, the rebuild, the atomicity rule, the update
+ *   form afterwards, brute-force contexts ignoring the count.  The three counts may alternate on one context.
+ * - The height is at most 30 + ceil(log2 n) + 1 levels; there is no fallback.  rvpt_hip_last_error is empty after a
+ *   SAH build.
+ * DESIGN.md 5.8 has what was measured (profiles/device_build_sah.txt). */
 #define RVPT_HIP_NODES_BUILD ((size_t)-1)
 #define RVPT_HIP_NODES_BUILD_PLOC ((size_t)-2)
+#define RVPT_HIP_NODES_BUILD_SAH ((size_t)-3)
 int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes,
                           const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats,
                           size_t n_mats);

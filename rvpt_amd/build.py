@@ -12,6 +12,7 @@ SOURCES = [_PKG / "csrc" / n for n in ("rvpt_kernels.hip", "rvpt_packets.hip", "
 SOURCES.append(_PKG / "csrc" / "rvpt_refit.hip")  # the geometry update's kernels: no frame kernels, hence not among KERNEL_SOURCES below (kernel_sha stands)
 SOURCES.append(_PKG / "csrc" / "rvpt_build.hip")  # the device BVH build's kernels (upload_scene's build form): likewise outside KERNEL_SOURCES
 SOURCES.append(_PKG / "csrc" / "rvpt_ploc.hip")  # the PLOC build form's kernels: likewise
+SOURCES.append(_PKG / "csrc" / "rvpt_sah.hip")  # the SAH build form's kernels: likewise
 HEADERS = [_PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
            _PKG / "csrc" / "rvpt_vis.h", _PKG.parent / "include" / "rvpt_hip.h", _PKG.parent / "include" / "rvpt_hip_lab.h"]
 
@@ -104,12 +105,13 @@ def build_leaf_variant(leaf_tris: int) -> Path:
 HOST_DIR = _PKG / "host"
 HOST_BIN_DIR = _PKG / "bin"  # git-ignored build outputs (travel to the GPU box with the snapshot)
 HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selftest": ["host_selftest.cpp", "rvpt_host.cpp"],
-                "host_selftest_build": ["host_selftest_build.cpp", "rvpt_host.cpp"], "host_selftest_build_ploc": ["host_selftest_build_ploc.cpp", "rvpt_host.cpp"]}
+                "host_selftest_build": ["host_selftest_build.cpp", "rvpt_host.cpp"], "host_selftest_build_ploc": ["host_selftest_build_ploc.cpp", "rvpt_host.cpp"],
+                "host_selftest_build_sah": ["host_selftest_build_sah.cpp", "rvpt_host.cpp"]}
 
 
 def build_host(force: bool = False) -> Path:
     """Compile the C++ host layer (rvpt_amd/host/: the mirror of the reference's class RVPT above the C ABI) with
-    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build` and `host_selftest_build_ploc`."""
+    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc` and `host_selftest_build_sah`."""
     build_native()
     HOST_BIN_DIR.mkdir(exist_ok=True)
     srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h"]

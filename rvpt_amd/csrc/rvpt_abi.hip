@@ -1078,7 +1078,8 @@ static int update_geometry(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t 
 // the device (rvpt_build.h: the specification of the tree and the stages).  It is born in the breadth-first layout the full upload makes on the host, with its
 // level table, its height and its 4-wide form; the host reads one word per level.  `tris` may be host memory or device memory of the context's GPU.
 // `ploc`: the PLOC tree (RVPT_HIP_NODES_BUILD_PLOC) instead of the LBVH between stage 3 and stage 5, with the fallback rule of rvpt_build.h.
-static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats, size_t n_mats, bool ploc)
+// `sah`: the SAH tree (RVPT_HIP_NODES_BUILD_SAH) in place of stages 1 - 4: the order of stage 3 is the index array its level loop leaves.
+static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats, size_t n_mats, bool ploc, bool sah)
 {
     int rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1116,9 +1117,14 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     // then three arrays of n + 1 words (flags A, flags B, offsets)
     const size_t words = ((static_cast<size_t>(n) + 1u) * 4u + 15u) & ~size_t(15);
     const size_t lbvh_bytes = 24u * static_cast<size_t>(n) + 3u * words;  // (a multiple of 8: the PLOC regions behind it hold 8-byte pairs)
-    const size_t scratch_bytes = lbvh_bytes + (ploc ? rv::ploc_scratch_bytes(n) : 0u);
+    const size_t scratch_bytes = sah ? std::max(lbvh_bytes, rv::sah_scratch_bytes(n)) : lbvh_bytes + (ploc ? rv::ploc_scratch_bytes(n) : 0u);
     size_t temp_bytes = 0;
     HIP_TRY(ctx, rv::build_temp_bytes(n, &temp_bytes));
+    if (sah) {
+        size_t sah_bytes = 0;
+        HIP_TRY(ctx, rv::sah_temp_bytes(n, &sah_bytes));
+        temp_bytes = std::max(temp_bytes, sah_bytes);
+    }
     const size_t node_cap = 2u * static_cast<size_t>(n) + 2u;  // 2 leaves - 1 nodes and the unused slot 1, leaves <= triangles
     if ((rc = grow(ctx, ctx->d_tris, ctx->cap_tris, n_tris, sizeof(rvpt_triangle)))) return rc;
     if ((rc = grow(ctx, ctx->d_prep, ctx->cap_prep, n_tris, sizeof(rvpt_triangle)))) return rc;
@@ -1145,13 +1151,41 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_prep, tris, n_tris * sizeof(rvpt_triangle), hipMemcpyHostToDevice, ctx->stream));
         src = ctx->d_prep;
     }
-    // stages 1-3: keys, sort, gather
-    HIP_TRY(ctx, rv::build_keys(ctx->stream, src, n, ctx->d_build_counters, keys));
-    HIP_TRY(ctx, rv::build_sort_keys(ctx->stream, ctx->d_build_temp, temp_bytes, keys, sorted, n));
-    HIP_TRY(ctx, rv::build_gather(ctx->stream, src, sorted, n, ctx->d_tris, ctx->d_perm));
-    // stage 4: the topology, level by level, straight into the device layout (root at 0, slot 1 unused, sibling pairs on even indices, upper levels first)
     std::vector<std::pair<uint32_t, uint32_t>> levels;
     const char *fell_back = nullptr;
+    if (sah) {  // the SAH tree in place of stages 1 - 4 (rvpt_build.h: THE SAH TREE): one level = decide + emit, three words read, partition
+        uint32_t height_bound = 30u + 1u;
+        while (height_bound - 31u < 32u && (1ull << (height_bound - 31u)) < n) height_bound += 1u;  // 30 + ceil(log2 n) + 1
+        height_bound = std::min(height_bound, rv::kBvhStackDepth);
+        HIP_TRY(ctx, rv::sah_begin(ctx->stream, src, n, base, ctx->d_build_counters, ctx->d_nodes));
+        uint32_t parity = 0, median_before = 0, large_seen = 0, large_base = 0, n_large = n > rv::kSahLargeNode ? 1u : 0u;  // (the root holds slot 0, as the first slot handed out will)
+        for (uint32_t begin = 0, count = 1, next_begin = 2;;) {
+            if (levels.size() >= height_bound)
+                return fail(ctx, RVPT_HIP_ERR_INVALID, "device BVH build: the SAH tree is higher than the %u levels its definition allows for %u triangles", height_bound, n);
+            const uint32_t depth = static_cast<uint32_t>(levels.size());
+            levels.emplace_back(begin, begin + count);
+            HIP_TRY(ctx, rv::sah_decide_level(ctx->stream, ctx->d_build_temp, temp_bytes, base, n, parity, depth, begin, count, next_begin, large_base, n_large, ctx->d_nodes,
+                                              static_cast<uint32_t>(node_cap), ctx->d_build_counters));
+            HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_build_counters + rv::kSahSplits, 3u * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            const uint32_t splits = h[0], median_total = h[1], large_total = h[2];
+            if (splits == 0) break;
+            if (splits > count || static_cast<size_t>(next_begin) + 2u * splits > node_cap || 2u * static_cast<uint64_t>(splits) > n)
+                return fail(ctx, RVPT_HIP_ERR_HIP, "device BVH build: a level of %u pairs does not fit the node buffer", splits);
+            HIP_TRY(ctx, rv::sah_partition_level(ctx->stream, ctx->d_build_temp, temp_bytes, base, n, parity, count, median_total - median_before));
+            median_before = median_total;
+            large_base = large_seen, n_large = large_total - large_seen, large_seen = large_total;
+            begin = next_begin, count = 2u * splits, next_begin = begin + count;
+            parity ^= 1u;
+        }
+        HIP_TRY(ctx, rv::sah_gather(ctx->stream, src, base, n, parity, ctx->d_tris, ctx->d_perm));
+    } else {
+        // stages 1-3: keys, sort, gather
+        HIP_TRY(ctx, rv::build_keys(ctx->stream, src, n, ctx->d_build_counters, keys));
+        HIP_TRY(ctx, rv::build_sort_keys(ctx->stream, ctx->d_build_temp, temp_bytes, keys, sorted, n));
+        HIP_TRY(ctx, rv::build_gather(ctx->stream, src, sorted, n, ctx->d_tris, ctx->d_perm));
+    }
+    // stage 4: the topology, level by level, straight into the device layout (root at 0, slot 1 unused, sibling pairs on even indices, upper levels first)
     if (ploc) {  // the PLOC tree in place of stage 4 (rvpt_build.h); the sorted keys stay as they are for the fallback
         unsigned char *const scratch = base + lbvh_bytes;
         uint32_t m = n, parity = 0, iterations = 0;
@@ -1223,7 +1257,7 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     HIP_TRY(ctx, hipGetLastError());
     // stage 6: can a node's (first, count) pair ride in one stack word?  (the rule of the full upload)
     uint32_t max_count = 0, head_shift = 0;
-    if (lbvh_tree) HIP_TRY(ctx, read_word(max_count, ctx->d_build_counters + rv::kBuildMaxLeaf));
+    if (lbvh_tree || sah) HIP_TRY(ctx, read_word(max_count, ctx->d_build_counters + rv::kBuildMaxLeaf));
     else max_count = 1;  // PLOC leaves hold one triangle
     {
         uint32_t shift = 1;
@@ -1294,6 +1328,7 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
         if (fell_back) fail(ctx, RVPT_HIP_OK, "device BVH build: the PLOC tree was dropped (%s), the scene holds the LBVH tree", fell_back);
         else ctx->err.clear();
     }
+    if (sah) ctx->err.clear();
     return RVPT_HIP_OK;
 }
 
@@ -1308,8 +1343,8 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     // the UPDATE FORM: triangles without nodes and without materials (as a full upload it could never succeed: no material index fits n_mats == 0)
     if (n_tris > 0 && !nodes && n_nodes == 0 && !mats && n_mats == 0) return update_geometry(ctx, tris, n_tris);
     // the BUILD FORM: no nodes and the sentinel count.  BVH contexts build the tree on the device; brute-force contexts ignore nodes and n_nodes as ever
-    if (!nodes && (n_nodes == RVPT_HIP_NODES_BUILD || n_nodes == RVPT_HIP_NODES_BUILD_PLOC)) {
-        if (is_bvh(ctx, n_tris)) return build_scene_on_device(ctx, tris, n_tris, mats, n_mats, n_nodes == RVPT_HIP_NODES_BUILD_PLOC);
+    if (!nodes && (n_nodes == RVPT_HIP_NODES_BUILD || n_nodes == RVPT_HIP_NODES_BUILD_PLOC || n_nodes == RVPT_HIP_NODES_BUILD_SAH)) {
+        if (is_bvh(ctx, n_tris)) return build_scene_on_device(ctx, tris, n_tris, mats, n_mats, n_nodes == RVPT_HIP_NODES_BUILD_PLOC, n_nodes == RVPT_HIP_NODES_BUILD_SAH);
         n_nodes = 0;
     }
     // an EMPTY scene has no tree (RVPT::initialize with no triangles): every ray misses whatever the traversal, and the

@@ -30,6 +30,30 @@
 //   bounds on trouble: PLOC promises neither a height nor an iteration count.  A tree of more than kPlocMaxHeight levels (62: the depth the BVH checks of the
 //       tests allow, inside the 64 the traversal stack walks), or one that is not finished after kPlocMaxIterations iterations, is dropped and the call
 //       builds the LBVH tree above from the same sorted keys.  A rule, not an error: rvpt_hip_last_error then says so (and is empty after a PLOC tree).
+//
+// THE SAH TREE (RVPT_HIP_NODES_BUILD_SAH; rvpt_sah.hip on the device, rvpt_amd/scene.py: build_sah in numpy — the same topology, compared bit for bit by
+// tests/test_device_build_sah.py): a restatement of build_tree in bvh_builder.cpp, level by level, with every unstable step made stable, so that node for node
+// the triangle sets and the boxes are rvpt_bvh_build's (tests/test_sah_host.py); only the order of triangles inside a leaf may differ (std::partition and
+// std::nth_element are unstable).  kSahBins = 16, kSahMinLeaf = 2, kSahMaxLeaf = 8, kSahBalanceDepth = 30, traversal cost 0: the device ignores
+// RVPT_BVH_TRAVERSAL_COST, which only the host builder reads.
+//   per triangle i (caller's index): box = fminf / fmaxf of the three vertices; centroid = (v0 + v1 + v2) * (1.0f / 3.0f), float32, left to right, no
+//       contraction; the index array starts as 0 .. n - 1.
+//   per node (a range of the index array, depth = its level): bounds and cbounds (of the centroids) are exact min / max, a NaN takes no part (a side nothing
+//       took part in stays +-FLT_MAX, the host's empty Box).  count < 2: a leaf.
+//   binning (only where depth < 30): per axis 0, 1, 2 with extent = cbounds.hi - cbounds.lo > 0: scale = 16.0f / extent (the IEEE float32 divide);
+//       bin = f >= 15 ? 15 : f >= 0 ? (int)f : 0 with f = (c - lo) * scale — the keys' rule above: a NaN gives 0, +inf gives 15, nothing leans on an undefined
+//       conversion; bin boxes and counts are exact.  The right sweep and then the left sweep as in the host code: half_area = dx * (dy + dz) + dy * dz in
+//       float32 on extents clamped at 0 (e < 0 ? 0 : e), cost = half_area * (float)count, FLT_MAX the sentinel of an empty right side; the winner is the FIRST
+//       strict minimum in (axis, bin) order.
+//   decision, with leaf_cost = half_area(bounds) * (float)count: a binned split if one was found and best_cost < leaf_cost; otherwise a leaf if count <= 8;
+//       otherwise the median split; also the median split if the binned split leaves one side empty.
+//   binned split: a STABLE partition, triangles with bin < best_bin go left and keep their relative order.
+//   median split: the widest cbounds axis (the first strict maximum, starting from -1 as the host does); the whole range SORTED by (NaN last, centroid on
+//       that axis with -0 == +0, caller's index); the left child takes the first count / 2.  (The host's nth_element selects the same sets.)
+//   layout: breadth first as above: root at 0, slot 1 unused, the children of the k-th splitting node of a level at next_begin + 2 k and + 2 k + 1; a leaf is
+//       (first = start of its range, count); perm = the final index array; boxes by refit_level.
+//   height: a binned or median split leaves both sides non-empty, a median split halves: at most 30 + ceil(log2 n) + 1 levels.  The build counts its levels and
+//       fails with a message rather than clamp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,7 +78,10 @@ enum BuildCounter : uint32_t {
     kBuildBounds = 2 /* .. 7: lo xyz, hi xyz as ordered integers */,
     kPlocRoot = 8 /* the provisional node of the PLOC tree's root */,
     kPlocIterations = 9 /* iterations in all; 0xFFFFFFFF: not finished within kPlocMaxIterations */,
-    kBuildCounters = 12
+    kSahSplits = 10 /* splitting nodes of the level just emitted */,
+    kSahMedianTris = 11 /* triangles of median-split nodes, all levels so far */,
+    kSahLargeNext = 12 /* large-node slots handed out, all levels so far */,
+    kBuildCounters = 16
 };
 
 // The PLOC tree's constants (each stated a second time in rvpt_amd/scene.py).  Radius: 16 against 8 is profiles/EXPERIMENTS.md's entry.
@@ -112,5 +139,26 @@ hipError_t ploc_finish(hipStream_t stream, unsigned char *scratch, uint32_t n_tr
 hipError_t ploc_layout_root(hipStream_t stream, const uint32_t *counters, uint32_t n_tris, uint32_t *cur, uint32_t *flags, float4 *nodes);
 hipError_t ploc_layout_level(hipStream_t stream, void *temp, size_t temp_bytes, const unsigned char *scratch, uint32_t n_tris, const uint32_t *cur, const uint32_t *flags, uint32_t *offs,
                              uint32_t begin, uint32_t count, uint32_t next_begin, uint32_t *cur_next, uint32_t *flags_next, float4 *nodes, uint32_t node_cap);
+
+
+// The SAH tree's constants (each stated a second time in rvpt_amd/scene.py; the first four are bvh_builder.cpp's).
+constexpr uint32_t kSahBins = 16, kSahMinLeaf = 2, kSahMaxLeaf = 8, kSahBalanceDepth = 30;
+// not part of the tree: a node of more than kSahLargeNode triangles is reduced by several work-groups, each over kSahChunk positions of the index array, through
+// global atomics; any other node by one wave in LDS.  kSahLargeNode >= kSahChunk is what lets a work-group meet at most two large nodes (rvpt_sah.hip: window_of).
+constexpr uint32_t kSahLargeNode = 2048, kSahChunk = 2048;
+
+// The SAH tree (rvpt_sah.hip), in place of stages 1 - 4.  scratch: sah_scratch_bytes(n) bytes, 16-byte aligned; temp: sah_temp_bytes (rocPRIM's scans and sorts).
+size_t sah_scratch_bytes(uint32_t n_tris);
+hipError_t sah_temp_bytes(uint32_t n_tris, size_t *bytes);
+// boxes, centroids, the iota, the root level; resets counters[kBuildMaxLeaf] and the three kSah counters
+hipError_t sah_begin(hipStream_t stream, const float4 *src, uint32_t n_tris, unsigned char *scratch, uint32_t *counters, float4 *nodes);
+// (a), (b), (d) of one level: its `count` nodes at device indices begin .. begin + count - 1, read from half `parity` of the level arrays; `n_large` of them hold
+// the large-node slots large_base .. large_base + n_large - 1.  counters[kSahSplits .. kSahLargeNext] when the stream gets there
+hipError_t sah_decide_level(hipStream_t stream, void *temp, size_t temp_bytes, unsigned char *scratch, uint32_t n_tris, uint32_t parity, uint32_t depth, uint32_t begin, uint32_t count,
+                            uint32_t next_begin, uint32_t large_base, uint32_t n_large, float4 *nodes, uint32_t node_cap, uint32_t *counters);
+// (c) of that level: the index array of half `parity` partitioned into the other half; n_median: triangles of its median-split nodes
+hipError_t sah_partition_level(hipStream_t stream, void *temp, size_t temp_bytes, unsigned char *scratch, uint32_t n_tris, uint32_t parity, uint32_t count, uint32_t n_median);
+// stage 3 behind the tree: build_gather with the order taken from half `parity` of the index array
+hipError_t sah_gather(hipStream_t stream, const float4 *src, const unsigned char *scratch, uint32_t n_tris, uint32_t parity, float4 *tris_out, uint32_t *perm_out);
 
 }  // namespace rv

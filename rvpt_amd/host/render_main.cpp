@@ -3,7 +3,7 @@
 // window's event loop, and writes the accumulated frame as a PFM image.
 //
 //   rvpt_render (--obj model.obj [--material-id 1] | --scene scene.obj) [--width 1024 --height 512] [--spp 1] [--bounces 8] [--frames 16] [--batch 1]
-//               [--traversal bvh|bvh_ordered|brute] [--build host|device|device-ploc] [--translate x y z] [--rotate x y z] [--fov 90] [--mode 9] [--camera-mode 0]
+//               [--traversal bvh|bvh_ordered|brute] [--build host|device|device-ploc|device-sah] [--translate x y z] [--rotate x y z] [--fov 90] [--mode 9] [--camera-mode 0]
 //               [--out frame.pfm] [--dump-prefix path]   (dump: camera block, sorted triangles, nodes, materials)
 #include <algorithm>
 #include <chrono>
@@ -74,7 +74,7 @@ int main(int argc, char **argv)
         else if (a == "--rotate") { rotate.x = static_cast<float>(std::atof(next())); rotate.y = static_cast<float>(std::atof(next())); rotate.z = static_cast<float>(std::atof(next())); }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
-    if (build != "host" && build != "device" && build != "device-ploc") { std::fprintf(stderr, "--build host|device|device-ploc\n"); return 2; }
+    if (build != "host" && build != "device" && build != "device-ploc" && build != "device-sah") { std::fprintf(stderr, "--build host|device|device-ploc|device-sah\n"); return 2; }
     if (build != "host" && !dump_prefix.empty()) { std::fprintf(stderr, "--dump-prefix needs --build host: a device-built tree has no host copy\n"); return 2; }
     if (obj.empty() && scene_obj.empty()) { std::fprintf(stderr, "usage: rvpt_render (--obj model.obj | --scene scene.obj) [options]\n"); return 2; }
     if (gpus > 1) {  // --gpus N means N devices: never a silent run on fewer (a figure labelled "gpus": N must be N GPUs' work)
@@ -98,6 +98,7 @@ int main(int argc, char **argv)
         opt.ordered_children = traversal == "bvh_ordered";
         opt.device_build = build != "host";
         opt.device_build_ploc = build == "device-ploc";
+        opt.device_build_sah = build == "device-sah";
         ranks.emplace_back(new rvpt::RVPT(width, height, opt));
         rvpt::RVPT &rvpt = *ranks.back();
         if (!scene_obj.empty()) {  // OBJ + MTL scene description: materials come from the file

@@ -182,7 +182,7 @@ bool RVPT::initialize()
     if (!check(backend_.create(&ctx_, options_.device, width_, height_, options_.tile_rank, options_.tile_world, flags), "rvpt_hip_create"))
         return false;
     if (device_built_)  // the build form: no nodes, the sentinel count, the triangles in the order they were added
-        return check(backend_.upload_scene(ctx_, nullptr, options_.device_build_ploc ? RVPT_HIP_NODES_BUILD_PLOC : RVPT_HIP_NODES_BUILD, reinterpret_cast<const rvpt_triangle *>(triangles_.data()), triangles_.size(),
+        return check(backend_.upload_scene(ctx_, nullptr, options_.device_build_sah ? RVPT_HIP_NODES_BUILD_SAH : options_.device_build_ploc ? RVPT_HIP_NODES_BUILD_PLOC : RVPT_HIP_NODES_BUILD, reinterpret_cast<const rvpt_triangle *>(triangles_.data()), triangles_.size(),
                                            reinterpret_cast<const rvpt_material *>(materials_.data()), materials_.size()),
                      "rvpt_hip_upload_scene (build form)");
     return check(backend_.upload_scene(ctx_, options_.bvh_traversal ? nodes_.data() : nullptr, options_.bvh_traversal ? nodes_.size() : 0,

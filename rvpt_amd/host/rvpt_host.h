@@ -109,6 +109,8 @@ public:
         bool device_build = false;
         // with device_build: the PLOC tree (RVPT_HIP_NODES_BUILD_PLOC) instead of the LBVH; false: the build form as it always was
         bool device_build_ploc = false;
+        // with device_build: rvpt_bvh_build's binned-SAH tree made on the device (RVPT_HIP_NODES_BUILD_SAH); wins over device_build_ploc when both are set
+        bool device_build_sah = false;
         uint32_t tile_rank = 0, tile_world = 1;
         uint32_t extra_flags = 0;   // RVPT_HIP_TIMING, RVPT_HIP_ACCUM_UNORM8, ...
     };

@@ -26,6 +26,7 @@ CULL_SKY_LIST = 0x80  # Context.cull_info: the launch took the listed path (rvpt
 TILE = 16
 TILE_SHIFT = 3  # RVPT_HIP_TILE_SHIFT: every row of the tile grid is rotated by this many more tiles than the one above (tile ownership)
 NODES_BUILD = C.c_size_t(-1).value  # RVPT_HIP_NODES_BUILD: upload_scene's node count for the build form (Context.build_scene)
+NODES_BUILD_SAH = C.c_size_t(-3).value  # RVPT_HIP_NODES_BUILD_SAH: the build form with rvpt_bvh_build's binned-SAH tree (Context.build_scene(method="sah"))
 NODES_BUILD_PLOC = C.c_size_t(-2).value  # RVPT_HIP_NODES_BUILD_PLOC: the build form with a PLOC tree (Context.build_scene(method="ploc"))
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_SIZE, ERR_COMM = -1, -2, -3, -4, -5, -6
 
@@ -348,11 +349,16 @@ class Context:
         """The build form of rvpt_hip_upload_scene (include/rvpt_hip.h): a full upload without nodes — on a BVH context the library builds the tree on the
         device (scene.build_lbvh is the same tree in numpy).  tris: float32[n, 16] in ANY order, a numpy array or — BVH contexts — a contiguous torch tensor on
         this context's device, which never visits the host; update_triangles afterwards takes the same order.  Brute-force contexts: the ordinary upload.
-        method: "lbvh", or "ploc" for the PLOC tree (scene.build_ploc in numpy), which falls back to the LBVH tree by the rule stated there.  Returns the tree
-        the scene holds, "lbvh" or "ploc" (read from rvpt_hip_last_error, where a PLOC build that fell back says so)."""
-        if method not in ("lbvh", "ploc"):
-            raise NativeError(ERR_INVALID, f"build_scene: method {method!r} is neither 'lbvh' nor 'ploc'")
-        count = NODES_BUILD_PLOC if method == "ploc" else NODES_BUILD
+        method: "lbvh", "ploc" for the PLOC tree (scene.build_ploc in numpy), which falls back to the LBVH tree by the rule stated there, or "sah" for the
+        binned-SAH tree of rvpt_bvh_build made on the device (scene.build_sah in numpy; no fallback).  Returns the tree the scene holds, "lbvh", "ploc" or "sah"
+        (for "ploc" read from rvpt_hip_last_error, where a PLOC build that fell back says so; brute-force contexts hold no tree, take "lbvh" and "ploc" as ever,
+        answer "lbvh", and refuse "sah" — at the C seam they ignore all three counts alike)."""
+        if method not in ("lbvh", "ploc", "sah"):
+            raise NativeError(ERR_INVALID, f"build_scene: method {method!r} is neither 'lbvh' nor 'ploc' nor 'sah'")
+        if method == "sah" and (self.flags & (TRAVERSAL_BVH | TRAVERSAL_BVH_ORDERED)) == 0:
+            # (the C call ignores every build count on a brute-force context; this wrapper has only ever taken the two older names there, and still does)
+            raise NativeError(ERR_INVALID, "build_scene: a brute-force context builds no tree, and there method 'sah' is neither 'lbvh' nor 'ploc', the names it takes and ignores")
+        count = {"lbvh": NODES_BUILD, "ploc": NODES_BUILD_PLOC, "sah": NODES_BUILD_SAH}[method]
         ptr, n, keep = self._triangle_source(tris, "build_scene")
         if not isinstance(keep, np.ndarray) and (self.flags & (TRAVERSAL_BVH | TRAVERSAL_BVH_ORDERED)) == 0:
             raise NativeError(ERR_INVALID, "build_scene: a brute-force context reads the triangles on the host, pass a host array")
@@ -362,7 +368,7 @@ class Context:
         del keep
         if method == "ploc" and (self.flags & (TRAVERSAL_BVH | TRAVERSAL_BVH_ORDERED)) != 0 and n > 0:
             return "lbvh" if b"LBVH tree" in (self._L.rvpt_hip_last_error(self._h) or b"") else "ploc"
-        return "lbvh"
+        return "sah" if method == "sah" else "lbvh"
 
     def update_triangles(self, tris) -> None:
         """The update form of rvpt_hip_upload_scene (include/rvpt_hip.h): the scene's triangles have moved — same count, same tree topology as the last full

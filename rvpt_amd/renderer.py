@@ -69,11 +69,12 @@ class RVPT:
                  tile_world: int = 1, flags: int = 0, build: str = "host"):
         """build: who makes the tree of a BVH traversal — "host": rvpt_bvh_build (binned SAH, the reference's builder class) and a full upload; "device": the
         library builds an LBVH on the GPU from the triangles as they were added (Context.build_scene): two orders of magnitude quicker to build, slower to
-        traverse; "device-ploc": the same with the PLOC tree (Context.build_scene(method="ploc"), scene.build_ploc)."""
+        traverse; "device-ploc": the same with the PLOC tree (Context.build_scene(method="ploc"), scene.build_ploc); "device-sah": the same with
+        rvpt_bvh_build's own binned-SAH tree made on the GPU (Context.build_scene(method="sah"), scene.build_sah)."""
         if traversal not in ("brute", "bvh", "bvh_ordered"):
             raise ValueError("traversal must be 'brute', 'bvh' (the reference's visiting order) or 'bvh_ordered'")
-        if build not in ("host", "device", "device-ploc"):
-            raise ValueError("build must be 'host', 'device' or 'device-ploc'")
+        if build not in ("host", "device", "device-ploc", "device-sah"):
+            raise ValueError("build must be 'host', 'device', 'device-ploc' or 'device-sah'")
         self.build = build
         self.width, self.height = int(width), int(height)
         self.device, self.traversal = device, traversal
@@ -108,7 +109,8 @@ class RVPT:
     @property
     def bvh_nodes(self):
         """top_level_bvh (rvpt.h:175): the tree initialize() built; after update_triangles its refit (scene.refit_bvh), made when first asked for.  With
-        build="device" / "device-ploc" the tree lives on the GPU: what is returned is the same tree stated on the host (scene.build_lbvh / build_ploc), made when first asked for."""
+        build="device" / "device-ploc" / "device-sah" the tree lives on the GPU: what is returned is the same tree stated on the host (scene.build_lbvh / build_ploc /
+        build_sah), made when first asked for."""
         self._host_statement()
         if self._nodes_stale:
             self._bvh_nodes = scene.refit_bvh(self._bvh_nodes, self.sorted_triangles)
@@ -120,10 +122,11 @@ class RVPT:
         self._bvh_nodes, self._nodes_stale = nodes, False
 
     def _host_statement(self) -> None:
-        """build="device": bvh_nodes, primitive_indices and sorted_triangles of the device-built tree, from scene.build_lbvh (build_ploc for "device-ploc") on the triangles it was built from"""
+        """build="device": bvh_nodes, primitive_indices and sorted_triangles of the device-built tree, from scene.build_lbvh (build_ploc for "device-ploc", build_sah for "device-sah") on the triangles it was built from"""
         if self._built_from is not None:
             built_from, self._built_from = self._built_from, None
-            self._bvh_nodes, self._primitive_indices = (scene.build_ploc if self.build == "device-ploc" else scene.build_lbvh)(built_from)
+            builder = {"device-ploc": scene.build_ploc, "device-sah": scene.build_sah}.get(self.build, scene.build_lbvh)
+            self._bvh_nodes, self._primitive_indices = builder(built_from)[:2]
             self._sorted_triangles = self._current_triangles[self._primitive_indices]
             self._nodes_stale = self._current_triangles is not built_from  # moved since: the boxes are refitted when the nodes are asked for
 
@@ -173,10 +176,10 @@ class RVPT:
         tris = np.concatenate(self.triangles) if self.triangles else np.zeros((0, 16), np.float32)
         mats = np.stack(self.materials) if self.materials else np.zeros((0, 12), np.float32)
         self._n_triangles = tris.shape[0]
-        self._device_built = self.build in ("device", "device-ploc") and self.traversal != "brute" and tris.shape[0] > 0
+        self._device_built = self.build in ("device", "device-ploc", "device-sah") and self.traversal != "brute" and tris.shape[0] > 0
         self._ctx = native.Context(self.width, self.height, self.device, self.tile_rank, self.tile_world, self._flags)
         if self._device_built:
-            self._ctx.build_scene(tris, mats, method="ploc" if self.build == "device-ploc" else "lbvh")
+            self._ctx.build_scene(tris, mats, method={"device-ploc": "ploc", "device-sah": "sah"}.get(self.build, "lbvh"))
             self._built_from = self._current_triangles = tris
             return True
         if tris.shape[0]:

@@ -272,6 +272,171 @@ def build_ploc(tris, radius: int = PLOC_RADIUS, info: dict | None = None):
     return refit_bvh(nodes, t[perm]), perm
 
 
+SAH_BINS = 16           # == rv::kSahBins (rvpt_amd/csrc/rvpt_build.h) == kBins of bvh_builder.cpp
+SAH_MIN_LEAF = 2        # == rv::kSahMinLeaf: below this a node is never split
+SAH_MAX_LEAF = 8        # == rv::kSahMaxLeaf: above this a node is always split
+SAH_BALANCE_DEPTH = 30  # == rv::kSahBalanceDepth: from this depth on only median splits
+
+_FLT_MAX = np.float32(np.finfo(np.float32).max)
+
+
+def _half_area(lo, hi):
+    """float32 dx * (dy + dz) + dy * dz on extents clamped at 0 (bvh_builder.cpp: Box::half_area; a NaN extent stays a NaN, as std::max(NaN, 0) does)"""
+    with np.errstate(all="ignore"):
+        d = hi - lo
+        d = np.where(d < 0, np.float32(0), d).astype(np.float32)
+        return (d[..., 0] * (d[..., 1] + d[..., 2]) + d[..., 1] * d[..., 2]).astype(np.float32)
+
+
+def _segment_min_max(lo_vals, hi_vals, starts):
+    """exact min of lo_vals / max of hi_vals per contiguous non-empty segment; a NaN takes no part, an all-NaN segment gives +-FLT_MAX (the host's Box)"""
+    with np.errstate(all="ignore"):
+        lo = np.fmin.reduceat(np.where(np.isnan(lo_vals), _FLT_MAX, lo_vals), starts, axis=0)
+        hi = np.fmax.reduceat(np.where(np.isnan(hi_vals), -_FLT_MAX, hi_vals), starts, axis=0)
+    return np.minimum(lo, _FLT_MAX), np.maximum(hi, -_FLT_MAX)
+
+
+def build_sah(tris, balance_depth: int = SAH_BALANCE_DEPTH):
+    """The tree rvpt_hip_upload_scene's SAH BUILD FORM (RVPT_HIP_NODES_BUILD_SAH) makes on the device, in numpy — the second statement of "THE SAH TREE" in
+    rvpt_amd/csrc/rvpt_build.h: rvpt_bvh_build's top-down binned-SAH build (bvh_builder.cpp: 16 bins per axis over the centroid bounds, leaves of 2 .. 8,
+    traversal cost 0, median splits from depth 30 on) run level by level with every unstable step made stable.  Node for node it is the host builder's tree —
+    the same triangle sets, the same boxes; only the order of triangles inside a leaf may differ (tests/test_sah_host.py).
+
+    Per node (a range of the index array): exact bounds and centroid bounds; where depth < balance_depth, per axis 0, 1, 2 with extent > 0 the triangles are
+    binned by f = (c - lo) * (16.0f / extent), bin = f >= 15 ? 15 : f >= 0 ? (int)f : 0, and the two sweeps of the host code pick the FIRST strict minimum of
+    the cost in (axis, bin) order.  A binned split (cost < half_area(bounds) * count) is a STABLE partition by bin < best_bin; otherwise a node of <= 8 is a
+    leaf; otherwise — and when a binned split leaves a side empty — the range is SORTED by (NaN last, centroid on the widest centroid axis with -0 == +0,
+    caller's index) and cut at count / 2.  Layout as build_lbvh's: breadth first, the children of the k-th splitting node of a level at next_begin + 2 k.
+
+    tris: float32[n, 16] in the CALLER'S order, n >= 1.  Returns (nodes, perm, info) with upload_scene(nodes, tris[perm], mats) the scene the form uploads and
+    info = {height, binned_splits, median_splits, max_leaf}."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    n = t.shape[0]
+    if n == 0:
+        raise ValueError("build_sah: no triangles")
+    v = t.reshape(-1, 4, 4)[:, :3, :3]
+    third = np.float32(1.0) / np.float32(3.0)
+    with np.errstate(all="ignore"):
+        tlo, thi = np.fmin.reduce(v, axis=1), np.fmax.reduce(v, axis=1)  # a NaN coordinate takes no part (fminf / fmaxf)
+        cent = (((v[:, 0] + v[:, 1]) + v[:, 2]) * third).astype(np.float32)  # float32, left to right
+    idx = np.arange(n, dtype=np.int64)
+    begin, count = np.zeros(1, dtype=np.int64), np.full(1, n, dtype=np.int64)
+    firsts, counts = [], []
+    next_index, depth = 1, 0
+    info = {"height": 0, "binned_splits": 0, "median_splits": 0, "max_leaf": 0}
+    max_height = 30 + int(np.ceil(np.log2(n))) + 1 if balance_depth == SAH_BALANCE_DEPTH else 64
+    while begin.size:
+        if depth >= max_height:
+            raise ValueError(f"build_sah: the tree is higher than {max_height} levels")
+        m = begin.size
+        kind = np.zeros(m, dtype=np.int8)  # 0 leaf, 1 binned, 2 median
+        n_left = np.zeros(m, dtype=np.int64)
+        act = np.flatnonzero(count >= SAH_MIN_LEAF)
+        if act.size:
+            k = act.size
+            cnt = count[act]
+            starts = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+            seg = np.repeat(np.arange(k, dtype=np.int64), cnt)
+            pos = np.repeat(begin[act] - starts, cnt) + np.arange(seg.size, dtype=np.int64)  # positions of the index array, node after node
+            ti = idx[pos]
+            blo, bhi = _segment_min_max(tlo[ti], thi[ti], starts)
+            clo, chi = _segment_min_max(cent[ti], cent[ti], starts)
+            best_cost = np.full(k, _FLT_MAX, dtype=np.float32)
+            best_axis = np.full(k, -1, dtype=np.int64)
+            best_bin = np.zeros(k, dtype=np.int64)
+            bins_of = np.zeros((3, seg.size), dtype=np.int64)
+            with np.errstate(all="ignore"):
+                ext = (chi - clo).astype(np.float32)
+                scale = (np.float32(SAH_BINS) / ext).astype(np.float32)
+                for ax in range(3 if depth < balance_depth else 0):
+                    live = ext[:, ax] > 0
+                    if not live.any():
+                        continue
+                    f = ((cent[ti, ax] - clo[seg, ax]) * scale[seg, ax]).astype(np.float32)
+                    b = np.zeros(seg.size, dtype=np.int64)
+                    inside = (f >= 0) & (f < SAH_BINS - 1)
+                    b[inside] = f[inside].astype(np.int32)
+                    b[f >= SAH_BINS - 1] = SAH_BINS - 1
+                    bins_of[ax] = b
+                    key = seg * SAH_BINS + b
+                    order = np.argsort(key, kind="stable")
+                    sk = key[order]
+                    first_of = np.flatnonzero(np.concatenate([[True], sk[1:] != sk[:-1]]))
+                    present = sk[first_of]
+                    bin_lo = np.full((k * SAH_BINS, 3), _FLT_MAX, dtype=np.float32)
+                    bin_hi = np.full((k * SAH_BINS, 3), -_FLT_MAX, dtype=np.float32)
+                    bin_lo[present], bin_hi[present] = _segment_min_max(tlo[ti[order]], thi[ti[order]], first_of)
+                    bin_cnt = np.bincount(key, minlength=k * SAH_BINS).astype(np.int64).reshape(k, SAH_BINS)
+                    bin_lo, bin_hi = bin_lo.reshape(k, SAH_BINS, 3), bin_hi.reshape(k, SAH_BINS, 3)
+                    right_cost = np.full((k, SAH_BINS), _FLT_MAX, dtype=np.float32)
+                    alo, ahi = np.full((k, 3), _FLT_MAX, dtype=np.float32), np.full((k, 3), -_FLT_MAX, dtype=np.float32)
+                    c = np.zeros(k, dtype=np.int64)
+                    for bn in range(SAH_BINS - 1, 0, -1):
+                        alo, ahi = np.minimum(alo, bin_lo[:, bn]), np.maximum(ahi, bin_hi[:, bn])
+                        c = c + bin_cnt[:, bn]
+                        right_cost[:, bn] = np.where(c > 0, (_half_area(alo, ahi) * c.astype(np.float32)).astype(np.float32), _FLT_MAX)
+                    alo, ahi = np.full((k, 3), _FLT_MAX, dtype=np.float32), np.full((k, 3), -_FLT_MAX, dtype=np.float32)
+                    c = np.zeros(k, dtype=np.int64)
+                    for bn in range(SAH_BINS - 1):
+                        alo, ahi = np.minimum(alo, bin_lo[:, bn]), np.maximum(ahi, bin_hi[:, bn])
+                        c = c + bin_cnt[:, bn]
+                        cost = ((_half_area(alo, ahi) * c.astype(np.float32)).astype(np.float32) + right_cost[:, bn + 1]).astype(np.float32)
+                        better = live & (c > 0) & (right_cost[:, bn + 1] != _FLT_MAX) & (cost < best_cost)
+                        best_cost = np.where(better, cost, best_cost)
+                        best_axis = np.where(better, ax, best_axis)
+                        best_bin = np.where(better, bn + 1, best_bin)
+                leaf_cost = (_half_area(blo, bhi) * cnt.astype(np.float32)).astype(np.float32)
+                binned = (best_axis >= 0) & (best_cost < leaf_cost)
+            goes_left = np.zeros(seg.size, dtype=bool)
+            if binned.any():
+                goes_left = binned[seg] & (bins_of[np.maximum(best_axis, 0)[seg], np.arange(seg.size)] < best_bin[seg])
+            nl = np.bincount(seg, weights=goes_left, minlength=k).astype(np.int64)
+            binned &= (nl > 0) & (nl < cnt)  # a side left empty: the median split
+            median = ~binned & ((cnt > SAH_MAX_LEAF) | ((best_axis >= 0) & (best_cost < leaf_cost)))
+            kind[act] = np.where(binned, 1, np.where(median, 2, 0))
+            n_left[act] = np.where(binned, nl, cnt // 2)
+            # the widest centroid axis: the first strict maximum, from -1
+            with np.errstate(all="ignore"):
+                widest, m_axis = np.full(k, -1.0, dtype=np.float32), np.zeros(k, dtype=np.int64)
+                for ax in range(3):
+                    w = ext[:, ax] > widest
+                    widest, m_axis = np.where(w, ext[:, ax], widest), np.where(w, ax, m_axis)
+            # one stable sort of every position of a splitting node: binned nodes by (node, goes right), median nodes by (node, NaN, value, index)
+            split_pos = binned[seg] | median[seg]
+            if split_pos.any():
+                sp = np.flatnonzero(split_pos)
+                s_seg, s_ti = seg[sp], ti[sp]
+                val = cent[s_ti, m_axis[s_seg]]
+                is_nan = np.isnan(val)
+                med = median[s_seg]
+                with np.errstate(all="ignore"):
+                    k1 = np.where(med, is_nan.astype(np.int64), (~goes_left[sp]).astype(np.int64))
+                    k2 = np.where(med & ~is_nan, val + np.float32(0), np.float32(0))  # -0 + 0 = +0
+                    k3 = np.where(med, s_ti, 0)
+                order = np.lexsort((k3, k2, k1, s_seg))  # stable: equal keys keep their order
+                idx[pos[sp]] = s_ti[order]
+        leaf = kind == 0
+        info["binned_splits"] += int((kind == 1).sum())
+        info["median_splits"] += int((kind == 2).sum())
+        if leaf.any():
+            info["max_leaf"] = max(info["max_leaf"], int(count[leaf].max()))
+        n_split = int((~leaf).sum())
+        first = begin.copy()
+        first[~leaf] = next_index + 2 * np.arange(n_split, dtype=np.int64)
+        firsts.append(first)
+        counts.append(np.where(leaf, count, 0))
+        next_index += 2 * n_split
+        sb, sc, sl = begin[~leaf], count[~leaf], n_left[~leaf]
+        begin = np.stack([sb, sb + sl], axis=1).reshape(-1)
+        count = np.stack([sl, sc - sl], axis=1).reshape(-1)
+        depth += 1
+    info["height"] = depth
+    perm = idx.astype(np.uint32)
+    nodes = np.zeros(next_index, dtype=NODE_DTYPE)
+    nodes["first"], nodes["count"] = np.concatenate(firsts), np.concatenate(counts)
+    return refit_bvh(nodes, t[perm]), perm, info
+
+
 def wobble(tris, phase: float, amplitude: float) -> np.ndarray:
     """A smooth deformation for moving-geometry demos, tests and tools/refit_bench.py: every vertex is displaced by a function of its own position and `phase`
     alone (three sines of the other two coordinates), so vertices that coincide stay welded; |displacement| <= amplitude * sqrt(3).  The .w lanes and the

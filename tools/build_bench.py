@@ -2,7 +2,10 @@
 """Run on the GPU box: what a REBUILD of the 1 M-triangle terrain's tree costs (BVH context, 1920x1080) by the build form of rvpt_hip_upload_scene against the
 only route there was before it — rvpt_bvh_build + permute + a full upload_scene — and against the floor, a bare host-to-device copy of the same 64 MB; then
 what traversal pays on the device-built LBVH against the binned-SAH tree of rvpt_bvh_build and against a refitted tree.  -> stdout (profiles/device_build.txt)
-usage: tools/build_bench.py [--method lbvh|ploc] [all|builds|traversal|stages <kernel_stats.csv> [n_builds]]
+usage: tools/build_bench.py [--method lbvh|ploc|sah] [all|builds|traversal|stages <kernel_stats.csv> [n_builds]]
+    --method sah: rvpt_bvh_build's binned-SAH tree made on the device (profiles/device_build_sah.txt).  all: its build time beside the LBVH's and
+        the host route's in the same run (asserted: from a device tensor below the host route's); traversal: four trees interleaved — SAH-device, PLOC, LBVH,
+        rvpt_bvh_build's — one context each
     --method ploc: the PLOC tree of the build form (DESIGN.md 5.7, profiles/device_build_ploc.txt).  all: its build time beside the LBVH's in the same run;
         builds: PLOC builds; traversal: three trees interleaved on one box — PLOC, LBVH, rvpt_bvh_build's — one context each, a repetition of each in turn
     builds: one upload and a few device builds from a device tensor, nothing else — the run to put under rocprofv3 --kernel-trace --stats
@@ -27,10 +30,12 @@ if "--method" in sys.argv:
     at = sys.argv.index("--method")
     METHOD = sys.argv[at + 1]
     del sys.argv[at:at + 2]
-    if METHOD not in ("lbvh", "ploc"):
-        sys.exit("--method lbvh|ploc")
+    if METHOD not in ("lbvh", "ploc", "sah"):
+        sys.exit("--method lbvh|ploc|sah")
 
-STAGES = {"ploc_init": "PLOC clusters", "ploc_nearest": "PLOC nearest neighbour", "ploc_keep": "PLOC merge + compaction", "ploc_merge": "PLOC merge + compaction", "ploc_tail": "PLOC tail (one work-group)",
+STAGES = {"sah_init": "SAH boxes, centroids, iota", "sah_large": "SAH node + bin reduction (large nodes)", "sah_decide": "SAH node + bin reduction (one wave per node) and decision",
+          "sah_emit": "SAH emit", "sah_flags": "SAH partition", "sah_scatter": "SAH partition", "sah_median": "SAH median sort", "gather_records_by_index": "gather",
+          "ploc_init": "PLOC clusters", "ploc_nearest": "PLOC nearest neighbour", "ploc_keep": "PLOC merge + compaction", "ploc_merge": "PLOC merge + compaction", "ploc_tail": "PLOC tail (one work-group)",
           "layout_root": "topology", "layout_level": "topology", "validate_materials": "validate", "reset_counters": "keys", "centroid_bounds": "keys", "make_keys": "keys", "gather_records": "gather", "root_level": "topology",
           "emit_level": "topology", "refit_level": "boxes", "wide_root": "wide form", "wide_pick": "wide form", "wide_emit": "wide form", "wide_heads": "wide form",
           "wide_need": "wide form", "refit_wide_gather": "wide form", "prepare_triangles": "prepare", "prepare_materials": "prepare",
@@ -172,13 +177,27 @@ if what == "all":
         pd = timed(ploc_dev, 20, warm=3)
         print(f"PLOC build form (torch tensor)         {spread(pd)}")
         print(f"PLOC / LBVH build time: host array {statistics.median(ph) / statistics.median(bh):.2f}, device tensor {statistics.median(pd) / statistics.median(bd):.2f}")
+    if METHOD == "sah":
+        def sah_host():
+            ctx.build_scene(poses[k[0] % 2], mats, method="sah"); k[0] += 1
+        def sah_dev():
+            ctx.build_scene(dev[k[0] % 2], mats, method="sah"); k[0] += 1
+        sh = timed(sah_host, 20, warm=3)
+        print(f"SAH build form (host numpy array)      {spread(sh)}")
+        sd = timed(sah_dev, 20, warm=3)
+        print(f"SAH build form (torch tensor)          {spread(sd)}")
+        print(f"SAH / LBVH build time: host array {statistics.median(sh) / statistics.median(bh):.2f}, device tensor {statistics.median(sd) / statistics.median(bd):.2f}; "
+              f"host route / SAH from a device tensor {statistics.median(base) / statistics.median(sd):.1f}")
+        assert statistics.median(sd) < statistics.median(base), "the SAH build form from a device pointer must take less wall time than the host route"
     m_b, m_h, m_d, m_f = (statistics.median(x) for x in (base, bh, bd, fl))
     print(f"summary: build form from a host array {m_h * 1e3:.2f} ms = {m_b / m_h:.1f} x faster than rvpt_bvh_build + upload ({m_b * 1e3:.0f} ms), {m_h / m_f:.2f} x the 64 MB copy floor "
           f"({m_f * 1e3:.2f} ms); from a device tensor {m_d * 1e3:.2f} ms")
     assert m_h < m_b, "the build form from a host array must take less wall time than the host route"
     del dev, dst64
 
-if METHOD == "ploc":
+if METHOD == "sah":
+    print("\n== traversal: rvpt_bvh_build's tree made on the device (SAH-device) against the PLOC tree, the LBVH and the host-built tree (one-frame launches, Msamples/s) ==")
+elif METHOD == "ploc":
     print(f"\n== traversal: the PLOC tree (radius {scene.PLOC_RADIUS}, leaves of 1) against the LBVH (leaves of <= {scene.LBVH_LEAF_TRIS}) and rvpt_bvh_build's binned-SAH tree (one-frame launches, Msamples/s) ==")
 else:
     print(f"\n== traversal: the device-built LBVH (leaves of <= {os.environ.get('LEAF_TRIS', scene.LBVH_LEAF_TRIS)}) against rvpt_bvh_build's binned-SAH tree (one-frame launches, Msamples/s) ==")
@@ -187,7 +206,9 @@ def compare_three(name, tris, ms, c, w, h, amps=()):
     e = float(np.ptp(tris.reshape(-1, 4, 4)[:, :3, :3].reshape(-1, 3), axis=0).max())
     for amp in (0.0,) + tuple(amps):
         pose = scene.wobble(tris, 1.4, amp * e) if amp else tris
-        cxs = {k_: native.Context(w, h, 0, 0, 1, native.TRAVERSAL_BVH) for k_ in ("ploc", "lbvh", "host")}
+        cxs = {k_: native.Context(w, h, 0, 0, 1, native.TRAVERSAL_BVH) for k_ in (("sah",) if METHOD == "sah" else ()) + ("ploc", "lbvh", "host")}
+        if METHOD == "sah":
+            t0 = time.perf_counter(); cxs["sah"].build_scene(pose, ms, method="sah"); t_sah = time.perf_counter() - t0
         t0 = time.perf_counter(); tree = cxs["ploc"].build_scene(pose, ms, method="ploc"); t_ploc = time.perf_counter() - t0
         t0 = time.perf_counter(); cxs["lbvh"].build_scene(pose, ms); t_lbvh = time.perf_counter() - t0
         t0 = time.perf_counter(); n2, i2 = native.build_bvh(pose); cxs["host"].upload_scene(n2, pose[i2], ms); t_host = time.perf_counter() - t0
@@ -201,6 +222,10 @@ def compare_three(name, tris, ms, c, w, h, amps=()):
         pad = f"{'':{len(name) + 18}}"
         line = (f"{name}, amplitude {amp:4.2f}: PLOC ({tree})  {rates(got['ploc'])}\n{pad}LBVH         {rates(got['lbvh'])}\n{pad}host-built   {rates(got['host'])}\n"
                 f"{pad}PLOC / LBVH = {med['ploc'] / med['lbvh']:.3f}   PLOC / host = {med['ploc'] / med['host']:.3f}   LBVH / host = {med['lbvh'] / med['host']:.3f}")
+        if METHOD == "sah":
+            line = (f"{name}, amplitude {amp:4.2f}: SAH-device   {rates(got['sah'])}\n{pad}" + line.split(": ", 1)[1] +
+                    f"\n{pad}SAH-device / host = {med['sah'] / med['host']:.3f}   (five rounds; host-built spread {min(got['host']) / med['host']:.3f} .. {max(got['host']) / med['host']:.3f} of its median)"
+                    f"\n{pad}rebuild {t_sah * 1e3:.1f} ms (SAH-device, first call of a context) vs {t_host * 1e3:.1f} ms (host)")
         for label, t_dev, r in (("PLOC", t_ploc, med["ploc"]), ("LBVH", t_lbvh, med["lbvh"])):
             per_dev, per_host = w * h / r / 1e6, w * h / med["host"] / 1e6
             line += f"\n{pad}rebuild {t_dev * 1e3:.1f} ms ({label}, first call of a context) vs {t_host * 1e3:.1f} ms (host): "
@@ -209,7 +234,7 @@ def compare_three(name, tris, ms, c, w, h, amps=()):
 
 
 def compare(name, tris, ms, c, w, h, amps=()):
-    if METHOD == "ploc":
+    if METHOD in ("ploc", "sah"):
         return compare_three(name, tris, ms, c, w, h, amps)
     cx = native.Context(w, h, 0, 0, 1, native.TRAVERSAL_BVH)
     e = float(np.ptp(tris.reshape(-1, 4, 4)[:, :3, :3].reshape(-1, 3), axis=0).max())

@@ -50,7 +50,9 @@ extern "C" {
                                      is the BUILD FORM (the library builds the tree on the device from the triangles alone).  Still 8, no new symbol: the
                                      count RVPT_HIP_NODES_BUILD_PLOC — until then the "needs nodes" error too — is the build form with a PLOC tree.  Still 8, no
                                      new symbol: the count RVPT_HIP_NODES_BUILD_SAH — until then the "needs nodes" error as well — is the build form with the
-                                     binned-SAH tree of rvpt_bvh_build, made on the device */
+                                     binned-SAH tree of rvpt_bvh_build, made on the device.  Still 8, no new symbol: `dst` of rvpt_hip_read and
+                                     `src_rgba32f` of rvpt_hip_write_accum may be DEVICE MEMORY of the context's GPU — until then undefined — and the frame
+                                     then never visits the host */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -293,7 +295,15 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  *     per-tile radiance is gathered to rank 0 over RCCL and un-tiled there; rank 0 receives the whole frame, the other ranks
  *     only send (their dst may be NULL and is not written).  In a single-process group only rank 0's context is called;
  *   - without one, pixels of tiles this rank does not own read as 0 (a host doing its own exchange uses
- *     rvpt_hip_tile_buffer / rvpt_hip_untile). */
+ *     rvpt_hip_tile_buffer / rvpt_hip_untile).
+ * FRAMES THAT STAY ON THE DEVICE: `dst` may be device memory of the context's GPU (hipMalloc: a torch tensor's storage, say; pinned and managed memory
+ * count as host memory, as for the triangles of rvpt_hip_upload_scene).  Both formats; the bytes written are exactly the bytes a host read of the same
+ * state returns.  Without a communicator the un-tiling kernel writes straight into `dst` (RGBA8: un-tiled and quantised in one kernel) — no staging
+ * buffer, no second copy; with one, rank 0 gathers as for a host read and the frame (RGBA8: quantised) goes from the staging buffer into `dst` on the
+ * device, and the rule that rank 0 takes part in the exchange before it reports its own bad argument stays.  `dst` need only be 4-byte aligned.  The
+ * call still implies rvpt_hip_wait and returns only after the context's stream has finished writing `dst`: the caller may then read it from any stream
+ * of its own.  dst_bytes too small is RVPT_HIP_ERR_SIZE, device memory of another GPU RVPT_HIP_ERR_INVALID (the message names both devices), so is
+ * device memory that is not 4-byte aligned; in every such case `dst` is untouched. */
 int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes);
 
 /* ---- multi-GPU: one RCCL communicator over the tile_world ranks of a partitioned image (no reference counterpart: the
@@ -343,7 +353,9 @@ int rvpt_hip_untile(rvpt_hip_ctx *ctx, const void *gathered_dev, size_t slot_byt
                     uint32_t n_ranks, void *dst_dev_rgba32f);
 
 /* Restore / snapshot the accumulator from host memory (row-major RGBA32F); enables resume of a
- * long accumulation.  (No reference counterpart: its temporal image dies with the process.) */
+ * long accumulation.  (No reference counterpart: its temporal image dies with the process.)
+ * `src_rgba32f` may be device memory of the context's GPU (4-byte aligned; classified as for rvpt_hip_read): the tiling kernel reads it directly, the
+ * caller guarantees that whatever wrote it has finished.  Device memory of another GPU is RVPT_HIP_ERR_INVALID, naming both devices. */
 int rvpt_hip_write_accum(rvpt_hip_ctx *ctx, const void *src_rgba32f, size_t src_bytes);
 
 /* Timing + counters (replaces Timer, src/rvpt/timer.cpp:15-46).  kernel_ms_last: hipEvent time

@@ -13,7 +13,8 @@ SOURCES.append(_PKG / "csrc" / "rvpt_refit.hip")  # the geometry update's kernel
 SOURCES.append(_PKG / "csrc" / "rvpt_build.hip")  # the device BVH build's kernels (upload_scene's build form): likewise outside KERNEL_SOURCES
 SOURCES.append(_PKG / "csrc" / "rvpt_ploc.hip")  # the PLOC build form's kernels: likewise
 SOURCES.append(_PKG / "csrc" / "rvpt_sah.hip")  # the SAH build form's kernels: likewise
-HEADERS = [_PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
+SOURCES.append(_PKG / "csrc" / "rvpt_frames.hip")  # rvpt_hip_read / write_accum on 4-byte aligned device memory: layout kernels, likewise
+HEADERS = [_PKG / "csrc" / "rvpt_frames.h", _PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
            _PKG / "csrc" / "rvpt_vis.h", _PKG.parent / "include" / "rvpt_hip.h", _PKG.parent / "include" / "rvpt_hip_lab.h"]
 
 # -ffp-contract=off: the arithmetic specification fixes where FMAs happen; applies to the
@@ -106,12 +107,20 @@ HOST_DIR = _PKG / "host"
 HOST_BIN_DIR = _PKG / "bin"  # git-ignored build outputs (travel to the GPU box with the snapshot)
 HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selftest": ["host_selftest.cpp", "rvpt_host.cpp"],
                 "host_selftest_build": ["host_selftest_build.cpp", "rvpt_host.cpp"], "host_selftest_build_ploc": ["host_selftest_build_ploc.cpp", "rvpt_host.cpp"],
-                "host_selftest_build_sah": ["host_selftest_build_sah.cpp", "rvpt_host.cpp"]}
+                "host_selftest_build_sah": ["host_selftest_build_sah.cpp", "rvpt_host.cpp"],
+                "host_selftest_frames": ["host_selftest_frames.cpp", "rvpt_host.cpp"]}
+HOST_NEEDS_HIP = {"host_selftest_frames"}  # targets that allocate device memory themselves (its `--gpu` case): HIP's host API, still compiled by g++
+
+
+def _hip_host_flags() -> list:
+    """g++ flags for a host program that calls the HIP runtime's C API itself: the headers and libamdhip64 of the ROCm tree hipcc belongs to."""
+    rocm = Path(hipcc()).resolve().parent.parent
+    return ["-D__HIP_PLATFORM_AMD__", f"-I{rocm / 'include'}", f"-L{rocm / 'lib'}", "-lamdhip64", f"-Wl,-rpath,{rocm / 'lib'}"]
 
 
 def build_host(force: bool = False) -> Path:
     """Compile the C++ host layer (rvpt_amd/host/: the mirror of the reference's class RVPT above the C ABI) with
-    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc` and `host_selftest_build_sah`."""
+    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah` and `host_selftest_frames`."""
     build_native()
     HOST_BIN_DIR.mkdir(exist_ok=True)
     srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h"]
@@ -121,7 +130,7 @@ def build_host(force: bool = False) -> Path:
         if not force and out.exists() and out.stat().st_mtime >= newest:
             continue
         cmd = [shutil.which("g++") or "g++", "-O2", "-std=c++17", "-Wall", "-Wextra", *[str(HOST_DIR / f) for f in files], "-o", str(out),
-               f"-L{_PKG}", "-lrvpt_hip", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib"]
+               f"-L{_PKG}", "-lrvpt_hip", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", *(_hip_host_flags() if name in HOST_NEEDS_HIP else [])]
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:
             raise RuntimeError("g++ failed:\n" + " ".join(cmd) + "\n" + res.stdout + res.stderr)

@@ -28,6 +28,7 @@
 #include "rvpt_kernels.h"
 #include "bvh_wide.h"
 #include "rvpt_refit.h"
+#include "rvpt_frames.h"
 #include "rvpt_build.h"
 #include "rvpt_packets.h"
 #include "rvpt_math.h"
@@ -1020,6 +1021,21 @@ static bool is_device_pointer(const void *p)
         return false;
     }
     return attr.type == hipMemoryTypeDevice;
+}
+
+// The frame pointer of rvpt_hip_read / rvpt_hip_write_accum (`what`: "dst" / "src"): host memory, or device memory of the context's GPU, which the layout kernels
+// then write or read in place.  Device memory of another GPU and device memory that is not 4-byte aligned are refused before anything touches them.
+static int classify_frame_pointer(rvpt_hip_ctx *ctx, const void *p, const char *what, bool *device)
+{
+    *device = is_device_pointer(p);
+    if (!*device) return RVPT_HIP_OK;
+    hipPointerAttribute_t attr{};
+    HIP_TRY(ctx, hipPointerGetAttributes(&attr, p));
+    if (attr.device != ctx->device)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "%s is device memory of GPU %d, the context lives on GPU %d: a frame stays on the context's own device", what, attr.device, ctx->device);
+    if (reinterpret_cast<uintptr_t>(p) % 4u)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "%s is device memory at %p: a frame on the device needs 4-byte alignment", what, p);
+    return RVPT_HIP_OK;
 }
 
 // The update form of rvpt_hip_upload_scene (include/rvpt_hip.h): same triangle count and tree topology as the last full upload, new vertex positions.  Takes the
@@ -2078,7 +2094,9 @@ int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
     else if (dst_bytes < need)
         arg_rc = fail(ctx, RVPT_HIP_ERR_SIZE, "dst holds %zu bytes, frame needs %zu", dst_bytes, need);
     if (arg_rc == RVPT_HIP_OK && hipSetDevice(ctx->device) != hipSuccess) arg_rc = fail(ctx, RVPT_HIP_ERR_HIP, "hipSetDevice failed");
-    if (arg_rc == RVPT_HIP_OK) arg_rc = ensure_rowmajor(ctx);
+    bool device_dst = false;  // dst is device memory of this GPU: the layout kernels write it in place, the frame never visits the host
+    if (arg_rc == RVPT_HIP_OK) arg_rc = classify_frame_pointer(ctx, dst, "dst", &device_dst);
+    if (arg_rc == RVPT_HIP_OK && (collective || !device_dst)) arg_rc = ensure_rowmajor(ctx);
     if (arg_rc != RVPT_HIP_OK) {
         if (collective) {
             const std::string keep = ctx->err;
@@ -2090,6 +2108,17 @@ int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
     int rc = RVPT_HIP_OK;
     if (collective) {
         if ((rc = gather_to_root(ctx, static_cast<float4 *>(ctx->d_rowmajor)))) return rc;
+        if (device_dst) {  // the gathered frame leaves d_rowmajor for dst on the device: quantised on the way, or as it is (a byte copy: dst may be 4-byte aligned only)
+            if (format == RVPT_HIP_FORMAT_RGBA8_UNORM) {
+                hipLaunchKernelGGL(rv::quantize_rowmajor, dim3(static_cast<uint32_t>((px + 255) / 256)), dim3(256), 0, ctx->stream,
+                                   static_cast<const float4 *>(ctx->d_rowmajor), static_cast<uint32_t>(px), static_cast<uint32_t *>(dst));
+                HIP_TRY(ctx, hipGetLastError());
+            } else {
+                HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->d_rowmajor, need, hipMemcpyDeviceToDevice, ctx->stream));
+            }
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            return RVPT_HIP_OK;
+        }
         const void *src = ctx->d_rowmajor;
         if (format == RVPT_HIP_FORMAT_RGBA8_UNORM) {
             if (!ctx->d_quant) HIP_TRY(ctx, hipMalloc(&ctx->d_quant, px * 4));
@@ -2103,6 +2132,17 @@ int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
         return RVPT_HIP_OK;
     }
     const dim3 blk(64, 4), grd((ctx->width + 63) / 64, (ctx->height + 3) / 4);
+    if (device_dst) {  // un-tiled (and quantised) straight into dst: no d_rowmajor, no second copy
+        const bool as_rgba8 = format == RVPT_HIP_FORMAT_RGBA8_UNORM;
+        if (as_rgba8 || reinterpret_cast<uintptr_t>(dst) % 16u == 0)  // (rgba8: 4-byte stores; RGBA32F: read_rowmajor stores a pixel as one float4)
+            hipLaunchKernelGGL(rv::read_rowmajor, grd, blk, 0, ctx->stream, ctx->d_accum, ctx->width, ctx->height, ctx->tiles_x, ctx->tile_rank, ctx->tile_world, as_rgba8 ? 1 : 0, dst);
+        else
+            hipLaunchKernelGGL(rv::read_rowmajor_dwords, dim3((4u * ctx->width + 63) / 64, grd.y), blk, 0, ctx->stream, reinterpret_cast<const float *>(ctx->d_accum), ctx->width,
+                               ctx->height, ctx->tiles_x, ctx->tile_rank, ctx->tile_world, static_cast<float *>(dst));
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the caller may read dst from any stream of its own on return
+        return RVPT_HIP_OK;
+    }
     hipLaunchKernelGGL(rv::read_rowmajor, grd, blk, 0, ctx->stream, ctx->d_accum, ctx->width, ctx->height, ctx->tiles_x,
                        ctx->tile_rank, ctx->tile_world, format == RVPT_HIP_FORMAT_RGBA8_UNORM ? 1 : 0, ctx->d_rowmajor);
     HIP_TRY(ctx, hipGetLastError());
@@ -2335,8 +2375,23 @@ int rvpt_hip_write_accum(rvpt_hip_ctx *ctx, const void *src_rgba32f, size_t src_
     if (!src_rgba32f) return fail(ctx, RVPT_HIP_ERR_INVALID, "src is NULL");
     if (src_bytes < need) return fail(ctx, RVPT_HIP_ERR_SIZE, "src holds %zu bytes, frame needs %zu", src_bytes, need);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_rowmajor(ctx);
+    bool device_src = false;
+    int rc = classify_frame_pointer(ctx, src_rgba32f, "src", &device_src);
     if (rc) return rc;
+    if (device_src) {  // tiled straight from the caller's device memory (whatever wrote it has finished: the caller's word); no staging buffer
+        if (ctx->n_work) {
+            if (reinterpret_cast<uintptr_t>(src_rgba32f) % 16u == 0)
+                hipLaunchKernelGGL(rv::tile_rgba32f, dim3((ctx->n_work + 255) / 256), dim3(256), 0, ctx->stream, static_cast<const float4 *>(src_rgba32f), ctx->width, ctx->height,
+                                   ctx->tiles_x, ctx->tile_rank, ctx->tile_world, ctx->n_work, ctx->d_accum);
+            else  // (tile_rgba32f loads a pixel as one float4)
+                hipLaunchKernelGGL(rv::tile_rgba32f_dwords, dim3((ctx->n_work + 63) / 64), dim3(256), 0, ctx->stream, static_cast<const float *>(src_rgba32f), ctx->width, ctx->height,
+                                   ctx->tiles_x, ctx->tile_rank, ctx->tile_world, ctx->n_work, reinterpret_cast<float *>(ctx->d_accum));
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return RVPT_HIP_OK;
+    }
+    if ((rc = ensure_rowmajor(ctx))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rowmajor, src_rgba32f, need, hipMemcpyHostToDevice, ctx->stream));
     if (ctx->n_work) {
         hipLaunchKernelGGL(rv::tile_rgba32f, dim3((ctx->n_work + 255) / 256), dim3(256), 0, ctx->stream, static_cast<const float4 *>(ctx->d_rowmajor),

@@ -183,24 +183,36 @@ class DistributedRVPT:
             import torch.distributed as dist
             dist.barrier()
 
-    def gather_frame(self):
-        """Collective.  Rank 0 returns the full frame as a cuda tensor [H, W, 4] (float32); others None."""
+    def gather_frame(self, out=None):
+        """Collective.  Rank 0 returns the full frame as a cuda tensor [H, W, 4] (float32); others None.  out= (rank 0; ignored elsewhere): a contiguous
+        float32 tensor [H, W, 4] on this rank's device to gather into instead of a new one."""
         import torch
+        if out is not None and self.rank == 0:
+            if not getattr(out, "is_cuda", False):
+                raise native.NativeError(native.ERR_INVALID, "gather_frame: out= is a tensor on this rank's device")
+            self.local.context._frame_buffer(out, native.FORMAT_RGBA32F, "gather_frame")  # dtype, shape and device, before any rank is kept waiting
+        if self.library_comm and out is not None and self.rank == 0:  # the collective rvpt_hip_read into device memory: any 4-byte aligned view will do
+            return self.local.context.read_into(out)
         if self.library_comm:  # rvpt_hip_gather: waits for the frames in flight, gathers, un-tiles on rank 0
-            out = None
             if self.rank == 0:
                 out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=f"cuda:{self.device}")
-            self.local.context.gather(out.data_ptr() if out is not None else None)
-            return out
+            self.local.context.gather(out.data_ptr() if self.rank == 0 else None)
+            return out if self.rank == 0 else None
         self.local.wait()  # the library renders on its own stream
         slots = gather_slots(self._slot_tensor(), self.rank, self.world)
         if self.rank != 0:
             return None
         torch.cuda.synchronize(self.device)
-        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=f"cuda:{self.device}")
-        self.local.context.untile(slots.data_ptr(), slots.shape[1] * 4, self.world, out.data_ptr())
-        return out
+        dst = out if out is not None and out.data_ptr() % 16 == 0 else torch.empty((self.height, self.width, 4), dtype=torch.float32, device=f"cuda:{self.device}")
+        self.local.context.untile(slots.data_ptr(), slots.shape[1] * 4, self.world, dst.data_ptr())  # (stores a pixel as one float4)
+        if out is not None and dst is not out:
+            out.copy_(dst)
+            torch.cuda.current_stream(out.device).synchronize()
+        return dst if out is None else out
 
-    def read_frame(self):
+    def read_frame(self, out=None):
+        """Collective.  Rank 0: the frame as a numpy array, or — out= — left in that tensor on the device, which is returned; others None."""
+        if out is not None:
+            return self.gather_frame(out=out)
         out = self.gather_frame()
         return None if out is None else out.cpu().numpy()

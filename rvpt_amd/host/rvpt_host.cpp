@@ -295,6 +295,7 @@ std::vector<uint8_t> RVPT::read_frame_rgba8()
     if (!check(backend_.read(ctx_, RVPT_HIP_FORMAT_RGBA8_UNORM, out.data(), out.size()), "rvpt_hip_read")) out.clear();
     return out;
 }
+bool RVPT::read_frame_device(void *dst, size_t bytes, int format) { return check(backend_.read(ctx_, format, dst, bytes), "rvpt_hip_read"); }
 
 // ---- main.cpp:12-62 ---------------------------------------------------------------------------------------
 long load_model(RVPT &rvpt, const std::string &path, int material_id, std::string *error)

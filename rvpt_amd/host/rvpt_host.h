@@ -139,6 +139,10 @@ public:
     // RGBA32F (width*height*4 floats) or RGBA8 (width*height*4 bytes), row-major, top row first
     std::vector<float> read_frame();
     std::vector<uint8_t> read_frame_rgba8();
+    // the same frame left on the device: `dst` is device memory of the context's GPU (4-byte aligned, `bytes` >= the frame's), `format` is
+    // RVPT_HIP_FORMAT_RGBA32F or RVPT_HIP_FORMAT_RGBA8_UNORM; the bytes are those read_frame() / read_frame_rgba8() return, and `dst` may be read from any
+    // stream once the call has returned.  (A host pointer is read_frame() into the caller's own memory.)
+    bool read_frame_device(void *dst, size_t bytes, int format);
     const std::string &last_error() const { return error_; }
     // the backend context, e.g. to join several RVPT objects (one per GPU, tile_rank i of n) into one RCCL group with
     // rvpt_hip_comm_init_all; read_frame() on rank 0's object is then the gather of the whole image

@@ -445,7 +445,55 @@ class Context:
         _check(self._L.rvpt_hip_read(self._h, fmt, _ptr(out), out.nbytes), self._h, self._L)
         return out
 
-    def write_accum(self, img: np.ndarray) -> None:
+    def _frame_buffer(self, buf, fmt: int, what: str):
+        """(pointer, bytes, object to keep alive) of a whole frame in a numpy array or a torch tensor — contiguous float32[h, w, 4] (FORMAT_RGBA32F) or
+        uint8[h, w, 4] (FORMAT_RGBA8_UNORM); resolved the way _triangle_source resolves triangles: a tensor on this context's device is passed as device memory
+        once the stream that last touched it has finished, and torch is imported only when a tensor is given.  Checked here, before the call."""
+        if fmt not in (FORMAT_RGBA32F, FORMAT_RGBA8_UNORM):
+            raise NativeError(ERR_INVALID, f"{what}: unknown format {fmt}")
+        name, size = ("float32", 4) if fmt == FORMAT_RGBA32F else ("uint8", 1)
+        shape, need = (self.height, self.width, 4), self.height * self.width * 4 * size
+        is_tensor = not isinstance(buf, np.ndarray) and hasattr(buf, "data_ptr")
+        if not is_tensor and not isinstance(buf, np.ndarray):
+            raise NativeError(ERR_INVALID, f"{what}: a numpy array or a torch tensor is needed, got {type(buf).__name__}")
+        if is_tensor:
+            import torch
+            dtype_ok, nbytes, contiguous = buf.dtype == getattr(torch, name), buf.numel() * buf.element_size(), buf.is_contiguous()
+        else:
+            dtype_ok, nbytes, contiguous = buf.dtype == np.dtype(name), buf.nbytes, buf.flags.c_contiguous
+        if not dtype_ok:
+            raise NativeError(ERR_INVALID, f"{what}: {name}[{self.height}, {self.width}, 4] is needed for format {fmt}, got {buf.dtype}")
+        if nbytes < need:
+            raise NativeError(ERR_SIZE, f"{what}: holds {nbytes} bytes, frame needs {need}")
+        if tuple(buf.shape) != shape or not contiguous:
+            raise NativeError(ERR_INVALID, f"{what}: a contiguous {name}{list(shape)} is needed, got {tuple(buf.shape)}{'' if contiguous else ', not contiguous'}")
+        if is_tensor:
+            if buf.is_cuda:
+                if buf.device.index != self.device:
+                    raise NativeError(ERR_INVALID, f"{what}: the tensor lives on device {buf.device.index}, the context on {self.device}")
+                torch.cuda.current_stream(buf.device).synchronize()  # the library works on its own stream: what touched the tensor last must have finished
+                return C.c_void_p(buf.data_ptr()), need, buf
+            buf = buf.numpy()  # (shares the tensor's memory)
+        return _ptr(buf), need, buf
+
+    def read_into(self, dst, fmt: int = FORMAT_RGBA32F):
+        """rvpt_hip_read into the caller's memory: `dst` is a contiguous torch tensor on this context's device — the frame then never visits the host: the
+        un-tiling kernel writes it in place, a view that is only 4-byte aligned included — or a numpy array (the host read); float32[h, w, 4] for
+        FORMAT_RGBA32F, uint8[h, w, 4] for FORMAT_RGBA8_UNORM.  The bytes are those read() returns.  On return the library's stream has finished writing: the
+        tensor may be used on any stream.  Returns dst."""
+        ptr, nbytes, keep = self._frame_buffer(dst, fmt, "read_into")
+        _check(self._L.rvpt_hip_read(self._h, fmt, ptr, nbytes), self._h, self._L)
+        del keep
+        return dst
+
+    def write_accum(self, img) -> None:
+        """rvpt_hip_write_accum: restore the accumulator from a row-major RGBA32F frame — anything numpy makes float32[h, w, 4] of, or a contiguous float32
+        torch tensor [h, w, 4] on this context's device, which the tiling kernel reads in place."""
+        if not isinstance(img, np.ndarray) and hasattr(img, "data_ptr") and img.is_cuda:  # (a tensor in host memory goes the way it always went: through numpy)
+            ptr, nbytes, keep = self._frame_buffer(img, FORMAT_RGBA32F, "write_accum")
+            _check(self._L.rvpt_hip_write_accum(self._h, ptr, nbytes), self._h, self._L)
+            del keep
+            return
         img = np.ascontiguousarray(img, dtype=np.float32).reshape(self.height, self.width, 4)
         _check(self._L.rvpt_hip_write_accum(self._h, _ptr(img), img.nbytes), self._h, self._L)
 

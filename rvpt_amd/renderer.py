@@ -222,7 +222,11 @@ class RVPT:
     def wait(self) -> None:
         self._ctx.wait()
 
-    def read_frame(self, fmt: int = native.FORMAT_RGBA32F) -> np.ndarray:
+    def read_frame(self, fmt: int = native.FORMAT_RGBA32F, out=None):
+        """The frame as a numpy array; with out= (Context.read_into: a torch tensor on the context's device, where the frame then stays, or a numpy array) it is
+        filled and returned instead."""
+        if out is not None:
+            return self._ctx.read_into(out, fmt)
         return self._ctx.read(fmt)
 
     def shutdown(self) -> None:

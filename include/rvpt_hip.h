@@ -52,7 +52,9 @@ extern "C" {
                                      new symbol: the count RVPT_HIP_NODES_BUILD_SAH — until then the "needs nodes" error as well — is the build form with the
                                      binned-SAH tree of rvpt_bvh_build, made on the device.  Still 8, no new symbol: `dst` of rvpt_hip_read and
                                      `src_rgba32f` of rvpt_hip_write_accum may be DEVICE MEMORY of the context's GPU — until then undefined — and the frame
-                                     then never visits the host */
+                                     then never visits the host.  Still 8, no new symbol: no nodes and a count RVPT_HIP_NODES_UPDATE_GUARDED(permille) — until then the
+                                     "needs nodes" error — is the GUARDED UPDATE: the update form, the SAH cost of the refitted tree computed on the device and
+                                     reported, and past a limit a rebuild by the builder that made the tree */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -253,7 +255,40 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  *   form afterwards, brute-force contexts ignoring the count.  The three counts may alternate on one context.
  * - The height is at most 30 + ceil(log2 n) + 1 levels; there is no fallback.  rvpt_hip_last_error is empty after a
  *   SAH build.
- * DESIGN.md 5.8 has what was measured (profiles/device_build_sah.txt). */
+ * DESIGN.md 5.8 has what was measured (profiles/device_build_sah.txt).
+ *
+ * GUARDED UPDATE — refit, cost the tree, rebuild when it has gone stale:
+ *
+ *     rvpt_hip_upload_scene(ctx, NULL, RVPT_HIP_NODES_UPDATE_GUARDED(permille), tris, n_tris, NULL, 0);      n_tris > 0
+ *
+ * permille is 0 (report only) or 1000 .. 65535: the limit as a factor of the base cost, in thousandths (1250 = 1.25).  Any other value, or materials passed
+ * with this count, is RVPT_HIP_ERR_INVALID and leaves the stored scene untouched.
+ * - BVH contexts.  Everything the update form says holds: the same n_tris, the order rule (the leaf order after an ordinary upload, the caller's order after a
+ *   build form), host or device `tris`, frames in flight finishing on the old geometry, the stored scene untouched on a bad argument — with the update
+ *   form's own messages.  Then:
+ * - The TREE COST of the refitted tree is computed on the device and one double is read back.  Every binary node the root reaches is one term.  A node's
+ *   extents are hi - lo per axis, taken in double from the float32 bounds; its half-area is ex*ey + ey*ez + ez*ex in double, in that order, every operation
+ *   rounded on its own (no fused multiply-add).  An inner node contributes its half-area, a leaf its half-area times its primitive_count.  The sum
+ *   is in double — a fixed order of additions, no atomics: the same tree gives the same 64 bits on every run — and is divided by the root's half-area.  A root
+ *   of half-area 0 gives cost 0 and never triggers a rebuild.  rvpt_amd/scene.py: tree_cost is the same in numpy.
+ * - The BASE COST is the cost of the tree that the last ordinary full upload or build form on this context left (recorded by every one of them on a BVH
+ *   context: the same two kernels and one more 8-byte read).
+ * - With a limit, if cost > (permille / 1000) * base cost and the stored scene came from a build form, the library REBUILDS with that build form's method
+ *   (LBVH, PLOC with its fallback rule, SAH) from the moved vertices in the caller's order, the stored mat_id rows carried back through the stored
+ *   permutation, and the materials as the caller last passed them.  What the context then holds — tree, permutation, level table, wide form, launch choice —
+ *   is what rvpt_hip_upload_scene(ctx, NULL, <that build count>, moved_tris_with_their_mat_rows, n_tris, mats, n_mats) leaves, and the base cost becomes the
+ *   new tree's.  A rebuild that fails follows the build form's rule: a HIP error or a tree higher than the stack leaves the context WITHOUT a scene.
+ * - After an ordinary upload with the caller's own nodes the library has no builder to name: a limit there is RVPT_HIP_ERR_INVALID, says so, and leaves the
+ *   scene untouched.  Report only (0) is legal there.
+ * - On success rvpt_hip_last_error holds ONE SENTENCE (as after a PLOC build that fell back), one of
+ *       guarded update: cost <%.17g>, base cost <%.17g>, limit <permille> permille: refitted
+ *       guarded update: cost <%.17g>, base cost <%.17g>, limit <permille> permille: rebuilt (<lbvh|ploc|sah>), new base cost <%.17g>
+ *   where `cost` is that of the refitted tree, the one the decision was taken by.  The wrappers parse this wording.
+ * - Brute-force contexts hold no tree: there the guarded count is the plain update form (host arrays only), and rvpt_hip_last_error is empty afterwards.
+ * - The plain update form and the three build counts behave and report exactly as before.
+ * What the guard costs, and which limit separates a tree worth keeping from one worth rebuilding, is not yet measured on the device (DESIGN.md 5.10 says
+ * what is open; the cost ratios of the test scenes in numpy are there). */
+#define RVPT_HIP_NODES_UPDATE_GUARDED(permille) ((size_t)0 - (size_t)(0x10000u + (permille)))
 #define RVPT_HIP_NODES_BUILD ((size_t)-1)
 #define RVPT_HIP_NODES_BUILD_PLOC ((size_t)-2)
 #define RVPT_HIP_NODES_BUILD_SAH ((size_t)-3)

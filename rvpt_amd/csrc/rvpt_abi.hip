@@ -123,6 +123,19 @@ struct rvpt_hip_ctx {
     unsigned char *d_build = nullptr, *d_build_temp = nullptr;
     size_t cap_build = 0, cap_build_temp = 0;
     uint32_t *d_build_counters = nullptr, *h_build_words = nullptr;
+    // the GUARDED UPDATE of upload_scene (include/rvpt_hip.h): the tree cost's buffer (three result doubles, a gap, then one partial per work-group of
+    // rv::tree_cost_partials) and the pinned double it is read into; the cost of the tree the last full upload or build form left (have_cost: there is a level
+    // table to compute one by); which builder made the stored tree (0: the caller, an ordinary upload); the caller's materials as they were passed (the device
+    // copy's data.w is rewritten by prepare_materials); and the buffer a rebuild's triangles are carried back into, in the caller's order
+    double *d_cost = nullptr, *h_cost = nullptr;
+    size_t cap_cost = 0;
+    double base_cost = 0.0;
+    bool have_cost = false;
+    enum { kBuiltByCaller = 0, kBuiltLbvh, kBuiltPloc, kBuiltSah };
+    int built_by = kBuiltByCaller;
+    std::vector<rvpt_material> host_mats;
+    float4 *d_carry = nullptr;
+    size_t cap_carry = 0;
     bool have_scene = false;
 
     rvpt_render_settings settings{};
@@ -931,6 +944,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     }
     if (ctx->h_sky_count) (void)hipHostFree(ctx->h_sky_count);
     if (ctx->h_build_words) (void)hipHostFree(ctx->h_build_words);
+    if (ctx->h_cost) (void)hipHostFree(ctx->h_cost);
     if (ctx->d_timeline && !ctx->knobs.timeline_path.empty()) {  // debugging aid: dump the last frame's wave timeline
         std::vector<unsigned long long> h(ctx->timeline_words);
         if (hipMemcpy(h.data(), ctx->d_timeline, ctx->timeline_words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -959,7 +973,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
         if (ctx->trace_stream[i]) (void)hipStreamDestroy(ctx->trace_stream[i]);
     }
     void *bufs[] = {ctx->d_tris, ctx->d_prep, ctx->d_mats, ctx->d_nodes, ctx->d_wide, ctx->d_wide_map, ctx->d_mat_index, ctx->d_unit_n, ctx->d_accum,
-                    ctx->d_rowmajor, ctx->d_counter, ctx->d_stats, ctx->d_perm, ctx->d_build, ctx->d_build_temp, ctx->d_build_counters};
+                    ctx->d_rowmajor, ctx->d_counter, ctx->d_stats, ctx->d_perm, ctx->d_build, ctx->d_build_temp, ctx->d_build_counters, ctx->d_cost, ctx->d_carry};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1035,6 +1049,28 @@ static int classify_frame_pointer(rvpt_hip_ctx *ctx, const void *p, const char *
         return fail(ctx, RVPT_HIP_ERR_INVALID, "%s is device memory of GPU %d, the context lives on GPU %d: a frame stays on the context's own device", what, attr.device, ctx->device);
     if (reinterpret_cast<uintptr_t>(p) % 4u)
         return fail(ctx, RVPT_HIP_ERR_INVALID, "%s is device memory at %p: a frame on the device needs 4-byte alignment", what, p);
+    return RVPT_HIP_OK;
+}
+
+// The cost of the tree in d_nodes (rvpt_refit.hip: two kernels on ctx->stream, then one double read behind them).  Needs the level table: the end of its last
+// level is the end of the tree in the breadth-first device layout.  Without one (no tree, or the laboratory's caller-layout knob) the cost is 0 and
+// *have is false.
+static int device_tree_cost(rvpt_hip_ctx *ctx, double *cost, bool *have)
+{
+    *cost = 0.0, *have = false;
+    if (ctx->refit_levels.empty()) return RVPT_HIP_OK;
+    const uint32_t n_nodes = static_cast<uint32_t>(std::min<size_t>(ctx->n_nodes, ctx->refit_levels.back().second));
+    if (n_nodes == 0) return RVPT_HIP_OK;
+    const uint32_t n_partials = (n_nodes + rv::kTreeCostBlock - 1u) / rv::kTreeCostBlock;
+    if (int rc = grow(ctx, ctx->d_cost, ctx->cap_cost, static_cast<size_t>(n_partials) + 4u, sizeof(double))) return rc;
+    if (!ctx->h_cost) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_cost), sizeof(double)));
+    double *const partials = ctx->d_cost + 4;
+    hipLaunchKernelGGL(rv::tree_cost_partials, dim3(n_partials), dim3(rv::kTreeCostBlock), 0, ctx->stream, ctx->d_nodes, n_nodes, partials);
+    hipLaunchKernelGGL(rv::tree_cost_finish, dim3(1), dim3(rv::kTreeCostBlock), 0, ctx->stream, partials, n_partials, ctx->d_nodes, ctx->d_cost);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cost, ctx->d_cost, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *cost = ctx->h_cost[0], *have = true;
     return RVPT_HIP_OK;
 }
 
@@ -1338,6 +1374,9 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     ctx->wide_stack_levels = wide_need_kept;
     ctx->have_perm = true;
     if ((rc = derive_bounce_state(ctx, true, nullptr, n_tris))) return rc;
+    if ((rc = device_tree_cost(ctx, &ctx->base_cost, &ctx->have_cost))) return rc;  // the base cost of the guarded update
+    ctx->built_by = sah ? rvpt_hip_ctx::kBuiltSah : ploc ? rvpt_hip_ctx::kBuiltPloc : rvpt_hip_ctx::kBuiltLbvh;  // (a PLOC build that fell back is rebuilt as PLOC, by the same rule)
+    if (mats != ctx->host_mats.data() || n_mats != ctx->host_mats.size()) ctx->host_mats.assign(mats, mats + n_mats);  // (a guarded rebuild passes the stored array itself)
     ctx->scene_gen += 1;  // the slots' screen rectangles belong to the old scene
     ctx->have_scene = true;
     if (ploc) {  // which tree this was: the one fact a PLOC build reports beside its return code
@@ -1345,6 +1384,39 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
         else ctx->err.clear();
     }
     if (sah) ctx->err.clear();
+    return RVPT_HIP_OK;
+}
+
+// The GUARDED UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; BVH contexts): the update form, then the cost of the refitted tree, then — with a limit,
+// once the cost has grown past limit x base cost — a rebuild by the builder that made the stored tree, from the moved triangles carried back into the
+// caller's order.  permille: 0 (report only) or 1000 .. 65535, checked by the caller.
+static int update_geometry_guarded(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t n_tris, uint32_t permille)
+{
+    // the update form's own refusals come first and in its words; then the one refusal of this form, before anything of the stored scene is touched
+    if (ctx->have_scene && n_tris == ctx->n_tris && permille != 0 && ctx->built_by == rvpt_hip_ctx::kBuiltByCaller)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded update with a limit after an ordinary upload_scene: the tree is the caller's, the library has no builder to rebuild it by (report only, limit 0, is legal)");
+    if (int rc = update_geometry(ctx, tris, n_tris)) return rc;
+    double cost = 0.0;
+    bool have = false;
+    if (int rc = device_tree_cost(ctx, &cost, &have)) return rc;
+    const double base = ctx->base_cost;
+    static const char *const kNames[] = {"", "lbvh", "ploc", "sah"};
+    if (permille == 0 || !have || !ctx->have_cost || !(cost > static_cast<double>(permille) / 1000.0 * base)) {
+        fail(ctx, RVPT_HIP_OK, "guarded update: cost %.17g, base cost %.17g, limit %u permille: refitted", cost, base, permille);
+        return RVPT_HIP_OK;
+    }
+    // the rebuild: d_tris holds the moved vertices beside the stored mat_id rows, in leaf order; d_carry receives them in the caller's order.  A buffer of
+    // its own: the build reads its source until its last gather and writes d_tris, d_prep and its scratch meanwhile
+    const uint32_t n = static_cast<uint32_t>(n_tris);
+    const int built_by = ctx->built_by;
+    if (int rc = grow(ctx, ctx->d_carry, ctx->cap_carry, n_tris * 4u, sizeof(float4))) return rc;
+    hipLaunchKernelGGL(rv::carry_back_triangles, dim3(static_cast<uint32_t>((4ull * n + 255u) / 256u)), dim3(256), 0, ctx->stream, ctx->d_tris, ctx->d_perm, n, ctx->d_carry);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = build_scene_on_device(ctx, reinterpret_cast<const rvpt_triangle *>(ctx->d_carry), n_tris, ctx->host_mats.data(), ctx->host_mats.size(), built_by == rvpt_hip_ctx::kBuiltPloc,
+                                       built_by == rvpt_hip_ctx::kBuiltSah))
+        return rc;  // the build form's rule: its message, and no scene after anything but a bad material index (which stored rows cannot hold)
+    fail(ctx, RVPT_HIP_OK, "guarded update: cost %.17g, base cost %.17g, limit %u permille: rebuilt (%s), new base cost %.17g", cost, base, permille, kNames[built_by], ctx->base_cost);
     return RVPT_HIP_OK;
 }
 
@@ -1358,6 +1430,18 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     if (n_tris > 0x3FFFFFFFull) return fail(ctx, RVPT_HIP_ERR_INVALID, "too many triangles");
     // the UPDATE FORM: triangles without nodes and without materials (as a full upload it could never succeed: no material index fits n_mats == 0)
     if (n_tris > 0 && !nodes && n_nodes == 0 && !mats && n_mats == 0) return update_geometry(ctx, tris, n_tris);
+    // the GUARDED UPDATE: no nodes and a count of the band RVPT_HIP_NODES_UPDATE_GUARDED(permille) lies in.  Brute-force contexts hold no tree: the plain update form
+    if (!nodes && (size_t)0 - n_nodes >= 0x10000u && (size_t)0 - n_nodes < 0x110000u) {
+        const size_t permille = (size_t)0 - n_nodes - 0x10000u;
+        if (permille != 0 && (permille < 1000u || permille > 65535u))
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded update: the limit is 0 (report only) or 1000 .. 65535 permille, got %zu", permille);
+        if (mats || n_mats) return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded update takes no materials: it keeps the stored ones");
+        if (n_tris == 0) return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded update without triangles");
+        if (is_bvh(ctx, n_tris)) return update_geometry_guarded(ctx, tris, n_tris, static_cast<uint32_t>(permille));
+        const int rc = update_geometry(ctx, tris, n_tris);
+        if (rc == RVPT_HIP_OK) ctx->err.clear();
+        return rc;
+    }
     // the BUILD FORM: no nodes and the sentinel count.  BVH contexts build the tree on the device; brute-force contexts ignore nodes and n_nodes as ever
     if (!nodes && (n_nodes == RVPT_HIP_NODES_BUILD || n_nodes == RVPT_HIP_NODES_BUILD_PLOC || n_nodes == RVPT_HIP_NODES_BUILD_SAH)) {
         if (is_bvh(ctx, n_tris)) return build_scene_on_device(ctx, tris, n_tris, mats, n_mats, n_nodes == RVPT_HIP_NODES_BUILD_PLOC, n_nodes == RVPT_HIP_NODES_BUILD_SAH);
@@ -1488,6 +1572,10 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
         }
     }
     if ((rc = derive_bounce_state(ctx, bvh, tris, n_tris))) return rc;
+    ctx->base_cost = 0.0, ctx->have_cost = false;
+    if (bvh && (rc = device_tree_cost(ctx, &ctx->base_cost, &ctx->have_cost))) return rc;  // the base cost of the guarded update
+    ctx->built_by = rvpt_hip_ctx::kBuiltByCaller;
+    if (bvh) ctx->host_mats.assign(mats, mats + n_mats);
     ctx->scene_gen += 1;  // the slots' screen rectangles belong to the old scene
     ctx->have_scene = true;
     return RVPT_HIP_OK;

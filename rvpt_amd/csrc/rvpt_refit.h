@@ -12,4 +12,13 @@ __global__ void refit_level(float4 *__restrict__ nodes, uint32_t begin, uint32_t
 // ... then the wide nodes' copies of those boxes: map = 4 words per wide node (bvh_wide.h: build_wide_nodes' kid_map), n_slots = 4 x wide nodes
 __global__ void refit_wide_gather(float *__restrict__ wide, const uint32_t *__restrict__ map, uint32_t n_slots, const float4 *__restrict__ nodes, uint32_t n_nodes);
 
+// the tree cost of the guarded update (rvpt_refit.hip has the definition and what it relies on): stage one, one node per lane and one partial per work-group of
+// kTreeCostBlock lanes (grid = ceil(n_nodes / kTreeCostBlock), partials holds that many doubles) ...
+constexpr uint32_t kTreeCostBlock = 256;
+__global__ void tree_cost_partials(const float4 *__restrict__ nodes, uint32_t n_nodes, double *__restrict__ partials);
+// ... stage two, ONE work-group of kTreeCostBlock lanes: out[0] = cost, out[1] = the sum, out[2] = the root's half-area
+__global__ void tree_cost_finish(const double *__restrict__ partials, uint32_t n_partials, const float4 *__restrict__ nodes, double *__restrict__ out);
+// the triangles of d_tris carried back into the caller's order for a guarded rebuild: out[perm[pos]] = tris[pos], grid = ceil(4 n / block) (one thread per quad)
+__global__ void carry_back_triangles(const float4 *__restrict__ tris, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ out);
+
 }  // namespace rv

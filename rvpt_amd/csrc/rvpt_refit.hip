@@ -55,4 +55,81 @@ __global__ void refit_wide_gather(float *__restrict__ wide, const uint32_t *__re
     q[0] = q0.z, q[4] = q0.w, q[8] = q1.x, q[12] = q1.y, q[16] = q1.z, q[20] = q1.w;
 }
 
+// ---- the tree cost (include/rvpt_hip.h: the guarded update) ------------------------------------------------------------------------------------------------------
+// cost = (sum over the inner nodes of their half-area + sum over the leaves of half-area x triangle count) / the root's half-area: rvpt_amd/scene.py: tree_cost.
+//
+// RELIES ON the breadth-first device layout: the node array [0, n_nodes) holds the root at 0, the unused slot 1, and from 2 on the levels of the tree back to
+// back, so EVERY slot but 1 is a node the root reaches and a flat pass over the array is a pass over the tree.  Established by rvpt_hip_upload_scene
+// (rvpt_abi.hip), which copies a caller's tree into that layout node by reachable node — strays never arrive — and by build_scene_on_device, whose level
+// loops hand out the slots pair by pair; both pass n_nodes = the end of the last level.  Slot 1 is skipped here by its index, whatever it holds.
+//
+// No atomics, and a fixed shape of additions: lane i of a wave holds node base + i, the wave folds its 64 terms with __shfl_down (32, 16, .. 1), lane 0 of
+// wave 0 adds the work-group's four wave sums in wave order and writes ONE partial per work-group with a plain vector store; tree_cost_finish then adds the
+// partials in index order.  The same tree gives the same 64 bits on every run.  Double precision: a node costs nine FP64 operations and
+// the fold six more against 32 bytes read, so the pass is bound by reading the nodes once, not by the FP64 rate.
+
+// the half-area of a box: its float32 bounds widened to double, the extents and everything after them in double, every operation rounded on its own (no
+// contraction: the host statement has none)
+__device__ inline double tree_cost_half_area(float4 q0, float4 q1)
+{
+    const double ex = __dsub_rn(static_cast<double>(q0.w), static_cast<double>(q0.z)), ey = __dsub_rn(static_cast<double>(q1.y), static_cast<double>(q1.x)),
+                 ez = __dsub_rn(static_cast<double>(q1.w), static_cast<double>(q1.z));
+    return __dadd_rn(__dadd_rn(__dmul_rn(ex, ey), __dmul_rn(ey, ez)), __dmul_rn(ez, ex));
+}
+
+__global__ __launch_bounds__(kTreeCostBlock) void tree_cost_partials(const float4 *__restrict__ nodes, uint32_t n_nodes, double *__restrict__ partials)
+{
+    __shared__ double wave_sum[kTreeCostBlock / 64];
+    const uint32_t i = blockIdx.x * kTreeCostBlock + threadIdx.x;
+    double term = 0.0;
+    if (i < n_nodes && i != 1u) {
+        const float4 q0 = nodes[2 * i], q1 = nodes[2 * i + 1];
+        const uint32_t count = __float_as_uint(q0.y);
+        term = tree_cost_half_area(q0, q1);
+        if (count > 0) term = __dmul_rn(term, static_cast<double>(count));
+    }
+    for (int off = 32; off > 0; off >>= 1) term = __dadd_rn(term, __shfl_down(term, off, 64));
+    if ((threadIdx.x & 63u) == 0) wave_sum[threadIdx.x >> 6] = term;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = wave_sum[0];
+        for (uint32_t w = 1; w < kTreeCostBlock / 64; ++w) s = __dadd_rn(s, wave_sum[w]);
+        partials[blockIdx.x] = s;
+    }
+}
+
+// ONE work-group: thread t adds the partials [t * chunk, (t + 1) * chunk) in index order, thread 0 then adds the kTreeCostBlock chunk sums in index order: index
+// order throughout, with the one grouping fixed by n_partials.  out[0] = the cost (0 where the root's half-area is 0), out[1] = the sum, out[2] = the root's half-area.
+__global__ __launch_bounds__(kTreeCostBlock) void tree_cost_finish(const double *__restrict__ partials, uint32_t n_partials, const float4 *__restrict__ nodes, double *__restrict__ out)
+{
+    __shared__ double chunk_sum[kTreeCostBlock];
+    const uint32_t chunk = (n_partials + kTreeCostBlock - 1u) / kTreeCostBlock;
+    const uint32_t begin = min(threadIdx.x * chunk, n_partials), end = min(begin + chunk, n_partials);
+    double s = 0.0;
+    for (uint32_t k = begin; k < end; ++k) s = __dadd_rn(s, partials[k]);
+    chunk_sum[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = chunk_sum[0];
+        for (uint32_t t = 1; t < kTreeCostBlock; ++t) total = __dadd_rn(total, chunk_sum[t]);
+        const double root = tree_cost_half_area(nodes[0], nodes[1]);
+        out[0] = root > 0.0 ? total / root : 0.0;
+        out[1] = total;
+        out[2] = root;
+    }
+}
+
+// The carry-back for a guarded rebuild: the 64-byte records of d_tris (leaf order: moved vertices, stored mat_id rows) into the caller's order,
+// out[perm[pos]] = tris[pos].  perm is a bijection of [0, n) (the build's gather wrote it), so every row of `out` is written exactly once; a word that is
+// not an index is dropped, never an address.  One thread per quad.
+__global__ void carry_back_triangles(const float4 *__restrict__ tris, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ out)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t pos = t >> 2, q = t & 3u;
+    if (pos >= n) return;
+    const uint32_t dst = perm[pos];
+    if (dst >= n) return;
+    out[4 * static_cast<size_t>(dst) + q] = tris[4 * static_cast<size_t>(pos) + q];
+}
+
 }  // namespace rv

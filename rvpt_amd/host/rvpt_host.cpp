@@ -191,7 +191,10 @@ bool RVPT::initialize()
                  "rvpt_hip_upload_scene");
 }
 
-bool RVPT::update_triangles(const std::vector<Triangle> &triangles)
+bool RVPT::update_triangles(const std::vector<Triangle> &triangles) { return update_triangles_with(triangles, 0, "rvpt_hip_upload_scene (geometry update)"); }
+
+// `count`: 0, the plain update form, or RVPT_HIP_NODES_UPDATE_GUARDED(permille)
+bool RVPT::update_triangles_with(const std::vector<Triangle> &triangles, size_t count, const char *what)
 {
     if (!ctx_) {
         error_ = "update_triangles before initialize()";
@@ -203,7 +206,7 @@ bool RVPT::update_triangles(const std::vector<Triangle> &triangles)
     }
     if (triangles.empty()) return true;
     if (device_built_) {  // the device gathers through the permutation it kept
-        if (!check(backend_.upload_scene(ctx_, nullptr, 0, reinterpret_cast<const rvpt_triangle *>(triangles.data()), triangles.size(), nullptr, 0), "rvpt_hip_upload_scene (geometry update)"))
+        if (!check(backend_.upload_scene(ctx_, nullptr, count, reinterpret_cast<const rvpt_triangle *>(triangles.data()), triangles.size(), nullptr, 0), what))
             return false;
         triangles_ = triangles;
         previous_.valid = false;
@@ -212,12 +215,55 @@ bool RVPT::update_triangles(const std::vector<Triangle> &triangles)
     std::vector<Triangle> moved;
     moved.reserve(triangles.size());
     for (uint32_t i : order_) moved.push_back(triangles[i]);  // leaf order (Bvh::permute_primitives)
-    if (!check(backend_.upload_scene(ctx_, nullptr, 0, reinterpret_cast<const rvpt_triangle *>(moved.data()), moved.size(), nullptr, 0), "rvpt_hip_upload_scene (geometry update)"))
+    if (!check(backend_.upload_scene(ctx_, nullptr, count, reinterpret_cast<const rvpt_triangle *>(moved.data()), moved.size(), nullptr, 0), what))
         return false;
     triangles_ = triangles;
     sorted_.swap(moved);
     nodes_stale_ = true;
     previous_.valid = false;  // a new scene: nothing accumulated so far belongs to it
+    return true;
+}
+
+// The sentence rvpt_hip_last_error holds after a guarded update (include/rvpt_hip.h fixes the wording).
+bool parse_update_report(const char *sentence, UpdateReport *report)
+{
+    UpdateReport r;
+    unsigned permille = 0;
+    int used = 0;
+    char tree[8] = {};
+    if (!sentence || std::sscanf(sentence, "guarded update: cost %lg, base cost %lg, limit %u permille: %n", &r.cost, &r.base_cost, &permille, &used) < 3 || used == 0) return false;
+    const char *rest = sentence + used;
+    if (std::strcmp(rest, "refitted") == 0) {
+        r.rebuilt = false;
+    } else if (std::sscanf(rest, "rebuilt (%7[a-z]), new base cost %lg", tree, &r.new_base_cost) == 2) {
+        r.rebuilt = true, r.tree = tree;
+    } else {
+        return false;
+    }
+    r.ratio = r.base_cost > 0.0 ? r.cost / r.base_cost : 0.0;
+    if (report) *report = r;
+    return true;
+}
+
+bool RVPT::update_triangles(const std::vector<Triangle> &triangles, double rebuild_above, UpdateReport *report)
+{
+    long permille = 0;  // infinity: report only
+    if (!std::isinf(rebuild_above) || rebuild_above < 0) {
+        permille = std::isnan(rebuild_above) ? -1 : std::lround(std::fmin(rebuild_above, 1e6) * 1000.0);
+        if (permille < 1000 || permille > 65535) {
+            error_ = "update_triangles: rebuild_above is a factor in [1, 65.535] or infinity (report only)";
+            return false;
+        }
+    }
+    if (!update_triangles_with(triangles, RVPT_HIP_NODES_UPDATE_GUARDED(static_cast<size_t>(permille)), "rvpt_hip_upload_scene (guarded update)")) return false;
+    UpdateReport r;  // (a brute-force context refits nothing and reports nothing: the empty record)
+    if (options_.bvh_traversal && !triangles.empty() && !parse_update_report(backend_.last_error(ctx_), &r)) {
+        error_ = "update_triangles: the guarded update's report could not be read";
+        return false;
+    }
+    // a rebuild happens only after a device build, where the tree lives on the device alone and bvh_nodes() is empty: there is no host copy to go wrong.  After a
+    // host build the library refuses a limit (the tree is the caller's), and a report-only update is a refit, which update_triangles_with has marked
+    if (report) *report = r;
     return true;
 }
 

@@ -97,6 +97,15 @@ struct Backend {
     static const Backend &native();
 };
 
+// What a guarded geometry update reports (RVPT::update_triangles with a limit), parsed from the one sentence rvpt_hip_last_error then holds
+struct UpdateReport {
+    double cost = 0, base_cost = 0, ratio = 0;  // the refitted tree's cost, the cost of the tree as it was built, cost / base_cost (0 when the base is 0)
+    bool rebuilt = false;
+    std::string tree;          // rebuilt: "lbvh", "ploc" or "sah"
+    double new_base_cost = 0;  // rebuilt: the new tree's cost, the base from here on
+};
+bool parse_update_report(const char *sentence, UpdateReport *report);
+
 class RVPT {
 public:
     struct Options {
@@ -135,6 +144,12 @@ public:
     // tree keeps its topology and is refitted on the device (the update form of rvpt_hip_upload_scene: no nodes, no materials), no rebuild; the next update()
     // restarts the accumulation.  After initialize() only.  (After a device build the device keeps the permutation: the triangles go down as they are.)
     bool update_triangles(const std::vector<Triangle> &triangles);
+    // The guarded form (RVPT_HIP_NODES_UPDATE_GUARDED): the same, then the SAH cost of the refitted tree from the device, and — `rebuild_above` a factor in
+    // [1, 65.535], rounded to thousandths — a rebuild by the device builder of initialize() once cost > rebuild_above x the base cost; infinity: report only.
+    // A limit needs Options::device_build (after a host build the tree is the caller's: the library refuses).  bvh_nodes() stays right: after a device build
+    // — the only case with a rebuild — the tree lives on the device alone and bvh_nodes() is EMPTY, as it always was there, rather than a tree the device no
+    // longer holds; after a host build only a refit can have happened.  Brute-force traversal: the plain update, `report` comes back empty.
+    bool update_triangles(const std::vector<Triangle> &triangles, double rebuild_above, UpdateReport *report = nullptr);
 
     // RGBA32F (width*height*4 floats) or RGBA8 (width*height*4 bytes), row-major, top row first
     std::vector<float> read_frame();
@@ -158,6 +173,7 @@ public:
 
 private:
     bool check(int rc, const char *what);
+    bool update_triangles_with(const std::vector<Triangle> &triangles, size_t count, const char *what);
     uint32_t width_, height_;
     Options options_;
     const Backend &backend_;

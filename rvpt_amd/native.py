@@ -5,7 +5,10 @@ There is no fallback: if librvpt_hip.so is missing or a call fails, NativeError 
 from __future__ import annotations
 
 import ctypes as C
+import math
+import re
 from pathlib import Path
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -27,6 +30,7 @@ TILE = 16
 TILE_SHIFT = 3  # RVPT_HIP_TILE_SHIFT: every row of the tile grid is rotated by this many more tiles than the one above (tile ownership)
 NODES_BUILD = C.c_size_t(-1).value  # RVPT_HIP_NODES_BUILD: upload_scene's node count for the build form (Context.build_scene)
 NODES_BUILD_SAH = C.c_size_t(-3).value  # RVPT_HIP_NODES_BUILD_SAH: the build form with rvpt_bvh_build's binned-SAH tree (Context.build_scene(method="sah"))
+NODES_UPDATE_GUARDED_BASE = 0x10000  # RVPT_HIP_NODES_UPDATE_GUARDED(permille) = (size_t)0 - (0x10000 + permille): the guarded update (Context.update_triangles(rebuild_above=))
 NODES_BUILD_PLOC = C.c_size_t(-2).value  # RVPT_HIP_NODES_BUILD_PLOC: the build form with a PLOC tree (Context.build_scene(method="ploc"))
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_SIZE, ERR_COMM = -1, -2, -3, -4, -5, -6
 
@@ -43,6 +47,33 @@ LAB_EXPORTS = [
     "rvpt_hip_selftest_div", "rvpt_hip_selftest_rcp", "rvpt_hip_selftest_pretest", "rvpt_hip_selftest_camera_rects", "rvpt_hip_selftest_bounce_cull",
     "rvpt_hip_selftest_fast_div", "rvpt_camera_rects", "rvpt_bounce_rows", "rvpt_bounce_leaf_boxes", "rvpt_bvh_wide_form", "rvpt_claim_order",
 ]
+
+
+def nodes_update_guarded(permille: int) -> int:
+    """RVPT_HIP_NODES_UPDATE_GUARDED(permille) of include/rvpt_hip.h as the size_t the call takes"""
+    return C.c_size_t(-(NODES_UPDATE_GUARDED_BASE + int(permille))).value
+
+
+class UpdateReport(NamedTuple):
+    """What a guarded update reports: the refitted tree's SAH cost, the cost of the tree as it was last built or uploaded, cost / base_cost (0.0 when the base is
+    0), whether the library rebuilt, and then the builder's name ("lbvh", "ploc", "sah"; None after a refit)."""
+    cost: float
+    base_cost: float
+    ratio: float
+    rebuilt: bool
+    tree: Optional[str]
+
+
+_GUARD_SENTENCE = re.compile(r"guarded update: cost (\S+), base cost (\S+), limit (\d+) permille: (?:refitted|rebuilt \((lbvh|ploc|sah)\), new base cost (\S+))\Z")
+
+
+def parse_update_report(sentence: str) -> UpdateReport:
+    """The one sentence rvpt_hip_last_error holds after a guarded update (include/rvpt_hip.h fixes its wording)"""
+    m = _GUARD_SENTENCE.match(sentence)
+    if m is None:
+        raise NativeError(ERR_INVALID, f"update_triangles: not a guarded update's report: {sentence!r}")
+    cost, base = float(m.group(1)), float(m.group(2))
+    return UpdateReport(cost, base, cost / base if base > 0.0 else 0.0, m.group(4) is not None, m.group(4))
 
 
 class NativeError(RuntimeError):
@@ -370,19 +401,34 @@ class Context:
             return "lbvh" if b"LBVH tree" in (self._L.rvpt_hip_last_error(self._h) or b"") else "ploc"
         return "sah" if method == "sah" else "lbvh"
 
-    def update_triangles(self, tris) -> None:
+    def update_triangles(self, tris, rebuild_above=None):
         """The update form of rvpt_hip_upload_scene (include/rvpt_hip.h): the scene's triangles have moved — same count, same tree topology as the last full
         upload, in the order that upload took them: the leaf order after upload_scene, the caller's own order after build_scene.
         Only vert0..vert2 are taken; material rows, materials and the tree's structure stay, every box of the tree is refitted on the
         device (scene.refit_bvh is the same on the host).  Frames in flight finish on the old geometry; restarting the accumulation is the caller's business.
-        tris: float32[n, 16], a numpy array or — BVH contexts — a contiguous torch tensor on this context's device, which never visits the host."""
+        tris: float32[n, 16], a numpy array or — BVH contexts — a contiguous torch tensor on this context's device, which never visits the host.
+
+        rebuild_above: None is the plain form and returns None.  A number is the GUARDED form (RVPT_HIP_NODES_UPDATE_GUARDED): after the refit the library
+        computes the tree's SAH cost on the device (scene.tree_cost is the same in numpy) and, when it exceeds rebuild_above x the cost of the tree as it was built,
+        rebuilds with the method of the build_scene that made it.  A float >= 1 is rounded to thousandths (at most 65.535); math.inf only reports.  Returns an
+        UpdateReport (cost, base_cost, ratio, rebuilt, tree); on a brute-force context, which holds no tree, the plain update happens and None is returned."""
         ptr, n, keep = self._triangle_source(tris, "update_triangles")
+        count = 0
+        if rebuild_above is not None:
+            limit = float(rebuild_above)
+            permille = 0 if limit == math.inf else int(round(min(limit, 1e6) * 1000.0)) if limit == limit and limit > 0 else -1
+            if permille != 0 and not 1000 <= permille <= 65535:
+                raise NativeError(ERR_INVALID, f"update_triangles: rebuild_above is a factor in [1, 65.535] or math.inf (report only), got {rebuild_above!r}")
+            count = nodes_update_guarded(permille)
         if n == 0:  # (in the C form a call without triangles is a full upload of the empty scene)
             if self._scene_tris != 0:
                 raise NativeError(ERR_INVALID, "update_triangles: no triangles given" + (" before any upload_scene" if self._scene_tris is None else f", the uploaded scene has {self._scene_tris}"))
-            return
-        _check(self._L.rvpt_hip_upload_scene(self._h, None, 0, ptr, n, None, 0), self._h, self._L)
+            return None
+        _check(self._L.rvpt_hip_upload_scene(self._h, None, count, ptr, n, None, 0), self._h, self._L)
         del keep
+        if count == 0 or (self.flags & (TRAVERSAL_BVH | TRAVERSAL_BVH_ORDERED)) == 0:
+            return None
+        return parse_update_report((self._L.rvpt_hip_last_error(self._h) or b"").decode())
 
     def set_frame(self, settings: np.ndarray, camera: np.ndarray) -> None:
         settings = np.ascontiguousarray(settings)

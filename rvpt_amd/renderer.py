@@ -148,28 +148,36 @@ class RVPT:
     def sorted_triangles(self, tris) -> None:
         self._sorted_triangles = tris
 
-    def update_triangles(self, triangles) -> None:
+    def update_triangles(self, triangles, rebuild_above=None):
         """Moving geometry — what the per-frame triangle copy of rvpt.cpp:124 is for: `triangles` (float32[n, 16], in the order they were ADDED, same count) replace
-        the scene's; the tree keeps its topology and is refitted on the device (Context.update_triangles), no rebuild.  The next update() restarts the accumulation."""
+        the scene's; the tree keeps its topology and is refitted on the device (Context.update_triangles), no rebuild.  The next update() restarts the accumulation.
+        rebuild_above: Context.update_triangles' keyword — the guarded form: the refitted tree's SAH cost is reported (native.UpdateReport) and, past that factor of
+        the cost of the tree as built, the device rebuilds by the builder of initialize().  A limit needs build="device*"; math.inf only reports."""
         tris = np.asarray(triangles, dtype=np.float32).reshape(-1, 16)
         if self._ctx is None or self._n_triangles is None:
             raise RuntimeError("update_triangles before initialize()")
         if tris.shape[0] != self._n_triangles:
             raise native.NativeError(native.ERR_INVALID, f"update_triangles: {tris.shape[0]} triangles given, the scene has {self._n_triangles}")
         if self._device_built:  # the device keeps the permutation: the caller's order goes down as it is
-            self._ctx.update_triangles(tris)
+            report = self._ctx.update_triangles(tris, rebuild_above)
             self._current_triangles = tris.copy()
             self.triangles = [self._current_triangles]
-            if self._built_from is None:
+            if report is not None and report.rebuilt:
+                # the device holds a new tree and a new permutation: the host statement is that of a fresh build from these triangles, made when asked for
+                self._built_from = self._current_triangles
+                self._bvh_nodes = self._primitive_indices = self._sorted_triangles = None
+                self._nodes_stale = False
+            elif self._built_from is None:
                 self._sorted_triangles = tris[self._primitive_indices]
                 self._nodes_stale = True
         else:
             sorted_tris = tris[self.primitive_indices]  # leaf order (Bvh::permute_primitives)
-            self._ctx.update_triangles(sorted_tris)
+            report = self._ctx.update_triangles(sorted_tris, rebuild_above)
             self.triangles = [tris.copy()]
             self.sorted_triangles = sorted_tris
             self._nodes_stale = self._bvh_nodes is not None
         self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
+        return report
 
     # -- lifecycle -----------------------------------------------------------------------------------------
     def initialize(self) -> bool:

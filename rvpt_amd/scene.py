@@ -96,6 +96,40 @@ def refit_bvh(nodes, tris) -> np.ndarray:
     return out
 
 
+def tree_cost(nodes) -> float:
+    """The SAH cost of a tree, the number the guarded update of rvpt_hip_upload_scene reports (include/rvpt_hip.h has the definition): every node the root reaches
+    is one term; a node's extents are hi - lo per axis, taken in double from the float32 bounds, its half-area ex*ey + ey*ez + ez*ex in double; an inner node
+    contributes its half-area, a leaf its half-area times its triangle count; the sum, in double, is divided by the root's half-area.  A root of half-area 0
+    costs 0.  The device adds in another order: the two agree to n * 2^-53 relative, not to the bit.
+
+    nodes: uint32[n, 8] (native.build_bvh) or NODE_DTYPE records, root at 0.  The levels are walked as refit_bvh walks them, so nodes the root does not reach
+    are left out."""
+    rec = np.ascontiguousarray(nodes).view(NODE_DTYPE).reshape(-1)
+    n = rec.shape[0]
+    if n == 0:
+        return 0.0
+    first, count = rec["first"].astype(np.int64), rec["count"].astype(np.int64)
+    levels, frontier, seen = [], np.zeros(1, dtype=np.int64), 1
+    while frontier.size:
+        levels.append(frontier)
+        inner = frontier[count[frontier] == 0]
+        if inner.size and int(first[inner].max()) + 1 >= n:
+            raise ValueError("tree_cost: child index outside the node array")
+        frontier = np.stack([first[inner], first[inner] + 1], axis=1).reshape(-1)
+        seen += frontier.size
+        if seen > n:
+            raise ValueError("tree_cost: not a tree (a node is reachable twice)")
+    reached = np.concatenate(levels)
+    b = rec["bounds"][reached].astype(np.float64)
+    e = b[:, 1::2] - b[:, 0::2]
+    area = e[:, 0] * e[:, 1] + e[:, 1] * e[:, 2] + e[:, 2] * e[:, 0]
+    root = float(area[0])
+    if not root > 0.0:
+        return 0.0
+    c = count[reached]
+    return float(np.sum(area * np.where(c > 0, c, 1).astype(np.float64)) / root)
+
+
 LBVH_LEAF_TRIS = 2  # == rv::kLbvhLeafTris (rvpt_amd/csrc/rvpt_build.h)
 
 

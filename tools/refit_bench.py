@@ -2,7 +2,9 @@
 """Run on the GPU box: what a pose change of the 1 M-triangle terrain costs (BVH context, 1920x1080) by the update form of rvpt_hip_upload_scene against the
 only route there was before it — rvpt_bvh_build + a full upload_scene — and against the floor, a bare host-to-device copy of the same 48 MB; then what
 traversal pays on a refitted tree against a freshly built one.  -> stdout (profiles/refit_update.txt)
-usage: tools/refit_bench.py [all|updates]     (updates: one upload and a few updates, nothing else — the run to put under rocprofv3 --kernel-trace --stats)"""
+usage: tools/refit_bench.py [all|updates|guard|guard-updates]     (updates: one upload and a few updates, nothing else — the run to put under rocprofv3
+--kernel-trace --stats; guard: only the guarded update's section, -> profiles/guarded_update.txt; guard-updates: a device build and a few guarded updates, for the
+same profiler run)"""
 import statistics, sys, time
 from pathlib import Path
 
@@ -42,8 +44,73 @@ def frame_rate(ctx, cam, frames=24, reps=5):
     return [W * H * frames / t / 1e6 for t in ts]
 
 
+def guard_section(tris0, mats, ext, cam):
+    """The guarded update (Context.update_triangles(rebuild_above=)) on the 1 M-triangle terrain, built on the device, poses in a device tensor: what the guard adds
+    to the plain update (same run, same context, interleaved), what a rebuild under it takes, and what the cost ratio says beside the traversal-rate ratio."""
+    import math
+    import torch
+    print("\n== guarded update: plain | guarded, report only | guarded, rebuilding (wall clock of the call, device tensor, SAH device build; interleaved) ==")
+    ctx = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BVH)
+    ctx.build_scene(tris0, mats, method="sah")
+    poses = [torch.from_numpy(scene.wobble(tris0, 0.5 + 0.9 * k, 0.02 * ext)).to("cuda:0") for k in range(2)]
+    plain, guarded = [], []
+    for it in range(23):
+        for which, out in (("plain", plain), ("guarded", guarded)):
+            t0 = time.perf_counter()
+            ctx.update_triangles(poses[it % 2], rebuild_above=None if which == "plain" else math.inf)
+            if it >= 3:
+                out.append(time.perf_counter() - t0)
+    print(f"plain update form                     {spread(plain)}")
+    print(f"guarded, report only                  {spread(guarded)}")
+    print(f"the guard adds (difference of medians) {(statistics.median(guarded) - statistics.median(plain)) * 1e6:8.1f} us")
+    for method in ("lbvh", "ploc", "sah"):
+        ctx.build_scene(tris0, mats, method=method)
+        far = [torch.from_numpy(scene.wobble(tris0, 1.4 + 1.7 * k, 0.10 * ext)).to("cuda:0") for k in range(2)]
+        rebuilds, n_rebuilt = [], 0
+        for it in range(7):
+            t0 = time.perf_counter()
+            rep = ctx.update_triangles(far[it % 2], rebuild_above=1.0)  # every pose change of this size costs more than the tree built for the pose before it
+            if it >= 1:
+                rebuilds.append(time.perf_counter() - t0)
+                n_rebuilt += int(rep.rebuilt)
+        print(f"guarded, limit 1.0, {method:4s} ({n_rebuilt} of {len(rebuilds)} rebuilt)  {spread(rebuilds)}")
+    print("\n== what the cost predicts: cost ratios beside the traversal-rate ratio (one-frame launches at 1080p, Msamples/s, median of 5 x 24 frames) ==")
+    print("builder  amplitude   cost refit/base   cost fresh/base   cost refit/fresh   rate refit   rate fresh   rate refit/fresh")
+    for method in ("lbvh", "ploc", "sah"):
+        for amp in (0.02, 0.10):
+            pose = scene.wobble(tris0, 1.4, amp * ext)
+            dev = torch.from_numpy(pose).to("cuda:0")
+            ctx.build_scene(tris0, mats, method=method)
+            rep = ctx.update_triangles(dev, rebuild_above=math.inf)
+            a = statistics.median(frame_rate(ctx, cam))
+            ctx.build_scene(dev, mats, method=method)
+            fresh = ctx.update_triangles(dev, rebuild_above=math.inf).base_cost
+            b = statistics.median(frame_rate(ctx, cam))
+            print(f"{method:7s}  {amp:9.2f}   {rep.ratio:15.4f}   {fresh / rep.base_cost:15.4f}   {rep.cost / fresh:16.4f}   {a:10.0f}   {b:10.0f}   {a / b:16.3f}")
+    ctx.close()
+
+
+def guard_updates(tris0, mats, ext):
+    import math
+    import torch
+    ctx = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BVH)
+    ctx.build_scene(tris0, mats, method="sah")
+    poses = [torch.from_numpy(scene.wobble(tris0, 0.5 + 0.9 * k, 0.02 * ext)).to("cuda:0") for k in range(2)]
+    for k in range(8):
+        ctx.update_triangles(poses[k % 2], rebuild_above=math.inf)
+    ctx.close()
+    print("8 guarded updates done")
+
+
 tris0, mats = scene.heightfield_scene()
 ext = float(np.ptp(tris0.reshape(-1, 4, 4)[:, :3, :3].reshape(-1, 3), axis=0).max())
+if what in ("guard", "guard-updates"):
+    c = Camera(W / H)
+    c.translation = np.array([0.0, 2.5, -5.0])
+    c.rotation = np.array([0.0, 25.0, 0.0])
+    print(f"scene: {tris0.shape[0]} triangles, extent {ext:.2f}")
+    guard_section(tris0, mats, ext, c.get_data()) if what == "guard" else guard_updates(tris0, mats, ext)
+    sys.exit(0)
 t0 = time.perf_counter()
 nodes, idx = native.build_bvh(tris0)
 print(f"scene: {tris0.shape[0]} triangles, {nodes.shape[0]} nodes, extent {ext:.2f}; first rvpt_bvh_build {(time.perf_counter() - t0) * 1e3:.0f} ms (cold)")
@@ -130,3 +197,4 @@ for amp in (0.02, 0.1):
     print(f"amplitude {amp:4.2f} x extent: refitted tree    median {statistics.median(a):8.0f}   min {min(a):8.0f}   max {max(a):8.0f}")
     print(f"                         rebuilt tree     median {statistics.median(b):8.0f}   min {min(b):8.0f}   max {max(b):8.0f}    refit / rebuilt = {statistics.median(a) / statistics.median(b):.3f}")
 ctx.close()
+guard_section(tris0, mats, ext, cam)

@@ -415,7 +415,8 @@ int rvpt_hip_get_launch_info(rvpt_hip_ctx *ctx, uint32_t *grid_blocks, uint32_t 
  * bit 2 = the launch's work plan starts every camera round on a 16 x 4 block (where it does not, the kernel skips the rectangles for that round), bit 4 = the leaf
  * boxes of the bounce rounds (with the table; RVPT_HIP_PACKETS_BOX_CULL=0 switches them off), bit 5 = the interleaved claim order (a frame's blocks dealt from all
  * over the frame; RVPT_HIP_PACKETS_INTERLEAVE=0 gives the tile-linear order), bit 6 = the kernel instance for launches with all three culls (the walks without
- * a cull compiled out: fewer registers to keep alive).  0 for
+ * a cull compiled out: fewer registers to keep alive), bit 7 = the batched launch that claims only the blocks that are not sky, bit 8 = the row boxes of bounce
+ * packets whose rays leave one triangle (with the leaf boxes; RVPT_HIP_PACKETS_BOX_CULL=0 switches both off).  0 for
  * every other kernel.  The image never depends on these; tools/fuzz_culls.py records them. */
 int rvpt_hip_get_cull_info(rvpt_hip_ctx *ctx, uint32_t *flags);
 

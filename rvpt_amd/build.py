@@ -92,6 +92,22 @@ def build_native_debug(force: bool = False) -> Path:
     return DEBUG_LIB_PATH
 
 
+TIMELINE_LIB_PATH = _PKG / "librvpt_hip_timeline.so"
+
+
+def build_native_timeline(force: bool = False) -> Path:
+    """The laboratory build with the packet kernel's per-wave timeline compiled in (-DRV_PACKETS_TIMELINE=1; five waves per SIMD: the clocks and counters need the
+    registers of the sixth): RVPT_HIP_TIMELINE=<file> then dumps, per wave, timestamps, round counts, the triangles the culled bounce rounds walked and how many of
+    those rounds took the row boxes (tools/packets_timeline.py, tools/row_box_paths.py, tests/test_row_boxes_gpu.py)."""
+    if not force and TIMELINE_LIB_PATH.exists() and TIMELINE_LIB_PATH.stat().st_mtime >= max(p.stat().st_mtime for p in SOURCES + HEADERS):
+        return TIMELINE_LIB_PATH
+    cmd = [hipcc(), *FLAGS, "-DRVPT_HIP_LAB=1", "-DRV_PACKETS_TIMELINE=1", "-DRV_PACKETS_MIN_WAVES=5", *map(str, SOURCES), "-o", str(TIMELINE_LIB_PATH)]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + res.stdout + res.stderr)
+    return TIMELINE_LIB_PATH
+
+
 def build_leaf_variant(leaf_tris: int) -> Path:
     """The release library with another leaf size of the device BVH build (-DRVPT_LBVH_LEAF_TRIS, rvpt_build.h): rvpt_amd/librvpt_hip_leaf<L>.so, for the
     leaf-size sweep of tools/build_bench.py (RVPT_HIP_LIB=<that file> LEAF_TRIS=<L> tools/build_bench.py traversal)."""
@@ -109,8 +125,16 @@ HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selft
                 "host_selftest_build": ["host_selftest_build.cpp", "rvpt_host.cpp"], "host_selftest_build_ploc": ["host_selftest_build_ploc.cpp", "rvpt_host.cpp"],
                 "host_selftest_build_sah": ["host_selftest_build_sah.cpp", "rvpt_host.cpp"],
                 "host_selftest_frames": ["host_selftest_frames.cpp", "rvpt_host.cpp"],
-                "host_selftest_guard": ["host_selftest_guard.cpp", "rvpt_host.cpp"]}
+                "host_selftest_guard": ["host_selftest_guard.cpp", "rvpt_host.cpp"],
+                "host_row_boxes": ["host_row_boxes.cpp"]}  # (rvpt_vis.h alone: the row boxes' table for scenes given in files, tests/test_row_boxes.py)
 HOST_NEEDS_HIP = {"host_selftest_frames"}  # targets that allocate device memory themselves (its `--gpu` case): HIP's host API, still compiled by g++
+
+
+HOST_WITH_HIPCC = {"host_row_boxes"}  # targets that include the kernels' host + device headers (csrc/): the host half of a HIP compilation, no device code, no library
+
+
+def hipcc_host_cmd(sources, out, extra=()) -> list:
+    return [hipcc(), "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function", *extra, *map(str, sources), "-o", str(out)]
 
 
 def _hip_host_flags() -> list:
@@ -124,7 +148,7 @@ def build_host(force: bool = False) -> Path:
     g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames` and `host_selftest_guard`."""
     build_native()
     HOST_BIN_DIR.mkdir(exist_ok=True)
-    srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h"]
+    srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h", _PKG / "csrc" / "rvpt_vis.h"]
     newest = max(p.stat().st_mtime for p in srcs + [LIB_PATH])
     for name, files in HOST_TARGETS.items():
         out = HOST_BIN_DIR / name
@@ -132,9 +156,11 @@ def build_host(force: bool = False) -> Path:
             continue
         cmd = [shutil.which("g++") or "g++", "-O2", "-std=c++17", "-Wall", "-Wextra", *[str(HOST_DIR / f) for f in files], "-o", str(out),
                f"-L{_PKG}", "-lrvpt_hip", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", *(_hip_host_flags() if name in HOST_NEEDS_HIP else [])]
+        if name in HOST_WITH_HIPCC:
+            cmd = hipcc_host_cmd([HOST_DIR / f for f in files], out)
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:
-            raise RuntimeError("g++ failed:\n" + " ".join(cmd) + "\n" + res.stdout + res.stderr)
+            raise RuntimeError("host build failed:\n" + " ".join(cmd) + "\n" + res.stdout + res.stderr)
     return HOST_BIN_DIR
 
 
@@ -143,4 +169,5 @@ if __name__ == "__main__" and len(__import__("sys").argv) > 2 and __import__("sy
 elif __name__ == "__main__":
     print(build_native(force=True, verbose=True))
     print(build_native_debug(force=True))
+    print(build_native_timeline(force=True))
     print(build_host(force=True))

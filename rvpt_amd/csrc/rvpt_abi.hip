@@ -160,6 +160,11 @@ struct rvpt_hip_ctx {
     size_t vis_cap = 0;                       // in words
     float4 *d_leaf_boxes = nullptr;           // the leaf boxes of the bounce rounds (rvpt_vis.h), made with the table; two float4 per kLeafTris triangles
     size_t leaf_boxes_cap = 0;                // in float4
+    uint32_t *d_row_bits = nullptr;           // the row boxes of the bounce rounds (rvpt_vis.h), made with the leaf boxes: the refined rows (d_vis' layout) ...
+    size_t row_bits_cap = 0;                  // in words
+    float4 *d_row_boxes = nullptr;            // ... and every row's own boxes, two float4 per leaf, 32 / kLeafTris * vis_words leaves per row
+    size_t row_boxes_cap = 0;                 // in float4
+    bool have_row_boxes = false;              // made for the scene in d_prep
     uint32_t vis_words = 0;                   // 0: no table for this scene
     double scene_scale = 0.0;                 // largest |coordinate| + largest extent of the uploaded triangles: what float errors of positions scale with
     // screen rectangles of the triangles for the packet kernel's camera rounds (rvpt_rect.h), one buffer per launch slot: rewritten (camera_rects, on the
@@ -203,6 +208,7 @@ struct rvpt_hip_ctx {
         int force_stack_levels = 0;       // RVPT_HIP_BVH_FORCE_STACK_LEVELS (tests of RVPT_HIP_DEBUG): lie to the kernels about the stack the tree needs
         bool packets_cull = true, packets_bounce_cull = true, packets_box_cull = true;  // RVPT_HIP_PACKETS_CULL / _BOUNCE_CULL / _BOX_CULL=0: each cull off (A/B)
         bool packets_lean_instance = true;  // RVPT_HIP_PACKETS_LEAN_INSTANCE=0: the general instances only (A/B)
+        bool packets_row_boxes = true;    // RVPT_HIP_PACKETS_ROW_BOXES=0 (laboratory build): uniform packets walk the union and the shared leaf boxes like the others (A/B)
         int packets_interleave = 1;       // RVPT_HIP_PACKETS_INTERLEAVE=g: launches of < 4 frames deal groups of g (1, 2, 4, 8) blocks from all over the frame; 0 = tile-linear (A/B)
         bool packets_interleave_all = false;  // ... =-g: launches of any size (measured slower for the batched ones: profiles/r06_interleave.txt)
         int packets_sky_list = 1;         // RVPT_HIP_PACKETS_SKY_LIST (laboratory build): batched launches claim only the blocks that are not sky (0 = off, 1 = once the
@@ -257,6 +263,7 @@ rvpt_hip_ctx::Knobs read_knobs(uint32_t flags)
     set_flag(k.brute_packets, getenv("RVPT_HIP_BRUTE_PACKETS"));
     set_int(k.force_stack_levels, getenv("RVPT_HIP_BVH_FORCE_STACK_LEVELS"), 0, INT32_MAX);
     set_flag(k.packets_lean_instance, getenv("RVPT_HIP_PACKETS_LEAN_INSTANCE"));
+    set_flag(k.packets_row_boxes, getenv("RVPT_HIP_PACKETS_ROW_BOXES"));
     if (const char *e = getenv("RVPT_HIP_TIMELINE")) k.timeline_path = e;
     set_int(k.blocks_per_cu, getenv("RVPT_HIP_BLOCKS_PER_CU"), 1, 8);
     set_int(k.first_units, getenv("RVPT_HIP_FIRST_UNITS"), 1, 1 << 20);
@@ -413,7 +420,9 @@ bool has_global_stack(Variant v) { return v == Variant::Bvh || v == Variant::Wid
 // rvpt_hip_get_cull_info bits (native.cull_info, tools/fuzz_culls.py): the screen rectangles (FrameParams::rects), the bounce table (vis), camera rounds
 // aligned to 16 x 4 blocks, the leaf boxes of the bounce rounds (leaf_boxes), the interleaved claim order (perm_*), the packet instance without the uncull'd walks
 // ... and the batched launch that claims only the blocks that are not sky (trace_brute_packets_aa1_culls_listed + blend_accumulate_sky)
+// ... and the row boxes of packets that leave one triangle (row_bits, row_boxes)
 constexpr uint32_t kCullRects = 1u, kCullBounce = 2u, kCullBlockRounds = 4u, kCullLeafBoxes = 16u, kCullClaimOrder = 32u, kCullLeanInstance = 64u, kCullSkyList = 128u;
+constexpr uint32_t kCullRowBoxes = 256u;
 
 struct Launch {
     Kernel kernel;
@@ -707,6 +716,7 @@ int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, i
             p.vis_words = ctx->vis_words;
             p.vis_stride = (ctx->vis_words + 3u) & ~3u;
             if (k.packets_box_cull && ctx->d_leaf_boxes) p.leaf_boxes = ctx->d_leaf_boxes;
+            if (p.leaf_boxes && k.packets_row_boxes && ctx->have_row_boxes) p.row_bits = ctx->d_row_bits, p.row_boxes = ctx->d_row_boxes;
         }
     }
     if (bvh && k.force_stack_levels > 0) {  // tests: a stack smaller than the tree needs — the kernels clamp and report (RVPT_HIP_DEBUG)
@@ -793,7 +803,8 @@ int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, i
         l.work.div_listed_frame = rv::fast_div_make(64u * n_listed);
     }
     l.cull_bits = (cull ? kCullRects : 0u) | (p.vis ? kCullBounce : 0u) | ((v == Variant::BrutePackets && p.first_units % 4u == 0u) ? kCullBlockRounds : 0u) |
-                  (p.leaf_boxes ? kCullLeafBoxes : 0u) | (p.perm_groups != 0u ? kCullClaimOrder : 0u) | (lean ? kCullLeanInstance : 0u) | (l.listed ? kCullSkyList : 0u);
+                  (p.leaf_boxes ? kCullLeafBoxes : 0u) | (p.perm_groups != 0u ? kCullClaimOrder : 0u) | (lean ? kCullLeanInstance : 0u) | (l.listed ? kCullSkyList : 0u) |
+                  (p.row_boxes ? kCullRowBoxes : 0u);
     return 0;
 }
 
@@ -929,6 +940,8 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     }
     if (ctx->d_vis) (void)hipFree(ctx->d_vis);
     if (ctx->d_leaf_boxes) (void)hipFree(ctx->d_leaf_boxes);
+    if (ctx->d_row_bits) (void)hipFree(ctx->d_row_bits);
+    if (ctx->d_row_boxes) (void)hipFree(ctx->d_row_boxes);
     if (ctx->d_gather) (void)hipFree(ctx->d_gather);
     if (ctx->d_barrier) (void)hipFree(ctx->d_barrier);
     if (ctx->d_quant) (void)hipFree(ctx->d_quant);
@@ -1000,6 +1013,7 @@ static int derive_bounce_state(rvpt_hip_ctx *ctx, bool bvh, const rvpt_triangle 
     int rc;
     ctx->vis_words = 0;
     ctx->scene_scale = 0.0;
+    ctx->have_row_boxes = false;
     if (!bvh && n_tris > 0 && n_tris <= rv::kResidentMaxTris) {
         const double scale = rv::bounce_scene_scale(reinterpret_cast<const float *>(tris), n_tris);
         if (scale > 0.0) {
@@ -1020,6 +1034,14 @@ static int derive_bounce_state(rvpt_hip_ctx *ctx, bool bvh, const rvpt_triangle 
             rv::bounce_leaf_boxes(reinterpret_cast<const float *>(tris), n_tris, scale, boxes.data());
             if ((rc = grow(ctx, ctx->d_leaf_boxes, ctx->leaf_boxes_cap, 2 * n_leaves, sizeof(float4)))) return rc;
             HIP_TRY(ctx, hipMemcpy(ctx->d_leaf_boxes, boxes.data(), boxes.size() * sizeof(float), hipMemcpyHostToDevice));
+            // ... and the row boxes (rvpt_vis.h): every row's refined words and its own box per leaf, from the records and the leaf boxes just copied
+            if ((rc = grow(ctx, ctx->d_row_bits, ctx->row_bits_cap, total, sizeof(uint32_t)))) return rc;
+            if ((rc = grow(ctx, ctx->d_row_boxes, ctx->row_boxes_cap, static_cast<size_t>(2) * n * 2 * n_leaves, sizeof(float4)))) return rc;
+            hipLaunchKernelGGL(rv::bounce_row_boxes, dim3(static_cast<uint32_t>((total + 63) / 64)), dim3(64), 0, ctx->stream, ctx->d_prep, n, scale, words, stride,
+                               reinterpret_cast<const float *>(ctx->d_leaf_boxes), ctx->d_row_bits, reinterpret_cast<float *>(ctx->d_row_boxes));
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            ctx->have_row_boxes = true;
         }
     }
     return 0;
@@ -2380,21 +2402,22 @@ int rvpt_hip_selftest_bounce_cull(rvpt_hip_ctx *ctx, uint32_t n_samples, uint64_
     p.vis_words = ctx->vis_words;
     p.vis_stride = (ctx->vis_words + 3u) & ~3u;
     p.leaf_boxes = ctx->d_leaf_boxes;
+    if (ctx->have_row_boxes) p.row_bits = ctx->d_row_bits, p.row_boxes = ctx->d_row_boxes;
     unsigned long long *d_out = nullptr;
-    unsigned long long h_out[5] = {};
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&d_out), 5 * sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(d_out, 0, 5 * sizeof(unsigned long long), ctx->stream);
+    unsigned long long h_out[6] = {};
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&d_out), 6 * sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(d_out, 0, 6 * sizeof(unsigned long long), ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(rv::selftest_bounce_cull, dim3(static_cast<uint32_t>(ctx->num_cus) * 8u), dim3(256), 0, ctx->stream, p, n_samples, d_out);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream);
     std::vector<uint32_t> table(static_cast<size_t>(2) * ctx->n_tris * ((ctx->vis_words + 3u) & ~3u));  // (the padding words are zero)
     if (e == hipSuccess) e = hipMemcpyAsync(table.data(), ctx->d_vis, table.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     (void)hipFree(d_out);
     if (e != hipSuccess) return fail(ctx, RVPT_HIP_ERR_HIP, "selftest_bounce_cull -> %s", hipGetErrorString(e));
-    out[0] = h_out[0], out[1] = h_out[1], out[4] = h_out[2], out[5] = h_out[3], out[6] = h_out[4];
+    out[0] = h_out[0], out[1] = h_out[1], out[4] = h_out[2], out[5] = h_out[3], out[6] = h_out[4], out[7] = h_out[5];
     for (uint32_t w : table) out[2] += static_cast<uint64_t>(__builtin_popcount(w));
     out[3] = static_cast<uint64_t>(2) * ctx->n_tris * ctx->n_tris;
     return RVPT_HIP_OK;

@@ -150,6 +150,9 @@ struct FrameParams {
     uint32_t vis_stride;      // ... and words from one row to the next: vis_words rounded up to a multiple of four (16-byte rows, zero padded)
     const float4 *leaf_boxes; // packet kernel (with vis): two float4 per group of kLeafTris consecutive triangles — (lo.xyz, hi.x) (hi.yz, 0, 0), widened (rvpt_vis.h:
                               // bounce_leaf_boxes); a bounce round drops a group no lane's ray can come near.  nullptr = off
+    const uint32_t *row_bits; // packet kernel (with leaf_boxes): the REFINED rows — vis' layout and stride; bit B of row 2 A + s = B is in the row and has a part above H0 over
+                              // A's plane on side s (rvpt_vis.h: bounce_row_boxes_word) — read with scalar loads by packets whose rays all leave one triangle.  nullptr = off
+    const float4 *row_boxes;  // ... and that row's own boxes, two float4 per leaf as leaf_boxes, 32 / kLeafTris * vis_words leaves per row: the parts above H0 only
     uint32_t bvh_cam_min;     // camera packets (trace_bvh4_resident): at least this many lanes must start a camera ray at once to walk as a packet
     uint32_t bvh_detach;      // ... and the lanes of a node leave the packet (go on per lane) when at most this many of them are in it
     // work distribution plan (units of kUnit work indices, see WavePool): wave w owns units

@@ -40,10 +40,15 @@ __global__ void sky_list(const uint32_t *__restrict__ sky_bits, uint32_t n_block
 // the bounce cull's table for `n` prepared triangles: out[(2 A + s) * words + w] bit b = 0 only when triangle B = 32 w + b lies wholly behind the plane of A as
 // seen from side s (s = 0: the side A's normal cross(e0, e1) points to), by more than `margin`, and both triangles are well shaped; bits >= n are 0
 __global__ void bounce_visibility(const float4 *__restrict__ prep, uint32_t n, double margin, uint32_t words, uint32_t stride, uint32_t *__restrict__ out);
+// the row boxes of the same table (rvpt_vis.h: bounce_row_boxes_word): refined[(2 A + s) * stride + w] and the 32 / kLeafTris boxes of that word at
+// boxes[8 * ((2 A + s) * (32 / kLeafTris) * words + (32 / kLeafTris) * w)]; leaf_boxes: bounce_leaf_boxes' array padded to whole words; one thread per (row, word)
+__global__ void bounce_row_boxes(const float4 *__restrict__ prep, uint32_t n, double scale, uint32_t words, uint32_t stride, const float *__restrict__ leaf_boxes,
+                                 uint32_t *__restrict__ refined, float *__restrict__ boxes);
 #if RVPT_HIP_LAB
 // diagnostics (rvpt_hip_selftest_bounce_cull): every pixel x n_samples paths traced against EVERY triangle; on segments that leave a triangle, out[0] += pairs the
 // float test accepts with the interval wide open, out[1] += those whose triangle is NOT in the row of where the segment leaves from (must stay 0), out[2] += those whose
-// ray fails the slab test of the triangle's leaf box (must stay 0), out[3] / out[4] += (ray, leaf box) pairs tested / passed
+// ray fails the slab test of the triangle's leaf box (must stay 0), out[3] / out[4] += (ray, leaf box) pairs tested / passed, out[5] += those whose bit is cleared in
+// the refined row of where the segment leaves from or whose ray fails the slab test of that row's box of the triangle's leaf (row boxes; must stay 0)
 __global__ void selftest_bounce_cull(const FrameParams p, uint32_t n_samples, unsigned long long *__restrict__ out);
 // diagnostics (rvpt_hip_selftest_camera_rects): every pixel of the image x n_samples jittered camera rays x every triangle through the float test with
 // an open interval; out[0] += accepted pairs, out[1] += accepted pairs whose block lies OUTSIDE the triangle's rectangle (must stay 0),

@@ -158,7 +158,7 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
     uint32_t nsmp = 0;
     // optional timeline (RVPT_HIP_TIMELINE): [0] start [1] pool dry [2] end (100 MHz wall clock) [3] camera rounds | bounce rounds << 32 [4] split rounds | lane-rounds << 32
     unsigned long long t_start = 0, t_dry = 0;
-    uint32_t n_cam = 0, n_bounce = 0, n_split = 0, lane_rounds = 0, n_listed = 0;  // [5] triangles walked by the culled bounce rounds
+    uint32_t n_cam = 0, n_bounce = 0, n_split = 0, lane_rounds = 0, n_listed = 0, n_uniform = 0;  // [5] triangles walked by the culled bounce rounds | those of them that took the row boxes << 32
     uint32_t n_after_dry = 0, lanes_after_dry = 0;  // [6] rounds | lane-rounds << 32 after the pool ran dry for this wave; [7] the wave's last camera round (clock)
     unsigned long long t_last_cam = 0;
     if (RV_PACKETS_TIMELINE && p.timeline) t_start = wall_clock64();
@@ -337,17 +337,37 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
             const bool own_row = has && leave != 0xFFFFFFFFu;
             constexpr uint32_t kPerWord = 32u / kLeafTris, kMask = (1u << kLeafTris) - 1u;
             constexpr uint32_t kBatchMask = static_cast<uint32_t>((1ull << (RV_BOX_BATCH * kLeafTris)) - 1ull);
+            // Round 8, the ROW BOXES (rvpt_vis.h): a packet whose rays all leave ONE triangle on one side (the headline frame: 97 % of them) needs no union — its row
+            // is one row, wave-uniform — and gets more than the table's: the REFINED row (members with a part above H0 over the leaving plane: the coplanar neighbours
+            // are gone) through scalar loads, and that row's OWN boxes, which hold only those parts, in place of the shared leaf boxes its rays start inside.
+            // Uniform: every lane with a ray names the same `leave` as the first of them, and that is a row (a lane that votes for every box differs from it or is it).
+            typedef const __attribute__((address_space(4))) uint32_t *ConstRowWords;
+            bool uni = false;
+            uint32_t uni_row = 0u;
+            if (boxes && p.row_boxes != nullptr) {
+                uni_row = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(leave), static_cast<int>(__builtin_ctzll(active))));
+                uni = uni_row != 0xFFFFFFFFu && ballot(has && leave != uni_row) == 0;
+            }
+            const ConstRowWords row_bits_k = (ConstRowWords)(reinterpret_cast<uintptr_t>(p.row_bits)) + static_cast<size_t>(uni ? uni_row : 0u) * p.vis_stride;
+            const ConstFloats boxes_k = uni ? (ConstFloats)(reinterpret_cast<uintptr_t>(p.row_boxes)) + static_cast<size_t>(uni_row) * (8u * kPerWord * p.vis_words) : leaf_boxes_k;
+            if (RV_PACKETS_TIMELINE && p.timeline) n_uniform += uni ? 1u : 0u;
             // What a bounce round WAITS for (the per-phase clocks of tools/packets_timeline.py: the culls took a quarter of a wave's time, more than the triangle tests they
             // leave): a row word per 32 triangles and a box per leaf, each a load the next step depended on.  So: FOUR words of the lane's row in one 16-byte load (rows
             // are 16-byte aligned, a multiple of four words apart, zero padded: vis_stride), the four wave-wide ORs back to back, and a word's boxes in ONE scalar request
             // (contiguous: 32 B x kPerWord) before any of them is tested.
             for (uint32_t w0 = 0; w0 < p.vis_words; w0 += 4u) {
-                uint4 r = make_uint4(0u, 0u, 0u, 0u);
-                if (own_row) r = *reinterpret_cast<const uint4 *>(row + w0);
-                if (vote_all) r = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-                // (all four even where the scene has fewer words — 143 triangles are five: four and one —: four independent DPP chains overlap, three branches around
-                // them measured 3 % slower)
-                const uint32_t m[4] = {wave_or(r.x), wave_or(r.y), wave_or(r.z), wave_or(r.w)};
+                uint32_t m[4];
+                if (uni) {  // (wave-uniform) four words of the refined row: one scalar request (rows are 16-byte aligned, zero padded)
+#pragma unroll
+                    for (uint32_t j = 0; j < 4u; ++j) m[j] = row_bits_k[w0 + j];
+                } else {
+                    uint4 r = make_uint4(0u, 0u, 0u, 0u);
+                    if (own_row) r = *reinterpret_cast<const uint4 *>(row + w0);
+                    if (vote_all) r = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+                    // (all four even where the scene has fewer words — 143 triangles are five: four and one —: four independent DPP chains overlap, three branches
+                    // around them measured 3 % slower)
+                    m[0] = wave_or(r.x), m[1] = wave_or(r.y), m[2] = wave_or(r.z), m[3] = wave_or(r.w);
+                }
                 RV_PHASE(4)
 #pragma unroll
                 for (uint32_t j = 0; j < 4u; ++j) {
@@ -362,7 +382,7 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
 #pragma unroll
                         for (uint32_t k0 = 0; k0 < kPerWord; k0 += RV_BOX_BATCH) {
                             if (((todo >> (kLeafTris * k0)) & kBatchMask) == 0u) continue;  // (wave-uniform)
-                            const ConstFloats b = leaf_boxes_k + 8u * (kPerWord * w + k0);
+                            const ConstFloats b = boxes_k + 8u * (kPerWord * w + k0);
                             float bb[8u * RV_BOX_BATCH];
 #pragma unroll
                             for (uint32_t i = 0; i < 8u * RV_BOX_BATCH; ++i) bb[i] = ((i & 7u) < 6u) ? b[i] : 0.0f;
@@ -430,7 +450,7 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
         t[2] = wall_clock64();
         t[3] = n_cam | (static_cast<unsigned long long>(n_bounce) << 32);
         t[4] = n_split | (static_cast<unsigned long long>(lane_rounds) << 32);
-        t[5] = n_listed;
+        t[5] = n_listed | (static_cast<unsigned long long>(n_uniform) << 32);
         t[6] = n_after_dry | (static_cast<unsigned long long>(lanes_after_dry) << 32);
         t[7] = t_last_cam;
     }
@@ -511,6 +531,20 @@ __global__ void bounce_visibility(const float4 *__restrict__ prep, uint32_t n, d
     out[id] = w >= words ? 0u : bounce_row_word(reinterpret_cast<const float *>(prep), n, row, w, margin);  // rvpt_vis.h: the host evaluates the same function (rvpt_bounce_rows)
 }
 
+__global__ void bounce_row_boxes(const float4 *__restrict__ prep, uint32_t n, double scale, uint32_t words, uint32_t stride, const float *__restrict__ leaf_boxes,
+                                 uint32_t *__restrict__ refined, float *__restrict__ boxes)
+{
+    const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= 2u * n * stride) return;
+    const uint32_t row = id / stride, w = id - row * stride;
+    if (w >= words) {  // (the rows' zero padding; the boxes have none: 32 / kLeafTris * words per row)
+        refined[id] = 0u;
+        return;
+    }
+    constexpr uint32_t kPerWord = 32u / kLeafTris;
+    refined[id] = bounce_row_boxes_word(reinterpret_cast<const float *>(prep), n, row, w, scale, leaf_boxes, boxes + 8u * (static_cast<size_t>(row) * kPerWord * words + kPerWord * w));
+}
+
 __global__ void camera_rects(const FrameParams p, uint2 *__restrict__ rects, float4 *__restrict__ records)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -581,7 +615,7 @@ __global__ void selftest_camera_rects(const FrameParams p, const uint2 *__restri
 
 __global__ void selftest_bounce_cull(const FrameParams p, uint32_t n_samples, unsigned long long *__restrict__ out)
 {
-    unsigned long long accepted = 0, outside = 0, outside_box = 0, box_tests = 0, box_hits = 0;
+    unsigned long long accepted = 0, outside = 0, outside_box = 0, box_tests = 0, box_hits = 0, outside_row_box = 0;
     const ShadeSrc shade_src{p.prep, p.mat_index, p.mats, p.unit_n};
     const uint32_t n_px = p.width * p.height;
     for (uint32_t px = blockIdx.x * blockDim.x + threadIdx.x; px < n_px; px += gridDim.x * blockDim.x) {
@@ -613,6 +647,12 @@ __global__ void selftest_bounce_cull(const FrameParams p, uint32_t n_samples, un
                             const uint32_t leaf = j / kLeafTris;
                             outside_box += leaf_slab(lr, p.leaf_boxes[2u * leaf + 0u], p.leaf_boxes[2u * leaf + 1u]) ? 0u : 1u;
                         }
+                        if (p.row_boxes != nullptr) {  // ... is in the refined row, and the ray passes the slab test of THAT ROW's box of the triangle's leaf
+                            const uint32_t refined = p.row_bits[static_cast<size_t>(leave) * p.vis_stride + (j >> 5)];
+                            const size_t box = static_cast<size_t>(leave) * (32u / kLeafTris) * p.vis_words + j / kLeafTris;
+                            const bool in = ((refined >> (j & 31u)) & 1u) != 0u && leaf_slab(lr, p.row_boxes[2u * box + 0u], p.row_boxes[2u * box + 1u]);
+                            outside_row_box += in ? 0u : 1u;
+                        }
                     }
                     if (leave != 0xFFFFFFFFu && p.leaf_boxes != nullptr && (j % kLeafTris) == 0u) {  // how selective the boxes are, per ray
                         box_tests += 1;
@@ -633,6 +673,7 @@ __global__ void selftest_bounce_cull(const FrameParams p, uint32_t n_samples, un
         outside_box += __shfl_down(outside_box, off, 64);
         box_tests += __shfl_down(box_tests, off, 64);
         box_hits += __shfl_down(box_hits, off, 64);
+        outside_row_box += __shfl_down(outside_row_box, off, 64);
     }
     if (lane_id() == 0) {
         atomicAdd(&out[0], accepted);
@@ -640,6 +681,7 @@ __global__ void selftest_bounce_cull(const FrameParams p, uint32_t n_samples, un
         atomicAdd(&out[2], outside_box);
         atomicAdd(&out[3], box_tests);
         atomicAdd(&out[4], box_hits);
+        atomicAdd(&out[5], outside_row_box);
     }
 }
 

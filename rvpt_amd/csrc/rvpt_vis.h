@@ -127,4 +127,116 @@ inline void bounce_leaf_boxes(const float *tris, const size_t n_tris, const doub
 constexpr double kBounceMarginScales = 0x1p-10;  // the table's margin in scene scales: eight times the float error a position can carry under the launch-time premise
 constexpr double kBounceCameraScales = 64.0;     // ... which is: the camera (the first segment's origin) no further than this many scene scales from the world origin
 
+// ---- the row boxes of the bounce rounds (round 8) ---------------------------------------------------------------------------------------------------------
+// Nearly every packet of bounce rays leaves ONE triangle on one side (the headline frame: 96.8 %), and the shared leaf boxes cannot cull what such a packet walks:
+// its rays start inside them, an EPSILON above a plane that most of the row's members lie in.  So every row 2 A + s gets boxes of its own, one per leaf, and a
+// REFINED ROW beside them (same words, same stride as the table's): both keep of a member B only the part at height >= H0(B) above A's plane on side s (height:
+// side * dot(x - v0_A, n_A) / |n_A| on the float record taken as exact, as bounce_row_word measures it).  Bit B of the refined row is set iff it is set in the
+// table and some vertex of B reaches H0(B); the box of (row, leaf) bounds the polygons {x in B : height >= H0(B)} of those members (the triangle clipped at the
+// plane, in double), widened by the leaf boxes' M and rounded to float; no such member: the empty box lo = +inf, hi = -inf, which a round never tests (the leaf's
+// bits of the refined row are zero, and the walk looks at the bits first — the slab test itself is symmetric in lo and hi and cannot express "empty").
+//
+// H0 is derived.  eps = EPSILON, margin = 2^-10 scale (the table's), E' = scale + 2 eps.  A segment whose `leave` names (A, s) (rvpt_device.h: shade):
+//   * starts at o = fma3(N', +-eps, pos), N' = the float unit normal of A (unit to 2^-22), pos = the accepted hit on A: on A's plane up to the float error of a
+//     position, <= 2^-13 scale under the launch-time premise (camera within 64 scales; the table's proof budgets the same) — height(o) >= eps - 2^-13 scale -
+//     2^-22 eps - 2^-23 E' (the fma's rounding of coordinates <= E');
+//   * does not descend towards the plane, up to rounding: dot(d, N') >= -2^-18 |d| (Lambert: > 0; mirror: cos_in >= 0 with 2^-22 of error; refraction: eta 2^-22,
+//     eta <= 16, else shade says "anywhere"); a point Y of the exact ray that an accepted pair needs lies within E_B of the scene, |Y - o| <= 4 E', so the
+//     descent up to Y is <= 2^-16 E'.
+//   So every point of the exact ray with t > 0 that matters has height >= eps - 2^-13 scale - 2^-15 E'.  The float test accepts (ray, B) only when such a point Y
+//   lies within E_B = (33 * 2^-24 / kappa_B)(t + S) of a point X of B (rvpt_rect.h), and height is 1-Lipschitz: height(X) >= eps - 2^-13 scale - 2^-15 E' - E_B.
+//   With t |d| <= 4 E' and S = |o|_1 + |v0 - o|_1 + |e0|_1 + |e1|_1 <= 6 E' + |e0|_1 + |e1|_1:  E_B <= (33 * 2^-24 / kappa_B)(10 E' + |e0|_1 + |e1|_1), computed per B.
+//   H0(B) = eps - margin - 2^-14 E' - E_B  —  the whole margin where the proof needs an eighth of it, 2^-14 E' where it needs 2^-15: looser than necessary, provable.
+//   X therefore lies in B's clipped polygon, and Y inside the polygon's bounds widened by E_B.  As for the leaf boxes the widening M = 2^-9 E' pays for E_B
+//   (a member with E_B > 0.4 M — kappa_B near 2^-6 — breaks the premise) and for the slab test's own error, 2^-12 of the remaining 0.6 M.
+// Premises, carried over from the table and the leaf boxes: A and B finite, non-degenerate, kappa >= 2^-6, a scene that has a scale; and E_B <= 0.4 M.  Where A
+// fails, the row's boxes are the shared leaf boxes and its refined words the table's; where a member B fails, its leaf's box in that row is the shared leaf box
+// and B's bit stays.  A positive H0 (scale < ~1.5 eps 2^10: the headline's is 3.2, H0 = +0.0016) drops the coplanar neighbours and A itself from the row; a scene
+// far larger than EPSILON gets H0 ~ -margin and keeps only what the clipped boxes save.
+// Checked like the table: tests/test_row_boxes.py (float64 restatement, GPU-free) and rvpt_hip_selftest_bounce_cull out[7] (accepted pairs that fail their row box
+// or whose refined bit is cleared: 0).
+constexpr double kRowSlackScales = 0x1p-14;
+
+// One word w of the refined row `row` (returned) and the boxes of its 32 / kLeafTris leaves (boxes_out: 8 floats each — lo.xyz, hi.xyz, 0, 0).  prep, n, row, w:
+// bounce_row_word's; scale = bounce_scene_scale; leaf_boxes = bounce_leaf_boxes' array, padded to whole words (leaf 32 / kLeafTris * w + k at 8 floats each)
+RV_HD uint32_t bounce_row_boxes_word(const float *prep, const uint32_t n, const uint32_t row, const uint32_t w, const double scale, const float *leaf_boxes, float *boxes_out)
+{
+    constexpr uint32_t kPerWord = 32u / kLeafTris;
+    const double eps = static_cast<double>(kEpsilon);
+    const double margin = kBounceMarginScales * scale;
+    const double Es = scale + 2.0 * eps;
+    const double M = kLeafBoxMarginScales * (scale + 2.0 * 0.005);  // bounce_group_boxes' M
+    const uint32_t bits = bounce_row_word(prep, n, row, w, margin);
+    const uint32_t A = row >> 1;
+    const double side = (row & 1u) ? -1.0 : 1.0;
+    const float *a = prep + 16u * A;
+    const double av0[3] = {a[0], a[1], a[2]}, an[3] = {a[3], a[4], a[5]}, ae0[3] = {a[6], a[7], a[8]}, ae1[3] = {a[9], a[10], a[11]};
+    const double nn = __builtin_sqrt(an[0] * an[0] + an[1] * an[1] + an[2] * an[2]);
+    bool a_ok;
+    {
+        const double a00 = ae1[0] * ae1[0] + ae1[1] * ae1[1] + ae1[2] * ae1[2], a11 = ae0[0] * ae0[0] + ae0[1] * ae0[1] + ae0[2] * ae0[2];
+        const double a01 = ae0[0] * ae1[0] + ae0[1] * ae1[1] + ae0[2] * ae1[2];
+        a_ok = (a00 * a11 - a01 * a01) >= 0x1p-6 * (a00 * a11) && a00 * a11 > 0.0 && nn > 0.0 && margin > 0.0;
+        for (int k = 0; k < 3; ++k) a_ok = a_ok && (av0[k] - av0[k] == 0.0) && (an[k] - an[k] == 0.0);
+    }
+    const float inf = __builtin_inff();
+    uint32_t refined = 0u;
+    for (uint32_t k = 0; k < kPerWord; ++k) {
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+        bool shared = !a_ok, any = false;
+        for (uint32_t b = kLeafTris * k; b < kLeafTris * (k + 1u); ++b) {
+            const uint32_t B = 32u * w + b;
+            if (B >= n) break;
+            if (((bits >> b) & 1u) == 0u) continue;
+            refined |= 1u << b;
+            if (!a_ok) continue;
+            const float *q = prep + 16u * B;
+            const double v0[3] = {q[0], q[1], q[2]}, e0[3] = {q[6], q[7], q[8]}, e1[3] = {q[9], q[10], q[11]};
+            const double a00 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2], a11 = e0[0] * e0[0] + e0[1] * e0[1] + e0[2] * e0[2];
+            const double a01 = e0[0] * e1[0] + e0[1] * e1[1] + e0[2] * e1[2];
+            const double kappa = (a00 * a11 - a01 * a01) / (a00 * a11);
+            auto abs1 = [](const double *x) { return __builtin_fabs(x[0]) + __builtin_fabs(x[1]) + __builtin_fabs(x[2]); };
+            const double EB = (33.0 * 0x1p-24 / kappa) * (10.0 * Es + abs1(e0) + abs1(e1));
+            double p[3][3], h[3];
+            bool b_ok = kappa >= 0x1p-6 && a00 * a11 > 0.0 && EB <= 0.4 * M;  // (NaN: false)
+            for (int v = 0; v < 3; ++v) {
+                for (int c = 0; c < 3; ++c) p[v][c] = v0[c] + (v == 1 ? e0[c] : (v == 2 ? e1[c] : 0.0));
+                h[v] = side * ((p[v][0] - av0[0]) * an[0] + (p[v][1] - av0[1]) * an[1] + (p[v][2] - av0[2]) * an[2]) / nn;
+                b_ok = b_ok && (h[v] - h[v] == 0.0) && (p[v][0] - p[v][0] == 0.0) && (p[v][1] - p[v][1] == 0.0) && (p[v][2] - p[v][2] == 0.0);
+            }
+            if (!b_ok) {  // a premise fails for this member: it stays, and its leaf keeps the shared box in this row
+                shared = true;
+                continue;
+            }
+            const double H0 = eps - margin - kRowSlackScales * Es - EB;
+            const bool up[3] = {h[0] >= H0, h[1] >= H0, h[2] >= H0};
+            if (!(up[0] || up[1] || up[2])) {  // wholly below H0: no segment that leaves (A, s) is accepted by B
+                refined &= ~(1u << b);
+                continue;
+            }
+            any = true;
+            for (int v = 0; v < 3; ++v) {
+                const int u = v == 2 ? 0 : v + 1;
+                if (up[v])
+                    for (int c = 0; c < 3; ++c) lo[c] = p[v][c] < lo[c] ? p[v][c] : lo[c], hi[c] = p[v][c] > hi[c] ? p[v][c] : hi[c];
+                if (up[v] != up[u]) {  // the edge v -> u crosses the plane height = H0 (h[u] != h[v])
+                    const double s = (H0 - h[v]) / (h[u] - h[v]);
+                    for (int c = 0; c < 3; ++c) {
+                        const double x = p[v][c] + s * (p[u][c] - p[v][c]);
+                        lo[c] = x < lo[c] ? x : lo[c], hi[c] = x > hi[c] ? x : hi[c];
+                    }
+                }
+            }
+        }
+        float *o = boxes_out + 8u * k;
+        const float *sb = leaf_boxes + 8u * (kPerWord * w + k);
+        for (int c = 0; c < 3; ++c) {
+            o[c] = shared ? sb[c] : (any ? static_cast<float>(lo[c] - M) : inf);
+            o[3 + c] = shared ? sb[3 + c] : (any ? static_cast<float>(hi[c] + M) : -inf);
+        }
+        o[6] = o[7] = 0.0f;
+    }
+    return refined;
+}
+
 }  // namespace rv

@@ -25,6 +25,7 @@ COUNT_SEGMENTS, KERNEL_SIMPLE, TIMING, ACCUM_UNORM8 = 0x4, 0x8, 0x10, 0x20
 BVH_PER_LANE = 0x400  # BVH contexts: no camera packets, every segment walks the tree per lane (rounds 1-3's kernel)
 BRUTE_MIXED_PACKETS = 0x200  # brute-force contexts: round 2's mixed-packet frame kernel instead of the packet kernel (rvpt_packets.hip)
 FORMAT_RGBA32F, FORMAT_RGBA8_UNORM = 0, 1
+CULL_ROW_BOXES = 0x100  # Context.cull_info: the launch rode with the row boxes (rvpt_abi.hip: kCullRowBoxes)
 CULL_SKY_LIST = 0x80  # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
 TILE = 16
 TILE_SHIFT = 3  # RVPT_HIP_TILE_SHIFT: every row of the tile grid is rotated by this many more tiles than the one above (tile ownership)
@@ -592,7 +593,7 @@ class Context:
     def cull_info(self) -> int:
         """rvpt_hip_get_cull_info of the last launch: bit 0 screen rectangles, bit 1 bounce table, bit 2 camera rounds aligned to 16 x 4 blocks, bit 4 leaf boxes,
         bit 5 interleaved claim order, bit 6 the kernel instance without the uncull'd walks, bit 7 (CULL_SKY_LIST) the batched launch that claims only the blocks
-        that are not sky and blends the sky from the RNG."""
+        that are not sky and blends the sky from the RNG, bit 8 (CULL_ROW_BOXES) the row boxes of bounce packets that leave one triangle."""
         f = C.c_uint32(0)
         _check(self._L.rvpt_hip_get_cull_info(self._h, C.byref(f)), self._h, self._L)
         return f.value
@@ -609,7 +610,8 @@ class Context:
 
     def selftest_bounce_cull(self, n_samples: int = 1):
         """rvpt_hip_selftest_bounce_cull: (accepted pairs on segments that leave a triangle, those the bounce cull's table excludes — the claim is 0 —, bits set in
-        the table, bits in the table, accepted pairs whose ray fails its triangle's leaf box — the claim is 0 —, (segment, leaf box) pairs tested, passed, 0)."""
+        the table, bits in the table, accepted pairs whose ray fails its triangle's leaf box — the claim is 0 —, (segment, leaf box) pairs tested, passed, accepted pairs
+        that the refined row or the row box of where the segment leaves from excludes — the claim is 0)."""
         out = (C.c_uint64 * 8)()
         _check(self._L.rvpt_hip_selftest_bounce_cull(self._h, int(n_samples), out), self._h, self._L)
         return tuple(int(x) for x in out)

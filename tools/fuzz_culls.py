@@ -305,6 +305,8 @@ def run_case(case, oracle_budget):
         problems.append(f"bounce table excludes {int(bounce[1])} accepted pairs of {int(bounce[0])}")
     if bounce[4] != 0 and guard_on:
         problems.append(f"leaf boxes exclude {int(bounce[4])} accepted pairs of {int(bounce[0])}")
+    if bounce[7] != 0 and guard_on:
+        problems.append(f"row boxes exclude {int(bounce[7])} accepted pairs of {int(bounce[0])}")
     cost = case["W"] * case["H"] * len(case["tris"]) * case["aa"] * case["frames"]
     checked = False
     if cost <= oracle_budget:
@@ -373,6 +375,7 @@ def main():
         f" = {bounce_tot[2] / max(1, bounce_tot[3]):.3f}",
         f"  leaf boxes (the same launches): accepted pairs whose ray fails its triangle's box {int(bounce_tot[4])}; a ray passes {int(bounce_tot[6])} of {int(bounce_tot[5])} boxes"
         f" = {bounce_tot[6] / max(1, bounce_tot[5]):.3f}",
+        f"  row boxes (the same launches): accepted pairs that the refined row or the row's box of where the segment leaves from excludes {int(bounce_tot[7])}",
         f"  launches beyond the table's premise (camera > 64 scene scales out, or no table): {n_guard_off} cases; the table would have excluded {int(beyond_guard[1])} of {int(beyond_guard[0])} accepted pairs there",
         "  by family: " + ", ".join(f"{k} {v[0]} ({v[1]} fail)" for k, v in sorted(by_kind.items())),
     ]

@@ -13,15 +13,11 @@ rank = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 os.environ["RVPT_HIP_TIMELINE"] = str(out / "packets_timeline.bin")
 # the instrumented build (-DRV_PACKETS_TIMELINE=1): made here if tools/packets_timeline.py build was not run before the snapshot
 from rvpt_amd import build as B
-lib = ROOT / "build" / "exp" / "packets_timeline.so"
-if not lib.exists() or lib.stat().st_mtime < max(p.stat().st_mtime for p in B.SOURCES + B.HEADERS):
-    import subprocess
-    lib.parent.mkdir(parents=True, exist_ok=True)
-    subprocess.run([B.hipcc(), *B.FLAGS, "-DRVPT_HIP_LAB=1", "-DRV_PACKETS_TIMELINE=1", "-DRV_PACKETS_MIN_WAVES=5",  # (five waves per SIMD: the clocks and counters need the registers of the sixth)
-                     *map(str, B.LAB_SOURCES), "-o", str(lib)], check=True)  # (RVPT_HIP_TIMELINE is a knob of the laboratory build)
+lib = B.build_native_timeline()  # (RVPT_HIP_TIMELINE is a knob of the laboratory build)
 if len(sys.argv) > 1 and sys.argv[1] == "build":
     sys.exit(0)
-os.environ["RVPT_HIP_LIB"] = str(lib)
+os.environ["RVPT_HIP_LAB_LIB"] = str(lib)
+os.environ["RVPT_HIP_LAB"] = "1"
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 from rvpt_amd import RVPT, native, scene
@@ -52,7 +48,8 @@ print(f"  pool dry (first wave {us(d.min()):.1f}, median {np.median(us(d)):.1f},
 print(f"  wave end: first {us(t1.min()):.1f}, 10% {np.percentile(us(t1), 10):.1f}, median {np.median(us(t1)):.1f}, 90% {np.percentile(us(t1), 90):.1f}, 99% {np.percentile(us(t1), 99):.1f}, last {us(t1.max()):.1f} us")
 cam = (raw[:, 3] & 0xFFFFFFFF).astype(np.int64); bnc = (raw[:, 3] >> 32).astype(np.int64); spl = (raw[:, 4] & 0xFFFFFFFF).astype(np.int64); lr = (raw[:, 4] >> 32).astype(np.int64)
 print(f"  per wave: camera rounds {cam.mean():.1f} (min {cam.min()} max {cam.max()}), bounce rounds {bnc.mean():.1f} (min {bnc.min()} max {bnc.max()}), split rounds {spl.mean():.2f}, lanes per round {lr.sum() / max(1, (cam + bnc).sum()):.1f}")
-print(f"  triangles walked per bounce round (the union of the lanes' rows): {raw[:, 5].sum() / max(1, bnc.sum()):.1f} of {tris.shape[0]}")
+walked, uni = (raw[:, 5] & 0xFFFFFFFF).astype(np.int64), (raw[:, 5] >> 32).astype(np.int64)
+print(f"  triangles walked per bounce round (after the row or the union of rows and the boxes): {walked.sum() / max(1, bnc.sum()):.2f} of {tris.shape[0]}; bounce rounds that took the row boxes (one leaving triangle): {uni.sum()} of {bnc.sum()} = {uni.sum() / max(1, bnc.sum()):.3f}")
 busy = (t1 - t0).astype(np.float64) / 100.0
 print(f"  wave busy time: mean {busy.mean():.1f} us, min {busy.min():.1f}, max {busy.max():.1f}; idle share of the span {1 - busy.mean() / us(t1.max()):.3f}")
 if phases.sum() > 0:

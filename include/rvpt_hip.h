@@ -54,7 +54,10 @@ extern "C" {
                                      `src_rgba32f` of rvpt_hip_write_accum may be DEVICE MEMORY of the context's GPU — until then undefined — and the frame
                                      then never visits the host.  Still 8, no new symbol: no nodes and a count RVPT_HIP_NODES_UPDATE_GUARDED(permille) — until then the
                                      "needs nodes" error — is the GUARDED UPDATE: the update form, the SAH cost of the refitted tree computed on the device and
-                                     reported, and past a limit a rebuild by the builder that made the tree */
+                                     reported, and past a limit a rebuild by the builder that made the tree.  Still 8, no new symbol: the count
+                                     RVPT_HIP_NODES_UPDATE_SPARSE with `nodes` pointing at a list of triangle indices — until then an error on brute-force
+                                     contexts and a read past the list on BVH contexts — is the SPARSE UPDATE: the listed triangles move, only the boxes on
+                                     their paths to the root are recomputed */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -287,11 +290,38 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  * - Brute-force contexts hold no tree: there the guarded count is the plain update form (host arrays only), and rvpt_hip_last_error is empty afterwards.
  * - The plain update form and the three build counts behave and report exactly as before.
  * What the guard costs, and which limit separates a tree worth keeping from one worth rebuilding, is not yet measured on the device (DESIGN.md 5.10 says
- * what is open; the cost ratios of the test scenes in numpy are there). */
+ * what is open; the cost ratios of the test scenes in numpy are there).
+ *
+ * SPARSE UPDATE — move the listed triangles, refit only their paths:
+ *
+ *     rvpt_hip_upload_scene(ctx, (const rvpt_bvh_node *)indices, RVPT_HIP_NODES_UPDATE_SPARSE, tris, k, NULL, 0);      k > 0
+ *
+ * - With this count `nodes` is not a node array: it points at k uint32_t values, 4-byte aligned.  indices[j] is the stored triangle that tris[j] replaces, in
+ *   the order the plain update form takes on this context: the leaf order after an ordinary upload, the caller's own order after a build form (the library
+ *   goes through the inverse of the permutation it kept).  No index twice, none outside the stored scene.
+ * - Only vert0..vert2 of each record are taken.  The stored mat_id rows, the materials, the topology and the guarded update's base cost stay.
+ * - Everything is checked BEFORE anything stored is touched; a failure is RVPT_HIP_ERR_INVALID and leaves the scene as it was: no full upload on this
+ *   context yet; k larger than the stored count; `nodes` NULL; materials passed; an index >= the stored count (the message names the smallest offending
+ *   list position and its value); an index that occurs twice (the message names the smallest such index).  Host and device lists get the same answers.
+ * - BVH contexts.  `indices` and `tris` are both host memory or both device memory of the context's GPU (16-byte aligned triangles); a mixed pair is
+ *   RVPT_HIP_ERR_INVALID, so is device memory of another GPU (the message names both devices).  A device list is checked by two kernels and one read of four
+ *   words.  Every touched triangle's prepared record, material index slot and unit normal are remade.  The box of every leaf that holds a touched triangle
+ *   and of every node between such a leaf and the root is recomputed by the refit's rule, deepest level first, and the copies of those boxes in the
+ *   4-wide form are refreshed.  EVERY OTHER BOX IS LEFT AS IT IS: a caller's loose boxes off those paths stay loose — the plain form tightens everything,
+ *   this one does not.  The context then renders exactly what a full upload of (refit_bvh(nodes, patched, touched), patched, mats) renders
+ *   (rvpt_amd/scene.py: refit_bvh with `touched`): images, statistics, kernel path and LDS bytes.  (The leaves of a caller's tree must not share
+ *   triangles: a triangle belongs to the one leaf whose range holds it.)
+ * - Brute-force contexts derive their scale, table and boxes from the whole vertex set on the host: the library reads its stored records back, patches them
+ *   and runs the plain update form.  Host arrays only; a device pointer gets the plain form's answer.
+ * - Frames in flight finish on the old geometry; `tris` and `indices` may be freed on return; the accumulate / reset rule stays with the caller.
+ * - The plain update, the guarded update and the three build counts behave and report exactly as before.  There is no guarded sparse update.
+ * Cost, 1 % of 1 M triangles on one MI355X (profiles/sparse_update.txt): from host arrays 0.32 ms for a block contiguous in the caller's
+ * order and 0.52 ms scattered, against 3.53 ms for the plain update from a host array in the same run; from device memory 0.15 / 0.18 ms against 0.20 ms. */
 #define RVPT_HIP_NODES_UPDATE_GUARDED(permille) ((size_t)0 - (size_t)(0x10000u + (permille)))
 #define RVPT_HIP_NODES_BUILD ((size_t)-1)
 #define RVPT_HIP_NODES_BUILD_PLOC ((size_t)-2)
 #define RVPT_HIP_NODES_BUILD_SAH ((size_t)-3)
+#define RVPT_HIP_NODES_UPDATE_SPARSE ((size_t)-4)
 int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes,
                           const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats,
                           size_t n_mats);

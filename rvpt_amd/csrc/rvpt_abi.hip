@@ -136,6 +136,16 @@ struct rvpt_hip_ctx {
     std::vector<rvpt_material> host_mats;
     float4 *d_carry = nullptr;
     size_t cap_carry = 0;
+    // the SPARSE UPDATE of upload_scene (include/rvpt_hip.h): the maps of the stored topology (parent per node, leaf per triangle position; have_sparse_maps:
+    // made for the tree in d_nodes, dropped by every full upload, build and rebuild), the inverse of d_perm (have_inv_perm: made for the d_perm of now, dropped
+    // whenever that changes), a flag per node (all zero between updates), a claim word per triangle, the words of the validation with their pinned host copy,
+    // and the staging buffer of a host source — d_prep holds the live records of the triangles that stay
+    uint32_t *d_sparse_parent = nullptr, *d_sparse_leaf_of = nullptr, *d_sparse_dirty = nullptr, *d_sparse_claim = nullptr, *d_inv_perm = nullptr;
+    size_t cap_sparse_parent = 0, cap_sparse_leaf_of = 0, cap_sparse_dirty = 0, cap_sparse_claim = 0, cap_inv_perm = 0;
+    bool have_sparse_maps = false, have_inv_perm = false;
+    uint32_t *d_sparse_words = nullptr, *h_sparse_words = nullptr;
+    unsigned char *d_sparse_stage = nullptr;
+    size_t cap_sparse_stage = 0;
     bool have_scene = false;
 
     rvpt_render_settings settings{};
@@ -958,6 +968,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     if (ctx->h_sky_count) (void)hipHostFree(ctx->h_sky_count);
     if (ctx->h_build_words) (void)hipHostFree(ctx->h_build_words);
     if (ctx->h_cost) (void)hipHostFree(ctx->h_cost);
+    if (ctx->h_sparse_words) (void)hipHostFree(ctx->h_sparse_words);
     if (ctx->d_timeline && !ctx->knobs.timeline_path.empty()) {  // debugging aid: dump the last frame's wave timeline
         std::vector<unsigned long long> h(ctx->timeline_words);
         if (hipMemcpy(h.data(), ctx->d_timeline, ctx->timeline_words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -986,7 +997,8 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
         if (ctx->trace_stream[i]) (void)hipStreamDestroy(ctx->trace_stream[i]);
     }
     void *bufs[] = {ctx->d_tris, ctx->d_prep, ctx->d_mats, ctx->d_nodes, ctx->d_wide, ctx->d_wide_map, ctx->d_mat_index, ctx->d_unit_n, ctx->d_accum,
-                    ctx->d_rowmajor, ctx->d_counter, ctx->d_stats, ctx->d_perm, ctx->d_build, ctx->d_build_temp, ctx->d_build_counters, ctx->d_cost, ctx->d_carry};
+                    ctx->d_rowmajor, ctx->d_counter, ctx->d_stats, ctx->d_perm, ctx->d_build, ctx->d_build_temp, ctx->d_build_counters, ctx->d_cost, ctx->d_carry,
+                    ctx->d_sparse_parent, ctx->d_sparse_leaf_of, ctx->d_sparse_dirty, ctx->d_sparse_claim, ctx->d_inv_perm, ctx->d_sparse_words, ctx->d_sparse_stage};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1215,6 +1227,7 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     uint32_t *flags = reinterpret_cast<uint32_t *>(base + 24u * static_cast<size_t>(n)), *flags_next = reinterpret_cast<uint32_t *>(base + 24u * static_cast<size_t>(n) + words);
     uint32_t *const offs = reinterpret_cast<uint32_t *>(base + 24u * static_cast<size_t>(n) + 2u * words);
     ctx->have_scene = false;  // from here on the stored scene is being replaced: an error below leaves none
+    ctx->have_sparse_maps = ctx->have_inv_perm = false;  // ... and with it the topology and the permutation the sparse update's maps were made for
     if (n_mats) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mats, mats, n_mats * sizeof(rvpt_material), hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(rv::prepare_materials, dim3((static_cast<uint32_t>(n_mats) + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_mats, static_cast<uint32_t>(n_mats));
@@ -1409,6 +1422,160 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     return RVPT_HIP_OK;
 }
 
+// the sparse update's list, checked on the host: the smallest position whose index is out of range, else the smallest index that occurs twice; the span of the indices
+static int sparse_validate_host(rvpt_hip_ctx *ctx, const uint32_t *indices, size_t k, size_t n_tris, uint32_t *lo_out, uint32_t *hi_out)
+{
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (size_t j = 0; j < k; ++j) {
+        if (indices[j] >= n_tris) return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: indices[%zu] = %u is outside the %zu stored triangles", j, indices[j], n_tris);
+        lo = std::min(lo, indices[j]), hi = std::max(hi, indices[j]);
+    }
+    std::vector<uint32_t> sorted(indices, indices + k);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t j = 1; j < k; ++j)
+        if (sorted[j] == sorted[j - 1]) return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: index %u occurs more than once in the list", sorted[j]);
+    *lo_out = lo, *hi_out = hi;
+    return RVPT_HIP_OK;
+}
+
+// The SPARSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): `indices` names k stored triangles, tris[j] replaces the vertices of triangle indices[j].
+// Everything is validated before anything stored is touched — a host list on the host, a device list by two kernels and one read of four words, with the same
+// answers.  BVH contexts: the rows are scattered into d_tris, the paths from their leaves to the root are flagged, prepare_triangles runs over the span of rows
+// the list touches, the flagged nodes are refitted level by level (deepest first) and the wide form's copies of the boxes are gathered again; every other box
+// stays as it is.  Brute-force contexts derive their scale, table and boxes from the whole vertex set on the host: the stored records are read back, patched,
+// and go through the plain update form.
+static int update_geometry_sparse(rvpt_hip_ctx *ctx, const uint32_t *indices, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats)
+{
+    if (!ctx->have_scene)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update before any full upload_scene on this context: there is no scene to update");
+    if (k == 0) return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update without triangles");
+    const size_t n_tris = ctx->n_tris;
+    if (k > n_tris) return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update with %zu triangles, the uploaded scene has %zu", k, n_tris);
+    if (!indices) return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update without indices: `nodes` points at one uint32_t per triangle passed");
+    if (mats || n_mats) return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update takes no materials: it keeps the stored ones");
+    if (reinterpret_cast<uintptr_t>(indices) % 4u) return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: the indices at %p are not 4-byte aligned", static_cast<const void *>(indices));
+    const bool bvh = is_bvh(ctx, n_tris);
+    if (bvh && ctx->refit_levels.empty())  // (the laboratory's knob only, as in the plain form)
+#if RVPT_HIP_LAB
+        return fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "geometry update needs the breadth-first device layout of the tree: RVPT_HIP_BVH_CALLER_LAYOUT keeps the caller's, which has no level ranges");
+#else
+        return fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "geometry update needs the level ranges of the tree's device layout, which this context does not hold");
+#endif
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool device_tris = is_device_pointer(tris), device_indices = is_device_pointer(indices);
+    if (!bvh && (device_tris || device_indices))
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "geometry update of a brute-force context from a device pointer: its scene scale and leaf boxes are computed on the host, pass a host array");
+    if (device_tris != device_indices)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: the indices are %s memory and the triangles %s memory: both on the host or both on the context's GPU",
+                    device_indices ? "device" : "host", device_tris ? "device" : "host");
+    if (device_tris) {
+        const void *const both[2] = {indices, tris};
+        for (int i = 0; i < 2; ++i) {
+            hipPointerAttribute_t attr{};
+            HIP_TRY(ctx, hipPointerGetAttributes(&attr, both[i]));
+            if (attr.device != ctx->device)
+                return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: the %s are device memory of GPU %d, the context lives on GPU %d", i ? "triangles" : "indices", attr.device, ctx->device);
+        }
+        if (reinterpret_cast<uintptr_t>(tris) % 16u)
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: triangles in device memory at %p need 16-byte alignment", static_cast<const void *>(tris));
+    }
+    const uint32_t n = static_cast<uint32_t>(n_tris), kk = static_cast<uint32_t>(k);
+    uint32_t span_lo = 0, span_hi = 0;
+
+    if (!bvh) {  // host arrays: validate, read the stored records back, patch, the plain form
+        if (int rc0 = sparse_validate_host(ctx, indices, k, n_tris, &span_lo, &span_hi)) return rc0;
+        if (int rc0 = sync_all(ctx)) return rc0;
+        std::vector<rvpt_triangle> patched(n_tris);
+        HIP_TRY(ctx, hipMemcpy(patched.data(), ctx->d_tris, n_tris * sizeof(rvpt_triangle), hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < k; ++j) std::memcpy(&patched[indices[j]], &tris[j], offsetof(rvpt_triangle, mat_id));
+        return update_geometry(ctx, patched.data(), n_tris);
+    }
+
+    int rc;
+    const uint32_t n_nodes = static_cast<uint32_t>(std::min<size_t>(ctx->n_nodes, ctx->refit_levels.back().second));
+    const uint32_t *d_indices = indices;
+    const float4 *d_src = reinterpret_cast<const float4 *>(tris);
+    if (!device_tris && (rc = sparse_validate_host(ctx, indices, k, n_tris, &span_lo, &span_hi))) return rc;
+    // the permutation's inverse: after a build form the caller's indices are not positions.  Needed by the device validation's span, so made in front of
+    // it; it reads and writes nothing a frame in flight uses
+    if (ctx->have_perm && !ctx->have_inv_perm) {
+        if ((rc = grow(ctx, ctx->d_inv_perm, ctx->cap_inv_perm, n_tris, sizeof(uint32_t)))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_inv_perm, 0xFF, n_tris * sizeof(uint32_t), ctx->stream));
+        hipLaunchKernelGGL(rv::sparse_invert_permutation, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_perm, n, ctx->d_inv_perm);
+        HIP_TRY(ctx, hipGetLastError());
+        ctx->have_inv_perm = true;
+    }
+    const uint32_t *const inv_perm = ctx->have_perm ? ctx->d_inv_perm : nullptr;
+    if (!device_tris) {  // a validated host list is staged: the indices behind the records
+        if (inv_perm) span_lo = 0, span_hi = n - 1u;  // (the positions are known on the device alone: the whole buffer)
+        if ((rc = grow(ctx, ctx->d_sparse_stage, ctx->cap_sparse_stage, k * (sizeof(rvpt_triangle) + sizeof(uint32_t)), 1))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sparse_stage, tris, k * sizeof(rvpt_triangle), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sparse_stage + k * sizeof(rvpt_triangle), indices, k * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        d_src = reinterpret_cast<const float4 *>(ctx->d_sparse_stage);
+        d_indices = reinterpret_cast<const uint32_t *>(ctx->d_sparse_stage + k * sizeof(rvpt_triangle));
+    } else {  // a device list: two kernels and one read of four words
+        size_t cap_words = ctx->d_sparse_words ? rv::kSparseWords : 0;
+        if ((rc = grow(ctx, ctx->d_sparse_words, cap_words, rv::kSparseWords, sizeof(uint32_t)))) return rc;
+        if (!ctx->h_sparse_words) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_sparse_words), rv::kSparseWords * sizeof(uint32_t)));
+        if ((rc = grow(ctx, ctx->d_sparse_claim, ctx->cap_sparse_claim, n_tris, sizeof(uint32_t)))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_claim, 0xFF, n_tris * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_words, 0xFF, 3u * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_words + rv::kSparseSpanHi, 0, sizeof(uint32_t), ctx->stream));
+        hipLaunchKernelGGL(rv::sparse_claim, dim3((kk + 255u) / 256u), dim3(256), 0, ctx->stream, d_indices, kk, n, inv_perm, ctx->d_sparse_claim, ctx->d_sparse_words);
+        hipLaunchKernelGGL(rv::sparse_duplicates, dim3((kk + 255u) / 256u), dim3(256), 0, ctx->stream, d_indices, kk, n, ctx->d_sparse_claim, ctx->d_sparse_words);
+        HIP_TRY(ctx, hipGetLastError());
+        uint32_t *const h = ctx->h_sparse_words;
+        HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_sparse_words, rv::kSparseWords * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (h[rv::kSparseBadPosition] != 0xFFFFFFFFu) {
+            const size_t j = h[rv::kSparseBadPosition];
+            uint32_t value = 0;
+            if (j < k) HIP_TRY(ctx, hipMemcpy(&value, indices + j, sizeof value, hipMemcpyDeviceToHost));
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: indices[%zu] = %u is outside the %zu stored triangles", j, value, n_tris);
+        }
+        if (h[rv::kSparseDuplicate] != 0xFFFFFFFFu)
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: index %u occurs more than once in the list", h[rv::kSparseDuplicate]);
+        span_lo = h[rv::kSparseSpanLo], span_hi = h[rv::kSparseSpanHi];
+        if (span_lo > span_hi || span_hi >= n) span_lo = 0, span_hi = n - 1u;
+    }
+    // the maps of the stored topology, made on the first sparse update after any full upload, build or rebuild
+    if (!ctx->have_sparse_maps) {
+        if ((rc = grow(ctx, ctx->d_sparse_parent, ctx->cap_sparse_parent, n_nodes, sizeof(uint32_t)))) return rc;
+        if ((rc = grow(ctx, ctx->d_sparse_dirty, ctx->cap_sparse_dirty, n_nodes, sizeof(uint32_t)))) return rc;
+        if ((rc = grow(ctx, ctx->d_sparse_leaf_of, ctx->cap_sparse_leaf_of, n_tris, sizeof(uint32_t)))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_parent, 0xFF, n_nodes * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_dirty, 0, n_nodes * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_leaf_of, 0xFF, n_tris * sizeof(uint32_t), ctx->stream));
+        hipLaunchKernelGGL(rv::sparse_topology, dim3((n_nodes + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_nodes, n_nodes, n, ctx->d_sparse_parent, ctx->d_sparse_leaf_of);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (int rc0 = sync_all(ctx)) return rc0;  // frames in flight finish on the old geometry
+    ctx->have_sparse_maps = false;  // (until the flags are known to be all zero again: after an error below the next update starts from fresh maps)
+    hipLaunchKernelGGL(rv::sparse_scatter, dim3((kk + 255u) / 256u), dim3(256), 0, ctx->stream, d_src, d_indices, kk, n, inv_perm, ctx->d_tris, ctx->d_sparse_leaf_of, ctx->d_sparse_parent,
+                       n_nodes, ctx->d_sparse_dirty);
+    HIP_TRY(ctx, hipGetLastError());
+    {  // prepare_triangles as it is, over the rows [span_lo, span_hi]: records, material index slots and unit normals
+        const uint32_t rows = span_hi - span_lo + 1u;
+        hipLaunchKernelGGL(rv::prepare_triangles, dim3((rows + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_tris + 4u * static_cast<size_t>(span_lo), rows,
+                           ctx->d_prep + 4u * static_cast<size_t>(span_lo), ctx->d_mat_index + span_lo, ctx->d_unit_n + span_lo);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    for (size_t l = ctx->refit_levels.size(); l-- > 0;) {
+        const auto [begin, end] = ctx->refit_levels[l];
+        hipLaunchKernelGGL(rv::refit_level_dirty, dim3((end - begin + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_nodes, begin, end, n_nodes, ctx->d_tris, n, ctx->d_sparse_dirty);
+    }
+    if (ctx->n_wide) {
+        const uint32_t n_slots = static_cast<uint32_t>(ctx->n_wide * 4);
+        hipLaunchKernelGGL(rv::refit_wide_gather, dim3((n_slots + 255u) / 256u), dim3(256), 0, ctx->stream, reinterpret_cast<float *>(ctx->d_wide), ctx->d_wide_map, n_slots, ctx->d_nodes,
+                           static_cast<uint32_t>(ctx->n_nodes));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // caller may free its arrays on return
+    ctx->have_sparse_maps = true;
+    ctx->scene_gen += 1;  // the slots' screen rectangles and sky lists belong to the old geometry
+    return RVPT_HIP_OK;
+}
+
 // The GUARDED UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; BVH contexts): the update form, then the cost of the refitted tree, then — with a limit,
 // once the cost has grown past limit x base cost — a rebuild by the builder that made the stored tree, from the moved triangles carried back into the
 // caller's order.  permille: 0 (report only) or 1000 .. 65535, checked by the caller.
@@ -1450,6 +1617,8 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
     if ((n_tris && !tris) || (n_mats && !mats)) return fail(ctx, RVPT_HIP_ERR_INVALID, "NULL scene array");
     if (n_tris > 0x3FFFFFFFull) return fail(ctx, RVPT_HIP_ERR_INVALID, "too many triangles");
+    // the SPARSE UPDATE: the count RVPT_HIP_NODES_UPDATE_SPARSE, `nodes` then points at n_tris indices (n_tris == 0 arrives here too: the form says so itself)
+    if (n_nodes == RVPT_HIP_NODES_UPDATE_SPARSE) return update_geometry_sparse(ctx, reinterpret_cast<const uint32_t *>(nodes), tris, n_tris, mats, n_mats);
     // the UPDATE FORM: triangles without nodes and without materials (as a full upload it could never succeed: no material index fits n_mats == 0)
     if (n_tris > 0 && !nodes && n_nodes == 0 && !mats && n_mats == 0) return update_geometry(ctx, tris, n_tris);
     // the GUARDED UPDATE: no nodes and a count of the band RVPT_HIP_NODES_UPDATE_GUARDED(permille) lies in.  Brute-force contexts hold no tree: the plain update form
@@ -1513,6 +1682,7 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc0 = sync_all(ctx)) return rc0;  // frames in flight still read the old scene
     int rc;
+    ctx->have_sparse_maps = ctx->have_inv_perm = false;  // the topology the sparse update's maps were made for is being replaced
     if ((rc = grow(ctx, ctx->d_tris, ctx->cap_tris, n_tris, sizeof(rvpt_triangle)))) return rc;
     if ((rc = grow(ctx, ctx->d_prep, ctx->cap_prep, n_tris, sizeof(rvpt_triangle)))) return rc;
     if ((rc = grow(ctx, ctx->d_mat_index, ctx->cap_mat_index, n_tris, sizeof(uint32_t)))) return rc;

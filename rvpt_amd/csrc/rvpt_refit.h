@@ -21,4 +21,20 @@ __global__ void tree_cost_finish(const double *__restrict__ partials, uint32_t n
 // the triangles of d_tris carried back into the caller's order for a guarded rebuild: out[perm[pos]] = tris[pos], grid = ceil(4 n / block) (one thread per quad)
 __global__ void carry_back_triangles(const float4 *__restrict__ tris, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ out);
 
+// The SPARSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; rvpt_abi.hip: update_geometry_sparse).  refit_level for the flagged nodes of a level alone ...
+__global__ void refit_level_dirty(float4 *__restrict__ nodes, uint32_t begin, uint32_t end, uint32_t n_nodes, const float4 *__restrict__ tris, uint32_t n_tris,
+                                  uint32_t *__restrict__ dirty);
+// ... the maps of a topology (both pre-filled with 0xFFFFFFFF; one thread per node) and the inverse of a build form's permutation (one thread per triangle) ...
+__global__ void sparse_topology(const float4 *__restrict__ nodes, uint32_t n_nodes, uint32_t n_tris, uint32_t *__restrict__ parent, uint32_t *__restrict__ leaf_of);
+__global__ void sparse_invert_permutation(const uint32_t *__restrict__ perm, uint32_t n, uint32_t *__restrict__ inv);
+// ... the list's validation in two launches (one thread per entry; inv_perm may be null): the words it leaves, read back in one copy ...
+enum : uint32_t { kSparseBadPosition = 0, kSparseDuplicate = 1, kSparseSpanLo = 2, kSparseSpanHi = 3, kSparseWords = 4 };
+__global__ void sparse_claim(const uint32_t *__restrict__ indices, uint32_t k, uint32_t n_tris, const uint32_t *__restrict__ inv_perm, uint32_t *__restrict__ claim,
+                             uint32_t *__restrict__ words);
+__global__ void sparse_duplicates(const uint32_t *__restrict__ indices, uint32_t k, uint32_t n_tris, const uint32_t *__restrict__ claim, uint32_t *__restrict__ words);
+// ... and the scatter of the vertex rows with the marking of their paths (one thread per entry of a validated list; src: four quads per entry, the fourth unread)
+__global__ void sparse_scatter(const float4 *__restrict__ src, const uint32_t *__restrict__ indices, uint32_t k, uint32_t n_tris, const uint32_t *__restrict__ inv_perm,
+                               float4 *__restrict__ tris, const uint32_t *__restrict__ leaf_of, const uint32_t *__restrict__ parent, uint32_t n_nodes,
+                               uint32_t *__restrict__ dirty);
+
 }  // namespace rv

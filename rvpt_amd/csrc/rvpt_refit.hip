@@ -13,10 +13,9 @@ namespace rv {
 // One launch per level of the breadth-first device layout, deepest first, in stream order: a level is the index range [begin, end), children have higher
 // indices than their parent and lie on deeper levels, so every box a thread reads was written by an earlier launch.  No atomics, no waiting on another
 // work-group.  A node = two quads: (first, count, minx, maxx), (miny, maxy, minz, maxz); only the six bounds are written.
-__global__ void refit_level(float4 *__restrict__ nodes, uint32_t begin, uint32_t end, uint32_t n_nodes, const float4 *__restrict__ tris, uint32_t n_tris)
+// (refit_node: the box of one node, shared by refit_level and the sparse update's refit_level_dirty.)
+__device__ inline void refit_node(float4 *__restrict__ nodes, uint32_t i, uint32_t n_nodes, const float4 *__restrict__ tris, uint32_t n_tris)
 {
-    const uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= end || i >= n_nodes) return;
     const float4 head = nodes[2 * i];
     const uint32_t first = __float_as_uint(head.x), count = __float_as_uint(head.y);
     float lo[3], hi[3];
@@ -40,6 +39,25 @@ __global__ void refit_level(float4 *__restrict__ nodes, uint32_t begin, uint32_t
     }
     nodes[2 * i] = make_float4(head.x, head.y, lo[0], hi[0]);
     nodes[2 * i + 1] = make_float4(lo[1], hi[1], lo[2], hi[2]);
+}
+
+__global__ void refit_level(float4 *__restrict__ nodes, uint32_t begin, uint32_t end, uint32_t n_nodes, const float4 *__restrict__ tris, uint32_t n_tris)
+{
+    const uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= end || i >= n_nodes) return;
+    refit_node(nodes, i, n_nodes, tris, n_tris);
+}
+
+// The SPARSE UPDATE's form of the same launch (include/rvpt_hip.h): the same arithmetic for the nodes of the level that sparse_scatter flagged, and only for
+// them; the flag is cleared for the next update.  Every other box of the level is left as it is.  The flags were written by an earlier launch on the stream.
+__global__ void refit_level_dirty(float4 *__restrict__ nodes, uint32_t begin, uint32_t end, uint32_t n_nodes, const float4 *__restrict__ tris, uint32_t n_tris,
+                                  uint32_t *__restrict__ dirty)
+{
+    const uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= end || i >= n_nodes) return;
+    if (dirty[i] == 0u) return;
+    dirty[i] = 0u;
+    refit_node(nodes, i, n_nodes, tris, n_tris);
 }
 
 // ... then the 4-wide form: slot s of wide node w holds a copy of the box of binary node map[4 w + s] (build_wide_nodes' grouping, kept from the full upload;
@@ -130,6 +148,97 @@ __global__ void carry_back_triangles(const float4 *__restrict__ tris, const uint
     const uint32_t dst = perm[pos];
     if (dst >= n) return;
     out[4 * static_cast<size_t>(dst) + q] = tris[4 * static_cast<size_t>(pos) + q];
+}
+
+// ---- the sparse update (include/rvpt_hip.h: SPARSE UPDATE) -----------------------------------------------------------------------------------------------------
+// The maps a sparse update walks, made from the breadth-first node array once per topology: parent[node] (0xFFFFFFFF for the root and for slots no node
+// owns) and leaf_of[triangle position] (0xFFFFFFFF where no leaf holds it; both arrays are filled with that word before the launch).  One thread per node;
+// the same guards as refit_node: a stray word never becomes an address.
+__global__ void sparse_topology(const float4 *__restrict__ nodes, uint32_t n_nodes, uint32_t n_tris, uint32_t *__restrict__ parent, uint32_t *__restrict__ leaf_of)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes || i == 1u) return;
+    const float4 head = nodes[2 * i];
+    const uint32_t first = __float_as_uint(head.x), count = __float_as_uint(head.y);
+    if (count > 0) {
+        if (first >= n_tris || count > n_tris - first) return;
+        for (uint32_t t = first; t < first + count; ++t) leaf_of[t] = i;
+    } else {
+        if (first <= i || first >= n_nodes - 1u) return;
+        parent[first] = i, parent[first + 1u] = i;
+    }
+}
+
+// inv[perm[pos]] = pos: the caller's index of a build form -> the position in leaf order.  perm is a bijection of [0, n); a word that is not an index is dropped.
+__global__ void sparse_invert_permutation(const uint32_t *__restrict__ perm, uint32_t n, uint32_t *__restrict__ inv)
+{
+    const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= n) return;
+    const uint32_t j = perm[pos];
+    if (j < n) inv[j] = pos;
+}
+
+// Validation, pass one (one thread per list entry; claim[] = n_tris words of 0xFFFFFFFF, words = kSparseWords words: 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF, 0):
+// an index outside [0, n_tris) lowers words[kSparseBadPosition] to its list position; every other entry claims its triangle with its list position (the
+// smallest position wins) and widens the span [words[kSparseSpanLo], words[kSparseSpanHi]] of the positions in leaf order the list touches.
+__global__ void sparse_claim(const uint32_t *__restrict__ indices, uint32_t k, uint32_t n_tris, const uint32_t *__restrict__ inv_perm, uint32_t *__restrict__ claim,
+                             uint32_t *__restrict__ words)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bad = 0xFFFFFFFFu, lo = 0xFFFFFFFFu, hi = 0u;  // (no early return: every lane of the wave takes part in the fold below)
+    if (j < k) {
+        const uint32_t idx = indices[j];
+        if (idx >= n_tris) {
+            bad = j;
+        } else {
+            atomicMin(&claim[idx], j);
+            const uint32_t pos = inv_perm ? inv_perm[idx] : idx;
+            if (pos < n_tris) lo = hi = pos;
+        }
+    }
+    // one atomic per wave and word instead of one per entry: thousands of entries would otherwise queue on three addresses
+    for (int off = 32; off > 0; off >>= 1) {
+        bad = min(bad, static_cast<uint32_t>(__shfl_down(bad, off, 64)));
+        lo = min(lo, static_cast<uint32_t>(__shfl_down(lo, off, 64)));
+        hi = max(hi, static_cast<uint32_t>(__shfl_down(hi, off, 64)));
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (bad != 0xFFFFFFFFu) atomicMin(&words[kSparseBadPosition], bad);
+        if (lo <= hi) {
+            atomicMin(&words[kSparseSpanLo], lo);
+            atomicMax(&words[kSparseSpanHi], hi);
+        }
+    }
+}
+
+// ... pass two, a launch of its own behind the first: an entry that lost its claim names an index that occurs twice; the smallest such index value.
+__global__ void sparse_duplicates(const uint32_t *__restrict__ indices, uint32_t k, uint32_t n_tris, const uint32_t *__restrict__ claim, uint32_t *__restrict__ words)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const uint32_t idx = indices[j];
+    if (idx < n_tris && claim[idx] != j) atomicMin(&words[kSparseDuplicate], idx);
+}
+
+// The scatter (one thread per entry of a VALIDATED list: in range, no index twice, so no two threads write one row): the 48 vertex bytes of src[j] into row
+// pos of tris — the mat_id quad of the row stays — and the path from the leaf that holds pos to the root flagged.  atomicExch hands the old flag back: a
+// thread that finds a node flagged stops, the thread that flagged it goes on to the root.  The flags are only read by later launches on the stream.
+__global__ void sparse_scatter(const float4 *__restrict__ src, const uint32_t *__restrict__ indices, uint32_t k, uint32_t n_tris, const uint32_t *__restrict__ inv_perm,
+                               float4 *__restrict__ tris, const uint32_t *__restrict__ leaf_of, const uint32_t *__restrict__ parent, uint32_t n_nodes,
+                               uint32_t *__restrict__ dirty)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    const uint32_t idx = indices[j];
+    if (idx >= n_tris) return;
+    const uint32_t pos = inv_perm ? inv_perm[idx] : idx;
+    if (pos >= n_tris) return;
+    const float4 a = src[4 * static_cast<size_t>(j)], b = src[4 * static_cast<size_t>(j) + 1], c = src[4 * static_cast<size_t>(j) + 2];
+    float4 *row = tris + 4 * static_cast<size_t>(pos);
+    row[0] = a, row[1] = b, row[2] = c;
+    // (a path holds at most one node per level; the bound keeps a malformed map from looping)
+    for (uint32_t node = leaf_of[pos], hops = 0; node < n_nodes && hops < 128u; node = parent[node], ++hops)
+        if (atomicExch(&dirty[node], 1u) != 0u) break;
 }
 
 }  // namespace rv

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -162,6 +163,7 @@ bool RVPT::initialize()
     nodes_.clear();
     nodes_stale_ = false;
     order_.clear();
+    inverse_.clear();
     device_built_ = options_.device_build && options_.bvh_traversal && !triangles_.empty();
     if (!triangles_.empty() && !device_built_) {
         nodes_.resize(2 * triangles_.size() - 1);
@@ -220,6 +222,46 @@ bool RVPT::update_triangles_with(const std::vector<Triangle> &triangles, size_t 
     triangles_ = triangles;
     sorted_.swap(moved);
     nodes_stale_ = true;
+    previous_.valid = false;  // a new scene: nothing accumulated so far belongs to it
+    return true;
+}
+
+// The sparse form: `nodes` carries the uint32 positions, the count is RVPT_HIP_NODES_UPDATE_SPARSE.
+bool RVPT::update_triangles(const std::vector<uint32_t> &indices, const std::vector<Triangle> &triangles)
+{
+    if (!ctx_) {
+        error_ = "update_triangles before initialize()";
+        return false;
+    }
+    if (indices.size() != triangles.size()) {
+        error_ = "update_triangles: " + std::to_string(indices.size()) + " indices for " + std::to_string(triangles.size()) + " triangles";
+        return false;
+    }
+    if (indices.empty()) return true;
+    for (size_t j = 0; j < indices.size(); ++j)
+        if (indices[j] >= triangles_.size()) {
+            error_ = "update_triangles: indices[" + std::to_string(j) + "] = " + std::to_string(indices[j]) + " is outside the " + std::to_string(triangles_.size()) + " triangles of the scene";
+            return false;
+        }
+    std::vector<uint32_t> positions;  // where the device holds them: leaf order after a host build
+    if (!device_built_) {
+        if (inverse_.size() != order_.size()) {
+            inverse_.resize(order_.size());
+            for (size_t i = 0; i < order_.size(); ++i) inverse_[order_[i]] = static_cast<uint32_t>(i);
+        }
+        positions.reserve(indices.size());
+        for (uint32_t j : indices) positions.push_back(inverse_[j]);
+    }
+    const std::vector<uint32_t> &sent = device_built_ ? indices : positions;
+    if (!check(backend_.upload_scene(ctx_, reinterpret_cast<const rvpt_bvh_node *>(sent.data()), RVPT_HIP_NODES_UPDATE_SPARSE, reinterpret_cast<const rvpt_triangle *>(triangles.data()),
+                                     triangles.size(), nullptr, 0),
+               "rvpt_hip_upload_scene (sparse update)"))
+        return false;
+    for (size_t j = 0; j < indices.size(); ++j) {  // the vertex rows move, the material rows are the stored ones
+        std::memcpy(triangles_[indices[j]].vertex0, triangles[j].vertex0, offsetof(Triangle, material_id));
+        if (!device_built_) std::memcpy(sorted_[positions[j]].vertex0, triangles[j].vertex0, offsetof(Triangle, material_id));
+    }
+    if (!device_built_) nodes_stale_ = true;  // (the host tree is tight: the full refit of bvh_nodes() is the sparse one)
     previous_.valid = false;  // a new scene: nothing accumulated so far belongs to it
     return true;
 }

@@ -151,6 +151,12 @@ public:
     // longer holds; after a host build only a refit can have happened.  Brute-force traversal: the plain update, `report` comes back empty.
     bool update_triangles(const std::vector<Triangle> &triangles, double rebuild_above, UpdateReport *report = nullptr);
 
+    // The sparse form (RVPT_HIP_NODES_UPDATE_SPARSE): triangles[j] replaces the vertices of triangle indices[j], numbered in the order the triangles were ADDED;
+    // everything else of the scene stays, and on the device only the boxes above the moved triangles are recomputed.  After a host build the indices go down
+    // as leaf-order positions (the inverse of the build's primitive indices), after a device build as they are.  An index outside the scene or a size
+    // mismatch never reaches the ABI; an index twice is the library's to refuse.  The host copies are patched, bvh_nodes() is refitted when next asked for.
+    bool update_triangles(const std::vector<uint32_t> &indices, const std::vector<Triangle> &triangles);
+
     // RGBA32F (width*height*4 floats) or RGBA8 (width*height*4 bytes), row-major, top row first
     std::vector<float> read_frame();
     std::vector<uint8_t> read_frame_rgba8();
@@ -183,6 +189,7 @@ private:
     mutable std::vector<rvpt_bvh_node> nodes_;
     mutable bool nodes_stale_ = false;  // update_triangles moved the geometry under nodes_' boxes
     std::vector<uint32_t> order_;       // primitive indices of the build: sorted_[i] = triangles_[order_[i]]
+    std::vector<uint32_t> inverse_;     // ... and their inverse, made by the first sparse update: triangles_[j] lives at sorted_[inverse_[j]]
     bool device_built_ = false;         // the scene went up by the build form: no nodes_, sorted_, order_ on the host
     // PreviousFrameState (rvpt.h:211-219, rvpt.cpp:21-29); empty camera data never compares equal
     struct Previous {

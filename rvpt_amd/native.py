@@ -31,6 +31,7 @@ TILE = 16
 TILE_SHIFT = 3  # RVPT_HIP_TILE_SHIFT: every row of the tile grid is rotated by this many more tiles than the one above (tile ownership)
 NODES_BUILD = C.c_size_t(-1).value  # RVPT_HIP_NODES_BUILD: upload_scene's node count for the build form (Context.build_scene)
 NODES_BUILD_SAH = C.c_size_t(-3).value  # RVPT_HIP_NODES_BUILD_SAH: the build form with rvpt_bvh_build's binned-SAH tree (Context.build_scene(method="sah"))
+NODES_UPDATE_SPARSE = C.c_size_t(-4).value  # RVPT_HIP_NODES_UPDATE_SPARSE: the sparse update (Context.update_triangles(indices=)): `nodes` then carries the indices
 NODES_UPDATE_GUARDED_BASE = 0x10000  # RVPT_HIP_NODES_UPDATE_GUARDED(permille) = (size_t)0 - (0x10000 + permille): the guarded update (Context.update_triangles(rebuild_above=))
 NODES_BUILD_PLOC = C.c_size_t(-2).value  # RVPT_HIP_NODES_BUILD_PLOC: the build form with a PLOC tree (Context.build_scene(method="ploc"))
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_SIZE, ERR_COMM = -1, -2, -3, -4, -5, -6
@@ -402,7 +403,7 @@ class Context:
             return "lbvh" if b"LBVH tree" in (self._L.rvpt_hip_last_error(self._h) or b"") else "ploc"
         return "sah" if method == "sah" else "lbvh"
 
-    def update_triangles(self, tris, rebuild_above=None):
+    def update_triangles(self, tris, rebuild_above=None, indices=None):
         """The update form of rvpt_hip_upload_scene (include/rvpt_hip.h): the scene's triangles have moved — same count, same tree topology as the last full
         upload, in the order that upload took them: the leaf order after upload_scene, the caller's own order after build_scene.
         Only vert0..vert2 are taken; material rows, materials and the tree's structure stay, every box of the tree is refitted on the
@@ -412,7 +413,14 @@ class Context:
         rebuild_above: None is the plain form and returns None.  A number is the GUARDED form (RVPT_HIP_NODES_UPDATE_GUARDED): after the refit the library
         computes the tree's SAH cost on the device (scene.tree_cost is the same in numpy) and, when it exceeds rebuild_above x the cost of the tree as it was built,
         rebuilds with the method of the build_scene that made it.  A float >= 1 is rounded to thousandths (at most 65.535); math.inf only reports.  Returns an
-        UpdateReport (cost, base_cost, ratio, rebuilt, tree); on a brute-force context, which holds no tree, the plain update happens and None is returned."""
+        UpdateReport (cost, base_cost, ratio, rebuilt, tree); on a brute-force context, which holds no tree, the plain update happens and None is returned.
+
+        indices: None, or the SPARSE form (RVPT_HIP_NODES_UPDATE_SPARSE): tris[j] replaces the vertices of stored triangle indices[j] (the same order rule), and on a
+        BVH context only the boxes on the paths from the touched leaves to the root are recomputed (scene.refit_bvh(..., touched=) is the same on the host); every
+        other box stays as it is.  A numpy integer array of k entries beside a host `tris` of k rows, or a contiguous 1-D torch.int32 tensor on this context's device
+        beside a device `tris`.  No index twice, none outside the scene.  Not together with rebuild_above.  An empty list changes nothing.  Returns None."""
+        if indices is not None:
+            return self._update_sparse(tris, rebuild_above, indices)
         ptr, n, keep = self._triangle_source(tris, "update_triangles")
         count = 0
         if rebuild_above is not None:
@@ -430,6 +438,42 @@ class Context:
         if count == 0 or (self.flags & (TRAVERSAL_BVH | TRAVERSAL_BVH_ORDERED)) == 0:
             return None
         return parse_update_report((self._L.rvpt_hip_last_error(self._h) or b"").decode())
+
+    def _update_sparse(self, tris, rebuild_above, indices) -> None:
+        if rebuild_above is not None:
+            raise NativeError(ERR_INVALID, "update_triangles: indices (the sparse form) and rebuild_above (the guarded form) do not combine")
+        ptr, n, keep = self._triangle_source(tris, "update_triangles")
+        if not isinstance(indices, np.ndarray) and hasattr(indices, "data_ptr"):  # a torch tensor
+            import torch
+            if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
+                raise NativeError(ERR_INVALID, f"update_triangles: indices as a tensor are contiguous 1-D torch.int32, got {indices.dtype} {tuple(indices.shape)}")
+            if indices.is_cuda != (not isinstance(keep, np.ndarray)):
+                raise NativeError(ERR_INVALID, "update_triangles: indices and triangles are both host arrays or both tensors on the context's device, got a mixed pair")
+            if indices.is_cuda:
+                if indices.device.index != self.device:
+                    raise NativeError(ERR_INVALID, f"update_triangles: the index tensor lives on device {indices.device.index}, the context on {self.device}")
+                torch.cuda.current_stream(indices.device).synchronize()
+                iptr, k, ikeep = C.c_void_p(indices.data_ptr()), int(indices.shape[0]), indices
+            else:
+                indices = indices.numpy()
+        if isinstance(indices, np.ndarray) or not hasattr(indices, "data_ptr"):
+            idx = np.asarray(indices)
+            if idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
+                raise NativeError(ERR_INVALID, f"update_triangles: indices are a 1-D integer array, got {idx.dtype} {idx.shape}")
+            if not isinstance(keep, np.ndarray):
+                raise NativeError(ERR_INVALID, "update_triangles: indices and triangles are both host arrays or both tensors on the context's device, got a mixed pair")
+            if idx.size and (int(idx.min()) < 0 or int(idx.max()) > 0xFFFFFFFF):
+                bad = int(np.flatnonzero((idx < 0) | (idx > 0xFFFFFFFF))[0])
+                raise NativeError(ERR_INVALID, f"update_triangles: indices[{bad}] = {int(idx[bad])} is not a triangle index")
+            ikeep = np.ascontiguousarray(idx, dtype=np.uint32)
+            iptr, k = _ptr(ikeep), int(ikeep.shape[0])
+        if k == 0:
+            return None
+        if k != n:
+            raise NativeError(ERR_INVALID, f"update_triangles: {k} indices for {n} triangles")
+        _check(self._L.rvpt_hip_upload_scene(self._h, iptr, NODES_UPDATE_SPARSE, ptr, n, None, 0), self._h, self._L)
+        del keep, ikeep
+        return None
 
     def set_frame(self, settings: np.ndarray, camera: np.ndarray) -> None:
         settings = np.ascontiguousarray(settings)

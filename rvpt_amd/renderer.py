@@ -87,6 +87,7 @@ class RVPT:
         self.materials: list[np.ndarray] = []
         self._bvh_nodes: np.ndarray | None = None
         self._nodes_stale = False  # update_triangles moved the geometry: bvh_nodes is refitted when it is next asked for
+        self._stale_touched = None  # ... only the paths above these leaf-order positions (sparse updates since), None: the whole tree
         self._primitive_indices: np.ndarray | None = None
         self._sorted_triangles: np.ndarray | None = None
         self._built_from: np.ndarray | None = None  # build="device": the triangles the device built its tree from, until the host statement is asked for
@@ -113,13 +114,13 @@ class RVPT:
         build_sah), made when first asked for."""
         self._host_statement()
         if self._nodes_stale:
-            self._bvh_nodes = scene.refit_bvh(self._bvh_nodes, self.sorted_triangles)
-            self._nodes_stale = False
+            self._bvh_nodes = scene.refit_bvh(self._bvh_nodes, self.sorted_triangles, touched=self._stale_touched)
+            self._nodes_stale, self._stale_touched = False, None
         return self._bvh_nodes
 
     @bvh_nodes.setter
     def bvh_nodes(self, nodes) -> None:
-        self._bvh_nodes, self._nodes_stale = nodes, False
+        self._bvh_nodes, self._nodes_stale, self._stale_touched = nodes, False, None
 
     def _host_statement(self) -> None:
         """build="device": bvh_nodes, primitive_indices and sorted_triangles of the device-built tree, from scene.build_lbvh (build_ploc for "device-ploc", build_sah for "device-sah") on the triangles it was built from"""
@@ -129,6 +130,7 @@ class RVPT:
             self._bvh_nodes, self._primitive_indices = builder(built_from)[:2]
             self._sorted_triangles = self._current_triangles[self._primitive_indices]
             self._nodes_stale = self._current_triangles is not built_from  # moved since: the boxes are refitted when the nodes are asked for
+            self._stale_touched = None
 
     @property
     def primitive_indices(self):
@@ -148,11 +150,15 @@ class RVPT:
     def sorted_triangles(self, tris) -> None:
         self._sorted_triangles = tris
 
-    def update_triangles(self, triangles, rebuild_above=None):
+    def update_triangles(self, triangles, rebuild_above=None, indices=None):
         """Moving geometry — what the per-frame triangle copy of rvpt.cpp:124 is for: `triangles` (float32[n, 16], in the order they were ADDED, same count) replace
         the scene's; the tree keeps its topology and is refitted on the device (Context.update_triangles), no rebuild.  The next update() restarts the accumulation.
         rebuild_above: Context.update_triangles' keyword — the guarded form: the refitted tree's SAH cost is reported (native.UpdateReport) and, past that factor of
-        the cost of the tree as built, the device rebuilds by the builder of initialize().  A limit needs build="device*"; math.inf only reports."""
+        the cost of the tree as built, the device rebuilds by the builder of initialize().  A limit needs build="device*"; math.inf only reports.
+        indices: the SPARSE form (Context.update_triangles' keyword) — `triangles` are k rows and replace the vertices of the triangles indices[j], numbered in the
+        order they were ADDED; only the boxes above them are recomputed, on the device and in bvh_nodes.  Not together with rebuild_above."""
+        if indices is not None:
+            return self._update_sparse(triangles, rebuild_above, indices)
         tris = np.asarray(triangles, dtype=np.float32).reshape(-1, 16)
         if self._ctx is None or self._n_triangles is None:
             raise RuntimeError("update_triangles before initialize()")
@@ -166,18 +172,60 @@ class RVPT:
                 # the device holds a new tree and a new permutation: the host statement is that of a fresh build from these triangles, made when asked for
                 self._built_from = self._current_triangles
                 self._bvh_nodes = self._primitive_indices = self._sorted_triangles = None
-                self._nodes_stale = False
+                self._nodes_stale, self._stale_touched = False, None
             elif self._built_from is None:
                 self._sorted_triangles = tris[self._primitive_indices]
-                self._nodes_stale = True
+                self._nodes_stale, self._stale_touched = True, None
         else:
             sorted_tris = tris[self.primitive_indices]  # leaf order (Bvh::permute_primitives)
             report = self._ctx.update_triangles(sorted_tris, rebuild_above)
             self.triangles = [tris.copy()]
             self.sorted_triangles = sorted_tris
-            self._nodes_stale = self._bvh_nodes is not None
+            self._nodes_stale, self._stale_touched = self._bvh_nodes is not None, None
         self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
         return report
+
+    def _update_sparse(self, triangles, rebuild_above, indices) -> None:
+        if self._ctx is None or self._n_triangles is None:
+            raise RuntimeError("update_triangles before initialize()")
+        if rebuild_above is not None:
+            raise native.NativeError(native.ERR_INVALID, "update_triangles: indices (the sparse form) and rebuild_above (the guarded form) do not combine")
+        tris = np.asarray(triangles, dtype=np.float32).reshape(-1, 16)
+        idx = np.asarray(indices)
+        if idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)) or idx.shape[0] != tris.shape[0]:
+            raise native.NativeError(native.ERR_INVALID, f"update_triangles: indices are a 1-D integer array with one entry per triangle given, got {idx.dtype} {idx.shape} for {tris.shape[0]}")
+        if idx.size == 0:
+            return None
+        if int(idx.min()) < 0 or int(idx.max()) >= self._n_triangles:
+            bad = int(np.flatnonzero((idx < 0) | (idx >= self._n_triangles))[0])
+            raise native.NativeError(native.ERR_INVALID, f"update_triangles: indices[{bad}] = {int(idx[bad])} is outside the {self._n_triangles} triangles of the scene")
+        idx = idx.astype(np.int64)
+        if self._device_built:  # the device keeps the permutation: the caller's numbering goes down as it is
+            self._ctx.update_triangles(tris, indices=idx)
+        else:  # a host-built tree: added order -> leaf order through the inverse of primitive_indices
+            inverse = np.empty(self._n_triangles, dtype=np.int64)
+            inverse[np.asarray(self.primitive_indices, dtype=np.int64)] = np.arange(self._n_triangles)
+            self._ctx.update_triangles(tris, indices=inverse[idx])
+        # the mirror's host copies: only the vertex columns move, the material rows are the stored ones
+        added = np.concatenate(self.triangles).copy() if self._current_triangles is None else self._current_triangles.copy()
+        added[idx, :12] = tris[:, :12]
+        self.triangles = [added]
+        if self._device_built:
+            self._current_triangles = added
+        if self._built_from is None:  # there is a host statement to keep right
+            inverse = np.empty(self._n_triangles, dtype=np.int64)
+            inverse[np.asarray(self._primitive_indices, dtype=np.int64)] = np.arange(self._n_triangles)
+            pos = inverse[idx]
+            sorted_tris = self._sorted_triangles.copy()
+            sorted_tris[pos, :12] = tris[:, :12]
+            self._sorted_triangles = sorted_tris
+            if self._bvh_nodes is not None:
+                if not self._nodes_stale:
+                    self._nodes_stale, self._stale_touched = True, pos
+                elif self._stale_touched is not None:
+                    self._stale_touched = np.concatenate([self._stale_touched, pos])
+        self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
+        return None
 
     # -- lifecycle -----------------------------------------------------------------------------------------
     def initialize(self) -> bool:

@@ -46,7 +46,7 @@ def make_material(albedo, emission, mtype: int) -> np.ndarray:
 NODE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("bounds", "<f4", (6,))])  # rvpt_bvh_node (== native.NODE_DTYPE)
 
 
-def refit_bvh(nodes, tris) -> np.ndarray:
+def refit_bvh(nodes, tris, touched=None) -> np.ndarray:
     """The normative refit of a tree whose triangles moved (the host statement of what rvpt_hip_upload_scene's update form does on the device): topology
     (`first`, `count`) kept, a leaf's box = component-wise min / max over the vertices of its triangles, an inner node's box = min / max of its two
     children's boxes.  min / max of floats is exact, so the result does not depend on the order of evaluation (up to the sign of a zero) and a tree whose
@@ -54,7 +54,11 @@ def refit_bvh(nodes, tris) -> np.ndarray:
 
     nodes: uint32[n, 8] (native.build_bvh) or NODE_DTYPE records, root at 0, children of an inner node at first, first + 1, leaf iff count > 0;
     tris: float32[m, 16] in the leaf order the tree indexes.  Returns a new array in the form of `nodes`; nodes the root does not reach are left as they are.
-    Iterative (level by level), a few seconds for the 1.5 M nodes of the 1 M-triangle terrain."""
+    Iterative (level by level), a few seconds for the 1.5 M nodes of the 1 M-triangle terrain.
+
+    touched: None, or positions in leaf order (integers, any order, repeats allowed) — the host statement of the SPARSE update (include/rvpt_hip.h): only the
+    leaves that hold a touched triangle and the nodes between such a leaf and the root are recomputed, by the same rule and deepest first; every other box comes
+    back as it was given, loose ones included.  On a tree whose boxes were tight the result is the full refit's."""
     src = np.ascontiguousarray(nodes)
     out = src.copy()
     rec = out.view(NODE_DTYPE).reshape(-1)
@@ -74,6 +78,8 @@ def refit_bvh(nodes, tris) -> np.ndarray:
         seen += frontier.size
         if seen > n:
             raise ValueError("refit_bvh: not a tree (a node is reachable twice)")
+    if touched is not None:
+        return _refit_touched(out, rec, v, first, count, levels, touched)
     lo = np.empty((n, 3), dtype=np.float32)
     hi = np.empty((n, 3), dtype=np.float32)
     leaves = np.concatenate([l[count[l] > 0] for l in levels])
@@ -93,6 +99,50 @@ def refit_bvh(nodes, tris) -> np.ndarray:
     reached = np.concatenate(levels)
     b = rec["bounds"]
     b[reached, 0::2], b[reached, 1::2] = lo[reached], hi[reached]
+    return out
+
+
+def _refit_touched(out, rec, v, first, count, levels, touched):
+    """refit_bvh's sparse form: `levels` are the node indices per level, root first"""
+    n = rec.shape[0]
+    pos = np.unique(np.asarray(touched, dtype=np.int64).reshape(-1))
+    if pos.size == 0:
+        return out
+    if int(pos[0]) < 0 or int(pos[-1]) >= v.shape[0]:
+        raise ValueError("refit_bvh: touched position outside the triangle array")
+    reached = np.concatenate(levels)
+    leaves = reached[count[reached] > 0]
+    if leaves.size and int((first[leaves] + count[leaves]).max()) > v.shape[0]:
+        raise ValueError("refit_bvh: leaf range outside the triangle array")
+    parent = np.full(n, -1, dtype=np.int64)
+    inner = reached[count[reached] == 0]
+    parent[first[inner]], parent[first[inner] + 1] = inner, inner
+    # the leaf of every touched position: the leaves' ranges are disjoint, so sorted by `first` the last range that starts at or before a position holds it
+    order = np.argsort(first[leaves], kind="stable")
+    starts, sorted_leaves = first[leaves][order], leaves[order]
+    slot = np.searchsorted(starts, pos, side="right") - 1
+    held = slot >= 0
+    cand = sorted_leaves[slot[held]]
+    cand = cand[pos[held] < first[cand] + count[cand]]
+    dirty = np.zeros(n, dtype=bool)
+    front = np.unique(cand)
+    while front.size:
+        dirty[front] = True
+        up = parent[front]
+        up = np.unique(up[up >= 0])
+        front = up[~dirty[up]]
+    b = rec["bounds"]
+    tlo, thi = v.min(axis=1), v.max(axis=1)
+    for level in reversed(levels):
+        lv = level[dirty[level]]
+        for i in lv[count[lv] > 0]:
+            f, c = int(first[i]), int(count[i])
+            b[i, 0::2], b[i, 1::2] = tlo[f:f + c].min(axis=0), thi[f:f + c].max(axis=0)
+        inn = lv[count[lv] == 0]
+        if inn.size:
+            l, r = first[inn], first[inn] + 1
+            b[inn, 0::2] = np.minimum(b[l, 0::2], b[r, 0::2])
+            b[inn, 1::2] = np.maximum(b[l, 1::2], b[r, 1::2])
     return out
 
 

@@ -4,7 +4,10 @@ only route there was before it — rvpt_bvh_build + a full upload_scene — and 
 traversal pays on a refitted tree against a freshly built one.  -> stdout (profiles/refit_update.txt)
 usage: tools/refit_bench.py [all|updates|guard|guard-updates]     (updates: one upload and a few updates, nothing else — the run to put under rocprofv3
 --kernel-trace --stats; guard: only the guarded update's section, -> profiles/guarded_update.txt; guard-updates: a device build and a few guarded updates, for the
-same profiler run)"""
+same profiler run)
+       tools/refit_bench.py --sparse 0.01 [updates]      the SPARSE update (Context.update_triangles(indices=)) of that fraction of the terrain beside the plain
+update in the same run, from a host array and from device memory, one block contiguous in added order and the same number scattered -> profiles/sparse_update.txt;
+exits non-zero unless the sparse update from a host array is quicker than the plain one.  With `updates`: a few sparse updates and nothing else, for the profiler"""
 import statistics, sys, time
 from pathlib import Path
 
@@ -15,6 +18,8 @@ sys.path.insert(0, str(ROOT))
 from rvpt_amd import Camera, RenderSettings, native, scene  # noqa: E402
 
 what = sys.argv[1] if len(sys.argv) > 1 else "all"
+sparse_fraction = float(sys.argv[2]) if what == "--sparse" and len(sys.argv) > 2 else 0.01
+sparse_only_updates = what == "--sparse" and len(sys.argv) > 3 and sys.argv[3] == "updates"
 W, H = 1920, 1080
 
 
@@ -122,6 +127,60 @@ cam = c.get_data()
 poses = [scene.wobble(tris, 0.5 + 0.9 * k, 0.02 * ext) for k in range(4)]  # in leaf order
 ctx = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BVH)
 ctx.upload_scene(nodes, tris, mats)
+
+
+
+def sparse_section(ctx, tris, idx, poses, fraction, only_updates):
+    """The sparse update beside the plain one on ONE context (host-built tree: the lists are leaf-order positions).  `block`: k triangles contiguous in the order
+    they were added, mapped through the inverse of the build's primitive indices; `scattered`: k positions drawn from the whole scene."""
+    import torch
+    n = tris.shape[0]
+    k = max(1, int(round(fraction * n)))
+    inverse = np.empty(n, dtype=np.int64)
+    inverse[np.asarray(idx, dtype=np.int64)] = np.arange(n)
+    rng = np.random.RandomState(9)
+    start = int(rng.randint(0, n - k + 1))
+    lists = {"block": inverse[start:start + k], "scattered": rng.permutation(n)[:k]}
+    rows = {name: [np.ascontiguousarray(p[l]) for p in poses[:2]] for name, l in lists.items()}
+    dev_rows = {name: [torch.from_numpy(r).to("cuda:0") for r in rs] for name, rs in rows.items()}
+    dev_lists = {name: torch.from_numpy(l.astype(np.int32)).to("cuda:0") for name, l in lists.items()}
+    it = [0]
+    if only_updates:
+        for name in lists:
+            for _ in range(4):
+                ctx.update_triangles(rows[name][it[0] % 2], indices=lists[name])
+                ctx.update_triangles(dev_rows[name][it[0] % 2], indices=dev_lists[name]); it[0] += 1
+        print(f"16 sparse updates of {k} triangles done")
+        return True
+    print(f"\n== sparse update of {k} of {n} triangles ({fraction:.4f}) beside the plain update, same context, same run (wall clock of the call, median of 20) ==")
+    def plain_host():
+        ctx.update_triangles(poses[it[0] % 4]); it[0] += 1
+    dev_poses = [torch.from_numpy(p).to("cuda:0") for p in poses[:2]]
+    def plain_dev():
+        ctx.update_triangles(dev_poses[it[0] % 2]); it[0] += 1
+    full_host, full_dev = timed(plain_host, 20, warm=3), timed(plain_dev, 20, warm=3)
+    print(f"plain update, host numpy array          {spread(full_host)}")
+    print(f"plain update, torch tensor on device    {spread(full_dev)}")
+    ok = True
+    for name in lists:
+        def sparse_host():
+            ctx.update_triangles(rows[name][it[0] % 2], indices=lists[name]); it[0] += 1
+        def sparse_dev():
+            ctx.update_triangles(dev_rows[name][it[0] % 2], indices=dev_lists[name]); it[0] += 1
+        h, d = timed(sparse_host, 20, warm=3), timed(sparse_dev, 20, warm=3)
+        span = int(lists[name].max() - lists[name].min() + 1)
+        print(f"sparse, {name:9s} host arrays         {spread(h)}    (rows prepared: {span})")
+        print(f"sparse, {name:9s} device memory       {spread(d)}")
+        quicker = statistics.median(h) < statistics.median(full_host)
+        print(f"        {name:9s} host: {statistics.median(full_host) / statistics.median(h):.1f} x the plain update from a host array -> {'ok' if quicker else 'NOT QUICKER'}")
+        ok = ok and quicker
+    return ok
+
+
+if what == "--sparse":
+    ok = sparse_section(ctx, tris, idx, poses, sparse_fraction, sparse_only_updates)
+    ctx.close()
+    sys.exit(0 if ok else 1)
 
 if what == "updates":
     for k in range(8):

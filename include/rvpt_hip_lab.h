@@ -90,6 +90,34 @@ int rvpt_claim_order(uint32_t n_work_frame, uint32_t group_blocks, uint32_t *ord
 int rvpt_bvh_wide_form(const rvpt_bvh_node *nodes, size_t n_nodes, uint32_t head_shift, float *wide_out, size_t wide_capacity, size_t *n_wide_out,
                        uint32_t *stack_need_out);
 
+/* The stored scene as the device holds it, read back (tests/test_device_state.py compares it byte for byte with the numpy statements of the builders, the refit
+ * and the sparse update's maps: images cannot tell two valid trees over the same triangles apart).  The call waits for everything the context has queued, as
+ * rvpt_hip_wait does, then copies device to host with plain hipMemcpy — exactly the live bytes, nothing launched, nothing changed: two calls in a row give the same
+ * bytes.  `info` (may be NULL) is filled with the counts and flags of the stored scene: built_by = 0 the caller's tree (an ordinary upload), 1 LBVH, 2 PLOC, 3 SAH
+ * (a PLOC build that fell back to the LBVH tree still says 2: it is rebuilt by the same rule); base_cost = the cost the guarded update compares with.
+ * `piece` selects ONE array; *bytes_out (may be NULL) = its live size; a piece the context does not hold now is 0 bytes and RVPT_HIP_OK:
+ *   NODES          n_nodes x 32 B, the breadth-first device layout (root 0, slot 1 unused, sibling pairs from 2 on); brute-force contexts hold none
+ *   TRIS           n_tris x 64 B, in leaf order
+ *   PERM           n_tris x 4 B after a build form (have_perm): leaf-order triangle j is the caller's triangle perm[j]
+ *   WIDE           n_wide x 128 B, the 4-wide nodes;  WIDE_MAP  n_wide x 16 B, the binary node behind every slot (0xFFFFFFFF: unused)
+ *   REFIT_LEVELS   bvh_height pairs of words [begin, end): the levels of the device layout, root first (kept on the host)
+ *   SPARSE_PARENT, SPARSE_DIRTY   one word per node up to the end of the last level, SPARSE_LEAF_OF  n_tris words: the sparse update's maps and flags, while
+ *                  have_sparse_maps (made by the first sparse update after a full upload, build or rebuild)
+ *   INV_PERM       n_tris words while have_inv_perm: the inverse of PERM
+ * dst == NULL or dst_capacity < the live size of a piece that has bytes: RVPT_HIP_ERR_SIZE, *bytes_out = the size needed, nothing written.  A context without a
+ * scene: RVPT_HIP_ERR_INVALID. */
+typedef struct rvpt_hip_scene_state_info {
+    uint64_t n_tris, n_nodes, n_wide;
+    uint32_t bvh_head_shift, wide_stack_levels, bvh_height, built_by;
+    uint32_t have_perm, have_sparse_maps, have_inv_perm, have_cost;
+    double base_cost;
+} rvpt_hip_scene_state_info;
+enum {
+    RVPT_HIP_STATE_NONE = 0, RVPT_HIP_STATE_NODES = 1, RVPT_HIP_STATE_TRIS = 2, RVPT_HIP_STATE_PERM = 3, RVPT_HIP_STATE_WIDE = 4, RVPT_HIP_STATE_WIDE_MAP = 5,
+    RVPT_HIP_STATE_REFIT_LEVELS = 6, RVPT_HIP_STATE_SPARSE_PARENT = 7, RVPT_HIP_STATE_SPARSE_LEAF_OF = 8, RVPT_HIP_STATE_SPARSE_DIRTY = 9, RVPT_HIP_STATE_INV_PERM = 10
+};
+int rvpt_hip_selftest_scene_state(rvpt_hip_ctx *ctx, rvpt_hip_scene_state_info *info, uint32_t piece, void *dst, size_t dst_capacity, size_t *bytes_out);
+
 #ifdef __cplusplus
 }
 #endif

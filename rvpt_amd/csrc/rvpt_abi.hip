@@ -2632,6 +2632,52 @@ int rvpt_hip_selftest_rcp(int device_id, uint64_t mismatches_per_exponent[256])
     return RVPT_HIP_OK;
 }
 
+// The stored scene as the device holds it (include/rvpt_hip_lab.h): waits like rvpt_hip_wait, then plain copies of the live bytes.  No launch, no write to
+// anything the context owns.
+int rvpt_hip_selftest_scene_state(rvpt_hip_ctx *ctx, rvpt_hip_scene_state_info *info, uint32_t piece, void *dst, size_t dst_capacity, size_t *bytes_out)
+{
+    if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
+    if (bytes_out) *bytes_out = 0;
+    if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "scene state before any upload_scene on this context: there is no scene to read");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = sync_all(ctx)) return rc;
+    const size_t n_tris = ctx->n_tris, n_nodes = ctx->n_nodes, n_wide = ctx->n_wide;
+    // the nodes the sparse update's maps cover: the end of the last level (update_geometry_sparse)
+    const size_t n_map_nodes = ctx->have_sparse_maps && !ctx->refit_levels.empty() ? std::min<size_t>(n_nodes, ctx->refit_levels.back().second) : 0;
+    if (info) {
+        std::memset(info, 0, sizeof *info);
+        info->n_tris = n_tris, info->n_nodes = n_nodes, info->n_wide = n_wide;
+        info->bvh_head_shift = ctx->bvh_head_shift, info->wide_stack_levels = ctx->wide_stack_levels, info->bvh_height = ctx->bvh_height;
+        info->built_by = static_cast<uint32_t>(ctx->built_by);
+        info->have_perm = ctx->have_perm, info->have_sparse_maps = ctx->have_sparse_maps, info->have_inv_perm = ctx->have_inv_perm, info->have_cost = ctx->have_cost;
+        info->base_cost = ctx->base_cost;
+    }
+    const void *src = nullptr;
+    bool host = false;
+    size_t bytes = 0;
+    switch (piece) {
+    case RVPT_HIP_STATE_NONE: break;
+    case RVPT_HIP_STATE_NODES: src = ctx->d_nodes, bytes = n_nodes * sizeof(rvpt_bvh_node); break;
+    case RVPT_HIP_STATE_TRIS: src = ctx->d_tris, bytes = n_tris * sizeof(rvpt_triangle); break;
+    case RVPT_HIP_STATE_PERM: src = ctx->d_perm, bytes = ctx->have_perm ? n_tris * sizeof(uint32_t) : 0; break;
+    case RVPT_HIP_STATE_WIDE: src = ctx->d_wide, bytes = n_wide * 128u; break;
+    case RVPT_HIP_STATE_WIDE_MAP: src = ctx->d_wide_map, bytes = n_wide * 16u; break;
+    case RVPT_HIP_STATE_REFIT_LEVELS: src = ctx->refit_levels.data(), bytes = ctx->refit_levels.size() * 2u * sizeof(uint32_t), host = true; break;
+    case RVPT_HIP_STATE_SPARSE_PARENT: src = ctx->d_sparse_parent, bytes = n_map_nodes * sizeof(uint32_t); break;
+    case RVPT_HIP_STATE_SPARSE_LEAF_OF: src = ctx->d_sparse_leaf_of, bytes = n_map_nodes ? n_tris * sizeof(uint32_t) : 0; break;
+    case RVPT_HIP_STATE_SPARSE_DIRTY: src = ctx->d_sparse_dirty, bytes = n_map_nodes * sizeof(uint32_t); break;
+    case RVPT_HIP_STATE_INV_PERM: src = ctx->d_inv_perm, bytes = ctx->have_perm && ctx->have_inv_perm ? n_tris * sizeof(uint32_t) : 0; break;
+    default: return fail(ctx, RVPT_HIP_ERR_INVALID, "scene state: there is no piece %u", piece);
+    }
+    if (bytes_out) *bytes_out = bytes;
+    if (bytes == 0) return RVPT_HIP_OK;
+    if (!src) return fail(ctx, RVPT_HIP_ERR_INVALID, "scene state: piece %u has %zu live bytes and no buffer", piece, bytes);
+    if (!dst || dst_capacity < bytes) return fail(ctx, RVPT_HIP_ERR_SIZE, "scene state: piece %u needs %zu bytes, dst holds %zu", piece, bytes, dst ? dst_capacity : size_t(0));
+    if (host) std::memcpy(dst, src, bytes);
+    else HIP_TRY(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return RVPT_HIP_OK;
+}
+
 #endif  // RVPT_HIP_LAB
 
 int rvpt_hip_untile(rvpt_hip_ctx *ctx, const void *gathered_dev, size_t slot_bytes, uint32_t n_ranks, void *dst_dev_rgba32f)

@@ -39,7 +39,8 @@
 //   per triangle i (caller's index): box = fminf / fmaxf of the three vertices; centroid = (v0 + v1 + v2) * (1.0f / 3.0f), float32, left to right, no
 //       contraction; the index array starts as 0 .. n - 1.
 //   per node (a range of the index array, depth = its level): bounds and cbounds (of the centroids) are exact min / max, a NaN takes no part (a side nothing
-//       took part in stays +-FLT_MAX, the host's empty Box).  count < 2: a leaf.
+//       took part in stays +-FLT_MAX, the host's empty Box; and as that Box starts at +-FLT_MAX and takes std::min / std::max, a low side is never above
+//       FLT_MAX and a high side never below -FLT_MAX: nothing but +inf on a low side gives FLT_MAX).  count < 2: a leaf.
 //   binning (only where depth < 30): per axis 0, 1, 2 with extent = cbounds.hi - cbounds.lo > 0: scale = 16.0f / extent (the IEEE float32 divide);
 //       bin = f >= 15 ? 15 : f >= 0 ? (int)f : 0 with f = (c - lo) * scale — the keys' rule above: a NaN gives 0, +inf gives 15, nothing leans on an undefined
 //       conversion; bin boxes and counts are exact.  The right sweep and then the left sweep as in the host code: half_area = dx * (dy + dz) + dy * dz in

@@ -3,6 +3,9 @@
 //
 // min / max of floats is exact and order-independent, so the result is THE refit of the tree (rvpt_amd/scene.py: refit_bvh is the same in numpy), not an
 // approximation of it.  (Only the sign of a zero bound may differ between two orders; a slab test cannot tell: (+-0 - o) * inv compares equal.)
+// A NaN takes no part (fminf / fmaxf return the other operand; rvpt_build.h states the rule for the builders): a bound is NaN only where nothing but NaN
+// took part — all of a leaf's coordinates on that axis, or both children's bounds — and refit_bvh says the same.  tests/test_device_state.py reads the
+// boxes back and compares them byte for byte, non-finite vertices included.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -38,8 +38,10 @@ __device__ inline uint32_t ordered(float f)
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ inline float unordered(uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e); }
-__device__ inline float lo_of(uint32_t e) { return e == 0xFFFFFFFFu ? FLT_MAX : unordered(e); }  // the host's empty Box
-__device__ inline float hi_of(uint32_t e) { return e == 0u ? -FLT_MAX : unordered(e); }
+// the host's Box: it starts at +-FLT_MAX and takes std::min / std::max, so a side on which nothing took part, or nothing but +inf (-inf for a high side), is
+// +-FLT_MAX — never an infinity of that sign (lo = hi = +inf would make the extent a NaN where the host's is +inf, and another median axis: tests/test_device_state.py)
+__device__ inline float lo_of(uint32_t e) { return e == 0xFFFFFFFFu ? FLT_MAX : fminf(unordered(e), FLT_MAX); }
+__device__ inline float hi_of(uint32_t e) { return e == 0u ? -FLT_MAX : fmaxf(unordered(e), -FLT_MAX); }
 __device__ inline uint32_t initial_word(uint32_t w) { return (w < 12u ? (w % 6u) < 3u : ((w - 12u) % kBinWords) < 3u) ? 0xFFFFFFFFu : 0u; }
 
 __device__ inline int bin_of(float c, float lo, float scale)

@@ -48,6 +48,7 @@ EXPORTS = [
 LAB_EXPORTS = [
     "rvpt_hip_selftest_div", "rvpt_hip_selftest_rcp", "rvpt_hip_selftest_pretest", "rvpt_hip_selftest_camera_rects", "rvpt_hip_selftest_bounce_cull",
     "rvpt_hip_selftest_fast_div", "rvpt_camera_rects", "rvpt_bounce_rows", "rvpt_bounce_leaf_boxes", "rvpt_bvh_wide_form", "rvpt_claim_order",
+    "rvpt_hip_selftest_scene_state",
 ]
 
 
@@ -76,6 +77,14 @@ def parse_update_report(sentence: str) -> UpdateReport:
         raise NativeError(ERR_INVALID, f"update_triangles: not a guarded update's report: {sentence!r}")
     cost, base = float(m.group(1)), float(m.group(2))
     return UpdateReport(cost, base, cost / base if base > 0.0 else 0.0, m.group(4) is not None, m.group(4))
+
+
+class SceneStateInfo(C.Structure):
+    """rvpt_hip_scene_state_info (include/rvpt_hip_lab.h)"""
+    _fields_ = [("n_tris", C.c_uint64), ("n_nodes", C.c_uint64), ("n_wide", C.c_uint64),
+                ("bvh_head_shift", C.c_uint32), ("wide_stack_levels", C.c_uint32), ("bvh_height", C.c_uint32), ("built_by", C.c_uint32),
+                ("have_perm", C.c_uint32), ("have_sparse_maps", C.c_uint32), ("have_inv_perm", C.c_uint32), ("have_cost", C.c_uint32),
+                ("base_cost", C.c_double)]
 
 
 class NativeError(RuntimeError):
@@ -139,6 +148,7 @@ def _bind(L, lab: bool):
         L.rvpt_hip_selftest_camera_rects.argtypes = [vp, u32, vp, vp, vp]
         L.rvpt_hip_selftest_bounce_cull.argtypes = [vp, u32, vp]
         L.rvpt_hip_selftest_fast_div.argtypes = [u32, vp, vp, sz]
+        L.rvpt_hip_selftest_scene_state.argtypes = [vp, C.POINTER(SceneStateInfo), u32, vp, sz, C.POINTER(sz)]
         names += LAB_EXPORTS
     for name in names:
         if name not in ("rvpt_hip_destroy", "rvpt_hip_last_error", "rvpt_hip_build_flags"):
@@ -323,6 +333,14 @@ def unpack_rects(words: np.ndarray) -> np.ndarray:
 
 
 NODE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("bounds", "<f4", (6,))])
+
+# the pieces of rvpt_hip_selftest_scene_state (include/rvpt_hip_lab.h: RVPT_HIP_STATE_*) as (number, dtype, trailing shape) by the name Context.scene_state returns them under
+SCENE_STATE_PIECES = {
+    "nodes": (1, NODE_DTYPE, ()), "tris": (2, np.float32, (16,)), "perm": (3, np.uint32, ()), "wide": (4, np.float32, (8, 4)), "wide_map": (5, np.uint32, (4,)),
+    "refit_levels": (6, np.uint32, (2,)), "sparse_parent": (7, np.uint32, ()), "sparse_leaf_of": (8, np.uint32, ()), "sparse_dirty": (9, np.uint32, ()),
+    "inv_perm": (10, np.uint32, ()),
+}
+BUILT_BY = (None, "lbvh", "ploc", "sah")  # rvpt_hip_scene_state_info::built_by
 
 
 class Context:
@@ -659,6 +677,32 @@ class Context:
         out = (C.c_uint64 * 8)()
         _check(self._L.rvpt_hip_selftest_bounce_cull(self._h, int(n_samples), out), self._h, self._L)
         return tuple(int(x) for x in out)
+
+    def scene_state(self, pieces=None) -> dict:
+        """rvpt_hip_selftest_scene_state (laboratory contexts only): the stored scene as the device holds it, after everything queued has finished.  Returns a dict
+        with the info block's fields (n_tris, n_nodes, n_wide, bvh_head_shift, wide_stack_levels, bvh_height, built_by as None / "lbvh" / "ploc" / "sah", the
+        have_* flags as bools, base_cost) and, per name of SCENE_STATE_PIECES (all of them, or those listed in `pieces`), a numpy array of exactly the live bytes
+        — empty where the context does not hold the piece now.  Nothing is launched and nothing changes."""
+        if not self.lab:
+            raise NativeError(ERR_UNSUPPORTED, "scene_state: only the laboratory build reads the scene back (Context(..., lab=True))")
+        info, size = SceneStateInfo(), C.c_size_t(0)
+        _check(self._L.rvpt_hip_selftest_scene_state(self._h, C.byref(info), 0, None, 0, C.byref(size)), self._h, self._L)
+        out = {name: getattr(info, name) for name, _ in SceneStateInfo._fields_}
+        for flag in ("have_perm", "have_sparse_maps", "have_inv_perm", "have_cost"):
+            out[flag] = bool(out[flag])
+        out["built_by"] = BUILT_BY[info.built_by]
+        for name in (SCENE_STATE_PIECES if pieces is None else pieces):
+            number, dtype, tail = SCENE_STATE_PIECES[name]
+            rc = self._L.rvpt_hip_selftest_scene_state(self._h, None, number, None, 0, C.byref(size))
+            if rc not in (0, ERR_SIZE):
+                _check(rc, self._h, self._L)
+            item = np.dtype(dtype).itemsize * int(np.prod(tail, dtype=np.int64))
+            buf = np.zeros((size.value // item,) + tail, dtype=dtype)
+            if size.value:
+                assert buf.nbytes == size.value, (name, buf.nbytes, size.value)
+                _check(self._L.rvpt_hip_selftest_scene_state(self._h, None, number, _ptr(buf), buf.nbytes, C.byref(size)), self._h, self._L)
+            out[name] = buf
+        return out
 
     def stats(self):
         """(segments, samples) traced since create / reset_timing (needs COUNT_SEGMENTS)."""

@@ -46,11 +46,34 @@ def make_material(albedo, emission, mtype: int) -> np.ndarray:
 NODE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("bounds", "<f4", (6,))])  # rvpt_bvh_node (== native.NODE_DTYPE)
 
 
+def _min_no_nan(a, b):
+    """np.minimum where neither is a NaN (the same bytes), otherwise the one that is not: fminf"""
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.minimum(a, b)))
+
+
+def _max_no_nan(a, b):
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.maximum(a, b)))
+
+
+def _reduce_no_nan(x, axis):
+    """(min, max) of x along axis: ndarray.min / max where no NaN took part (the same bytes), np.fmin / np.fmax — a NaN takes no part — elsewhere"""
+    with np.errstate(invalid="ignore"):
+        lo, hi = x.min(axis=axis), x.max(axis=axis)
+        bad = np.isnan(lo)  # (min and max meet a NaN in the same places)
+        if bad.any():
+            lo, hi = np.where(bad, np.fmin.reduce(x, axis=axis), lo), np.where(bad, np.fmax.reduce(x, axis=axis), hi)
+    return lo, hi
+
+
 def refit_bvh(nodes, tris, touched=None) -> np.ndarray:
     """The normative refit of a tree whose triangles moved (the host statement of what rvpt_hip_upload_scene's update form does on the device): topology
     (`first`, `count`) kept, a leaf's box = component-wise min / max over the vertices of its triangles, an inner node's box = min / max of its two
     children's boxes.  min / max of floats is exact, so the result does not depend on the order of evaluation (up to the sign of a zero) and a tree whose
-    boxes were tight comes back byte for byte; loose boxes become tight.
+    boxes were tight comes back byte for byte; loose boxes become tight.  A NaN takes no part (the device's fminf / fmaxf, the rule of
+    rvpt_amd/csrc/rvpt_build.h): a bound is NaN only where nothing but NaN took part — every coordinate of a leaf on that axis, or both children's bounds.
+    Infinities are ordinary values.
 
     nodes: uint32[n, 8] (native.build_bvh) or NODE_DTYPE records, root at 0, children of an inner node at first, first + 1, leaf iff count > 0;
     tris: float32[m, 16] in the leaf order the tree indexes.  Returns a new array in the form of `nodes`; nodes the root does not reach are left as they are.
@@ -86,16 +109,16 @@ def refit_bvh(nodes, tris, touched=None) -> np.ndarray:
     if leaves.size:
         if int((first[leaves] + count[leaves]).max()) > v.shape[0]:
             raise ValueError("refit_bvh: leaf range outside the triangle array")
-        tlo, thi = v.min(axis=1), v.max(axis=1)
+        tlo, thi = _reduce_no_nan(v, 1)
         lo[leaves], hi[leaves] = tlo[first[leaves]], thi[first[leaves]]
         for k in range(1, int(count[leaves].max())):  # the k-th triangle of every leaf that has one
             more = leaves[count[leaves] > k]
-            lo[more] = np.minimum(lo[more], tlo[first[more] + k])
-            hi[more] = np.maximum(hi[more], thi[first[more] + k])
+            lo[more] = _min_no_nan(lo[more], tlo[first[more] + k])
+            hi[more] = _max_no_nan(hi[more], thi[first[more] + k])
     for level in reversed(levels):
         inner = level[count[level] == 0]
-        lo[inner] = np.minimum(lo[first[inner]], lo[first[inner] + 1])
-        hi[inner] = np.maximum(hi[first[inner]], hi[first[inner] + 1])
+        lo[inner] = _min_no_nan(lo[first[inner]], lo[first[inner] + 1])
+        hi[inner] = _max_no_nan(hi[first[inner]], hi[first[inner] + 1])
     reached = np.concatenate(levels)
     b = rec["bounds"]
     b[reached, 0::2], b[reached, 1::2] = lo[reached], hi[reached]
@@ -132,17 +155,17 @@ def _refit_touched(out, rec, v, first, count, levels, touched):
         up = np.unique(up[up >= 0])
         front = up[~dirty[up]]
     b = rec["bounds"]
-    tlo, thi = v.min(axis=1), v.max(axis=1)
+    tlo, thi = _reduce_no_nan(v, 1)
     for level in reversed(levels):
         lv = level[dirty[level]]
         for i in lv[count[lv] > 0]:
             f, c = int(first[i]), int(count[i])
-            b[i, 0::2], b[i, 1::2] = tlo[f:f + c].min(axis=0), thi[f:f + c].max(axis=0)
+            b[i, 0::2], b[i, 1::2] = _reduce_no_nan(tlo[f:f + c], 0)[0], _reduce_no_nan(thi[f:f + c], 0)[1]
         inn = lv[count[lv] == 0]
         if inn.size:
             l, r = first[inn], first[inn] + 1
-            b[inn, 0::2] = np.minimum(b[l, 0::2], b[r, 0::2])
-            b[inn, 1::2] = np.maximum(b[l, 1::2], b[r, 1::2])
+            b[inn, 0::2] = _min_no_nan(b[l, 0::2], b[r, 0::2])
+            b[inn, 1::2] = _max_no_nan(b[l, 1::2], b[r, 1::2])
     return out
 
 

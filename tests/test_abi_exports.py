@@ -40,7 +40,7 @@ RELEASE_ABI = [
 ]
 LAB_ABI = [
     "rvpt_bounce_leaf_boxes", "rvpt_bounce_rows", "rvpt_bvh_wide_form", "rvpt_camera_rects", "rvpt_claim_order", "rvpt_hip_selftest_bounce_cull", "rvpt_hip_selftest_camera_rects",
-    "rvpt_hip_selftest_div", "rvpt_hip_selftest_fast_div", "rvpt_hip_selftest_pretest", "rvpt_hip_selftest_rcp",
+    "rvpt_hip_selftest_div", "rvpt_hip_selftest_fast_div", "rvpt_hip_selftest_pretest", "rvpt_hip_selftest_rcp", "rvpt_hip_selftest_scene_state",
 ]
 
 

@@ -1,7 +1,8 @@
 """The device BVH build: the build form of rvpt_hip_upload_scene (Context.build_scene) makes the tree on the GPU from triangles in the caller's order.
 Everything here is bit-exact: context A, given build_scene(tris, mats), renders what a fresh context B renders given upload_scene(nodes, tris[perm], mats) with
 (nodes, perm) = scene.build_lbvh(tris) — the same tree stated in numpy — and what the CPU oracle renders on that tree; work-groups, LDS bytes and kernel path
-of the launch are equal too, which pins the device's level table, head shift, wide nodes and wide stack need against the host's."""
+of the launch are equal too.  That agrees with the host's level table, head shift, wide nodes and wide stack need but does not pin them, nor the topology: a
+walk finds the same closest hit in any valid tree over the same triangles.  tests/test_device_state.py reads the device's tree back and compares the bytes."""
 import numpy as np
 import pytest
 

@@ -1,7 +1,8 @@
 """The PLOC build form: Context.build_scene(tris, mats, method="ploc") (RVPT_HIP_NODES_BUILD_PLOC) makes the PLOC tree on the GPU.  As in
 tests/test_device_build.py everything is bit-exact: context A, given the build, renders what a fresh context B renders given upload_scene(nodes, tris[perm],
 mats) with (nodes, perm) = scene.build_ploc(tris) and what the CPU oracle renders on that tree; segment and sample counts, work-groups, LDS bytes and kernel path
-are equal too, which pins the device's topology, level table, head shift, wide nodes and wide stack need against the host's."""
+are equal too; the device's topology, level table, head shift, wide nodes and wide stack need themselves are compared byte for byte in tests/test_device_state.py
+(equal renders do not pin them: any valid tree over the same triangles gives the same closest hits)."""
 import numpy as np
 import pytest
 

@@ -115,3 +115,113 @@ def test_renderer_and_context_check_their_arguments_without_a_gpu():
     r._nodes_stale = True  # what update_triangles leaves behind: refitted on demand, once
     first = r.bvh_nodes
     assert first.tobytes() == scene.refit_bvh(nodes, r.sorted_triangles).tobytes() and r.bvh_nodes is first
+
+
+def _slow_refit(nodes, tris):
+    """refit_bvh's rule said once more, one node and one coordinate at a time, in Python floats: a bound is the min / max of the values that are not NaN, and
+    NaN where there is none"""
+    import math
+    rec = np.ascontiguousarray(nodes).view(native.NODE_DTYPE).reshape(-1).copy()
+    v = tris.reshape(-1, 4, 4)[:, :3, :3]
+
+    def fold(values, pick):
+        real = [float(x) for x in values if not math.isnan(x)]
+        return pick(real) if real else math.nan
+
+    def visit(i):
+        f, c = int(rec["first"][i]), int(rec["count"][i])
+        if c > 0:
+            los = his = [v[f:f + c, :, ax].reshape(-1).tolist() for ax in range(3)]
+        else:
+            visit(f), visit(f + 1)
+            los = [[rec["bounds"][f][2 * ax], rec["bounds"][f + 1][2 * ax]] for ax in range(3)]
+            his = [[rec["bounds"][f][2 * ax + 1], rec["bounds"][f + 1][2 * ax + 1]] for ax in range(3)]
+        for ax in range(3):
+            rec["bounds"][i][2 * ax], rec["bounds"][i][2 * ax + 1] = fold(los[ax], min), fold(his[ax], max)
+
+    visit(0)
+    return rec
+
+
+def _same_with_nan_in_place(a, b):
+    a, b = a["bounds"], b["bounds"]
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
+
+
+def _non_finite_soup(n, seed, whole_axis=None):
+    rng = np.random.RandomState(seed)
+    p = (rng.uniform(-4, 4, (n, 1, 3)) + rng.uniform(-0.3, 0.3, (n, 3, 3))).astype(np.float32)
+    pick = rng.permutation(n)[:max(3, n // 50)]
+    for j, i in enumerate(pick):
+        val = (np.nan, np.inf, -np.inf)[j % 3]
+        if (j // 3) % 2 == 0:
+            p[i, rng.randint(3), rng.randint(3)] = val
+        else:
+            p[i] = val
+    if whole_axis is not None:
+        p[:, :, whole_axis] = np.nan
+    with np.errstate(all="ignore"):
+        return scene.make_triangles(p, 0), pick
+
+
+@pytest.mark.parametrize("builder", ["lbvh", "ploc", "sah"])
+@pytest.mark.parametrize("n,axis", [(65, None), (257, 1), (1025, None)])
+def test_a_nan_takes_no_part_in_a_refit(builder, n, axis):
+    """rvpt_build.h's rule, which the device's fminf / fmaxf follow: a NaN coordinate takes no part in a box; a bound is NaN only where nothing else took part
+    (a whole leaf's coordinates on an axis, both children's bounds); infinities are ordinary values.  The full refit, the sparse form, and the boxes the three
+    numpy builders return (they end in refit_bvh) against the rule said one coordinate at a time."""
+    tris, pick = _non_finite_soup(n, 100 + n, axis)
+    with np.errstate(all="ignore"):
+        nodes, perm = {"lbvh": scene.build_lbvh, "ploc": scene.build_ploc, "sah": scene.build_sah}[builder](tris)[:2]
+    t = tris[perm]
+    want = _slow_refit(nodes, t)
+    assert _same_with_nan_in_place(nodes, want)
+    b = nodes["bounds"]
+    if axis is None:
+        assert not np.isnan(b[0]).any()  # the root: finite triangles took part on every axis ...
+        assert np.isinf(b[0]).any()       # ... and so did the infinities
+        # a finite triangle that shares a leaf with a NaN one is not hidden: no leaf bound is NaN unless the whole leaf is NaN on that axis
+        v = t.reshape(-1, 4, 4)[:, :3, :3]
+        for i in np.flatnonzero(nodes["count"] > 0):
+            p = v[nodes["first"][i]: nodes["first"][i] + nodes["count"][i]].reshape(-1, 3)
+            assert np.array_equal(np.isnan(b[i][0::2]), np.isnan(p).all(axis=0)) and np.array_equal(np.isnan(b[i][1::2]), np.isnan(p).all(axis=0))
+    else:
+        assert np.isnan(b[:, 2 * axis: 2 * axis + 2]).all() and not np.isnan(np.delete(b[0], [2 * axis, 2 * axis + 1])).any()
+    # the sparse form: move the non-finite values elsewhere, touch both sets
+    moved, pick2 = _non_finite_soup(n, 200 + n, axis)
+    moved = moved[perm]
+    inv = np.argsort(perm)
+    touched = np.unique(np.concatenate([inv[pick], inv[pick2]]))
+    patched = t.copy()
+    patched[touched] = moved[touched]
+    with np.errstate(all="ignore"):
+        sparse, full = scene.refit_bvh(nodes, patched, touched=touched), scene.refit_bvh(nodes, patched)
+    assert _same_with_nan_in_place(full, _slow_refit(nodes, patched))
+    assert _same_with_nan_in_place(sparse, full)  # the boxes were tight: the sparse refit is the full one
+
+
+def test_finite_triangles_refit_to_the_bytes_of_plain_min_and_max():
+    """... and without a NaN nothing changed: the boxes are ndarray.min / max and np.minimum / np.maximum of before, zeros of either sign included"""
+    tris, _ = scene.heightfield_scene(16)
+    tris = tris.copy()
+    tris[::5, 0] = -0.0
+    tris[1::7, 1] = 0.0
+    tris[2::9, 6] = np.inf
+    nodes, perm = scene.build_lbvh(tris)
+    t = tris[perm]
+    v = t.reshape(-1, 4, 4)[:, :3, :3]
+    tlo, thi = v.min(axis=1), v.max(axis=1)
+    old = nodes.copy()
+    for i in reversed(range(len(old))):  # breadth first: children behind their parent
+        f, c = int(old["first"][i]), int(old["count"][i])
+        if c > 0:
+            lo, hi = tlo[f], thi[f]
+            for k in range(1, c):
+                lo, hi = np.minimum(lo, tlo[f + k]), np.maximum(hi, thi[f + k])
+        else:
+            lo, hi = np.minimum(old["bounds"][f][0::2], old["bounds"][f + 1][0::2]), np.maximum(old["bounds"][f][1::2], old["bounds"][f + 1][1::2])
+        old["bounds"][i][0::2], old["bounds"][i][1::2] = lo, hi
+    assert scene.refit_bvh(nodes, t).tobytes() == old.tobytes()
+    pos = np.arange(0, t.shape[0], 3)
+    assert scene.refit_bvh(nodes, t, touched=pos).tobytes() == old.tobytes()

@@ -194,3 +194,25 @@ def test_the_depth_rule(k):
     assert full[2]["median_splits"] == 0
     # a median split halves: below level k the tree is balanced, leaves of <= 8
     assert info["height"] <= k + int(np.ceil(np.log2(2000))) + 1
+
+
+def infinite_axis(n=12):
+    """n triangles whose x coordinates are all +inf, y falling with the index, z constant"""
+    p = np.zeros((n, 3, 3), np.float32)
+    p[:, :, 0] = np.inf
+    p[:, :, 1] = (np.arange(n, 0, -1, dtype=np.float32) * 1.5)[:, None] + np.array([0.25, 0.5, 0.75], np.float32)
+    p[:, :, 2] = np.array([1.25, 1.5, 1.75], np.float32)
+    with np.errstate(all="ignore"):
+        return scene.make_triangles(p, 0)
+
+
+def test_a_low_side_of_nothing_but_infinity_is_flt_max_as_in_the_hosts_box():
+    """bvh_builder.cpp's Box starts at +-FLT_MAX and takes std::min / std::max: the centroid bounds of a node whose x centroids are all +inf are [FLT_MAX, +inf],
+    extent +inf, so x is the widest axis and the median split sorts by (x: all equal, index): the left child takes the first half of the caller's order.  With
+    lo = +inf the extent would be a NaN, y the widest axis, and the left child the LAST half (y falls with the index)."""
+    tris = infinite_axis()
+    with np.errstate(all="ignore"):
+        nodes, perm, info = build_sah(tris)
+    assert info["median_splits"] >= 1 and nodes[0]["count"] == 0
+    left = nodes[nodes[0]["first"]]
+    assert left["count"] == 6 and sorted(perm[left["first"]: left["first"] + 6].tolist()) == [0, 1, 2, 3, 4, 5]

@@ -57,7 +57,8 @@ extern "C" {
                                      reported, and past a limit a rebuild by the builder that made the tree.  Still 8, no new symbol: the count
                                      RVPT_HIP_NODES_UPDATE_SPARSE with `nodes` pointing at a list of triangle indices — until then an error on brute-force
                                      contexts and a read past the list on BVH contexts — is the SPARSE UPDATE: the listed triangles move, only the boxes on
-                                     their paths to the root are recomputed */
+                                     their paths to the root are recomputed.  Still 8, no new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_RAY_HITS (2) —
+                                     until then the "unknown format" error — is a RAY QUERY: `dst` holds rvpt_ray_hit records, rays in and hits out, in place */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -145,6 +146,15 @@ typedef struct rvpt_camera_data {
 #define RVPT_HIP_FORMAT_RGBA32F 0     /* float radiance running mean, alpha 0            */
 #define RVPT_HIP_FORMAT_RGBA8_UNORM 1 /* clamp+quantise of the above (reference image format,
                                          compute_pass.comp:41-42)                        */
+#define RVPT_HIP_FORMAT_RAY_HITS 2    /* dst: rvpt_ray_hit[dst_bytes / 48], in and out (RAY QUERIES at rvpt_hip_read) */
+#define RVPT_HIP_RAY_ANY_HIT 0x1u     /* per ray: stop at the first accepted triangle    */
+
+/* One ray of a query and its answer (48 B = three float4; no reference counterpart: the reference traces only its camera's paths). */
+typedef struct rvpt_ray_hit {
+    float org[3]; float tmax;        /* in: the interval is (0, tmax); +inf = the reference's */
+    float dir[3]; uint32_t flags;    /* in: 0 or RVPT_HIP_RAY_ANY_HIT; other bits reserved, ignored */
+    float t; uint32_t prim; float u; float v;   /* out */
+} rvpt_ray_hit;
 
 /* Image tiles are RVPT_HIP_TILE x RVPT_HIP_TILE pixels — the footprint of one reference
  * work-group (compute_pass.comp:27).  The tile at (tx, ty) of the tiles_x-wide tile grid has slot
@@ -368,7 +378,32 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  * device, and the rule that rank 0 takes part in the exchange before it reports its own bad argument stays.  `dst` need only be 4-byte aligned.  The
  * call still implies rvpt_hip_wait and returns only after the context's stream has finished writing `dst`: the caller may then read it from any stream
  * of its own.  dst_bytes too small is RVPT_HIP_ERR_SIZE, device memory of another GPU RVPT_HIP_ERR_INVALID (the message names both devices), so is
- * device memory that is not 4-byte aligned; in every such case `dst` is untouched. */
+ * device memory that is not 4-byte aligned; in every such case `dst` is untouched.
+ *
+ * RAY QUERIES — closest and any hit for the caller's own rays, in place:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_RAY_HITS, records, n * sizeof(rvpt_ray_hit));
+ *
+ * `dst` then holds n rvpt_ray_hit records: each comes in as a ray (org, tmax, dir, flags) and goes out as a hit (t, prim, u, v).  The in fields are never written.
+ * - THE ORDER A QUERY WALKS.  BVH contexts (RVPT_HIP_TRAVERSAL_BVH and RVPT_HIP_TRAVERSAL_BVH_ORDERED alike): intersect_bvh of the reference
+ *   (intersection.glsl:361-413) — left child first, closest-t starts at tmax, a triangle is accepted iff 0 < t < closest, 0 < u, 0 < v and u + v < 1.  Brute-force
+ *   contexts: triangles 0 .. n-1 in stored order with the same shrinking interval.  A query never uses the nearer-child-first order: its answer is defined by one
+ *   order per kind of context, not by a create flag.  `dir` need not be normalised, t is in units of `dir`; zero components of `dir` get what the arithmetic
+ *   gives (1.0f / 0), as they do in a frame.
+ * - WHAT A RECORD HOLDS ON RETURN.  Closest hit: t is the accepted distance, u and v the two values the accepting test computed, prim the triangle.  With
+ *   RVPT_HIP_RAY_ANY_HIT: the same fields for the FIRST triangle accepted in that order; the walk stops there.  Miss: prim = 0xFFFFFFFF, t = the bits of tmax as
+ *   given, u = v = 0.  A ray with a non-finite component in org or dir is a miss, decided before the walk; so is a tmax that is NaN, zero or negative.
+ * - THE NUMBERING OF prim follows the order the plain update form takes on this context: the stored order (the leaf order the caller uploaded) after an
+ *   ordinary upload, the CALLER'S order after a build form (through the stored permutation).
+ * - The call needs a scene — before any full upload it is RVPT_HIP_ERR_INVALID; the empty scene answers every ray with a miss — and no rvpt_hip_set_frame.
+ *   dst_bytes must be a multiple of 48, else RVPT_HIP_ERR_INVALID; dst_bytes == 0 is a successful no-op; fewer than 2^32 records per call.
+ * - `dst` is host memory or device memory of the context's GPU, classified as for frames.  Device memory must be 16-byte aligned, else RVPT_HIP_ERR_INVALID;
+ *   another GPU's memory is RVPT_HIP_ERR_INVALID naming both devices.  In every error case `dst` is untouched.  Host records go through a staging buffer the
+ *   context grows; device records never visit the host, and the call returns after the context's stream has finished writing them.
+ * - The call is LOCAL: with a communicator it is not collective and touches no peer.  Every rank holds the whole scene, and any rank answers.
+ * - It implies rvpt_hip_wait, as every read does, and leaves untouched the accumulator, rvpt_hip_get_timing, rvpt_hip_get_stats, rvpt_hip_get_launch_info,
+ *   rvpt_hip_get_cull_info, the frame counter, and rvpt_hip_last_error on success: a frame dispatched after a query is bit for bit the frame dispatched without it.
+ * DESIGN.md 5.13 has the kernels and what was measured (profiles/ray_queries.txt). */
 int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes);
 
 /* ---- multi-GPU: one RCCL communicator over the tile_world ranks of a partitioned image (no reference counterpart: the

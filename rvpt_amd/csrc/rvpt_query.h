@@ -1,0 +1,47 @@
+// rvpt_query.h — ray queries (include/rvpt_hip.h: RVPT_HIP_FORMAT_RAY_HITS): closest and any hit for a caller's rays, in place.  The kernels live in
+// rvpt_query.hip; rvpt_abi.hip validates, stages host records and owns the buffers.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace rv {
+
+// Which walk answers a context's queries (one order per kind of context, never the nearer-child-first order):
+//   Wide   — intersect_bvh (intersection.glsl:361-413) over the 4-wide form of the tree, where the context holds one (rvpt_bvh4.hip's per-lane walk)
+//   Binary — the same traversal over the binary nodes: heads that do not pack, a wide stack past 4096 slots, the laboratory's caller-layout knob
+//   Brute  — triangles 0 .. n-1 in stored order (brute-force contexts, and the empty scene of any context)
+enum class QueryKind : uint32_t { Wide = 0, Binary = 1, Brute = 2 };
+
+constexpr uint32_t kQueryRecordBytes = 48;   // sizeof(rvpt_ray_hit): three float4
+constexpr uint32_t kQueryLdsLevels = 8;      // stack slots per lane kept in LDS (16 KiB per work-group); deeper ones go to one global column per thread and level
+constexpr uint32_t kQueryTopNodes = 64;      // wide nodes from the top of the (breadth-first) tree copied into LDS: 8 KiB
+constexpr uint32_t kQueryTileTris = 512;     // prepared triangles per LDS tile of the brute-force kernel: 32 KiB
+constexpr size_t kQueryStackMaxBytes = size_t(256) << 20;  // the global part of the stack never takes more: the persistent grid shrinks instead
+
+struct QueryScene {
+    QueryKind kind;
+    const float4 *prep;    // n_tris x 4 float4, prepared triangles
+    const float4 *nodes;   // binary nodes, 2 float4 each (Wide: the root's box; Binary: the tree)
+    const float4 *wide;    // Wide: 8 float4 per node
+    const uint32_t *perm;  // non-null: prim = perm[stored index] (the caller's numbering after a build form)
+    uint32_t n_tris, n_wide, head_shift;
+    uint32_t stack_levels;  // slots a walk can hold at once (Wide: wide_stack_levels; Binary: the tree's height)
+};
+
+struct QueryPlan {
+    uint32_t grid;         // work-groups of kBlock threads
+    uint32_t lds_levels;   // stack slots per lane in LDS
+    uint32_t top_nodes;    // Wide: nodes copied into LDS
+    size_t lds_bytes;      // dynamic LDS per work-group
+    size_t stack_words;    // uint32 words of the global part of the stack (0: none); the launch also needs one claim word, which precedes them
+};
+
+// The launch shape for n records: a persistent grid sized from occupancy for the tree walks (the overflow stack is bounded by the grid, not by n), one
+// work-group per 256 records for the brute-force kernel.
+hipError_t query_plan(const QueryScene &scene, uint32_t n, int num_cus, QueryPlan *plan);
+// Answers records[0 .. n) in place on `stream`.  `scratch` holds 64 words (the first is the claim counter, zeroed here) followed by plan.stack_words words.
+hipError_t query_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n);
+
+}  // namespace rv

@@ -1,0 +1,357 @@
+// rvpt_query.hip — ray queries (include/rvpt_hip.h: RVPT_HIP_FORMAT_RAY_HITS): a record comes in as a ray and goes out as a hit, in place.
+//
+// The walks are the frame kernels' with the path tracer taken out: the same slab test, the same triangle test, the same order (rvpt_device.h), so a query's
+// answer is the closest_t / hit pair a frame's segment along that ray would shade — the reference's intersect_bvh (intersection.glsl:361-413: left child first,
+// the interval shrinking with every accept) on BVH contexts, triangles 0 .. n-1 in stored order on brute-force contexts.  What a query adds: the interval starts
+// at the record's tmax instead of +inf; a record with the any-hit bit stops at the FIRST triangle that order accepts; u and v of the accepting test go out.
+//
+// One ray per lane.  The tree walks run on a PERSISTENT grid sized from occupancy whose waves claim runs of 64 consecutive records: the part of the traversal
+// stack that does not fit LDS is one global column per thread of the grid and level, bounded by the grid and not by the number of rays.  No camera packets: a
+// caller's rays have no common origin.  A record is three float4; only the third (the out fields) is stored.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "rvpt_device.h"
+#include "rvpt_query.h"
+
+namespace rv {
+
+namespace {
+
+constexpr uint32_t kNoPrim = 0xFFFFFFFFu;
+constexpr uint32_t kRayAnyHit = 0x1u;  // RVPT_HIP_RAY_ANY_HIT
+
+struct QueryArgs {
+    const float4 *prep, *nodes, *wide;
+    const uint32_t *perm;
+    float4 *records;
+    uint32_t n, n_runs;          // records, runs of 64 records
+    uint32_t *counter;           // the next run to claim (0 at launch)
+    uint32_t *stack_overflow;    // [stack_levels - lds_levels][2][threads of the grid]
+    uint32_t n_tris, head_shift, stack_levels, lds_levels, top_nodes;
+};
+
+struct QueryRay {
+    f3 o, d;
+    uint32_t tmax_bits;
+    bool any, valid;
+};
+
+__device__ __forceinline__ bool finite_(const float x) { return __builtin_fabsf(x) < kInf; }  // false for NaN and +-inf
+
+// A record's in fields.  A ray with a non-finite component is a miss before any walk; so is a tmax that is NaN, zero or negative (the interval (0, tmax) is empty).
+__device__ __forceinline__ QueryRay load_ray(const float4 *records, const size_t r, const bool live)
+{
+    QueryRay q;
+    const float4 a = live ? records[3 * r + 0] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 b = live ? records[3 * r + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+    q.o = mk(a.x, a.y, a.z);
+    q.d = mk(b.x, b.y, b.z);
+    q.tmax_bits = __float_as_uint(a.w);
+    q.any = (__float_as_uint(b.w) & kRayAnyHit) != 0u;
+    q.valid = live && finite_(a.x) && finite_(a.y) && finite_(a.z) && finite_(b.x) && finite_(b.y) && finite_(b.z) && a.w > 0.0f;
+    return q;
+}
+
+// A record's out fields.  u and v are recomputed for the winning triangle with test_triangle's own expression (the same operations on the same operands: the
+// same bits the accepting test had), which is cheaper than carrying two more registers through the walk.
+__device__ __forceinline__ void store_hit(float4 *records, const size_t r, const QueryRay &q, const float4 *prep, const uint32_t *perm, const float closest,
+                                          const uint32_t hit)
+{
+    float4 out = make_float4(__uint_as_float(q.tmax_bits), __uint_as_float(kNoPrim), 0.0f, 0.0f);
+    if (hit != kNoPrim) {
+        const v4f *tp = reinterpret_cast<const v4f *>(prep) + 4 * static_cast<size_t>(hit);
+        const PrepTri t = unpack(tp[0], tp[1], tp[2], tp[3]);
+        const float tt = div_dots(dot(t.v0 - q.o, t.n), dot(q.d, t.n));
+        const f3 p0 = fma3(q.d, tt, q.o) - t.v0;
+        const float b0 = dot(p0, t.e0);
+        const float b1 = dot(p0, t.e1);
+        const float u = t.inv_det * fma_(t.a01, b1, t.a00 * b0);
+        const float v = t.inv_det * fma_(t.a11, b1, t.a01 * b0);
+        out = make_float4(closest, __uint_as_float(perm ? perm[hit] : hit), u, v);
+    }
+    records[3 * r + 2] = out;
+}
+
+// A leaf's triangles in index order; an any-hit ray stops at the first accept (returns true: the ray is finished)
+__device__ __forceinline__ bool test_leaf(const v4f *prep, const uint32_t first, const uint32_t count, const QueryRay &q, float &closest, uint32_t &hit)
+{
+    for (uint32_t i = first; i < first + count; ++i) {
+        const v4f *tp = prep + 4 * static_cast<size_t>(i);
+        test_triangle(unpack(tp[0], tp[1], tp[2], tp[3]), q.o, q.d, i, closest, hit);
+        if (q.any && hit != kNoPrim) return true;
+    }
+    return false;
+}
+
+// intersect_run<4> (rvpt_device.h) with the query's rider: `active` masks the accept, and an any-hit lane leaves after its first one
+__device__ __forceinline__ void accept_query(const OpenTest r, const uint32_t index, const bool any, float &closest, uint32_t &hit, bool &active)
+{
+    const bool accept = (r.m > 0.0f) & (r.s < 1.0f) & (r.tt < closest) & active;
+    if (ballot(accept) != 0) {
+        closest = accept ? r.tt : closest;
+        hit = accept ? index : hit;
+        active = active && !(accept && any);
+    }
+}
+__device__ __forceinline__ void query_run(const v4f *src, const uint32_t index0, const uint32_t count, const QueryRay &q, float &closest, uint32_t &hit, bool &active)
+{
+    uint32_t i = 0;
+    for (; i + 4 <= count; i += 4) {
+        OpenTest r[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint32_t j = i + k;
+            r[k] = test_triangle_open(unpack(src[4 * j + 0], src[4 * j + 1], src[4 * j + 2], src[4 * j + 3]), q.o, q.d);
+        }
+        asm volatile("" ::"v"(r[0].tt), "v"(r[0].m), "v"(r[0].s), "v"(r[1].tt), "v"(r[1].m), "v"(r[1].s), "v"(r[2].tt), "v"(r[2].m), "v"(r[2].s), "v"(r[3].tt),
+                     "v"(r[3].m), "v"(r[3].s));
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) accept_query(r[k], index0 + i + k, q.any, closest, hit, active);
+    }
+    for (; i < count; ++i)
+        accept_query(test_triangle_open(unpack(src[4 * i + 0], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]), q.o, q.d), index0 + i, q.any, closest, hit, active);
+}
+
+// the next run of 64 records for this wave (wave-uniform)
+__device__ __forceinline__ uint32_t claim_run(uint32_t *counter, const uint32_t lane)
+{
+    uint32_t run = 0;
+    if (lane == 0) run = atomicAdd(counter, 1u);
+    return __builtin_amdgcn_readlane(run, 0);
+}
+
+}  // namespace
+
+// rvpt_bvh4.hip's per-lane walk: slab_entry at the root, four slab_child tests per wide node, on with the first child that passes, the others stacked (the last
+// first) with their entry distances and packed heads, popped with closest >= entry.  LDS: [stack: lds_levels x 2 words x kBlock][root: 2 float4][top_nodes wide nodes]
+__global__ __launch_bounds__(kBlock) void query_bvh4(const QueryArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const uint32_t lds_levels = a.lds_levels;
+    float4 *lds_root = reinterpret_cast<float4 *>(lds_stack + 2u * lds_levels * kBlock);
+    float4 *lds_top = lds_root + 2;
+    const uint32_t top_nodes = a.top_nodes;
+    if (threadIdx.x < 2u) lds_root[threadIdx.x] = a.nodes[threadIdx.x];
+    for (uint32_t i = threadIdx.x; i < 8u * top_nodes; i += kBlock) lds_top[i] = a.wide[i];
+    __syncthreads();
+    const v4f *prep = reinterpret_cast<const v4f *>(a.prep);
+    const uint32_t top_level = a.stack_levels - 1u;
+    const uint32_t head_shift = a.head_shift;
+    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
+    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
+    const uint32_t lane = lane_id();
+
+    for (;;) {
+        const uint32_t run = claim_run(a.counter, lane);
+        if (run >= a.n_runs) break;
+        const size_t r = static_cast<size_t>(run) * 64u + lane;
+        const bool live = r < a.n;
+        const QueryRay q = load_ray(a.records, r, live);
+        float closest = __uint_as_float(q.tmax_bits);
+        uint32_t hit = kNoPrim, sp = 0, cur = 0, leaf_first = 0, leaf_count = 0;
+        const f3 inv = mk(1.0f / q.d.x, 1.0f / q.d.y, 1.0f / q.d.z);
+        bool walking = q.valid;
+        {
+            float entry;  // the root is a node like any other: its own box first (intersection.glsl:369-380)
+            walking = walking && slab_entry(q.o, inv, lds_root[0], lds_root[1], closest, entry);
+        }
+        auto enter = [&](const uint32_t head) {  // head = first | count << head_shift (leaf, count > 0) or a wide node index (count 0)
+            const uint32_t first = head & ((1u << head_shift) - 1u), count = head >> head_shift;
+            cur = first;
+            leaf_first = first;
+            leaf_count = count;
+        };
+        auto push = [&](const float entry, const uint32_t head) {
+            const uint32_t at = min(sp, top_level);  // the host sized the stack from the wide tree: sp never passes top_level; the clamp keeps a wrong size inside the memory
+            if (at < lds_levels) {
+                lds_stack[(2u * at + 0u) * kBlock + threadIdx.x] = __float_as_uint(entry);
+                lds_stack[(2u * at + 1u) * kBlock + threadIdx.x] = head;
+            } else {
+                ovf[(2u * (at - lds_levels) + 0u) * ovf_stride] = __float_as_uint(entry);
+                ovf[(2u * (at - lds_levels) + 1u) * ovf_stride] = head;
+            }
+            sp = at + 1u;
+        };
+        while (ballot(walking) != 0) {  // (any hit: a lane that accepted has left; the loop ends for the wave when none walks)
+            bool need_pop = false;
+            if (walking && leaf_count == 0) {
+                const float4 *node = cur < top_nodes ? lds_top + 8u * cur : a.wide + 8u * static_cast<size_t>(cur);
+                const float4 minx = node[0], maxx = node[1], miny = node[2], maxy = node[3], minz = node[4], maxz = node[5], hq = node[6];
+                const uint32_t hd0 = __float_as_uint(hq.x), hd1 = __float_as_uint(hq.y), hd2 = __float_as_uint(hq.z), hd3 = __float_as_uint(hq.w);
+                float e0, e1, e2, e3;
+                const bool h0 = slab_child(q.o, inv, minx.x, maxx.x, miny.x, maxy.x, minz.x, maxz.x, closest, e0);  // (a wide node has at least two children)
+                const bool h1 = slab_child(q.o, inv, minx.y, maxx.y, miny.y, maxy.y, minz.y, maxz.y, closest, e1);
+                const bool h2 = slab_child(q.o, inv, minx.z, maxx.z, miny.z, maxy.z, minz.z, maxz.z, closest, e2) && hd2 != kWideEmpty;
+                const bool h3 = slab_child(q.o, inv, minx.w, maxx.w, miny.w, maxy.w, minz.w, maxz.w, closest, e3) && hd3 != kWideEmpty;
+                if (h3 && (h0 || h1 || h2)) push(e3, hd3);
+                if (h2 && (h0 || h1)) push(e2, hd2);
+                if (h1 && h0) push(e1, hd1);
+                if (h0 || h1 || h2 || h3)
+                    enter(h0 ? hd0 : (h1 ? hd1 : (h2 ? hd2 : hd3)));
+                else
+                    need_pop = true;
+            }
+            if (walking && leaf_count > 0) {
+                if (test_leaf(prep, leaf_first, leaf_count, q, closest, hit)) walking = false;
+                leaf_count = 0;
+                need_pop = true;
+            }
+            if (walking && need_pop) {
+                bool found = false;
+                while (sp > 0 && !found) {
+                    sp -= 1;
+                    uint32_t entry_bits, cand;
+                    if (sp < lds_levels) {
+                        entry_bits = lds_stack[(2u * sp + 0u) * kBlock + threadIdx.x];
+                        cand = lds_stack[(2u * sp + 1u) * kBlock + threadIdx.x];
+                    } else {
+                        entry_bits = ovf[(2u * (sp - lds_levels) + 0u) * ovf_stride];
+                        cand = ovf[(2u * (sp - lds_levels) + 1u) * ovf_stride];
+                    }
+                    if (closest >= __uint_as_float(entry_bits)) {  // the reference's box test at the visit (rvpt_bvh4.hip's header comment)
+                        enter(cand);
+                        found = true;
+                    }
+                }
+                walking = found;
+            }
+        }
+        if (live) store_hit(a.records, r, q, a.prep, a.perm, closest, hit);
+    }
+}
+
+// intersect_bvh as the reference writes it, over the binary nodes (children of an inner node at first, first + 1): pop a node, test its box against the interval
+// of that moment, a leaf's triangles in order, an inner node's right child stacked and its left child next.  One word per stack slot (the node index); the LDS
+// part uses the first word of query_bvh4's two-word slots, the global part the first half of its columns.
+__global__ __launch_bounds__(kBlock) void query_bvh2(const QueryArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const uint32_t lds_levels = a.lds_levels;
+    const v4f *prep = reinterpret_cast<const v4f *>(a.prep);
+    const uint32_t top_level = a.stack_levels - 1u;
+    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
+    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
+    const uint32_t lane = lane_id();
+
+    for (;;) {
+        const uint32_t run = claim_run(a.counter, lane);
+        if (run >= a.n_runs) break;
+        const size_t r = static_cast<size_t>(run) * 64u + lane;
+        const bool live = r < a.n;
+        const QueryRay q = load_ray(a.records, r, live);
+        float closest = __uint_as_float(q.tmax_bits);
+        uint32_t hit = kNoPrim, sp = 0, cur = 0;
+        const f3 inv = mk(1.0f / q.d.x, 1.0f / q.d.y, 1.0f / q.d.z);
+        bool walking = q.valid;
+        while (ballot(walking) != 0) {
+            if (walking) {
+                const float4 n0 = a.nodes[2u * static_cast<size_t>(cur)], n1 = a.nodes[2u * static_cast<size_t>(cur) + 1u];
+                const uint32_t first = __float_as_uint(n0.x), count = __float_as_uint(n0.y);
+                bool pop = true;
+                float entry;
+                if (slab_entry(q.o, inv, n0, n1, closest, entry)) {
+                    if (count > 0) {
+                        if (test_leaf(prep, first, count, q, closest, hit)) walking = false;
+                    } else {
+                        const uint32_t at = min(sp, top_level);  // (the tree's height bounds the pushes of a root-to-leaf path; the clamp as in query_bvh4)
+                        if (at < lds_levels)
+                            lds_stack[at * kBlock + threadIdx.x] = first + 1u;
+                        else
+                            ovf[(at - lds_levels) * ovf_stride] = first + 1u;
+                        sp = at + 1u;
+                        cur = first;
+                        pop = false;
+                    }
+                }
+                if (walking && pop) {
+                    if (sp == 0) {
+                        walking = false;
+                    } else {
+                        sp -= 1;
+                        cur = sp < lds_levels ? lds_stack[sp * kBlock + threadIdx.x] : ovf[(sp - lds_levels) * ovf_stride];
+                    }
+                }
+            }
+        }
+        if (live) store_hit(a.records, r, q, a.prep, a.perm, closest, hit);
+    }
+}
+
+// Brute force: a work-group answers 256 records and streams the prepared triangles through LDS in tiles of kQueryTileTris; every lane runs over each tile in
+// index order.  The loop ends for the work-group when no lane is left (every ray invalid, or every any-hit ray served).
+__global__ __launch_bounds__(kBlock) void query_brute(const QueryArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tile[];
+    const size_t r = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const bool live = r < a.n;
+    const QueryRay q = load_ray(a.records, r, live);
+    float closest = __uint_as_float(q.tmax_bits);
+    uint32_t hit = kNoPrim;
+    bool active = q.valid;
+    for (uint32_t base = 0; base < a.n_tris; base += kQueryTileTris) {
+        const uint32_t count = min(kQueryTileTris, a.n_tris - base);
+        for (uint32_t i = threadIdx.x; i < 4u * count; i += kBlock) lds_tile[i] = a.prep[4u * static_cast<size_t>(base) + i];
+        __syncthreads();
+        if (ballot(active) != 0) query_run(reinterpret_cast<const v4f *>(lds_tile), base, count, q, closest, hit, active);
+        if (__syncthreads_or(active ? 1 : 0) == 0) break;  // (also the barrier in front of the next tile's stores)
+    }
+    if (live) store_hit(a.records, r, q, a.prep, a.perm, closest, hit);
+}
+
+hipError_t query_plan(const QueryScene &scene, const uint32_t n, const int num_cus, QueryPlan *plan)
+{
+    QueryPlan p{};
+    if (scene.kind == QueryKind::Brute) {
+        p.grid = std::max<uint32_t>(1u, static_cast<uint32_t>((static_cast<uint64_t>(n) + kBlock - 1u) / kBlock));
+        p.lds_bytes = static_cast<size_t>(kQueryTileTris) * 64u;
+        *plan = p;
+        return hipSuccess;
+    }
+    const uint32_t levels = std::max<uint32_t>(1u, scene.stack_levels);
+    p.lds_levels = std::min(levels, kQueryLdsLevels);
+    p.top_nodes = scene.kind == QueryKind::Wide ? std::min(scene.n_wide, kQueryTopNodes) : 0u;
+    p.lds_bytes = static_cast<size_t>(p.lds_levels) * kBlock * 2u * sizeof(uint32_t) + 2u * sizeof(float4) + static_cast<size_t>(p.top_nodes) * 128u;
+    int per_cu = 0;
+    const void *kernel = scene.kind == QueryKind::Wide ? reinterpret_cast<const void *>(query_bvh4) : reinterpret_cast<const void *>(query_bvh2);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, p.lds_bytes);
+    if (e != hipSuccess) return e;
+    const uint64_t runs = (static_cast<uint64_t>(n) + 63u) / 64u;
+    const uint64_t want = (runs + kBlock / 64u - 1u) / (kBlock / 64u);  // a work-group's four waves claim a run each
+    p.grid = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>(want, static_cast<uint64_t>(std::max(per_cu, 1)) * static_cast<uint64_t>(std::max(num_cus, 1)))));
+    const size_t column_words = static_cast<size_t>(2u) * (levels - p.lds_levels) * kBlock;  // per work-group
+    while (p.grid > 1u && column_words * p.grid * sizeof(uint32_t) > kQueryStackMaxBytes) p.grid = (p.grid + 1u) / 2u;
+    p.stack_words = column_words * p.grid;
+    *plan = p;
+    return hipSuccess;
+}
+
+hipError_t query_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, const uint32_t n)
+{
+    if (n == 0) return hipSuccess;
+    QueryArgs a{};
+    a.prep = scene.prep, a.nodes = scene.nodes, a.wide = scene.wide, a.perm = scene.perm;
+    a.records = static_cast<float4 *>(records);
+    a.n = n;
+    a.n_runs = static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u);
+    a.counter = scratch;
+    a.stack_overflow = scratch + 64;
+    a.n_tris = scene.n_tris, a.head_shift = scene.head_shift;
+    a.stack_levels = std::max<uint32_t>(1u, scene.stack_levels);
+    a.lds_levels = plan.lds_levels, a.top_nodes = plan.top_nodes;
+    if (scene.kind == QueryKind::Brute) {
+        hipLaunchKernelGGL(query_brute, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
+        return hipGetLastError();
+    }
+    const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    if (scene.kind == QueryKind::Wide)
+        hipLaunchKernelGGL(query_bvh4, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
+    else
+        hipLaunchKernelGGL(query_bvh2, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace rv

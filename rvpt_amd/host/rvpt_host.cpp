@@ -385,6 +385,27 @@ std::vector<uint8_t> RVPT::read_frame_rgba8()
 }
 bool RVPT::read_frame_device(void *dst, size_t bytes, int format) { return check(backend_.read(ctx_, format, dst, bytes), "rvpt_hip_read"); }
 
+bool RVPT::trace_rays(std::vector<rvpt_ray_hit> &records)
+{
+    if (!ctx_) {
+        error_ = "trace_rays before initialize()";
+        return false;
+    }
+    if (!check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_HITS, records.data(), records.size() * sizeof(rvpt_ray_hit)), "rvpt_hip_read")) return false;
+    if (!device_built_)  // the library numbered the leaf order it was given
+        for (rvpt_ray_hit &r : records)
+            if (r.prim < order_.size()) r.prim = order_[r.prim];
+    return true;
+}
+bool RVPT::trace_rays_device(void *records, size_t n)
+{
+    if (!ctx_) {
+        error_ = "trace_rays_device before initialize()";
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_HITS, records, n * sizeof(rvpt_ray_hit)), "rvpt_hip_read");
+}
+
 // ---- main.cpp:12-62 ---------------------------------------------------------------------------------------
 long load_model(RVPT &rvpt, const std::string &path, int material_id, std::string *error)
 {

@@ -164,6 +164,13 @@ public:
     // RVPT_HIP_FORMAT_RGBA32F or RVPT_HIP_FORMAT_RGBA8_UNORM; the bytes are those read_frame() / read_frame_rgba8() return, and `dst` may be read from any
     // stream once the call has returned.  (A host pointer is read_frame() into the caller's own memory.)
     bool read_frame_device(void *dst, size_t bytes, int format);
+    // Ray queries (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS; include/rvpt_hip.h: RAY QUERIES): every record comes in as a ray (org, tmax, dir, flags) and goes
+    // out as a hit (t, prim, u, v), in place.  After initialize(); no update() is needed, a query has no camera.  prim numbers the triangles in the order they
+    // were ADDED, as update_triangles' indices do (after a host build the library's leaf-order answer goes through the build's primitive indices).
+    bool trace_rays(std::vector<rvpt_ray_hit> &records);
+    // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host: prim then stays as the LIBRARY numbers
+    // it — the leaf order after a host build (sorted_triangles()), the added order after a device build.  `records` may be read from any stream on return.
+    bool trace_rays_device(void *records, size_t n);
     const std::string &last_error() const { return error_; }
     // the backend context, e.g. to join several RVPT objects (one per GPU, tile_rank i of n) into one RCCL group with
     // rvpt_hip_comm_init_all; read_frame() on rank 0's object is then the gather of the whole image

@@ -25,6 +25,11 @@ COUNT_SEGMENTS, KERNEL_SIMPLE, TIMING, ACCUM_UNORM8 = 0x4, 0x8, 0x10, 0x20
 BVH_PER_LANE = 0x400  # BVH contexts: no camera packets, every segment walks the tree per lane (rounds 1-3's kernel)
 BRUTE_MIXED_PACKETS = 0x200  # brute-force contexts: round 2's mixed-packet frame kernel instead of the packet kernel (rvpt_packets.hip)
 FORMAT_RGBA32F, FORMAT_RGBA8_UNORM = 0, 1
+FORMAT_RAY_HITS = 2  # RVPT_HIP_FORMAT_RAY_HITS: rvpt_hip_read answers ray queries, `dst` holds RAY_HIT_DTYPE records (Context.trace_rays)
+RAY_ANY_HIT = 0x1  # RVPT_HIP_RAY_ANY_HIT: a record's flag — stop at the first accepted triangle
+NO_PRIM = 0xFFFFFFFF  # a record's prim after a miss
+# rvpt_ray_hit (48 B): org, tmax, dir, flags come in, t, prim, u, v go out
+RAY_HIT_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("flags", "<u4"), ("t", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4")])
 CULL_ROW_BOXES = 0x100  # Context.cull_info: the launch rode with the row boxes (rvpt_abi.hip: kCullRowBoxes)
 CULL_SKY_LIST = 0x80  # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
 TILE = 16
@@ -594,6 +599,46 @@ class Context:
         _check(self._L.rvpt_hip_read(self._h, fmt, ptr, nbytes), self._h, self._L)
         del keep
         return dst
+
+    def trace_rays(self, org, dir, tmax=math.inf, any_hit=False) -> np.ndarray:
+        """Closest (any_hit: first accepted) hit of the rays org[n, 3] + t dir[n, 3], 0 < t < tmax, against the uploaded scene — include/rvpt_hip.h: RAY QUERIES
+        has the order a query walks and the numbering of prim.  tmax and any_hit are scalars or one value per ray.  Returns RAY_HIT_DTYPE[n]: t, prim, u, v of
+        the hit, prim == NO_PRIM where there is none."""
+        org = np.asarray(org, dtype=np.float32).reshape(-1, 3)
+        dirv = np.asarray(dir, dtype=np.float32).reshape(-1, 3)
+        if org.shape != dirv.shape:
+            raise NativeError(ERR_INVALID, f"trace_rays: {org.shape[0]} origins, {dirv.shape[0]} directions")
+        rec = np.zeros(org.shape[0], dtype=RAY_HIT_DTYPE)
+        rec["org"], rec["dir"] = org, dirv
+        rec["tmax"] = np.asarray(tmax, dtype=np.float32)
+        rec["flags"] = np.where(np.asarray(any_hit, dtype=bool), RAY_ANY_HIT, 0).astype(np.uint32)
+        return self.trace_rays_into(rec)
+
+    def trace_rays_into(self, records):
+        """rvpt_hip_read with FORMAT_RAY_HITS in the caller's memory: `records` is a contiguous RAY_HIT_DTYPE array, or a contiguous float32 torch tensor [n, 12]
+        (48-byte records) on the host or on this context's device — resolved the way _frame_buffer resolves frames; device records never visit the host.  The
+        in fields stay as they are, the out fields are written.  Returns records."""
+        is_tensor = not isinstance(records, np.ndarray) and hasattr(records, "data_ptr")
+        if is_tensor:
+            import torch
+            if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != 12 or not records.is_contiguous():
+                raise NativeError(ERR_INVALID, f"trace_rays_into: a contiguous float32 tensor [n, 12] is needed, got {records.dtype} {tuple(records.shape)}")
+            nbytes = int(records.shape[0]) * 48
+            if records.is_cuda:
+                if records.device.index != self.device:
+                    raise NativeError(ERR_INVALID, f"trace_rays_into: the tensor lives on device {records.device.index}, the context on {self.device}")
+                torch.cuda.current_stream(records.device).synchronize()  # the library works on its own stream: what wrote the rays must have finished
+                ptr = C.c_void_p(records.data_ptr())
+            else:
+                ptr = _ptr(records.numpy())  # (shares the tensor's memory)
+        elif isinstance(records, np.ndarray):
+            if records.dtype != RAY_HIT_DTYPE or not records.flags.c_contiguous or not records.flags.writeable:
+                raise NativeError(ERR_INVALID, f"trace_rays_into: a contiguous writeable RAY_HIT_DTYPE array is needed, got {records.dtype}")
+            ptr, nbytes = _ptr(records), records.nbytes
+        else:
+            raise NativeError(ERR_INVALID, f"trace_rays_into: a numpy array or a torch tensor is needed, got {type(records).__name__}")
+        _check(self._L.rvpt_hip_read(self._h, FORMAT_RAY_HITS, ptr, nbytes), self._h, self._L)
+        return records
 
     def write_accum(self, img) -> None:
         """rvpt_hip_write_accum: restore the accumulator from a row-major RGBA32F frame — anything numpy makes float32[h, w, 4] of, or a contiguous float32

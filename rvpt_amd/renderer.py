@@ -285,6 +285,34 @@ class RVPT:
             return self._ctx.read_into(out, fmt)
         return self._ctx.read(fmt)
 
+    def trace_rays(self, org, dir, tmax=float("inf"), any_hit=False) -> np.ndarray:
+        """Ray queries against the scene as it is now (Context.trace_rays; include/rvpt_hip.h: RAY QUERIES): closest — any_hit: first accepted — hit of every ray
+        org + t dir, 0 < t < tmax.  Returns native.RAY_HIT_DTYPE records; prim numbers the triangles in the order they were ADDED (native.NO_PRIM: a miss), as
+        update_triangles' indices do.  Needs initialize(), not update(): a query has no camera."""
+        if self._ctx is None:
+            raise RuntimeError("trace_rays before initialize()")
+        rec = self._ctx.trace_rays(org, dir, tmax, any_hit)
+        if not self._device_built and rec.shape[0]:  # a host-built tree: the device numbers the leaf order it was given
+            hit = rec["prim"] != native.NO_PRIM
+            rec["prim"][hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[rec["prim"][hit]]
+        return rec
+
+    def pick(self, x: int, y: int):
+        """What is under pixel (x, y) of the current camera: (prim, t) of the closest hit along the pixel-centre ray, or None.  The ray is made HERE, on the host, from
+        scene_camera.get_data() (camera.glsl:29-51 in double, rounded to float32 once) — not by the frame kernel's float32 arithmetic: t agrees with a frame's to
+        rounding, not to the bit.  Pinhole camera only."""
+        if self.scene_camera.mode != 0:
+            raise ValueError("pick: only the pinhole camera (mode 0) has a pixel-centre ray made here")
+        if not (0 <= int(x) < self.width and 0 <= int(y) < self.height):
+            raise ValueError(f"pick: pixel ({x}, {y}) is outside the {self.width} x {self.height} frame")
+        cam = np.asarray(self.scene_camera.get_data(), dtype=np.float64)
+        m = cam[:16].reshape(4, 4).T  # column-major camera-to-world
+        cx, cy = (int(x) + 0.5) / self.width, 1.0 - (int(y) + 0.5) / self.height  # compute_pass.comp:151-156
+        d = m[:3, :3] @ np.array([cam[16] * (2.0 * cx - 1.0), 2.0 * cy - 1.0, 1.0 / np.tan(0.5 * cam[17])])
+        d /= np.linalg.norm(d)
+        rec = self.trace_rays(m[:3, 3], d)[0]
+        return None if rec["prim"] == native.NO_PRIM else (int(rec["prim"]), float(rec["t"]))
+
     def shutdown(self) -> None:
         if self._ctx is not None:
             self._ctx.close()

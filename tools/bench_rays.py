@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Ray queries (rvpt_hip_read with FORMAT_RAY_HITS; Context.trace_rays_into) measured -> profiles/ray_queries.txt.
+
+usage: tools/bench_rays.py rates [default cornell terrain]     on the GPU box: rays/s for the 1920 x 1080 pinhole camera rays of each scene — in pixel order and in a
+                                                               random permutation, from host records and from device records, closest hit and any hit with tmax =
+                                                               half the scene extent — beside two yardsticks taken in the same run: the context's own frame kernel on
+                                                               the same camera with max_bounces = 1 (one segment per sample: primaries only), in segments/s, and
+                                                               oracle.closest_hit on this CPU
+       tools/bench_rays.py queries [scene]                     a few device-record queries and nothing else: the run to put under rocprofv3
+       tools/bench_rays.py resources <parent tree>             where hipcc and a checkout of the parent commit are: VGPR, SGPR, scratch and static LDS of every frame
+                                                               kernel there and here (tools/kernel_resources.py), and of the query kernels
+Each mode rewrites its own section of profiles/ray_queries.txt and leaves the other."""
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+OUT = ROOT / "profiles" / "ray_queries.txt"
+MARK = "==== kernel resources"
+W, H = 1920, 1080
+
+
+def write_section(text, resources):
+    old = OUT.read_text() if OUT.exists() else ""
+    head, _, tail = old.partition(MARK)
+    if resources:
+        OUT.write_text(head.rstrip("\n") + ("\n\n" if head.strip() else "") + MARK + text)
+    else:
+        OUT.write_text(text.rstrip("\n") + "\n" + ("\n" + MARK + tail if tail else ""))
+
+
+def scenes(names):
+    from rvpt_amd import Camera, native, scene
+    for name in names:
+        c = Camera(W / H)
+        if name == "default":
+            tris, mats = scene.default_scene()
+            c.translation = np.array([0.0, 0.8, -1.5])
+        elif name == "cornell":
+            tris, mats = scene.cornell_scene()
+            c.translation = np.array([0.0, 2.0, -1.9])
+        else:
+            tris, mats = scene.heightfield_scene()
+            c.translation = np.array([0.0, 2.5, -5.0])
+            c.rotation = np.array([0.0, 25.0, 0.0])
+        nodes, idx = native.build_bvh(tris)
+        yield name, tris[idx], mats, nodes, c.get_data()
+
+
+def camera_records(cam, tmax=np.inf, flags=0):
+    """the pixel-centre rays of the pinhole camera `cam` (camera.glsl:29-51, float32, made on the host), in pixel order"""
+    from rvpt_amd import native
+    cam = np.asarray(cam, dtype=np.float32)
+    m = cam[:16].reshape(4, 4).T
+    x, y = np.meshgrid((np.arange(W, dtype=np.float32) + 0.5) / W, 1.0 - (np.arange(H, dtype=np.float32) + 0.5) / H)
+    u, v, w = cam[16] * (2 * x - 1), 2 * y - 1, np.float32(1.0 / np.tan(0.5 * cam[17]))
+    d = u[..., None] * m[:3, 0] + v[..., None] * m[:3, 1] + w * m[:3, 2]
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    rec = np.zeros(W * H, dtype=native.RAY_HIT_DTYPE)
+    rec["org"], rec["dir"], rec["tmax"], rec["flags"] = m[:3, 3], d.reshape(-1, 3).astype(np.float32), tmax, flags
+    return rec
+
+
+def rate(fn, n_rays, reps=7, warm=2):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    r = [n_rays / t / 1e6 for t in ts]
+    return f"median {statistics.median(r):9.1f}   min {min(r):9.1f}   max {max(r):9.1f}   Mrays/s (wall clock of the call, n {reps})"
+
+
+def rates(names):
+    import torch
+    from oracle import oracle
+    from rvpt_amd import RenderSettings, native
+    lines = ["ray queries: tools/bench_rays.py rates " + " ".join(names), f"1920 x 1080 pinhole camera rays = {W * H} records per call; one MI355X; rates are wall clock around the call (it returns after its stream has finished)", ""]
+    for name, tris, mats, nodes, cam in scenes(names):
+        ext = float(np.ptp(tris.reshape(-1, 4, 4)[:, :3, :3].reshape(-1, 3), axis=0).max())
+        lines.append(f"== {name}: {tris.shape[0]} triangles, {nodes.shape[0]} nodes, extent {ext:.2f} ==")
+        ctx = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BVH | native.COUNT_SEGMENTS)
+        ctx.upload_scene(nodes, tris, mats)
+        order = np.random.RandomState(1).permutation(W * H)
+        for what, kw in (("closest hit", {}), (f"any hit, tmax = extent / 2 = {ext / 2:.2f}", {"tmax": np.float32(ext / 2), "flags": native.RAY_ANY_HIT})):
+            pixel = camera_records(cam, **kw)
+            for oname, rec in (("pixel order", pixel), ("random permutation", np.ascontiguousarray(pixel[order]))):
+                dev = torch.from_numpy(rec.view(np.float32).reshape(-1, 12)).to("cuda:0")
+                lines.append(f"{what:36s} {oname:20s} host records    {rate(lambda: ctx.trace_rays_into(rec), W * H)}")
+                lines.append(f"{what:36s} {oname:20s} device records  {rate(lambda: ctx.trace_rays_into(dev), W * H)}")
+                got = dev.cpu().numpy().view(native.RAY_HIT_DTYPE).reshape(-1)
+                assert got.tobytes() == rec.tobytes(), "host and device records differ"
+                lines.append(f"{'':36s} {'':20s} hits: {int((rec['prim'] != native.NO_PRIM).sum())} of {W * H}")
+        # yardstick 1: the context's own frame kernel, primaries only
+        frames = 16
+        def primaries():
+            for f in range(frames):
+                ctx.set_frame(RenderSettings(max_bounces=1, aa=1, current_frame=f).pack(), cam)
+                ctx.dispatch()
+            ctx.wait()
+        primaries()
+        s0 = ctx.stats()[0]
+        t0 = time.perf_counter()
+        primaries()
+        dt = time.perf_counter() - t0
+        seg = ctx.stats()[0] - s0
+        lines.append(f"yardstick: frame kernel (variant {ctx.launch_info()[2]}), max_bounces = 1, aa = 1, {frames} one-frame launches: {seg} segments in {dt * 1e3:.2f} ms = {seg / dt / 1e6:.1f} Msegments/s")
+        ctx.close()
+        # yardstick 2: the oracle on this CPU (one call per ray; every call prepares the scene again, so few rays on the large scene)
+        n_cpu = 200 if tris.shape[0] < 100000 else 8
+        pick = camera_records(cam)[np.random.RandomState(2).randint(0, W * H, n_cpu)]
+        t0 = time.perf_counter()
+        for r in pick:
+            oracle.closest_hit(nodes, tris, oracle.TRAVERSAL_BVH, r["org"], r["dir"])
+        dt = time.perf_counter() - t0
+        lines.append(f"yardstick: oracle.closest_hit on this CPU, {n_cpu} rays, one call each (a call prepares the scene's triangles first): {n_cpu / dt:.1f} rays/s")
+        lines.append("")
+    text = "\n".join(lines)
+    print(text)
+    write_section(text, resources=False)
+
+
+def queries(names):
+    import torch
+    from rvpt_amd import native
+    for name, tris, mats, nodes, cam in scenes(names):
+        ctx = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BVH)
+        ctx.upload_scene(nodes, tris, mats)
+        dev = torch.from_numpy(camera_records(cam).view(np.float32).reshape(-1, 12)).to("cuda:0")
+        for _ in range(8):
+            ctx.trace_rays_into(dev)
+        ctx.close()
+        print(f"{name}: 8 queries of {W * H} device records done")
+
+
+def resources(parent):
+    import importlib.util
+
+    def tables(root, files=None):
+        for k in [k for k in sys.modules if k == "rvpt_amd" or k.startswith("rvpt_amd.")]:
+            del sys.modules[k]
+        sys.path.insert(0, str(root))
+        try:
+            spec = importlib.util.spec_from_file_location("kernel_resources", Path(root) / "tools" / "kernel_resources.py")
+            m = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(m)
+            return m.kernel_resources(files) if files else m.kernel_resources()
+        finally:
+            sys.path.remove(str(root))
+
+    def table(title, res):
+        out = [title, f"  {'kernel':88s} {'vgpr':>5s} {'sgpr':>5s} {'scratch':>8s} {'static_lds':>10s}"]
+        for k in sorted(res):
+            v = res[k]
+            out.append(f"  {k[:88]:88s} {v['vgpr']:5d} {v['sgpr']:5d} {v['scratch_bytes']:8d} {v['static_lds_bytes']:10d}")
+        return out
+
+    before, after = tables(parent), tables(ROOT)
+    lines = [" (tools/bench_rays.py resources <parent tree>; tools/kernel_resources.py: the compiler's own metadata) ====", ""]
+    lines += table("frame kernels, parent commit (rvpt_kernels.hip, rvpt_packets.hip, rvpt_bvh4.hip)", before) + [""]
+    lines += table("frame kernels, this commit", after) + [""]
+    lines += [f"identical: {before == after} ({len(after)} kernels)", ""]
+    lines += table("query kernels (rvpt_query.hip)", tables(ROOT, ["rvpt_query.hip"]))
+    text = "\n".join(lines) + "\n"
+    print(MARK + text)
+    write_section(text, resources=True)
+    return before == after
+
+
+if __name__ == "__main__":
+    mode = sys.argv[1] if len(sys.argv) > 1 else "rates"
+    if mode == "resources":
+        sys.exit(0 if resources(sys.argv[2]) else 1)
+    names = sys.argv[2:] or ["default", "cornell", "terrain"]
+    rates(names) if mode == "rates" else queries(names)

@@ -58,7 +58,9 @@ extern "C" {
                                      RVPT_HIP_NODES_UPDATE_SPARSE with `nodes` pointing at a list of triangle indices — until then an error on brute-force
                                      contexts and a read past the list on BVH contexts — is the SPARSE UPDATE: the listed triangles move, only the boxes on
                                      their paths to the root are recomputed.  Still 8, no new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_RAY_HITS (2) —
-                                     until then the "unknown format" error — is a RAY QUERY: `dst` holds rvpt_ray_hit records, rays in and hits out, in place */
+                                     until then the "unknown format" error — is a RAY QUERY: `dst` holds rvpt_ray_hit records, rays in and hits out, in place.  Still 8, no
+                                     new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_RAY_PATHS (3) — until then the "unknown format" error — is a
+                                     PATH QUERY: `dst` holds rvpt_ray_path records, a ray, an RNG state and a bounce budget in, integrator_Kajiya's radiance out */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -155,6 +157,16 @@ typedef struct rvpt_ray_hit {
     float dir[3]; uint32_t flags;    /* in: 0 or RVPT_HIP_RAY_ANY_HIT; other bits reserved, ignored */
     float t; uint32_t prim; float u; float v;   /* out */
 } rvpt_ray_hit;
+
+#define RVPT_HIP_FORMAT_RAY_PATHS 3   /* dst: rvpt_ray_path[dst_bytes / 48], in and out (PATH QUERIES at rvpt_hip_read) */
+#define RVPT_HIP_PATH_MAX_BOUNCES 1024u /* per path: the largest bounce budget a record may ask for */
+
+/* One path of a query and its answer (48 B = three float4; no reference counterpart: the reference traces only its camera's paths). */
+typedef struct rvpt_ray_path {
+    float org[3]; uint32_t seed;          /* in: the first segment's origin; the RNG state the path starts from */
+    float dir[3]; uint32_t max_bounces;   /* in: the first segment's direction (need not be unit); the bounce budget, 1 .. RVPT_HIP_PATH_MAX_BOUNCES */
+    float radiance[3]; uint32_t segments; /* out */
+} rvpt_ray_path;
 
 /* Image tiles are RVPT_HIP_TILE x RVPT_HIP_TILE pixels — the footprint of one reference
  * work-group (compute_pass.comp:27).  The tile at (tx, ty) of the tiles_x-wide tile grid has slot
@@ -403,7 +415,37 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  * - The call is LOCAL: with a communicator it is not collective and touches no peer.  Every rank holds the whole scene, and any rank answers.
  * - It implies rvpt_hip_wait, as every read does, and leaves untouched the accumulator, rvpt_hip_get_timing, rvpt_hip_get_stats, rvpt_hip_get_launch_info,
  *   rvpt_hip_get_cull_info, the frame counter, and rvpt_hip_last_error on success: a frame dispatched after a query is bit for bit the frame dispatched without it.
- * DESIGN.md 5.13 has the kernels and what was measured (profiles/ray_queries.txt). */
+ * DESIGN.md 5.13 has the kernels and what was measured (profiles/ray_queries.txt).
+ *
+ * PATH QUERIES — radiance along the caller's own rays, in place:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_RAY_PATHS, records, n * sizeof(rvpt_ray_path));
+ *
+ * `dst` then holds n rvpt_ray_path records: each comes in as a ray, an RNG state and a bounce budget (org, seed, dir, max_bounces) and goes out as a radiance and
+ * a count (radiance, segments).  The in fields are never written.
+ * - WHAT A RECORD HOLDS ON RETURN.  radiance is what integrator_Kajiya (integrators.glsl:571-671) returns for the ray (org, dir): the function a frame's mode-9
+ *   pixel evaluates after its camera ray is made, run with the record's max_bounces and with the RNG state `seed` — every rand() of the path advances that state
+ *   as util.glsl:38-50 does.  segments is the number of closest-hit queries the path made: what RVPT_HIP_COUNT_SEGMENTS counts, per path.  radiance is the
+ *   integrator's value itself: a frame adds it to zero, which turns -0 into +0; the query does not.
+ * - THE ORDER A PATH WALKS is a ray query's, for every segment: intersect_bvh of the reference on BVH contexts (RVPT_HIP_TRAVERSAL_BVH_ORDERED contexts too),
+ *   stored order on brute-force contexts, each segment with the interval (0, +inf).  A path query's bits therefore depend on no create flag other than brute
+ *   force against BVH.
+ * - INVALID RECORDS.  A record is invalid if a component of org or dir is non-finite, if max_bounces == 0 or if max_bounces > RVPT_HIP_PATH_MAX_BOUNCES.  That is
+ *   decided before any walk and answered radiance = 0, 0, 0 and segments = 0 — as the reference's loop integrators return black without tracing for a
+ *   non-positive budget (integrators.glsl:574).  The upper bound is not a convenience: a mirror box with a budget of 2^32 would hold a shared GPU for minutes,
+ *   and no input may make a launch unbounded.
+ * - A seed of 0 is legal: xorshift32 then stays 0, which is what the arithmetic gives.
+ * - The call needs a scene — before any full upload it is RVPT_HIP_ERR_INVALID; the empty scene answers every valid record with the miss radiance of its dir and
+ *   segments = 1 — and no rvpt_hip_set_frame.  dst_bytes must be a multiple of 48, else RVPT_HIP_ERR_INVALID; dst_bytes == 0 is a successful no-op; fewer than
+ *   2^32 records per call.
+ * - `dst` is host memory or device memory of the context's GPU, classified as for frames.  Device memory must be 16-byte aligned, else RVPT_HIP_ERR_INVALID;
+ *   another GPU's memory is RVPT_HIP_ERR_INVALID naming both devices.  In every error case `dst` is untouched.  Host records go through the ray queries' staging
+ *   buffer, and only the out fields travel back; device records never visit the host.
+ * - The call is LOCAL: with a communicator it is not collective and touches no peer.
+ * - It implies rvpt_hip_wait and leaves untouched the accumulator, rvpt_hip_get_timing, rvpt_hip_get_stats, rvpt_hip_get_launch_info, rvpt_hip_get_cull_info,
+ *   the frame counter, and rvpt_hip_last_error on success: a frame dispatched after a path query is bit for bit the frame dispatched without it.
+ * - ONLY KAJIYA IS BUILT.  The other ten integrators of compute_pass.comp (render modes 0-8 and Hart) are not part of this form.
+ * DESIGN.md 5.14 has the kernels and what was measured (profiles/path_queries.txt). */
 int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes);
 
 /* ---- multi-GPU: one RCCL communicator over the tile_world ranks of a partitioned image (no reference counterpart: the

@@ -31,6 +31,7 @@
 #include "rvpt_frames.h"
 #include "rvpt_build.h"
 #include "rvpt_query.h"
+#include "rvpt_paths.h"
 #include "rvpt_packets.h"
 #include "rvpt_math.h"
 #include "rvpt_rect.h"
@@ -65,6 +66,10 @@ static_assert(sizeof(rvpt_camera_data) == 80, "Camera block (compute_pass.comp:4
 static_assert(sizeof(rvpt_ray_hit) == rv::kQueryRecordBytes && offsetof(rvpt_ray_hit, tmax) == 12 && offsetof(rvpt_ray_hit, dir) == 16 && offsetof(rvpt_ray_hit, flags) == 28 &&
                   offsetof(rvpt_ray_hit, t) == 32 && offsetof(rvpt_ray_hit, prim) == 36 && offsetof(rvpt_ray_hit, u) == 40 && offsetof(rvpt_ray_hit, v) == 44,
               "a ray query's record: three float4 (rvpt_query.hip)");
+static_assert(sizeof(rvpt_ray_path) == rv::kPathRecordBytes && offsetof(rvpt_ray_path, seed) == 12 && offsetof(rvpt_ray_path, dir) == 16 && offsetof(rvpt_ray_path, max_bounces) == 28 &&
+                  offsetof(rvpt_ray_path, radiance) == 32 && offsetof(rvpt_ray_path, segments) == 44 && RVPT_HIP_PATH_MAX_BOUNCES == rv::kPathMaxBounces,
+              "a path query's record: three float4 (rvpt_paths.hip)");
+static_assert(sizeof(rvpt_ray_path) == sizeof(rvpt_ray_hit) && offsetof(rvpt_ray_path, radiance) == offsetof(rvpt_ray_hit, t), "ray and path queries share query_records");
 static_assert(offsetof(rvpt_triangle, mat_id) == 48 && offsetof(rvpt_bvh_node, bounds) == 8 &&
                   offsetof(rvpt_material, data) == 32 && offsetof(rvpt_render_settings, split_ratio) == 32 &&
                   offsetof(rvpt_camera_data, params) == 64,
@@ -151,7 +156,7 @@ struct rvpt_hip_ctx {
     unsigned char *d_sparse_stage = nullptr;
     size_t cap_sparse_stage = 0;
     bool have_scene = false;
-    // RAY QUERIES (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS; rvpt_query.h): the staging buffer of host records (bytes) and the launch's scratch — 64 words whose
+    // RAY QUERIES and PATH QUERIES (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS / RVPT_HIP_FORMAT_RAY_PATHS; rvpt_query.h, rvpt_paths.h): the staging buffer of host records (bytes) and the launch's scratch — 64 words whose
     // first is the claim counter, then the global part of the traversal stack (words).  Both only grow.
     unsigned char *d_query_stage = nullptr;
     size_t cap_query_stage = 0;
@@ -2368,32 +2373,40 @@ int rvpt_hip_gather(rvpt_hip_ctx *ctx, void *dst_dev_rgba32f)
     return gather_to_root(ctx, static_cast<float4 *>(dst_dev_rgba32f));
 }
 
-// rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS (include/rvpt_hip.h: RAY QUERIES): `dst` holds dst_bytes / 48 records, rays in and hits out.  LOCAL: no
-// communicator is touched.  Everything is checked before anything is written; on success ctx->err stays as it was.
-static int query_rays(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes)
+// rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS (include/rvpt_hip.h: RAY QUERIES) or, `paths`, with RVPT_HIP_FORMAT_RAY_PATHS (PATH QUERIES): `dst` holds
+// dst_bytes / 48 records, rays in and hits — radiance — out.  The two forms share everything but the kernels: the checks, the pointer's classification, the
+// staging of host records (only a record's third float4, the out fields, travels back).  LOCAL: no communicator is touched.  Everything is checked before
+// anything is written; on success ctx->err stays as it was.  No event is recorded: RVPT_HIP_TIMING does not see a query.
+static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const bool paths)
 {
+    const char *what = paths ? "path" : "ray", *record = paths ? "rvpt_ray_path" : "rvpt_ray_hit";
     if (dst_bytes % sizeof(rvpt_ray_hit))
-        return fail(ctx, RVPT_HIP_ERR_INVALID, "ray query: dst_bytes %zu is not a multiple of the %zu bytes of a rvpt_ray_hit", dst_bytes, sizeof(rvpt_ray_hit));
-    if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "ray query before any full upload_scene on this context: there is no scene to ask");
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "%s query: dst_bytes %zu is not a multiple of the %zu bytes of a %s", what, dst_bytes, sizeof(rvpt_ray_hit), record);
+    if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "%s query before any full upload_scene on this context: there is no scene to ask", what);
     const size_t n = dst_bytes / sizeof(rvpt_ray_hit);
     if (n == 0) return RVPT_HIP_OK;
     if (!dst) return fail(ctx, RVPT_HIP_ERR_INVALID, "dst is NULL");
-    if (n > 0xFFFFFFFFull) return fail(ctx, RVPT_HIP_ERR_INVALID, "ray query: %zu records, at most 2^32 - 1 per call", n);
+    if (n > 0xFFFFFFFFull) return fail(ctx, RVPT_HIP_ERR_INVALID, "%s query: %zu records, at most 2^32 - 1 per call", what, n);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     bool device_dst = false;
     if (int rc = classify_frame_pointer(ctx, dst, "dst", &device_dst)) return rc;
     if (device_dst && reinterpret_cast<uintptr_t>(dst) % 16u)
-        return fail(ctx, RVPT_HIP_ERR_INVALID, "dst is device memory at %p: ray records on the device need 16-byte alignment", dst);
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "dst is device memory at %p: %s records on the device need 16-byte alignment", dst, what);
 
-    rv::QueryScene scene{};
+    rv::PathScene path_scene{};
+    rv::QueryScene &scene = path_scene.walk;
     const bool bvh = is_bvh(ctx, ctx->n_tris);
     scene.kind = !bvh ? rv::QueryKind::Brute : (ctx->n_wide > 0 && ctx->bvh_head_shift != 0 ? rv::QueryKind::Wide : rv::QueryKind::Binary);
     scene.prep = ctx->d_prep, scene.nodes = ctx->d_nodes, scene.wide = ctx->d_wide;
     scene.perm = ctx->have_perm ? ctx->d_perm : nullptr;
     scene.n_tris = static_cast<uint32_t>(ctx->n_tris), scene.n_wide = static_cast<uint32_t>(ctx->n_wide), scene.head_shift = ctx->bvh_head_shift;
     scene.stack_levels = scene.kind == rv::QueryKind::Wide ? ctx->wide_stack_levels : bvh_stack_levels(ctx);
+    path_scene.mat_index = ctx->d_mat_index, path_scene.unit_n = ctx->d_unit_n, path_scene.mats = ctx->d_mats;
     rv::QueryPlan plan{};
-    HIP_TRY(ctx, rv::query_plan(scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
+    if (paths)
+        HIP_TRY(ctx, rv::path_plan(path_scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
+    else
+        HIP_TRY(ctx, rv::query_plan(scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
     if (int rc = rvpt_hip_wait(ctx)) return rc;  // every read implies it; frames in flight still read the scene, and the buffers below may be regrown
     if (int rc = grow(ctx, ctx->d_query_scratch, ctx->cap_query_scratch, 64u + plan.stack_words, sizeof(uint32_t))) return rc;
     void *records = dst;
@@ -2402,7 +2415,10 @@ static int query_rays(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes)
         records = ctx->d_query_stage;
         HIP_TRY(ctx, hipMemcpyAsync(records, dst, dst_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    HIP_TRY(ctx, rv::query_launch(ctx->stream, scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
+    if (paths)
+        HIP_TRY(ctx, rv::path_launch(ctx->stream, path_scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
+    else
+        HIP_TRY(ctx, rv::query_launch(ctx->stream, scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
     if (!device_dst)  // only the out fields travel back: the in fields of a host record are never written either
         HIP_TRY(ctx, hipMemcpy2DAsync(static_cast<unsigned char *>(dst) + offsetof(rvpt_ray_hit, t), sizeof(rvpt_ray_hit), ctx->d_query_stage + offsetof(rvpt_ray_hit, t),
                                       sizeof(rvpt_ray_hit), sizeof(rvpt_ray_hit) - offsetof(rvpt_ray_hit, t), n, hipMemcpyDeviceToHost, ctx->stream));
@@ -2413,7 +2429,8 @@ static int query_rays(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes)
 int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
 {
     if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
-    if (format == RVPT_HIP_FORMAT_RAY_HITS) return query_rays(ctx, dst, dst_bytes);  // local even with a communicator: every rank holds the whole scene
+    if (format == RVPT_HIP_FORMAT_RAY_HITS || format == RVPT_HIP_FORMAT_RAY_PATHS)  // local even with a communicator: every rank holds the whole scene
+        return query_records(ctx, dst, dst_bytes, format == RVPT_HIP_FORMAT_RAY_PATHS);
     const bool collective = ctx->comm != nullptr;  // partitioned image with a communicator: gather to rank 0, which gets the frame
     if (collective && ctx->tile_rank != 0 && ctx->local_group.empty()) return gather_to_root(ctx, nullptr);  // peers only send
     const size_t px = static_cast<size_t>(ctx->width) * ctx->height;

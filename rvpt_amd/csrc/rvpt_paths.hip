@@ -1,0 +1,412 @@
+// rvpt_paths.hip — path queries (include/rvpt_hip.h: RVPT_HIP_FORMAT_RAY_PATHS): a record comes in as a ray, an RNG state and a bounce budget and goes out as
+// the radiance integrator_Kajiya (integrators.glsl:571-671) returns for that ray, with the number of segments the path traced, in place.
+//
+// The functions are the frame kernels', unchanged (rvpt_device.h): per segment the closest hit — the ray queries' walks (rvpt_query.hip) with the interval
+// (0, +inf) —, then shade(), then shade's `bounce >= max_bounces` test against the RECORD's budget.  What a frame's mode-9 pixel evaluates after its camera ray
+// is made, from a record instead of from a pixel.
+//
+// One path per lane, and REGENERATION: paths end after 1 .. max_bounces segments, so a lane whose path has ended stores its 16 out bytes and takes the next
+// record of the run its wave has claimed (runs of kPathRun consecutive records off one counter; ballot / mbcnt hand-out as WavePool deals pixels) before the
+// next segment's walk.  All three kernels run on a PERSISTENT grid sized from occupancy.  A record's answer is a function of its 32 in bytes and the scene
+// alone: which lane or wave traced it, and beside which other records, changes nothing.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "rvpt_device.h"
+#include "rvpt_paths.h"
+
+namespace rv {
+
+namespace {
+
+constexpr uint32_t kNoPrim = 0xFFFFFFFFu;
+
+struct PathArgs {
+    const float4 *prep, *nodes, *wide, *unit_n, *mats;
+    const uint32_t *mat_index;
+    float4 *records;
+    uint32_t n, n_runs;          // records, runs of kPathRun records
+    uint32_t *counter;           // the next run to claim (0 at launch)
+    uint32_t *stack_overflow;    // [stack_levels - lds_levels][2][threads of the grid]
+    uint32_t n_tris, head_shift, stack_levels, lds_levels, top_nodes;
+};
+
+// The path a lane is tracing: the frame kernels' Lane (segment, throughput, radiance so far, RNG state, finished segments) with the record it came from
+struct PathLane {
+    Lane L;
+    uint32_t rec;     // index of the record
+    int max_bounces;  // the record's budget, 1 .. kPathMaxBounces
+    bool have;        // false: this lane holds no path
+};
+
+// The records of the run a wave has claimed and not yet dealt (wave-uniform)
+struct RunPool {
+    uint32_t next = 0, end = 0;
+    bool exhausted = false;  // the counter has passed the last run
+};
+
+__device__ __forceinline__ bool finite_(const float x) { return __builtin_fabsf(x) < kInf; }  // false for NaN and +-inf
+
+// Every lane without a path takes the next record of the wave's run, in lane order; the wave claims a new run when the one it holds is dealt.  An invalid
+// record — a non-finite component of org or dir, a budget of 0 or past kPathMaxBounces — is answered here, before any walk: radiance 0, segments 0.
+// On return a lane without a path means that the records are all dealt.
+__device__ __forceinline__ void regenerate_paths(RunPool &pool, const PathArgs &a, const uint32_t lane, PathLane &P)
+{
+    bool need = !P.have;
+    for (;;) {
+        const uint64_t mask = ballot(need);
+        if (mask == 0) break;
+        uint32_t avail = pool.end - pool.next;
+        if (avail == 0) {
+            if (pool.exhausted) break;
+            uint32_t run = 0;
+            if (lane == 0) run = atomicAdd(a.counter, 1u);
+            run = __builtin_amdgcn_readlane(run, 0);
+            if (run >= a.n_runs) {
+                pool.exhausted = true;
+                break;
+            }
+            pool.next = run * kPathRun;  // (< n <= 2^32 - 1)
+            avail = min(kPathRun, a.n - pool.next);
+            pool.end = pool.next + avail;
+        }
+        const uint32_t rank = prefix_rank(mask);
+        const uint32_t wanted = static_cast<uint32_t>(__builtin_popcountll(mask));
+        if (need && rank < avail) {
+            const size_t r = static_cast<size_t>(pool.next) + rank;
+            const float4 ra = a.records[3 * r + 0];
+            const float4 rb = a.records[3 * r + 1];
+            const uint32_t budget = __float_as_uint(rb.w);
+            const bool valid = finite_(ra.x) && finite_(ra.y) && finite_(ra.z) && finite_(rb.x) && finite_(rb.y) && finite_(rb.z) && budget >= 1u && budget <= kPathMaxBounces;
+            if (valid) {
+                P.L.o = mk(ra.x, ra.y, ra.z);
+                P.L.d = mk(rb.x, rb.y, rb.z);
+                P.L.thr = mk(1.0f, 1.0f, 1.0f);
+                P.L.col = mk(0.0f, 0.0f, 0.0f);
+                P.L.rng = __float_as_uint(ra.w);
+                P.L.bounce = 0;
+                P.L.nseg = 0;
+                P.rec = static_cast<uint32_t>(r);
+                P.max_bounces = static_cast<int>(budget);
+                P.have = true;
+                need = false;
+            } else {
+                a.records[3 * r + 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+        }
+        pool.next += min(wanted, avail);
+    }
+}
+
+// A finished segment: shade() as a frame runs it, with the record's budget where a frame has its settings'.  A path that ended stores its out fields — the
+// integrator's value itself (a frame adds it to zero), the segments it traced — and frees the lane.  Returns true when the path goes on with L.o, L.d.
+__device__ __forceinline__ bool finish_segment(const PathArgs &a, const ShadeSrc src, PathLane &P, const uint32_t hit, const float closest)
+{
+    FrameParams fp;  // shade() reads its bounce budget and nothing else
+    fp.max_bounces = P.max_bounces;
+    f3 radiance = mk(0.0f, 0.0f, 0.0f);
+    P.L.nseg += 1;
+    if (!shade(P.L, fp, src, hit, closest, radiance)) return true;
+    a.records[3 * static_cast<size_t>(P.rec) + 2] = make_float4(radiance.x, radiance.y, radiance.z, __uint_as_float(P.L.nseg));
+    P.have = false;
+    return false;
+}
+
+enum { S_IDLE = 0, S_TRAV = 1, S_HIT = 2 };  // no segment / a segment whose walk is to start or under way / a segment whose closest hit is known
+
+}  // namespace
+
+// query_bvh4's walk (rvpt_bvh4.hip's per-lane walk: slab_entry at the root, four slab_child tests per wide node, on with the first child that passes, the others
+// stacked, the last first, with their entry distances and packed heads, popped with closest >= entry) under the frame kernel's loop: lanes whose walk has ended
+// wait in S_HIT until kPathRefill of them do, then shade, regenerate and start the next walk together; reached leaves are parked and run in batches.
+// LDS: [stack: lds_levels x 2 words x kBlock][root: 2 float4][top_nodes wide nodes]
+__global__ __launch_bounds__(kBlock) void path_bvh4(const PathArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const uint32_t lds_levels = a.lds_levels;
+    float4 *lds_root = reinterpret_cast<float4 *>(lds_stack + 2u * lds_levels * kBlock);
+    float4 *lds_top = lds_root + 2;
+    const uint32_t top_nodes = a.top_nodes;
+    if (threadIdx.x < 2u) lds_root[threadIdx.x] = a.nodes[threadIdx.x];
+    for (uint32_t i = threadIdx.x; i < 8u * top_nodes; i += kBlock) lds_top[i] = a.wide[i];
+    __syncthreads();
+    const v4f *prep = reinterpret_cast<const v4f *>(a.prep);
+    const ShadeSrc shade_src{a.prep, a.mat_index, a.mats, a.unit_n};
+    const uint32_t top_level = a.stack_levels - 1u;
+    const uint32_t head_shift = a.head_shift;
+    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
+    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
+    const uint32_t lane = lane_id();
+
+    RunPool pool;
+    PathLane P{};
+    int state = S_IDLE;
+    bool walking = false;
+    float closest = kInf;
+    uint32_t hit = kNoPrim, sp = 0, cur = 0, leaf_first = 0, leaf_count = 0;
+    f3 inv = mk(0.0f, 0.0f, 0.0f);
+    auto enter = [&](const uint32_t head) {  // head = first | count << head_shift (leaf, count > 0) or a wide node index (count 0)
+        const uint32_t first = head & ((1u << head_shift) - 1u), count = head >> head_shift;
+        cur = first;
+        leaf_first = first;
+        leaf_count = count;
+    };
+    auto push = [&](const float entry, const uint32_t head) {
+        const uint32_t at = min(sp, top_level);  // the host sized the stack from the wide tree: sp never passes top_level; the clamp keeps a wrong size inside the memory
+        if (at < lds_levels) {
+            lds_stack[(2u * at + 0u) * kBlock + threadIdx.x] = __float_as_uint(entry);
+            lds_stack[(2u * at + 1u) * kBlock + threadIdx.x] = head;
+        } else {
+            ovf[(2u * (at - lds_levels) + 0u) * ovf_stride] = __float_as_uint(entry);
+            ovf[(2u * (at - lds_levels) + 1u) * ovf_stride] = head;
+        }
+        sp = at + 1u;
+    };
+
+    for (;;) {
+        // ---- refill: every lane that is not walking shades the segment it finished, takes a record if its path ended, and starts its next walk
+        for (;;) {
+            if (state == S_HIT) state = finish_segment(a, shade_src, P, hit, closest) ? S_TRAV : S_IDLE;
+            regenerate_paths(pool, a, lane, P);
+            if (P.have && state == S_IDLE) state = S_TRAV;
+            if (state == S_TRAV && !walking) {  // start at the root: its own box first (the root is a node like any other, intersection.glsl:369-380)
+                closest = kInf;
+                hit = kNoPrim;
+                inv = mk(1.0f / P.L.d.x, 1.0f / P.L.d.y, 1.0f / P.L.d.z);
+                sp = 0;
+                float entry;
+                if (slab_entry(P.L.o, inv, lds_root[0], lds_root[1], closest, entry)) {
+                    cur = 0;  // the wide root
+                    leaf_count = 0;
+                    walking = true;
+                } else {
+                    state = S_HIT;
+                }
+            }
+            if (ballot(state == S_HIT) == 0) break;  // (a ray that misses the root's box is a finished segment: round again)
+        }
+        if (ballot(state == S_TRAV) == 0) break;  // no lane walks: none holds a path, and none is left to deal
+
+        // ---- traverse: every iteration each walking lane handles one wide node; leaves are parked and run in batches
+        for (uint32_t steps = 0;; ++steps) {
+            bool need_pop = false;
+            if (state == S_TRAV && leaf_count == 0) {
+                const float4 *node = cur < top_nodes ? lds_top + 8u * cur : a.wide + 8u * static_cast<size_t>(cur);
+                const float4 minx = node[0], maxx = node[1], miny = node[2], maxy = node[3], minz = node[4], maxz = node[5], hq = node[6];
+                const uint32_t hd0 = __float_as_uint(hq.x), hd1 = __float_as_uint(hq.y), hd2 = __float_as_uint(hq.z), hd3 = __float_as_uint(hq.w);
+                float e0, e1, e2, e3;
+                const bool h0 = slab_child(P.L.o, inv, minx.x, maxx.x, miny.x, maxy.x, minz.x, maxz.x, closest, e0);  // (a wide node has at least two children)
+                const bool h1 = slab_child(P.L.o, inv, minx.y, maxx.y, miny.y, maxy.y, minz.y, maxz.y, closest, e1);
+                const bool h2 = slab_child(P.L.o, inv, minx.z, maxx.z, miny.z, maxy.z, minz.z, maxz.z, closest, e2) && hd2 != kWideEmpty;
+                const bool h3 = slab_child(P.L.o, inv, minx.w, maxx.w, miny.w, maxy.w, minz.w, maxz.w, closest, e3) && hd3 != kWideEmpty;
+                if (h3 && (h0 || h1 || h2)) push(e3, hd3);
+                if (h2 && (h0 || h1)) push(e2, hd2);
+                if (h1 && h0) push(e1, hd1);
+                if (h0 || h1 || h2 || h3)
+                    enter(h0 ? hd0 : (h1 ? hd1 : (h2 ? hd2 : hd3)));
+                else
+                    need_pop = true;
+            }
+            const uint32_t at_leaf = static_cast<uint32_t>(__builtin_popcountll(ballot(leaf_count > 0)));
+            const uint32_t at_inner = static_cast<uint32_t>(__builtin_popcountll(ballot(state == S_TRAV && leaf_count == 0)));
+            const bool run_leaves = at_leaf > 0 && (at_inner == 0 || at_leaf >= kPathLeafBatch);
+            if (run_leaves && leaf_count > 0) {
+                for (uint32_t i = leaf_first; i < leaf_first + leaf_count; ++i) {
+                    const v4f *tp = prep + 4 * static_cast<size_t>(i);
+                    test_triangle(unpack(tp[0], tp[1], tp[2], tp[3]), P.L.o, P.L.d, i, closest, hit);
+                }
+                leaf_count = 0;
+                need_pop = true;
+            }
+            if (need_pop) {
+                bool found = false;
+                while (sp > 0 && !found) {
+                    sp -= 1;
+                    uint32_t entry_bits, cand;
+                    if (sp < lds_levels) {
+                        entry_bits = lds_stack[(2u * sp + 0u) * kBlock + threadIdx.x];
+                        cand = lds_stack[(2u * sp + 1u) * kBlock + threadIdx.x];
+                    } else {
+                        entry_bits = ovf[(2u * (sp - lds_levels) + 0u) * ovf_stride];
+                        cand = ovf[(2u * (sp - lds_levels) + 1u) * ovf_stride];
+                    }
+                    if (closest >= __uint_as_float(entry_bits)) {  // the reference's box test at the visit (rvpt_bvh4.hip's header comment)
+                        enter(cand);
+                        found = true;
+                    }
+                }
+                if (!found) {
+                    state = S_HIT;
+                    walking = false;
+                }
+            }
+            if (ballot(state == S_TRAV) == 0) break;
+            const uint32_t waiting = static_cast<uint32_t>(__builtin_popcountll(ballot(state == S_HIT)));
+            if (waiting >= kPathRefill || (waiting > 0 && steps >= 4u * kPathRefill)) break;
+        }
+    }
+}
+
+// query_bvh2's walk — intersect_bvh as the reference writes it, over the binary nodes: pop a node, test its box against the interval of that moment, a leaf's
+// triangles in order, an inner node's right child stacked and its left child next — under the same loop.  One word per stack slot (the node index).
+__global__ __launch_bounds__(kBlock) void path_bvh2(const PathArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const uint32_t lds_levels = a.lds_levels;
+    const v4f *prep = reinterpret_cast<const v4f *>(a.prep);
+    const ShadeSrc shade_src{a.prep, a.mat_index, a.mats, a.unit_n};
+    const uint32_t top_level = a.stack_levels - 1u;
+    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
+    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
+    const uint32_t lane = lane_id();
+
+    RunPool pool;
+    PathLane P{};
+    int state = S_IDLE;
+    bool walking = false;
+    float closest = kInf;
+    uint32_t hit = kNoPrim, sp = 0, cur = 0;
+    f3 inv = mk(0.0f, 0.0f, 0.0f);
+
+    for (;;) {
+        for (;;) {
+            if (state == S_HIT) state = finish_segment(a, shade_src, P, hit, closest) ? S_TRAV : S_IDLE;
+            regenerate_paths(pool, a, lane, P);
+            if (P.have && state == S_IDLE) state = S_TRAV;
+            if (state == S_TRAV && !walking) {  // (the root's box is tested by the first step below, as every node's)
+                closest = kInf;
+                hit = kNoPrim;
+                inv = mk(1.0f / P.L.d.x, 1.0f / P.L.d.y, 1.0f / P.L.d.z);
+                sp = 0;
+                cur = 0;
+                walking = true;
+            }
+            if (ballot(state == S_HIT) == 0) break;
+        }
+        if (ballot(state == S_TRAV) == 0) break;
+
+        for (uint32_t steps = 0;; ++steps) {
+            if (state == S_TRAV) {
+                const float4 n0 = a.nodes[2u * static_cast<size_t>(cur)], n1 = a.nodes[2u * static_cast<size_t>(cur) + 1u];
+                const uint32_t first = __float_as_uint(n0.x), count = __float_as_uint(n0.y);
+                bool pop = true;
+                float entry;
+                if (slab_entry(P.L.o, inv, n0, n1, closest, entry)) {
+                    if (count > 0) {
+                        for (uint32_t i = first; i < first + count; ++i) {
+                            const v4f *tp = prep + 4 * static_cast<size_t>(i);
+                            test_triangle(unpack(tp[0], tp[1], tp[2], tp[3]), P.L.o, P.L.d, i, closest, hit);
+                        }
+                    } else {
+                        const uint32_t at = min(sp, top_level);  // (the tree's height bounds the pushes of a root-to-leaf path; the clamp as in path_bvh4)
+                        if (at < lds_levels)
+                            lds_stack[at * kBlock + threadIdx.x] = first + 1u;
+                        else
+                            ovf[(at - lds_levels) * ovf_stride] = first + 1u;
+                        sp = at + 1u;
+                        cur = first;
+                        pop = false;
+                    }
+                }
+                if (pop) {
+                    if (sp == 0) {
+                        state = S_HIT;
+                        walking = false;
+                    } else {
+                        sp -= 1;
+                        cur = sp < lds_levels ? lds_stack[sp * kBlock + threadIdx.x] : ovf[(sp - lds_levels) * ovf_stride];
+                    }
+                }
+            }
+            if (ballot(state == S_TRAV) == 0) break;
+            const uint32_t waiting = static_cast<uint32_t>(__builtin_popcountll(ballot(state == S_HIT)));
+            if (waiting >= kPathRefill || (waiting > 0 && steps >= 4u * kPathRefill)) break;
+        }
+    }
+}
+
+// Brute force, in work-group-synchronous ROUNDS: at a round's start every lane without a path takes a record (each wave deals its own runs); then the prepared
+// triangles stream through LDS in tiles of kQueryTileTris, as query_brute streams them, and every lane that holds a path runs its current segment over each
+// tile in index order; then it shades.  The work-group leaves when a round starts with no path in any of its lanes.  No culls: the packet kernel's rest on a
+// camera and a block of pixels.
+__global__ __launch_bounds__(kBlock) void path_brute(const PathArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tile[];
+    const ShadeSrc shade_src{a.prep, a.mat_index, a.mats, a.unit_n};
+    const uint32_t lane = lane_id();
+    RunPool pool;
+    PathLane P{};
+    for (;;) {
+        regenerate_paths(pool, a, lane, P);
+        if (__syncthreads_or(P.have ? 1 : 0) == 0) break;  // (also the barrier between the last round's tile reads and this round's tile stores)
+        if (!P.have) P.L.d = mk(0.0f, 0.0f, 0.0f);  // a lane without a path runs along: every test of a zero direction is NaN and accepts nothing
+        float closest = kInf;
+        uint32_t hit = kNoPrim;
+        const uint64_t wave_has = ballot(P.have);
+        for (uint32_t base = 0; base < a.n_tris; base += kQueryTileTris) {
+            const uint32_t count = min(kQueryTileTris, a.n_tris - base);
+            if (base != 0) __syncthreads();  // the tile before this one has been read by every wave
+            for (uint32_t i = threadIdx.x; i < 4u * count; i += kBlock) lds_tile[i] = a.prep[4u * static_cast<size_t>(base) + i];
+            __syncthreads();
+            if (wave_has != 0) intersect_run<4>(reinterpret_cast<const v4f *>(lds_tile), base, count, P.L.o, P.L.d, closest, hit);
+        }
+        if (P.have) (void)finish_segment(a, shade_src, P, hit, closest);
+    }
+}
+
+hipError_t path_plan(const PathScene &scene, const uint32_t n, const int num_cus, QueryPlan *plan)
+{
+    QueryPlan p{};
+    const QueryKind kind = scene.walk.kind;
+    const void *kernel = reinterpret_cast<const void *>(path_brute);
+    uint32_t levels = 0;
+    if (kind == QueryKind::Brute) {
+        p.lds_bytes = static_cast<size_t>(kQueryTileTris) * 64u;
+    } else {
+        levels = std::max<uint32_t>(1u, scene.walk.stack_levels);
+        p.lds_levels = std::min(levels, kQueryLdsLevels);
+        p.top_nodes = kind == QueryKind::Wide ? std::min(scene.walk.n_wide, kQueryTopNodes) : 0u;
+        p.lds_bytes = static_cast<size_t>(p.lds_levels) * kBlock * 2u * sizeof(uint32_t) + 2u * sizeof(float4) + static_cast<size_t>(p.top_nodes) * 128u;
+        kernel = kind == QueryKind::Wide ? reinterpret_cast<const void *>(path_bvh4) : reinterpret_cast<const void *>(path_bvh2);
+    }
+    int per_cu = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, p.lds_bytes);
+    if (e != hipSuccess) return e;
+    const uint64_t runs = (static_cast<uint64_t>(n) + kPathRun - 1u) / kPathRun;
+    const uint64_t want = (runs + kBlock / 64u - 1u) / (kBlock / 64u);  // a work-group's four waves claim a run each
+    p.grid = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>(want, static_cast<uint64_t>(std::max(per_cu, 1)) * static_cast<uint64_t>(std::max(num_cus, 1)))));
+    const size_t column_words = static_cast<size_t>(2u) * (levels - p.lds_levels) * kBlock;  // per work-group
+    while (p.grid > 1u && column_words * p.grid * sizeof(uint32_t) > kQueryStackMaxBytes) p.grid = (p.grid + 1u) / 2u;
+    p.stack_words = column_words * p.grid;
+    *plan = p;
+    return hipSuccess;
+}
+
+hipError_t path_launch(hipStream_t stream, const PathScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, const uint32_t n)
+{
+    if (n == 0) return hipSuccess;
+    PathArgs a{};
+    a.prep = scene.walk.prep, a.nodes = scene.walk.nodes, a.wide = scene.walk.wide;
+    a.unit_n = scene.unit_n, a.mats = scene.mats, a.mat_index = scene.mat_index;
+    a.records = static_cast<float4 *>(records);
+    a.n = n;
+    a.n_runs = static_cast<uint32_t>((static_cast<uint64_t>(n) + kPathRun - 1u) / kPathRun);
+    a.counter = scratch;
+    a.stack_overflow = scratch + 64;
+    a.n_tris = scene.walk.n_tris, a.head_shift = scene.walk.head_shift;
+    a.stack_levels = std::max<uint32_t>(1u, scene.walk.stack_levels);
+    a.lds_levels = plan.lds_levels, a.top_nodes = plan.top_nodes;
+    const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    if (scene.walk.kind == QueryKind::Brute)
+        hipLaunchKernelGGL(path_brute, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
+    else if (scene.walk.kind == QueryKind::Wide)
+        hipLaunchKernelGGL(path_bvh4, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
+    else
+        hipLaunchKernelGGL(path_bvh2, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace rv

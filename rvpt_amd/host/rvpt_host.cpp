@@ -405,6 +405,22 @@ bool RVPT::trace_rays_device(void *records, size_t n)
     }
     return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_HITS, records, n * sizeof(rvpt_ray_hit)), "rvpt_hip_read");
 }
+bool RVPT::trace_paths(std::vector<rvpt_ray_path> &records)
+{
+    if (!ctx_) {
+        error_ = "trace_paths before initialize()";
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_PATHS, records.data(), records.size() * sizeof(rvpt_ray_path)), "rvpt_hip_read");
+}
+bool RVPT::trace_paths_device(void *records, size_t n)
+{
+    if (!ctx_) {
+        error_ = "trace_paths_device before initialize()";
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_PATHS, records, n * sizeof(rvpt_ray_path)), "rvpt_hip_read");
+}
 
 // ---- main.cpp:12-62 ---------------------------------------------------------------------------------------
 long load_model(RVPT &rvpt, const std::string &path, int material_id, std::string *error)

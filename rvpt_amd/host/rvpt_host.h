@@ -171,6 +171,12 @@ public:
     // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host: prim then stays as the LIBRARY numbers
     // it — the leaf order after a host build (sorted_triangles()), the added order after a device build.  `records` may be read from any stream on return.
     bool trace_rays_device(void *records, size_t n);
+    // Path queries (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_PATHS; include/rvpt_hip.h: PATH QUERIES): every record comes in as a ray, an RNG state and a bounce
+    // budget (org, seed, dir, max_bounces) and goes out as integrator_Kajiya's radiance along it and the segments the path traced, in place.  After
+    // initialize(); no update() is needed.  Nothing is renumbered: radiance does not depend on the order of the triangles.
+    bool trace_paths(std::vector<rvpt_ray_path> &records);
+    // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host
+    bool trace_paths_device(void *records, size_t n);
     const std::string &last_error() const { return error_; }
     // the backend context, e.g. to join several RVPT objects (one per GPU, tile_rank i of n) into one RCCL group with
     // rvpt_hip_comm_init_all; read_frame() on rank 0's object is then the gather of the whole image

@@ -30,6 +30,10 @@ RAY_ANY_HIT = 0x1  # RVPT_HIP_RAY_ANY_HIT: a record's flag — stop at the first
 NO_PRIM = 0xFFFFFFFF  # a record's prim after a miss
 # rvpt_ray_hit (48 B): org, tmax, dir, flags come in, t, prim, u, v go out
 RAY_HIT_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("flags", "<u4"), ("t", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4")])
+FORMAT_RAY_PATHS = 3  # RVPT_HIP_FORMAT_RAY_PATHS: rvpt_hip_read answers path queries, `dst` holds RAY_PATH_DTYPE records (Context.trace_paths)
+PATH_MAX_BOUNCES = 1024  # RVPT_HIP_PATH_MAX_BOUNCES: a record with a larger bounce budget, or with none, is invalid (radiance 0, segments 0)
+# rvpt_ray_path (48 B): org, seed, dir, max_bounces come in, radiance and segments go out
+RAY_PATH_DTYPE = np.dtype([("org", "<f4", (3,)), ("seed", "<u4"), ("dir", "<f4", (3,)), ("max_bounces", "<u4"), ("radiance", "<f4", (3,)), ("segments", "<u4")])
 CULL_ROW_BOXES = 0x100  # Context.cull_info: the launch rode with the row boxes (rvpt_abi.hip: kCullRowBoxes)
 CULL_SKY_LIST = 0x80  # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
 TILE = 16
@@ -563,6 +567,8 @@ class Context:
         """(pointer, bytes, object to keep alive) of a whole frame in a numpy array or a torch tensor — contiguous float32[h, w, 4] (FORMAT_RGBA32F) or
         uint8[h, w, 4] (FORMAT_RGBA8_UNORM); resolved the way _triangle_source resolves triangles: a tensor on this context's device is passed as device memory
         once the stream that last touched it has finished, and torch is imported only when a tensor is given.  Checked here, before the call."""
+        if fmt in (FORMAT_RAY_HITS, FORMAT_RAY_PATHS):  # known formats, but of records and not of a frame
+            raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use trace_rays_into / trace_paths_into")
         if fmt not in (FORMAT_RGBA32F, FORMAT_RGBA8_UNORM):
             raise NativeError(ERR_INVALID, f"{what}: unknown format {fmt}")
         name, size = ("float32", 4) if fmt == FORMAT_RGBA32F else ("uint8", 1)
@@ -618,27 +624,58 @@ class Context:
         """rvpt_hip_read with FORMAT_RAY_HITS in the caller's memory: `records` is a contiguous RAY_HIT_DTYPE array, or a contiguous float32 torch tensor [n, 12]
         (48-byte records) on the host or on this context's device — resolved the way _frame_buffer resolves frames; device records never visit the host.  The
         in fields stay as they are, the out fields are written.  Returns records."""
+        return self._query_into(records, FORMAT_RAY_HITS, RAY_HIT_DTYPE, "trace_rays_into", "RAY_HIT_DTYPE")
+
+    def _query_into(self, records, fmt: int, dtype, what: str, dtype_name: str):
         is_tensor = not isinstance(records, np.ndarray) and hasattr(records, "data_ptr")
         if is_tensor:
             import torch
             if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != 12 or not records.is_contiguous():
-                raise NativeError(ERR_INVALID, f"trace_rays_into: a contiguous float32 tensor [n, 12] is needed, got {records.dtype} {tuple(records.shape)}")
+                raise NativeError(ERR_INVALID, f"{what}: a contiguous float32 tensor [n, 12] is needed, got {records.dtype} {tuple(records.shape)}")
             nbytes = int(records.shape[0]) * 48
             if records.is_cuda:
                 if records.device.index != self.device:
-                    raise NativeError(ERR_INVALID, f"trace_rays_into: the tensor lives on device {records.device.index}, the context on {self.device}")
+                    raise NativeError(ERR_INVALID, f"{what}: the tensor lives on device {records.device.index}, the context on {self.device}")
                 torch.cuda.current_stream(records.device).synchronize()  # the library works on its own stream: what wrote the rays must have finished
                 ptr = C.c_void_p(records.data_ptr())
             else:
                 ptr = _ptr(records.numpy())  # (shares the tensor's memory)
         elif isinstance(records, np.ndarray):
-            if records.dtype != RAY_HIT_DTYPE or not records.flags.c_contiguous or not records.flags.writeable:
-                raise NativeError(ERR_INVALID, f"trace_rays_into: a contiguous writeable RAY_HIT_DTYPE array is needed, got {records.dtype}")
+            if records.dtype != dtype or not records.flags.c_contiguous or not records.flags.writeable:
+                raise NativeError(ERR_INVALID, f"{what}: a contiguous writeable {dtype_name} array is needed, got {records.dtype}")
             ptr, nbytes = _ptr(records), records.nbytes
         else:
-            raise NativeError(ERR_INVALID, f"trace_rays_into: a numpy array or a torch tensor is needed, got {type(records).__name__}")
-        _check(self._L.rvpt_hip_read(self._h, FORMAT_RAY_HITS, ptr, nbytes), self._h, self._L)
+            raise NativeError(ERR_INVALID, f"{what}: a numpy array or a torch tensor is needed, got {type(records).__name__}")
+        _check(self._L.rvpt_hip_read(self._h, fmt, ptr, nbytes), self._h, self._L)
         return records
+
+    def trace_paths(self, org, dir, seed, max_bounces) -> np.ndarray:
+        """integrator_Kajiya's radiance along the rays org[n, 3] + t dir[n, 3] against the uploaded scene — include/rvpt_hip.h: PATH QUERIES.  seed (the RNG state
+        a path starts from) and max_bounces (1 .. PATH_MAX_BOUNCES) are scalars or one value per ray.  Returns RAY_PATH_DTYPE[n]: radiance, and the segments the
+        path traced; both 0 for an invalid record."""
+        org = np.asarray(org, dtype=np.float32).reshape(-1, 3)
+        dirv = np.asarray(dir, dtype=np.float32).reshape(-1, 3)
+        if org.shape != dirv.shape:
+            raise NativeError(ERR_INVALID, f"trace_paths: {org.shape[0]} origins, {dirv.shape[0]} directions")
+        n = org.shape[0]
+        per_ray = {}
+        for name, value in (("seed", seed), ("max_bounces", max_bounces)):
+            value = np.asarray(value)
+            if value.ndim > 1 or (value.ndim == 1 and value.shape[0] != n):
+                raise NativeError(ERR_INVALID, f"trace_paths: {n} rays, {name} of shape {tuple(value.shape)}")
+            if value.dtype.kind not in "iu" or (value.size and (value.min() < 0 or value.max() > 0xFFFFFFFF)):
+                raise NativeError(ERR_INVALID, f"trace_paths: {name} must be integers in [0, 2^32), got {value.dtype}")
+            per_ray[name] = value.astype(np.uint32)
+        rec = np.zeros(n, dtype=RAY_PATH_DTYPE)
+        rec["org"], rec["dir"] = org, dirv
+        rec["seed"], rec["max_bounces"] = per_ray["seed"], per_ray["max_bounces"]
+        return self.trace_paths_into(rec)
+
+    def trace_paths_into(self, records):
+        """rvpt_hip_read with FORMAT_RAY_PATHS in the caller's memory: `records` is a contiguous RAY_PATH_DTYPE array, or a contiguous float32 torch tensor
+        [n, 12] (48-byte records; seed, max_bounces and segments are the bits of their floats) on the host or on this context's device, as for trace_rays_into.
+        The in fields stay as they are, the out fields are written.  Returns records."""
+        return self._query_into(records, FORMAT_RAY_PATHS, RAY_PATH_DTYPE, "trace_paths_into", "RAY_PATH_DTYPE")
 
     def write_accum(self, img) -> None:
         """rvpt_hip_write_accum: restore the accumulator from a row-major RGBA32F frame — anything numpy makes float32[h, w, 4] of, or a contiguous float32

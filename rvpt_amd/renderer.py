@@ -19,6 +19,18 @@ from . import native, scene
 from .camera import Camera
 
 
+def wang_hash(v) -> np.ndarray:
+    """util.glsl:25-33 on uint32 arrays (arithmetic modulo 2^32): the hash a pixel's index goes through before the frame number is added (util.glsl:35-36)"""
+    v = np.array(v, dtype=np.uint32, copy=True)
+    with np.errstate(over="ignore"):  # (a 0-d array multiplies as a scalar, which warns where arrays wrap silently)
+        v = (v ^ np.uint32(61)) ^ (v >> np.uint32(16))
+        v = v * np.uint32(9)
+        v = v ^ (v >> np.uint32(4))
+        v = v * np.uint32(0x27D4EB2D)
+        v = v ^ (v >> np.uint32(15))
+    return v
+
+
 @dataclass
 class RenderSettings:
     """rvpt.h:77-89 (defaults included: current_frame starts at 1 and is reset by the first update())."""
@@ -296,6 +308,20 @@ class RVPT:
             hit = rec["prim"] != native.NO_PRIM
             rec["prim"][hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[rec["prim"][hit]]
         return rec
+
+    def trace_paths(self, org, dir, seed=None, max_bounces=None) -> np.ndarray:
+        """Path queries against the scene as it is now (Context.trace_paths; include/rvpt_hip.h: PATH QUERIES): integrator_Kajiya's radiance along every ray
+        org + t dir, as a frame's mode-9 pixel evaluates it for its camera ray.  seed (one RNG state per ray, or a scalar) defaults to what pixel i of a frame
+        starts from before its two jitter values, wang_hash(i) + render_settings.current_frame; max_bounces to render_settings.max_bounces.  Returns
+        native.RAY_PATH_DTYPE records: radiance, and the segments the path traced.  Needs initialize(), not update(): a query has no camera."""
+        if self._ctx is None:
+            raise RuntimeError("trace_paths before initialize()")
+        n = np.asarray(org, dtype=np.float32).reshape(-1, 3).shape[0]
+        if seed is None:
+            seed = wang_hash(np.arange(n, dtype=np.uint32)) + np.uint32(self.render_settings.current_frame & 0xFFFFFFFF)
+        if max_bounces is None:
+            max_bounces = int(self.render_settings.max_bounces)
+        return self._ctx.trace_paths(org, dir, seed, max_bounces)
 
     def pick(self, x: int, y: int):
         """What is under pixel (x, y) of the current camera: (prim, t) of the closest hit along the pixel-centre ray, or None.  The ray is made HERE, on the host, from

@@ -1196,16 +1196,23 @@ def test_fuzz_culls_slice(native, oracle):
     sys.path.insert(0, str(ROOT / "tools"))
     import fuzz_culls
     failed, packets = [], 0
-    for idx in range(60):
-        case = fuzz_culls.make_case(606, idx)
-        r = fuzz_culls.run_case(case, 6e7)
-        packets += int(bool(r["info"] & 8))
-        if r["problems"]:
-            failed.append((fuzz_culls.describe(case), r["problems"]))
+    knobs = ("RVPT_HIP_PACKETS_CULL", "RVPT_HIP_PACKETS_BOUNCE_CULL", "RVPT_HIP_PACKETS_BOX_CULL", "RVPT_HIP_PACKETS_INTERLEAVE")  # what fuzz_culls sets in os.environ
+    saved = {k: os.environ.get(k) for k in knobs}
+    try:
+        for idx in range(60):
+            case = fuzz_culls.make_case(606, idx)
+            r = fuzz_culls.run_case(case, 6e7)
+            packets += int(bool(r["info"] & 8))
+            if r["problems"]:
+                failed.append((fuzz_culls.describe(case), r["problems"]))
+    finally:  # whether it passes or fails: the tests after this one run in the same process
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     assert not failed, failed[:3]
     assert packets >= 40  # most cases reach the packet kernel and both of its culls
-    for k in ("RVPT_HIP_PACKETS_CULL", "RVPT_HIP_PACKETS_BOUNCE_CULL"):
-        os.environ.pop(k, None)
 
 
 def test_dispatch_frames_host_counter_and_errors(native, oracle):

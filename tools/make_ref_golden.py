@@ -208,12 +208,46 @@ def converged_case():
     print("converged_libm.npz: mean", mean.mean(), "mean var", var.mean())
 
 
+# (case of tools/fuzz_bvh.py's slice make_case(606, idx), tree, width, height, what the case is there for)
+HOSTILE_BVH = [(13, "ploc", 48, 32, "soup_dup: exact duplicates in different leaves, equal t — the visiting order decides, and a pixel differs from brute force"),
+               (9, "lbvh", 64, 32, "camera ON a triangle's plane inside a box of twelve large triangles: flat boxes, 0 * inf in the slab test"),
+               (38, "sah", 64, 32, "the scene scaled by 2^18"),
+               (22, "ploc", 64, 32, "the scene scaled by 2^-20"),
+               (27, "host", 64, 32, "translated by 128 scene scales, camera on a plane"),
+               (24, "loose", 48, 32, "a third of the host tree's inner boxes shrunk or grown: a pixel differs from the tight tree's image")]
+
+
+def hostile_bvh_cases():
+    """The oracle's own BVH walk on hostile input, pinned to the reference binary: six cases of the slice tools/fuzz_bvh.py and tests/test_fuzz_bvh.py run
+    (fuzz_culls.make_case(606, idx)), reduced to at most 64 x 32 pixels and the last 256 triangles (fuzz_bvh.reduced_case), each with one of the trees the
+    fuzz walks.  -> hostile_bvh.npz: per case k the inputs (triangles in leaf order, materials, nodes, camera, size, max_bounces) and frames 0 and 1 of an
+    aa=2 chain, both variants."""
+    import fuzz_bvh
+    data = {"n_cases": len(HOSTILE_BVH), "seed": 606, "aa": 2}
+    for k, (idx, tree_name, W, H, what) in enumerate(HOSTILE_BVH):
+        case = fuzz_bvh.reduced_case(606, idx, W, H)
+        tree = {t["name"]: t for t in fuzz_bvh.case_trees(case)}[tree_name]
+        sc = (np.ascontiguousarray(tree["tris"]), np.ascontiguousarray(case["mats"]), np.ascontiguousarray(tree["nodes"]))
+        cam = case["cams"][0]
+        data.update({f"k{k}_idx": idx, f"k{k}_tree": tree_name, f"k{k}_what": what, f"k{k}_tris": sc[0], f"k{k}_mats": sc[1],
+                     f"k{k}_nodes": sc[2].view(np.uint32).reshape(-1, 8), f"k{k}_camera": cam, f"k{k}_size": np.array([W, H]), f"k{k}_max_bounces": case["max_bounces"]})
+        for tag, fused in (("u", False), ("c", True)):
+            imgs = chain(dict(max_bounces=case["max_bounces"], aa=2), cam, sc, W, H, fused, frames=2)
+            for f in (0, 1):
+                assert not imgs[f][..., 3].any()
+                data[f"k{k}_f{f}_{tag}"] = imgs[f][..., :3].copy()
+        print("hostile", k, fuzz_bvh.describe(case), tree_name, "written")
+    np.savez_compressed(OUT / "hostile_bvh.npz", **data)
+    largest = max(p.stat().st_size for p in OUT.glob("*.npz") if p.name != "hostile_bvh.npz")
+    assert (OUT / "hostile_bvh.npz").stat().st_size <= largest, "hostile_bvh.npz must be no larger than the largest fixture beside it"
+
+
 def main():
     ref_spv.build()
     OUT.mkdir(parents=True, exist_ok=True)
     if "--only" in sys.argv:  # add / refresh one group of fixtures without touching the others
         what = sys.argv[sys.argv.index("--only") + 1]
-        {"big": big_cases, "converged": converged_case, "functions": function_vectors}[what]()
+        {"big": big_cases, "converged": converged_case, "functions": function_vectors, "hostile": hostile_bvh_cases}[what]()
         return
     for old in OUT.glob("*.npz"):
         old.unlink()
@@ -290,6 +324,7 @@ def main():
     function_vectors()
     big_cases()
     converged_case()
+    hostile_bvh_cases()
     total = sum(p.stat().st_size for p in OUT.glob("*.npz"))
     print(f"{len(list(OUT.glob('*.npz')))} files, {total / 1e6:.2f} MB")
 

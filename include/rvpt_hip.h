@@ -60,7 +60,10 @@ extern "C" {
                                      their paths to the root are recomputed.  Still 8, no new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_RAY_HITS (2) —
                                      until then the "unknown format" error — is a RAY QUERY: `dst` holds rvpt_ray_hit records, rays in and hits out, in place.  Still 8, no
                                      new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_RAY_PATHS (3) — until then the "unknown format" error — is a
-                                     PATH QUERY: `dst` holds rvpt_ray_path records, a ray, an RNG state and a bounce budget in, integrator_Kajiya's radiance out */
+                                     PATH QUERY: `dst` holds rvpt_ray_path records, a ray, an RNG state and a bounce budget in, integrator_Kajiya's radiance out.  Still 8, no
+                                     new symbol: the count RVPT_HIP_NODES_UPDATE_POSE with `nodes` pointing at a list of rvpt_part_move records — until then the
+                                     "needs nodes" or "NULL scene array" error — is the POSE UPDATE: ranges of triangles move by one 3x4 matrix each, posed on
+                                     the device from a rest pose it keeps, and only the boxes on their paths to the root are recomputed */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -338,7 +341,52 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  * - Frames in flight finish on the old geometry; `tris` and `indices` may be freed on return; the accumulate / reset rule stays with the caller.
  * - The plain update, the guarded update and the three build counts behave and report exactly as before.  There is no guarded sparse update.
  * Cost, 1 % of 1 M triangles on one MI355X (profiles/sparse_update.txt): from host arrays 0.32 ms for a block contiguous in the caller's
- * order and 0.52 ms scattered, against 3.53 ms for the plain update from a host array in the same run; from device memory 0.15 / 0.18 ms against 0.20 ms. */
+ * order and 0.52 ms scattered, against 3.53 ms for the plain update from a host array in the same run; from device memory 0.15 / 0.18 ms against 0.20 ms.
+ *
+ * POSE UPDATE — move parts of the mesh by one matrix each; the device poses them from a rest pose it keeps:
+ *
+ *     rvpt_hip_upload_scene(ctx, (const rvpt_bvh_node *)moves, RVPT_HIP_NODES_UPDATE_POSE, NULL, k, NULL, 0);      k > 0
+ *
+ * - With this count `nodes` is not a node array: it points at k rvpt_part_move records (64 bytes each, 4-byte aligned) in HOST memory, and `tris` is NULL.
+ *   A record names the triangles [first, first + count) and carries one 3x4 matrix, row major.  `first` and `count` are in the order the plain update form
+ *   takes on this context: the leaf order after an ordinary upload, the caller's own order after a build form (through the inverse of the permutation the
+ *   library kept, the one the sparse update makes).  No triangle in two ranges, none outside the stored scene, no empty range; the reserved words are 0.
+ * - The REST POSE is the stored vertices as they stood when the last call of any OTHER form — the full upload, a build form, the plain, guarded and sparse
+ *   updates — returned successfully.  The library snapshots it at the first pose update after such a call: a device-to-device copy of the 48 vertex bytes
+ *   per triangle, in stored order (a context that never poses never allocates it).  A pose update ALWAYS poses from the rest pose, never from the current
+ *   position: two pose updates of one part do not compose, the second replaces the first.  A part not listed keeps the pose it has.
+ *   After any successful call of another form the next pose update takes a FRESH snapshot, and that snapshot includes whatever earlier pose updates left:
+ *   pose A, a sparse update of one unrelated triangle, pose B of the same part gives B applied to the A-posed vertices.
+ * - The arithmetic.  For a vertex (x, y, z) and the output component i (0, 1, 2) the value is ((m[4i]*x + m[4i+1]*y) + m[4i+2]*z) + m[4i+3]: three products
+ *   and three sums, each rounded to binary32 on its own, in that order, with NO fused multiply-add.  rvpt_amd/scene.py: pose_parts is the same in numpy
+ *   float32; the device, the host (brute-force contexts) and numpy agree bit for bit.  An identity matrix therefore turns a coordinate of -0.0 into +0.0
+ *   (-0.0 + 0.0 is +0.0): that is what the arithmetic gives.  Non-finite matrix entries are the caller's problem, as non-finite vertices are.
+ * - Only the vertices move: the x, y, z of vert0..vert2.  Their w lanes come from the rest pose; the stored mat_id rows, the materials, the topology, the
+ *   permutation and the guarded update's base cost stay.
+ * - Everything is checked BEFORE anything stored is touched; a failure is RVPT_HIP_ERR_INVALID, has a message, and leaves the scene and the rest pose as they
+ *   were: no full upload on this context yet; k == 0; k larger than the stored count; `moves` NULL; `moves` not 4-byte aligned; `tris` not NULL; materials
+ *   passed; `moves` in device memory (this form takes its list from the host); then, record by record in list order, a count of 0, a non-zero reserved
+ *   word, first + count past the stored count (computed without overflow) — the message names the smallest offending list position; then two ranges that share
+ *   a triangle — the message names the smallest pair of list positions (i, j), i < j, whose ranges meet.
+ * - BVH contexts.  Every listed triangle's vertex rows are written, its prepared record, material index slot and unit normal are remade; the box of every leaf
+ *   that holds a listed triangle and of every node from there to the root is recomputed by the refit's rule, deepest level first; the wide form's copies are
+ *   refreshed; EVERY OTHER BOX IS LEFT AS IT IS, as in the sparse update.  The context then renders exactly what a full upload of
+ *   (refit_bvh(nodes, posed, touched = the listed positions), posed, mats) renders: images, statistics and kernel path.  (The 4-wide form keeps the grouping
+ *   the upload made, as after every update form; a fresh upload of a tree moved far may group its children anew and then asks for other LDS bytes, never for
+ *   another image.)  Ray and path queries answer on the posed scene with `prim` numbered as before.
+ * - Brute-force contexts keep the rest pose on the host: the stored records are read back, the listed ranges are posed there, and the plain update form runs,
+ *   as the sparse form does there.
+ * - Frames in flight finish on the old geometry; `moves` may be freed on return; the accumulate / reset rule stays with the caller; rvpt_hip_last_error is
+ *   empty afterwards.  There is no guarded pose update: a caller who wants a fresh tree for a pose calls a build form with the posed triangles
+ *   (scene.pose_parts of its own rest triangles gives the same bits).  The laboratory's caller-layout knob has no sparse form and so no pose form: the same error.
+ * - Every other form behaves and reports exactly as before.
+ * Cost on one MI355X: profiles/pose_update.txt; DESIGN.md 5.16. */
+typedef struct rvpt_part_move {      /* 64 bytes */
+    float    m[12];                  /* 3x4, row major: x' = m[0] x + m[1] y + m[2] z + m[3], y' from m[4..7], z' from m[8..11] */
+    uint32_t first, count;           /* the triangles [first, first + count) */
+    uint32_t reserved[2];            /* must be 0 */
+} rvpt_part_move;
+#define RVPT_HIP_NODES_UPDATE_POSE ((size_t)-5)
 #define RVPT_HIP_NODES_UPDATE_GUARDED(permille) ((size_t)0 - (size_t)(0x10000u + (permille)))
 #define RVPT_HIP_NODES_BUILD ((size_t)-1)
 #define RVPT_HIP_NODES_BUILD_PLOC ((size_t)-2)

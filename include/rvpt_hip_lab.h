@@ -104,6 +104,8 @@ int rvpt_bvh_wide_form(const rvpt_bvh_node *nodes, size_t n_nodes, uint32_t head
  *   SPARSE_PARENT, SPARSE_DIRTY   one word per node up to the end of the last level, SPARSE_LEAF_OF  n_tris words: the sparse update's maps and flags, while
  *                  have_sparse_maps (made by the first sparse update after a full upload, build or rebuild)
  *   INV_PERM       n_tris words while have_inv_perm: the inverse of PERM
+ *   REST           n_tris x 48 B while the context holds a rest pose for the stored scene (include/rvpt_hip.h: POSE UPDATE — taken by the first pose update after
+ *                  a successful call of any other form, dropped by the next such call): vert0..vert2 of every triangle, in stored order; 0 bytes otherwise
  * dst == NULL or dst_capacity < the live size of a piece that has bytes: RVPT_HIP_ERR_SIZE, *bytes_out = the size needed, nothing written.  A context without a
  * scene: RVPT_HIP_ERR_INVALID. */
 typedef struct rvpt_hip_scene_state_info {
@@ -114,7 +116,8 @@ typedef struct rvpt_hip_scene_state_info {
 } rvpt_hip_scene_state_info;
 enum {
     RVPT_HIP_STATE_NONE = 0, RVPT_HIP_STATE_NODES = 1, RVPT_HIP_STATE_TRIS = 2, RVPT_HIP_STATE_PERM = 3, RVPT_HIP_STATE_WIDE = 4, RVPT_HIP_STATE_WIDE_MAP = 5,
-    RVPT_HIP_STATE_REFIT_LEVELS = 6, RVPT_HIP_STATE_SPARSE_PARENT = 7, RVPT_HIP_STATE_SPARSE_LEAF_OF = 8, RVPT_HIP_STATE_SPARSE_DIRTY = 9, RVPT_HIP_STATE_INV_PERM = 10
+    RVPT_HIP_STATE_REFIT_LEVELS = 6, RVPT_HIP_STATE_SPARSE_PARENT = 7, RVPT_HIP_STATE_SPARSE_LEAF_OF = 8, RVPT_HIP_STATE_SPARSE_DIRTY = 9, RVPT_HIP_STATE_INV_PERM = 10,
+    RVPT_HIP_STATE_REST = 11
 };
 int rvpt_hip_selftest_scene_state(rvpt_hip_ctx *ctx, rvpt_hip_scene_state_info *info, uint32_t piece, void *dst, size_t dst_capacity, size_t *bytes_out);
 

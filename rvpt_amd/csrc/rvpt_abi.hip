@@ -69,7 +69,8 @@ static_assert(sizeof(rvpt_ray_hit) == rv::kQueryRecordBytes && offsetof(rvpt_ray
 static_assert(sizeof(rvpt_ray_path) == rv::kPathRecordBytes && offsetof(rvpt_ray_path, seed) == 12 && offsetof(rvpt_ray_path, dir) == 16 && offsetof(rvpt_ray_path, max_bounces) == 28 &&
                   offsetof(rvpt_ray_path, radiance) == 32 && offsetof(rvpt_ray_path, segments) == 44 && RVPT_HIP_PATH_MAX_BOUNCES == rv::kPathMaxBounces,
               "a path query's record: three float4 (rvpt_paths.hip)");
-static_assert(sizeof(rvpt_ray_path) == sizeof(rvpt_ray_hit) && offsetof(rvpt_ray_path, radiance) == offsetof(rvpt_ray_hit, t), "ray and path queries share query_records");
+static_assert(sizeof(rvpt_part_move) == 64 && offsetof(rvpt_part_move, first) == 48 && offsetof(rvpt_part_move, count) == 52, "rvpt_part_move: the sixteen words rv::pose_parts reads");
+static_assert(sizeof(rvpt_ray_path) == sizeof(rvpt_ray_hit) &&offsetof(rvpt_ray_path, radiance) == offsetof(rvpt_ray_hit, t), "ray and path queries share query_records");
 static_assert(offsetof(rvpt_triangle, mat_id) == 48 && offsetof(rvpt_bvh_node, bounds) == 8 &&
                   offsetof(rvpt_material, data) == 32 && offsetof(rvpt_render_settings, split_ratio) == 32 &&
                   offsetof(rvpt_camera_data, params) == 64,
@@ -155,6 +156,13 @@ struct rvpt_hip_ctx {
     uint32_t *d_sparse_words = nullptr, *h_sparse_words = nullptr;
     unsigned char *d_sparse_stage = nullptr;
     size_t cap_sparse_stage = 0;
+    // the POSE UPDATE of upload_scene (include/rvpt_hip.h): the REST POSE — the 48 vertex bytes of every stored triangle, in stored order, as the last call of
+    // any other form left them.  have_rest: the snapshot belongs to the stored scene; dropped by every successful call of another form, taken again by the
+    // next pose update.  BVH contexts keep it on the device (three quads per triangle), brute-force contexts on the host (twelve floats per triangle).
+    float4 *d_rest = nullptr;
+    size_t cap_rest = 0;
+    std::vector<float> h_rest;
+    bool have_rest = false;
     bool have_scene = false;
     // RAY QUERIES and PATH QUERIES (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS / RVPT_HIP_FORMAT_RAY_PATHS; rvpt_query.h, rvpt_paths.h): the staging buffer of host records (bytes) and the launch's scratch — 64 words whose
     // first is the claim counter, then the global part of the traversal stack (words).  Both only grow.
@@ -1014,7 +1022,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     void *bufs[] = {ctx->d_tris, ctx->d_prep, ctx->d_mats, ctx->d_nodes, ctx->d_wide, ctx->d_wide_map, ctx->d_mat_index, ctx->d_unit_n, ctx->d_accum,
                     ctx->d_rowmajor, ctx->d_counter, ctx->d_stats, ctx->d_perm, ctx->d_build, ctx->d_build_temp, ctx->d_build_counters, ctx->d_cost, ctx->d_carry,
                     ctx->d_sparse_parent, ctx->d_sparse_leaf_of, ctx->d_sparse_dirty, ctx->d_sparse_claim, ctx->d_inv_perm, ctx->d_sparse_words, ctx->d_sparse_stage,
-                    ctx->d_query_stage, ctx->d_query_scratch};
+                    ctx->d_query_stage, ctx->d_query_scratch, ctx->d_rest};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1454,6 +1462,67 @@ static int sparse_validate_host(rvpt_hip_ctx *ctx, const uint32_t *indices, size
     return RVPT_HIP_OK;
 }
 
+// What the sparse update and the pose update share (BVH contexts with a level table).
+// The permutation's inverse: after a build form the caller's indices are not positions.  It reads and writes nothing a frame in flight uses.
+static int ensure_inverse_permutation(rvpt_hip_ctx *ctx)
+{
+    if (!ctx->have_perm || ctx->have_inv_perm) return RVPT_HIP_OK;
+    const size_t n_tris = ctx->n_tris;
+    const uint32_t n = static_cast<uint32_t>(n_tris);
+    if (int rc = grow(ctx, ctx->d_inv_perm, ctx->cap_inv_perm, n_tris, sizeof(uint32_t))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_inv_perm, 0xFF, n_tris * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(rv::sparse_invert_permutation, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_perm, n, ctx->d_inv_perm);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->have_inv_perm = true;
+    return RVPT_HIP_OK;
+}
+
+// The maps of the stored topology, made on the first sparse or pose update after any full upload, build or rebuild.  n_nodes: the end of the last level.
+static int ensure_sparse_maps(rvpt_hip_ctx *ctx, uint32_t n_nodes)
+{
+    if (ctx->have_sparse_maps) return RVPT_HIP_OK;
+    int rc;
+    const size_t n_tris = ctx->n_tris;
+    if ((rc = grow(ctx, ctx->d_sparse_parent, ctx->cap_sparse_parent, n_nodes, sizeof(uint32_t)))) return rc;
+    if ((rc = grow(ctx, ctx->d_sparse_dirty, ctx->cap_sparse_dirty, n_nodes, sizeof(uint32_t)))) return rc;
+    if ((rc = grow(ctx, ctx->d_sparse_leaf_of, ctx->cap_sparse_leaf_of, n_tris, sizeof(uint32_t)))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_parent, 0xFF, n_nodes * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_dirty, 0, n_nodes * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_leaf_of, 0xFF, n_tris * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(rv::sparse_topology, dim3((n_nodes + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_nodes, n_nodes, static_cast<uint32_t>(n_tris), ctx->d_sparse_parent,
+                       ctx->d_sparse_leaf_of);
+    HIP_TRY(ctx, hipGetLastError());
+    return RVPT_HIP_OK;
+}
+
+// The tail of both forms, behind the launch that wrote the rows of d_tris and flagged their paths (have_sparse_maps is false while flags may be set):
+// prepare_triangles as it is over the rows [span_lo, span_hi] — records, material index slots and unit normals —, the flagged nodes refitted level by level,
+// deepest first, the wide form's copies gathered again, and the stream waited for: the caller may free its arrays on return.
+static int refit_flagged_paths(rvpt_hip_ctx *ctx, uint32_t n_nodes, uint32_t span_lo, uint32_t span_hi)
+{
+    const uint32_t n = static_cast<uint32_t>(ctx->n_tris);
+    {
+        const uint32_t rows = span_hi - span_lo + 1u;
+        hipLaunchKernelGGL(rv::prepare_triangles, dim3((rows + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_tris + 4u * static_cast<size_t>(span_lo), rows,
+                           ctx->d_prep + 4u * static_cast<size_t>(span_lo), ctx->d_mat_index + span_lo, ctx->d_unit_n + span_lo);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    for (size_t l = ctx->refit_levels.size(); l-- > 0;) {
+        const auto [begin, end] = ctx->refit_levels[l];
+        hipLaunchKernelGGL(rv::refit_level_dirty, dim3((end - begin + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_nodes, begin, end, n_nodes, ctx->d_tris, n, ctx->d_sparse_dirty);
+    }
+    if (ctx->n_wide) {
+        const uint32_t n_slots = static_cast<uint32_t>(ctx->n_wide * 4);
+        hipLaunchKernelGGL(rv::refit_wide_gather, dim3((n_slots + 255u) / 256u), dim3(256), 0, ctx->stream, reinterpret_cast<float *>(ctx->d_wide), ctx->d_wide_map, n_slots, ctx->d_nodes,
+                           static_cast<uint32_t>(ctx->n_nodes));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->have_sparse_maps = true;
+    ctx->scene_gen += 1;  // the slots' screen rectangles and sky lists belong to the old geometry
+    return RVPT_HIP_OK;
+}
+
 // The SPARSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): `indices` names k stored triangles, tris[j] replaces the vertices of triangle indices[j].
 // Everything is validated before anything stored is touched — a host list on the host, a device list by two kernels and one read of four words, with the same
 // answers.  BVH contexts: the rows are scattered into d_tris, the paths from their leaves to the root are flagged, prepare_triangles runs over the span of rows
@@ -1512,15 +1581,8 @@ static int update_geometry_sparse(rvpt_hip_ctx *ctx, const uint32_t *indices, co
     const uint32_t *d_indices = indices;
     const float4 *d_src = reinterpret_cast<const float4 *>(tris);
     if (!device_tris && (rc = sparse_validate_host(ctx, indices, k, n_tris, &span_lo, &span_hi))) return rc;
-    // the permutation's inverse: after a build form the caller's indices are not positions.  Needed by the device validation's span, so made in front of
-    // it; it reads and writes nothing a frame in flight uses
-    if (ctx->have_perm && !ctx->have_inv_perm) {
-        if ((rc = grow(ctx, ctx->d_inv_perm, ctx->cap_inv_perm, n_tris, sizeof(uint32_t)))) return rc;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_inv_perm, 0xFF, n_tris * sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(rv::sparse_invert_permutation, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_perm, n, ctx->d_inv_perm);
-        HIP_TRY(ctx, hipGetLastError());
-        ctx->have_inv_perm = true;
-    }
+    // the permutation's inverse is needed by the device validation's span, so made in front of it
+    if ((rc = ensure_inverse_permutation(ctx))) return rc;
     const uint32_t *const inv_perm = ctx->have_perm ? ctx->d_inv_perm : nullptr;
     if (!device_tris) {  // a validated host list is staged: the indices behind the records
         if (inv_perm) span_lo = 0, span_hi = n - 1u;  // (the positions are known on the device alone: the whole buffer)
@@ -1554,41 +1616,152 @@ static int update_geometry_sparse(rvpt_hip_ctx *ctx, const uint32_t *indices, co
         span_lo = h[rv::kSparseSpanLo], span_hi = h[rv::kSparseSpanHi];
         if (span_lo > span_hi || span_hi >= n) span_lo = 0, span_hi = n - 1u;
     }
-    // the maps of the stored topology, made on the first sparse update after any full upload, build or rebuild
-    if (!ctx->have_sparse_maps) {
-        if ((rc = grow(ctx, ctx->d_sparse_parent, ctx->cap_sparse_parent, n_nodes, sizeof(uint32_t)))) return rc;
-        if ((rc = grow(ctx, ctx->d_sparse_dirty, ctx->cap_sparse_dirty, n_nodes, sizeof(uint32_t)))) return rc;
-        if ((rc = grow(ctx, ctx->d_sparse_leaf_of, ctx->cap_sparse_leaf_of, n_tris, sizeof(uint32_t)))) return rc;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_parent, 0xFF, n_nodes * sizeof(uint32_t), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_dirty, 0, n_nodes * sizeof(uint32_t), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sparse_leaf_of, 0xFF, n_tris * sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(rv::sparse_topology, dim3((n_nodes + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_nodes, n_nodes, n, ctx->d_sparse_parent, ctx->d_sparse_leaf_of);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    if ((rc = ensure_sparse_maps(ctx, n_nodes))) return rc;
     if (int rc0 = sync_all(ctx)) return rc0;  // frames in flight finish on the old geometry
     ctx->have_sparse_maps = false;  // (until the flags are known to be all zero again: after an error below the next update starts from fresh maps)
     hipLaunchKernelGGL(rv::sparse_scatter, dim3((kk + 255u) / 256u), dim3(256), 0, ctx->stream, d_src, d_indices, kk, n, inv_perm, ctx->d_tris, ctx->d_sparse_leaf_of, ctx->d_sparse_parent,
                        n_nodes, ctx->d_sparse_dirty);
     HIP_TRY(ctx, hipGetLastError());
-    {  // prepare_triangles as it is, over the rows [span_lo, span_hi]: records, material index slots and unit normals
-        const uint32_t rows = span_hi - span_lo + 1u;
-        hipLaunchKernelGGL(rv::prepare_triangles, dim3((rows + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_tris + 4u * static_cast<size_t>(span_lo), rows,
-                           ctx->d_prep + 4u * static_cast<size_t>(span_lo), ctx->d_mat_index + span_lo, ctx->d_unit_n + span_lo);
-        HIP_TRY(ctx, hipGetLastError());
+    return refit_flagged_paths(ctx, n_nodes, span_lo, span_hi);
+}
+
+// the pose update's list, checked on the host before anything stored is touched: per record, in list order, a count of 0, a non-zero reserved word, a range
+// that leaves the stored scene (the first position that offends in any of these ways is named); then two ranges that share a triangle — the ranges are sorted
+// by `first`, as sparse_validate_host sorts indices, and the message names the smallest pair of list positions (i, j), i < j, whose ranges meet.  total_out: the
+// triangles listed; lo_out / hi_out: the span of their indices.
+static int pose_validate_host(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, size_t k, size_t n_tris, uint32_t *total_out, uint32_t *lo_out, uint32_t *hi_out)
+{
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (size_t p = 0; p < k; ++p) {
+        const rvpt_part_move &m = moves[p];
+        if (m.count == 0) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update: moves[%zu] has a count of 0: a part holds at least one triangle", p);
+        if (m.reserved[0] != 0 || m.reserved[1] != 0)
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update: moves[%zu] has the reserved words %u, %u: they must be 0", p, m.reserved[0], m.reserved[1]);
+        if (m.first >= n_tris || m.count > n_tris - m.first)  // (first + count > n_tris, without the sum)
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update: moves[%zu] = [%u, %u + %u) is outside the %zu stored triangles", p, m.first, m.first, m.count, n_tris);
+        lo = std::min(lo, m.first), hi = std::max(hi, m.first + (m.count - 1u));
     }
-    for (size_t l = ctx->refit_levels.size(); l-- > 0;) {
-        const auto [begin, end] = ctx->refit_levels[l];
-        hipLaunchKernelGGL(rv::refit_level_dirty, dim3((end - begin + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_nodes, begin, end, n_nodes, ctx->d_tris, n, ctx->d_sparse_dirty);
+    std::vector<uint32_t> order(k);
+    for (size_t p = 0; p < k; ++p) order[p] = static_cast<uint32_t>(p);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return moves[a].first != moves[b].first ? moves[a].first < moves[b].first : a < b; });
+    // a range meets another iff it meets one of its neighbours in the sorted order, the furthest-reaching range in front of it taken for the predecessor
+    size_t smallest = k;
+    uint64_t reach = 0;  // the largest end of the ranges in front of slot s
+    for (size_t s = 0; s < k; ++s) {
+        const rvpt_part_move &m = moves[order[s]];
+        const uint64_t end = static_cast<uint64_t>(m.first) + m.count;
+        const bool meets = (s > 0 && reach > m.first) || (s + 1 < k && moves[order[s + 1]].first < end);
+        if (meets) smallest = std::min<size_t>(smallest, order[s]);
+        reach = std::max(reach, end);
     }
-    if (ctx->n_wide) {
-        const uint32_t n_slots = static_cast<uint32_t>(ctx->n_wide * 4);
-        hipLaunchKernelGGL(rv::refit_wide_gather, dim3((n_slots + 255u) / 256u), dim3(256), 0, ctx->stream, reinterpret_cast<float *>(ctx->d_wide), ctx->d_wide_map, n_slots, ctx->d_nodes,
-                           static_cast<uint32_t>(ctx->n_nodes));
+    if (smallest < k) {
+        const rvpt_part_move &a = moves[smallest];
+        for (size_t q = 0; q < k; ++q) {  // (every range that meets moves[smallest] lies behind it in the list: it is the smallest position that meets any)
+            const rvpt_part_move &b = moves[q];
+            if (q == smallest || static_cast<uint64_t>(b.first) >= static_cast<uint64_t>(a.first) + a.count || static_cast<uint64_t>(a.first) >= static_cast<uint64_t>(b.first) + b.count) continue;
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update: moves[%zu] = [%u, %u + %u) and moves[%zu] = [%u, %u + %u) share triangle %u: a triangle belongs to one part", smallest,
+                        a.first, a.first, a.count, q, b.first, b.first, b.count, std::max(a.first, b.first));
+        }
     }
+    *total_out = 0;
+    for (size_t p = 0; p < k; ++p) *total_out += moves[p].count;  // (disjoint ranges inside the scene: at most n_tris)
+    *lo_out = lo, *hi_out = hi;
+    return RVPT_HIP_OK;
+}
+
+// one vertex through one 3x4 matrix, the host form of rv::pose_vertex: three products and three sums per component, each rounded to binary32 on its own, in the
+// order ((m0 x + m1 y) + m2 z) + m3.  This file is compiled with -ffp-contract=off (rvpt_amd/build.py), so the expressions below are not fused.
+static void pose_vertex_host(const float m[12], const float p[3], float out[3])
+{
+    for (int i = 0; i < 3; ++i) {
+        const float a = m[4 * i] * p[0], b = m[4 * i + 1] * p[1], c = m[4 * i + 2] * p[2];
+        const float ab = a + b;
+        const float abc = ab + c;
+        out[i] = abc + m[4 * i + 3];
+    }
+}
+
+// The POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): `moves` names k disjoint ranges of stored triangles and one 3x4 matrix per range.  Everything is
+// validated on the host before anything stored is touched.  BVH contexts: the rest pose is snapshotted on the device if the context holds none for the stored
+// scene, rv::pose_parts poses the listed rows of d_tris from it and flags their paths, and the sparse update's tail does the rest.  Brute-force contexts keep the
+// rest pose on the host: the stored records are read back, the listed ranges are posed there, and the plain update form runs.
+static int update_geometry_pose(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats)
+{
+    if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update before any full upload_scene on this context: there is no scene to update");
+    if (k == 0) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update without parts");
+    const size_t n_tris = ctx->n_tris;
+    if (k > n_tris) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update with %zu parts, the uploaded scene has %zu triangles", k, n_tris);
+    if (!moves) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update without a list: `nodes` points at one rvpt_part_move per part");
+    if (reinterpret_cast<uintptr_t>(moves) % 4u) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update: the list at %p is not 4-byte aligned", static_cast<const void *>(moves));
+    if (tris) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update takes no triangles: the library poses the ones it holds (`tris` must be NULL)");
+    if (mats || n_mats) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update takes no materials: it keeps the stored ones");
+    const bool bvh = is_bvh(ctx, n_tris);
+    if (bvh && ctx->refit_levels.empty())  // (the laboratory's knob only, as in the plain form)
+#if RVPT_HIP_LAB
+        return fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "geometry update needs the breadth-first device layout of the tree: RVPT_HIP_BVH_CALLER_LAYOUT keeps the caller's, which has no level ranges");
+#else
+        return fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "geometry update needs the level ranges of the tree's device layout, which this context does not hold");
+#endif
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (is_device_pointer(moves))
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update: the list at %p is device memory: this form takes its list from the host (64 bytes per part)", static_cast<const void *>(moves));
+    uint32_t total = 0, span_lo = 0, span_hi = 0;
+    if (int rc0 = pose_validate_host(ctx, moves, k, n_tris, &total, &span_lo, &span_hi)) return rc0;
+    const uint32_t n = static_cast<uint32_t>(n_tris), kk = static_cast<uint32_t>(k);
+
+    if (!bvh) {  // the rest pose on the host, the posed records through the plain form
+        if (int rc0 = sync_all(ctx)) return rc0;
+        std::vector<rvpt_triangle> posed(n_tris);
+        HIP_TRY(ctx, hipMemcpy(posed.data(), ctx->d_tris, n_tris * sizeof(rvpt_triangle), hipMemcpyDeviceToHost));
+        if (!ctx->have_rest) {
+            ctx->h_rest.resize(12 * n_tris);
+            for (size_t t = 0; t < n_tris; ++t) std::memcpy(&ctx->h_rest[12 * t], &posed[t], offsetof(rvpt_triangle, mat_id));
+            ctx->have_rest = true;
+        }
+        for (size_t p = 0; p < k; ++p)
+            for (size_t t = moves[p].first; t < static_cast<size_t>(moves[p].first) + moves[p].count; ++t) {
+                const float *r = &ctx->h_rest[12 * t];
+                float *rows[3] = {posed[t].vert0, posed[t].vert1, posed[t].vert2};
+                for (int v = 0; v < 3; ++v) {
+                    pose_vertex_host(moves[p].m, r + 4 * v, rows[v]);
+                    rows[v][3] = r[4 * v + 3];
+                }
+            }
+        const int rc0 = update_geometry(ctx, posed.data(), n_tris);
+        if (rc0 == RVPT_HIP_OK) ctx->err.clear();
+        return rc0;
+    }
+
+    int rc;
+    const uint32_t n_nodes = static_cast<uint32_t>(std::min<size_t>(ctx->n_nodes, ctx->refit_levels.back().second));
+    if ((rc = ensure_inverse_permutation(ctx))) return rc;
+    const uint32_t *const inv_perm = ctx->have_perm ? ctx->d_inv_perm : nullptr;
+    if (inv_perm) span_lo = 0, span_hi = n - 1u;  // (the positions are known on the device alone: the whole buffer)
+    // the list and the exclusive sums of its counts, staged where a sparse update stages its rows
+    std::vector<uint32_t> prefix(k + 1);
+    prefix[0] = 0;
+    for (size_t p = 0; p < k; ++p) prefix[p + 1] = prefix[p] + moves[p].count;
+    if ((rc = grow(ctx, ctx->d_sparse_stage, ctx->cap_sparse_stage, k * sizeof(rvpt_part_move) + (k + 1) * sizeof(uint32_t), 1))) return rc;
+    if ((rc = ensure_sparse_maps(ctx, n_nodes))) return rc;
+    if (!ctx->have_rest && (rc = grow(ctx, ctx->d_rest, ctx->cap_rest, 3 * n_tris, sizeof(float4)))) return rc;
+    if (int rc0 = sync_all(ctx)) return rc0;  // frames in flight finish on the old geometry
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sparse_stage, moves, k * sizeof(rvpt_part_move), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sparse_stage + k * sizeof(rvpt_part_move), prefix.data(), (k + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (!ctx->have_rest) {  // the snapshot: 48 of every 64 bytes of d_tris, device to device, in stored order
+        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_rest, offsetof(rvpt_triangle, mat_id), ctx->d_tris, sizeof(rvpt_triangle), offsetof(rvpt_triangle, mat_id), n_tris, hipMemcpyDeviceToDevice,
+                                      ctx->stream));
+        ctx->have_rest = true;
+    }
+    ctx->have_sparse_maps = false;  // (until the flags are known to be all zero again, as in the sparse update)
+    hipLaunchKernelGGL(rv::pose_parts, dim3((total + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_rest, reinterpret_cast<const uint32_t *>(ctx->d_sparse_stage),
+                       reinterpret_cast<const uint32_t *>(ctx->d_sparse_stage + k * sizeof(rvpt_part_move)), kk, total, n, inv_perm, ctx->d_tris, ctx->d_sparse_leaf_of, ctx->d_sparse_parent,
+                       n_nodes, ctx->d_sparse_dirty);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // caller may free its arrays on return
-    ctx->have_sparse_maps = true;
-    ctx->scene_gen += 1;  // the slots' screen rectangles and sky lists belong to the old geometry
+    if ((rc = refit_flagged_paths(ctx, n_nodes, span_lo, span_hi))) {  // (prefix is read by the copy above until the stream has been waited for)
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    ctx->err.clear();
     return RVPT_HIP_OK;
 }
 
@@ -1627,10 +1800,22 @@ static int update_geometry_guarded(rvpt_hip_ctx *ctx, const rvpt_triangle *tris,
 
 }  // namespace
 
+static int upload_scene_other_forms(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes, const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats, size_t n_mats);
+
 int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes, const rvpt_triangle *tris,
                           size_t n_tris, const rvpt_material *mats, size_t n_mats)
 {
     if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
+    // the POSE UPDATE: the count RVPT_HIP_NODES_UPDATE_POSE, `nodes` then points at n_tris rvpt_part_move records and `tris` is NULL (the form checks that itself)
+    if (n_nodes == RVPT_HIP_NODES_UPDATE_POSE) return update_geometry_pose(ctx, reinterpret_cast<const rvpt_part_move *>(nodes), tris, n_tris, mats, n_mats);
+    const int rc = upload_scene_other_forms(ctx, nodes, n_nodes, tris, n_tris, mats, n_mats);
+    // the rest pose of the pose update is the stored vertices as the last successful call of any OTHER form left them: the next pose update snapshots afresh
+    if (rc == RVPT_HIP_OK || !ctx->have_scene) ctx->have_rest = false;
+    return rc;
+}
+
+static int upload_scene_other_forms(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t n_nodes, const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats, size_t n_mats)
+{
     if ((n_tris && !tris) || (n_mats && !mats)) return fail(ctx, RVPT_HIP_ERR_INVALID, "NULL scene array");
     if (n_tris > 0x3FFFFFFFull) return fail(ctx, RVPT_HIP_ERR_INVALID, "too many triangles");
     // the SPARSE UPDATE: the count RVPT_HIP_NODES_UPDATE_SPARSE, `nodes` then points at n_tris indices (n_tris == 0 arrives here too: the form says so itself)
@@ -2738,6 +2923,11 @@ int rvpt_hip_selftest_scene_state(rvpt_hip_ctx *ctx, rvpt_hip_scene_state_info *
     case RVPT_HIP_STATE_SPARSE_LEAF_OF: src = ctx->d_sparse_leaf_of, bytes = n_map_nodes ? n_tris * sizeof(uint32_t) : 0; break;
     case RVPT_HIP_STATE_SPARSE_DIRTY: src = ctx->d_sparse_dirty, bytes = n_map_nodes * sizeof(uint32_t); break;
     case RVPT_HIP_STATE_INV_PERM: src = ctx->d_inv_perm, bytes = ctx->have_perm && ctx->have_inv_perm ? n_tris * sizeof(uint32_t) : 0; break;
+    case RVPT_HIP_STATE_REST:  // the pose update's rest pose: on the device of a BVH context, on the host of a brute-force one
+        if (is_bvh(ctx, n_tris)) src = ctx->d_rest;
+        else src = ctx->h_rest.data(), host = true;
+        bytes = ctx->have_rest ? n_tris * offsetof(rvpt_triangle, mat_id) : 0;
+        break;
     default: return fail(ctx, RVPT_HIP_ERR_INVALID, "scene state: there is no piece %u", piece);
     }
     if (bytes_out) *bytes_out = bytes;

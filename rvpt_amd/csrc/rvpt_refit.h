@@ -37,4 +37,11 @@ __global__ void sparse_scatter(const float4 *__restrict__ src, const uint32_t *_
                                float4 *__restrict__ tris, const uint32_t *__restrict__ leaf_of, const uint32_t *__restrict__ parent, uint32_t n_nodes,
                                uint32_t *__restrict__ dirty);
 
+// The POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; rvpt_abi.hip: update_geometry_pose): one thread per listed triangle of a validated list, blocks
+// of 256.  rest: three quads per triangle in stored order; moves: k rvpt_part_move records as 16 words each; prefix: k + 1 exclusive sums of their counts,
+// prefix[k] = total; inv_perm may be null.  Writes the vertex rows of tris and flags the paths as sparse_scatter does.
+__global__ void pose_parts(const float4 *__restrict__ rest, const uint32_t *__restrict__ moves, const uint32_t *__restrict__ prefix, uint32_t k, uint32_t total,
+                           uint32_t n_tris, const uint32_t *__restrict__ inv_perm, float4 *__restrict__ tris, const uint32_t *__restrict__ leaf_of,
+                           const uint32_t *__restrict__ parent, uint32_t n_nodes, uint32_t *__restrict__ dirty);
+
 }  // namespace rv

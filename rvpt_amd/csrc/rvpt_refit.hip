@@ -244,4 +244,61 @@ __global__ void sparse_scatter(const float4 *__restrict__ src, const uint32_t *_
         if (atomicExch(&dirty[node], 1u) != 0u) break;
 }
 
+// ---- the pose update (include/rvpt_hip.h: POSE UPDATE) ---------------------------------------------------------------------------------------------------------
+// One thread per listed triangle of a VALIDATED list (ranges in range, no two sharing a triangle, so no two threads write one row).  moves: k records of 16
+// words (twelve floats of the matrix, first, count, two zero words); prefix: k + 1 words, the exclusive sums of the counts, prefix[k] = total.  Thread t finds
+// its part p — the last one with prefix[p] <= t — by binary search and takes triangle first[p] + (t - prefix[p]): consecutive lanes, consecutive triangles, and
+// the twelve floats are the same address across a wave wherever the wave lies inside one part.  The vertex rows are posed FROM THE REST POSE (three quads per
+// triangle, stored order), never from tris; every product and every sum is rounded on its own (__fmul_rn / __fadd_rn: no contraction whatever the flags).
+// The w lanes (the host-side face normal the live code never reads) are carried over from the rest pose; the mat_id quad of the row stays.
+// The flagging is sparse_scatter's walk, made once per run of equal leaves inside a wave: a lane whose predecessor in the wave holds the same leaf leaves the
+// walk to it.  The first lane of a wave, a lane behind one of another part, behind one past the end of the grid or behind one that was dropped always walks:
+// their leaves differ or are 0xFFFFFFFF.  No early return before the shuffle: every lane of the wave takes part in it.
+__device__ inline float4 pose_vertex(const float *__restrict__ m, float4 p)
+{
+    float4 q;
+    q.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[0], p.x), __fmul_rn(m[1], p.y)), __fmul_rn(m[2], p.z)), m[3]);
+    q.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[4], p.x), __fmul_rn(m[5], p.y)), __fmul_rn(m[6], p.z)), m[7]);
+    q.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[8], p.x), __fmul_rn(m[9], p.y)), __fmul_rn(m[10], p.z)), m[11]);
+    q.w = p.w;
+    return q;
+}
+
+__global__ __launch_bounds__(256) void pose_parts(const float4 *__restrict__ rest, const uint32_t *__restrict__ moves, const uint32_t *__restrict__ prefix, uint32_t k, uint32_t total,
+                                                  uint32_t n_tris, const uint32_t *__restrict__ inv_perm, float4 *__restrict__ tris, const uint32_t *__restrict__ leaf_of,
+                                                  const uint32_t *__restrict__ parent, uint32_t n_nodes, uint32_t *__restrict__ dirty)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t leaf = 0xFFFFFFFFu;
+    if (t < total && k > 0u) {
+        uint32_t lo = 0u, hi = k;  // prefix[lo] <= t < prefix[hi]
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (prefix[mid] <= t) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t *__restrict__ rec = moves + 16u * static_cast<size_t>(lo);
+        const uint32_t j = t - prefix[lo];
+        const uint32_t first = rec[12], count = rec[13];
+        if (j < count && first < n_tris && j < n_tris - first) {  // (the host validated the ranges; a stray word must not become an address)
+            const uint32_t idx = first + j;
+            const uint32_t pos = inv_perm ? inv_perm[idx] : idx;
+            if (pos < n_tris) {
+                const float *__restrict__ m = reinterpret_cast<const float *>(rec);
+                const float4 *__restrict__ src = rest + 3u * static_cast<size_t>(pos);
+                const float4 a = src[0], b = src[1], c = src[2];
+                float4 *row = tris + 4u * static_cast<size_t>(pos);
+                row[0] = pose_vertex(m, a), row[1] = pose_vertex(m, b), row[2] = pose_vertex(m, c);
+                leaf = leaf_of[pos];
+            }
+        }
+    }
+    const uint32_t before = static_cast<uint32_t>(__shfl_up(static_cast<int>(leaf), 1, 64));
+    if (leaf >= n_nodes) return;
+    if ((threadIdx.x & 63u) != 0u && before == leaf) return;
+    // (a path holds at most one node per level; the bound keeps a malformed map from looping)
+    for (uint32_t node = leaf, hops = 0; node < n_nodes && hops < 128u; node = parent[node], ++hops)
+        if (atomicExch(&dirty[node], 1u) != 0u) break;
+}
+
 }  // namespace rv

@@ -164,7 +164,8 @@ bool RVPT::initialize()
     nodes_stale_ = false;
     order_.clear();
     inverse_.clear();
-    device_built_ = options_.device_build && options_.bvh_traversal && !triangles_.empty();
+    have_rest_ = false;
+    device_built_ =options_.device_build && options_.bvh_traversal && !triangles_.empty();
     if (!triangles_.empty() && !device_built_) {
         nodes_.resize(2 * triangles_.size() - 1);
         std::vector<uint32_t> &order = order_;
@@ -212,6 +213,7 @@ bool RVPT::update_triangles_with(const std::vector<Triangle> &triangles, size_t 
             return false;
         triangles_ = triangles;
         previous_.valid = false;
+        have_rest_ = false;
         return true;
     }
     std::vector<Triangle> moved;
@@ -223,6 +225,7 @@ bool RVPT::update_triangles_with(const std::vector<Triangle> &triangles, size_t 
     sorted_.swap(moved);
     nodes_stale_ = true;
     previous_.valid = false;  // a new scene: nothing accumulated so far belongs to it
+    have_rest_ = false;  // the next pose_parts poses from these triangles
     return true;
 }
 
@@ -261,6 +264,91 @@ bool RVPT::update_triangles(const std::vector<uint32_t> &indices, const std::vec
         std::memcpy(triangles_[indices[j]].vertex0, triangles[j].vertex0, offsetof(Triangle, material_id));
         if (!device_built_) std::memcpy(sorted_[positions[j]].vertex0, triangles[j].vertex0, offsetof(Triangle, material_id));
     }
+    if (!device_built_) nodes_stale_ = true;  // (the host tree is tight: the full refit of bvh_nodes() is the sparse one)
+    previous_.valid = false;  // a new scene: nothing accumulated so far belongs to it
+    have_rest_ = false;
+    return true;
+}
+
+// (volatile: every product and every sum is stored before it is used, so no compiler and no flag can contract a pair into a fused multiply-add)
+void pose_vertex(const float m[12], const float in[4], float out[4])
+{
+    const float x = in[0], y = in[1], z = in[2], w = in[3];
+    for (int i = 0; i < 3; ++i) {
+        volatile float a = m[4 * i] * x, b = m[4 * i + 1] * y, c = m[4 * i + 2] * z;
+        volatile float s = a + b;
+        s = s + c;
+        s = s + m[4 * i + 3];
+        out[i] = s;
+    }
+    out[3] = w;
+}
+
+// The pose form: `nodes` carries rvpt_part_move records, the count is RVPT_HIP_NODES_UPDATE_POSE, no triangles go down.
+bool RVPT::pose_parts(const rvpt_part_move *moves, size_t k)
+{
+    if (!ctx_) {
+        error_ = "pose_parts before initialize()";
+        return false;
+    }
+    if (k == 0) return true;
+    if (!moves) {
+        error_ = "pose_parts: no moves given";
+        return false;
+    }
+    const size_t n = triangles_.size();
+    std::vector<char> listed(n, 0);
+    for (size_t p = 0; p < k; ++p) {
+        const rvpt_part_move &m = moves[p];
+        const std::string range = "moves[" + std::to_string(p) + "] = [" + std::to_string(m.first) + ", " + std::to_string(m.first) + " + " + std::to_string(m.count) + ")";
+        if (m.count == 0 || m.reserved[0] != 0 || m.reserved[1] != 0) {
+            error_ = "pose_parts: " + range + (m.count == 0 ? " has a count of 0" : " has a non-zero reserved word");
+            return false;
+        }
+        if (m.first >= n || m.count > n - m.first) {
+            error_ = "pose_parts: " + range + " is outside the " + std::to_string(n) + " triangles of the scene";
+            return false;
+        }
+        for (size_t t = m.first; t < size_t(m.first) + m.count; ++t) {
+            if (listed[t]) {
+                error_ = "pose_parts: " + range + " shares triangle " + std::to_string(t) + " with an earlier move";
+                return false;
+            }
+            listed[t] = 1;
+        }
+    }
+    std::vector<rvpt_part_move> runs;  // what goes down after a host build: one record per run of consecutive leaf-order positions
+    if (!device_built_) {
+        if (inverse_.size() != order_.size()) {
+            inverse_.resize(order_.size());
+            for (size_t i = 0; i < order_.size(); ++i) inverse_[order_[i]] = static_cast<uint32_t>(i);
+        }
+        std::vector<uint32_t> positions;
+        for (size_t p = 0; p < k; ++p) {
+            positions.assign(inverse_.begin() + moves[p].first, inverse_.begin() + moves[p].first + moves[p].count);
+            std::sort(positions.begin(), positions.end());
+            for (size_t j = 0; j < positions.size(); ++j) {
+                if (j > 0 && positions[j] == positions[j - 1] + 1u) {
+                    runs.back().count += 1;
+                } else {
+                    runs.push_back(moves[p]);
+                    runs.back().first = positions[j], runs.back().count = 1;
+                }
+            }
+        }
+    }
+    const rvpt_part_move *sent = device_built_ ? moves : runs.data();
+    const size_t n_sent = device_built_ ? k : runs.size();
+    if (!check(backend_.upload_scene(ctx_, reinterpret_cast<const rvpt_bvh_node *>(sent), RVPT_HIP_NODES_UPDATE_POSE, nullptr, n_sent, nullptr, 0), "rvpt_hip_upload_scene (pose update)"))
+        return false;
+    if (!have_rest_) rest_ = triangles_, have_rest_ = true;
+    for (size_t p = 0; p < k; ++p)
+        for (size_t t = moves[p].first; t < size_t(moves[p].first) + moves[p].count; ++t) {
+            pose_vertex(moves[p].m, rest_[t].vertex0, triangles_[t].vertex0);
+            pose_vertex(moves[p].m, rest_[t].vertex1, triangles_[t].vertex1);
+            pose_vertex(moves[p].m, rest_[t].vertex2, triangles_[t].vertex2);
+            if (!device_built_) std::memcpy(sorted_[inverse_[t]].vertex0, triangles_[t].vertex0, offsetof(Triangle, material_id));
+        }
     if (!device_built_) nodes_stale_ = true;  // (the host tree is tight: the full refit of bvh_nodes() is the sparse one)
     previous_.valid = false;  // a new scene: nothing accumulated so far belongs to it
     return true;

@@ -105,6 +105,9 @@ struct UpdateReport {
     double new_base_cost = 0;  // rebuilt: the new tree's cost, the base from here on
 };
 bool parse_update_report(const char *sentence, UpdateReport *report);
+// One vertex through the 3x4 matrix of a rvpt_part_move, the arithmetic of the pose update (include/rvpt_hip.h): out[i] = ((m[4i] x + m[4i+1] y) + m[4i+2] z) + m[4i+3],
+// three products and three sums, each rounded to binary32 on its own — never fused, whatever the compiler's flags; out[3] = in[3].  `out` may be `in`.
+void pose_vertex(const float m[12], const float in[4], float out[4]);
 
 class RVPT {
 public:
@@ -157,6 +160,14 @@ public:
     // mismatch never reaches the ABI; an index twice is the library's to refuse.  The host copies are patched, bvh_nodes() is refitted when next asked for.
     bool update_triangles(const std::vector<uint32_t> &indices, const std::vector<Triangle> &triangles);
 
+    // Rigid parts — the pose update (RVPT_HIP_NODES_UPDATE_POSE; include/rvpt_hip.h: POSE UPDATE): moves[p] names the triangles [first, first + count) in the
+    // order they were ADDED and carries one 3x4 matrix; the device poses them from the REST POSE — the triangles as the last initialize() or update_triangles
+    // left them; two poses of one part do not compose — and recomputes only the boxes above them.  After a device build the records go down as they are;
+    // after a host build a range of added triangles is scattered over the leaf order and goes down as one record per run of consecutive positions.  A range
+    // outside the scene, an empty one, a non-zero reserved word or two ranges that share a triangle never reach the ABI.  The host copies are posed by
+    // pose_vertex (the same bits as the device), bvh_nodes() is refitted when next asked for; the next update() restarts the accumulation.
+    bool pose_parts(const rvpt_part_move *moves, size_t k);
+
     // RGBA32F (width*height*4 floats) or RGBA8 (width*height*4 bytes), row-major, top row first
     std::vector<float> read_frame();
     std::vector<uint8_t> read_frame_rgba8();
@@ -204,6 +215,8 @@ private:
     std::vector<uint32_t> order_;       // primitive indices of the build: sorted_[i] = triangles_[order_[i]]
     std::vector<uint32_t> inverse_;     // ... and their inverse, made by the first sparse update: triangles_[j] lives at sorted_[inverse_[j]]
     bool device_built_ = false;         // the scene went up by the build form: no nodes_, sorted_, order_ on the host
+    std::vector<Triangle> rest_;        // pose_parts: the rest pose in the order the triangles were added, taken by the first pose after another form
+    bool have_rest_ = false;
     // PreviousFrameState (rvpt.h:211-219, rvpt.cpp:21-29); empty camera data never compares equal
     struct Previous {
         bool valid = false;

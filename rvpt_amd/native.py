@@ -41,6 +41,9 @@ TILE_SHIFT = 3  # RVPT_HIP_TILE_SHIFT: every row of the tile grid is rotated by 
 NODES_BUILD = C.c_size_t(-1).value  # RVPT_HIP_NODES_BUILD: upload_scene's node count for the build form (Context.build_scene)
 NODES_BUILD_SAH = C.c_size_t(-3).value  # RVPT_HIP_NODES_BUILD_SAH: the build form with rvpt_bvh_build's binned-SAH tree (Context.build_scene(method="sah"))
 NODES_UPDATE_SPARSE = C.c_size_t(-4).value  # RVPT_HIP_NODES_UPDATE_SPARSE: the sparse update (Context.update_triangles(indices=)): `nodes` then carries the indices
+NODES_UPDATE_POSE = C.c_size_t(-5).value  # RVPT_HIP_NODES_UPDATE_POSE: the pose update (Context.pose_parts): `nodes` then carries PART_MOVE_DTYPE records, no triangles
+# rvpt_part_move (64 B): a 3x4 matrix, row major, for the triangles [first, first + count); two reserved words, 0
+PART_MOVE_DTYPE = np.dtype([("m", "<f4", (12,)), ("first", "<u4"), ("count", "<u4"), ("reserved", "<u4", (2,))])
 NODES_UPDATE_GUARDED_BASE = 0x10000  # RVPT_HIP_NODES_UPDATE_GUARDED(permille) = (size_t)0 - (0x10000 + permille): the guarded update (Context.update_triangles(rebuild_above=))
 NODES_BUILD_PLOC = C.c_size_t(-2).value  # RVPT_HIP_NODES_BUILD_PLOC: the build form with a PLOC tree (Context.build_scene(method="ploc"))
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_SIZE, ERR_COMM = -1, -2, -3, -4, -5, -6
@@ -347,7 +350,7 @@ NODE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("bounds", "<f4", (6,
 SCENE_STATE_PIECES = {
     "nodes": (1, NODE_DTYPE, ()), "tris": (2, np.float32, (16,)), "perm": (3, np.uint32, ()), "wide": (4, np.float32, (8, 4)), "wide_map": (5, np.uint32, (4,)),
     "refit_levels": (6, np.uint32, (2,)), "sparse_parent": (7, np.uint32, ()), "sparse_leaf_of": (8, np.uint32, ()), "sparse_dirty": (9, np.uint32, ()),
-    "inv_perm": (10, np.uint32, ()),
+    "inv_perm": (10, np.uint32, ()), "rest": (11, np.float32, (12,)),
 }
 BUILT_BY = (None, "lbvh", "ploc", "sah")  # rvpt_hip_scene_state_info::built_by
 
@@ -500,6 +503,23 @@ class Context:
             raise NativeError(ERR_INVALID, f"update_triangles: {k} indices for {n} triangles")
         _check(self._L.rvpt_hip_upload_scene(self._h, iptr, NODES_UPDATE_SPARSE, ptr, n, None, 0), self._h, self._L)
         del keep, ikeep
+        return None
+
+    def pose_parts(self, moves) -> None:
+        """The POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): every move names a range of triangles [first, first + count) — in the order
+        update_triangles takes: the leaf order after upload_scene, the caller's own order after build_scene — and a 3x4 matrix; the device poses those triangles
+        from the REST POSE it keeps (the vertices as the last call of any other form left them; two poses of one part do not compose) and recomputes only the boxes
+        above them.  scene.pose_parts is the same on the host, bit for bit.  moves: a structured array of PART_MOVE_DTYPE, or a sequence of
+        (first, count, matrix) with a 3x4 matrix or a 4x4 matrix whose last row is 0 0 0 1.  A malformed matrix or a negative `first` is refused here; ranges that
+        overlap or leave the scene are left to the library, which names them.  An empty list changes nothing.  Returns None."""
+        from . import scene
+        try:
+            rec = scene.part_moves(moves)
+        except (ValueError, TypeError) as e:
+            raise NativeError(ERR_INVALID, f"pose_parts: {e}") from None
+        if rec.shape[0] == 0:
+            return None
+        _check(self._L.rvpt_hip_upload_scene(self._h, _ptr(rec), NODES_UPDATE_POSE, None, rec.shape[0], None, 0), self._h, self._L)
         return None
 
     def set_frame(self, settings: np.ndarray, camera: np.ndarray) -> None:

@@ -104,6 +104,7 @@ class RVPT:
         self._sorted_triangles: np.ndarray | None = None
         self._built_from: np.ndarray | None = None  # build="device": the triangles the device built its tree from, until the host statement is asked for
         self._current_triangles: np.ndarray | None = None  # ... and the triangles the scene holds now, in the order they were added
+        self._rest_triangles: np.ndarray | None = None  # pose_parts: the rest pose, in the order they were added — the triangles as the last call of another form left them
         self._previous_key = None  # default-constructed PreviousFrameState never compares equal (empty camera data)
         self._ctx: native.Context | None = None
         self._n_triangles: int | None = None
@@ -195,6 +196,7 @@ class RVPT:
             self.sorted_triangles = sorted_tris
             self._nodes_stale, self._stale_touched = self._bvh_nodes is not None, None
         self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
+        self._rest_triangles = None
         return report
 
     def _update_sparse(self, triangles, rebuild_above, indices) -> None:
@@ -237,6 +239,62 @@ class RVPT:
                 elif self._stale_touched is not None:
                     self._stale_touched = np.concatenate([self._stale_touched, pos])
         self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
+        self._rest_triangles = None
+        return None
+
+    def pose_parts(self, moves) -> None:
+        """Rigid parts — the POSE UPDATE (Context.pose_parts; include/rvpt_hip.h): every move is (first, count, matrix) or a native.PART_MOVE_DTYPE record and
+        names the triangles [first, first + count) in the order they were ADDED; the device poses them by the move's 3x4 matrix from the REST POSE — the
+        triangles as the last initialize() or update_triangles left them; two poses of one part do not compose — and recomputes only the boxes above them, as in
+        bvh_nodes.  scene.pose_parts is the statement.  The next update() restarts the accumulation, as after update_triangles.  After a host build a range of
+        added triangles is scattered over the leaf order: it goes down as one record per run of consecutive positions, all with the part's matrix."""
+        if self._ctx is None or self._n_triangles is None:
+            raise RuntimeError("pose_parts before initialize()")
+        try:
+            rec = scene.part_moves(moves)
+        except (ValueError, TypeError) as e:
+            raise native.NativeError(native.ERR_INVALID, f"pose_parts: {e}") from None
+        if rec.shape[0] == 0:
+            return None
+        n = self._n_triangles
+        current = np.concatenate(self.triangles) if self._current_triangles is None else self._current_triangles
+        rest = current if self._rest_triangles is None else self._rest_triangles
+        try:  # (ranges outside the scene and ranges that share a triangle: refused here in the added numbering, before anything is sent)
+            if (rec["count"] == 0).any():
+                raise ValueError(f"moves[{int(np.argmax(rec['count'] == 0))}] has a count of 0")
+            posed = scene.pose_parts(rest, rec, current=current)
+        except ValueError as e:
+            raise native.NativeError(native.ERR_INVALID, f"pose_parts: {e}") from None
+        idx = np.concatenate([np.arange(int(r["first"]), int(r["first"]) + int(r["count"]), dtype=np.int64) for r in rec])
+        pos = None
+        if self._built_from is None:  # (always so after a host build) added order -> leaf order through the inverse of primitive_indices
+            inverse = np.empty(n, dtype=np.int64)
+            inverse[np.asarray(self._primitive_indices, dtype=np.int64)] = np.arange(n)
+            pos = inverse[idx]
+        if self._device_built:  # the device keeps the permutation: the caller's numbering goes down as it is
+            self._ctx.pose_parts(rec)
+        else:  # a host-built tree: added order -> runs of consecutive positions in leaf order
+            runs = []
+            for r in rec:
+                p = np.sort(inverse[int(r["first"]):int(r["first"]) + int(r["count"])])
+                starts = np.flatnonzero(np.concatenate([[True], np.diff(p) != 1]))
+                ends = np.concatenate([starts[1:], [p.size]])
+                run = np.zeros(starts.size, dtype=native.PART_MOVE_DTYPE)
+                run["m"], run["first"], run["count"] = r["m"], p[starts], ends - starts
+                runs.append(run)
+            self._ctx.pose_parts(np.concatenate(runs))
+        self._rest_triangles = rest
+        self.triangles = [posed]
+        if self._device_built:
+            self._current_triangles = posed
+        if self._built_from is None:  # there is a host statement to keep right
+            self._sorted_triangles = posed[np.asarray(self._primitive_indices, dtype=np.int64)]
+            if self._bvh_nodes is not None:
+                if not self._nodes_stale:
+                    self._nodes_stale, self._stale_touched = True, pos
+                elif self._stale_touched is not None:
+                    self._stale_touched = np.concatenate([self._stale_touched, pos])
+        self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
         return None
 
     # -- lifecycle -----------------------------------------------------------------------------------------
@@ -244,6 +302,7 @@ class RVPT:
         tris = np.concatenate(self.triangles) if self.triangles else np.zeros((0, 16), np.float32)
         mats = np.stack(self.materials) if self.materials else np.zeros((0, 12), np.float32)
         self._n_triangles = tris.shape[0]
+        self._rest_triangles = None
         self._device_built = self.build in ("device", "device-ploc", "device-sah") and self.traversal != "brute" and tris.shape[0] > 0
         self._ctx = native.Context(self.width, self.height, self.device, self.tile_rank, self.tile_world, self._flags)
         if self._device_built:

@@ -558,6 +558,74 @@ def wobble(tris, phase: float, amplitude: float) -> np.ndarray:
     return t
 
 
+PART_MOVE_DTYPE = np.dtype([("m", "<f4", (12,)), ("first", "<u4"), ("count", "<u4"), ("reserved", "<u4", (2,))])  # rvpt_part_move (== native.PART_MOVE_DTYPE)
+
+
+def part_moves(moves) -> np.ndarray:
+    """A list of moves as PART_MOVE_DTYPE records: a structured array of that dtype as it is, or a sequence of (first, count, matrix) with a 3x4 matrix or a
+    4x4 matrix whose last row is 0 0 0 1.  Raises ValueError for anything else: a negative `first` or `count`, one past 2^32 - 1, a matrix of another shape."""
+    if isinstance(moves, np.ndarray) and moves.dtype == PART_MOVE_DTYPE:
+        return np.ascontiguousarray(moves).reshape(-1)
+    out = np.zeros(len(moves), dtype=PART_MOVE_DTYPE)
+    for p, move in enumerate(moves):
+        if isinstance(move, np.void) and move.dtype == PART_MOVE_DTYPE:  # (a record among tuples, part_move's say)
+            out[p] = move
+            continue
+        first, count, matrix = move
+        first, count = int(first), int(count)
+        if not 0 <= first <= 0xFFFFFFFF or not 0 <= count <= 0xFFFFFFFF:
+            raise ValueError(f"moves[{p}]: first = {first}, count = {count} is not a range of triangles")
+        m = np.asarray(matrix, dtype=np.float32)
+        if m.shape == (4, 4):
+            if m[3].tobytes() != np.array([0, 0, 0, 1], dtype=np.float32).tobytes():
+                raise ValueError(f"moves[{p}]: the last row of a 4x4 matrix must be 0 0 0 1, got {m[3].tolist()}")
+            m = m[:3]
+        if m.shape != (3, 4):
+            raise ValueError(f"moves[{p}]: the matrix is 3x4 or 4x4, got {m.shape}")
+        out[p] = (m.reshape(12), first, count, (0, 0))
+    return out
+
+
+def part_move(first: int, count: int, rotation=None, translation=None) -> np.ndarray:
+    """One rvpt_part_move row from a rotation (3x3, None: the identity) and a translation (3, None: none): x' = R x + t, rounded to float32."""
+    m = np.zeros((3, 4), dtype=np.float32)
+    m[:, :3] = np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64).reshape(3, 3)
+    if translation is not None:
+        m[:, 3] = np.asarray(translation, dtype=np.float64).reshape(3)
+    return part_moves([(first, count, m)])[0]
+
+
+def pose_parts(rest_tris, moves, current=None) -> np.ndarray:
+    """The normative statement of the POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): the triangles [first, first + count) of every move are posed FROM
+    `rest_tris` by the move's 3x4 matrix; every other row is `current`'s (None: rest_tris').  Per vertex and output component i the value is
+    ((m[4i]*x + m[4i+1]*y) + m[4i+2]*z) + m[4i+3] in float32: three products and three sums, each rounded on its own — numpy never fuses — so the device and the
+    host give the same bits.  Only x, y, z of the three vertices change: the .w lanes are the rest pose's, the material row is `current`'s.
+    moves: what part_moves takes.  The ranges must lie inside the array and share no triangle (ValueError).  float32[n, 16] -> a new float32[n, 16]."""
+    rest = np.ascontiguousarray(rest_tris, dtype=np.float32).reshape(-1, 16)
+    out = rest.copy() if current is None else np.array(current, dtype=np.float32).reshape(-1, 16)
+    if out.shape != rest.shape:
+        raise ValueError(f"pose_parts: current has {out.shape[0]} triangles, the rest pose {rest.shape[0]}")
+    rec = part_moves(moves)
+    taken = np.zeros(rest.shape[0], dtype=bool)
+    for p, r in enumerate(rec):
+        first, count = int(r["first"]), int(r["count"])
+        if first + count > rest.shape[0]:
+            raise ValueError(f"pose_parts: moves[{p}] = [{first}, {first} + {count}) is outside the {rest.shape[0]} triangles")
+        if taken[first:first + count].any():
+            raise ValueError(f"pose_parts: moves[{p}] shares triangle {first + int(np.argmax(taken[first:first + count]))} with an earlier move")
+        taken[first:first + count] = True
+        m = r["m"].reshape(3, 4)
+        v = rest[first:first + count].reshape(-1, 4, 4)[:, :3, :]  # [count, vertex, xyzw]
+        x, y, z = v[..., 0:1], v[..., 1:2], v[..., 2:3]
+        with np.errstate(all="ignore"):
+            xyz = ((m[:, 0] * x + m[:, 1] * y) + m[:, 2] * z) + m[:, 3]  # float32 throughout: [count, vertex, i]
+        rows = out[first:first + count].reshape(-1, 4, 4)
+        rows[:, :3, :3] = xyz
+        rows[:, :3, 3] = v[..., 3]
+        out[first:first + count] = rows.reshape(-1, 16)
+    return out
+
+
 def load_obj_positions(path) -> np.ndarray:
     """Minimal Wavefront OBJ reader: `v` records and `f` records (v, v/vt, v/vt/vn, v//vn, negative
     indices); polygons are fan-triangulated (tinyobjloader's default `triangulate=true`, which is

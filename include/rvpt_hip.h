@@ -63,7 +63,10 @@ extern "C" {
                                      PATH QUERY: `dst` holds rvpt_ray_path records, a ray, an RNG state and a bounce budget in, integrator_Kajiya's radiance out.  Still 8, no
                                      new symbol: the count RVPT_HIP_NODES_UPDATE_POSE with `nodes` pointing at a list of rvpt_part_move records — until then the
                                      "needs nodes" or "NULL scene array" error — is the POSE UPDATE: ranges of triangles move by one 3x4 matrix each, posed on
-                                     the device from a rest pose it keeps, and only the boxes on their paths to the root are recomputed */
+                                     the device from a rest pose it keeps, and only the boxes on their paths to the root are recomputed.  Still 8, no
+                                     new symbol: the same arguments under a count RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille) — until then the "NULL scene
+                                     array" error — are the GUARDED POSE UPDATE: the pose update, the SAH cost of the posed tree reported, and past a limit a
+                                     rebuild by the builder that made the tree, through which the rest pose follows its triangles */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -377,16 +380,51 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  * - Brute-force contexts keep the rest pose on the host: the stored records are read back, the listed ranges are posed there, and the plain update form runs,
  *   as the sparse form does there.
  * - Frames in flight finish on the old geometry; `moves` may be freed on return; the accumulate / reset rule stays with the caller; rvpt_hip_last_error is
- *   empty afterwards.  There is no guarded pose update: a caller who wants a fresh tree for a pose calls a build form with the posed triangles
- *   (scene.pose_parts of its own rest triangles gives the same bits).  The laboratory's caller-layout knob has no sparse form and so no pose form: the same error.
+ *   empty afterwards.  The GUARDED POSE UPDATE below is this form with the tree costed behind it and rebuilt past a limit.  The laboratory's caller-layout
+ *   knob has no sparse form and so no pose form: the same error.
  * - Every other form behaves and reports exactly as before.
- * Cost on one MI355X: profiles/pose_update.txt; DESIGN.md 5.16. */
+ * Cost on one MI355X: profiles/pose_update.txt; DESIGN.md 5.16.
+ *
+ * GUARDED POSE UPDATE — the pose update, then the cost of the posed tree, and a rebuild once it has gone stale; the rest pose survives the rebuild:
+ *
+ *     rvpt_hip_upload_scene(ctx, (const rvpt_bvh_node *)moves, RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille), NULL, k, NULL, 0);      k > 0
+ *
+ * permille is 0 (report only) or 1000 .. 65535, the guarded update's limit.  Any other value in the band is RVPT_HIP_ERR_INVALID and leaves the stored scene
+ * and the rest pose untouched.
+ * - BVH contexts.  Every refusal of the pose update comes first, in its words and its order.  Then the one refusal of this form: a limit on a tree that came
+ *   from an ordinary upload with the caller's own nodes is RVPT_HIP_ERR_INVALID — the library has no builder to name —, decided before anything is touched.
+ *   Report only (0) is legal there.
+ * - The pose update runs exactly as above: the snapshot if the context holds no rest pose, the listed rows posed from it, the boxes on their paths refitted.
+ *   Then the TREE COST of the stored tree is computed as in the guarded update; the boxes off the listed paths enter it as they are, loose ones included.
+ *   The base cost is the guarded update's.
+ * - With a limit, if cost > (permille / 1000) * base cost and the stored scene came from a build form, the library REBUILDS with that build form's method from
+ *   the posed vertices beside the stored mat_id rows, carried back into the caller's order, and the materials as the caller last passed them.  What the
+ *   context then holds — tree, permutation, level table, wide form, launch choice — is what
+ *   rvpt_hip_upload_scene(ctx, NULL, <that build count>, posed_in_caller_order, n_tris, mats, n_mats) leaves, and the base cost becomes the new tree's.
+ * - THE REST POSE GOES WITH THE REBUILD.  Its 48 bytes per triangle are carried into the caller's order by the old permutation and gathered back by the new
+ *   one, on the device (a second buffer of 48 bytes per triangle, allocated at the first such rebuild of a context).  The next pose update — plain or
+ *   guarded — poses from the same rest pose as before the rebuild: a caller sends absolute poses frame after frame, and they never compose.  A part not
+ *   listed keeps the pose it has.  `first` and `count` stay in the caller's order, as after any build form.
+ * - A successful call of this form, like one of the plain pose form, keeps the rest pose.  A rebuild that fails follows the build form's rule: the context is
+ *   left WITHOUT a scene, and the rest pose is dropped with it.
+ * - On success rvpt_hip_last_error holds ONE SENTENCE, one of
+ *       guarded pose update: cost <%.17g>, base cost <%.17g>, limit <permille> permille: refitted
+ *       guarded pose update: cost <%.17g>, base cost <%.17g>, limit <permille> permille: rebuilt (<lbvh|ploc|sah>), new base cost <%.17g>
+ *   where `cost` is that of the posed tree, the one the decision was taken by, and the name is that of the tree the scene then holds (a PLOC rebuild that
+ *   fell back names lbvh; the next rebuild is a PLOC build again).  The wrappers parse this wording.
+ * - Brute-force contexts hold no tree: there the count is the plain pose update, and rvpt_hip_last_error is empty afterwards.
+ * - Frames in flight finish on the old geometry; `moves` may be freed on return.  Every other form, the plain pose update included, behaves and reports
+ *   exactly as before, and after each of the others the next pose update takes a fresh snapshot.
+ * Measured on one MI355X, 1 M triangles (profiles/guarded_pose.txt): the guard adds 0.045 ms to the 0.140 ms pose of a 1 % part; a call that
+ * rebuilds takes 2.2 / 3.5 / 15.1 ms (LBVH / PLOC / SAH); a tenth of the mesh rotated by 2 degrees reports a ratio of 1.33 with the tree at 0.40 of a rebuilt
+ * one's rate, the same part carried across the scene 226.  A limit at or below 1.3 catches the first; nothing finer was measured. */
 typedef struct rvpt_part_move {      /* 64 bytes */
     float    m[12];                  /* 3x4, row major: x' = m[0] x + m[1] y + m[2] z + m[3], y' from m[4..7], z' from m[8..11] */
     uint32_t first, count;           /* the triangles [first, first + count) */
     uint32_t reserved[2];            /* must be 0 */
 } rvpt_part_move;
 #define RVPT_HIP_NODES_UPDATE_POSE ((size_t)-5)
+#define RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille) ((size_t)0 - (size_t)(0x200000u + (permille)))
 #define RVPT_HIP_NODES_UPDATE_GUARDED(permille) ((size_t)0 - (size_t)(0x10000u + (permille)))
 #define RVPT_HIP_NODES_BUILD ((size_t)-1)
 #define RVPT_HIP_NODES_BUILD_PLOC ((size_t)-2)

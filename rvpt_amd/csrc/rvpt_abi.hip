@@ -157,10 +157,13 @@ struct rvpt_hip_ctx {
     unsigned char *d_sparse_stage = nullptr;
     size_t cap_sparse_stage = 0;
     // the POSE UPDATE of upload_scene (include/rvpt_hip.h): the REST POSE — the 48 vertex bytes of every stored triangle, in stored order, as the last call of
-    // any other form left them.  have_rest: the snapshot belongs to the stored scene; dropped by every successful call of another form, taken again by the
+    // any other form left them.  have_rest: the snapshot belongs to the stored scene; kept by the two pose forms (through a guarded rebuild too), dropped by every successful call of another form, taken again by the
     // next pose update.  BVH contexts keep it on the device (three quads per triangle), brute-force contexts on the host (twelve floats per triangle).
     float4 *d_rest = nullptr;
     size_t cap_rest = 0;
+    // the GUARDED POSE UPDATE: the rest pose in the caller's order while a rebuild replaces the permutation (allocated at the first such rebuild)
+    float4 *d_rest_carry = nullptr;
+    size_t cap_rest_carry = 0;
     std::vector<float> h_rest;
     bool have_rest = false;
     bool have_scene = false;
@@ -1022,7 +1025,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     void *bufs[] = {ctx->d_tris, ctx->d_prep, ctx->d_mats, ctx->d_nodes, ctx->d_wide, ctx->d_wide_map, ctx->d_mat_index, ctx->d_unit_n, ctx->d_accum,
                     ctx->d_rowmajor, ctx->d_counter, ctx->d_stats, ctx->d_perm, ctx->d_build, ctx->d_build_temp, ctx->d_build_counters, ctx->d_cost, ctx->d_carry,
                     ctx->d_sparse_parent, ctx->d_sparse_leaf_of, ctx->d_sparse_dirty, ctx->d_sparse_claim, ctx->d_inv_perm, ctx->d_sparse_words, ctx->d_sparse_stage,
-                    ctx->d_query_stage, ctx->d_query_scratch, ctx->d_rest};
+                    ctx->d_query_stage, ctx->d_query_scratch, ctx->d_rest, ctx->d_rest_carry};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1685,7 +1688,14 @@ static void pose_vertex_host(const float m[12], const float p[3], float out[3])
 // validated on the host before anything stored is touched.  BVH contexts: the rest pose is snapshotted on the device if the context holds none for the stored
 // scene, rv::pose_parts poses the listed rows of d_tris from it and flags their paths, and the sparse update's tail does the rest.  Brute-force contexts keep the
 // rest pose on the host: the stored records are read back, the listed ranges are posed there, and the plain update form runs.
-static int update_geometry_pose(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats)
+// (Two halves, so that the guarded pose form can put its own refusal between them: pose_validate touches nothing stored, pose_execute refuses nothing a
+// caller's arguments decide.)
+struct PoseList {
+    uint32_t total = 0, span_lo = 0, span_hi = 0;  // the triangles listed, the span of their indices
+    bool bvh = false;
+};
+
+static int pose_validate(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats, PoseList *list)
 {
     if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update before any full upload_scene on this context: there is no scene to update");
     if (k == 0) return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update without parts");
@@ -1705,8 +1715,16 @@ static int update_geometry_pose(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (is_device_pointer(moves))
         return fail(ctx, RVPT_HIP_ERR_INVALID, "pose update: the list at %p is device memory: this form takes its list from the host (64 bytes per part)", static_cast<const void *>(moves));
-    uint32_t total = 0, span_lo = 0, span_hi = 0;
-    if (int rc0 = pose_validate_host(ctx, moves, k, n_tris, &total, &span_lo, &span_hi)) return rc0;
+    list->bvh = bvh;
+    return pose_validate_host(ctx, moves, k, n_tris, &list->total, &list->span_lo, &list->span_hi);
+}
+
+static int pose_execute(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, size_t k, const PoseList &list)
+{
+    const size_t n_tris = ctx->n_tris;
+    const bool bvh = list.bvh;
+    const uint32_t total = list.total;
+    uint32_t span_lo = list.span_lo, span_hi = list.span_hi;
     const uint32_t n = static_cast<uint32_t>(n_tris), kk = static_cast<uint32_t>(k);
 
     if (!bvh) {  // the rest pose on the host, the posed records through the plain form
@@ -1765,6 +1783,63 @@ static int update_geometry_pose(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, 
     return RVPT_HIP_OK;
 }
 
+static int update_geometry_pose(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats)
+{
+    PoseList list;
+    if (int rc = pose_validate(ctx, moves, tris, k, mats, n_mats, &list)) return rc;
+    return pose_execute(ctx, moves, k, list);
+}
+
+// The GUARDED POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): the pose update, then the cost of the stored tree — the boxes off the listed paths as
+// they were, loose ones included —, then, with a limit, once the cost has grown past limit x base cost, a rebuild by the builder that made the stored tree
+// from the posed triangles carried back into the caller's order.  The rest pose goes with the rebuild: into the caller's order by the old permutation, back
+// into stored order by the new one, so that the next pose update poses from the same rest pose as before.  permille: 0 (report only) or 1000 .. 65535, checked
+// by the caller.  Brute-force contexts hold no tree: the plain pose form.
+static int update_geometry_pose_guarded(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats, uint32_t permille)
+{
+    // the pose form's own refusals come first, in its words and its order; then the one refusal of this form, before anything of the stored scene is touched
+    PoseList list;
+    if (int rc = pose_validate(ctx, moves, tris, k, mats, n_mats, &list)) return rc;
+    if (!list.bvh) return pose_execute(ctx, moves, k, list);
+    if (permille != 0 && ctx->built_by == rvpt_hip_ctx::kBuiltByCaller)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded pose update with a limit after an ordinary upload_scene: the tree is the caller's, the library has no builder to rebuild it by (report only, limit 0, is legal)");
+    if (int rc = pose_execute(ctx, moves, k, list)) return rc;
+    double cost = 0.0;
+    bool have = false;
+    if (int rc = device_tree_cost(ctx, &cost, &have)) return rc;
+    const double base = ctx->base_cost;
+    if (permille == 0 || !have || !ctx->have_cost || !ctx->have_perm || !(cost > static_cast<double>(permille) / 1000.0 * base)) {
+        fail(ctx, RVPT_HIP_OK, "guarded pose update: cost %.17g, base cost %.17g, limit %u permille: refitted", cost, base, permille);
+        return RVPT_HIP_OK;
+    }
+    // the rebuild, as the guarded update's: d_tris (posed vertices beside the stored mat_id rows, leaf order) into d_carry in the caller's order, and beside it
+    // the rest pose into d_rest_carry by the same permutation, before the build writes a new one
+    const size_t n_tris = ctx->n_tris;
+    const uint32_t n = static_cast<uint32_t>(n_tris);
+    const int built_by = ctx->built_by;
+    if (int rc = grow(ctx, ctx->d_carry, ctx->cap_carry, n_tris * 4u, sizeof(float4))) return rc;
+    if (int rc = grow(ctx, ctx->d_rest_carry, ctx->cap_rest_carry, n_tris * 3u, sizeof(float4))) return rc;
+    const uint32_t rest_blocks = static_cast<uint32_t>((3ull * n + 255u) / 256u);
+    hipLaunchKernelGGL(rv::carry_back_triangles, dim3(static_cast<uint32_t>((4ull * n + 255u) / 256u)), dim3(256), 0, ctx->stream, ctx->d_tris, ctx->d_perm, n, ctx->d_carry);
+    hipLaunchKernelGGL(rv::rest_to_caller_order, dim3(rest_blocks), dim3(256), 0, ctx->stream, ctx->d_rest, ctx->d_perm, n, ctx->d_rest_carry);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->have_rest = false;  // (d_rest is in the order of a permutation that is about to go: an error below leaves no rest pose)
+    if (int rc = build_scene_on_device(ctx, reinterpret_cast<const rvpt_triangle *>(ctx->d_carry), n_tris, ctx->host_mats.data(), ctx->host_mats.size(), built_by == rvpt_hip_ctx::kBuiltPloc,
+                                       built_by == rvpt_hip_ctx::kBuiltSah))
+        return rc;  // the build form's rule: its message, and no scene after anything but a bad material index (which stored rows cannot hold)
+    // (a PLOC build that fell back has left its sentence: the scene then holds the LBVH tree, and the report names it)
+    const bool fell_back = built_by == rvpt_hip_ctx::kBuiltPloc && !ctx->err.empty();
+    hipLaunchKernelGGL(rv::rest_to_stored_order, dim3(rest_blocks), dim3(256), 0, ctx->stream, ctx->d_rest_carry, ctx->d_perm, n, ctx->d_rest);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->have_rest = true;
+    static const char *const kNames[] = {"", "lbvh", "ploc", "sah"};
+    fail(ctx, RVPT_HIP_OK, "guarded pose update: cost %.17g, base cost %.17g, limit %u permille: rebuilt (%s), new base cost %.17g", cost, base, permille,
+         kNames[fell_back ? rvpt_hip_ctx::kBuiltLbvh : built_by], ctx->base_cost);
+    return RVPT_HIP_OK;
+}
+
 // The GUARDED UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; BVH contexts): the update form, then the cost of the refitted tree, then — with a limit,
 // once the cost has grown past limit x base cost — a rebuild by the builder that made the stored tree, from the moved triangles carried back into the
 // caller's order.  permille: 0 (report only) or 1000 .. 65535, checked by the caller.
@@ -1808,6 +1883,14 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
     // the POSE UPDATE: the count RVPT_HIP_NODES_UPDATE_POSE, `nodes` then points at n_tris rvpt_part_move records and `tris` is NULL (the form checks that itself)
     if (n_nodes == RVPT_HIP_NODES_UPDATE_POSE) return update_geometry_pose(ctx, reinterpret_cast<const rvpt_part_move *>(nodes), tris, n_tris, mats, n_mats);
+    // the GUARDED POSE UPDATE: the same arguments and a count of the band RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille) lies in.  It keeps the rest pose, through a
+    // rebuild too; only a rebuild that failed, and so left no scene, has dropped it
+    if ((size_t)0 - n_nodes >= 0x200000u && (size_t)0 - n_nodes < 0x300000u) {
+        const size_t permille = (size_t)0 - n_nodes - 0x200000u;
+        if (permille != 0 && (permille < 1000u || permille > 65535u))
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded pose update: the limit is 0 (report only) or 1000 .. 65535 permille, got %zu", permille);
+        return update_geometry_pose_guarded(ctx, reinterpret_cast<const rvpt_part_move *>(nodes), tris, n_tris, mats, n_mats, static_cast<uint32_t>(permille));
+    }
     const int rc = upload_scene_other_forms(ctx, nodes, n_nodes, tris, n_tris, mats, n_mats);
     // the rest pose of the pose update is the stored vertices as the last successful call of any OTHER form left them: the next pose update snapshots afresh
     if (rc == RVPT_HIP_OK || !ctx->have_scene) ctx->have_rest = false;

@@ -44,4 +44,10 @@ __global__ void pose_parts(const float4 *__restrict__ rest, const uint32_t *__re
                            uint32_t n_tris, const uint32_t *__restrict__ inv_perm, float4 *__restrict__ tris, const uint32_t *__restrict__ leaf_of,
                            const uint32_t *__restrict__ parent, uint32_t n_nodes, uint32_t *__restrict__ dirty);
 
+// The GUARDED POSE UPDATE (include/rvpt_hip.h; rvpt_abi.hip: update_geometry_pose_guarded): the rest pose through a rebuild.  Three quads per triangle on both
+// sides, one thread per quad, grid = ceil(3 n / block): out[perm[pos]] = rest[pos] with the old permutation in front of the build ...
+__global__ void rest_to_caller_order(const float4 *__restrict__ rest, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ out);
+// ... and rest[pos] = in[perm[pos]] with the new one behind it
+__global__ void rest_to_stored_order(const float4 *__restrict__ in, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ rest);
+
 }  // namespace rv

@@ -301,4 +301,32 @@ __global__ __launch_bounds__(256) void pose_parts(const float4 *__restrict__ res
         if (atomicExch(&dirty[node], 1u) != 0u) break;
 }
 
+// ---- the guarded pose update (include/rvpt_hip.h: GUARDED POSE UPDATE) -----------------------------------------------------------------------------------------
+// The rest pose goes with a rebuild: its 48 bytes per triangle (three quads, stored order of the OLD permutation) are scattered into the caller's order in front
+// of the build, out[perm_old[pos]] = rest[pos], and gathered by the permutation the build wrote behind it, rest[pos] = in[perm_new[pos]].  Two buffers: neither
+// step can be done in place.  One thread per quad, 16-byte loads and stores; thread t holds quad t of the side in STORED order, so that side — the read of the
+// scatter, the write of the gather — runs along consecutive lanes, and the other side moves in runs of 48 bytes.  perm is a bijection of [0, n) (the build's
+// gather wrote it), so the scatter writes every row exactly once; a word that is not an index is dropped, never an address.  No atomics, no LDS.
+__global__ void rest_to_caller_order(const float4 *__restrict__ rest, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ out)
+{
+    const size_t t = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const size_t pos = t / 3u;
+    if (pos >= n) return;
+    const uint32_t q = static_cast<uint32_t>(t - 3u * pos);
+    const uint32_t dst = perm[pos];
+    if (dst >= n) return;
+    out[3u * static_cast<size_t>(dst) + q] = rest[t];
+}
+
+__global__ void rest_to_stored_order(const float4 *__restrict__ in, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ rest)
+{
+    const size_t t = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const size_t pos = t / 3u;
+    if (pos >= n) return;
+    const uint32_t q = static_cast<uint32_t>(t - 3u * pos);
+    const uint32_t src = perm[pos];
+    if (src >= n) return;
+    rest[t] = in[3u * static_cast<size_t>(src) + q];
+}
+
 }  // namespace rv

@@ -285,7 +285,10 @@ void pose_vertex(const float m[12], const float in[4], float out[4])
 }
 
 // The pose form: `nodes` carries rvpt_part_move records, the count is RVPT_HIP_NODES_UPDATE_POSE, no triangles go down.
-bool RVPT::pose_parts(const rvpt_part_move *moves, size_t k)
+bool RVPT::pose_parts(const rvpt_part_move *moves, size_t k) { return pose_parts_with(moves, k, RVPT_HIP_NODES_UPDATE_POSE, "rvpt_hip_upload_scene (pose update)"); }
+
+// `count`: RVPT_HIP_NODES_UPDATE_POSE or RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille)
+bool RVPT::pose_parts_with(const rvpt_part_move *moves, size_t k, size_t count, const char *what)
 {
     if (!ctx_) {
         error_ = "pose_parts before initialize()";
@@ -339,8 +342,7 @@ bool RVPT::pose_parts(const rvpt_part_move *moves, size_t k)
     }
     const rvpt_part_move *sent = device_built_ ? moves : runs.data();
     const size_t n_sent = device_built_ ? k : runs.size();
-    if (!check(backend_.upload_scene(ctx_, reinterpret_cast<const rvpt_bvh_node *>(sent), RVPT_HIP_NODES_UPDATE_POSE, nullptr, n_sent, nullptr, 0), "rvpt_hip_upload_scene (pose update)"))
-        return false;
+    if (!check(backend_.upload_scene(ctx_, reinterpret_cast<const rvpt_bvh_node *>(sent), count, nullptr, n_sent, nullptr, 0), what)) return false;
     if (!have_rest_) rest_ = triangles_, have_rest_ = true;
     for (size_t p = 0; p < k; ++p)
         for (size_t t = moves[p].first; t < size_t(moves[p].first) + moves[p].count; ++t) {
@@ -354,14 +356,18 @@ bool RVPT::pose_parts(const rvpt_part_move *moves, size_t k)
     return true;
 }
 
-// The sentence rvpt_hip_last_error holds after a guarded update (include/rvpt_hip.h fixes the wording).
+// The sentence rvpt_hip_last_error holds after a guarded update or a guarded pose update (include/rvpt_hip.h fixes both wordings: they differ in the prefix).
 bool parse_update_report(const char *sentence, UpdateReport *report)
 {
     UpdateReport r;
     unsigned permille = 0;
     int used = 0;
     char tree[8] = {};
-    if (!sentence || std::sscanf(sentence, "guarded update: cost %lg, base cost %lg, limit %u permille: %n", &r.cost, &r.base_cost, &permille, &used) < 3 || used == 0) return false;
+    if (!sentence) return false;
+    if (std::strncmp(sentence, "guarded pose update: ", 21) == 0) sentence += 21;
+    else if (std::strncmp(sentence, "guarded update: ", 16) == 0) sentence += 16;
+    else return false;
+    if (std::sscanf(sentence, "cost %lg, base cost %lg, limit %u permille: %n", &r.cost, &r.base_cost, &permille, &used) < 3 || used == 0) return false;
     const char *rest = sentence + used;
     if (std::strcmp(rest, "refitted") == 0) {
         r.rebuilt = false;
@@ -393,6 +399,29 @@ bool RVPT::update_triangles(const std::vector<Triangle> &triangles, double rebui
     }
     // a rebuild happens only after a device build, where the tree lives on the device alone and bvh_nodes() is empty: there is no host copy to go wrong.  After a
     // host build the library refuses a limit (the tree is the caller's), and a report-only update is a refit, which update_triangles_with has marked
+    if (report) *report = r;
+    return true;
+}
+
+// The guarded pose form: the pose update under the count RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille), then the report.  The rest pose kept here, in the order
+// the triangles were added, stays through a rebuild, as the device's does.
+bool RVPT::pose_parts(const rvpt_part_move *moves, size_t k, double rebuild_above, UpdateReport *report)
+{
+    long permille = 0;  // infinity: report only
+    if (!std::isinf(rebuild_above) || rebuild_above < 0) {
+        permille = std::isnan(rebuild_above) ? -1 : std::lround(std::fmin(rebuild_above, 1e6) * 1000.0);
+        if (permille < 1000 || permille > 65535) {
+            error_ = "pose_parts: rebuild_above is a factor in [1, 65.535] or infinity (report only)";
+            return false;
+        }
+    }
+    if (!pose_parts_with(moves, k, RVPT_HIP_NODES_UPDATE_POSE_GUARDED(static_cast<size_t>(permille)), "rvpt_hip_upload_scene (guarded pose update)")) return false;
+    UpdateReport r;  // (a brute-force context holds no tree and reports nothing, an empty list sends nothing: the empty record)
+    if (options_.bvh_traversal && k > 0 && !parse_update_report(backend_.last_error(ctx_), &r)) {
+        error_ = "pose_parts: the guarded pose update's report could not be read";
+        return false;
+    }
+    // (a rebuild happens only after a device build, where bvh_nodes() is empty: there is no host copy of the tree to go wrong, as in update_triangles)
     if (report) *report = r;
     return true;
 }

@@ -97,7 +97,7 @@ struct Backend {
     static const Backend &native();
 };
 
-// What a guarded geometry update reports (RVPT::update_triangles with a limit), parsed from the one sentence rvpt_hip_last_error then holds
+// What a guarded geometry update or a guarded pose update reports (RVPT::update_triangles / RVPT::pose_parts with a limit), parsed from the one sentence rvpt_hip_last_error then holds
 struct UpdateReport {
     double cost = 0, base_cost = 0, ratio = 0;  // the refitted tree's cost, the cost of the tree as it was built, cost / base_cost (0 when the base is 0)
     bool rebuilt = false;
@@ -167,6 +167,11 @@ public:
     // outside the scene, an empty one, a non-zero reserved word or two ranges that share a triangle never reach the ABI.  The host copies are posed by
     // pose_vertex (the same bits as the device), bvh_nodes() is refitted when next asked for; the next update() restarts the accumulation.
     bool pose_parts(const rvpt_part_move *moves, size_t k);
+    // The guarded form (RVPT_HIP_NODES_UPDATE_POSE_GUARDED; include/rvpt_hip.h: GUARDED POSE UPDATE): the same, then the SAH cost of the posed tree from the
+    // device, and — `rebuild_above` a factor in [1, 65.535], rounded to thousandths — a rebuild by the device builder of initialize() once cost >
+    // rebuild_above x the base cost; infinity: report only.  The device carries its rest pose through the rebuild and the copy kept here stays, so later poses
+    // start from the same rest pose.  A limit needs Options::device_build.  Brute-force traversal: the plain pose, `report` comes back empty.
+    bool pose_parts(const rvpt_part_move *moves, size_t k, double rebuild_above, UpdateReport *report = nullptr);
 
     // RGBA32F (width*height*4 floats) or RGBA8 (width*height*4 bytes), row-major, top row first
     std::vector<float> read_frame();
@@ -204,6 +209,7 @@ public:
 private:
     bool check(int rc, const char *what);
     bool update_triangles_with(const std::vector<Triangle> &triangles, size_t count, const char *what);
+    bool pose_parts_with(const rvpt_part_move *moves, size_t k, size_t count, const char *what);
     uint32_t width_, height_;
     Options options_;
     const Backend &backend_;

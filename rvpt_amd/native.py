@@ -45,6 +45,7 @@ NODES_UPDATE_POSE = C.c_size_t(-5).value  # RVPT_HIP_NODES_UPDATE_POSE: the pose
 # rvpt_part_move (64 B): a 3x4 matrix, row major, for the triangles [first, first + count); two reserved words, 0
 PART_MOVE_DTYPE = np.dtype([("m", "<f4", (12,)), ("first", "<u4"), ("count", "<u4"), ("reserved", "<u4", (2,))])
 NODES_UPDATE_GUARDED_BASE = 0x10000  # RVPT_HIP_NODES_UPDATE_GUARDED(permille) = (size_t)0 - (0x10000 + permille): the guarded update (Context.update_triangles(rebuild_above=))
+NODES_UPDATE_POSE_GUARDED_BASE = 0x200000  # RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille) = (size_t)0 - (0x200000 + permille): the guarded pose update (Context.pose_parts(rebuild_above=))
 NODES_BUILD_PLOC = C.c_size_t(-2).value  # RVPT_HIP_NODES_BUILD_PLOC: the build form with a PLOC tree (Context.build_scene(method="ploc"))
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_SIZE, ERR_COMM = -1, -2, -3, -4, -5, -6
 
@@ -69,8 +70,22 @@ def nodes_update_guarded(permille: int) -> int:
     return C.c_size_t(-(NODES_UPDATE_GUARDED_BASE + int(permille))).value
 
 
+def nodes_update_pose_guarded(permille: int) -> int:
+    """RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille) of include/rvpt_hip.h as the size_t the call takes"""
+    return C.c_size_t(-(NODES_UPDATE_POSE_GUARDED_BASE + int(permille))).value
+
+
+def _guard_permille(rebuild_above, who: str) -> int:
+    """rebuild_above of the two guarded forms as the permille their counts carry: a float >= 1 rounded to thousandths, math.inf is 0 (report only)"""
+    limit = float(rebuild_above)
+    permille = 0 if limit == math.inf else int(round(min(limit, 1e6) * 1000.0)) if limit == limit and limit > 0 else -1
+    if permille != 0 and not 1000 <= permille <= 65535:
+        raise NativeError(ERR_INVALID, f"{who}: rebuild_above is a factor in [1, 65.535] or math.inf (report only), got {rebuild_above!r}")
+    return permille
+
+
 class UpdateReport(NamedTuple):
-    """What a guarded update reports: the refitted tree's SAH cost, the cost of the tree as it was last built or uploaded, cost / base_cost (0.0 when the base is
+    """What a guarded update or a guarded pose update reports: the refitted tree's SAH cost, the cost of the tree as it was last built or uploaded, cost / base_cost (0.0 when the base is
     0), whether the library rebuilt, and then the builder's name ("lbvh", "ploc", "sah"; None after a refit)."""
     cost: float
     base_cost: float
@@ -79,11 +94,11 @@ class UpdateReport(NamedTuple):
     tree: Optional[str]
 
 
-_GUARD_SENTENCE = re.compile(r"guarded update: cost (\S+), base cost (\S+), limit (\d+) permille: (?:refitted|rebuilt \((lbvh|ploc|sah)\), new base cost (\S+))\Z")
+_GUARD_SENTENCE = re.compile(r"guarded (?:pose )?update: cost (\S+), base cost (\S+), limit (\d+) permille: (?:refitted|rebuilt \((lbvh|ploc|sah)\), new base cost (\S+))\Z")
 
 
 def parse_update_report(sentence: str) -> UpdateReport:
-    """The one sentence rvpt_hip_last_error holds after a guarded update (include/rvpt_hip.h fixes its wording)"""
+    """The one sentence rvpt_hip_last_error holds after a guarded update or a guarded pose update (include/rvpt_hip.h fixes both wordings)"""
     m = _GUARD_SENTENCE.match(sentence)
     if m is None:
         raise NativeError(ERR_INVALID, f"update_triangles: not a guarded update's report: {sentence!r}")
@@ -454,11 +469,7 @@ class Context:
         ptr, n, keep = self._triangle_source(tris, "update_triangles")
         count = 0
         if rebuild_above is not None:
-            limit = float(rebuild_above)
-            permille = 0 if limit == math.inf else int(round(min(limit, 1e6) * 1000.0)) if limit == limit and limit > 0 else -1
-            if permille != 0 and not 1000 <= permille <= 65535:
-                raise NativeError(ERR_INVALID, f"update_triangles: rebuild_above is a factor in [1, 65.535] or math.inf (report only), got {rebuild_above!r}")
-            count = nodes_update_guarded(permille)
+            count = nodes_update_guarded(_guard_permille(rebuild_above, "update_triangles"))
         if n == 0:  # (in the C form a call without triangles is a full upload of the empty scene)
             if self._scene_tris != 0:
                 raise NativeError(ERR_INVALID, "update_triangles: no triangles given" + (" before any upload_scene" if self._scene_tris is None else f", the uploaded scene has {self._scene_tris}"))
@@ -505,22 +516,31 @@ class Context:
         del keep, ikeep
         return None
 
-    def pose_parts(self, moves) -> None:
+    def pose_parts(self, moves, rebuild_above=None):
         """The POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): every move names a range of triangles [first, first + count) — in the order
         update_triangles takes: the leaf order after upload_scene, the caller's own order after build_scene — and a 3x4 matrix; the device poses those triangles
         from the REST POSE it keeps (the vertices as the last call of any other form left them; two poses of one part do not compose) and recomputes only the boxes
         above them.  scene.pose_parts is the same on the host, bit for bit.  moves: a structured array of PART_MOVE_DTYPE, or a sequence of
         (first, count, matrix) with a 3x4 matrix or a 4x4 matrix whose last row is 0 0 0 1.  A malformed matrix or a negative `first` is refused here; ranges that
-        overlap or leave the scene are left to the library, which names them.  An empty list changes nothing.  Returns None."""
+        overlap or leave the scene are left to the library, which names them.  An empty list changes nothing.
+
+        rebuild_above: None is the plain form and returns None.  A number is the GUARDED form (RVPT_HIP_NODES_UPDATE_POSE_GUARDED): behind the pose the library
+        computes the tree's SAH cost on the device and, when it exceeds rebuild_above x the cost of the tree as it was built, rebuilds with the method of the
+        build_scene that made it; the rest pose follows the triangles through the rebuild, so later poses start from the same rest pose.  A float >= 1 is rounded
+        to thousandths (at most 65.535); math.inf only reports.  Returns an UpdateReport, whose `tree` names the tree the scene holds after a rebuild; on a
+        brute-force context, which holds no tree, the plain pose happens and None is returned."""
         from . import scene
+        count = NODES_UPDATE_POSE if rebuild_above is None else nodes_update_pose_guarded(_guard_permille(rebuild_above, "pose_parts"))
         try:
             rec = scene.part_moves(moves)
         except (ValueError, TypeError) as e:
             raise NativeError(ERR_INVALID, f"pose_parts: {e}") from None
         if rec.shape[0] == 0:
             return None
-        _check(self._L.rvpt_hip_upload_scene(self._h, _ptr(rec), NODES_UPDATE_POSE, None, rec.shape[0], None, 0), self._h, self._L)
-        return None
+        _check(self._L.rvpt_hip_upload_scene(self._h, _ptr(rec), count, None, rec.shape[0], None, 0), self._h, self._L)
+        if rebuild_above is None or (self.flags & (TRAVERSAL_BVH | TRAVERSAL_BVH_ORDERED)) == 0:
+            return None
+        return parse_update_report((self._L.rvpt_hip_last_error(self._h) or b"").decode())
 
     def set_frame(self, settings: np.ndarray, camera: np.ndarray) -> None:
         settings = np.ascontiguousarray(settings)

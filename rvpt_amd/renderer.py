@@ -242,12 +242,16 @@ class RVPT:
         self._rest_triangles = None
         return None
 
-    def pose_parts(self, moves) -> None:
+    def pose_parts(self, moves, rebuild_above=None):
         """Rigid parts — the POSE UPDATE (Context.pose_parts; include/rvpt_hip.h): every move is (first, count, matrix) or a native.PART_MOVE_DTYPE record and
         names the triangles [first, first + count) in the order they were ADDED; the device poses them by the move's 3x4 matrix from the REST POSE — the
         triangles as the last initialize() or update_triangles left them; two poses of one part do not compose — and recomputes only the boxes above them, as in
         bvh_nodes.  scene.pose_parts is the statement.  The next update() restarts the accumulation, as after update_triangles.  After a host build a range of
-        added triangles is scattered over the leaf order: it goes down as one record per run of consecutive positions, all with the part's matrix."""
+        added triangles is scattered over the leaf order: it goes down as one record per run of consecutive positions, all with the part's matrix.
+        rebuild_above: Context.pose_parts' keyword — the GUARDED form: the posed tree's SAH cost is reported (native.UpdateReport) and, past that factor of the cost
+        of the tree as built, the device rebuilds by the builder of initialize() and carries its rest pose along; bvh_nodes, primitive_indices and sorted_triangles
+        are then those of a fresh build of the posed triangles, made when asked for.  The rest copy kept here, in added order, stays.  A limit needs
+        build="device*"; math.inf only reports."""
         if self._ctx is None or self._n_triangles is None:
             raise RuntimeError("pose_parts before initialize()")
         try:
@@ -272,7 +276,7 @@ class RVPT:
             inverse[np.asarray(self._primitive_indices, dtype=np.int64)] = np.arange(n)
             pos = inverse[idx]
         if self._device_built:  # the device keeps the permutation: the caller's numbering goes down as it is
-            self._ctx.pose_parts(rec)
+            report = self._ctx.pose_parts(rec) if rebuild_above is None else self._ctx.pose_parts(rec, rebuild_above=rebuild_above)
         else:  # a host-built tree: added order -> runs of consecutive positions in leaf order
             runs = []
             for r in rec:
@@ -282,12 +286,18 @@ class RVPT:
                 run = np.zeros(starts.size, dtype=native.PART_MOVE_DTYPE)
                 run["m"], run["first"], run["count"] = r["m"], p[starts], ends - starts
                 runs.append(run)
-            self._ctx.pose_parts(np.concatenate(runs))
+            runs = np.concatenate(runs)
+            report = self._ctx.pose_parts(runs) if rebuild_above is None else self._ctx.pose_parts(runs, rebuild_above=rebuild_above)
         self._rest_triangles = rest
         self.triangles = [posed]
         if self._device_built:
             self._current_triangles = posed
-        if self._built_from is None:  # there is a host statement to keep right
+        if report is not None and report.rebuilt:
+            # the device holds a new tree and a new permutation: the host statement is that of a fresh build from the posed triangles, made when asked for
+            self._built_from = posed
+            self._bvh_nodes = self._primitive_indices = self._sorted_triangles = None
+            self._nodes_stale, self._stale_touched = False, None
+        elif self._built_from is None:  # there is a host statement to keep right
             self._sorted_triangles = posed[np.asarray(self._primitive_indices, dtype=np.int64)]
             if self._bvh_nodes is not None:
                 if not self._nodes_stale:
@@ -295,7 +305,7 @@ class RVPT:
                 elif self._stale_touched is not None:
                     self._stale_touched = np.concatenate([self._stale_touched, pos])
         self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
-        return None
+        return report
 
     # -- lifecycle -----------------------------------------------------------------------------------------
     def initialize(self) -> bool:

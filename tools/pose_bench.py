@@ -6,9 +6,12 @@ six alternate inside one loop (wall clock of the call, median of 20 after 3 warm
 tree rebuilt for that pose, for a small rotation of one part and for a part carried across the scene.  -> stdout (profiles/pose_update.txt)
 Exits non-zero unless the whole-mesh pose costs less than the plain update from a host array in the same run: the plain form is bound by a 48 MB copy that
 the pose form does not make.
-usage: tools/pose_bench.py [all|updates]     (updates: a device build and a few pose updates of each kind, nothing else — the run to put under
-rocprofv3 --kernel-trace --stats)"""
-import statistics, sys, time
+usage: tools/pose_bench.py [all|updates|guard]     (updates: a device build and a few pose updates of each kind, nothing else — the run to put under
+rocprofv3 --kernel-trace --stats; guard: the GUARDED POSE UPDATE (Context.pose_parts(rebuild_above=)) alone -> stdout (profiles/guarded_pose.txt): what the
+guard adds to a plain pose of a 1 % part, both alternating in one loop on one context; what a guarded pose that rebuilds costs, per builder; and the two motions
+of the traversal table under a limit of 1.1 — the ratio each reports, what was decided, and the one-frame rate afterwards beside the refitted and the freshly
+built rates.  Nothing there is a pass/fail bar.)"""
+import math, statistics, sys, time
 from pathlib import Path
 
 import numpy as np
@@ -116,6 +119,68 @@ if what == "updates":
             ctx.pose_parts(lists[j % 2][name])
     ctx.close()
     print("18 pose updates done: 6 of one 1 % part, 6 of 100 parts, 6 of the whole mesh")
+    sys.exit(0)
+
+
+
+def guard_section(ctx):
+    k = n // 100
+    lists = [move_lists(tris0, flip)["pose, 1 part of 1 %"] for flip in (0, 1)]
+    variants = {"plain pose, 1 part of 1 %": lambda j: ctx.pose_parts(lists[j]),
+                "guarded pose, report only, the same part": lambda j: ctx.pose_parts(lists[j], rebuild_above=math.inf),
+                "guarded pose, limit 1.1 (never reached), the same part": lambda j: ctx.pose_parts(lists[j], rebuild_above=1.1)}
+    times = {name: [] for name in variants}
+    for it in range(23):  # the candidate and its yardstick alternate: whatever drifts, drifts for both
+        for name, fn in variants.items():
+            t0 = time.perf_counter()
+            rep = fn(it % 2)
+            if it >= 3:
+                times[name].append(time.perf_counter() - t0)
+            assert rep is None or not rep.rebuilt
+    print(f"\n== the guard's cost: {n} triangles, one part of {k}, SAH device build (wall clock of the call; alternating in one loop on one context) ==")
+    for name, ts in times.items():
+        print(f"{name:56s} {spread(ts)}")
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    plain = med["plain pose, 1 part of 1 %"]
+    print(f"guarded (report only) - plain = {(med['guarded pose, report only, the same part'] - plain) * 1e3:.3f} ms;   guarded / plain = {med['guarded pose, report only, the same part'] / plain:.2f}")
+
+    first, count = n // 2, n // 10
+    centre = centroid(tris0, first, count)
+    turned = [(first, count, about(centre, rotation_y(np.radians(2.0))))]
+    carried = [(first, count, scene.part_move(0, 1, translation=(0.5 * ext, 0.1 * ext, 0.0))["m"].reshape(3, 4))]
+    home = [(first, count, np.eye(3, 4))]
+    print("\n== a guarded pose that rebuilds (limit 1.0; the part carried across the scene and brought home in turn, each on the tree built for the other; wall clock of the call) ==")
+    for method in ("lbvh", "ploc", "sah"):
+        built = ctx.build_scene(tris0, mats, method=method)
+        ts, kept = [], 0
+        for it in range(7):
+            t0 = time.perf_counter()
+            rep = ctx.pose_parts(carried if it % 2 == 0 else home, rebuild_above=1.0)
+            dt = time.perf_counter() - t0
+            if rep.rebuilt and it >= 1:
+                ts.append(dt)
+            kept += not rep.rebuilt
+        print(f"{method:5s} (the scene holds: {built:4s}) " + (spread(ts) if ts else "never rebuilt") + f"   calls that refitted: {kept} of 7")
+
+    print("\n== the two motions under a limit of 1.1 (SAH device build, one-frame launches at 1080p, Msamples/s, median of 5 x 24 frames) ==")
+    ctx.build_scene(tris0, mats, method="sah")
+    print(f"rest pose, built tree                                        {statistics.median(frame_rate(ctx, cam)):8.0f}")
+    for name, moves in (("a rotation of one part (10 % of the mesh) by 2 degrees", turned), ("the same part carried across the scene", carried)):
+        ctx.build_scene(tris0, mats, method="sah")
+        ctx.pose_parts(moves)
+        refitted = statistics.median(frame_rate(ctx, cam))
+        ctx.build_scene(tris0, mats, method="sah")
+        rep = ctx.pose_parts(moves, rebuild_above=1.1)
+        guarded = statistics.median(frame_rate(ctx, cam))
+        ctx.build_scene(scene.pose_parts(tris0, moves), mats, method="sah")
+        fresh = statistics.median(frame_rate(ctx, cam))
+        print(f"{name:56s} ratio {rep.ratio:8.4f} -> {'rebuilt (' + rep.tree + ')' if rep.rebuilt else 'refitted':14s}   afterwards {guarded:8.0f}   plain pose, refitted {refitted:8.0f}   "
+              f"fresh build {fresh:8.0f}   afterwards / fresh = {guarded / fresh:.3f}")
+
+
+if what == "guard":
+    guard_section(ctx)
+    ctx.close()
     sys.exit(0)
 
 ok = updates_section(ctx, tris0, "after build_scene(method='sah'), ranges in the caller's order")

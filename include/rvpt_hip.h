@@ -66,7 +66,12 @@ extern "C" {
                                      the device from a rest pose it keeps, and only the boxes on their paths to the root are recomputed.  Still 8, no
                                      new symbol: the same arguments under a count RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille) — until then the "NULL scene
                                      array" error — are the GUARDED POSE UPDATE: the pose update, the SAH cost of the posed tree reported, and past a limit a
-                                     rebuild by the builder that made the tree, through which the rest pose follows its triangles */
+                                     rebuild by the builder that made the tree, through which the rest pose follows its triangles.  Still 8, no
+                                     new symbol: the count RVPT_HIP_NODES_BIND_SKIN with `nodes` pointing at three rvpt_vertex_skin records per stored
+                                     triangle — until then the "NULL scene array" error — is the BIND: four bone indices and four weights per vertex, kept
+                                     on the device.  Still 8, no new symbol: the count RVPT_HIP_NODES_UPDATE_SKIN with `nodes` pointing at a list of rvpt_bone
+                                     matrices — until then the "NULL scene array" error — is the SKIN UPDATE: every vertex posed from the rest pose by its
+                                     four weighted matrices (linear blend skinning), every box refitted */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -358,6 +363,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  *   updates — returned successfully.  The library snapshots it at the first pose update after such a call: a device-to-device copy of the 48 vertex bytes
  *   per triangle, in stored order (a context that never poses never allocates it).  A pose update ALWAYS poses from the rest pose, never from the current
  *   position: two pose updates of one part do not compose, the second replaces the first.  A part not listed keeps the pose it has.
+ *   (The SKIN UPDATE below shares this rest pose: a pose update after a skin update poses its listed parts from the rest pose and leaves the others skinned.)
  *   After any successful call of another form the next pose update takes a FRESH snapshot, and that snapshot includes whatever earlier pose updates left:
  *   pose A, a sparse update of one unrelated triangle, pose B of the same part gives B applied to the A-posed vertices.
  * - The arithmetic.  For a vertex (x, y, z) and the output component i (0, 1, 2) the value is ((m[4i]*x + m[4i+1]*y) + m[4i+2]*z) + m[4i+3]: three products
@@ -417,7 +423,68 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  *   exactly as before, and after each of the others the next pose update takes a fresh snapshot.
  * Measured on one MI355X, 1 M triangles (profiles/guarded_pose.txt): the guard adds 0.045 ms to the 0.140 ms pose of a 1 % part; a call that
  * rebuilds takes 2.2 / 3.5 / 15.1 ms (LBVH / PLOC / SAH); a tenth of the mesh rotated by 2 degrees reports a ratio of 1.33 with the tree at 0.40 of a rebuilt
- * one's rate, the same part carried across the scene 226.  A limit at or below 1.3 catches the first; nothing finer was measured. */
+ * one's rate, the same part carried across the scene 226.  A limit at or below 1.3 catches the first; nothing finer was measured.
+ *
+ * BIND — four bone indices and four weights per vertex, kept by the library for the skin update below:
+ *
+ *     rvpt_hip_upload_scene(ctx, (const rvpt_bvh_node *)skin, RVPT_HIP_NODES_BIND_SKIN, NULL, n_tris, NULL, 0);
+ *
+ * - `skin` points at 3 * n_tris rvpt_vertex_skin records (32 bytes each); record 3 t + v belongs to vertex v of triangle t, and t is numbered in the order the
+ *   plain update form takes on this context: the leaf order after an ordinary upload, the caller's own order after a build form.  The library keeps its copy
+ *   IN THAT ORDER (96 bytes per triangle, one device buffer, freed with the context) and goes through the stored permutation when it skins: a guarded rebuild,
+ *   which changes the permutation and not the update order, leaves the binding valid.
+ * - `skin` may be host memory (4-byte aligned); on BVH contexts also device memory of the context's GPU, 16-byte aligned.  Brute-force contexts keep the
+ *   binding on the host and take host memory only.
+ * - Refusals, RVPT_HIP_ERR_INVALID with a message, decided in this order before anything is touched — the earlier binding stays: no scene; n_tris is not the
+ *   stored count; `skin` NULL; `skin` misaligned; `tris` not NULL; materials passed; device memory of another GPU (both devices named) or a device pointer on a
+ *   brute-force context; a bone[j] >= RVPT_HIP_SKIN_MAX_BONES — the message names the smallest offending record position, its j and the value, the same for
+ *   host and device lists (a device list is checked by one kernel and one read of four words).
+ * - The bind records the LARGEST BONE INDEX of the list and the smallest record position that holds it: a skin update needs more matrices than that.
+ * - It moves nothing.  It is not "another form" in the pose update's snapshot rule: the rest pose stays.  The slots' prepared state stays, rvpt_hip_last_error
+ *   is empty afterwards, and a frame after a bind is bit for bit the frame without it.  A second bind replaces the first.
+ * - The binding is DROPPED by an ordinary full upload, by a build form the caller asks for, and whenever a call leaves the context without a scene.  It
+ *   SURVIVES the plain, guarded, sparse, pose and guarded pose updates, their rebuilds included.
+ * - Weights are taken as given: they need not sum to 1, and non-finite weights are the caller's problem.
+ *
+ * SKIN UPDATE — linear blend skinning: every vertex of the mesh posed from the rest pose by its four weighted bone matrices, on the device:
+ *
+ *     rvpt_hip_upload_scene(ctx, (const rvpt_bvh_node *)bones, RVPT_HIP_NODES_UPDATE_SKIN, NULL, k, NULL, 0);      0 < k <= RVPT_HIP_SKIN_MAX_BONES
+ *
+ * - `bones` points at k rvpt_bone records (48 bytes: a 3x4 matrix, row major, as rvpt_part_move::m) in host memory (4-byte aligned) or, on BVH contexts, in
+ *   device memory of the context's GPU, 16-byte aligned (a tensor an animation system wrote; the caller guarantees that the writer has finished).
+ * - The arithmetic.  For a vertex with rest position p and influences j = 0..3: q_j = pose(M[bone[j]], p), where pose is EXACTLY the pose update's arithmetic
+ *   (((m0 x + m1 y) + m2 z) + m3 per component), and out_i = ((w0*q0_i + w1*q1_i) + w2*q2_i) + w3*q3_i: four products and three sums, each rounded to
+ *   binary32 on its own, in that order, with NO fused multiply-add anywhere.  All four influences are always evaluated: a zero weight contributes 0 * q.
+ *   One-hot weights therefore reproduce the pose update's bytes, up to -0 + 0 = +0.  rvpt_amd/scene.py: skin_triangles is the same in numpy float32; the
+ *   device, the host (brute-force contexts) and numpy agree bit for bit.  The w lanes come from the rest pose; the stored mat_id rows, the materials, the
+ *   topology, the permutation and the guarded update's base cost stay.  Non-finite matrix entries are the caller's problem.
+ * - THE REST POSE IS THE POSE UPDATE'S: the same buffer, the same flag, the same rule.  It is snapshotted by the first pose OR skin update after a successful
+ *   call of any form that is not a pose update, a guarded pose update, a skin update or a bind.  A skin update always skins from it, writes EVERY triangle, and
+ *   keeps it: two skin updates never compose.
+ * - Every box is then refitted by the PLAIN form's rule (every level, deepest first, then the wide copies), and prepared records, material slots and unit
+ *   normals are remade.  The context then renders exactly what the plain update form, called with the skinned vertices, renders — images, statistics, kernel
+ *   path —, which is a fresh upload of (refit_bvh(nodes, skinned), skinned, mats) with the wide grouping kept as after every update form.  Loose boxes become
+ *   tight, as after a plain update.  Ray and path queries answer on the skinned scene, with `prim` numbered as before.
+ * - Brute-force contexts work on the host: the stored records are read back, the rest pose is kept on the host, the vertices are skinned there with the same
+ *   unfused arithmetic, and the plain update form runs.
+ * - Refusals, in this order, decided before anything stored is touched — the scene, the rest pose and the binding are left as they were: no scene; k == 0;
+ *   k > RVPT_HIP_SKIN_MAX_BONES; `bones` NULL; `bones` misaligned; `tris` not NULL; materials passed; no binding ("skin update before a bind"); k <= the
+ *   largest bound bone index (the message names the index, the record position that holds it, and k); device memory of another GPU; a device pointer on a
+ *   brute-force context; the laboratory's caller-layout knob, with the answer the plain form gives.
+ * - Frames in flight finish on the old geometry; `bones` may be freed on return; rvpt_hip_last_error is empty afterwards.  Every other form behaves and reports
+ *   exactly as before.  There is NO GUARDED SKIN UPDATE: the tree is refitted, never costed or rebuilt, by this form; a caller whose skinned mesh has left its
+ *   tree behind runs a guarded update or a build form.
+ * Cost on one MI355X: profiles/skin_update.txt; DESIGN.md 5.18. */
+typedef struct rvpt_vertex_skin {    /* 32 bytes: the four influences of ONE vertex */
+    uint32_t bone[4];                /* indices into the skin update's matrices, each < RVPT_HIP_SKIN_MAX_BONES */
+    float    weight[4];
+} rvpt_vertex_skin;
+typedef struct rvpt_bone {           /* 48 bytes */
+    float    m[12];                  /* 3x4, row major, as rvpt_part_move::m */
+} rvpt_bone;
+#define RVPT_HIP_SKIN_MAX_BONES 1024u
+#define RVPT_HIP_NODES_BIND_SKIN ((size_t)-6)
+#define RVPT_HIP_NODES_UPDATE_SKIN ((size_t)-7)
 typedef struct rvpt_part_move {      /* 64 bytes */
     float    m[12];                  /* 3x4, row major: x' = m[0] x + m[1] y + m[2] z + m[3], y' from m[4..7], z' from m[8..11] */
     uint32_t first, count;           /* the triangles [first, first + count) */

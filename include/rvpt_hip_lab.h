@@ -106,6 +106,10 @@ int rvpt_bvh_wide_form(const rvpt_bvh_node *nodes, size_t n_nodes, uint32_t head
  *   INV_PERM       n_tris words while have_inv_perm: the inverse of PERM
  *   REST           n_tris x 48 B while the context holds a rest pose for the stored scene (include/rvpt_hip.h: POSE UPDATE — taken by the first pose update after
  *                  a successful call of any other form, dropped by the next such call): vert0..vert2 of every triangle, in stored order; 0 bytes otherwise
+ *   SKIN           3 n_tris x 32 B while the context holds a binding (include/rvpt_hip.h: BIND): the rvpt_vertex_skin records in the order the plain update
+ *                  form takes (NOT in stored order: the skin update goes through PERM); brute-force contexts hold it on the host; 0 bytes otherwise
+ *   BONES          k x 48 B: the matrices of the last successful skin update of a BVH context as its kernel read them from the device, until the next bind or
+ *                  the end of the binding; 0 bytes otherwise (brute-force contexts skin on the host and hold none)
  * dst == NULL or dst_capacity < the live size of a piece that has bytes: RVPT_HIP_ERR_SIZE, *bytes_out = the size needed, nothing written.  A context without a
  * scene: RVPT_HIP_ERR_INVALID. */
 typedef struct rvpt_hip_scene_state_info {
@@ -117,7 +121,7 @@ typedef struct rvpt_hip_scene_state_info {
 enum {
     RVPT_HIP_STATE_NONE = 0, RVPT_HIP_STATE_NODES = 1, RVPT_HIP_STATE_TRIS = 2, RVPT_HIP_STATE_PERM = 3, RVPT_HIP_STATE_WIDE = 4, RVPT_HIP_STATE_WIDE_MAP = 5,
     RVPT_HIP_STATE_REFIT_LEVELS = 6, RVPT_HIP_STATE_SPARSE_PARENT = 7, RVPT_HIP_STATE_SPARSE_LEAF_OF = 8, RVPT_HIP_STATE_SPARSE_DIRTY = 9, RVPT_HIP_STATE_INV_PERM = 10,
-    RVPT_HIP_STATE_REST = 11
+    RVPT_HIP_STATE_REST = 11, RVPT_HIP_STATE_SKIN = 12, RVPT_HIP_STATE_BONES = 13
 };
 int rvpt_hip_selftest_scene_state(rvpt_hip_ctx *ctx, rvpt_hip_scene_state_info *info, uint32_t piece, void *dst, size_t dst_capacity, size_t *bytes_out);
 

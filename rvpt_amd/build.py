@@ -131,6 +131,7 @@ HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selft
                 "host_selftest_sparse": ["host_selftest_sparse.cpp", "rvpt_host.cpp"],
                 "host_selftest_pose": ["host_selftest_pose.cpp", "rvpt_host.cpp"],
                 "host_selftest_pose_guard": ["host_selftest_pose_guard.cpp", "rvpt_host.cpp"],
+                "host_selftest_skin": ["host_selftest_skin.cpp", "rvpt_host.cpp"],
                 "host_selftest_rays": ["host_selftest_rays.cpp", "rvpt_host.cpp"],
                 "host_selftest_paths": ["host_selftest_paths.cpp", "rvpt_host.cpp"],
                 "host_row_boxes": ["host_row_boxes.cpp"]}  # (rvpt_vis.h alone: the row boxes' table for scenes given in files, tests/test_row_boxes.py)
@@ -152,7 +153,7 @@ def _hip_host_flags() -> list:
 
 def build_host(force: bool = False) -> Path:
     """Compile the C++ host layer (rvpt_amd/host/: the mirror of the reference's class RVPT above the C ABI) with
-    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames`, `host_selftest_guard`, `host_selftest_sparse`, `host_selftest_pose`, `host_selftest_pose_guard`, `host_selftest_rays` and `host_selftest_paths`."""
+    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames`, `host_selftest_guard`, `host_selftest_sparse`, `host_selftest_pose`, `host_selftest_pose_guard`, `host_selftest_skin`, `host_selftest_rays` and `host_selftest_paths`."""
     build_native()
     HOST_BIN_DIR.mkdir(exist_ok=True)
     srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h", _PKG / "csrc" / "rvpt_vis.h"]

@@ -70,6 +70,8 @@ static_assert(sizeof(rvpt_ray_path) == rv::kPathRecordBytes && offsetof(rvpt_ray
                   offsetof(rvpt_ray_path, radiance) == 32 && offsetof(rvpt_ray_path, segments) == 44 && RVPT_HIP_PATH_MAX_BOUNCES == rv::kPathMaxBounces,
               "a path query's record: three float4 (rvpt_paths.hip)");
 static_assert(sizeof(rvpt_part_move) == 64 && offsetof(rvpt_part_move, first) == 48 && offsetof(rvpt_part_move, count) == 52, "rvpt_part_move: the sixteen words rv::pose_parts reads");
+static_assert(sizeof(rvpt_vertex_skin) == 32 && offsetof(rvpt_vertex_skin, weight) == 16 && sizeof(rvpt_bone) == 48 && RVPT_HIP_SKIN_MAX_BONES * sizeof(rvpt_bone) <= 48u * 1024u,
+              "rvpt_vertex_skin, rvpt_bone: the two quads and the three quads rv::skin_vertices reads; every matrix fits its 48 KiB of LDS");
 static_assert(sizeof(rvpt_ray_path) == sizeof(rvpt_ray_hit) &&offsetof(rvpt_ray_path, radiance) == offsetof(rvpt_ray_hit, t), "ray and path queries share query_records");
 static_assert(offsetof(rvpt_triangle, mat_id) == 48 && offsetof(rvpt_bvh_node, bounds) == 8 &&
                   offsetof(rvpt_material, data) == 32 && offsetof(rvpt_render_settings, split_ratio) == 32 &&
@@ -166,6 +168,19 @@ struct rvpt_hip_ctx {
     size_t cap_rest_carry = 0;
     std::vector<float> h_rest;
     bool have_rest = false;
+    // the BIND and the SKIN UPDATE of upload_scene (include/rvpt_hip.h): the binding — three rvpt_vertex_skin records per triangle in the order the plain update
+    // form takes — on the device of a BVH context, on the host of a brute-force one; the largest bone index it holds and the smallest record position that
+    // holds it; the words of a device list's check with their pinned host copy; and the matrices of the last skin update (BVH contexts: skin_bones of them)
+    uint4 *d_skin = nullptr;
+    size_t cap_skin = 0;
+    std::vector<rvpt_vertex_skin> h_skin;
+    bool have_skin = false;
+    uint32_t skin_max_bone = 0;
+    uint64_t skin_max_pos = 0;
+    unsigned long long *d_skin_words = nullptr, *h_skin_words = nullptr;
+    float4 *d_bones = nullptr;
+    size_t cap_bones = 0;
+    uint32_t skin_bones = 0;
     bool have_scene = false;
     // RAY QUERIES and PATH QUERIES (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS / RVPT_HIP_FORMAT_RAY_PATHS; rvpt_query.h, rvpt_paths.h): the staging buffer of host records (bytes) and the launch's scratch — 64 words whose
     // first is the claim counter, then the global part of the traversal stack (words).  Both only grow.
@@ -995,6 +1010,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     if (ctx->h_build_words) (void)hipHostFree(ctx->h_build_words);
     if (ctx->h_cost) (void)hipHostFree(ctx->h_cost);
     if (ctx->h_sparse_words) (void)hipHostFree(ctx->h_sparse_words);
+    if (ctx->h_skin_words) (void)hipHostFree(ctx->h_skin_words);
     if (ctx->d_timeline && !ctx->knobs.timeline_path.empty()) {  // debugging aid: dump the last frame's wave timeline
         std::vector<unsigned long long> h(ctx->timeline_words);
         if (hipMemcpy(h.data(), ctx->d_timeline, ctx->timeline_words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1025,7 +1041,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     void *bufs[] = {ctx->d_tris, ctx->d_prep, ctx->d_mats, ctx->d_nodes, ctx->d_wide, ctx->d_wide_map, ctx->d_mat_index, ctx->d_unit_n, ctx->d_accum,
                     ctx->d_rowmajor, ctx->d_counter, ctx->d_stats, ctx->d_perm, ctx->d_build, ctx->d_build_temp, ctx->d_build_counters, ctx->d_cost, ctx->d_carry,
                     ctx->d_sparse_parent, ctx->d_sparse_leaf_of, ctx->d_sparse_dirty, ctx->d_sparse_claim, ctx->d_inv_perm, ctx->d_sparse_words, ctx->d_sparse_stage,
-                    ctx->d_query_stage, ctx->d_query_scratch, ctx->d_rest, ctx->d_rest_carry};
+                    ctx->d_query_stage, ctx->d_query_scratch, ctx->d_rest, ctx->d_rest_carry, ctx->d_skin, ctx->d_skin_words, ctx->d_bones};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1139,6 +1155,8 @@ static int device_tree_cost(rvpt_hip_ctx *ctx, double *cost, bool *have)
 // twelve floats vert0..vert2 of every triangle (the stored mat_id rows, the materials and the tree's (first, count) words stay) and recomputes what depends on
 // positions: prepared records and hit normals, the boxes of the binary nodes (level by level, deepest first) and their copies in the wide nodes, the bounce
 // cull's table, scale and leaf boxes.  What depends on topology alone — bvh_height, bvh_head_shift, n_wide, wide_stack_levels, hence the launch choice — stays.
+static int update_geometry_tail(rvpt_hip_ctx *ctx, bool bvh, const rvpt_triangle *tris, size_t n_tris);
+
 static int update_geometry(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t n_tris)
 {
     if (!ctx->have_scene)
@@ -1167,6 +1185,13 @@ static int update_geometry(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, size_t 
     } else {
         HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_tris, sizeof(rvpt_triangle), tris, sizeof(rvpt_triangle), offsetof(rvpt_triangle, mat_id), n_tris, hipMemcpyDefault, ctx->stream));
     }
+    return update_geometry_tail(ctx, bvh, tris, n_tris);
+}
+
+// ... and what follows once d_tris holds the moved vertices, shared with the skin update, whose kernel writes them: prepared records and hit normals, every
+// box of the tree, the wide copies, the bounce cull's state.  `tris`: the caller's host array on brute-force contexts, unread on BVH contexts.
+static int update_geometry_tail(rvpt_hip_ctx *ctx, bool bvh, const rvpt_triangle *tris, size_t n_tris)
+{
     if (int rc = launch_prepare_triangles(ctx, n_tris)) return rc;
     if (bvh) {
         const uint32_t n_nodes = static_cast<uint32_t>(ctx->n_nodes);
@@ -1840,6 +1865,181 @@ static int update_geometry_pose_guarded(rvpt_hip_ctx *ctx, const rvpt_part_move 
     return RVPT_HIP_OK;
 }
 
+// is `p` device memory, and of which GPU (-1: host memory)?
+static int device_of_pointer(const void *p)
+{
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return attr.type == hipMemoryTypeDevice ? attr.device : -1;
+}
+
+static void drop_skin(rvpt_hip_ctx *ctx)
+{
+    ctx->have_skin = false;
+    ctx->skin_bones = 0;
+}
+
+// The BIND of rvpt_hip_upload_scene (include/rvpt_hip.h): three rvpt_vertex_skin records per stored triangle, in the order the plain update form takes, copied
+// into d_skin (BVH contexts) or h_skin (brute-force contexts) once every refusal is behind.  A host list is checked here, a device list by rv::skin_check and
+// one read of its four words.  Moves nothing, keeps the rest pose, leaves scene_gen alone.
+static int bind_skin(rvpt_hip_ctx *ctx, const rvpt_vertex_skin *skin, const rvpt_triangle *tris, size_t n_tris, const rvpt_material *mats, size_t n_mats)
+{
+    if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "bind before any full upload_scene on this context: there is no scene to bind weights to");
+    if (n_tris != ctx->n_tris) return fail(ctx, RVPT_HIP_ERR_INVALID, "bind for %zu triangles, the uploaded scene has %zu: three records per stored triangle", n_tris, ctx->n_tris);
+    if (!skin) return fail(ctx, RVPT_HIP_ERR_INVALID, "bind without a list: `nodes` points at three rvpt_vertex_skin records per triangle");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int dev = device_of_pointer(skin);
+    if (reinterpret_cast<uintptr_t>(skin) % (dev >= 0 ? 16u : 4u))
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "bind: the list at %p is not %u-byte aligned", static_cast<const void *>(skin), dev >= 0 ? 16u : 4u);
+    if (tris) return fail(ctx, RVPT_HIP_ERR_INVALID, "bind takes no triangles: the weights belong to the stored ones (`tris` must be NULL)");
+    if (mats || n_mats) return fail(ctx, RVPT_HIP_ERR_INVALID, "bind takes no materials: it keeps the stored ones");
+    const bool bvh = is_bvh(ctx, n_tris);
+    if (dev >= 0 && dev != ctx->device) return fail(ctx, RVPT_HIP_ERR_INVALID, "bind: the list is device memory of GPU %d, the context lives on GPU %d", dev, ctx->device);
+    if (dev >= 0 && !bvh) return fail(ctx, RVPT_HIP_ERR_INVALID, "bind on a brute-force context from a device pointer: its binding is kept on the host, pass a host array");
+    const uint64_t n_records = 3ull * n_tris;
+    uint32_t max_bone = 0;
+    uint64_t max_pos = 0;
+    if (dev < 0) {
+        for (uint64_t r = 0; r < n_records; ++r)
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t b = skin[r].bone[j];
+                if (b >= RVPT_HIP_SKIN_MAX_BONES)
+                    return fail(ctx, RVPT_HIP_ERR_INVALID, "bind: skin[%llu].bone[%u] = %u: a bone index lies below %u", static_cast<unsigned long long>(r), j, b, RVPT_HIP_SKIN_MAX_BONES);
+                if (b > max_bone) max_bone = b, max_pos = r;
+            }
+    } else if (n_records) {
+        size_t cap_words = ctx->d_skin_words ? 2 : 0;
+        if (int rc = grow(ctx, ctx->d_skin_words, cap_words, 2, sizeof(unsigned long long))) return rc;
+        if (!ctx->h_skin_words) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_skin_words), 2 * sizeof(unsigned long long)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_skin_words, 0xFF, sizeof(unsigned long long), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_skin_words + 1, 0, sizeof(unsigned long long), ctx->stream));
+        hipLaunchKernelGGL(rv::skin_check, dim3(static_cast<uint32_t>((n_records + 255u) / 256u)), dim3(256), 0, ctx->stream, reinterpret_cast<const uint4 *>(skin), n_records,
+                           RVPT_HIP_SKIN_MAX_BONES, ctx->d_skin_words);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_skin_words, ctx->d_skin_words, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const unsigned long long bad = ctx->h_skin_words[0], top = ctx->h_skin_words[1];
+        if (bad != ~0ull) {
+            const uint64_t r = bad >> 2;
+            const uint32_t j = static_cast<uint32_t>(bad & 3u);
+            uint32_t value = 0;
+            if (r < n_records) HIP_TRY(ctx, hipMemcpy(&value, &skin[r].bone[j], sizeof value, hipMemcpyDeviceToHost));
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "bind: skin[%llu].bone[%u] = %u: a bone index lies below %u", static_cast<unsigned long long>(r), j, value, RVPT_HIP_SKIN_MAX_BONES);
+        }
+        max_bone = static_cast<uint32_t>(top >> 32), max_pos = 0xFFFFFFFFull - (top & 0xFFFFFFFFull);
+    }
+    // every refusal is behind: the copy (no frame reads d_skin, and every skin update has waited for its kernel)
+    if (bvh) {
+        if (int rc = grow(ctx, ctx->d_skin, ctx->cap_skin, 2 * n_records, sizeof(uint4))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_skin, skin, n_records * sizeof(rvpt_vertex_skin), dev >= 0 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // caller may free its list on return
+    } else {
+        ctx->h_skin.assign(skin, skin + n_records);
+    }
+    ctx->have_skin = true;
+    ctx->skin_max_bone = max_bone, ctx->skin_max_pos = max_pos;
+    ctx->skin_bones = 0;
+    ctx->err.clear();
+    return RVPT_HIP_OK;
+}
+
+// one vertex through its four weighted matrices, the host form of rv::skin_vertices' arithmetic: q_j = pose_vertex_host(M[bone[j]], p), then per component
+// ((w0 q0 + w1 q1) + w2 q2) + w3 q3, every product and sum rounded on its own (this file is compiled with -ffp-contract=off)
+static void skin_vertex_host(const rvpt_bone *bones, const rvpt_vertex_skin &s, const float p[3], float out[3])
+{
+    float q[4][3];
+    for (int j = 0; j < 4; ++j) pose_vertex_host(bones[s.bone[j]].m, p, q[j]);
+    for (int i = 0; i < 3; ++i) {
+        const float a = s.weight[0] * q[0][i], b = s.weight[1] * q[1][i], c = s.weight[2] * q[2][i], d = s.weight[3] * q[3][i];
+        const float ab = a + b;
+        const float abc = ab + c;
+        out[i] = abc + d;
+    }
+}
+
+// The SKIN UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): k matrices; every vertex of the stored scene is posed from the rest pose by the four weighted
+// matrices its bound record names.  BVH contexts: the snapshot if the context holds no rest pose, rv::skin_vertices over every vertex quad, then the plain
+// update form's tail (every box refitted).  Brute-force contexts skin on the host and run the plain form.  Everything is refused before anything is touched.
+static int update_geometry_skin(rvpt_hip_ctx *ctx, const rvpt_bone *bones, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats)
+{
+    if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update before any full upload_scene on this context: there is no scene to update");
+    if (k == 0) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update without bones");
+    if (k > RVPT_HIP_SKIN_MAX_BONES) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update with %zu bones: at most %u", k, RVPT_HIP_SKIN_MAX_BONES);
+    if (!bones) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update without a list: `nodes` points at one rvpt_bone per bone");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int dev = device_of_pointer(bones);
+    if (reinterpret_cast<uintptr_t>(bones) % (dev >= 0 ? 16u : 4u))
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update: the list at %p is not %u-byte aligned", static_cast<const void *>(bones), dev >= 0 ? 16u : 4u);
+    if (tris) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update takes no triangles: the library skins the ones it holds (`tris` must be NULL)");
+    if (mats || n_mats) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update takes no materials: it keeps the stored ones");
+    if (!ctx->have_skin) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update before a bind: the stored scene has no weights (RVPT_HIP_NODES_BIND_SKIN)");
+    if (k <= ctx->skin_max_bone)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update with %zu bones: the binding names bone %u (skin[%llu]), which needs %u", k, ctx->skin_max_bone,
+                    static_cast<unsigned long long>(ctx->skin_max_pos), ctx->skin_max_bone + 1u);
+    const size_t n_tris = ctx->n_tris;
+    const bool bvh = is_bvh(ctx, n_tris);
+    if (dev >= 0 && dev != ctx->device) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update: the bones are device memory of GPU %d, the context lives on GPU %d", dev, ctx->device);
+    if (dev >= 0 && !bvh) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update of a brute-force context from a device pointer: it skins on the host, pass a host array");
+    if (bvh && ctx->refit_levels.empty())  // (the laboratory's knob only, as in the plain form)
+#if RVPT_HIP_LAB
+        return fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "geometry update needs the breadth-first device layout of the tree: RVPT_HIP_BVH_CALLER_LAYOUT keeps the caller's, which has no level ranges");
+#else
+        return fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "geometry update needs the level ranges of the tree's device layout, which this context does not hold");
+#endif
+
+    if (!bvh) {  // the rest pose on the host, the skinned records through the plain form
+        if (int rc0 = sync_all(ctx)) return rc0;
+        std::vector<rvpt_triangle> skinned(n_tris);
+        HIP_TRY(ctx, hipMemcpy(skinned.data(), ctx->d_tris, n_tris * sizeof(rvpt_triangle), hipMemcpyDeviceToHost));
+        if (!ctx->have_rest) {
+            ctx->h_rest.resize(12 * n_tris);
+            for (size_t t = 0; t < n_tris; ++t) std::memcpy(&ctx->h_rest[12 * t], &skinned[t], offsetof(rvpt_triangle, mat_id));
+            ctx->have_rest = true;
+        }
+        for (size_t t = 0; t < n_tris; ++t) {
+            const float *r = &ctx->h_rest[12 * t];
+            float *rows[3] = {skinned[t].vert0, skinned[t].vert1, skinned[t].vert2};
+            for (int v = 0; v < 3; ++v) {
+                skin_vertex_host(bones, ctx->h_skin[3 * t + v], r + 4 * v, rows[v]);
+                rows[v][3] = r[4 * v + 3];
+            }
+        }
+        const int rc0 = update_geometry(ctx, skinned.data(), n_tris);
+        if (rc0 == RVPT_HIP_OK) ctx->err.clear();
+        return rc0;
+    }
+
+    int rc;
+    const uint32_t n = static_cast<uint32_t>(n_tris), kk = static_cast<uint32_t>(k);
+    if ((rc = grow(ctx, ctx->d_bones, ctx->cap_bones, 3 * static_cast<size_t>(RVPT_HIP_SKIN_MAX_BONES), sizeof(float4)))) return rc;
+    if (!ctx->have_rest && (rc = grow(ctx, ctx->d_rest, ctx->cap_rest, 3 * n_tris, sizeof(float4)))) return rc;
+    if (int rc0 = sync_all(ctx)) return rc0;  // frames in flight finish on the old geometry
+    ctx->skin_bones = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bones, bones, k * sizeof(rvpt_bone), dev >= 0 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    if (!ctx->have_rest) {  // the snapshot, as the pose update takes it: 48 of every 64 bytes of d_tris, device to device, in stored order
+        HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_rest, offsetof(rvpt_triangle, mat_id), ctx->d_tris, sizeof(rvpt_triangle), offsetof(rvpt_triangle, mat_id), n_tris, hipMemcpyDeviceToDevice,
+                                      ctx->stream));
+        ctx->have_rest = true;
+    }
+    // a grid the device holds at once — as many work-groups per CU as their LDS allows, eight at the most —, each staging the matrices once and striding over the vertices
+    const uint64_t skin_blocks = (3ull * n + rv::kSkinBlock - 1u) / rv::kSkinBlock;
+    const uint64_t skin_per_cu = std::min<uint64_t>(8u, (160u * 1024u) / (k * sizeof(rvpt_bone) + 512u));
+    const uint32_t skin_grid = static_cast<uint32_t>(std::min<uint64_t>(skin_blocks, static_cast<uint64_t>(std::max(ctx->num_cus, 1)) * skin_per_cu));
+    hipLaunchKernelGGL(rv::skin_vertices, dim3(skin_grid), dim3(rv::kSkinBlock), k * sizeof(rvpt_bone), ctx->stream, ctx->d_rest,
+                       ctx->d_skin, ctx->d_bones, kk, n, ctx->have_perm ? ctx->d_perm : nullptr, ctx->d_tris);
+    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = update_geometry_tail(ctx, true, nullptr, n_tris))) {  // (a host `bones` is read by the copy above until the stream has been waited for)
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    ctx->skin_bones = kk;
+    ctx->err.clear();
+    return RVPT_HIP_OK;
+}
+
 // The GUARDED UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; BVH contexts): the update form, then the cost of the refitted tree, then — with a limit,
 // once the cost has grown past limit x base cost — a rebuild by the builder that made the stored tree, from the moved triangles carried back into the
 // caller's order.  permille: 0 (report only) or 1000 .. 65535, checked by the caller.
@@ -1883,15 +2083,24 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
     if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
     // the POSE UPDATE: the count RVPT_HIP_NODES_UPDATE_POSE, `nodes` then points at n_tris rvpt_part_move records and `tris` is NULL (the form checks that itself)
     if (n_nodes == RVPT_HIP_NODES_UPDATE_POSE) return update_geometry_pose(ctx, reinterpret_cast<const rvpt_part_move *>(nodes), tris, n_tris, mats, n_mats);
+    // the BIND and the SKIN UPDATE: `nodes` points at three rvpt_vertex_skin records per triangle, or at n_tris rvpt_bone matrices; both keep the rest pose
+    if (n_nodes == RVPT_HIP_NODES_BIND_SKIN) return bind_skin(ctx, reinterpret_cast<const rvpt_vertex_skin *>(nodes), tris, n_tris, mats, n_mats);
+    if (n_nodes == RVPT_HIP_NODES_UPDATE_SKIN) return update_geometry_skin(ctx, reinterpret_cast<const rvpt_bone *>(nodes), tris, n_tris, mats, n_mats);
     // the GUARDED POSE UPDATE: the same arguments and a count of the band RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille) lies in.  It keeps the rest pose, through a
     // rebuild too; only a rebuild that failed, and so left no scene, has dropped it
     if ((size_t)0 - n_nodes >= 0x200000u && (size_t)0 - n_nodes < 0x300000u) {
         const size_t permille = (size_t)0 - n_nodes - 0x200000u;
         if (permille != 0 && (permille < 1000u || permille > 65535u))
             return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded pose update: the limit is 0 (report only) or 1000 .. 65535 permille, got %zu", permille);
-        return update_geometry_pose_guarded(ctx, reinterpret_cast<const rvpt_part_move *>(nodes), tris, n_tris, mats, n_mats, static_cast<uint32_t>(permille));
+        const int rc = update_geometry_pose_guarded(ctx, reinterpret_cast<const rvpt_part_move *>(nodes), tris, n_tris, mats, n_mats, static_cast<uint32_t>(permille));
+        if (!ctx->have_scene) drop_skin(ctx);  // (a rebuild that failed)
+        return rc;
     }
+    // the update forms keep the skin update's binding; a full upload and a build form the caller asks for drop it, and so does any call that leaves no scene
+    const bool update_form = n_nodes == RVPT_HIP_NODES_UPDATE_SPARSE || (n_tris > 0 && !nodes && n_nodes == 0 && !mats && n_mats == 0) ||
+                             (!nodes && (size_t)0 - n_nodes >= 0x10000u && (size_t)0 - n_nodes < 0x110000u);
     const int rc = upload_scene_other_forms(ctx, nodes, n_nodes, tris, n_tris, mats, n_mats);
+    if ((rc == RVPT_HIP_OK && !update_form) || !ctx->have_scene) drop_skin(ctx);
     // the rest pose of the pose update is the stored vertices as the last successful call of any OTHER form left them: the next pose update snapshots afresh
     if (rc == RVPT_HIP_OK || !ctx->have_scene) ctx->have_rest = false;
     return rc;
@@ -3011,6 +3220,12 @@ int rvpt_hip_selftest_scene_state(rvpt_hip_ctx *ctx, rvpt_hip_scene_state_info *
         else src = ctx->h_rest.data(), host = true;
         bytes = ctx->have_rest ? n_tris * offsetof(rvpt_triangle, mat_id) : 0;
         break;
+    case RVPT_HIP_STATE_SKIN:  // the binding, in the update form's order: on the device of a BVH context, on the host of a brute-force one
+        if (is_bvh(ctx, n_tris)) src = ctx->d_skin;
+        else src = ctx->h_skin.data(), host = true;
+        bytes = ctx->have_skin ? 3 * n_tris * sizeof(rvpt_vertex_skin) : 0;
+        break;
+    case RVPT_HIP_STATE_BONES: src = ctx->d_bones, bytes = ctx->have_skin ? ctx->skin_bones * sizeof(rvpt_bone) : 0; break;
     default: return fail(ctx, RVPT_HIP_ERR_INVALID, "scene state: there is no piece %u", piece);
     }
     if (bytes_out) *bytes_out = bytes;

@@ -50,4 +50,14 @@ __global__ void rest_to_caller_order(const float4 *__restrict__ rest, const uint
 // ... and rest[pos] = in[perm[pos]] with the new one behind it
 __global__ void rest_to_stored_order(const float4 *__restrict__ in, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ rest);
 
+// The SKIN UPDATE (include/rvpt_hip.h; rvpt_abi.hip: bind_skin, update_geometry_skin).  skin_check: the check of a bind from device memory, one thread per
+// 32-byte record, grid = ceil(n_records / block); words = {all ones, 0} before the launch, the smallest offence and the largest bone with its place after it ...
+__global__ void skin_check(const uint4 *__restrict__ skin, uint64_t n_records, uint32_t limit, unsigned long long *__restrict__ words);
+// ... and the skin: one thread per vertex quad of the rest pose at a time, ANY grid of kSkinBlock lanes (the work-groups stride over the 3 n quads; the host
+// launches what the device holds at once), k x 48 bytes of dynamic LDS for the matrices (k <= 1024), staged once per work-group.  skin: two
+// quads per vertex in the update form's order, bones: three quads per matrix, perm may be null.  Writes the three vertex rows of every triangle of tris.
+constexpr uint32_t kSkinBlock = 256;
+__global__ void skin_vertices(const float4 *__restrict__ rest, const uint4 *__restrict__ skin, const float4 *__restrict__ bones, uint32_t k, uint32_t n_tris,
+                              const uint32_t *__restrict__ perm, float4 *__restrict__ tris);
+
 }  // namespace rv

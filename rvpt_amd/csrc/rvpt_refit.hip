@@ -329,4 +329,71 @@ __global__ void rest_to_stored_order(const float4 *__restrict__ in, const uint32
     rest[t] = in[3u * static_cast<size_t>(src) + q];
 }
 
+// ---- the skin update (include/rvpt_hip.h: BIND, SKIN UPDATE) ---------------------------------------------------------------------------------------------------
+// The check of a bind from DEVICE memory, one thread per rvpt_vertex_skin record (eight words: bone[4], weight[4]; 3 n of them).  words[0] is lowered to the
+// smallest key 4 position + j of a bone[j] >= limit — the smallest offending record position, then the smallest j in it; the host fetches the value itself only
+// when it has to word the refusal —, words[1] is raised to the largest key bone << 32 | ~position of the bones below the limit: the largest bone index and the
+// smallest record position that holds it.  The host fills words with {all ones, 0} and reads both back in one copy.  One atomic per wave and word, as in sparse_claim; no early return in front of the fold.
+__global__ void skin_check(const uint4 *__restrict__ skin, uint64_t n_records, uint32_t limit, unsigned long long *__restrict__ words)
+{
+    const uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    unsigned long long bad = ~0ull, top = 0ull;
+    if (r < n_records) {
+        const uint4 b = skin[2 * r];
+        const uint32_t bone[4] = {b.x, b.y, b.z, b.w};
+        for (uint32_t j = 4; j-- > 0;) {
+            if (bone[j] >= limit) bad = 4ull * r + j;
+            else top = max(top, (static_cast<unsigned long long>(bone[j]) << 32) | (0xFFFFFFFFull - r));
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        bad = min(bad, static_cast<unsigned long long>(__shfl_down(bad, off, 64)));
+        top = max(top, static_cast<unsigned long long>(__shfl_down(top, off, 64)));
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (bad != ~0ull) atomicMin(&words[0], bad);
+        atomicMax(&words[1], top);
+    }
+}
+
+// The skin itself: one thread per VERTEX QUAD of the rest pose at a time, t = 3 pos + v as in rest_to_*_order, so rest[t] is a 16-byte load consecutive across
+// lanes.  The grid is one the device holds at once (the host sizes it: as many work-groups per CU as their LDS allows, eight at the most) and strides over
+// the quads, so that the matrices are staged once per RESIDENT work-group and not once per 256 quads: with 1024 matrices a work-group per 256 quads staged
+// 48 KiB to skin 12 KiB of vertices and measured 0.264 ms against 0.216 ms on 1 M triangles (profiles/skin_update.txt).
+// The record of the vertex is skin[3 idx + v], idx = perm ? perm[pos] : pos (the binding is kept in the order the plain update form takes; perm[pos] is the
+// caller's index of stored position pos), read as two 16-byte loads.  The k matrices are staged once per work-group into dynamic LDS, ROW MAJOR as they
+// arrive (k x 12 floats): a matrix is three ds_read_b128, whose bank is (address / 4) mod 64, so the sixteen lanes of one LDS cycle conflict only where two
+// DIFFERENT bones lie a multiple of 16 bones apart (12 b mod 64 runs through all sixteen 4-bank slots over sixteen consecutive bones), and lanes of one
+// triangle or of neighbours share their bones and are served by broadcast.  A transposed layout would turn the three loads into twelve.
+// The arithmetic is the header's: q_j = pose_vertex(M[bone[j]], p), out = ((w0 q0 + w1 q1) + w2 q2) + w3 q3 per component, every product and sum rounded on its
+// own; all four influences are evaluated whatever their weight.  A bone index >= k, or a perm word >= n, drops the vertex: it never becomes an address (the
+// bind refused such records; a stray word must not fault).  No atomics, no return in front of the barrier or inside the loop.  The w lane comes from the rest pose.
+__global__ __launch_bounds__(kSkinBlock) void skin_vertices(const float4 *__restrict__ rest, const uint4 *__restrict__ skin, const float4 *__restrict__ bones, uint32_t k,
+                                                            uint32_t n_tris, const uint32_t *__restrict__ perm, float4 *__restrict__ tris)
+{
+    extern __shared__ float4 staged[];  // 3 k quads
+    for (uint32_t i = threadIdx.x; i < 3u * k; i += kSkinBlock) staged[i] = bones[i];
+    __syncthreads();
+    const float *__restrict__ m = reinterpret_cast<const float *>(staged);
+    const uint64_t total = 3ull * n_tris, step = static_cast<uint64_t>(gridDim.x) * kSkinBlock;
+    for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * kSkinBlock + threadIdx.x; t < total; t += step) {
+        const uint64_t pos = t / 3u;
+        const uint32_t v = static_cast<uint32_t>(t - 3u * pos);
+        const uint32_t idx = perm ? perm[pos] : static_cast<uint32_t>(pos);
+        if (idx >= n_tris) continue;
+        const float4 p = rest[t];
+        const uint4 *__restrict__ rec = skin + 2u * (3u * static_cast<uint64_t>(idx) + v);
+        const uint4 b = rec[0], wq = rec[1];
+        if (b.x >= k || b.y >= k || b.z >= k || b.w >= k) continue;
+        const float w0 = __uint_as_float(wq.x), w1 = __uint_as_float(wq.y), w2 = __uint_as_float(wq.z), w3 = __uint_as_float(wq.w);
+        const float4 q0 = pose_vertex(m + 12u * b.x, p), q1 = pose_vertex(m + 12u * b.y, p), q2 = pose_vertex(m + 12u * b.z, p), q3 = pose_vertex(m + 12u * b.w, p);
+        float4 out;
+        out.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(w0, q0.x), __fmul_rn(w1, q1.x)), __fmul_rn(w2, q2.x)), __fmul_rn(w3, q3.x));
+        out.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(w0, q0.y), __fmul_rn(w1, q1.y)), __fmul_rn(w2, q2.y)), __fmul_rn(w3, q3.y));
+        out.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(w0, q0.z), __fmul_rn(w1, q1.z)), __fmul_rn(w2, q2.z)), __fmul_rn(w3, q3.z));
+        out.w = p.w;
+        tris[4u * pos + v] = out;
+    }
+}
+
 }  // namespace rv

@@ -165,6 +165,7 @@ bool RVPT::initialize()
     order_.clear();
     inverse_.clear();
     have_rest_ = false;
+    skin_.clear();  // (a full upload or a build form drops the device's binding)
     device_built_ =options_.device_build && options_.bvh_traversal && !triangles_.empty();
     if (!triangles_.empty() && !device_built_) {
         nodes_.resize(2 * triangles_.size() - 1);
@@ -352,6 +353,90 @@ bool RVPT::pose_parts_with(const rvpt_part_move *moves, size_t k, size_t count, 
             if (!device_built_) std::memcpy(sorted_[inverse_[t]].vertex0, triangles_[t].vertex0, offsetof(Triangle, material_id));
         }
     if (!device_built_) nodes_stale_ = true;  // (the host tree is tight: the full refit of bvh_nodes() is the sparse one)
+    previous_.valid = false;  // a new scene: nothing accumulated so far belongs to it
+    return true;
+}
+
+// (volatile, as in pose_vertex: no pair of a product and a sum can be contracted)
+void skin_vertex(const rvpt_bone *bones, const rvpt_vertex_skin &skin, const float in[4], float out[4])
+{
+    float q[4][4];
+    for (int j = 0; j < 4; ++j) pose_vertex(bones[skin.bone[j]].m, in, q[j]);
+    const float w = in[3];
+    for (int i = 0; i < 3; ++i) {
+        volatile float a = skin.weight[0] * q[0][i], b = skin.weight[1] * q[1][i], c = skin.weight[2] * q[2][i], d = skin.weight[3] * q[3][i];
+        volatile float s = a + b;
+        s = s + c;
+        s = s + d;
+        out[i] = s;
+    }
+    out[3] = w;
+}
+
+// The bind: `nodes` carries three rvpt_vertex_skin records per triangle, the count is RVPT_HIP_NODES_BIND_SKIN, no triangles go down.
+bool RVPT::bind_skin(const rvpt_vertex_skin *skin, size_t n_tris)
+{
+    if (!ctx_) {
+        error_ = "bind_skin before initialize()";
+        return false;
+    }
+    if (!skin) {
+        error_ = "bind_skin: no records given";
+        return false;
+    }
+    if (n_tris != triangles_.size()) {
+        error_ = "bind_skin: records for " + std::to_string(n_tris) + " triangles given, the scene has " + std::to_string(triangles_.size());
+        return false;
+    }
+    for (size_t r = 0; r < 3 * n_tris; ++r)
+        for (int j = 0; j < 4; ++j)
+            if (skin[r].bone[j] >= RVPT_HIP_SKIN_MAX_BONES) {
+                error_ = "bind_skin: skin[" + std::to_string(r) + "].bone[" + std::to_string(j) + "] = " + std::to_string(skin[r].bone[j]) + " is not below " + std::to_string(RVPT_HIP_SKIN_MAX_BONES);
+                return false;
+            }
+    std::vector<rvpt_vertex_skin> sorted;  // what goes down after a host build: the records of leaf-order triangle i are those of added triangle order_[i]
+    if (!device_built_) {
+        sorted.resize(3 * n_tris);
+        for (size_t i = 0; i < n_tris; ++i) std::memcpy(&sorted[3 * i], &skin[3 * size_t(order_[i])], 3 * sizeof(rvpt_vertex_skin));
+    }
+    const rvpt_vertex_skin *sent = device_built_ ? skin : sorted.data();
+    if (!check(backend_.upload_scene(ctx_, reinterpret_cast<const rvpt_bvh_node *>(sent), RVPT_HIP_NODES_BIND_SKIN, nullptr, n_tris, nullptr, 0), "rvpt_hip_upload_scene (bind)")) return false;
+    skin_.assign(skin, skin + 3 * n_tris);
+    return true;
+}
+
+// The skin form: `nodes` carries rvpt_bone records, the count is RVPT_HIP_NODES_UPDATE_SKIN, no triangles go down.
+bool RVPT::skin(const rvpt_bone *bones, size_t k)
+{
+    if (!ctx_) {
+        error_ = "skin before initialize()";
+        return false;
+    }
+    if (skin_.empty() && !triangles_.empty()) {
+        error_ = "skin: skin update before a bind (bind_skin)";
+        return false;
+    }
+    if (!bones || k == 0 || k > RVPT_HIP_SKIN_MAX_BONES) {
+        error_ = "skin: 1 .. " + std::to_string(RVPT_HIP_SKIN_MAX_BONES) + " bones are needed, got " + std::to_string(bones ? k : 0);
+        return false;
+    }
+    for (size_t r = 0; r < skin_.size(); ++r)
+        for (int j = 0; j < 4; ++j)
+            if (skin_[r].bone[j] >= k) {
+                error_ = "skin: skin[" + std::to_string(r) + "].bone[" + std::to_string(j) + "] = " + std::to_string(skin_[r].bone[j]) + " with " + std::to_string(k) + " bones";
+                return false;
+            }
+    if (!check(backend_.upload_scene(ctx_, reinterpret_cast<const rvpt_bvh_node *>(bones), RVPT_HIP_NODES_UPDATE_SKIN, nullptr, k, nullptr, 0), "rvpt_hip_upload_scene (skin update)")) return false;
+    if (!have_rest_) rest_ = triangles_, have_rest_ = true;
+    for (size_t t = 0; t < triangles_.size(); ++t) {
+        skin_vertex(bones, skin_[3 * t], rest_[t].vertex0, triangles_[t].vertex0);
+        skin_vertex(bones, skin_[3 * t + 1], rest_[t].vertex1, triangles_[t].vertex1);
+        skin_vertex(bones, skin_[3 * t + 2], rest_[t].vertex2, triangles_[t].vertex2);
+    }
+    if (!device_built_) {
+        for (size_t i = 0; i < order_.size(); ++i) std::memcpy(sorted_[i].vertex0, triangles_[order_[i]].vertex0, offsetof(Triangle, material_id));
+        nodes_stale_ = true;
+    }
     previous_.valid = false;  // a new scene: nothing accumulated so far belongs to it
     return true;
 }

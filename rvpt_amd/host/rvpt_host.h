@@ -108,6 +108,9 @@ bool parse_update_report(const char *sentence, UpdateReport *report);
 // One vertex through the 3x4 matrix of a rvpt_part_move, the arithmetic of the pose update (include/rvpt_hip.h): out[i] = ((m[4i] x + m[4i+1] y) + m[4i+2] z) + m[4i+3],
 // three products and three sums, each rounded to binary32 on its own — never fused, whatever the compiler's flags; out[3] = in[3].  `out` may be `in`.
 void pose_vertex(const float m[12], const float in[4], float out[4]);
+// One vertex through its four weighted bone matrices, the arithmetic of the skin update (include/rvpt_hip.h): q_j = pose_vertex(bones[skin.bone[j]].m, in), then
+// out[i] = ((w0 q0[i] + w1 q1[i]) + w2 q2[i]) + w3 q3[i], every product and sum rounded to binary32 on its own — never fused; out[3] = in[3].  `out` may be `in`.
+void skin_vertex(const rvpt_bone *bones, const rvpt_vertex_skin &skin, const float in[4], float out[4]);
 
 class RVPT {
 public:
@@ -173,6 +176,16 @@ public:
     // start from the same rest pose.  A limit needs Options::device_build.  Brute-force traversal: the plain pose, `report` comes back empty.
     bool pose_parts(const rvpt_part_move *moves, size_t k, double rebuild_above, UpdateReport *report = nullptr);
 
+    // Skinning weights — the bind (RVPT_HIP_NODES_BIND_SKIN; include/rvpt_hip.h: BIND): three records per triangle, four bone indices and four weights per vertex,
+    // for the triangles in the order they were ADDED.  After a device build the records go down as they are; after a host build they are reordered into leaf
+    // order.  Moves nothing; a second bind replaces the first; initialize() drops the binding.  A bone index >= RVPT_HIP_SKIN_MAX_BONES never reaches the ABI.
+    bool bind_skin(const rvpt_vertex_skin *skin, size_t n_tris);
+    // Linear blend skinning — the skin update (RVPT_HIP_NODES_UPDATE_SKIN; include/rvpt_hip.h: SKIN UPDATE): k matrices pose EVERY vertex from the rest pose
+    // pose_parts shares — the triangles as the last initialize() or update_triangles left them; two skin updates do not compose — and every box is refitted.
+    // The host copies are skinned by skin_vertex (the same bits as the device), bvh_nodes() is refitted when next asked for; the next update() restarts the
+    // accumulation.  There is no guarded form.
+    bool skin(const rvpt_bone *bones, size_t k);
+
     // RGBA32F (width*height*4 floats) or RGBA8 (width*height*4 bytes), row-major, top row first
     std::vector<float> read_frame();
     std::vector<uint8_t> read_frame_rgba8();
@@ -223,6 +236,7 @@ private:
     bool device_built_ = false;         // the scene went up by the build form: no nodes_, sorted_, order_ on the host
     std::vector<Triangle> rest_;        // pose_parts: the rest pose in the order the triangles were added, taken by the first pose after another form
     bool have_rest_ = false;
+    std::vector<rvpt_vertex_skin> skin_;  // bind_skin: the bound records in the order the triangles were added
     // PreviousFrameState (rvpt.h:211-219, rvpt.cpp:21-29); empty camera data never compares equal
     struct Previous {
         bool valid = false;

@@ -44,6 +44,12 @@ NODES_UPDATE_SPARSE = C.c_size_t(-4).value  # RVPT_HIP_NODES_UPDATE_SPARSE: the 
 NODES_UPDATE_POSE = C.c_size_t(-5).value  # RVPT_HIP_NODES_UPDATE_POSE: the pose update (Context.pose_parts): `nodes` then carries PART_MOVE_DTYPE records, no triangles
 # rvpt_part_move (64 B): a 3x4 matrix, row major, for the triangles [first, first + count); two reserved words, 0
 PART_MOVE_DTYPE = np.dtype([("m", "<f4", (12,)), ("first", "<u4"), ("count", "<u4"), ("reserved", "<u4", (2,))])
+NODES_BIND_SKIN = C.c_size_t(-6).value  # RVPT_HIP_NODES_BIND_SKIN: the bind (Context.bind_skin): `nodes` then carries three VERTEX_SKIN_DTYPE records per triangle, no triangles
+NODES_UPDATE_SKIN = C.c_size_t(-7).value  # RVPT_HIP_NODES_UPDATE_SKIN: the skin update (Context.skin): `nodes` then carries BONE_DTYPE matrices, no triangles
+SKIN_MAX_BONES = 1024  # RVPT_HIP_SKIN_MAX_BONES
+# rvpt_vertex_skin (32 B): the four bone indices and the four weights of one vertex;  rvpt_bone (48 B): a 3x4 matrix, row major
+VERTEX_SKIN_DTYPE = np.dtype([("bone", "<u4", (4,)), ("weight", "<f4", (4,))])
+BONE_DTYPE = np.dtype([("m", "<f4", (12,))])
 NODES_UPDATE_GUARDED_BASE = 0x10000  # RVPT_HIP_NODES_UPDATE_GUARDED(permille) = (size_t)0 - (0x10000 + permille): the guarded update (Context.update_triangles(rebuild_above=))
 NODES_UPDATE_POSE_GUARDED_BASE = 0x200000  # RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille) = (size_t)0 - (0x200000 + permille): the guarded pose update (Context.pose_parts(rebuild_above=))
 NODES_BUILD_PLOC = C.c_size_t(-2).value  # RVPT_HIP_NODES_BUILD_PLOC: the build form with a PLOC tree (Context.build_scene(method="ploc"))
@@ -365,7 +371,7 @@ NODE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("bounds", "<f4", (6,
 SCENE_STATE_PIECES = {
     "nodes": (1, NODE_DTYPE, ()), "tris": (2, np.float32, (16,)), "perm": (3, np.uint32, ()), "wide": (4, np.float32, (8, 4)), "wide_map": (5, np.uint32, (4,)),
     "refit_levels": (6, np.uint32, (2,)), "sparse_parent": (7, np.uint32, ()), "sparse_leaf_of": (8, np.uint32, ()), "sparse_dirty": (9, np.uint32, ()),
-    "inv_perm": (10, np.uint32, ()), "rest": (11, np.float32, (12,)),
+    "inv_perm": (10, np.uint32, ()), "rest": (11, np.float32, (12,)), "skin": (12, VERTEX_SKIN_DTYPE, ()), "bones": (13, np.float32, (12,)),
 }
 BUILT_BY = (None, "lbvh", "ploc", "sah")  # rvpt_hip_scene_state_info::built_by
 
@@ -541,6 +547,64 @@ class Context:
         if rebuild_above is None or (self.flags & (TRAVERSAL_BVH | TRAVERSAL_BVH_ORDERED)) == 0:
             return None
         return parse_update_report((self._L.rvpt_hip_last_error(self._h) or b"").decode())
+
+    def _device_tensor(self, t, what: str, words: int):
+        """(pointer, rows) of a contiguous float32 / int32 / uint8 torch tensor on this context's device whose rows are `words` 4-byte words: device memory passed
+        as it is once the stream that wrote it has finished.  None for a tensor on the host (the caller then takes its numpy view)."""
+        import torch
+        if not t.is_cuda:
+            return None
+        if t.device.index != self.device:
+            raise NativeError(ERR_INVALID, f"{what}: the tensor lives on device {t.device.index}, the context on {self.device}")
+        nbytes = t.numel() * t.element_size()
+        if not t.is_contiguous() or t.element_size() not in (1, 4) or nbytes % (4 * words):
+            raise NativeError(ERR_INVALID, f"{what}: a contiguous tensor of {4 * words}-byte records is needed, got {t.dtype} {tuple(t.shape)}")
+        torch.cuda.current_stream(t.device).synchronize()  # the library works on its own stream: what wrote the tensor must have finished
+        return C.c_void_p(t.data_ptr()), nbytes // (4 * words)
+
+    def bind_skin(self, skin, weights=None) -> None:
+        """The BIND of rvpt_hip_upload_scene (include/rvpt_hip.h): four bone indices and four weights per vertex, three records per triangle in the order
+        update_triangles takes, kept by the library for skin().  skin: what scene.vertex_skins takes — a VERTEX_SKIN_DTYPE array, or indices[n, 3, 4] beside
+        weights[n, 3, 4] — or, on a BVH context, a contiguous torch tensor on this context's device holding the 32-byte records (int32 / float32 [3 n, 8], or
+        uint8 [3 n, 32]), which never visits the host.  Moves nothing; a second bind replaces the first; an upload_scene or build_scene drops the binding."""
+        from . import scene
+        if weights is None and not isinstance(skin, (np.ndarray, tuple, list)) and hasattr(skin, "data_ptr"):
+            dev = self._device_tensor(skin, "bind_skin", 8)
+            if dev is not None:
+                ptr, records = dev
+                if records % 3:
+                    raise NativeError(ERR_INVALID, f"bind_skin: {records} records are not three per triangle")
+                _check(self._L.rvpt_hip_upload_scene(self._h, ptr, NODES_BIND_SKIN, None, records // 3, None, 0), self._h, self._L)
+                return None
+            skin = skin.numpy().view(np.uint8).reshape(-1).view(VERTEX_SKIN_DTYPE)
+        try:
+            rec = scene.vertex_skins(skin, weights)
+        except (ValueError, TypeError) as e:
+            raise NativeError(ERR_INVALID, f"bind_skin: {e}") from None
+        _check(self._L.rvpt_hip_upload_scene(self._h, _ptr(rec), NODES_BIND_SKIN, None, rec.shape[0] // 3, None, 0), self._h, self._L)
+        return None
+
+    def skin(self, bones) -> None:
+        """The SKIN UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): linear blend skinning — every vertex is posed FROM THE REST POSE (the pose update's) by
+        the four weighted matrices its bound record names, and every box of the tree is refitted as after update_triangles.  scene.skin_triangles is the same
+        on the host, bit for bit.  bones: float32[k, 3, 4] or [k, 12], [k, 4, 4] with last rows 0 0 0 1, or — BVH contexts — a contiguous float32 torch tensor
+        [k, 3, 4] / [k, 12] on this context's device, which never visits the host.  Needs a bind_skin first and more bones than its largest index."""
+        from . import scene
+        if not isinstance(bones, np.ndarray) and hasattr(bones, "data_ptr"):
+            import torch
+            if bones.dtype != torch.float32 or tuple(bones.shape[1:]) not in ((3, 4), (12,)):
+                raise NativeError(ERR_INVALID, f"skin: a float32 tensor [k, 3, 4] or [k, 12] is needed, got {bones.dtype} {tuple(bones.shape)}")
+            dev = self._device_tensor(bones, "skin", 12)
+            if dev is not None:
+                _check(self._L.rvpt_hip_upload_scene(self._h, dev[0], NODES_UPDATE_SKIN, None, dev[1], None, 0), self._h, self._L)
+                return None
+            bones = bones.numpy()
+        try:
+            m = scene.bone_matrices(bones)
+        except (ValueError, TypeError) as e:
+            raise NativeError(ERR_INVALID, f"skin: {e}") from None
+        _check(self._L.rvpt_hip_upload_scene(self._h, _ptr(m), NODES_UPDATE_SKIN, None, m.shape[0], None, 0), self._h, self._L)
+        return None
 
     def set_frame(self, settings: np.ndarray, camera: np.ndarray) -> None:
         settings = np.ascontiguousarray(settings)

@@ -104,6 +104,7 @@ class RVPT:
         self._sorted_triangles: np.ndarray | None = None
         self._built_from: np.ndarray | None = None  # build="device": the triangles the device built its tree from, until the host statement is asked for
         self._current_triangles: np.ndarray | None = None  # ... and the triangles the scene holds now, in the order they were added
+        self._skin: np.ndarray | None = None  # bind_skin: the bound records, in the order the triangles were added
         self._rest_triangles: np.ndarray | None = None  # pose_parts: the rest pose, in the order they were added — the triangles as the last call of another form left them
         self._previous_key = None  # default-constructed PreviousFrameState never compares equal (empty camera data)
         self._ctx: native.Context | None = None
@@ -307,12 +308,59 @@ class RVPT:
         self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
         return report
 
+    def bind_skin(self, skin, weights=None) -> None:
+        """Skinning weights — the BIND (Context.bind_skin; include/rvpt_hip.h): four bone indices and four weights per vertex, what scene.vertex_skins takes (a
+        native.VERTEX_SKIN_DTYPE array of three records per triangle, or indices[n, 3, 4] beside weights[n, 3, 4]), for the triangles in the order they were
+        ADDED.  After a host build the records are reordered into leaf order with primitive_indices, the counterpart of pose_parts' runs; after a device build
+        they go down as given.  Moves nothing and restarts nothing; a second bind replaces the first; initialize() drops the binding."""
+        if self._ctx is None or self._n_triangles is None:
+            raise RuntimeError("bind_skin before initialize()")
+        try:
+            rec = scene.vertex_skins(skin, weights)
+        except (ValueError, TypeError) as e:
+            raise native.NativeError(native.ERR_INVALID, f"bind_skin: {e}") from None
+        if rec.shape[0] != 3 * self._n_triangles:
+            raise native.NativeError(native.ERR_INVALID, f"bind_skin: {rec.shape[0]} records given, the scene has {self._n_triangles} triangles: three per triangle")
+        if self._device_built:
+            self._ctx.bind_skin(rec)
+        else:
+            self._ctx.bind_skin(np.ascontiguousarray(rec.reshape(-1, 3)[np.asarray(self.primitive_indices, dtype=np.int64)]).reshape(-1))
+        self._skin = rec.copy()
+
+    def skin(self, bones) -> None:
+        """Linear blend skinning — the SKIN UPDATE (Context.skin; include/rvpt_hip.h): `bones` (float32[k, 3, 4], [k, 12], or [k, 4, 4] with last rows 0 0 0 1) pose
+        EVERY vertex from the REST POSE — pose_parts' rest pose: the triangles as the last initialize() or update_triangles left them; two skin updates do not
+        compose — by the four weighted matrices bind_skin gave it; every box is refitted, on the device and in bvh_nodes.  scene.skin_triangles is the statement.
+        The next update() restarts the accumulation, as after update_triangles."""
+        if self._ctx is None or self._n_triangles is None:
+            raise RuntimeError("skin before initialize()")
+        if self._skin is None:
+            raise native.NativeError(native.ERR_INVALID, "skin: skin update before a bind (bind_skin)")
+        current = np.concatenate(self.triangles) if self._current_triangles is None else self._current_triangles
+        rest = current if self._rest_triangles is None else self._rest_triangles
+        try:
+            m = scene.bone_matrices(bones)
+            skinned = scene.skin_triangles(rest, self._skin, m)
+            skinned[:, 12:] = current[:, 12:]
+        except (ValueError, TypeError) as e:
+            raise native.NativeError(native.ERR_INVALID, f"skin: {e}") from None
+        self._ctx.skin(m)
+        self._rest_triangles = rest
+        self.triangles = [skinned]
+        if self._device_built:
+            self._current_triangles = skinned
+        if self._built_from is None:  # there is a host statement to keep right: every box moves
+            self._sorted_triangles = skinned[np.asarray(self._primitive_indices, dtype=np.int64)]
+            self._nodes_stale, self._stale_touched = self._bvh_nodes is not None, None
+        self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
+
     # -- lifecycle -----------------------------------------------------------------------------------------
     def initialize(self) -> bool:
         tris = np.concatenate(self.triangles) if self.triangles else np.zeros((0, 16), np.float32)
         mats = np.stack(self.materials) if self.materials else np.zeros((0, 12), np.float32)
         self._n_triangles = tris.shape[0]
         self._rest_triangles = None
+        self._skin = None
         self._device_built = self.build in ("device", "device-ploc", "device-sah") and self.traversal != "brute" and tris.shape[0] > 0
         self._ctx = native.Context(self.width, self.height, self.device, self.tile_rank, self.tile_world, self._flags)
         if self._device_built:

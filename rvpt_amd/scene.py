@@ -626,6 +626,84 @@ def pose_parts(rest_tris, moves, current=None) -> np.ndarray:
     return out
 
 
+VERTEX_SKIN_DTYPE = np.dtype([("bone", "<u4", (4,)), ("weight", "<f4", (4,))])  # rvpt_vertex_skin (== native.VERTEX_SKIN_DTYPE)
+SKIN_MAX_BONES = 1024  # == RVPT_HIP_SKIN_MAX_BONES
+
+
+def vertex_skins(skin, weights=None) -> np.ndarray:
+    """The four influences of every vertex as VERTEX_SKIN_DTYPE records [3 n], record 3 t + v for vertex v of triangle t: a structured array of that dtype as it
+    is (any shape of 3 n records), or the pair (indices[n, 3, 4], weights[n, 3, 4]) — as two arguments or as one tuple.  Raises ValueError for anything else:
+    another shape, a record count that is no multiple of three, indices that are not integers, a negative index or one past 2^32 - 1."""
+    if weights is None and isinstance(skin, (tuple, list)) and len(skin) == 2:
+        skin, weights = skin
+    if weights is None:
+        if not (isinstance(skin, np.ndarray) and skin.dtype == VERTEX_SKIN_DTYPE):
+            raise ValueError("vertex_skins: a VERTEX_SKIN_DTYPE array or a pair (indices[n, 3, 4], weights[n, 3, 4]) is needed")
+        rec = np.ascontiguousarray(skin).reshape(-1)
+        if rec.shape[0] % 3:
+            raise ValueError(f"vertex_skins: {rec.shape[0]} records are not three per triangle")
+        return rec
+    idx, w = np.asarray(skin), np.asarray(weights)
+    if idx.ndim != 3 or idx.shape[1:] != (3, 4) or w.shape != idx.shape:
+        raise ValueError(f"vertex_skins: indices and weights are [n, 3, 4] both, got {idx.shape} and {w.shape}")
+    if idx.size and not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError(f"vertex_skins: the indices are integers, got {idx.dtype}")
+    if idx.size and (int(idx.min()) < 0 or int(idx.max()) > 0xFFFFFFFF):
+        bad = int(np.flatnonzero((idx.reshape(-1) < 0) | (idx.reshape(-1) > 0xFFFFFFFF))[0])
+        raise ValueError(f"vertex_skins: skin[{bad // 4}].bone[{bad % 4}] = {int(idx.reshape(-1)[bad])} is not a bone index")
+    rec = np.zeros(idx.shape[0] * 3, dtype=VERTEX_SKIN_DTYPE)
+    rec["bone"] = idx.reshape(-1, 4).astype(np.uint32)
+    rec["weight"] = w.reshape(-1, 4).astype(np.float32)
+    return rec
+
+
+def bone_matrices(bones) -> np.ndarray:
+    """The matrices of a skin update as float32[k, 12] (rvpt_bone: 3x4, row major): float32[k, 3, 4] or [k, 12] as they are, or [k, 4, 4] with every last row
+    0 0 0 1.  ValueError for another shape, such a last row, or more than SKIN_MAX_BONES matrices."""
+    m = np.asarray(bones, dtype=np.float32)
+    if m.ndim == 3 and m.shape[1:] == (4, 4):
+        last = np.array([0, 0, 0, 1], dtype=np.float32)
+        bad = np.flatnonzero((m[:, 3].view(np.uint32) != last.view(np.uint32)).any(axis=1))
+        if bad.size:
+            raise ValueError(f"bones[{int(bad[0])}]: the last row of a 4x4 matrix must be 0 0 0 1, got {m[int(bad[0]), 3].tolist()}")
+        m = m[:, :3]
+    if not ((m.ndim == 3 and m.shape[1:] == (3, 4)) or (m.ndim == 2 and m.shape[1] == 12)):
+        raise ValueError(f"bones: float32[k, 3, 4], [k, 12] or [k, 4, 4] is needed, got {m.shape}")
+    if m.shape[0] > SKIN_MAX_BONES:
+        raise ValueError(f"bones: {m.shape[0]} matrices, at most {SKIN_MAX_BONES}")
+    return np.ascontiguousarray(m.reshape(-1, 12))
+
+
+def skin_triangles(rest_tris, skin, bones) -> np.ndarray:
+    """The normative statement of the SKIN UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): linear blend skinning of EVERY vertex of `rest_tris`.  For a
+    vertex p with the record (bone[4], weight[4]): q_j = ((m0 x + m1 y) + m2 z) + m3 per component with the matrix of bone[j] — pose_parts' arithmetic —, then
+    out_i = ((w0 q0_i + w1 q1_i) + w2 q2_i) + w3 q3_i: float32 throughout, every product and sum rounded on its own (numpy never fuses), all four influences
+    always evaluated, so the device and the host give the same bits.  Only x, y, z of the three vertices change: the .w lanes and the material row are kept.
+    skin: what vertex_skins takes, in the triangles' order; bones: what bone_matrices takes.  ValueError for a shape mismatch, a bone index >= len(bones), or more
+    than SKIN_MAX_BONES bones.  float32[n, 16] -> a new float32[n, 16]."""
+    rest = np.ascontiguousarray(rest_tris, dtype=np.float32).reshape(-1, 16)
+    rec = vertex_skins(skin)
+    m = bone_matrices(bones).reshape(-1, 3, 4)
+    if rec.shape[0] != 3 * rest.shape[0]:
+        raise ValueError(f"skin_triangles: {rec.shape[0]} records for {rest.shape[0]} triangles: three per triangle")
+    if rec.size and int(rec["bone"].max()) >= m.shape[0]:
+        r, j = np.argwhere(rec["bone"] >= m.shape[0])[0]
+        raise ValueError(f"skin_triangles: skin[{int(r)}].bone[{int(j)}] = {int(rec['bone'][r, j])} with {m.shape[0]} bones")
+    out = rest.copy()
+    v = rest.reshape(-1, 4, 4)[:, :3, :].reshape(-1, 4)  # [3 n, xyzw]
+    x, y, z = v[:, 0:1], v[:, 1:2], v[:, 2:3]
+    with np.errstate(all="ignore"):
+        q = []
+        for j in range(4):
+            mj = m[rec["bone"][:, j]]  # [3 n, 3, 4]
+            q.append(((mj[:, :, 0] * x + mj[:, :, 1] * y) + mj[:, :, 2] * z) + mj[:, :, 3])  # [3 n, i]
+        w = rec["weight"]
+        xyz = ((w[:, 0:1] * q[0] + w[:, 1:2] * q[1]) + w[:, 2:3] * q[2]) + w[:, 3:4] * q[3]
+    assert xyz.dtype == np.float32
+    out.reshape(-1, 4, 4)[:, :3, :3] = xyz.reshape(-1, 3, 3)
+    return out
+
+
 def load_obj_positions(path) -> np.ndarray:
     """Minimal Wavefront OBJ reader: `v` records and `f` records (v, v/vt, v/vt/vn, v//vn, negative
     indices); polygons are fan-triangulated (tinyobjloader's default `triangulate=true`, which is

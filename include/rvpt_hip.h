@@ -71,7 +71,10 @@ extern "C" {
                                      triangle — until then the "NULL scene array" error — is the BIND: four bone indices and four weights per vertex, kept
                                      on the device.  Still 8, no new symbol: the count RVPT_HIP_NODES_UPDATE_SKIN with `nodes` pointing at a list of rvpt_bone
                                      matrices — until then the "NULL scene array" error — is the SKIN UPDATE: every vertex posed from the rest pose by its
-                                     four weighted matrices (linear blend skinning), every box refitted */
+                                     four weighted matrices (linear blend skinning), every box refitted.  Still 8, no
+                                     new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_NEAREST_POINTS (4) — until then the "unknown format" error — is a
+                                     POINT QUERY: `dst` holds rvpt_point_hit records, a point and a squared bound in, the nearest point of the mesh, its squared
+                                     distance and its triangle out */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -178,6 +181,15 @@ typedef struct rvpt_ray_path {
     float dir[3]; uint32_t max_bounces;   /* in: the first segment's direction (need not be unit); the bounce budget, 1 .. RVPT_HIP_PATH_MAX_BOUNCES */
     float radiance[3]; uint32_t segments; /* out */
 } rvpt_ray_path;
+
+#define RVPT_HIP_FORMAT_NEAREST_POINTS 4 /* dst: rvpt_point_hit[dst_bytes / 48], in and out (NEAREST POINTS at rvpt_hip_read) */
+
+/* One point of a query and its answer (48 B = three float4; no reference counterpart: the reference asks its scene nothing but its camera's paths). */
+typedef struct rvpt_point_hit {
+    float point[3];   float max_d2;                        /* in: the query point; the search bound as a SQUARED distance, +inf = unbounded */
+    float closest[3]; float d2;                            /* out: the nearest point of the mesh and its squared distance */
+    uint32_t prim;    float u; float v; uint32_t region;   /* out: the triangle, the pair the region computed, 0 face, 1/2/3 vertex a/b/c, 4/5/6 edge ab/ac/bc */
+} rvpt_point_hit;
 
 /* Image tiles are RVPT_HIP_TILE x RVPT_HIP_TILE pixels — the footprint of one reference
  * work-group (compute_pass.comp:27).  The tile at (tx, ty) of the tiles_x-wide tile grid has slot
@@ -598,7 +610,52 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  * - It implies rvpt_hip_wait and leaves untouched the accumulator, rvpt_hip_get_timing, rvpt_hip_get_stats, rvpt_hip_get_launch_info, rvpt_hip_get_cull_info,
  *   the frame counter, and rvpt_hip_last_error on success: a frame dispatched after a path query is bit for bit the frame dispatched without it.
  * - ONLY KAJIYA IS BUILT.  The other ten integrators of compute_pass.comp (render modes 0-8 and Hart) are not part of this form.
- * DESIGN.md 5.14 has the kernels and what was measured (profiles/path_queries.txt). */
+ * DESIGN.md 5.14 has the kernels and what was measured (profiles/path_queries.txt).
+ *
+ * NEAREST POINTS — the nearest point of the mesh to the caller's own points, in place:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_NEAREST_POINTS, records, n * sizeof(rvpt_point_hit));
+ *
+ * `dst` then holds n rvpt_point_hit records: each comes in as a point and a bound (point, max_d2) and goes out as the nearest point of the mesh (closest, d2,
+ * prim, u, v, region).  The in fields are never written.  max_d2 and d2 are SQUARED distances: there is no square root in this form.
+ * - THE ANSWER IS DEFINED WITHOUT REFERENCE TO ANY WALK.  Every stored triangle i gets a candidate (d2_i, prim_i) by the arithmetic below; the answer is the
+ *   lexicographically smallest candidate that is smaller than (max_d2, 0xFFFFFFFF).  A candidate whose d2 is NaN never wins (< and == are both false for it).
+ *   So d2 == max_d2 is accepted, max_d2 == 0 finds a point on the surface, and among equal d2 the smaller reported prim wins.  (On a BVH context the stored
+ *   triangles are those under the leaves of the tree, as for a ray.)
+ * - THE NUMBERING OF prim is a ray query's: the stored order after an ordinary upload, the CALLER'S order after a build form (through the stored
+ *   permutation).  The tie is broken on that reported number, so the answer does not depend on which builder made the tree.
+ * - PER-TRIANGLE ARITHMETIC.  binary32 throughout; every product, sum and quotient is rounded on its own, no FMA.  a, b, c = vert0..2 of the stored row, p = point.
+ *     ab = b-a, ac = c-a, ap = p-a, bp = p-b, cp = p-c;   dot(x,y) = (x0*y0 + x1*y1) + x2*y2;
+ *     d1 = dot(ab,ap), d2' = dot(ac,ap), d3 = dot(ab,bp), d4 = dot(ac,bp), d5 = dot(ab,cp), d6 = dot(ac,cp);
+ *     vc = d1*d4 - d3*d2', vb = d5*d2' - d1*d6, va = d3*d6 - d5*d4.
+ *   The regions (the Voronoi regions of Ericson's point-triangle test) are tested in this order, and the first that holds decides (u, v, region):
+ *     d1<=0 && d2'<=0               -> (0, 0, 1)
+ *     d3>=0 && d4<=d3               -> (1, 0, 2)
+ *     vc<=0 && d1>=0 && d3<=0       -> (d1/(d1-d3), 0, 4)
+ *     d6>=0 && d5<=d6               -> (0, 1, 3)
+ *     vb<=0 && d2'>=0 && d6<=0      -> (0, d2'/(d2'-d6), 5)
+ *     va<=0 && e1>=0 && e2>=0       -> (1-w, w, 6)   with e1 = d4-d3, e2 = d5-d6, w = e1/(e1+e2)
+ *     otherwise the face            -> (vb/s, vc/s, 0) with s = (va+vb)+vc
+ *   A quotient whose divisor is 0 is taken as 0; every other quotient is the correctly rounded IEEE one.  Then q = (a + ab*u) + ac*v per component, and q is
+ *   CLAMPED INTO THE TRIANGLE'S OWN BOX per axis by comparisons that leave a NaN a NaN: q < lo ? lo : (q > hi ? hi : q), lo / hi the exact min / max of a, b, c.
+ *   closest = q, and d2 = (dx*dx + dy*dy) + dz*dz with d = p - q.  u and v are the values the region computed, before the clamp.
+ * - The clamp makes pruning exact: with g = max(max(lo-p, p-hi), 0) per axis of a node's box and box_d2 = (gx*gx + gy*gy) + gz*gz, box_d2 <= d2_i holds in
+ *   floats for every triangle under the node, so a walk that skips a node iff box_d2 > best returns the definition's answer bit for bit — over any tree whose
+ *   boxes contain their vertices, the caller's loose boxes included (DESIGN.md 5.19 has the proof).
+ * - A ZERO-AREA TRIANGLE gets what this arithmetic gives: a point of its box, not necessarily its nearest (with a == b the edge-ab region answers a).  The
+ *   error is bounded by the triangle's own extent.
+ * - INVALID RECORDS AND MISSES.  A record is invalid if a component of point is non-finite, or if max_d2 is NaN or < 0 (-0.0 is 0); that is decided before any
+ *   walk.  Invalid records and misses go out as closest = 0, 0, 0, d2 = the bits of max_d2 as given, prim = 0xFFFFFFFF, u = v = 0, region = 0.
+ * - The call needs a scene — before any full upload it is RVPT_HIP_ERR_INVALID; the empty scene answers every record with a miss — and no rvpt_hip_set_frame.
+ *   dst_bytes must be a multiple of 48, else RVPT_HIP_ERR_INVALID; dst_bytes == 0 is a successful no-op; fewer than 2^32 records per call.
+ * - `dst` is host memory or device memory of the context's GPU, classified as for frames.  Device memory must be 16-byte aligned, else RVPT_HIP_ERR_INVALID;
+ *   another GPU's memory is RVPT_HIP_ERR_INVALID naming both devices.  In every error case `dst` is untouched.  Host records go through the ray queries' staging
+ *   buffer, and only the out fields — the last 32 bytes of a record — travel back; device records never visit the host.
+ * - The call is LOCAL: with a communicator it is not collective and touches no peer.
+ * - It implies rvpt_hip_wait and leaves untouched the accumulator, rvpt_hip_get_timing, rvpt_hip_get_stats, rvpt_hip_get_launch_info, rvpt_hip_get_cull_info,
+ *   the frame counter, and rvpt_hip_last_error on success: a frame dispatched after a point query is bit for bit the frame dispatched without it.
+ * - The answer is on the scene as the last update form left it: plain, guarded, sparse, pose or skin.
+ * DESIGN.md 5.19 has the kernels and what was measured (profiles/nearest_points.txt). */
 int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes);
 
 /* ---- multi-GPU: one RCCL communicator over the tile_world ranks of a partitioned image (no reference counterpart: the

@@ -31,6 +31,7 @@
 #include "rvpt_frames.h"
 #include "rvpt_build.h"
 #include "rvpt_query.h"
+#include "rvpt_nearest.h"
 #include "rvpt_paths.h"
 #include "rvpt_packets.h"
 #include "rvpt_math.h"
@@ -73,6 +74,10 @@ static_assert(sizeof(rvpt_part_move) == 64 && offsetof(rvpt_part_move, first) ==
 static_assert(sizeof(rvpt_vertex_skin) == 32 && offsetof(rvpt_vertex_skin, weight) == 16 && sizeof(rvpt_bone) == 48 && RVPT_HIP_SKIN_MAX_BONES * sizeof(rvpt_bone) <= 48u * 1024u,
               "rvpt_vertex_skin, rvpt_bone: the two quads and the three quads rv::skin_vertices reads; every matrix fits its 48 KiB of LDS");
 static_assert(sizeof(rvpt_ray_path) == sizeof(rvpt_ray_hit) &&offsetof(rvpt_ray_path, radiance) == offsetof(rvpt_ray_hit, t), "ray and path queries share query_records");
+static_assert(sizeof(rvpt_point_hit) == rv::kNearestRecordBytes && sizeof(rvpt_point_hit) == sizeof(rvpt_ray_hit) && offsetof(rvpt_point_hit, max_d2) == 12 &&
+                  offsetof(rvpt_point_hit, closest) == 16 && offsetof(rvpt_point_hit, d2) == 28 && offsetof(rvpt_point_hit, prim) == 32 && offsetof(rvpt_point_hit, u) == 36 &&
+                  offsetof(rvpt_point_hit, v) == 40 && offsetof(rvpt_point_hit, region) == 44,
+              "a point query's record: three float4 (rvpt_nearest.hip), and it shares query_records");
 static_assert(offsetof(rvpt_triangle, mat_id) == 48 && offsetof(rvpt_bvh_node, bounds) == 8 &&
                   offsetof(rvpt_material, data) == 32 && offsetof(rvpt_render_settings, split_ratio) == 32 &&
                   offsetof(rvpt_camera_data, params) == 64,
@@ -182,7 +187,7 @@ struct rvpt_hip_ctx {
     size_t cap_bones = 0;
     uint32_t skin_bones = 0;
     bool have_scene = false;
-    // RAY QUERIES and PATH QUERIES (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS / RVPT_HIP_FORMAT_RAY_PATHS; rvpt_query.h, rvpt_paths.h): the staging buffer of host records (bytes) and the launch's scratch — 64 words whose
+    // RAY, PATH and POINT QUERIES (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS / RVPT_HIP_FORMAT_RAY_PATHS / RVPT_HIP_FORMAT_NEAREST_POINTS; rvpt_query.h, rvpt_paths.h, rvpt_nearest.h): the staging buffer of host records (bytes) and the launch's scratch — 64 words whose
     // first is the claim counter, then the global part of the traversal stack (words).  Both only grow.
     unsigned char *d_query_stage = nullptr;
     size_t cap_query_stage = 0;
@@ -2850,13 +2855,17 @@ int rvpt_hip_gather(rvpt_hip_ctx *ctx, void *dst_dev_rgba32f)
     return gather_to_root(ctx, static_cast<float4 *>(dst_dev_rgba32f));
 }
 
-// rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS (include/rvpt_hip.h: RAY QUERIES) or, `paths`, with RVPT_HIP_FORMAT_RAY_PATHS (PATH QUERIES): `dst` holds
-// dst_bytes / 48 records, rays in and hits — radiance — out.  The two forms share everything but the kernels: the checks, the pointer's classification, the
-// staging of host records (only a record's third float4, the out fields, travels back).  LOCAL: no communicator is touched.  Everything is checked before
+// rvpt_hip_read with a format of records, by `kind`: RVPT_HIP_FORMAT_RAY_HITS (include/rvpt_hip.h: RAY QUERIES), RVPT_HIP_FORMAT_RAY_PATHS (PATH QUERIES) or
+// RVPT_HIP_FORMAT_NEAREST_POINTS (NEAREST POINTS).  `dst` holds dst_bytes / 48 records: rays in and hits — radiance — out, or points in and nearest points out.
+// The forms share everything but the kernels and the first out byte: the checks, the pointer's classification, the staging of host records (only a record's
+// out fields travel back: its third float4, for a point query its second and third).  LOCAL: no communicator is touched.  Everything is checked before
 // anything is written; on success ctx->err stays as it was.  No event is recorded: RVPT_HIP_TIMING does not see a query.
-static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const bool paths)
+enum class RecordKind { Rays, Paths, Points };
+static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const RecordKind kind)
 {
-    const char *what = paths ? "path" : "ray", *record = paths ? "rvpt_ray_path" : "rvpt_ray_hit";
+    const bool paths = kind == RecordKind::Paths, points = kind == RecordKind::Points;
+    const char *what = points ? "point" : (paths ? "path" : "ray"), *record = points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : "rvpt_ray_hit");
+    const size_t out_offset = points ? offsetof(rvpt_point_hit, closest) : offsetof(rvpt_ray_hit, t);  // where a record's out fields begin
     if (dst_bytes % sizeof(rvpt_ray_hit))
         return fail(ctx, RVPT_HIP_ERR_INVALID, "%s query: dst_bytes %zu is not a multiple of the %zu bytes of a %s", what, dst_bytes, sizeof(rvpt_ray_hit), record);
     if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "%s query before any full upload_scene on this context: there is no scene to ask", what);
@@ -2879,8 +2888,14 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const b
     scene.n_tris = static_cast<uint32_t>(ctx->n_tris), scene.n_wide = static_cast<uint32_t>(ctx->n_wide), scene.head_shift = ctx->bvh_head_shift;
     scene.stack_levels = scene.kind == rv::QueryKind::Wide ? ctx->wide_stack_levels : bvh_stack_levels(ctx);
     path_scene.mat_index = ctx->d_mat_index, path_scene.unit_n = ctx->d_unit_n, path_scene.mats = ctx->d_mats;
+    rv::NearestScene nearest{};  // a point query reads the vertex rows and the binary nodes, whichever form the ray walks of this context take
+    nearest.brute = !bvh;
+    nearest.tris = ctx->d_tris, nearest.nodes = ctx->d_nodes, nearest.perm = scene.perm;
+    nearest.n_tris = scene.n_tris, nearest.n_nodes = static_cast<uint32_t>(ctx->n_nodes), nearest.stack_levels = bvh_stack_levels(ctx);
     rv::QueryPlan plan{};
-    if (paths)
+    if (points)
+        HIP_TRY(ctx, rv::nearest_plan(nearest, static_cast<uint32_t>(n), ctx->num_cus, &plan));
+    else if (paths)
         HIP_TRY(ctx, rv::path_plan(path_scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
     else
         HIP_TRY(ctx, rv::query_plan(scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
@@ -2892,13 +2907,15 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const b
         records = ctx->d_query_stage;
         HIP_TRY(ctx, hipMemcpyAsync(records, dst, dst_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    if (paths)
+    if (points)
+        HIP_TRY(ctx, rv::nearest_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
+    else if (paths)
         HIP_TRY(ctx, rv::path_launch(ctx->stream, path_scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
     else
         HIP_TRY(ctx, rv::query_launch(ctx->stream, scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
     if (!device_dst)  // only the out fields travel back: the in fields of a host record are never written either
-        HIP_TRY(ctx, hipMemcpy2DAsync(static_cast<unsigned char *>(dst) + offsetof(rvpt_ray_hit, t), sizeof(rvpt_ray_hit), ctx->d_query_stage + offsetof(rvpt_ray_hit, t),
-                                      sizeof(rvpt_ray_hit), sizeof(rvpt_ray_hit) - offsetof(rvpt_ray_hit, t), n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpy2DAsync(static_cast<unsigned char *>(dst) + out_offset, sizeof(rvpt_ray_hit), ctx->d_query_stage + out_offset, sizeof(rvpt_ray_hit),
+                                      sizeof(rvpt_ray_hit) - out_offset, n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // device records: the caller may read them from any stream of its own on return
     return RVPT_HIP_OK;
 }
@@ -2906,8 +2923,9 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const b
 int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
 {
     if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
-    if (format == RVPT_HIP_FORMAT_RAY_HITS || format == RVPT_HIP_FORMAT_RAY_PATHS)  // local even with a communicator: every rank holds the whole scene
-        return query_records(ctx, dst, dst_bytes, format == RVPT_HIP_FORMAT_RAY_PATHS);
+    if (format == RVPT_HIP_FORMAT_RAY_HITS || format == RVPT_HIP_FORMAT_RAY_PATHS || format == RVPT_HIP_FORMAT_NEAREST_POINTS)  // local even with a communicator: every rank holds the whole scene
+        return query_records(ctx, dst, dst_bytes,
+                             format == RVPT_HIP_FORMAT_NEAREST_POINTS ? RecordKind::Points : (format == RVPT_HIP_FORMAT_RAY_PATHS ? RecordKind::Paths : RecordKind::Rays));
     const bool collective = ctx->comm != nullptr;  // partitioned image with a communicator: gather to rank 0, which gets the frame
     if (collective && ctx->tile_rank != 0 && ctx->local_group.empty()) return gather_to_root(ctx, nullptr);  // peers only send
     const size_t px = static_cast<size_t>(ctx->width) * ctx->height;

@@ -1,0 +1,310 @@
+// rvpt_nearest.hip — point queries (include/rvpt_hip.h: RVPT_HIP_FORMAT_NEAREST_POINTS): a record comes in as a point and a squared bound and goes out as the
+// nearest point of the mesh, its squared distance, the triangle, the barycentric pair and the Voronoi region that decided.
+//
+// THE ANSWER IS DEFINED WITHOUT A WALK (NEAREST POINTS at rvpt_hip_read; rvpt_amd/scene.py: closest_point_triangles / closest_points state it in numpy): every
+// stored triangle i gets a candidate (d2_i, prim_i) from closest_point() below, and the answer is the lexicographically smallest candidate below
+// (max_d2, 0xFFFFFFFF).  The arithmetic is binary32 with every product, sum and quotient rounded on its own: this translation unit is compiled with
+// -ffp-contract=off and without fast-math like every other, there is no fma_() in this file, and the divisions are plain `/`, which hipcc expands to the
+// correctly rounded IEEE quotient (v_div_scale / v_rcp / v_fma / v_div_fmas / v_div_fixup) — numpy's float32 divide is the yardstick, NOT div_dots (rvpt_math.h),
+// whose refined reciprocal leaves the IEEE result outside the normal range.
+//
+// WHY ANY WALK GIVES THAT ANSWER.  closest_point() clamps its point q into the triangle's own box, so q lies in the box of every node above the triangle; with
+// g = max(max(lo - p, p - hi), 0) per axis of a node's box, rounding is monotone, hence |p - q| >= g per axis IN FLOATS and box_d2 <= d2_i for every triangle
+// under the node.  A walk that skips a node iff box_d2 > best (strict) never skips a candidate that could win or tie: the visiting order is free.
+//
+// One point per lane.  nearest_bvh2 walks the BINARY nodes — the form every update keeps current — on the ray queries' persistent grid: waves claim runs of 64
+// records, the first stack levels per lane live in LDS and the rest in one global column per thread of the grid (rvpt_query.hip).  The nearer child by box_d2
+// goes first, the farther is stacked with its box_d2 and popped only while box_d2 <= best still holds.  nearest_brute streams the vertex rows through LDS in tiles.
+// A record is three float4; the second and third (the out fields) are stored.  An index read from the tree never becomes an address unchecked.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "rvpt_device.h"
+#include "rvpt_nearest.h"
+
+namespace rv {
+
+namespace {
+
+constexpr uint32_t kNoPrim = 0xFFFFFFFFu;
+
+struct NearestArgs {
+    const float4 *tris, *nodes;
+    const uint32_t *perm;
+    float4 *records;
+    uint32_t n, n_runs;          // records, runs of 64 records
+    uint32_t *counter;           // the next run to claim (0 at launch)
+    uint32_t *stack_overflow;    // [stack_levels - lds_levels][2][threads of the grid]
+    uint32_t n_tris, n_nodes, stack_levels, lds_levels;
+};
+
+struct NearestPoint {
+    f3 p;
+    uint32_t max_bits;
+    bool valid;
+};
+
+struct Closest {
+    f3 q;
+    float d2, u, v;
+    uint32_t region;
+};
+
+__device__ __forceinline__ bool finite_(const float x) { return __builtin_fabsf(x) < kInf; }  // false for NaN and +-inf
+
+// (x0*y0 + x1*y1) + x2*y2, three products and two sums, each rounded (rv::dot of rvpt_math.h is the FUSED one: not used here)
+__device__ __forceinline__ float dot_rounded(const f3 a, const f3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+// the IEEE quotient; a quotient whose divisor is 0 is taken as 0
+__device__ __forceinline__ float quotient(const float num, const float den) { return den == 0.0f ? 0.0f : num / den; }
+__device__ __forceinline__ float clamp_keep_nan(const float q, const float lo, const float hi) { return q < lo ? lo : (q > hi ? hi : q); }
+
+// The candidate of one triangle (a, b, c) for the point p: Ericson's point-triangle test, its regions tested in the specified order — written as selects over
+// the seven predicates, which picks the first that holds exactly as the chain of ifs does — then q = (a + ab*u) + ac*v clamped into the triangle's own box.
+// Two quotients at most (the face's u and v); every other region has one or none, and their operands are selected before the divide.
+__device__ __forceinline__ Closest closest_point(const f3 a, const f3 b, const f3 c, const f3 p)
+{
+    const f3 ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c;
+    const float d1 = dot_rounded(ab, ap), d2 = dot_rounded(ac, ap), d3 = dot_rounded(ab, bp), d4 = dot_rounded(ac, bp), d5 = dot_rounded(ab, cp), d6 = dot_rounded(ac, cp);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float e1 = d4 - d3, e2 = d5 - d6;
+    const bool r1 = d1 <= 0.0f && d2 <= 0.0f;
+    const bool r2 = d3 >= 0.0f && d4 <= d3;
+    const bool r4 = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
+    const bool r3 = d6 >= 0.0f && d5 <= d6;
+    const bool r5 = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
+    const bool r6 = va <= 0.0f && e1 >= 0.0f && e2 >= 0.0f;
+    const uint32_t region = r1 ? 1u : (r2 ? 2u : (r4 ? 4u : (r3 ? 3u : (r5 ? 5u : (r6 ? 6u : 0u)))));
+    const float s = (va + vb) + vc;
+    const float num_a = region == 4u ? d1 : (region == 5u ? d2 : (region == 6u ? e1 : vb));
+    const float den_a = region == 4u ? d1 - d3 : (region == 5u ? d2 - d6 : (region == 6u ? e1 + e2 : s));
+    const bool one = region >= 4u || region == 0u;  // the regions with a quotient
+    const float qa = quotient(one ? num_a : 0.0f, one ? den_a : 1.0f);
+    const float qb = quotient(region == 0u ? vc : 0.0f, region == 0u ? s : 1.0f);
+    Closest r;
+    r.region = region;
+    r.u = region == 2u ? 1.0f : (region == 4u ? qa : (region == 6u ? 1.0f - qa : (region == 0u ? qa : 0.0f)));
+    r.v = region == 3u ? 1.0f : (region == 5u ? qa : (region == 6u ? qa : (region == 0u ? qb : 0.0f)));
+    const f3 raw = (a + ab * r.u) + ac * r.v;
+    const f3 lo = mk(__builtin_fminf(__builtin_fminf(a.x, b.x), c.x), __builtin_fminf(__builtin_fminf(a.y, b.y), c.y), __builtin_fminf(__builtin_fminf(a.z, b.z), c.z));
+    const f3 hi = mk(__builtin_fmaxf(__builtin_fmaxf(a.x, b.x), c.x), __builtin_fmaxf(__builtin_fmaxf(a.y, b.y), c.y), __builtin_fmaxf(__builtin_fmaxf(a.z, b.z), c.z));
+    r.q = mk(clamp_keep_nan(raw.x, lo.x, hi.x), clamp_keep_nan(raw.y, lo.y, hi.y), clamp_keep_nan(raw.z, lo.z, hi.z));
+    const f3 d = p - r.q;
+    r.d2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+    return r;
+}
+
+__device__ __forceinline__ Closest closest_point_row(const float4 *row, const f3 p)
+{
+    const float4 a = row[0], b = row[1], c = row[2];
+    return closest_point(mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), mk(c.x, c.y, c.z), p);
+}
+
+// box_d2 of a binary node's box (bounds = {minx,maxx,miny,maxy,minz,maxz}: n0.zw = x, n1.xy = y, n1.zw = z) in the expression shape of d2
+__device__ __forceinline__ float box_d2(const f3 p, const float4 n0, const float4 n1)
+{
+    const float gx = __builtin_fmaxf(__builtin_fmaxf(n0.z - p.x, p.x - n0.w), 0.0f);
+    const float gy = __builtin_fmaxf(__builtin_fmaxf(n1.x - p.y, p.y - n1.y), 0.0f);
+    const float gz = __builtin_fmaxf(__builtin_fmaxf(n1.z - p.z, p.z - n1.w), 0.0f);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+__device__ __forceinline__ uint32_t reported(const uint32_t *perm, const uint32_t i) { return i == kNoPrim ? kNoPrim : (perm ? perm[i] : i); }
+
+// (d2, prim of stored triangle i) against (best, prim of best_i), lexicographically; a NaN d2 passes neither comparison.  The perm words are loaded only on a tie.
+__device__ __forceinline__ void accept(const uint32_t *perm, const float d2, const uint32_t i, float &best, uint32_t &best_i)
+{
+    if (d2 < best) {
+        best = d2;
+        best_i = i;
+    } else if (d2 == best) {
+        if (reported(perm, i) < reported(perm, best_i)) best_i = i;
+    }
+}
+
+// A record's in fields.  A point with a non-finite component is a miss before any walk; so is a max_d2 that is NaN or below zero (-0.0 is zero).
+__device__ __forceinline__ NearestPoint load_point(const float4 *records, const size_t r, const bool live)
+{
+    NearestPoint q;
+    const float4 a = live ? records[3 * r + 0] : make_float4(0.f, 0.f, 0.f, 0.f);
+    q.p = mk(a.x, a.y, a.z);
+    q.max_bits = __float_as_uint(a.w);
+    q.valid = live && finite_(a.x) && finite_(a.y) && finite_(a.z) && a.w >= 0.0f;
+    return q;
+}
+
+// A record's out fields.  The winner's candidate is recomputed from its row (the same operations on the same operands: d2 has the bits the walk compared),
+// which is cheaper than carrying eight more registers through the walk.
+__device__ __forceinline__ void store_point(float4 *records, const size_t r, const NearestPoint &q, const float4 *tris, const uint32_t *perm, const uint32_t best_i)
+{
+    float4 out1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(q.max_bits));
+    float4 out2 = make_float4(__uint_as_float(kNoPrim), 0.0f, 0.0f, __uint_as_float(0u));
+    if (best_i != kNoPrim) {
+        const Closest c = closest_point_row(tris + 4 * static_cast<size_t>(best_i), q.p);
+        out1 = make_float4(c.q.x, c.q.y, c.q.z, c.d2);
+        out2 = make_float4(__uint_as_float(reported(perm, best_i)), c.u, c.v, __uint_as_float(c.region));
+    }
+    records[3 * r + 1] = out1;
+    records[3 * r + 2] = out2;
+}
+
+// the next run of 64 records for this wave (wave-uniform)
+__device__ __forceinline__ uint32_t claim_run(uint32_t *counter, const uint32_t lane)
+{
+    uint32_t run = 0;
+    if (lane == 0) run = atomicAdd(counter, 1u);
+    return __builtin_amdgcn_readlane(run, 0);
+}
+
+}  // namespace
+
+// LDS: [stack: lds_levels x 2 words x kBlock] — a slot is (box_d2 bits, node index), query_bvh4's two-word layout; the global part likewise.
+__global__ __launch_bounds__(kBlock) void nearest_bvh2(const NearestArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const uint32_t lds_levels = a.lds_levels;
+    const uint32_t top_level = a.stack_levels - 1u;
+    const uint32_t n_nodes = a.n_nodes, n_tris = a.n_tris;
+    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
+    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
+    const uint32_t lane = lane_id();
+
+    for (;;) {
+        const uint32_t run = claim_run(a.counter, lane);
+        if (run >= a.n_runs) break;
+        const size_t r = static_cast<size_t>(run) * 64u + lane;
+        const bool live = r < a.n;
+        const NearestPoint q = load_point(a.records, r, live);
+        float best = __uint_as_float(q.max_bits);
+        uint32_t best_i = kNoPrim, sp = 0, cur = 0;
+        bool walking = q.valid && n_nodes > 0u;
+        if (walking) walking = box_d2(q.p, a.nodes[0], a.nodes[1]) <= best;  // the root is a node like any other
+        while (ballot(walking) != 0) {
+            if (walking) {  // cur < n_nodes, and its box passed box_d2 <= best when it was chosen
+                const float4 n0 = a.nodes[2u * static_cast<size_t>(cur)];
+                const uint32_t first = __float_as_uint(n0.x), count = __float_as_uint(n0.y);
+                bool pop = true;
+                if (count > 0) {
+                    const uint32_t end = static_cast<uint32_t>(min(static_cast<uint64_t>(first) + count, static_cast<uint64_t>(n_tris)));  // (first >= n_tris: no triangle)
+                    for (uint32_t i = first; i < end; ++i) accept(a.perm, closest_point_row(a.tris + 4 * static_cast<size_t>(i), q.p).d2, i, best, best_i);
+                } else if (first < n_nodes && first + 1u < n_nodes) {  // both children inside the node buffer (first + 1 may wrap: then first fails)
+                    const float4 *kids = a.nodes + 2u * static_cast<size_t>(first);
+                    const float dl = box_d2(q.p, kids[0], kids[1]), dr = box_d2(q.p, kids[2], kids[3]);
+                    const bool vl = dl <= best, vr = dr <= best;
+                    const bool left_first = dl <= dr || !vr;
+                    if (vl && vr) {
+                        const uint32_t at = min(sp, top_level);  // (the tree's height bounds the pushes of a root-to-leaf path; the clamp keeps a wrong size inside the memory)
+                        const float far_d = left_first ? dr : dl;
+                        const uint32_t far_node = left_first ? first + 1u : first;
+                        if (at < lds_levels) {
+                            lds_stack[(2u * at + 0u) * kBlock + threadIdx.x] = __float_as_uint(far_d);
+                            lds_stack[(2u * at + 1u) * kBlock + threadIdx.x] = far_node;
+                        } else {
+                            ovf[(2u * (at - lds_levels) + 0u) * ovf_stride] = __float_as_uint(far_d);
+                            ovf[(2u * (at - lds_levels) + 1u) * ovf_stride] = far_node;
+                        }
+                        sp = at + 1u;
+                    }
+                    if (vl || vr) {
+                        cur = (vl && left_first) ? first : first + 1u;
+                        pop = false;
+                    }
+                }
+                if (pop) {
+                    bool found = false;
+                    while (sp > 0 && !found) {
+                        sp -= 1;
+                        uint32_t d_bits, node;
+                        if (sp < lds_levels) {
+                            d_bits = lds_stack[(2u * sp + 0u) * kBlock + threadIdx.x];
+                            node = lds_stack[(2u * sp + 1u) * kBlock + threadIdx.x];
+                        } else {
+                            d_bits = ovf[(2u * (sp - lds_levels) + 0u) * ovf_stride];
+                            node = ovf[(2u * (sp - lds_levels) + 1u) * ovf_stride];
+                        }
+                        if (__uint_as_float(d_bits) <= best && node < n_nodes) {  // best may have shrunk since the push
+                            cur = node;
+                            found = true;
+                        }
+                    }
+                    walking = found;
+                }
+            }
+        }
+        if (live) store_point(a.records, r, q, a.tris, a.perm, best_i);
+    }
+}
+
+// Brute force: a work-group answers 256 records and streams the vertex quads of the triangle rows through LDS in tiles of kNearestTileTris; every lane runs over
+// each tile in index order.  (A brute-force context has no permutation, but nothing here relies on that.)
+__global__ __launch_bounds__(kBlock) void nearest_brute(const NearestArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float4 lds_rows[];
+    const size_t r = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const bool live = r < a.n;
+    const NearestPoint q = load_point(a.records, r, live);
+    float best = __uint_as_float(q.max_bits);
+    uint32_t best_i = kNoPrim;
+    if (__syncthreads_or(q.valid ? 1 : 0) != 0) {
+        for (uint32_t base = 0; base < a.n_tris; base += kNearestTileTris) {
+            const uint32_t count = min(kNearestTileTris, a.n_tris - base);
+            for (uint32_t i = threadIdx.x; i < 3u * count; i += kBlock) lds_rows[i] = a.tris[4u * (static_cast<size_t>(base) + i / 3u) + i % 3u];
+            __syncthreads();
+            if (q.valid)
+                for (uint32_t i = 0; i < count; ++i) accept(a.perm, closest_point_row(lds_rows + 3u * i, q.p).d2, base + i, best, best_i);
+            __syncthreads();  // the barrier in front of the next tile's stores
+        }
+    }
+    if (live) store_point(a.records, r, q, a.tris, a.perm, best_i);
+}
+
+hipError_t nearest_plan(const NearestScene &scene, const uint32_t n, const int num_cus, QueryPlan *plan)
+{
+    QueryPlan p{};
+    if (scene.brute) {
+        p.grid = std::max<uint32_t>(1u, static_cast<uint32_t>((static_cast<uint64_t>(n) + kBlock - 1u) / kBlock));
+        p.lds_bytes = static_cast<size_t>(kNearestTileTris) * 48u;
+        *plan = p;
+        return hipSuccess;
+    }
+    const uint32_t levels = std::max<uint32_t>(1u, scene.stack_levels);
+    p.lds_levels = std::min(levels, kQueryLdsLevels);
+    p.lds_bytes = static_cast<size_t>(p.lds_levels) * kBlock * 2u * sizeof(uint32_t);
+    int per_cu = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(nearest_bvh2), kBlock, p.lds_bytes);
+    if (e != hipSuccess) return e;
+    const uint64_t runs = (static_cast<uint64_t>(n) + 63u) / 64u;
+    const uint64_t want = (runs + kBlock / 64u - 1u) / (kBlock / 64u);  // a work-group's four waves claim a run each
+    p.grid = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>(want, static_cast<uint64_t>(std::max(per_cu, 1)) * static_cast<uint64_t>(std::max(num_cus, 1)))));
+    const size_t column_words = static_cast<size_t>(2u) * (levels - p.lds_levels) * kBlock;  // per work-group
+    while (p.grid > 1u && column_words * p.grid * sizeof(uint32_t) > kQueryStackMaxBytes) p.grid = (p.grid + 1u) / 2u;
+    p.stack_words = column_words * p.grid;
+    *plan = p;
+    return hipSuccess;
+}
+
+hipError_t nearest_launch(hipStream_t stream, const NearestScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, const uint32_t n)
+{
+    if (n == 0) return hipSuccess;
+    NearestArgs a{};
+    a.tris = scene.tris, a.nodes = scene.nodes, a.perm = scene.perm;
+    a.records = static_cast<float4 *>(records);
+    a.n = n;
+    a.n_runs = static_cast<uint32_t>((static_cast<uint64_t>(n) + 63u) / 64u);
+    a.counter = scratch;
+    a.stack_overflow = scratch + 64;
+    a.n_tris = scene.n_tris, a.n_nodes = scene.n_nodes;
+    a.stack_levels = std::max<uint32_t>(1u, scene.stack_levels);
+    a.lds_levels = plan.lds_levels;
+    if (scene.brute) {
+        hipLaunchKernelGGL(nearest_brute, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
+        return hipGetLastError();
+    }
+    const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(nearest_bvh2, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace rv

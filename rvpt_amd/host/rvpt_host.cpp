@@ -623,6 +623,26 @@ bool RVPT::trace_paths_device(void *records, size_t n)
     }
     return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_PATHS, records, n * sizeof(rvpt_ray_path)), "rvpt_hip_read");
 }
+bool RVPT::closest_points(rvpt_point_hit *records, size_t n)
+{
+    if (!ctx_) {
+        error_ = "closest_points before initialize()";
+        return false;
+    }
+    if (!check(backend_.read(ctx_, RVPT_HIP_FORMAT_NEAREST_POINTS, records, n * sizeof(rvpt_point_hit)), "rvpt_hip_read")) return false;
+    if (!device_built_)  // the library numbered the leaf order it was given
+        for (size_t k = 0; k < n; ++k)
+            if (records[k].prim < order_.size()) records[k].prim = order_[records[k].prim];
+    return true;
+}
+bool RVPT::closest_points_device(void *records, size_t n)
+{
+    if (!ctx_) {
+        error_ = "closest_points_device before initialize()";
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_NEAREST_POINTS, records, n * sizeof(rvpt_point_hit)), "rvpt_hip_read");
+}
 
 // ---- main.cpp:12-62 ---------------------------------------------------------------------------------------
 long load_model(RVPT &rvpt, const std::string &path, int material_id, std::string *error)

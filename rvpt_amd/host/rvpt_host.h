@@ -206,6 +206,13 @@ public:
     bool trace_paths(std::vector<rvpt_ray_path> &records);
     // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host
     bool trace_paths_device(void *records, size_t n);
+    // Point queries (rvpt_hip_read with RVPT_HIP_FORMAT_NEAREST_POINTS; include/rvpt_hip.h: NEAREST POINTS): every record comes in as a point and a SQUARED
+    // search bound (point, max_d2) and goes out as the nearest point of the mesh (closest, d2, prim, u, v, region), in place.  After initialize(); no update()
+    // is needed.  prim numbers the triangles in the order they were ADDED, as trace_rays does (after a host build a tie between equal distances is broken on the
+    // library's stored number, before this renumbering).
+    bool closest_points(rvpt_point_hit *records, size_t n);
+    // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host: prim then stays as the LIBRARY numbers it
+    bool closest_points_device(void *records, size_t n);
     const std::string &last_error() const { return error_; }
     // the backend context, e.g. to join several RVPT objects (one per GPU, tile_rank i of n) into one RCCL group with
     // rvpt_hip_comm_init_all; read_frame() on rank 0's object is then the gather of the whole image

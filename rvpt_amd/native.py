@@ -34,6 +34,9 @@ FORMAT_RAY_PATHS = 3  # RVPT_HIP_FORMAT_RAY_PATHS: rvpt_hip_read answers path qu
 PATH_MAX_BOUNCES = 1024  # RVPT_HIP_PATH_MAX_BOUNCES: a record with a larger bounce budget, or with none, is invalid (radiance 0, segments 0)
 # rvpt_ray_path (48 B): org, seed, dir, max_bounces come in, radiance and segments go out
 RAY_PATH_DTYPE = np.dtype([("org", "<f4", (3,)), ("seed", "<u4"), ("dir", "<f4", (3,)), ("max_bounces", "<u4"), ("radiance", "<f4", (3,)), ("segments", "<u4")])
+FORMAT_NEAREST_POINTS = 4  # RVPT_HIP_FORMAT_NEAREST_POINTS: rvpt_hip_read answers point queries, `dst` holds POINT_HIT_DTYPE records (Context.closest_points)
+# rvpt_point_hit: 48 bytes, three float4 — a point and a SQUARED bound in; the nearest point of the mesh, its squared distance, the triangle, u, v and the region out
+POINT_HIT_DTYPE = np.dtype([("point", "<f4", (3,)), ("max_d2", "<f4"), ("closest", "<f4", (3,)), ("d2", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("region", "<u4")])
 CULL_ROW_BOXES = 0x100  # Context.cull_info: the launch rode with the row boxes (rvpt_abi.hip: kCullRowBoxes)
 CULL_SKY_LIST = 0x80  # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
 TILE = 16
@@ -780,6 +783,31 @@ class Context:
         [n, 12] (48-byte records; seed, max_bounces and segments are the bits of their floats) on the host or on this context's device, as for trace_rays_into.
         The in fields stay as they are, the out fields are written.  Returns records."""
         return self._query_into(records, FORMAT_RAY_PATHS, RAY_PATH_DTYPE, "trace_paths_into", "RAY_PATH_DTYPE")
+
+    def closest_points(self, points, max_dist=math.inf) -> np.ndarray:
+        """The nearest point of the uploaded mesh to every point of points[n, 3] — include/rvpt_hip.h: NEAREST POINTS has the definition, the arithmetic and the
+        numbering of prim.  max_dist, a scalar or one value per point, is a DISTANCE: it is squared here in float32 (max_dist * max_dist, one rounding) into the
+        record's max_d2, the bound the library compares squared distances against; +inf searches without a bound, a negative or NaN max_dist makes the record
+        invalid.  Returns POINT_HIT_DTYPE[n]: closest, d2 (squared: np.sqrt(rec["d2"]) is the distance), prim, u, v, region; prim == NO_PRIM where no triangle is
+        within the bound."""
+        pts = np.asarray(points, dtype=np.float32)
+        if pts.ndim == 0 or pts.size % 3 or (pts.ndim > 1 and pts.shape[-1] != 3):
+            raise NativeError(ERR_INVALID, f"closest_points: points[n, 3] are needed, got shape {tuple(pts.shape)}")
+        pts = pts.reshape(-1, 3)
+        dist = np.asarray(max_dist, dtype=np.float32)
+        if dist.ndim > 1 or (dist.ndim == 1 and dist.shape[0] != pts.shape[0]):
+            raise NativeError(ERR_INVALID, f"closest_points: {pts.shape[0]} points, max_dist of shape {tuple(dist.shape)}")
+        rec = np.zeros(pts.shape[0], dtype=POINT_HIT_DTYPE)
+        rec["point"] = pts
+        with np.errstate(all="ignore"):
+            rec["max_d2"] = np.where(dist < 0, np.float32(-1), dist * dist)  # (a negative distance must not square into a valid bound)
+        return self.closest_points_into(rec)
+
+    def closest_points_into(self, records):
+        """rvpt_hip_read with FORMAT_NEAREST_POINTS in the caller's memory: `records` is a contiguous POINT_HIT_DTYPE array, or a contiguous float32 torch tensor
+        [n, 12] (48-byte records; prim and region are the bits of their floats) on the host or on this context's device, as for trace_rays_into.  The in fields
+        (point, max_d2 — a SQUARED distance) stay as they are, the out fields are written.  Returns records."""
+        return self._query_into(records, FORMAT_NEAREST_POINTS, POINT_HIT_DTYPE, "closest_points_into", "POINT_HIT_DTYPE")
 
     def write_accum(self, img) -> None:
         """rvpt_hip_write_accum: restore the accumulator from a row-major RGBA32F frame — anything numpy makes float32[h, w, 4] of, or a contiguous float32

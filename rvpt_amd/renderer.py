@@ -440,6 +440,19 @@ class RVPT:
             max_bounces = int(self.render_settings.max_bounces)
         return self._ctx.trace_paths(org, dir, seed, max_bounces)
 
+    def closest_points(self, points, max_dist=float("inf")) -> np.ndarray:
+        """Point queries against the scene as it is now (Context.closest_points; include/rvpt_hip.h: NEAREST POINTS): the nearest point of the mesh to every
+        point of points[n, 3] within max_dist (a distance; the records carry it squared).  Returns native.POINT_HIT_DTYPE records: closest, d2 (the SQUARED
+        distance), u, v, region, and prim numbering the triangles in the order they were ADDED (native.NO_PRIM: nothing within the bound), as trace_rays does.
+        Over a host-built tree a tie between equal distances is broken on the stored number, before this renumbering.  Needs initialize(), not update()."""
+        if self._ctx is None:
+            raise RuntimeError("closest_points before initialize()")
+        rec = self._ctx.closest_points(points, max_dist)
+        if not self._device_built and rec.shape[0]:  # a host-built tree: the device numbers the leaf order it was given
+            hit = rec["prim"] != native.NO_PRIM
+            rec["prim"][hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[rec["prim"][hit]]
+        return rec
+
     def pick(self, x: int, y: int):
         """What is under pixel (x, y) of the current camera: (prim, t) of the closest hit along the pixel-centre ray, or None.  The ray is made HERE, on the host, from
         scene_camera.get_data() (camera.glsl:29-51 in double, rounded to float32 once) — not by the frame kernel's float32 arithmetic: t agrees with a frame's to

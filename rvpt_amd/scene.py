@@ -704,6 +704,108 @@ def skin_triangles(rest_tris, skin, bones) -> np.ndarray:
     return out
 
 
+POINT_HIT_DTYPE = np.dtype([("point", "<f4", (3,)), ("max_d2", "<f4"), ("closest", "<f4", (3,)), ("d2", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4"),
+                            ("region", "<u4")])  # rvpt_point_hit (== native.POINT_HIT_DTYPE)
+NO_PRIM = 0xFFFFFFFF  # a record's prim after a miss
+
+
+def _dot_rounded(x, y):
+    return (x[..., 0] * y[..., 0] + x[..., 1] * y[..., 1]) + x[..., 2] * y[..., 2]
+
+
+def _quotient(num, den):
+    """The correctly rounded float32 quotient; a quotient whose divisor is 0 is taken as 0."""
+    zero = den == 0
+    return np.where(zero, np.float32(0), num / np.where(zero, np.float32(1), den)).astype(np.float32)
+
+
+def closest_point_triangles(p, tris):
+    """The per-triangle arithmetic of a POINT QUERY (include/rvpt_hip.h: NEAREST POINTS), vectorised: the candidate of every triangle of `tris` (float32[n, 16]
+    rows, or [n, 3, 3] vertices) for every point of `p` (float32[3] or [m, 3]).  float32 throughout, every product, sum and quotient rounded on its own — numpy
+    never fuses, and its float32 divide is the correctly rounded one — so the device and the host give the same bits: Ericson's point-triangle test with its
+    regions tested in the header's order (the first that holds decides u, v, region), q = (a + ab*u) + ac*v clamped into the triangle's own box by comparisons
+    that leave a NaN a NaN, d2 = (dx*dx + dy*dy) + dz*dz with d = p - q.
+    Returns (closest[..., n, 3], d2[..., n], u[..., n], v[..., n], region[..., n] uint32), the leading axis being p's (none for a single point)."""
+    t = np.asarray(tris, dtype=np.float32)
+    verts = t.reshape(-1, 4, 4)[:, :3, :3] if t.ndim == 2 and t.shape[1] == 16 else t.reshape(-1, 3, 3)
+    p = np.asarray(p, dtype=np.float32)
+    single = p.ndim == 1
+    pp = p.reshape(-1, 1, 3)  # [m, 1, 3] against [n, 3]
+    a, b, c = verts[:, 0], verts[:, 1], verts[:, 2]
+    one, zero = np.float32(1), np.float32(0)
+    with np.errstate(all="ignore"):
+        ab, ac = b - a, c - a
+        ap, bp, cp = pp - a, pp - b, pp - c
+        ab_, ac_ = np.broadcast_to(ab, ap.shape), np.broadcast_to(ac, ap.shape)
+        d1, d2, d3, d4, d5, d6 = _dot_rounded(ab_, ap), _dot_rounded(ac_, ap), _dot_rounded(ab_, bp), _dot_rounded(ac_, bp), _dot_rounded(ab_, cp), _dot_rounded(ac_, cp)
+        vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+        e1, e2 = d4 - d3, d5 - d6
+        conds = [(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6), (vb <= 0) & (d2 >= 0) & (d6 <= 0),
+                 (va <= 0) & (e1 >= 0) & (e2 >= 0)]
+        region = np.select(conds, [1, 2, 4, 3, 5, 6], default=0).astype(np.uint32)  # (np.select takes the first condition that holds)
+        s = (va + vb) + vc
+        w = _quotient(e1, e1 + e2)
+        u = np.select([region == 2, region == 4, region == 6, region == 0], [np.broadcast_to(one, s.shape), _quotient(d1, d1 - d3), one - w, _quotient(vb, s)], default=zero)
+        v = np.select([region == 3, region == 5, region == 6, region == 0], [np.broadcast_to(one, s.shape), _quotient(d2, d2 - d6), w, _quotient(vc, s)], default=zero)
+        u, v = u.astype(np.float32), v.astype(np.float32)
+        q = (a + ab * u[..., None]) + ac * v[..., None]
+        lo, hi = np.fmin(np.fmin(a, b), c), np.fmax(np.fmax(a, b), c)
+        q = np.where(q < lo, lo, np.where(q > hi, hi, q))
+        d = pp - q
+        dist2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    assert q.dtype == np.float32 and dist2.dtype == np.float32
+    if single:
+        return q[0], dist2[0], u[0], v[0], region[0]
+    return q, dist2, u, v, region
+
+
+def point_box_d2(p, lo, hi):
+    """The squared distance from p[..., 3] to the boxes [lo, hi] as a point query's walk computes it: g = max(max(lo - p, p - hi), 0) per axis, then
+    (gx*gx + gy*gy) + gz*gz in float32 — the expression shape of closest_point_triangles' d2, which is what makes box_d2 <= d2 hold in floats for every triangle
+    inside the box."""
+    p, lo, hi = np.asarray(p, dtype=np.float32), np.asarray(lo, dtype=np.float32), np.asarray(hi, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        g = np.fmax(np.fmax(lo - p, p - hi), np.float32(0))
+        return (g[..., 0] * g[..., 0] + g[..., 1] * g[..., 1]) + g[..., 2] * g[..., 2]
+
+
+def closest_points(tris, points, max_d2=np.inf, chunk: int = 1 << 20) -> np.ndarray:
+    """The normative statement of a POINT QUERY (include/rvpt_hip.h: NEAREST POINTS), by brute force: every triangle's candidate (d2_i, i) from
+    closest_point_triangles, the answer the lexicographically smallest one below (max_d2, 0xFFFFFFFF) — a NaN d2 never wins, d2 == max_d2 is accepted, among
+    equal d2 the smaller index.  `tris` (float32[n, 16]) in the order the update form takes on the context asked, which is the numbering of prim; points
+    float32[m, 3]; max_d2 a scalar or one SQUARED bound per point.  A point with a non-finite component, a max_d2 that is NaN or < 0, and a miss go out as
+    closest 0, d2 = the bits of max_d2, prim NO_PRIM, u = v = 0, region 0.  Returns POINT_HIT_DTYPE[m] with the in fields filled."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    pts = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    rec = np.zeros(pts.shape[0], dtype=POINT_HIT_DTYPE)
+    rec["point"] = pts
+    rec["max_d2"] = np.asarray(max_d2, dtype=np.float32)
+    rec["d2"], rec["prim"] = rec["max_d2"], NO_PRIM
+    bound = rec["max_d2"]
+    with np.errstate(all="ignore"):
+        valid = np.isfinite(pts).all(axis=1) & (bound >= 0)
+    rows = np.flatnonzero(valid)
+    n = t.shape[0]
+    if n == 0 or rows.size == 0:
+        return rec
+    step = max(1, chunk // n)
+    for lo in range(0, rows.size, step):
+        sel = rows[lo:lo + step]
+        q, d2, u, v, region = closest_point_triangles(pts[sel], t)
+        with np.errstate(all="ignore"):
+            ok = d2 <= bound[sel, None]  # (false for a NaN d2)
+        key = np.where(ok, d2, np.float32(np.inf))
+        best = ok & (key == key.min(axis=1, keepdims=True))
+        hit = best.any(axis=1)
+        i = np.argmax(best, axis=1)  # the first, hence the smallest index among equal d2
+        k = np.arange(sel.size)
+        out = rec[sel]
+        out["closest"][hit], out["d2"][hit] = q[k, i][hit], d2[k, i][hit]
+        out["prim"][hit], out["u"][hit], out["v"][hit], out["region"][hit] = i[hit].astype(np.uint32), u[k, i][hit], v[k, i][hit], region[k, i][hit]
+        rec[sel] = out
+    return rec
+
+
 def load_obj_positions(path) -> np.ndarray:
     """Minimal Wavefront OBJ reader: `v` records and `f` records (v, v/vt, v/vt/vn, v//vn, negative
     indices); polygons are fan-triangulated (tinyobjloader's default `triangulate=true`, which is

@@ -1614,7 +1614,9 @@ static int update_geometry_sparse(rvpt_hip_ctx *ctx, const uint32_t *indices, co
     const uint32_t *d_indices = indices;
     const float4 *d_src = reinterpret_cast<const float4 *>(tris);
     if (!device_tris && (rc = sparse_validate_host(ctx, indices, k, n_tris, &span_lo, &span_hi))) return rc;
-    // the permutation's inverse is needed by the device validation's span, so made in front of it
+    // the permutation's inverse is needed by the device validation's span, so made in front of it; a device list that is then refused leaves the flag as it
+    // found it: a refusal changes nothing the context holds, the inverse a later update would make included
+    const bool had_inv_perm = ctx->have_inv_perm;
     if ((rc = ensure_inverse_permutation(ctx))) return rc;
     const uint32_t *const inv_perm = ctx->have_perm ? ctx->d_inv_perm : nullptr;
     if (!device_tris) {  // a validated host list is staged: the indices behind the records
@@ -1642,10 +1644,13 @@ static int update_geometry_sparse(rvpt_hip_ctx *ctx, const uint32_t *indices, co
             const size_t j = h[rv::kSparseBadPosition];
             uint32_t value = 0;
             if (j < k) HIP_TRY(ctx, hipMemcpy(&value, indices + j, sizeof value, hipMemcpyDeviceToHost));
+            ctx->have_inv_perm = had_inv_perm;
             return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: indices[%zu] = %u is outside the %zu stored triangles", j, value, n_tris);
         }
-        if (h[rv::kSparseDuplicate] != 0xFFFFFFFFu)
+        if (h[rv::kSparseDuplicate] != 0xFFFFFFFFu) {
+            ctx->have_inv_perm = had_inv_perm;
             return fail(ctx, RVPT_HIP_ERR_INVALID, "sparse update: index %u occurs more than once in the list", h[rv::kSparseDuplicate]);
+        }
         span_lo = h[rv::kSparseSpanLo], span_hi = h[rv::kSparseSpanHi];
         if (span_lo > span_hi || span_hi >= n) span_lo = 0, span_hi = n - 1u;
     }

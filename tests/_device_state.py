@@ -36,6 +36,39 @@ def lattice(n, seed):
 SOUPS = {"soup": soup, "lattice": lattice}
 
 
+def ladder(rungs, cluster, seed, top=2.0 ** 75, ratio=1.0 / 32.0, h=2.0 ** -60):
+    """A geometric ladder along x: `rungs` triangles at top * ratio^k, then `cluster` triangles within [1/4, 1) of top * ratio^rungs; each is (x, h, h)
+    (x + x/64, 2h, h) (x, h, 2h), the rows shuffled.  Centroid y and z are one float32 for all, so only axis 0 is live; a rung lies more than 16 times further
+    out than everything below it, so it falls alone into bin 15 and the rest into bin 0: the SAH build peels one triangle per level and meets the cluster at
+    depth `rungs` — 30 is rv::kSahBalanceDepth, from where on only median splits are made.  h is below the smallest extent in x, every box area is a normal
+    float32 (about 2^16 down to 2^-115), no coordinate is zero.  NOT one of SOUPS: a few tests name it, the parametrised ones do not take it."""
+    rng = np.random.RandomState(seed)
+    xs = np.concatenate([top * ratio ** np.arange(rungs), top * ratio ** rungs * rng.uniform(0.25, 1.0, cluster)])  # float64
+    p = np.empty((xs.shape[0], 3, 3), dtype=np.float64)
+    p[:, 0] = np.stack([xs, np.full_like(xs, h), np.full_like(xs, h)], axis=1)
+    p[:, 1] = np.stack([xs + xs / 64.0, np.full_like(xs, 2.0 * h), np.full_like(xs, h)], axis=1)
+    p[:, 2] = np.stack([xs, np.full_like(xs, h), np.full_like(xs, 2.0 * h)], axis=1)
+    t = scene.make_triangles(p.astype(np.float32), 0)
+    return np.ascontiguousarray(t[rng.permutation(t.shape[0])])
+
+
+# the ladders the tests build: (rungs, cluster, seed) -> what scene.build_sah reports; the rows are, in order: the plain case; a node of 5000 > kSahLargeNode at depth 30
+# and two of 2500 at depth 31, large nodes whose bin launch is skipped; the cluster's first split at depth 29, still binned; nine triangles at depth 30 (one
+# median split); eight (a leaf: no median split at all)
+LADDERS = {
+    (30, 300, 1): {"n": 330, "height": 37, "binned_splits": 30, "median_splits": 63, "max_leaf": 5},
+    (30, 5000, 2): {"n": 5030, "height": 41, "binned_splits": 30, "median_splits": 1023, "max_leaf": 5},
+    (29, 300, 3): {"n": 329, "height": 36, "binned_splits": 30, "median_splits": 62, "max_leaf": 5},
+    (30, 9, 4): {"n": 39, "height": 32, "binned_splits": 30, "median_splits": 1, "max_leaf": 5},
+    (30, 8, 5): {"n": 38, "height": 31, "binned_splits": 30, "median_splits": 0, "max_leaf": 8},
+}
+# The first row squeezed into the binades in which a ray can hit its cluster (tests/test_ray_query.py).  The reference's triangle test divides by
+# det = |e0|^2 |e1|^2 - (e0 . e1)^2 = (dx^2 + h^2) h^2 with dx = x / 64: with the defaults above that is 2^-240 for every triangle of the cluster, zero in float32,
+# and no ray whatever hits one.  Here a rung lies 17 times further out than the next (still alone in bin 15), dx >= 2^-30 and h = 2^-32: det >= 2^-124, a normal float32.  The
+# eight rungs furthest out (dx >= 2^66, dx^2 = inf) stay beyond any ray.  scene.build_sah reports what it reports for the first row.
+HITTABLE_LADDER = {"rungs": 30, "cluster": 300, "seed": 1, "top": 2.0 ** 101, "ratio": 1.0 / 17.0, "h": 2.0 ** -32}
+
+
 def vertices(tris):
     """the nine coordinates of every triangle, float32[n, 3, 3] (a view where `tris` is contiguous)"""
     return np.asarray(tris).reshape(-1, 4, 4)[:, :3, :3]

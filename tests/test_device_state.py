@@ -374,7 +374,7 @@ def check_update_state(before, after, exp, want_nodes, want_vertices, what):
     # A fresh regrouping of the refit tree opens the child with the largest box first and may group differently (tests/test_refit_host.py); the device keeps the
     # upload's grouping, which the comparison above and check_wide_map below pin.  Where the fresh form has the same heads throughout it is compared whole as
     # well; where not, that is counted and printed, never silent.  (A prefix cannot be compared instead: slots that are all inner carry consecutive wide
-    # indices as heads whichever binary nodes stand behind them.)  On the MI355X 4 of the file's 44 updates keep every head.
+    # indices as heads whichever binary nodes stand behind them.)  On the MI355X 5 of the file's 46 updates keep every head.
     regrouped = not (fresh.shape == want_wide.shape and ds.same_bytes(fresh[:, 6:, :], want_wide[:, 6:, :]))
     WIDE_FORM_COMPARED[regrouped] += 1
     print(f"{what}: d_wide against the wide form of the refit tree: {'NOT compared, a fresh regrouping has other heads' if regrouped else 'equal heads, compared'} "
@@ -680,3 +680,151 @@ def test_guarded_update_state(native, method):
         moved_rows = moved.copy()
         moved_rows[:, 12:] = tris[:, 12:]
         check_build_state(s2, moved_rows, new_nodes, new_perm, ds.Expected(new_nodes, breadth_first=True), method, f"{method} guarded, rebuilt")  # base_cost: the new tree's
+
+
+# ---- GPU (g): the geometric ladder — the SAH build's rule "from depth 30 on, only median splits" -------------------------------------------------------------------
+
+LADDER_ROWS = list(ds.LADDERS)
+LADDER_IDS = ["-".join(map(str, r)) for r in LADDER_ROWS]
+PLAIN_LADDER = LADDER_ROWS[0]  # (30, 300, 1): 330 triangles, 37 levels
+
+
+def ladder_tree(method, row):
+    """tree_of for ds.ladder(*row): (tris, nodes, perm, reported tree, ds.Expected, the builder's info) — built once, shared and left unchanged"""
+    key = (method, "ladder", row)
+    if key not in _TREES:
+        tris = ds.ladder(*row)
+        assert ds.no_zero_coordinate(tris)
+        nodes, perm, tree, built = numpy_tree(method, tris)
+        _TREES[key] = (tris, nodes, perm, tree, ds.Expected(nodes, breadth_first=True), built)
+    return _TREES[key]
+
+
+@gpu
+@pytest.mark.parametrize("row", LADDER_ROWS, ids=LADDER_IDS)
+def test_ladder_sah_build_state_is_the_numpy_statements(native, row):
+    """sah_decide's `depth < kSahBalanceDepth` and sah_decide_level's skipped sah_large_bins, reached: thirty binned levels that peel one triangle each, then
+    the cluster at depth 30 (29 for the third row, the other side of the comparison) — 5000 triangles are a large node whose bins nobody fills, nine are one
+    median split, eight a leaf.  tests/test_sah_host.py holds the numpy tree to the table of ds.LADDERS and to rvpt_bvh_build's tree."""
+    tris, nodes, perm, tree, exp, info = ladder_tree("sah", row)
+    assert info == {k: v for k, v in ds.LADDERS[row].items() if k != "n"} and exp.height == info["height"]
+    with lab_context(native) as ctx:
+        assert ctx.build_scene(tris, materials(), method="sah") == "sah"
+        state = ctx.scene_state()
+        print(f"ladder {row}: n {tris.shape[0]} bvh_height {state['bvh_height']} wide_stack_levels {state['wide_stack_levels']} n_wide {state['n_wide']}")
+        check_build_state(state, tris, nodes, perm, exp, "sah", f"sah ladder {row}")
+
+
+@gpu
+def test_hittable_ladder_sah_build_state_is_the_numpy_statements(native):
+    """the ladder tests/test_ray_query.py sends rays down (ds.HITTABLE_LADDER): 17 between the rungs, not 32 — nearer to the edge of bin 15"""
+    tris = ds.ladder(**ds.HITTABLE_LADDER)
+    assert ds.no_zero_coordinate(tris)
+    nodes, perm, _, info = numpy_tree("sah", tris)
+    assert info == {k: v for k, v in ds.LADDERS[PLAIN_LADDER].items() if k != "n"}
+    with lab_context(native) as ctx:
+        assert ctx.build_scene(tris, materials(), method="sah") == "sah"
+        check_build_state(ctx.scene_state(), tris, nodes, perm, ds.Expected(nodes, breadth_first=True), "sah", "sah hittable ladder")
+
+
+@gpu
+def test_ladder_sah_build_state_from_a_device_tensor(native):
+    import torch
+    tris, nodes, perm, tree, exp, _ = ladder_tree("sah", PLAIN_LADDER)
+    with lab_context(native) as ctx:
+        assert ctx.build_scene(torch.from_numpy(tris).to("cuda:0"), materials(), method="sah") == "sah"
+        check_build_state(ctx.scene_state(), tris, nodes, perm, exp, "sah", f"sah ladder {PLAIN_LADDER} from a tensor")
+
+
+@gpu
+@pytest.mark.parametrize("row", LADDER_ROWS[:2], ids=LADDER_IDS[:2])
+@pytest.mark.parametrize("method", ["lbvh", "ploc"])
+def test_ladder_morton_build_state_is_the_numpy_statements(native, method, row):
+    """The same input through the two Morton builders: an axis of 150 binades quantised to 10 bits leaves nearly every triangle in one cell"""
+    tris, nodes, perm, tree, exp, _ = ladder_tree(method, row)
+    assert tree == method  # (PLOC: no fallback)
+    with lab_context(native) as ctx:
+        assert ctx.build_scene(tris, materials(), method=method) == tree
+        state = ctx.scene_state()
+        print(f"ladder {row} {method}: bvh_height {state['bvh_height']} wide_stack_levels {state['wide_stack_levels']}")
+        check_build_state(state, tris, nodes, perm, exp, method, f"{method} ladder {row}")
+
+
+def ladder_rungs(tris, rungs=30):
+    """the caller's indices of the `rungs` triangles furthest out"""
+    return np.sort(np.argsort(tris[:, 0])[-rungs:])
+
+
+@gpu
+def test_plain_update_of_a_device_built_tree_of_37_levels(native):
+    """Another ladder of the same size over the stored topology: the refit level table's 37 levels, deepest first"""
+    from rvpt_amd import scene
+    tris, nodes, perm, _, exp, _ = ladder_tree("sah", PLAIN_LADDER)
+    moved = ds.ladder(30, 300, 11)
+    assert moved.shape == tris.shape and ds.no_zero_coordinate(moved) and not ds.same_bytes(moved, tris)
+    want = scene.refit_bvh(nodes, moved[perm])
+    assert not ds.same_bytes(want["bounds"], nodes["bounds"])
+    with lab_context(native) as ctx:
+        ctx.build_scene(tris, materials(), method="sah")
+        s0 = ctx.scene_state()
+        assert s0["bvh_height"] == 37
+        ctx.update_triangles(moved)
+        check_update_state(s0, ctx.scene_state(), exp, want, moved[perm], "ladder plain update")
+
+
+@gpu
+def test_sparse_update_of_a_device_built_tree_of_37_levels(native):
+    """The 30 rungs, their x scaled by 0.75 (exact), and 30 triangles of the cluster as they are: every leaf of the cluster lies 36 parents below the root, so
+    the flag walk climbs 36 levels; the boxes of all 30 chain nodes change, the rest keep the bytes they had."""
+    from rvpt_amd import scene
+    tris, nodes, perm, _, exp, _ = ladder_tree("sah", PLAIN_LADDER)
+    rungs = ladder_rungs(tris)
+    others = np.setdiff1d(np.arange(tris.shape[0]), rungs)
+    idx = np.concatenate([rungs, np.random.RandomState(5).permutation(others)[:30]])  # the caller's indices, in no order
+    patched = tris.copy()
+    patched[rungs, 0:12:4] *= np.float32(0.75)
+    assert ds.no_zero_coordinate(patched) and np.array_equal(patched[rungs, 0].astype(np.float64), tris[rungs, 0].astype(np.float64) * 0.75)
+    inv = np.argsort(perm)
+    pos = inv[idx]
+    want = scene.refit_bvh(nodes, patched[perm], touched=pos)
+    # the walks, from the maps alone: the nodes on the touched paths and the longest climb
+    on, longest = np.zeros(exp.n_nodes, dtype=bool), 0
+    for leaf in np.unique(exp.leaf_of[pos]):
+        steps, at = 0, exp.parent[leaf]
+        on[leaf] = True
+        while at != ds.EMPTY:
+            on[at] = True
+            steps, at = steps + 1, exp.parent[at]
+        longest = max(longest, steps)
+    assert longest == 36 == exp.height - 1
+    with lab_context(native) as ctx:
+        ctx.build_scene(tris, materials(), method="sah")
+        s0 = ctx.scene_state()
+        ctx.update_triangles(patched[idx], indices=idx)
+        s1 = ctx.scene_state()
+        check_update_state(s0, s1, exp, want, patched[perm], "ladder sparse update")
+        check_sparse_maps(s1, exp, perm, "ladder sparse update")
+        assert ds.same_bytes(s1["nodes"][~on], s0["nodes"][~on]), "boxes off the touched paths moved"
+        chain = np.flatnonzero(on & (s0["nodes"]["count"] == 0))[:30]  # the 30 nodes above the cluster, root first
+        assert (s1["nodes"]["bounds"][chain] != s0["nodes"]["bounds"][chain]).any(axis=1).all()
+
+
+@gpu
+def test_guarded_update_rebuilds_a_ladder_by_the_depth_rule(native):
+    """The smallest limit there is, and a third ladder: the refitted tree costs more, the rebuild is reported, and the state is a fresh SAH build's of the new
+    ladder — the depth rule reached through the rebuild path."""
+    from rvpt_amd import scene
+    tris, nodes, perm, _, exp, _ = ladder_tree("sah", PLAIN_LADDER)
+    moved = ds.ladder(30, 300, 12)
+    assert moved.shape == tris.shape and ds.no_zero_coordinate(moved)
+    ratio = scene.tree_cost(scene.refit_bvh(nodes, moved[perm])) / scene.tree_cost(nodes)
+    assert ratio > 1.01, ratio  # clear of the limit
+    new_nodes, new_perm, _, info = numpy_tree("sah", moved)
+    assert info["height"] > 31 and info["median_splits"] > 0 and info["binned_splits"] == 30
+    with lab_context(native) as ctx:
+        ctx.build_scene(tris, materials(), method="sah")
+        rep = ctx.update_triangles(moved, rebuild_above=1.0)
+        assert rep.rebuilt and rep.tree == "sah"
+        moved_rows = moved.copy()
+        moved_rows[:, 12:] = tris[:, 12:]  # an update keeps the stored material rows
+        check_build_state(ctx.scene_state(), moved_rows, new_nodes, new_perm, ds.Expected(new_nodes, breadth_first=True), "sah", "ladder guarded, rebuilt")

@@ -200,6 +200,46 @@ def test_prim_is_the_callers_index_after_a_build_form(native, oracle, default_sc
         assert abs(np.dot(p - a, n)) <= 1e-4 * np.linalg.norm(n) * (1 + np.linalg.norm(p))
 
 
+def test_a_walk_down_a_device_built_tree_of_37_levels(native, oracle):
+    """Case 5, deep.  tests/_device_state.py's geometric ladder built by "sah": thirty levels that peel one triangle each, then the cluster in median splits
+    (rv::kSahBalanceDepth) — leaves 36 levels below the root.  One ray at every triangle, from 4 h above its centroid straight down, tmax = 8 h, a third any
+    hit; 64 more displaced by 3 h in z, past every triangle.  On the ladder of the generator's defaults (top 2^75, h 2^-60) no ray at all can hit the cluster: the
+    triangle test's determinant is 2^-240, zero in float32 (ds.HITTABLE_LADDER says it in full), so this is that ladder with 17 between the rungs and
+    h = 2^-32; the rays are the ones described.  What the rays must be is asserted of the statement before the GPU is asked."""
+    import _device_state as ds
+    from rvpt_amd import scene
+    h = ds.HITTABLE_LADDER["h"]
+    tris = ds.ladder(**ds.HITTABLE_LADDER)
+    mats = scene.default_materials()
+    n = tris.shape[0]
+    nodes, perm, info = scene.build_sah(tris)
+    assert info == {k: v for k, v in ds.LADDERS[(30, 300, 1)].items() if k != "n"}
+    centroid = ds.vertices(tris).astype(np.float64).mean(axis=1)
+    org = np.concatenate([centroid + [0.0, 4.0 * h, 0.0], centroid[:64] + [0.0, 4.0 * h, 3.0 * h]])
+    flags = np.where(np.arange(n + 64) % 3 == 0, native.RAY_ANY_HIT, 0).astype(np.uint32)
+    records = rq.make_records(org, np.tile([0.0, -1.0, 0.0], (n + 64, 1)), np.float32(8.0 * h), flags)
+    want = rq.Statement(oracle, nodes, tris[perm]).answer(records, 0, perm=perm)
+    hit = want["prim"][:n] != rq.NO_PRIM
+    assert 4 * int(hit.sum()) >= 3 * n, int(hit.sum())
+    assert (want["prim"][n:] == rq.NO_PRIM).all()
+    depth_of = np.zeros(len(nodes), dtype=np.int64)  # a numpy builder's tree is breadth first: parents come before their children
+    leaf_at = np.zeros(n, dtype=np.int64)  # the depth of the leaf that holds a stored position
+    for i in range(len(nodes)):
+        f, c = int(nodes[i]["first"]), int(nodes[i]["count"])
+        if c == 0:
+            depth_of[f] = depth_of[f + 1] = depth_of[i] + 1
+        else:
+            leaf_at[f:f + c] = depth_of[i]
+    deepest = leaf_at[np.argsort(perm)[want["prim"][:n][hit]]]
+    assert (deepest >= 31).any() and deepest.max() == 36
+    assert (want["prim"][:n][hit] != np.flatnonzero(hit)).any()  # the cluster's triangles overlap: some rays meet a nearer one than their own
+    got, state = ask(native, native.TRAVERSAL_BVH, None, records, lab=True, upload=lambda ctx: ctx.build_scene(tris, mats, "sah") == "sah" or pytest.fail("fell back"))
+    assert state["bvh_height"] == 37 and state["n_wide"] > 0
+    check(got, want, records, "ladder, sah")
+    got, _ = ask(native, native.TRAVERSAL_BVH, None, records, upload=lambda ctx: ctx.build_scene(tris, mats, "sah") == "sah" or pytest.fail("fell back"))
+    check(got, want, records, "ladder, sah, release build")
+
+
 @pytest.mark.parametrize("form", ["plain", "sparse"])
 def test_queries_answer_for_the_moved_mesh(native, oracle, default_scene, form):
     """Case 6.  After update_triangles — plain, and indices= on a loose tree — a query answers for the moved mesh: the statement runs on refit_bvh(...)

@@ -4,6 +4,7 @@ with this one bit for bit."""
 import numpy as np
 import pytest
 
+import _device_state as ds
 from rvpt_amd import scene
 from rvpt_amd.scene import build_sah
 from test_lbvh_host import SCENES, scene_of, strip
@@ -175,8 +176,9 @@ def test_negative_zero_equals_zero_in_the_median_sort():
 @pytest.mark.parametrize("k", [0, 3])
 def test_the_depth_rule(k):
     """balance_depth = k on strip2000: from level k on only median splits (no binning), and the tree stays valid.  The device's trigger is the same comparison
-    against the compile-time 30 (rv::kSahBalanceDepth); no test input is known to reach depth 30 on the GPU — the bins halve well-spread scenes long before —
-    so that branch of the kernels is covered by this statement of the rule alone, not by a GPU test."""
+    against the compile-time 30 (rv::kSahBalanceDepth); the bins halve well-spread scenes long before depth 30, so the GPU meets that branch of the kernels on
+    tests/_device_state.py's geometric ladder alone: test_the_ladder_reaches_the_depth_rule below states its trees, tests/test_device_state.py's ladder
+    tests compare the device's with them byte for byte, and tests/test_ray_query.py walks one."""
     tris = strip(2000)
     nodes, perm, info = build_sah(tris, balance_depth=k)
     check_sah_tree(tris, nodes, perm, info)
@@ -194,6 +196,45 @@ def test_the_depth_rule(k):
     assert full[2]["median_splits"] == 0
     # a median split halves: below level k the tree is balanced, leaves of <= 8
     assert info["height"] <= k + int(np.ceil(np.log2(2000))) + 1
+
+
+@pytest.mark.parametrize("row", list(ds.LADDERS), ids=["-".join(map(str, r)) for r in ds.LADDERS])
+def test_the_ladder_reaches_the_depth_rule(row):
+    """tests/_device_state.py's geometric ladder: the binned split peels one triangle per level down to depth 30 (rv::kSahBalanceDepth), where the cluster
+    arrives whole and takes median splits only.  The builder's report is the table's, exactly; every level that still holds a rung has one inner node, with a
+    child of one triangle; every inner node from depth 30 on has children whose counts differ by at most one; and the tree is rvpt_bvh_build's.  The row of 29
+    rungs has one more inner node above depth 30, the cluster itself at depth 29: no rung is left to peel, its split is binned all the same (156 | 144)."""
+    from rvpt_amd import native
+    want = ds.LADDERS[row]
+    tris = ds.ladder(*row)
+    assert tris.shape[0] == want["n"] and ds.no_zero_coordinate(tris)
+    c = (tris[:, 0:3] + tris[:, 4:7] + tris[:, 8:11]) * np.float32(1.0 / 3.0)
+    assert np.ptp(c[:, 1]) == 0 and np.ptp(c[:, 2]) == 0 and np.unique(c[:, 0]).size == want["n"]  # one live axis, no two centroids alike
+    nodes, perm, info = build_sah(tris)
+    assert check_sah_tree(tris, nodes, perm, info) == want["height"]
+    assert info == {k: v for k, v in want.items() if k != "n"}
+    first, count = nodes["first"].astype(np.int64), nodes["count"].astype(np.int64)
+    below = np.zeros(len(nodes), dtype=np.int64)  # triangles below every node: children follow their parents in the layout
+    for i in range(len(nodes) - 1, -1, -1):
+        below[i] = count[i] if count[i] > 0 else below[first[i]] + below[first[i] + 1]
+    level, depth, binned, medians = np.zeros(1, dtype=np.int64), 0, 0, 0
+    while level.size:
+        inner = level[count[level] == 0]
+        left, right = below[first[inner]], below[first[inner] + 1]
+        if depth < row[0]:  # a rung is still there
+            assert inner.size == 1 and ((left == 1) | (right == 1)).all(), depth
+            binned += inner.size
+        elif depth < scene.SAH_BALANCE_DEPTH:  # (29, 300, 3): the cluster's first split is still a binned one, by the bins' cost and not in halves
+            assert inner.size == 1 and (np.abs(left - right) > 1).all(), (depth, left, right)
+            binned += inner.size
+        else:
+            assert (np.abs(left - right) <= 1).all(), depth
+            medians += inner.size
+        level = np.stack([first[inner], first[inner] + 1], axis=1).reshape(-1)
+        depth += 1
+    assert (binned, medians) == (want["binned_splits"], want["median_splits"])
+    host_nodes, host_perm = native.build_bvh(tris)
+    same_tree(nodes, perm, host_nodes.view(scene.NODE_DTYPE).reshape(-1), host_perm)
 
 
 def infinite_axis(n=12):

@@ -74,7 +74,9 @@ extern "C" {
                                      four weighted matrices (linear blend skinning), every box refitted.  Still 8, no
                                      new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_NEAREST_POINTS (4) — until then the "unknown format" error — is a
                                      POINT QUERY: `dst` holds rvpt_point_hit records, a point and a squared bound in, the nearest point of the mesh, its squared
-                                     distance and its triangle out */
+                                     distance and its triangle out.  Still 8, no new symbol: rvpt_hip_read with a format RVPT_HIP_FORMAT_RAY_PATHS_MODE(mode)
+                                     (16 .. 25) — until then the "unknown format" error — is a PATH QUERY BY INTEGRATOR: the records of format 3, each
+                                     evaluated by the render mode 0 .. 9 of compute_pass.comp the call names; mode 9 is format 3 itself */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -174,6 +176,7 @@ typedef struct rvpt_ray_hit {
 
 #define RVPT_HIP_FORMAT_RAY_PATHS 3   /* dst: rvpt_ray_path[dst_bytes / 48], in and out (PATH QUERIES at rvpt_hip_read) */
 #define RVPT_HIP_PATH_MAX_BOUNCES 1024u /* per path: the largest bounce budget a record may ask for */
+#define RVPT_HIP_FORMAT_RAY_PATHS_MODE(mode) (16 + (mode))   /* mode 0 .. 9: the render modes of compute_pass.comp:76-95 */
 
 /* One path of a query and its answer (48 B = three float4; no reference counterpart: the reference traces only its camera's paths). */
 typedef struct rvpt_ray_path {
@@ -609,8 +612,18 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  * - The call is LOCAL: with a communicator it is not collective and touches no peer.
  * - It implies rvpt_hip_wait and leaves untouched the accumulator, rvpt_hip_get_timing, rvpt_hip_get_stats, rvpt_hip_get_launch_info, rvpt_hip_get_cull_info,
  *   the frame counter, and rvpt_hip_last_error on success: a frame dispatched after a path query is bit for bit the frame dispatched without it.
- * - ONLY KAJIYA IS BUILT.  The other ten integrators of compute_pass.comp (render modes 0-8 and Hart) are not part of this form.
- * DESIGN.md 5.14 has the kernels and what was measured (profiles/path_queries.txt).
+ * - THE OTHER INTEGRATORS, PER CALL.  rvpt_hip_read(ctx, RVPT_HIP_FORMAT_RAY_PATHS_MODE(m), records, n * sizeof(rvpt_ray_path)), m = 0 .. 9, is this form with
+ *   every record evaluated by the integrator of render mode m (compute_pass.comp:76-95: 0 binary, 1 color, 2 depth, 3 normal, 4 Utah, 5 ambient occlusion,
+ *   6 Appel, 7 Whitted, 8 Cook, 9 Kajiya) instead of integrator_Kajiya.  The mode belongs to the call, not to the record: a launch is uniform in its integrator.
+ *   Mode 9 (format 25) IS format 3: the same kernels and the same bytes.  max_bounces is what the integrator receives as render_settings.max_bounces: the bounce
+ *   budget of Whitted, Cook and Kajiya, the number of occlusion samples of integrator_ao; modes 0-4 and 6 ignore it.  The validity rule above holds for EVERY
+ *   mode, those that ignore the budget included; a frame with max_bounces <= 0 is therefore not reproduced for the modes that would still trace (0-6: such a
+ *   frame's ambient occlusion is 1 - 0/0) — one rule for all modes is worth more than that corner.  segments counts every closest-hit query the record made,
+ *   shadow and occlusion queries included: what RVPT_HIP_COUNT_SEGMENTS counts in a frame of that mode.  Everything else is as written above for format 3.
+ * - HART IS NOT PART OF THIS FORM: mode 10 and every mode eval_integrator sends to its default branch.  integrator_Hart marches 32 steps over all triangles per
+ *   ray, and on a large scene no record count keeps such a launch bounded — the rule RVPT_HIP_PATH_MAX_BOUNCES exists for.  Format 26 and every other value are
+ *   the "unknown format" error.
+ * DESIGN.md 5.14 has the kernels and what was measured (profiles/path_queries.txt); 5.21 has the integrators per call (profiles/path_modes.txt).
  *
  * NEAREST POINTS — the nearest point of the mesh to the caller's own points, in place:
  *

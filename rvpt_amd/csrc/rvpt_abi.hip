@@ -2865,8 +2865,9 @@ int rvpt_hip_gather(rvpt_hip_ctx *ctx, void *dst_dev_rgba32f)
 // The forms share everything but the kernels and the first out byte: the checks, the pointer's classification, the staging of host records (only a record's
 // out fields travel back: its third float4, for a point query its second and third).  LOCAL: no communicator is touched.  Everything is checked before
 // anything is written; on success ctx->err stays as it was.  No event is recorded: RVPT_HIP_TIMING does not see a query.
+// `path_mode` (RecordKind::Paths only): the integrator of the call, 0 .. 9 — RVPT_HIP_FORMAT_RAY_PATHS is mode 9, RVPT_HIP_FORMAT_RAY_PATHS_MODE(m) is mode m.
 enum class RecordKind { Rays, Paths, Points };
-static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const RecordKind kind)
+static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const RecordKind kind, const uint32_t path_mode = rv::kPathModeKajiya)
 {
     const bool paths = kind == RecordKind::Paths, points = kind == RecordKind::Points;
     const char *what = points ? "point" : (paths ? "path" : "ray"), *record = points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : "rvpt_ray_hit");
@@ -2901,7 +2902,7 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
     if (points)
         HIP_TRY(ctx, rv::nearest_plan(nearest, static_cast<uint32_t>(n), ctx->num_cus, &plan));
     else if (paths)
-        HIP_TRY(ctx, rv::path_plan(path_scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
+        HIP_TRY(ctx, rv::path_plan(path_scene, static_cast<uint32_t>(n), ctx->num_cus, path_mode, &plan));
     else
         HIP_TRY(ctx, rv::query_plan(scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
     if (int rc = rvpt_hip_wait(ctx)) return rc;  // every read implies it; frames in flight still read the scene, and the buffers below may be regrown
@@ -2915,7 +2916,7 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
     if (points)
         HIP_TRY(ctx, rv::nearest_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
     else if (paths)
-        HIP_TRY(ctx, rv::path_launch(ctx->stream, path_scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
+        HIP_TRY(ctx, rv::path_launch(ctx->stream, path_scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n), path_mode));
     else
         HIP_TRY(ctx, rv::query_launch(ctx->stream, scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
     if (!device_dst)  // only the out fields travel back: the in fields of a host record are never written either
@@ -2928,6 +2929,8 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
 int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
 {
     if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
+    if (format >= RVPT_HIP_FORMAT_RAY_PATHS_MODE(0) && format <= RVPT_HIP_FORMAT_RAY_PATHS_MODE(9))  // a path query by integrator (mode 9 is RVPT_HIP_FORMAT_RAY_PATHS itself); local as well
+        return query_records(ctx, dst, dst_bytes, RecordKind::Paths, static_cast<uint32_t>(format - RVPT_HIP_FORMAT_RAY_PATHS_MODE(0)));
     if (format == RVPT_HIP_FORMAT_RAY_HITS || format == RVPT_HIP_FORMAT_RAY_PATHS || format == RVPT_HIP_FORMAT_NEAREST_POINTS)  // local even with a communicator: every rank holds the whole scene
         return query_records(ctx, dst, dst_bytes,
                              format == RVPT_HIP_FORMAT_NEAREST_POINTS ? RecordKind::Points : (format == RVPT_HIP_FORMAT_RAY_PATHS ? RecordKind::Paths : RecordKind::Rays));

@@ -9,6 +9,12 @@
 // record of the run its wave has claimed (runs of kPathRun consecutive records off one counter; ballot / mbcnt hand-out as WavePool deals pixels) before the
 // next segment's walk.  All three kernels run on a PERSISTENT grid sized from occupancy.  A record's answer is a function of its 32 in bytes and the scene
 // alone: which lane or wave traced it, and beside which other records, changes nothing.
+//
+// GENERIC instances (RVPT_HIP_FORMAT_RAY_PATHS_MODE(0 .. 8)): the same kernels with shade_generic() where the lean ones have shade().  The mode belongs to the
+// launch and sits in an SGPR; the continuation state (phase, ao_i, ao_acc, aux_o, aux_n) is per lane and exists only in the instance of the modes that ask
+// further queries (PathForm below: HIT_ONLY for modes 0 .. 4, CONTINUING for 5 .. 8).  Lanes of one wave sit
+// in different phases — a main segment beside a shadow query beside an occlusion sample —, and every phase asks the same question, the closest hit in (0, +inf);
+// so regeneration is unchanged, and a record's answer is a function of its 32 in bytes, the call's mode and the scene.  Hart is not built.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,6 +37,7 @@ struct PathArgs {
     uint32_t *counter;           // the next run to claim (0 at launch)
     uint32_t *stack_overflow;    // [stack_levels - lds_levels][2][threads of the grid]
     uint32_t n_tris, head_shift, stack_levels, lds_levels, top_nodes;
+    uint32_t mode;               // GENERIC instances: the call's integrator, render mode 0 .. 8 of compute_pass.comp:76-95 (the lean instances are mode 9 and do not read it)
 };
 
 // The path a lane is tracing: the frame kernels' Lane (segment, throughput, radiance so far, RNG state, finished segments) with the record it came from
@@ -47,11 +54,29 @@ struct RunPool {
     bool exhausted = false;  // the counter has passed the last run
 };
 
+// The instances of each kernel.  LEAN is integrator_Kajiya under shade(), the code of RVPT_HIP_FORMAT_RAY_PATHS.  The GENERIC instances run shade_generic() and
+// are two: HIT_ONLY for the modes that end at the first hit (0 .. 4: no continuation state, no RNG use) and CONTINUING for those that ask further queries (5 .. 8).
+// One GENERIC instance for all nine modes cost path_bvh4 a work-group per CU against the lean one (89 VGPRs: five waves per SIMD where 74 allow six); the split
+// keeps that cost to the modes whose state needs the registers (profiles/path_modes.txt has both sets of figures).
+enum PathForm { LEAN = 0, HIT_ONLY = 1, CONTINUING = 2 };
+
+// The integrator of a GENERIC launch: a kernel argument, so one value for the whole wave, held in an SGPR — shade_generic's switch on it is a scalar branch.
+// The host launches an instance with the modes of its form only; the clamp tells the compiler so: the other forms' cases and shade_generic's default branch
+// (hart(), which would read tris the path kernels are not given) are not built into it.
+template <int FORM>
+__device__ __forceinline__ uint32_t path_mode(const PathArgs &a)
+{
+    return FORM == HIT_ONLY ? min(a.mode, 4u) : max(5u, min(a.mode, 8u));
+}
+
 __device__ __forceinline__ bool finite_(const float x) { return __builtin_fabsf(x) < kInf; }  // false for NaN and +-inf
 
 // Every lane without a path takes the next record of the wave's run, in lane order; the wave claims a new run when the one it holds is dealt.  An invalid
 // record — a non-finite component of org or dir, a budget of 0 or past kPathMaxBounces — is answered here, before any walk: radiance 0, segments 0.
 // On return a lane without a path means that the records are all dealt.
+// CONTINUING: a record starts as begin_sample_generic leaves a sample after the camera — the main phase, and integrator_Whitted's ambient term (integrators.glsl:293)
+// in col.  The continuation state of the record before it on the lane needs no reset: shade_generic writes aux_o, aux_n, ao_acc and ao_i when it enters PH_AO.
+template <int FORM>
 __device__ __forceinline__ void regenerate_paths(RunPool &pool, const PathArgs &a, const uint32_t lane, PathLane &P)
 {
     bool need = !P.have;
@@ -85,6 +110,11 @@ __device__ __forceinline__ void regenerate_paths(RunPool &pool, const PathArgs &
                 P.L.d = mk(rb.x, rb.y, rb.z);
                 P.L.thr = mk(1.0f, 1.0f, 1.0f);
                 P.L.col = mk(0.0f, 0.0f, 0.0f);
+                if (FORM == CONTINUING) {
+                    const float ambient = (path_mode<FORM>(a) == 7u) ? 0.1f : 0.0f;
+                    P.L.col = mk(ambient, ambient, ambient);
+                    P.L.phase = PH_MAIN;
+                }
                 P.L.rng = __float_as_uint(ra.w);
                 P.L.bounce = 0;
                 P.L.nseg = 0;
@@ -102,13 +132,18 @@ __device__ __forceinline__ void regenerate_paths(RunPool &pool, const PathArgs &
 
 // A finished segment: shade() as a frame runs it, with the record's budget where a frame has its settings'.  A path that ended stores its out fields — the
 // integrator's value itself (a frame adds it to zero), the segments it traced — and frees the lane.  Returns true when the path goes on with L.o, L.d.
+// GENERIC forms: shade_generic() with the launch's mode, for the phase the lane is in: a shadow query or an occlusion sample is a segment like any other, and the
+// record's budget is also what PH_AO reads as its sample count.
+template <int FORM>
 __device__ __forceinline__ bool finish_segment(const PathArgs &a, const ShadeSrc src, PathLane &P, const uint32_t hit, const float closest)
 {
-    FrameParams fp;  // shade() reads its bounce budget and nothing else
+    FrameParams fp;  // shade() and shade_generic() read their bounce budget and nothing else
     fp.max_bounces = P.max_bounces;
+    if (FORM != LEAN) P.L.mode = static_cast<int>(path_mode<FORM>(a));
+    if (FORM == HIT_ONLY) P.L.phase = PH_MAIN;  // (these modes never leave it)
     f3 radiance = mk(0.0f, 0.0f, 0.0f);
     P.L.nseg += 1;
-    if (!shade(P.L, fp, src, hit, closest, radiance)) return true;
+    if (!shade_t<FORM != LEAN>(P.L, fp, src, hit, closest, radiance)) return true;
     a.records[3 * static_cast<size_t>(P.rec) + 2] = make_float4(radiance.x, radiance.y, radiance.z, __uint_as_float(P.L.nseg));
     P.have = false;
     return false;
@@ -122,6 +157,7 @@ enum { S_IDLE = 0, S_TRAV = 1, S_HIT = 2 };  // no segment / a segment whose wal
 // stacked, the last first, with their entry distances and packed heads, popped with closest >= entry) under the frame kernel's loop: lanes whose walk has ended
 // wait in S_HIT until kPathRefill of them do, then shade, regenerate and start the next walk together; reached leaves are parked and run in batches.
 // LDS: [stack: lds_levels x 2 words x kBlock][root: 2 float4][top_nodes wide nodes]
+template <int FORM>
 __global__ __launch_bounds__(kBlock) void path_bvh4(const PathArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
@@ -168,8 +204,8 @@ __global__ __launch_bounds__(kBlock) void path_bvh4(const PathArgs a)
     for (;;) {
         // ---- refill: every lane that is not walking shades the segment it finished, takes a record if its path ended, and starts its next walk
         for (;;) {
-            if (state == S_HIT) state = finish_segment(a, shade_src, P, hit, closest) ? S_TRAV : S_IDLE;
-            regenerate_paths(pool, a, lane, P);
+            if (state == S_HIT) state = finish_segment<FORM>(a, shade_src, P, hit, closest) ? S_TRAV : S_IDLE;
+            regenerate_paths<FORM>(pool, a, lane, P);
             if (P.have && state == S_IDLE) state = S_TRAV;
             if (state == S_TRAV && !walking) {  // start at the root: its own box first (the root is a node like any other, intersection.glsl:369-380)
                 closest = kInf;
@@ -251,6 +287,7 @@ __global__ __launch_bounds__(kBlock) void path_bvh4(const PathArgs a)
 
 // query_bvh2's walk — intersect_bvh as the reference writes it, over the binary nodes: pop a node, test its box against the interval of that moment, a leaf's
 // triangles in order, an inner node's right child stacked and its left child next — under the same loop.  One word per stack slot (the node index).
+template <int FORM>
 __global__ __launch_bounds__(kBlock) void path_bvh2(const PathArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
@@ -272,8 +309,8 @@ __global__ __launch_bounds__(kBlock) void path_bvh2(const PathArgs a)
 
     for (;;) {
         for (;;) {
-            if (state == S_HIT) state = finish_segment(a, shade_src, P, hit, closest) ? S_TRAV : S_IDLE;
-            regenerate_paths(pool, a, lane, P);
+            if (state == S_HIT) state = finish_segment<FORM>(a, shade_src, P, hit, closest) ? S_TRAV : S_IDLE;
+            regenerate_paths<FORM>(pool, a, lane, P);
             if (P.have && state == S_IDLE) state = S_TRAV;
             if (state == S_TRAV && !walking) {  // (the root's box is tested by the first step below, as every node's)
                 closest = kInf;
@@ -331,6 +368,7 @@ __global__ __launch_bounds__(kBlock) void path_bvh2(const PathArgs a)
 // triangles stream through LDS in tiles of kQueryTileTris, as query_brute streams them, and every lane that holds a path runs its current segment over each
 // tile in index order; then it shades.  The work-group leaves when a round starts with no path in any of its lanes.  No culls: the packet kernel's rest on a
 // camera and a block of pixels.
+template <int FORM>
 __global__ __launch_bounds__(kBlock) void path_brute(const PathArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float4 lds_tile[];
@@ -339,7 +377,7 @@ __global__ __launch_bounds__(kBlock) void path_brute(const PathArgs a)
     RunPool pool;
     PathLane P{};
     for (;;) {
-        regenerate_paths(pool, a, lane, P);
+        regenerate_paths<FORM>(pool, a, lane, P);
         if (__syncthreads_or(P.have ? 1 : 0) == 0) break;  // (also the barrier between the last round's tile reads and this round's tile stores)
         if (!P.have) P.L.d = mk(0.0f, 0.0f, 0.0f);  // a lane without a path runs along: every test of a zero direction is NaN and accepts nothing
         float closest = kInf;
@@ -352,15 +390,34 @@ __global__ __launch_bounds__(kBlock) void path_brute(const PathArgs a)
             __syncthreads();
             if (wave_has != 0) intersect_run<4>(reinterpret_cast<const v4f *>(lds_tile), base, count, P.L.o, P.L.d, closest, hit);
         }
-        if (P.have) (void)finish_segment(a, shade_src, P, hit, closest);
+        if (P.have) (void)finish_segment<FORM>(a, shade_src, P, hit, closest);
     }
 }
 
-hipError_t path_plan(const PathScene &scene, const uint32_t n, const int num_cus, QueryPlan *plan)
+namespace {
+
+template <int FORM>
+const void *path_kernel_of(const QueryKind kind)
 {
+    if (kind == QueryKind::Brute) return reinterpret_cast<const void *>(path_brute<FORM>);
+    return kind == QueryKind::Wide ? reinterpret_cast<const void *>(path_bvh4<FORM>) : reinterpret_cast<const void *>(path_bvh2<FORM>);
+}
+
+// The instance a launch runs: the lean one for integrator_Kajiya, a GENERIC one for the render modes 0 .. 8
+const void *path_kernel(const QueryKind kind, const uint32_t mode)
+{
+    if (mode == kPathModeKajiya) return path_kernel_of<LEAN>(kind);
+    return mode <= 4u ? path_kernel_of<HIT_ONLY>(kind) : path_kernel_of<CONTINUING>(kind);
+}
+
+}  // namespace
+
+hipError_t path_plan(const PathScene &scene, const uint32_t n, const int num_cus, const uint32_t mode, QueryPlan *plan)
+{
+    if (mode > kPathModeKajiya) return hipErrorInvalidValue;
     QueryPlan p{};
     const QueryKind kind = scene.walk.kind;
-    const void *kernel = reinterpret_cast<const void *>(path_brute);
+    const void *kernel = path_kernel(kind, mode);  // the occupancy is the launched instance's own
     uint32_t levels = 0;
     if (kind == QueryKind::Brute) {
         p.lds_bytes = static_cast<size_t>(kQueryTileTris) * 64u;
@@ -369,7 +426,6 @@ hipError_t path_plan(const PathScene &scene, const uint32_t n, const int num_cus
         p.lds_levels = std::min(levels, kQueryLdsLevels);
         p.top_nodes = kind == QueryKind::Wide ? std::min(scene.walk.n_wide, kQueryTopNodes) : 0u;
         p.lds_bytes = static_cast<size_t>(p.lds_levels) * kBlock * 2u * sizeof(uint32_t) + 2u * sizeof(float4) + static_cast<size_t>(p.top_nodes) * 128u;
-        kernel = kind == QueryKind::Wide ? reinterpret_cast<const void *>(path_bvh4) : reinterpret_cast<const void *>(path_bvh2);
     }
     int per_cu = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, p.lds_bytes);
@@ -384,8 +440,9 @@ hipError_t path_plan(const PathScene &scene, const uint32_t n, const int num_cus
     return hipSuccess;
 }
 
-hipError_t path_launch(hipStream_t stream, const PathScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, const uint32_t n)
+hipError_t path_launch(hipStream_t stream, const PathScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, const uint32_t n, const uint32_t mode)
 {
+    if (mode > kPathModeKajiya) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     PathArgs a{};
     a.prep = scene.walk.prep, a.nodes = scene.walk.nodes, a.wide = scene.walk.wide;
@@ -398,15 +455,11 @@ hipError_t path_launch(hipStream_t stream, const PathScene &scene, const QueryPl
     a.n_tris = scene.walk.n_tris, a.head_shift = scene.walk.head_shift;
     a.stack_levels = std::max<uint32_t>(1u, scene.walk.stack_levels);
     a.lds_levels = plan.lds_levels, a.top_nodes = plan.top_nodes;
+    a.mode = mode;
     const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    if (scene.walk.kind == QueryKind::Brute)
-        hipLaunchKernelGGL(path_brute, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
-    else if (scene.walk.kind == QueryKind::Wide)
-        hipLaunchKernelGGL(path_bvh4, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
-    else
-        hipLaunchKernelGGL(path_bvh2, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, a);
-    return hipGetLastError();
+    void *kernel_args[] = {&a};
+    return hipLaunchKernel(path_kernel(scene.walk.kind, mode), dim3(plan.grid), dim3(kBlock), kernel_args, plan.lds_bytes, stream);
 }
 
 }  // namespace rv

@@ -623,6 +623,19 @@ bool RVPT::trace_paths_device(void *records, size_t n)
     }
     return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_PATHS, records, n * sizeof(rvpt_ray_path)), "rvpt_hip_read");
 }
+bool RVPT::trace_paths(rvpt_ray_path *records, size_t n, int mode) { return trace_paths_device(records, n, mode); }  // (the library classifies the pointer)
+bool RVPT::trace_paths_device(void *records, size_t n, int mode)
+{
+    if (!ctx_) {
+        error_ = "trace_paths before initialize()";
+        return false;
+    }
+    if (mode < 0 || mode > 9) {
+        error_ = "trace_paths: mode " + std::to_string(mode) + " is outside 0 .. 9 (integrator_Hart is not part of the form)";
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_PATHS_MODE(mode), records, n * sizeof(rvpt_ray_path)), "rvpt_hip_read");
+}
 bool RVPT::closest_points(rvpt_point_hit *records, size_t n)
 {
     if (!ctx_) {

@@ -206,6 +206,11 @@ public:
     bool trace_paths(std::vector<rvpt_ray_path> &records);
     // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host
     bool trace_paths_device(void *records, size_t n);
+    // the same by another integrator (RVPT_HIP_FORMAT_RAY_PATHS_MODE(mode)): every record is evaluated by render mode 0 .. 9 of compute_pass.comp — binary, color,
+    // depth, normal, Utah, ambient occlusion, Appel, Whitted, Cook, Kajiya — with max_bounces as that integrator's render_settings.max_bounces; one mode per
+    // call.  Mode 9 returns the bytes of the overloads above.  Hart is not part of the form: a mode outside 0 .. 9 fails here, before any call.
+    bool trace_paths(rvpt_ray_path *records, size_t n, int mode);
+    bool trace_paths_device(void *records, size_t n, int mode);
     // Point queries (rvpt_hip_read with RVPT_HIP_FORMAT_NEAREST_POINTS; include/rvpt_hip.h: NEAREST POINTS): every record comes in as a point and a SQUARED
     // search bound (point, max_d2) and goes out as the nearest point of the mesh (closest, d2, prim, u, v, region), in place.  After initialize(); no update()
     // is needed.  prim numbers the triangles in the order they were ADDED, as trace_rays does (after a host build a tie between equal distances is broken on the

@@ -31,6 +31,17 @@ NO_PRIM = 0xFFFFFFFF  # a record's prim after a miss
 # rvpt_ray_hit (48 B): org, tmax, dir, flags come in, t, prim, u, v go out
 RAY_HIT_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("flags", "<u4"), ("t", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4")])
 FORMAT_RAY_PATHS = 3  # RVPT_HIP_FORMAT_RAY_PATHS: rvpt_hip_read answers path queries, `dst` holds RAY_PATH_DTYPE records (Context.trace_paths)
+PATH_MODE_KAJIYA = 9  # the render mode of integrator_Kajiya: format_ray_paths_mode(9) is FORMAT_RAY_PATHS' own kernels and bytes
+
+
+def format_ray_paths_mode(mode) -> int:
+    """RVPT_HIP_FORMAT_RAY_PATHS_MODE(mode): the format of a path query whose records are evaluated by the integrator of render mode 0 .. 9
+    (compute_pass.comp:76-95: binary, color, depth, normal, Utah, ambient occlusion, Appel, Whitted, Cook, Kajiya).  Any other mode — Hart is 10 — raises."""
+    if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)):
+        raise NativeError(ERR_INVALID, f"path query: mode {mode!r} is not an integer; render modes 0 .. 9 are built (Hart is not part of the form)")
+    if not 0 <= int(mode) <= PATH_MODE_KAJIYA:
+        raise NativeError(ERR_INVALID, f"path query: mode {int(mode)} is outside 0 .. 9; integrator_Hart and the modes that default to it are not part of the form")
+    return 16 + int(mode)
 PATH_MAX_BOUNCES = 1024  # RVPT_HIP_PATH_MAX_BOUNCES: a record with a larger bounce budget, or with none, is invalid (radiance 0, segments 0)
 # rvpt_ray_path (48 B): org, seed, dir, max_bounces come in, radiance and segments go out
 RAY_PATH_DTYPE = np.dtype([("org", "<f4", (3,)), ("seed", "<u4"), ("dir", "<f4", (3,)), ("max_bounces", "<u4"), ("radiance", "<f4", (3,)), ("segments", "<u4")])
@@ -674,7 +685,7 @@ class Context:
         """(pointer, bytes, object to keep alive) of a whole frame in a numpy array or a torch tensor — contiguous float32[h, w, 4] (FORMAT_RGBA32F) or
         uint8[h, w, 4] (FORMAT_RGBA8_UNORM); resolved the way _triangle_source resolves triangles: a tensor on this context's device is passed as device memory
         once the stream that last touched it has finished, and torch is imported only when a tensor is given.  Checked here, before the call."""
-        if fmt in (FORMAT_RAY_HITS, FORMAT_RAY_PATHS):  # known formats, but of records and not of a frame
+        if fmt in (FORMAT_RAY_HITS, FORMAT_RAY_PATHS) or (isinstance(fmt, int) and 16 <= fmt <= 16 + PATH_MODE_KAJIYA):  # known formats, but of records and not of a frame
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use trace_rays_into / trace_paths_into")
         if fmt not in (FORMAT_RGBA32F, FORMAT_RGBA8_UNORM):
             raise NativeError(ERR_INVALID, f"{what}: unknown format {fmt}")
@@ -756,10 +767,13 @@ class Context:
         _check(self._L.rvpt_hip_read(self._h, fmt, ptr, nbytes), self._h, self._L)
         return records
 
-    def trace_paths(self, org, dir, seed, max_bounces) -> np.ndarray:
+    def trace_paths(self, org, dir, seed, max_bounces, mode=PATH_MODE_KAJIYA) -> np.ndarray:
         """integrator_Kajiya's radiance along the rays org[n, 3] + t dir[n, 3] against the uploaded scene — include/rvpt_hip.h: PATH QUERIES.  seed (the RNG state
         a path starts from) and max_bounces (1 .. PATH_MAX_BOUNCES) are scalars or one value per ray.  Returns RAY_PATH_DTYPE[n]: radiance, and the segments the
-        path traced; both 0 for an invalid record."""
+        path traced; both 0 for an invalid record.  mode (0 .. 9, one for the whole call) names another integrator of compute_pass.comp for every record:
+        max_bounces is then what that integrator reads as render_settings.max_bounces (the occlusion samples of mode 5; modes 0-4 and 6 ignore it, but the
+        validity rule does not), and the segments count shadow and occlusion queries too.  A mode outside 0 .. 9 raises before any call."""
+        fmt = format_ray_paths_mode(mode)  # (before anything else: a refusal needs no arrays)
         org = np.asarray(org, dtype=np.float32).reshape(-1, 3)
         dirv = np.asarray(dir, dtype=np.float32).reshape(-1, 3)
         if org.shape != dirv.shape:
@@ -776,13 +790,17 @@ class Context:
         rec = np.zeros(n, dtype=RAY_PATH_DTYPE)
         rec["org"], rec["dir"] = org, dirv
         rec["seed"], rec["max_bounces"] = per_ray["seed"], per_ray["max_bounces"]
-        return self.trace_paths_into(rec)
+        return self.trace_paths_into(rec, mode=fmt - 16)
 
-    def trace_paths_into(self, records):
+    def trace_paths_into(self, records, mode=PATH_MODE_KAJIYA):
         """rvpt_hip_read with FORMAT_RAY_PATHS in the caller's memory: `records` is a contiguous RAY_PATH_DTYPE array, or a contiguous float32 torch tensor
         [n, 12] (48-byte records; seed, max_bounces and segments are the bits of their floats) on the host or on this context's device, as for trace_rays_into.
-        The in fields stay as they are, the out fields are written.  Returns records."""
-        return self._query_into(records, FORMAT_RAY_PATHS, RAY_PATH_DTYPE, "trace_paths_into", "RAY_PATH_DTYPE")
+        The in fields stay as they are, the out fields are written.  Returns records.  mode (0 .. 9) as for trace_paths: the call then goes out with
+        format_ray_paths_mode(mode); the default, 9, is FORMAT_RAY_PATHS itself."""
+        fmt = format_ray_paths_mode(mode)
+        if fmt == 16 + PATH_MODE_KAJIYA:
+            fmt = FORMAT_RAY_PATHS  # (the same kernels and bytes under either value: the form's first name is kept on the wire)
+        return self._query_into(records, fmt, RAY_PATH_DTYPE, "trace_paths_into", "RAY_PATH_DTYPE")
 
     def closest_points(self, points, max_dist=math.inf) -> np.ndarray:
         """The nearest point of the uploaded mesh to every point of points[n, 3] — include/rvpt_hip.h: NEAREST POINTS has the definition, the arithmetic and the

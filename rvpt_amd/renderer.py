@@ -31,6 +31,19 @@ def wang_hash(v) -> np.ndarray:
     return v
 
 
+# The render modes a path query takes by name: eval_integrator's case labels 0 .. 9 (compute_pass.comp:76-95).  Hart, its default branch, is not part of the form.
+PATH_MODE_NAMES = {"binary": 0, "color": 1, "depth": 2, "normal": 3, "utah": 4, "ao": 5, "appel": 6, "whitted": 7, "cook": 8, "kajiya": 9}
+
+
+def path_mode(mode) -> int:
+    """The render mode 0 .. 9 that `mode` — an int or a name of PATH_MODE_NAMES — stands for in RVPT.trace_paths; anything else raises native.NativeError."""
+    if isinstance(mode, str):
+        if mode not in PATH_MODE_NAMES:
+            raise native.NativeError(native.ERR_INVALID, f"path query: unknown mode name {mode!r}; the names are {', '.join(PATH_MODE_NAMES)} (Hart is not part of the form)")
+        return PATH_MODE_NAMES[mode]
+    return native.format_ray_paths_mode(mode) - native.format_ray_paths_mode(0)
+
+
 @dataclass
 class RenderSettings:
     """rvpt.h:77-89 (defaults included: current_frame starts at 1 and is reset by the first update())."""
@@ -426,11 +439,15 @@ class RVPT:
             rec["prim"][hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[rec["prim"][hit]]
         return rec
 
-    def trace_paths(self, org, dir, seed=None, max_bounces=None) -> np.ndarray:
+    def trace_paths(self, org, dir, seed=None, max_bounces=None, mode=None) -> np.ndarray:
         """Path queries against the scene as it is now (Context.trace_paths; include/rvpt_hip.h: PATH QUERIES): integrator_Kajiya's radiance along every ray
         org + t dir, as a frame's mode-9 pixel evaluates it for its camera ray.  seed (one RNG state per ray, or a scalar) defaults to what pixel i of a frame
         starts from before its two jitter values, wang_hash(i) + render_settings.current_frame; max_bounces to render_settings.max_bounces.  Returns
-        native.RAY_PATH_DTYPE records: radiance, and the segments the path traced.  Needs initialize(), not update(): a query has no camera."""
+        native.RAY_PATH_DTYPE records: radiance, and the segments the path traced.  Needs initialize(), not update(): a query has no camera.
+        mode — an int 0 .. 9 or a name of PATH_MODE_NAMES ("binary", "color", "depth", "normal", "utah", "ao", "appel", "whitted", "cook", "kajiya") — evaluates
+        every record by that integrator instead (one mode per call; max_bounces is then the integrator's render_settings.max_bounces: the occlusion samples of
+        "ao"); None is integrator_Kajiya, as before.  Hart is not part of the form: any other mode raises native.NativeError before any call."""
+        mode = native.PATH_MODE_KAJIYA if mode is None else path_mode(mode)
         if self._ctx is None:
             raise RuntimeError("trace_paths before initialize()")
         n = np.asarray(org, dtype=np.float32).reshape(-1, 3).shape[0]
@@ -438,7 +455,7 @@ class RVPT:
             seed = wang_hash(np.arange(n, dtype=np.uint32)) + np.uint32(self.render_settings.current_frame & 0xFFFFFFFF)
         if max_bounces is None:
             max_bounces = int(self.render_settings.max_bounces)
-        return self._ctx.trace_paths(org, dir, seed, max_bounces)
+        return self._ctx.trace_paths(org, dir, seed, max_bounces, mode=mode)
 
     def closest_points(self, points, max_dist=float("inf")) -> np.ndarray:
         """Point queries against the scene as it is now (Context.closest_points; include/rvpt_hip.h: NEAREST POINTS): the nearest point of the mesh to every

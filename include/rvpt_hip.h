@@ -76,7 +76,12 @@ extern "C" {
                                      POINT QUERY: `dst` holds rvpt_point_hit records, a point and a squared bound in, the nearest point of the mesh, its squared
                                      distance and its triangle out.  Still 8, no new symbol: rvpt_hip_read with a format RVPT_HIP_FORMAT_RAY_PATHS_MODE(mode)
                                      (16 .. 25) — until then the "unknown format" error — is a PATH QUERY BY INTEGRATOR: the records of format 3, each
-                                     evaluated by the render mode 0 .. 9 of compute_pass.comp the call names; mode 9 is format 3 itself */
+                                     evaluated by the render mode 0 .. 9 of compute_pass.comp the call names; mode 9 is format 3 itself.  Still 8, no new
+                                     symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_TRIANGLES (5) — until then the "unknown format" error — is the
+                                     TRIANGLE READ-BACK: `dst` receives the stored rvpt_triangle rows, as the last update form left them, in update order.
+                                     Still 8, no new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_SURFACE_POINTS (6) — until then the "unknown
+                                     format" error — is a SURFACE POINT read: `dst` holds rvpt_surface_point records, (prim, u, v) as a query reported them
+                                     in, the point of the stored mesh, its material word and its normal out */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -193,6 +198,16 @@ typedef struct rvpt_point_hit {
     float closest[3]; float d2;                            /* out: the nearest point of the mesh and its squared distance */
     uint32_t prim;    float u; float v; uint32_t region;   /* out: the triangle, the pair the region computed, 0 face, 1/2/3 vertex a/b/c, 4/5/6 edge ab/ac/bc */
 } rvpt_point_hit;
+
+#define RVPT_HIP_FORMAT_TRIANGLES 5      /* dst: rvpt_triangle[n_tris], out: the stored rows in update order (TRIANGLES at rvpt_hip_read) */
+#define RVPT_HIP_FORMAT_SURFACE_POINTS 6 /* dst: rvpt_surface_point[dst_bytes / 48], in and out (SURFACE POINTS at rvpt_hip_read) */
+
+/* One point on the stored mesh (48 B = three float4; no reference counterpart).  The first quad is laid out as the last quad of an rvpt_point_hit. */
+typedef struct rvpt_surface_point {
+    uint32_t prim; float u; float v; uint32_t flags;   /* in: a triangle in the queries' numbering, the pair a query reported; flags reserved, ignored */
+    float point[3];  uint32_t mat;                     /* out: (a + (b-a)*u) + (c-a)*v of the stored row, its material word */
+    float normal[3]; uint32_t reserved;                /* out: the stored unit normal; reserved is written 0 */
+} rvpt_surface_point;
 
 /* Image tiles are RVPT_HIP_TILE x RVPT_HIP_TILE pixels — the footprint of one reference
  * work-group (compute_pass.comp:27).  The tile at (tx, ty) of the tiles_x-wide tile grid has slot
@@ -668,7 +683,53 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  * - It implies rvpt_hip_wait and leaves untouched the accumulator, rvpt_hip_get_timing, rvpt_hip_get_stats, rvpt_hip_get_launch_info, rvpt_hip_get_cull_info,
  *   the frame counter, and rvpt_hip_last_error on success: a frame dispatched after a point query is bit for bit the frame dispatched without it.
  * - The answer is on the scene as the last update form left it: plain, guarded, sparse, pose or skin.
- * DESIGN.md 5.19 has the kernels and what was measured (profiles/nearest_points.txt). */
+ * DESIGN.md 5.19 has the kernels and what was measured (profiles/nearest_points.txt).
+ *
+ * TRIANGLES — the whole mesh as it now stands:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_TRIANGLES, dst, dst_bytes);
+ *
+ * `dst` receives n_tris rvpt_triangle rows (64 B each) in the UPDATE ORDER of this context — the order the plain update form takes: the leaf order after an
+ * ordinary upload, the caller's own order after a build form or a guarded rebuild.  Row perm[s] of the answer is stored row s.
+ * - THE BYTES ARE THE STORED BYTES, all 64 of a row: vert0..vert2 with their w lanes as the last form that wrote them left them, the mat_id row as the last
+ *   full upload or build left it.  Nothing is recomputed; a NaN payload in a w lane comes back as it went in.  After a pose or skin update these rows are the
+ *   only copy of the moved vertices there is.
+ * - ROUND TRIPS.  Passing the answer straight to the plain update form moves nothing.  After a build form, passing it with the stored materials to the same
+ *   build count on a fresh context gives the tree a guarded rebuild would give.
+ * - `dst` is host memory or device memory of the context's GPU, classified as for frames.  Device memory must be 16-byte aligned, else RVPT_HIP_ERR_INVALID;
+ *   another GPU's memory is RVPT_HIP_ERR_INVALID naming both devices.
+ * - dst_bytes < n_tris * 64 is RVPT_HIP_ERR_SIZE, and the message gives both numbers.  More is allowed: the bytes past n_tris * 64 are not touched.
+ * - Before any full upload the call is RVPT_HIP_ERR_INVALID.  The empty scene is a successful no-op, and `dst` may then be NULL.
+ * - In every error case `dst` is untouched.
+ * - The call is LOCAL: with a communicator it is not collective and touches no peer.
+ * - It implies rvpt_hip_wait, returns after the context's stream has finished writing, and leaves untouched the accumulator, rvpt_hip_get_timing,
+ *   rvpt_hip_get_stats, rvpt_hip_get_launch_info, rvpt_hip_get_cull_info, the frame counter, and rvpt_hip_last_error on success: a frame dispatched after the
+ *   read is bit for bit the frame dispatched without it.
+ *
+ * SURFACE POINTS — points on the stored mesh for the (prim, u, v) a query reported, in place:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_SURFACE_POINTS, records, n * sizeof(rvpt_surface_point));
+ *
+ * `dst` then holds n rvpt_surface_point records: each comes in as (prim, u, v) and goes out as (point, mat, normal, reserved = 0).  The in fields are never
+ * written; flags is reserved and ignored.
+ * - prim IS NUMBERED exactly as rvpt_ray_hit::prim and rvpt_point_hit::prim are.  The last float4 of an rvpt_point_hit is already a valid in-quad.
+ * - CONVENTION.  u weights vert1 - vert0 and v weights vert2 - vert0: what both query forms report.
+ * - ARITHMETIC.  binary32, every operation rounded on its own, no FMA.  a, b, c = vert0..2 of the stored row:
+ *     ab = b - a, ac = c - a, point = (a + ab*u) + ac*v per component.
+ *   This is the nearest form's q before its clamp: for an rvpt_point_hit the answer equals `closest` wherever the clamp did nothing.  For a ray hit it is NOT
+ *   org + t*dir: it is the point of the stored triangle at the reported pair, which differs from the ray's own point by rounding.  (u, v) need not lie in the
+ *   triangle: any finite pair is evaluated.
+ * - normal is the 12 bytes stored for the hit normal when the row was last written: normalize(cross(vert1 - vert0, vert2 - vert0)) by the cross, dot and
+ *   normalize of the frame kernels (the normal intersect_scene normalises, intersection.glsl:511-513), NOT turned towards any ray.  A zero-area triangle gets
+ *   what that arithmetic gives.
+ * - mat is the stored material index word of the row.
+ * - INVALID RECORDS are prim >= n_tris (so 0xFFFFFFFF, a miss piped through, is invalid) or a non-finite u or v.  They go out as point = normal = 0,
+ *   mat = 0xFFFFFFFF, reserved = 0.  On the empty scene every record is invalid.
+ * - Sizes, alignment, classification, staging, locality, rvpt_hip_wait and what is left alone are a ray query's: dst_bytes a multiple of 48, 0 being a
+ *   successful no-op; fewer than 2^32 records per call; device records 16-byte aligned; before any full upload RVPT_HIP_ERR_INVALID; in every error case `dst`
+ *   is untouched; for host records only the out fields — the last 32 bytes of a record — travel back.
+ * - The answer is on the scene as the last update form left it: a record kept from frame to frame stays attached to the posed or skinned surface.
+ * DESIGN.md 5.22 has the kernels and what was measured. */
 int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes);
 
 /* ---- multi-GPU: one RCCL communicator over the tile_world ranks of a partitioned image (no reference counterpart: the

@@ -17,7 +17,8 @@ SOURCES.append(_PKG / "csrc" / "rvpt_frames.hip")  # rvpt_hip_read / write_accum
 SOURCES.append(_PKG / "csrc" / "rvpt_query.hip")  # ray queries (rvpt_hip_read with FORMAT_RAY_HITS): the walks without the path tracer, no frame kernels, likewise
 SOURCES.append(_PKG / "csrc" / "rvpt_paths.hip")  # path queries (rvpt_hip_read with FORMAT_RAY_PATHS and FORMAT_RAY_PATHS_MODE): those walks under shade() / shade_generic(), kernels of their own, likewise
 SOURCES.append(_PKG / "csrc" / "rvpt_nearest.hip")  # point queries (rvpt_hip_read with FORMAT_NEAREST_POINTS): a walk that prunes by distance, kernels of its own, likewise
-HEADERS = [_PKG / "csrc" / "rvpt_nearest.h", _PKG / "csrc" / "rvpt_paths.h", _PKG / "csrc" / "rvpt_query.h", _PKG / "csrc" / "rvpt_frames.h", _PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
+SOURCES.append(_PKG / "csrc" / "rvpt_surface.hip")  # the geometry read-back (rvpt_hip_read with FORMAT_TRIANGLES and FORMAT_SURFACE_POINTS): one record kernel, the row scatter launched from there, likewise
+HEADERS = [_PKG / "csrc" / "rvpt_surface.h", _PKG / "csrc" / "rvpt_nearest.h", _PKG / "csrc" / "rvpt_paths.h", _PKG / "csrc" / "rvpt_query.h", _PKG / "csrc" / "rvpt_frames.h", _PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
            _PKG / "csrc" / "rvpt_vis.h", _PKG.parent / "include" / "rvpt_hip.h", _PKG.parent / "include" / "rvpt_hip_lab.h"]
 
 # -ffp-contract=off: the arithmetic specification fixes where FMAs happen; applies to the
@@ -137,8 +138,9 @@ HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selft
                 "host_selftest_paths": ["host_selftest_paths.cpp", "rvpt_host.cpp"],
                 "host_selftest_path_modes": ["host_selftest_path_modes.cpp", "rvpt_host.cpp"],
                 "host_selftest_nearest": ["host_selftest_nearest.cpp", "rvpt_host.cpp"],
+                "host_selftest_surface": ["host_selftest_surface.cpp", "rvpt_host.cpp"],
                 "host_row_boxes": ["host_row_boxes.cpp"]}  # (rvpt_vis.h alone: the row boxes' table for scenes given in files, tests/test_row_boxes.py)
-HOST_NEEDS_HIP = {"host_selftest_frames", "host_selftest_rays", "host_selftest_paths", "host_selftest_path_modes", "host_selftest_nearest"}  # targets that allocate device memory themselves (its `--gpu` case): HIP's host API, still compiled by g++
+HOST_NEEDS_HIP = {"host_selftest_frames", "host_selftest_rays", "host_selftest_paths", "host_selftest_path_modes", "host_selftest_nearest", "host_selftest_surface"}  # targets that allocate device memory themselves (its `--gpu` case): HIP's host API, still compiled by g++
 
 
 HOST_WITH_HIPCC = {"host_row_boxes"}  # targets that include the kernels' host + device headers (csrc/): the host half of a HIP compilation, no device code, no library
@@ -156,7 +158,7 @@ def _hip_host_flags() -> list:
 
 def build_host(force: bool = False) -> Path:
     """Compile the C++ host layer (rvpt_amd/host/: the mirror of the reference's class RVPT above the C ABI) with
-    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames`, `host_selftest_guard`, `host_selftest_sparse`, `host_selftest_pose`, `host_selftest_pose_guard`, `host_selftest_skin`, `host_selftest_rays`, `host_selftest_paths`, `host_selftest_path_modes` and `host_selftest_nearest`."""
+    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames`, `host_selftest_guard`, `host_selftest_sparse`, `host_selftest_pose`, `host_selftest_pose_guard`, `host_selftest_skin`, `host_selftest_rays`, `host_selftest_paths`, `host_selftest_path_modes`, `host_selftest_nearest` and `host_selftest_surface`."""
     build_native()
     HOST_BIN_DIR.mkdir(exist_ok=True)
     srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h", _PKG / "csrc" / "rvpt_vis.h"]

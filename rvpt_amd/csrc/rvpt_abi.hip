@@ -32,6 +32,7 @@
 #include "rvpt_build.h"
 #include "rvpt_query.h"
 #include "rvpt_nearest.h"
+#include "rvpt_surface.h"
 #include "rvpt_paths.h"
 #include "rvpt_packets.h"
 #include "rvpt_math.h"
@@ -78,6 +79,11 @@ static_assert(sizeof(rvpt_point_hit) == rv::kNearestRecordBytes && sizeof(rvpt_p
                   offsetof(rvpt_point_hit, closest) == 16 && offsetof(rvpt_point_hit, d2) == 28 && offsetof(rvpt_point_hit, prim) == 32 && offsetof(rvpt_point_hit, u) == 36 &&
                   offsetof(rvpt_point_hit, v) == 40 && offsetof(rvpt_point_hit, region) == 44,
               "a point query's record: three float4 (rvpt_nearest.hip), and it shares query_records");
+static_assert(sizeof(rvpt_surface_point) == rv::kSurfaceRecordBytes && sizeof(rvpt_surface_point) == sizeof(rvpt_ray_hit) && offsetof(rvpt_surface_point, u) == 4 &&
+                  offsetof(rvpt_surface_point, v) == 8 && offsetof(rvpt_surface_point, flags) == 12 && offsetof(rvpt_surface_point, point) == 16 &&
+                  offsetof(rvpt_surface_point, mat) == 28 && offsetof(rvpt_surface_point, normal) == 32 && offsetof(rvpt_surface_point, reserved) == 44 &&
+                  offsetof(rvpt_point_hit, prim) == 32 && offsetof(rvpt_point_hit, u) == 36 && offsetof(rvpt_point_hit, v) == 40 && sizeof(rvpt_triangle) == 64,
+              "a surface record: three float4 (rvpt_surface.hip), its in-quad laid out as the last quad of an rvpt_point_hit, and it shares query_records");
 static_assert(offsetof(rvpt_triangle, mat_id) == 48 && offsetof(rvpt_bvh_node, bounds) == 8 &&
                   offsetof(rvpt_material, data) == 32 && offsetof(rvpt_render_settings, split_ratio) == 32 &&
                   offsetof(rvpt_camera_data, params) == 64,
@@ -188,11 +194,18 @@ struct rvpt_hip_ctx {
     uint32_t skin_bones = 0;
     bool have_scene = false;
     // RAY, PATH and POINT QUERIES (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_HITS / RVPT_HIP_FORMAT_RAY_PATHS / RVPT_HIP_FORMAT_NEAREST_POINTS; rvpt_query.h, rvpt_paths.h, rvpt_nearest.h): the staging buffer of host records (bytes) and the launch's scratch — 64 words whose
-    // first is the claim counter, then the global part of the traversal stack (words).  Both only grow.
+    // first is the claim counter, then the global part of the traversal stack (words).  Both only grow.  A SURFACE POINTS read stages its host records there
+    // too, and a TRIANGLES read into host memory on a context with a permutation scatters its rows into the staging buffer (rvpt_surface.h).
     unsigned char *d_query_stage = nullptr;
     size_t cap_query_stage = 0;
     uint32_t *d_query_scratch = nullptr;
     size_t cap_query_scratch = 0;
+    // SURFACE POINTS (rvpt_hip_read with RVPT_HIP_FORMAT_SURFACE_POINTS; rvpt_surface.h): the inverse of d_perm once more, the read side's own — the sparse
+    // update's d_inv_perm and its flag belong to the update forms and to the laboratory read-back, which a read must leave as it found them.
+    // have_surface_inv: made for the d_perm of now, dropped wherever have_inv_perm is (every full upload, build and rebuild).
+    uint32_t *d_surface_inv = nullptr;
+    size_t cap_surface_inv = 0;
+    bool have_surface_inv = false;
 
     rvpt_render_settings settings{};
     rvpt_camera_data camera{};
@@ -1046,7 +1059,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     void *bufs[] = {ctx->d_tris, ctx->d_prep, ctx->d_mats, ctx->d_nodes, ctx->d_wide, ctx->d_wide_map, ctx->d_mat_index, ctx->d_unit_n, ctx->d_accum,
                     ctx->d_rowmajor, ctx->d_counter, ctx->d_stats, ctx->d_perm, ctx->d_build, ctx->d_build_temp, ctx->d_build_counters, ctx->d_cost, ctx->d_carry,
                     ctx->d_sparse_parent, ctx->d_sparse_leaf_of, ctx->d_sparse_dirty, ctx->d_sparse_claim, ctx->d_inv_perm, ctx->d_sparse_words, ctx->d_sparse_stage,
-                    ctx->d_query_stage, ctx->d_query_scratch, ctx->d_rest, ctx->d_rest_carry, ctx->d_skin, ctx->d_skin_words, ctx->d_bones};
+                    ctx->d_query_stage, ctx->d_query_scratch, ctx->d_surface_inv, ctx->d_rest, ctx->d_rest_carry, ctx->d_skin, ctx->d_skin_words, ctx->d_bones};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1284,7 +1297,7 @@ static int build_scene_on_device(rvpt_hip_ctx *ctx, const rvpt_triangle *tris, s
     uint32_t *flags = reinterpret_cast<uint32_t *>(base + 24u * static_cast<size_t>(n)), *flags_next = reinterpret_cast<uint32_t *>(base + 24u * static_cast<size_t>(n) + words);
     uint32_t *const offs = reinterpret_cast<uint32_t *>(base + 24u * static_cast<size_t>(n) + 2u * words);
     ctx->have_scene = false;  // from here on the stored scene is being replaced: an error below leaves none
-    ctx->have_sparse_maps = ctx->have_inv_perm = false;  // ... and with it the topology and the permutation the sparse update's maps were made for
+    ctx->have_sparse_maps = ctx->have_inv_perm = ctx->have_surface_inv = false;  // ... and with it the topology and the permutation the sparse update's maps were made for
     if (n_mats) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mats, mats, n_mats * sizeof(rvpt_material), hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(rv::prepare_materials, dim3((static_cast<uint32_t>(n_mats) + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_mats, static_cast<uint32_t>(n_mats));
@@ -2185,7 +2198,7 @@ static int upload_scene_other_forms(rvpt_hip_ctx *ctx, const rvpt_bvh_node *node
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc0 = sync_all(ctx)) return rc0;  // frames in flight still read the old scene
     int rc;
-    ctx->have_sparse_maps = ctx->have_inv_perm = false;  // the topology the sparse update's maps were made for is being replaced
+    ctx->have_sparse_maps = ctx->have_inv_perm = ctx->have_surface_inv = false;  // the topology the sparse update's maps were made for is being replaced
     if ((rc = grow(ctx, ctx->d_tris, ctx->cap_tris, n_tris, sizeof(rvpt_triangle)))) return rc;
     if ((rc = grow(ctx, ctx->d_prep, ctx->cap_prep, n_tris, sizeof(rvpt_triangle)))) return rc;
     if ((rc = grow(ctx, ctx->d_mat_index, ctx->cap_mat_index, n_tris, sizeof(uint32_t)))) return rc;
@@ -2860,18 +2873,20 @@ int rvpt_hip_gather(rvpt_hip_ctx *ctx, void *dst_dev_rgba32f)
     return gather_to_root(ctx, static_cast<float4 *>(dst_dev_rgba32f));
 }
 
-// rvpt_hip_read with a format of records, by `kind`: RVPT_HIP_FORMAT_RAY_HITS (include/rvpt_hip.h: RAY QUERIES), RVPT_HIP_FORMAT_RAY_PATHS (PATH QUERIES) or
-// RVPT_HIP_FORMAT_NEAREST_POINTS (NEAREST POINTS).  `dst` holds dst_bytes / 48 records: rays in and hits — radiance — out, or points in and nearest points out.
+// rvpt_hip_read with a format of records, by `kind`: RVPT_HIP_FORMAT_RAY_HITS (include/rvpt_hip.h: RAY QUERIES), RVPT_HIP_FORMAT_RAY_PATHS (PATH QUERIES),
+// RVPT_HIP_FORMAT_NEAREST_POINTS (NEAREST POINTS) or RVPT_HIP_FORMAT_SURFACE_POINTS (SURFACE POINTS).  `dst` holds dst_bytes / 48 records: rays in and hits —
+// radiance — out, points in and nearest points out, or (prim, u, v) in and the point, material and normal of the stored mesh out.
 // The forms share everything but the kernels and the first out byte: the checks, the pointer's classification, the staging of host records (only a record's
 // out fields travel back: its third float4, for a point query its second and third).  LOCAL: no communicator is touched.  Everything is checked before
 // anything is written; on success ctx->err stays as it was.  No event is recorded: RVPT_HIP_TIMING does not see a query.
 // `path_mode` (RecordKind::Paths only): the integrator of the call, 0 .. 9 — RVPT_HIP_FORMAT_RAY_PATHS is mode 9, RVPT_HIP_FORMAT_RAY_PATHS_MODE(m) is mode m.
-enum class RecordKind { Rays, Paths, Points };
+enum class RecordKind { Rays, Paths, Points, Surface };
 static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const RecordKind kind, const uint32_t path_mode = rv::kPathModeKajiya)
 {
-    const bool paths = kind == RecordKind::Paths, points = kind == RecordKind::Points;
-    const char *what = points ? "point" : (paths ? "path" : "ray"), *record = points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : "rvpt_ray_hit");
-    const size_t out_offset = points ? offsetof(rvpt_point_hit, closest) : offsetof(rvpt_ray_hit, t);  // where a record's out fields begin
+    const bool paths = kind == RecordKind::Paths, points = kind == RecordKind::Points, surface = kind == RecordKind::Surface;
+    const char *what = surface ? "surface" : (points ? "point" : (paths ? "path" : "ray"));
+    const char *record = surface ? "rvpt_surface_point" : (points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : "rvpt_ray_hit"));
+    const size_t out_offset = surface ? offsetof(rvpt_surface_point, point) : (points ? offsetof(rvpt_point_hit, closest) : offsetof(rvpt_ray_hit, t));  // where a record's out fields begin
     if (dst_bytes % sizeof(rvpt_ray_hit))
         return fail(ctx, RVPT_HIP_ERR_INVALID, "%s query: dst_bytes %zu is not a multiple of the %zu bytes of a %s", what, dst_bytes, sizeof(rvpt_ray_hit), record);
     if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "%s query before any full upload_scene on this context: there is no scene to ask", what);
@@ -2903,7 +2918,7 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
         HIP_TRY(ctx, rv::nearest_plan(nearest, static_cast<uint32_t>(n), ctx->num_cus, &plan));
     else if (paths)
         HIP_TRY(ctx, rv::path_plan(path_scene, static_cast<uint32_t>(n), ctx->num_cus, path_mode, &plan));
-    else
+    else if (!surface)  // (a surface read is one record per lane and no walk: no plan, no stack)
         HIP_TRY(ctx, rv::query_plan(scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
     if (int rc = rvpt_hip_wait(ctx)) return rc;  // every read implies it; frames in flight still read the scene, and the buffers below may be regrown
     if (int rc = grow(ctx, ctx->d_query_scratch, ctx->cap_query_scratch, 64u + plan.stack_words, sizeof(uint32_t))) return rc;
@@ -2913,7 +2928,22 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
         records = ctx->d_query_stage;
         HIP_TRY(ctx, hipMemcpyAsync(records, dst, dst_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    if (points)
+    if (surface) {
+        // caller's index -> stored row on a context with a permutation: an inverse of the read side's own, under its own flag (d_inv_perm and have_inv_perm
+        // are the update forms', and the laboratory read-back shows them)
+        const bool permuted = ctx->have_perm && ctx->n_tris > 0;
+        if (permuted && !ctx->have_surface_inv) {
+            if (int rc = grow(ctx, ctx->d_surface_inv, ctx->cap_surface_inv, ctx->n_tris, sizeof(uint32_t))) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_surface_inv, 0xFF, ctx->n_tris * sizeof(uint32_t), ctx->stream));
+            hipLaunchKernelGGL(rv::sparse_invert_permutation, dim3((scene.n_tris + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_perm, scene.n_tris, ctx->d_surface_inv);
+            HIP_TRY(ctx, hipGetLastError());
+            ctx->have_surface_inv = true;
+        }
+        rv::SurfaceScene mesh{};
+        mesh.tris = ctx->d_tris, mesh.unit_n = ctx->d_unit_n, mesh.mat_index = ctx->d_mat_index;
+        mesh.inv_perm = permuted ? ctx->d_surface_inv : nullptr, mesh.n_tris = scene.n_tris;
+        HIP_TRY(ctx, rv::surface_launch(ctx->stream, mesh, records, static_cast<uint32_t>(n)));
+    } else if (points)
         HIP_TRY(ctx, rv::nearest_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
     else if (paths)
         HIP_TRY(ctx, rv::path_launch(ctx->stream, path_scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n), path_mode));
@@ -2926,11 +2956,43 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
     return RVPT_HIP_OK;
 }
 
+// rvpt_hip_read with RVPT_HIP_FORMAT_TRIANGLES (include/rvpt_hip.h: TRIANGLES): the stored rows of d_tris, all 64 bytes of each, in the update order of the
+// context — d_tris itself without a permutation (one copy), the row scatter out[perm[s]] = tris[s] with one (straight into a device `dst`; for a host `dst`
+// into the queries' staging buffer, then one copy).  Nothing is recomputed.  LOCAL.  Everything is checked before anything is written; on success ctx->err
+// stays as it was.
+static int read_triangles(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes)
+{
+    if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "triangle read before any full upload_scene on this context: there is no scene to read");
+    const size_t need = ctx->n_tris * sizeof(rvpt_triangle);
+    if (need == 0) return RVPT_HIP_OK;  // the empty scene: nothing to write, dst may be NULL
+    if (!dst) return fail(ctx, RVPT_HIP_ERR_INVALID, "dst is NULL");
+    if (dst_bytes < need) return fail(ctx, RVPT_HIP_ERR_SIZE, "dst holds %zu bytes, the %zu stored triangles need %zu", dst_bytes, ctx->n_tris, need);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    bool device_dst = false;
+    if (int rc = classify_frame_pointer(ctx, dst, "dst", &device_dst)) return rc;
+    if (device_dst && reinterpret_cast<uintptr_t>(dst) % 16u)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "dst is device memory at %p: triangle rows on the device need 16-byte alignment", dst);
+    if (int rc = rvpt_hip_wait(ctx)) return rc;  // every read implies it; the staging buffer below may be regrown
+    if (!ctx->have_perm) {
+        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->d_tris, need, device_dst ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    } else if (device_dst) {
+        HIP_TRY(ctx, rv::surface_scatter_rows(ctx->stream, ctx->d_tris, ctx->d_perm, static_cast<uint32_t>(ctx->n_tris), dst));
+    } else {
+        if (int rc = grow(ctx, ctx->d_query_stage, ctx->cap_query_stage, need, 1)) return rc;
+        HIP_TRY(ctx, rv::surface_scatter_rows(ctx->stream, ctx->d_tris, ctx->d_perm, static_cast<uint32_t>(ctx->n_tris), ctx->d_query_stage));
+        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->d_query_stage, need, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a device dst: the caller may read it from any stream of its own on return
+    return RVPT_HIP_OK;
+}
+
 int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
 {
     if (!ctx) return fail(nullptr, RVPT_HIP_ERR_INVALID, "ctx is NULL");
     if (format >= RVPT_HIP_FORMAT_RAY_PATHS_MODE(0) && format <= RVPT_HIP_FORMAT_RAY_PATHS_MODE(9))  // a path query by integrator (mode 9 is RVPT_HIP_FORMAT_RAY_PATHS itself); local as well
         return query_records(ctx, dst, dst_bytes, RecordKind::Paths, static_cast<uint32_t>(format - RVPT_HIP_FORMAT_RAY_PATHS_MODE(0)));
+    if (format == RVPT_HIP_FORMAT_TRIANGLES) return read_triangles(ctx, dst, dst_bytes);  // local as well
+    if (format == RVPT_HIP_FORMAT_SURFACE_POINTS) return query_records(ctx, dst, dst_bytes, RecordKind::Surface);
     if (format == RVPT_HIP_FORMAT_RAY_HITS || format == RVPT_HIP_FORMAT_RAY_PATHS || format == RVPT_HIP_FORMAT_NEAREST_POINTS)  // local even with a communicator: every rank holds the whole scene
         return query_records(ctx, dst, dst_bytes,
                              format == RVPT_HIP_FORMAT_NEAREST_POINTS ? RecordKind::Points : (format == RVPT_HIP_FORMAT_RAY_PATHS ? RecordKind::Paths : RecordKind::Rays));

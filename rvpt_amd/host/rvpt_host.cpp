@@ -656,6 +656,60 @@ bool RVPT::closest_points_device(void *records, size_t n)
     }
     return check(backend_.read(ctx_, RVPT_HIP_FORMAT_NEAREST_POINTS, records, n * sizeof(rvpt_point_hit)), "rvpt_hip_read");
 }
+bool RVPT::read_triangles(std::vector<rvpt_triangle> &triangles)
+{
+    if (!ctx_) {
+        error_ = "read_triangles before initialize()";
+        return false;
+    }
+    const size_t n = triangles_.size();
+    std::vector<rvpt_triangle> stored(n);
+    if (!check(backend_.read(ctx_, RVPT_HIP_FORMAT_TRIANGLES, n ? stored.data() : nullptr, n * sizeof(rvpt_triangle)), "rvpt_hip_read")) return false;
+    if (device_built_ || order_.size() != n) {  // the update order is the added order
+        triangles.swap(stored);
+        return true;
+    }
+    triangles.resize(n);
+    for (size_t i = 0; i < n; ++i) triangles[order_[i]] = stored[i];  // the library holds the leaf order it was given
+    return true;
+}
+bool RVPT::read_triangles_device(void *dst, size_t dst_bytes)
+{
+    if (!ctx_) {
+        error_ = "read_triangles_device before initialize()";
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_TRIANGLES, dst, dst_bytes), "rvpt_hip_read");
+}
+bool RVPT::surface_points(rvpt_surface_point *records, size_t n)
+{
+    if (!ctx_) {
+        error_ = "surface_points before initialize()";
+        return false;
+    }
+    if (device_built_) return check(backend_.read(ctx_, RVPT_HIP_FORMAT_SURFACE_POINTS, records, n * sizeof(rvpt_surface_point)), "rvpt_hip_read");
+    // the library numbers the leaf order it was given: the added numbers go down through the inverse of the build's order and come back as given
+    if (inverse_.size() != order_.size()) {
+        inverse_.resize(order_.size());
+        for (size_t i = 0; i < order_.size(); ++i) inverse_[order_[i]] = static_cast<uint32_t>(i);
+    }
+    std::vector<uint32_t> given(n);
+    for (size_t k = 0; k < n; ++k) {
+        given[k] = records[k].prim;
+        records[k].prim = given[k] < inverse_.size() ? inverse_[given[k]] : 0xFFFFFFFFu;
+    }
+    const bool ok = check(backend_.read(ctx_, RVPT_HIP_FORMAT_SURFACE_POINTS, records, n * sizeof(rvpt_surface_point)), "rvpt_hip_read");
+    for (size_t k = 0; k < n; ++k) records[k].prim = given[k];
+    return ok;
+}
+bool RVPT::surface_points_device(void *records, size_t n)
+{
+    if (!ctx_) {
+        error_ = "surface_points_device before initialize()";
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_SURFACE_POINTS, records, n * sizeof(rvpt_surface_point)), "rvpt_hip_read");
+}
 
 // ---- main.cpp:12-62 ---------------------------------------------------------------------------------------
 long load_model(RVPT &rvpt, const std::string &path, int material_id, std::string *error)

@@ -218,6 +218,19 @@ public:
     bool closest_points(rvpt_point_hit *records, size_t n);
     // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host: prim then stays as the LIBRARY numbers it
     bool closest_points_device(void *records, size_t n);
+    // The geometry read-back (rvpt_hip_read with RVPT_HIP_FORMAT_TRIANGLES; include/rvpt_hip.h: TRIANGLES): the stored rows of the mesh as the last update,
+    // pose or skin form left them — all 64 bytes of each, nothing recomputed — in the order the triangles were ADDED (after a host build the leaf order the
+    // library holds is undone here).  After initialize(); no update() is needed.
+    bool read_triangles(std::vector<rvpt_triangle> &triangles);
+    // the same into device memory of the context's GPU (16-byte aligned, dst_bytes >= 64 x triangles), in the order the LIBRARY's update form takes: the
+    // leaf order after a host build (sorted_triangles()), the added order after a device build
+    bool read_triangles_device(void *dst, size_t dst_bytes);
+    // Surface points (RVPT_HIP_FORMAT_SURFACE_POINTS; include/rvpt_hip.h: SURFACE POINTS): every record comes in as (prim, u, v) — prim numbering the
+    // triangles in the order they were ADDED, as trace_rays and closest_points report it — and goes out as the point (a + (b-a)*u) + (c-a)*v of the mesh
+    // as it now stands, its material word and its stored unit normal, in place; prim stays as given.
+    bool surface_points(rvpt_surface_point *records, size_t n);
+    // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host: prim is then as the LIBRARY numbers it
+    bool surface_points_device(void *records, size_t n);
     const std::string &last_error() const { return error_; }
     // the backend context, e.g. to join several RVPT objects (one per GPU, tile_rank i of n) into one RCCL group with
     // rvpt_hip_comm_init_all; read_frame() on rank 0's object is then the gather of the whole image

@@ -48,6 +48,10 @@ RAY_PATH_DTYPE = np.dtype([("org", "<f4", (3,)), ("seed", "<u4"), ("dir", "<f4",
 FORMAT_NEAREST_POINTS = 4  # RVPT_HIP_FORMAT_NEAREST_POINTS: rvpt_hip_read answers point queries, `dst` holds POINT_HIT_DTYPE records (Context.closest_points)
 # rvpt_point_hit: 48 bytes, three float4 — a point and a SQUARED bound in; the nearest point of the mesh, its squared distance, the triangle, u, v and the region out
 POINT_HIT_DTYPE = np.dtype([("point", "<f4", (3,)), ("max_d2", "<f4"), ("closest", "<f4", (3,)), ("d2", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("region", "<u4")])
+FORMAT_TRIANGLES = 5  # RVPT_HIP_FORMAT_TRIANGLES: rvpt_hip_read returns the stored rvpt_triangle rows in update order (Context.read_triangles)
+FORMAT_SURFACE_POINTS = 6  # RVPT_HIP_FORMAT_SURFACE_POINTS: rvpt_hip_read answers surface records, `dst` holds SURFACE_POINT_DTYPE records (Context.surface_points)
+# rvpt_surface_point: 48 bytes, three float4 — prim, u, v as a query reported them (and a reserved word) in; the point of the stored mesh, its material word, its normal out
+SURFACE_POINT_DTYPE = np.dtype([("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("mat", "<u4"), ("normal", "<f4", (3,)), ("reserved", "<u4")])
 CULL_ROW_BOXES = 0x100  # Context.cull_info: the launch rode with the row boxes (rvpt_abi.hip: kCullRowBoxes)
 CULL_SKY_LIST = 0x80  # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
 TILE = 16
@@ -687,6 +691,10 @@ class Context:
         once the stream that last touched it has finished, and torch is imported only when a tensor is given.  Checked here, before the call."""
         if fmt in (FORMAT_RAY_HITS, FORMAT_RAY_PATHS) or (isinstance(fmt, int) and 16 <= fmt <= 16 + PATH_MODE_KAJIYA):  # known formats, but of records and not of a frame
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use trace_rays_into / trace_paths_into")
+        if fmt == FORMAT_TRIANGLES:
+            raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds the stored triangle rows, not a frame: use read_triangles / read_triangles_into")
+        if fmt == FORMAT_SURFACE_POINTS:
+            raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds surface records, not a frame: use surface_points / surface_points_into")
         if fmt not in (FORMAT_RGBA32F, FORMAT_RGBA8_UNORM):
             raise NativeError(ERR_INVALID, f"{what}: unknown format {fmt}")
         name, size = ("float32", 4) if fmt == FORMAT_RGBA32F else ("uint8", 1)
@@ -826,6 +834,65 @@ class Context:
         [n, 12] (48-byte records; prim and region are the bits of their floats) on the host or on this context's device, as for trace_rays_into.  The in fields
         (point, max_d2 — a SQUARED distance) stay as they are, the out fields are written.  Returns records."""
         return self._query_into(records, FORMAT_NEAREST_POINTS, POINT_HIT_DTYPE, "closest_points_into", "POINT_HIT_DTYPE")
+
+    def read_triangles(self) -> np.ndarray:
+        """rvpt_hip_read with FORMAT_TRIANGLES: the stored triangle rows as the last update form left them — all 64 bytes of each, nothing recomputed — as
+        float32[n, 16] in the order update_triangles takes on this context (the leaf order after upload_scene, the caller's own after build_scene or a guarded
+        rebuild).  include/rvpt_hip.h: TRIANGLES."""
+        if self._scene_tris is None:
+            _check(self._L.rvpt_hip_read(self._h, FORMAT_TRIANGLES, None, 0), self._h, self._L)  # (the library's own refusal: no scene)
+        out = np.empty((int(self._scene_tris or 0), 16), dtype=np.float32)
+        _check(self._L.rvpt_hip_read(self._h, FORMAT_TRIANGLES, _ptr(out) if out.size else None, out.nbytes), self._h, self._L)
+        return out
+
+    def read_triangles_into(self, dst):
+        """read_triangles into the caller's memory: `dst` is a contiguous float32[n, 16] numpy array, or a contiguous float32 torch tensor [n, 16] on the host or
+        on this context's device — the rows then never visit the host.  More rows than the scene holds are allowed; those past the scene's are not touched.
+        On return the library's stream has finished writing.  Returns dst."""
+        is_tensor = not isinstance(dst, np.ndarray) and hasattr(dst, "data_ptr")
+        if is_tensor:
+            import torch
+            if dst.dtype != torch.float32 or dst.dim() != 2 or dst.shape[1] != 16 or not dst.is_contiguous():
+                raise NativeError(ERR_INVALID, f"read_triangles_into: a contiguous float32 tensor [n, 16] is needed, got {dst.dtype} {tuple(dst.shape)}")
+            nbytes = int(dst.shape[0]) * 64
+            if dst.is_cuda:
+                if dst.device.index != self.device:
+                    raise NativeError(ERR_INVALID, f"read_triangles_into: the tensor lives on device {dst.device.index}, the context on {self.device}")
+                torch.cuda.current_stream(dst.device).synchronize()  # the library works on its own stream: what touched the tensor last must have finished
+                ptr = C.c_void_p(dst.data_ptr())
+            else:
+                ptr = _ptr(dst.numpy())  # (shares the tensor's memory)
+        elif isinstance(dst, np.ndarray):
+            if dst.dtype != np.float32 or dst.ndim != 2 or dst.shape[1] != 16 or not dst.flags.c_contiguous or not dst.flags.writeable:
+                raise NativeError(ERR_INVALID, f"read_triangles_into: a contiguous writeable float32[n, 16] array is needed, got {dst.dtype} {tuple(dst.shape)}")
+            ptr, nbytes = _ptr(dst), dst.nbytes
+        else:
+            raise NativeError(ERR_INVALID, f"read_triangles_into: a numpy array or a torch tensor is needed, got {type(dst).__name__}")
+        _check(self._L.rvpt_hip_read(self._h, FORMAT_TRIANGLES, ptr if nbytes else None, nbytes), self._h, self._L)
+        return dst
+
+    def surface_points(self, prim, u, v) -> np.ndarray:
+        """Points on the stored mesh, as the last update form left it, for the (prim, u, v) a query reported — include/rvpt_hip.h: SURFACE POINTS has the
+        convention (u weights vert1 - vert0, v weights vert2 - vert0), the arithmetic and the numbering of prim (a ray query's).  prim[n] unsigned, u[n], v[n]
+        float32.  Returns SURFACE_POINT_DTYPE[n]: point, mat, normal; an invalid record (prim outside the scene — NO_PRIM, a miss piped through —, a non-finite
+        u or v) goes out as point = normal = 0, mat = NO_PRIM."""
+        prim = np.asarray(prim)
+        if prim.dtype.kind not in "iu" or (prim.size and (prim.min() < 0 or prim.max() > 0xFFFFFFFF)):
+            raise NativeError(ERR_INVALID, f"surface_points: prim must be integers in [0, 2^32), got {prim.dtype}")
+        prim = prim.astype(np.uint32).reshape(-1)
+        uv = [np.asarray(x, dtype=np.float32) for x in (u, v)]
+        for name, x in zip("uv", uv):
+            if x.ndim > 1 or (x.ndim == 1 and x.shape[0] != prim.shape[0]):
+                raise NativeError(ERR_INVALID, f"surface_points: {prim.shape[0]} records, {name} of shape {tuple(x.shape)}")
+        rec = np.zeros(prim.shape[0], dtype=SURFACE_POINT_DTYPE)
+        rec["prim"], rec["u"], rec["v"] = prim, uv[0], uv[1]
+        return self.surface_points_into(rec)
+
+    def surface_points_into(self, records):
+        """rvpt_hip_read with FORMAT_SURFACE_POINTS in the caller's memory: `records` is a contiguous SURFACE_POINT_DTYPE array, or a contiguous float32 torch
+        tensor [n, 12] (48-byte records; prim, flags, mat and reserved are the bits of their floats) on the host or on this context's device, as for
+        trace_rays_into.  The in fields (prim, u, v, flags) stay as they are, the out fields are written.  Returns records."""
+        return self._query_into(records, FORMAT_SURFACE_POINTS, SURFACE_POINT_DTYPE, "surface_points_into", "SURFACE_POINT_DTYPE")
 
     def write_accum(self, img) -> None:
         """rvpt_hip_write_accum: restore the accumulator from a row-major RGBA32F frame — anything numpy makes float32[h, w, 4] of, or a contiguous float32

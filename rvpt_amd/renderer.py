@@ -470,6 +470,49 @@ class RVPT:
             rec["prim"][hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[rec["prim"][hit]]
         return rec
 
+    def read_triangles(self, out=None):
+        """The mesh as it now stands on the device (Context.read_triangles; include/rvpt_hip.h: TRIANGLES): float32[n, 16], the stored bytes of every triangle
+        after whatever update, pose or skin form ran last, rows in the order the triangles were ADDED.  After a device build out= (Context.read_triangles_into:
+        a numpy array or a torch tensor on the context's device, where the rows then stay) is filled and returned instead; after a host build the device holds
+        the leaf order, the rows go through primitive_indices here on the host, and out= must be a numpy array.  Needs initialize(), not update()."""
+        if self._ctx is None:
+            raise RuntimeError("read_triangles before initialize()")
+        if self._device_built or self._n_triangles == 0:
+            return self._ctx.read_triangles() if out is None else self._ctx.read_triangles_into(out)
+        stored = self._ctx.read_triangles()
+        if out is None:
+            out = np.empty_like(stored)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.ndim != 2 or out.shape[1] != 16 or out.shape[0] < stored.shape[0]:
+            raise native.NativeError(native.ERR_INVALID, f"read_triangles: after a host build out= must be a numpy float32[n >= {stored.shape[0]}, 16] array")
+        out[np.asarray(self.primitive_indices, dtype=np.int64)] = stored  # stored row s is added triangle primitive_indices[s]
+        return out
+
+    def surface_points(self, prim, u=None, v=None) -> np.ndarray:
+        """Points on the mesh as it now stands (Context.surface_points; include/rvpt_hip.h: SURFACE POINTS) for triangles and pairs a query reported: prim[n]
+        numbering the triangles in the order they were ADDED, as trace_rays and closest_points report it, with u[n], v[n] — or, alone, a native.RAY_HIT_DTYPE or
+        native.POINT_HIT_DTYPE array, whose prim, u, v are taken.  Returns native.SURFACE_POINT_DTYPE records: point = (a + (b-a)*u) + (c-a)*v, the material
+        word and the stored unit normal; prim comes back as given.  A miss (native.NO_PRIM) is an invalid record: zeros, mat NO_PRIM.  Needs initialize()."""
+        if self._ctx is None:
+            raise RuntimeError("surface_points before initialize()")
+        if isinstance(prim, np.ndarray) and prim.dtype in (native.RAY_HIT_DTYPE, native.POINT_HIT_DTYPE):
+            if u is not None or v is not None:
+                raise native.NativeError(native.ERR_INVALID, "surface_points: query records carry their own u and v")
+            prim, u, v = prim["prim"], prim["u"], prim["v"]
+        elif u is None or v is None:
+            raise native.NativeError(native.ERR_INVALID, "surface_points: prim, u and v are needed, or an array of RAY_HIT_DTYPE / POINT_HIT_DTYPE records")
+        prim = np.asarray(prim)
+        if self._device_built or prim.size == 0 or prim.dtype.kind not in "iu":  # (Context.surface_points refuses what is no integer)
+            return self._ctx.surface_points(prim, u, v)
+        # a host-built tree: added order -> leaf order through the inverse of primitive_indices; what is outside the scene stays outside
+        given = prim.reshape(-1).astype(np.int64)
+        inverse = np.empty(self._n_triangles, dtype=np.int64)
+        inverse[np.asarray(self.primitive_indices, dtype=np.int64)] = np.arange(self._n_triangles)
+        inside = (given >= 0) & (given < self._n_triangles)
+        stored = np.where(inside, inverse[np.where(inside, given, 0)] if self._n_triangles else 0, native.NO_PRIM)
+        rec = self._ctx.surface_points(stored.astype(np.uint32), u, v)
+        rec["prim"] = given.astype(np.uint32)
+        return rec
+
     def pick(self, x: int, y: int):
         """What is under pixel (x, y) of the current camera: (prim, t) of the closest hit along the pixel-centre ray, or None.  The ray is made HERE, on the host, from
         scene_camera.get_data() (camera.glsl:29-51 in double, rounded to float32 once) — not by the frame kernel's float32 arithmetic: t agrees with a frame's to

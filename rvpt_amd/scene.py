@@ -806,6 +806,77 @@ def closest_points(tris, points, max_d2=np.inf, chunk: int = 1 << 20) -> np.ndar
     return rec
 
 
+SURFACE_POINT_DTYPE = np.dtype([("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("mat", "<u4"), ("normal", "<f4", (3,)),
+                                ("reserved", "<u4")])  # rvpt_surface_point (== native.SURFACE_POINT_DTYPE)
+_LIBM_FMAF = None
+
+
+def _fmaf(x, y, z) -> np.ndarray:
+    """fma(x, y, z) in float32 with ONE rounding, element by element through libm's fmaf (Python 3.10 has no math.fma, and numpy never fuses)."""
+    global _LIBM_FMAF
+    if _LIBM_FMAF is None:
+        import ctypes
+        import ctypes.util
+        libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+        libm.fmaf.restype = ctypes.c_float
+        libm.fmaf.argtypes = [ctypes.c_float] * 3
+        _LIBM_FMAF = libm.fmaf
+    x, y, z = np.broadcast_arrays(np.asarray(x, dtype=np.float32), np.asarray(y, dtype=np.float32), np.asarray(z, dtype=np.float32))
+    out = np.empty(x.shape, dtype=np.float32)
+    flat = out.reshape(-1)
+    for k, (a, b, c) in enumerate(zip(x.reshape(-1).tolist(), y.reshape(-1).tolist(), z.reshape(-1).tolist())):
+        flat[k] = _LIBM_FMAF(a, b, c)
+    return out
+
+
+def triangle_unit_normals(tris) -> np.ndarray:
+    """The hit normal the library stores per triangle (rvpt_kernels.hip: prepare_triangles; intersection.glsl:511-513), float32[n, 3]:
+    normalize(cross(vert1 - vert0, vert2 - vert0)) by rvpt_math.h — cross with every product and difference rounded on its own, the squared length by the FUSED
+    dot fma(z, z, fma(y, y, x*x)), its square root and the quotient 1 / len correctly rounded, then one product per component.  Not turned towards any ray.  A
+    zero-area triangle gets what this arithmetic gives (0 * inf = NaN)."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    a, b, c = t[:, 0:3], t[:, 4:7], t[:, 8:11]
+    with np.errstate(all="ignore"):
+        e0, e1 = b - a, c - a
+        nn = np.stack([e0[:, 1] * e1[:, 2] - e0[:, 2] * e1[:, 1], e0[:, 2] * e1[:, 0] - e0[:, 0] * e1[:, 2], e0[:, 0] * e1[:, 1] - e0[:, 1] * e1[:, 0]], axis=1)
+        sq = _fmaf(nn[:, 2], nn[:, 2], _fmaf(nn[:, 1], nn[:, 1], nn[:, 0] * nn[:, 0]))
+        inv = np.float32(1) / np.sqrt(sq)
+        out = nn * inv[:, None]
+    assert out.dtype == np.float32
+    return out
+
+
+def surface_points(tris, prim, u, v) -> np.ndarray:
+    """The normative statement of a SURFACE POINT read (include/rvpt_hip.h: SURFACE POINTS).  `tris` (float32[n, 16]) in the order the update form takes on the
+    context asked, which is the numbering of prim.  Per record, with a, b, c = vert0..2 of triangle prim: point = (a + (b-a)*u) + (c-a)*v per component in
+    float32, every operation rounded on its own (numpy never fuses) — u weights vert1 - vert0, v weights vert2 - vert0, any finite pair is evaluated; normal =
+    triangle_unit_normals of the row; mat = int(mat_id.x) as a uint32 word.  prim >= n or a non-finite u or v: point = normal = 0, mat = 0xFFFFFFFF.  reserved is 0.
+    Returns SURFACE_POINT_DTYPE[m] with the in fields filled (flags 0)."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    prim = np.asarray(prim, dtype=np.uint32).reshape(-1)
+    u, v = np.asarray(u, dtype=np.float32), np.asarray(v, dtype=np.float32)
+    rec = np.zeros(prim.shape[0], dtype=SURFACE_POINT_DTYPE)
+    rec["prim"], rec["u"], rec["v"] = prim, u, v
+    rec["mat"] = NO_PRIM
+    valid = (prim < t.shape[0]) & np.isfinite(rec["u"]) & np.isfinite(rec["v"])
+    rows = np.flatnonzero(valid)
+    if rows.size == 0:
+        return rec
+    used, where = np.unique(prim[rows], return_inverse=True)
+    normals = triangle_unit_normals(t[used])[where]
+    tri = t[prim[rows]]
+    a, b, c = tri[:, 0:3], tri[:, 4:7], tri[:, 8:11]
+    uu, vv = rec["u"][rows][:, None], rec["v"][rows][:, None]
+    with np.errstate(all="ignore"):
+        point = (a + (b - a) * uu) + (c - a) * vv
+        mat = tri[:, 12].astype(np.int32).astype(np.uint32)
+    assert point.dtype == np.float32
+    out = rec[rows]
+    out["point"], out["normal"], out["mat"] = point, normals, mat
+    rec[rows] = out
+    return rec
+
+
 def load_obj_positions(path) -> np.ndarray:
     """Minimal Wavefront OBJ reader: `v` records and `f` records (v, v/vt, v/vt/vn, v//vn, negative
     indices); polygons are fan-triangulated (tinyobjloader's default `triangulate=true`, which is

@@ -248,7 +248,8 @@ struct rvpt_hip_ctx {
     bool rects_valid[kMaxSlots] = {};
     // the SKY blocks of the slot's camera (rvpt_packets.hip: sky_blocks, sky_list — made with the slot's rectangles, for batched launches): a bit per block, the
     // ascending list of the other blocks and its count, copied into pinned host memory behind them (sky_ready); choose_launch takes the listed path only once it is there
-    uint32_t *d_sky_bits[kMaxSlots] = {}, *d_sky_list[kMaxSlots] = {}, *d_sky_count[kMaxSlots] = {};
+    uint32_t *d_sky_bits[kMaxSlots] = {}, *d_sky_count[kMaxSlots] = {};
+    uint2 *d_sky_list[kMaxSlots] = {};       // (block, origin of the block) per entry: rvpt_packets.h, ListedWork::list
     uint32_t *h_sky_count = nullptr;          // kMaxSlots counts (hipHostMalloc)
     hipEvent_t sky_ready[kMaxSlots] = {}, sky_read[kMaxSlots] = {};  // the count has arrived / the last blend that read the slot's sky bits is done
     bool sky_valid[kMaxSlots] = {};           // made for rects_key[slot]
@@ -282,6 +283,9 @@ struct rvpt_hip_ctx {
         bool packets_interleave_all = false;  // ... =-g: launches of any size (measured slower for the batched ones: profiles/r06_interleave.txt)
         int packets_sky_list = 1;         // RVPT_HIP_PACKETS_SKY_LIST (laboratory build): batched launches claim only the blocks that are not sky (0 = off, 1 = once the
                                           // slot's list has arrived, 2 = wait for the list on first use: tests/test_sky_list.py)
+        int packets_frame_runs = -1;      // RVPT_HIP_PACKETS_FRAME_RUNS (laboratory build): listed launches run each block's frames back to back in groups of this many frames, with the
+                                          // camera set-up of a block made once per run (rvpt_packets.h: ListedWork; 0 = frame-major order and per-round set-up, F > 0: groups of F
+                                          // for every listed launch; the default: groups of 16 for launches of 16 frames or more — choose_launch)
         std::string timeline_path;        // RVPT_HIP_TIMELINE=<file>: the last frame's per-wave timestamps, written at destroy
         int blocks_per_cu = 0;            // RVPT_HIP_BLOCKS_PER_CU: work-groups per CU of the persistent kernels (0 / -1 here and below: the built-in policy)
         int first_units = 0, claim_units = 0;  // RVPT_HIP_FIRST_UNITS, RVPT_HIP_CLAIM_UNITS: the work plan's static chunk and claim size (plan_work)
@@ -344,6 +348,7 @@ rvpt_hip_ctx::Knobs read_knobs(uint32_t flags)
     set_int(k.bvh_cam_min, getenv("RVPT_HIP_BVH_CAM_MIN"), 1, 65);  // 65 = never
     set_int(k.bvh_detach, getenv("RVPT_HIP_BVH_DETACH"), 0, 64);
     set_int(k.packets_sky_list, getenv("RVPT_HIP_PACKETS_SKY_LIST"), 0, 2);
+    set_int(k.packets_frame_runs, getenv("RVPT_HIP_PACKETS_FRAME_RUNS"), 0, 64);
 #endif
     return k;
 }
@@ -492,6 +497,7 @@ bool has_global_stack(Variant v) { return v == Variant::Bvh || v == Variant::Wid
 // ... and the row boxes of packets that leave one triangle (row_bits, row_boxes)
 constexpr uint32_t kCullRects = 1u, kCullBounce = 2u, kCullBlockRounds = 4u, kCullLeafBoxes = 16u, kCullClaimOrder = 32u, kCullLeanInstance = 64u, kCullSkyList = 128u;
 constexpr uint32_t kCullRowBoxes = 256u;
+constexpr uint32_t kCullFrameRuns = 512u;  // ... and the listed launch in frame-run order with run headers (trace_brute_packets_aa1_culls_listed_runs)
 
 struct Launch {
     Kernel kernel;
@@ -870,10 +876,17 @@ int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, i
         l.work.list = ctx->d_sky_list[slot];
         l.work.n_listed_frame = 64u * n_listed;
         l.work.div_listed_frame = rv::fast_div_make(64u * n_listed);
+        // Frame runs (the origin of a block is two 16-bit fields of the list's entry).  Groups of 16 frames, for launches that hold a whole group: measured on the
+        // headline (profiles/frame_runs.txt), 200 steps as 4 x 50 frames gain 3 % at F = 4, 8 and 16 alike, but a lone 20-frame launch LOSES 3 % at F = 8 — where a
+        // 512-item claim is exactly one block's run, eight camera rounds of one block in one wave — and nothing at 4 (two blocks per claim) or 16 (a run is two
+        // claims).  Shorter launches keep the frame-major order.
+        const uint32_t n_frames = p.n_work / (64u * n_listed);
+        const uint32_t run_frames = k.packets_frame_runs >= 0 ? static_cast<uint32_t>(k.packets_frame_runs) : (n_frames >= 16u ? 16u : 0u);
+        rv::listed_runs_make(l.work, n_listed, n_frames, (p.width <= 65536u && p.height <= 65536u) ? run_frames : 0u);
     }
     l.cull_bits = (cull ? kCullRects : 0u) | (p.vis ? kCullBounce : 0u) | ((v == Variant::BrutePackets && p.first_units % 4u == 0u) ? kCullBlockRounds : 0u) |
                   (p.leaf_boxes ? kCullLeafBoxes : 0u) | (p.perm_groups != 0u ? kCullClaimOrder : 0u) | (lean ? kCullLeanInstance : 0u) | (l.listed ? kCullSkyList : 0u) |
-                  (p.row_boxes ? kCullRowBoxes : 0u);
+                  (p.row_boxes ? kCullRowBoxes : 0u) | ((l.listed && l.work.run_frames != 0u) ? kCullFrameRuns : 0u);
     return 0;
 }
 
@@ -2334,10 +2347,11 @@ static int update_rects(rvpt_hip_ctx *ctx, int slot, hipStream_t tstream, const 
     if (sky && !ctx->sky_valid[slot]) {
         const uint32_t n_blocks = ctx->n_work / 64u;  // (n_work: whole 16 x 16 tiles)
         if (!ctx->d_sky_bits[slot]) {  // (all five made, then published together: a failure part way leaves the slot without a list, never with half of one)
-            uint32_t *bits = nullptr, *list = nullptr, *count = nullptr;
+            uint32_t *bits = nullptr, *count = nullptr;
+            uint2 *list = nullptr;
             hipEvent_t ready = nullptr, read = nullptr;
             hipError_t e = hipMalloc(reinterpret_cast<void **>(&bits), static_cast<size_t>((n_blocks + 31u) / 32u) * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&list), static_cast<size_t>(n_blocks) * sizeof(uint32_t));
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&list), static_cast<size_t>(n_blocks) * sizeof(uint2));
             if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&count), sizeof(uint32_t));
             if (e == hipSuccess) e = hipEventCreateWithFlags(&ready, hipEventDisableTiming);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&read, hipEventDisableTiming);
@@ -2354,7 +2368,7 @@ static int update_rects(rvpt_hip_ctx *ctx, int slot, hipStream_t tstream, const 
         if (!ctx->h_sky_count) HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_sky_count), rvpt_hip_ctx::kMaxSlots * sizeof(uint32_t)));
         if (ctx->sky_read_used[slot]) HIP_TRY(ctx, hipStreamWaitEvent(tstream, ctx->sky_read[slot], 0));  // the last blend that reads the slot's old bits
         hipLaunchKernelGGL(rv::sky_blocks, dim3((n_blocks + 255u) / 256u), dim3(256), 0, tstream, p, ctx->d_rects[slot], n_blocks, ctx->d_sky_bits[slot]);
-        hipLaunchKernelGGL(rv::sky_list, dim3(1), dim3(1024), 0, tstream, ctx->d_sky_bits[slot], n_blocks, ctx->d_sky_list[slot], ctx->d_sky_count[slot]);
+        hipLaunchKernelGGL(rv::sky_list, dim3(1), dim3(1024), 0, tstream, p, ctx->d_sky_bits[slot], n_blocks, ctx->d_sky_list[slot], ctx->d_sky_count[slot]);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(ctx->h_sky_count + slot, ctx->d_sky_count[slot], sizeof(uint32_t), hipMemcpyDeviceToHost, tstream));
         HIP_TRY(ctx, hipEventRecord(ctx->sky_ready[slot], tstream));
@@ -2464,7 +2478,9 @@ static int dispatch_launch(rvpt_hip_ctx *ctx, uint32_t n_frames)
     ctx->buf_used[buf] = true;
     ctx->slot_used[slot] = true;
     if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ev0, tstream));
-    if (launch.listed)
+    if (launch.listed && launch.work.run_frames != 0u)
+        hipLaunchKernelGGL(rv::trace_brute_packets_aa1_culls_listed_runs, dim3(launch.grid), dim3(rv::kBlock), launch.lds, tstream, p, launch.work);
+    else if (launch.listed)
         hipLaunchKernelGGL(rv::trace_brute_packets_aa1_culls_listed, dim3(launch.grid), dim3(rv::kBlock), launch.lds, tstream, p, launch.work);
     else
         hipLaunchKernelGGL(launch.kernel, dim3(launch.grid), dim3(rv::kBlock), launch.lds, tstream, p);

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "rvpt_kernels.h"
+#include "rvpt_math.h"
 
 namespace rv {
 
@@ -17,12 +18,41 @@ __global__ void trace_brute_packets_culls_order(const FrameParams p);
 __global__ void trace_brute_packets_aa1_culls_order(const FrameParams p);
 // The LISTED instance (batched launches of a still camera, one sample per pixel): the claims count only the blocks of a frame that are not SKY (sky_blocks below), 64
 // work items per block of `list` (ascending frame-local block indices) per frame — n_listed_frame items per frame; blend_accumulate_sky makes the sky blocks' samples
+// FRAME RUNS (run_frames = F > 0, trace_brute_packets_aa1_culls_listed_runs): the items are ordered by GROUP of F consecutive frames (the last group may be shorter),
+// then list position, then frame within the group, so that a block's F camera rounds follow each other (F = 16: two 512-item claims) and a wave does what depends
+// on the camera and the block alone — the pixel coordinates, their hash, the candidate triangles — once per run (listed_item below; packets_body: the run header)
 struct ListedWork {
-    const uint32_t *list;
+    const uint2 *list;        // per listed block: (frame-local block index, pixel coordinates of its first item as gx0 | gy0 << 16)
     uint32_t n_listed_frame;  // 64 x the blocks of the list
     FastDiv div_listed_frame;
+    uint32_t run_frames;      // F; 0 = frame-major order (items ordered by frame, then list position)
+    uint32_t n_blocks;        // the blocks of the list
+    uint32_t n_full_groups;   // frames of the launch / F
+    uint32_t last_frames;     // frames of the launch % F: the frames of the short last group (0: there is none)
+    FastDiv div_group, div_run, div_last;  // by F * n_blocks (the blocks' items of a whole group), by F and by max(last_frames, 1)
 };
+// host side of the above for a launch of n_frames frames over a list of n_blocks blocks
+inline void listed_runs_make(ListedWork &w, const uint32_t n_blocks, const uint32_t n_frames, const uint32_t run_frames)
+{
+    w.run_frames = run_frames;
+    w.n_blocks = n_blocks;
+    w.n_full_groups = run_frames ? n_frames / run_frames : 0u;
+    w.last_frames = run_frames ? n_frames % run_frames : 0u;
+    w.div_group = fast_div_make(run_frames * n_blocks);
+    w.div_run = fast_div_make(run_frames);
+    w.div_last = fast_div_make(w.last_frames ? w.last_frames : 1u);
+}
+// block-item k of a launch in frame-run order (item index >> 6) -> the frame offset in the launch and the position in the list
+RV_HD void listed_item(const ListedWork &w, const uint32_t k, uint32_t &frame, uint32_t &pos)
+{
+    const uint32_t g = fast_div(k, w.div_group);
+    const uint32_t r = k - g * (w.run_frames * w.n_blocks);
+    const bool last = g >= w.n_full_groups;  // (the short group: last_frames * n_blocks < F * n_blocks items, all of them with g = n_full_groups)
+    pos = fast_div(r, last ? w.div_last : w.div_run);
+    frame = g * w.run_frames + (r - pos * (last ? w.last_frames : w.run_frames));
+}
 __global__ void trace_brute_packets_aa1_culls_listed(const FrameParams p, const ListedWork w);
+__global__ void trace_brute_packets_aa1_culls_listed_runs(const FrameParams p, const ListedWork w);
 #if RVPT_HIP_LAB
 // diagnostics (rvpt_hip_selftest_pretest): per element, bit 0 = the division-free pre-test of a camera round lets the pair through, bit 1 = the
 // quotient's own condition 0 < t < closest holds; the numerator goes through the camera record's rule (not safe -> NaN -> always through)
@@ -35,8 +65,8 @@ __global__ void camera_rects(const FrameParams p, uint2 *__restrict__ rects, flo
 // the SKY blocks of a frame for the same camera: bit b of sky_bits (ceil(n_blocks / 32) words) = no rectangle holds the frame's 16 x 4 block b (work items 64 b ..) or
 // the block lies wholly outside the image; one thread per block, 256 per work-group
 __global__ void sky_blocks(const FrameParams p, const uint2 *__restrict__ rects, uint32_t n_blocks, uint32_t *__restrict__ sky_bits);
-// ... and the blocks that are not, in ascending order, and their count: ONE work-group of 1024 threads
-__global__ void sky_list(const uint32_t *__restrict__ sky_bits, uint32_t n_blocks, uint32_t *__restrict__ list, uint32_t *__restrict__ count);
+// ... and the blocks that are not, in ascending order, each with the pixel coordinates of its first item (ListedWork::list), and their count: ONE work-group of 1024 threads
+__global__ void sky_list(const FrameParams p, const uint32_t *__restrict__ sky_bits, uint32_t n_blocks, uint2 *__restrict__ list, uint32_t *__restrict__ count);
 // the bounce cull's table for `n` prepared triangles: out[(2 A + s) * words + w] bit b = 0 only when triangle B = 32 w + b lies wholly behind the plane of A as
 // seen from side s (s = 0: the side A's normal cross(e0, e1) points to), by more than `margin`, and both triangles are well shaped; bits >= n are 0
 __global__ void bounce_visibility(const float4 *__restrict__ prep, uint32_t n, double margin, uint32_t words, uint32_t stride, uint32_t *__restrict__ out);

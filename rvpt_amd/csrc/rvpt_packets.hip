@@ -42,6 +42,9 @@
 #ifndef RV_BOX_BATCH
 #define RV_BOX_BATCH 1  // leaf boxes of a bounce round requested together (1, 2 or 4: a whole word's); more boxes in flight = fewer waits and more SGPRs: 2 and 4 measured slower
 #endif
+#ifndef RV_PACKETS_RUN_MASKS
+#define RV_PACKETS_RUN_MASKS 1  // the run header of listed launches keeps the candidate ballots of the rectangle scan (scenes of at most 192 triangles: six SGPRs); 0: origin and hash only, the scan every round
+#endif
 #ifndef RV_PACKETS_BOUNCE_EARLY
 #define RV_PACKETS_BOUNCE_EARLY 0  // 1: the early-out loop in bounce rounds as well (experiment: incoherent packets rarely fail the pre-test together)
 #endif
@@ -122,7 +125,10 @@ __device__ __forceinline__ void intersect_listed(const v4f *src, const uint32_t 
 // map's six scalars cost eleven SGPR spills in a kernel that never uses them
 // LISTED (AA1, CULLS, batched, no claim order): pool.next counts the items of the sky-less work list `lw` (rvpt_packets.h: ListedWork); a camera round maps its 64 to
 // (frame, lw.list[b]) and L.work stays the launch's uncompacted index frame * n_work_frame + pixel (sample slot, seed and statistics as without the list)
-template <bool AA1, bool CULLS, bool ORDER = true, bool LISTED = false>
+// RUNS (LISTED only): the list's items come in frame-run order (rvpt_packets.h: listed_item) and the wave keeps a RUN HEADER — what a camera round of the block at
+// one list position needs that does not depend on the frame: the block and its origin (from the list's entry), the per-lane hash of the pixel that the seed starts
+// from, and, for scenes of at most 192 triangles, the candidate ballots of the rectangle scan — rebuilt only when a camera round maps to another position
+template <bool AA1, bool CULLS, bool ORDER = true, bool LISTED = false, bool RUNS = false>
 __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedWork &lw = ListedWork{})
 {
     constexpr uint32_t kPathWords = AA1 ? kPacketQueueWordsAA1 : kPacketQueueWords;
@@ -156,6 +162,9 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
     bool has = false;  // this lane holds a live path whose next segment is to be traced
     uint32_t leave = 0xFFFFFFFFu;  // ... and where that segment leaves from: 2 * triangle + side (shade), all ones = anywhere (a camera ray)
     uint32_t nsmp = 0;
+    // the run header (RUNS): the list position it was made for (wave-uniform; all ones = none yet), the entry's block and origin, hash(pixel) per lane, the ballots
+    uint32_t hdr_pos = 0xFFFFFFFFu, hdr_block = 0, hdr_origin = 0, hdr_hash = 0;
+    uint64_t hdr_todo[3] = {0, 0, 0};
     // optional timeline (RVPT_HIP_TIMELINE): [0] start [1] pool dry [2] end (100 MHz wall clock) [3] camera rounds | bounce rounds << 32 [4] split rounds | lane-rounds << 32
     unsigned long long t_start = 0, t_dry = 0;
     uint32_t n_cam = 0, n_bounce = 0, n_split = 0, lane_rounds = 0, n_listed = 0, n_uniform = 0;  // [5] triangles walked by the culled bounce rounds | those of them that took the row boxes << 32
@@ -207,11 +216,44 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
             uint32_t work = first + lane;
             pool.next += 64u;
             uint32_t frame_offset = 0, pixel = work;
-            if (LISTED) {  // item `first` of the list's launch: frame f, the list's block b (one scalar load: wave-uniform)
+            uint32_t gx, gy;
+            bool inside;
+            if (LISTED && RUNS) {  // item `first` in frame-run order: frame f, list position pos (scalar arithmetic); the block and its pixels from the header
+                uint32_t f, pos;
+                listed_item(lw, uniform(first >> 6), f, pos);
+                f = uniform(f), pos = uniform(pos);
+                if (pos != hdr_pos) {
+                    typedef const __attribute__((address_space(4))) uint32_t *ConstWords;
+                    const ConstWords e = (ConstWords)(reinterpret_cast<uintptr_t>(lw.list)) + 2u * static_cast<size_t>(pos);  // (the entry's two words: one scalar request)
+                    hdr_pos = pos;
+                    hdr_block = e[0];
+                    hdr_origin = e[1];
+                    const uint32_t hx = (hdr_origin & 0xFFFFu) + (lane & 15u), hy = (hdr_origin >> 16) + (lane >> 4);
+                    hdr_hash = wang_hash(hx + hy * p.width);
+                    if (RV_PACKETS_RUN_MASKS && p.n_tris <= 192u) {  // the rectangle scan of the camera walk below, once per run
+                        const uint32_t hbx = (hdr_origin & 0xFFFFu) >> 4, hby = hdr_origin >> 18;
+#pragma unroll
+                        for (uint32_t c = 0; c < 3u; ++c) {
+                            const uint32_t idx = 64u * c + lane;
+                            bool candidate = false;
+                            if (idx < p.n_tris) {
+                                const uint2 r = lds_rect[idx];
+                                candidate = rect_holds(r.x, r.y, hbx, hby);
+                            }
+                            hdr_todo[c] = ballot(candidate);
+                        }
+                    }
+                }
+                frame_offset = f;
+                gx = (hdr_origin & 0xFFFFu) + (lane & 15u);
+                gy = (hdr_origin >> 16) + (lane >> 4);
+                inside = (gx < p.width) & (gy < p.height);
+                work = f * p.n_work_frame + ((hdr_block << 6) | lane);
+            } else if (LISTED) {  // item `first` of the list's launch: frame f, the list's block b (one scalar load: wave-uniform)
                 typedef const __attribute__((address_space(4))) uint32_t *ConstWords;
                 const uint32_t f = uniform(fast_div(first, lw.div_listed_frame));
                 const uint32_t b = uniform((first - f * lw.n_listed_frame) >> 6);
-                const uint32_t block = ((ConstWords)(reinterpret_cast<uintptr_t>(lw.list)))[b];
+                const uint32_t block = ((ConstWords)(reinterpret_cast<uintptr_t>(lw.list)))[2u * b];  // (.x of the entry)
                 frame_offset = f;
                 pixel = (block << 6) | lane;
                 work = f * p.n_work_frame + pixel;
@@ -219,8 +261,7 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
                 frame_offset = fast_div(work, p.div_work_frame);
                 pixel = work - frame_offset * p.n_work_frame;
             }
-            uint32_t gx, gy;
-            const bool inside = decode_work(p, pixel, gx, gy);
+            if (!(LISTED && RUNS)) inside = decode_work(p, pixel, gx, gy);
             // 64 consecutive work items starting at a multiple of 64 = rows 4 k .. 4 k + 3 of one 16 x 16 tile of one frame (n_work_frame is a multiple
             // of 256); chunks start at multiples of 64 for every launch of a size that matters (rvpt_abi.hip: plan_work) — otherwise no culling this round
             cull = CULLS || (p.rects != nullptr && (uniform(work) & 63u) == 0u);
@@ -230,7 +271,7 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
                 L.work = work;
                 L.gx = gx;
                 L.gy = gy;
-                L.rng = camera_seed(p, gx, gy, frame_offset);
+                L.rng = (LISTED && RUNS) ? hdr_hash + (p.frame + frame_offset) : camera_seed(p, gx, gy, frame_offset);  // (camera_seed with the header's hash)
                 L.sample = 0;
                 L.sum = mk(0.0f, 0.0f, 0.0f);
                 begin_sample(L, p);
@@ -306,6 +347,18 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
             hit = __shfl(h, rank * k, 64);
             n_split += 1;
             __builtin_amdgcn_wave_barrier();  // the table is read before anything is parked over it
+        } else if (RV_PACKETS_RUN_MASKS && LISTED && RUNS && camera_round && p.n_tris <= 192u) {
+            // ---- the header's candidates (the scan below, made once for the run): the same triangles in the same ascending order
+#pragma unroll
+            for (uint32_t c = 0; c < 3u; ++c) {
+                uint64_t todo = hdr_todo[c];
+                while (todo != 0) {
+                    const uint32_t j = 64u * c + static_cast<uint32_t>(__builtin_ctzll(todo));
+                    todo &= todo - 1;
+                    if (has) camera_test_one(src, cam_records, j, L.o, L.d, closest, hit);
+                }
+            }
+            RV_PHASE(3)
         } else if (camera_round && cull) {
             // ---- the triangles whose rectangle holds this block, 64 at a time: lane i looks at rectangle base + i, the ballot is the candidate list
             for (uint32_t base = 0; base < p.n_tris; base += 64u) {
@@ -464,6 +517,7 @@ __global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_pack
 __global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_packets_culls_order(const FrameParams p) { packets_body<false, true, true>(p); }
 __global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_packets_aa1_culls_order(const FrameParams p) { packets_body<true, true, true>(p); }
 __global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_packets_aa1_culls_listed(const FrameParams p, const ListedWork w) { packets_body<true, true, false, true>(p, w); }
+__global__ __launch_bounds__(kBlock, RV_PACKETS_MIN_WAVES) void trace_brute_packets_aa1_culls_listed_runs(const FrameParams p, const ListedWork w) { packets_body<true, true, false, true, true>(p, w); }
 
 __global__ void sky_blocks(const FrameParams p, const uint2 *__restrict__ rects, uint32_t n_blocks, uint32_t *__restrict__ sky_bits)
 {
@@ -487,7 +541,7 @@ __global__ void sky_blocks(const FrameParams p, const uint2 *__restrict__ rects,
     if (lane_id() == 0 && w + 1u < n_words) sky_bits[w + 1u] = static_cast<uint32_t>(m >> 32);
 }
 
-__global__ void sky_list(const uint32_t *__restrict__ sky_bits, uint32_t n_blocks, uint32_t *__restrict__ list, uint32_t *__restrict__ count)
+__global__ void sky_list(const FrameParams p, const uint32_t *__restrict__ sky_bits, uint32_t n_blocks, uint2 *__restrict__ list, uint32_t *__restrict__ count)
 {
     __shared__ uint32_t wave_total[16];
     const uint32_t n_words = (n_blocks + 31u) >> 5;
@@ -514,7 +568,10 @@ __global__ void sky_list(const uint32_t *__restrict__ sky_bits, uint32_t n_block
             all += wave_total[k];
         }
         while (keep != 0u) {
-            list[pos++] = 32u * w + static_cast<uint32_t>(__builtin_ctz(keep));
+            const uint32_t b = 32u * w + static_cast<uint32_t>(__builtin_ctz(keep));
+            uint32_t gx, gy;
+            decode_work(p, b << 6, gx, gy);  // (inside the image: sky_blocks marks the blocks outside as sky)
+            list[pos++] = make_uint2(b, gx | (gy << 16));
             keep &= keep - 1u;
         }
         base += all;

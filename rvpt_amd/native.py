@@ -54,6 +54,7 @@ FORMAT_SURFACE_POINTS = 6  # RVPT_HIP_FORMAT_SURFACE_POINTS: rvpt_hip_read answe
 SURFACE_POINT_DTYPE = np.dtype([("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("mat", "<u4"), ("normal", "<f4", (3,)), ("reserved", "<u4")])
 CULL_ROW_BOXES = 0x100  # Context.cull_info: the launch rode with the row boxes (rvpt_abi.hip: kCullRowBoxes)
 CULL_SKY_LIST = 0x80  # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
+CULL_FRAME_RUNS = 0x200  # Context.cull_info: ... in frame-run order, the camera set-up of a block made once per run (rvpt_abi.hip: kCullFrameRuns)
 TILE = 16
 TILE_SHIFT = 3  # RVPT_HIP_TILE_SHIFT: every row of the tile grid is rotated by this many more tiles than the one above (tile ownership)
 NODES_BUILD = C.c_size_t(-1).value  # RVPT_HIP_NODES_BUILD: upload_scene's node count for the build form (Context.build_scene)
@@ -954,7 +955,7 @@ class Context:
     def cull_info(self) -> int:
         """rvpt_hip_get_cull_info of the last launch: bit 0 screen rectangles, bit 1 bounce table, bit 2 camera rounds aligned to 16 x 4 blocks, bit 4 leaf boxes,
         bit 5 interleaved claim order, bit 6 the kernel instance without the uncull'd walks, bit 7 (CULL_SKY_LIST) the batched launch that claims only the blocks
-        that are not sky and blends the sky from the RNG, bit 8 (CULL_ROW_BOXES) the row boxes of bounce packets that leave one triangle."""
+        that are not sky and blends the sky from the RNG, bit 8 (CULL_ROW_BOXES) the row boxes of bounce packets that leave one triangle, bit 9 (CULL_FRAME_RUNS) the listed launch in frame-run order."""
         f = C.c_uint32(0)
         _check(self._L.rvpt_hip_get_cull_info(self._h, C.byref(f)), self._h, self._L)
         return f.value

@@ -81,7 +81,9 @@ extern "C" {
                                      TRIANGLE READ-BACK: `dst` receives the stored rvpt_triangle rows, as the last update form left them, in update order.
                                      Still 8, no new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_SURFACE_POINTS (6) — until then the "unknown
                                      format" error — is a SURFACE POINT read: `dst` holds rvpt_surface_point records, (prim, u, v) as a query reported them
-                                     in, the point of the stored mesh, its material word and its normal out */
+                                     in, the point of the stored mesh, its material word and its normal out.  Still 8, no new symbol: rvpt_hip_read with
+                                     a format RVPT_HIP_FORMAT_RAY_HITS_NEAREST(k) (33 .. 40) — until then the "unknown format" error — is a K-NEAREST RAY
+                                     QUERY: `dst` holds groups of k rvpt_ray_hit records, the ray in the first, the k nearest hits along it out */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -171,6 +173,8 @@ typedef struct rvpt_camera_data {
                                          compute_pass.comp:41-42)                        */
 #define RVPT_HIP_FORMAT_RAY_HITS 2    /* dst: rvpt_ray_hit[dst_bytes / 48], in and out (RAY QUERIES at rvpt_hip_read) */
 #define RVPT_HIP_RAY_ANY_HIT 0x1u     /* per ray: stop at the first accepted triangle    */
+#define RVPT_HIP_RAY_MAX_HITS 8u      /* per call: the largest k of a k-nearest ray query */
+#define RVPT_HIP_FORMAT_RAY_HITS_NEAREST(k) (32 + (k))     /* k = 1 .. RVPT_HIP_RAY_MAX_HITS: formats 33 .. 40; dst: n groups of k rvpt_ray_hit (K-NEAREST RAY QUERIES at rvpt_hip_read) */
 
 /* One ray of a query and its answer (48 B = three float4; no reference counterpart: the reference traces only its camera's paths). */
 typedef struct rvpt_ray_hit {
@@ -599,6 +603,35 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  * - It implies rvpt_hip_wait, as every read does, and leaves untouched the accumulator, rvpt_hip_get_timing, rvpt_hip_get_stats, rvpt_hip_get_launch_info,
  *   rvpt_hip_get_cull_info, the frame counter, and rvpt_hip_last_error on success: a frame dispatched after a query is bit for bit the frame dispatched without it.
  * DESIGN.md 5.13 has the kernels and what was measured (profiles/ray_queries.txt).
+ *
+ * K-NEAREST RAY QUERIES — the first k hits along the caller's own rays, in place:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_RAY_HITS_NEAREST(k), records, n * k * sizeof(rvpt_ray_hit));      k = 1 .. RVPT_HIP_RAY_MAX_HITS
+ *
+ * `dst` then holds n GROUPS of k consecutive rvpt_ray_hit records.  Record 0 of a group carries the ray in its in fields (org, tmax, dir, flags); the in fields
+ * of records 1 .. k-1 are ignored.  No in field of any record is ever written.  On return the out quad (t, prim, u, v) of record j holds the j-th hit of the
+ * group's ray.  The k belongs to the call, not to the record: a launch is uniform in k.  Formats 32 and 41 are the "unknown format" error.
+ * - THE ANSWER IS DEFINED BY THE WALK, as a ray query's is: the order is THE ORDER A QUERY WALKS above — intersect_bvh of the reference, left child first, on
+ *   BVH contexts under both BVH traversal flags; triangles 0 .. n-1 in stored order on brute-force contexts.  A valid ray keeps a list H of at most k accepted
+ *   hits and a value `bound` that starts at tmax.
+ * - CLOSEST MODE (flags without RVPT_HIP_RAY_ANY_HIT).  Every box test and every triangle test uses the interval (0, bound).  A triangle is accepted iff
+ *   0 < t < bound, 0 < u, 0 < v and u + v < 1: the tests of a ray query.  An accepted hit is inserted behind every entry whose t is <= its own: among equal t
+ *   the one accepted earlier stays in front.  If H then holds k + 1 entries, the last is dropped.  Whenever H holds k entries, `bound` is the t of the last.
+ *   A later triangle at exactly the k-th t is therefore not accepted: the test is strict, as a ray query's is.
+ * - ANY-HIT MODE (the bit set in record 0).  `bound` stays tmax, accepted hits are appended in the order of acceptance, and the walk stops when H holds k:
+ *   record j is the j-th triangle accepted.
+ * - WHAT A GROUP HOLDS ON RETURN.  For j < |H| the quad of record j is (t, prim, u, v) of the j-th entry: u and v are what the accepting test computed, prim is
+ *   numbered as a ray query numbers it (THE NUMBERING OF prim above).  For j >= |H| it is the miss quad of a ray query: t = the bits of record 0's tmax as
+ *   given, prim = 0xFFFFFFFF, u = v = 0.  A ray with a non-finite component in org or dir, or a tmax that is NaN, zero or negative, gets k miss quads, decided
+ *   before the walk.
+ * - With k = 1 both modes are format 2 exactly: RVPT_HIP_FORMAT_RAY_HITS_NEAREST(1) is format 2, the same kernels and the same bytes.
+ * - ON BRUTE-FORCE CONTEXTS the closest-mode answer is therefore the first k of all triangles accepted in (0, tmax), ordered by (t, stored index).  On BVH
+ *   contexts the visiting order decides among equal t, as it does for a ray query.
+ * - Everything else is a ray query's rule: the call needs a scene and no rvpt_hip_set_frame, the empty scene answers with misses; dst_bytes must be a multiple
+ *   of 48 * k, else RVPT_HIP_ERR_INVALID (the message gives k and the byte count); dst_bytes == 0 is a successful no-op; fewer than 2^32 records (n * k) per
+ *   call; `dst` is host memory or 16-byte aligned device memory of the context's GPU, another GPU's memory is an error naming both devices, and in every error
+ *   case `dst` is untouched; the call is LOCAL under a communicator, implies rvpt_hip_wait, and leaves untouched what a ray query leaves untouched.
+ * DESIGN.md 5.23 has the kernels and what was measured (profiles/ray_queries.txt).
  *
  * PATH QUERIES — radiance along the caller's own rays, in place:
  *

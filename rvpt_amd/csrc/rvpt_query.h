@@ -18,6 +18,7 @@ constexpr uint32_t kQueryRecordBytes = 48;   // sizeof(rvpt_ray_hit): three floa
 constexpr uint32_t kQueryLdsLevels = 8;      // stack slots per lane kept in LDS (16 KiB per work-group); deeper ones go to one global column per thread and level
 constexpr uint32_t kQueryTopNodes = 64;      // wide nodes from the top of the (breadth-first) tree copied into LDS: 8 KiB
 constexpr uint32_t kQueryTileTris = 512;     // prepared triangles per LDS tile of the brute-force kernel: 32 KiB
+constexpr uint32_t kQueryMaxHits = 8;        // RVPT_HIP_RAY_MAX_HITS: the k of a k-nearest query, held in register lists of 2, 4 or 8 slots
 constexpr size_t kQueryStackMaxBytes = size_t(256) << 20;  // the global part of the stack never takes more: the persistent grid shrinks instead
 
 struct QueryScene {
@@ -39,9 +40,11 @@ struct QueryPlan {
 };
 
 // The launch shape for n records: a persistent grid sized from occupancy for the tree walks (the overflow stack is bounded by the grid, not by n), one
-// work-group per 256 records for the brute-force kernel.
-hipError_t query_plan(const QueryScene &scene, uint32_t n, int num_cus, QueryPlan *plan);
-// Answers records[0 .. n) in place on `stream`.  `scratch` holds 64 words (the first is the claim counter, zeroed here) followed by plan.stack_words words.
-hipError_t query_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n);
+// work-group per 256 records for the brute-force kernel.  k > 1 (RVPT_HIP_FORMAT_RAY_HITS_NEAREST(k)): n counts GROUPS of k records, one ray each, and the
+// occupancy is that of the k-nearest instance the launch will use.
+hipError_t query_plan(const QueryScene &scene, uint32_t n, int num_cus, QueryPlan *plan, uint32_t k = 1);
+// Answers records[0 .. n) in place on `stream` — with k > 1 the n groups records[0 .. n * k), the plan made with the same k.  `scratch` holds 64 words (the
+// first is the claim counter, zeroed here) followed by plan.stack_words words.
+hipError_t query_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n, uint32_t k = 1);
 
 }  // namespace rv

@@ -607,6 +607,26 @@ bool RVPT::trace_rays_device(void *records, size_t n)
     }
     return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_HITS, records, n * sizeof(rvpt_ray_hit)), "rvpt_hip_read");
 }
+bool RVPT::trace_rays(rvpt_ray_hit *records, size_t n, int hits)
+{
+    if (!trace_rays_device(records, n, hits)) return false;  // (the library classifies the pointer)
+    if (!device_built_)  // the library numbered the leaf order it was given: every slot of every group
+        for (size_t i = 0; i < n * static_cast<size_t>(hits); ++i)
+            if (records[i].prim < order_.size()) records[i].prim = order_[records[i].prim];
+    return true;
+}
+bool RVPT::trace_rays_device(void *records, size_t n, int hits)
+{
+    if (!ctx_) {
+        error_ = "trace_rays before initialize()";
+        return false;
+    }
+    if (hits < 1 || hits > static_cast<int>(RVPT_HIP_RAY_MAX_HITS)) {
+        error_ = "trace_rays: hits " + std::to_string(hits) + " is outside 1 .. " + std::to_string(RVPT_HIP_RAY_MAX_HITS);
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_HITS_NEAREST(hits), records, n * static_cast<size_t>(hits) * sizeof(rvpt_ray_hit)), "rvpt_hip_read");
+}
 bool RVPT::trace_paths(std::vector<rvpt_ray_path> &records)
 {
     if (!ctx_) {

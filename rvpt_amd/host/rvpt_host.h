@@ -200,6 +200,12 @@ public:
     // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host: prim then stays as the LIBRARY numbers
     // it — the leaf order after a host build (sorted_triangles()), the added order after a device build.  `records` may be read from any stream on return.
     bool trace_rays_device(void *records, size_t n);
+    // The k nearest hits along every ray (RVPT_HIP_FORMAT_RAY_HITS_NEAREST(hits); include/rvpt_hip.h: K-NEAREST RAY QUERIES): `records` holds n GROUPS of `hits`
+    // consecutive records, n * hits in all; record 0 of a group carries the ray, the out quad of record j receives the j-th hit (prim 0xFFFFFFFF from the first
+    // slot no hit fills).  prim of every slot is numbered as trace_rays numbers it.  hits outside 1 .. RVPT_HIP_RAY_MAX_HITS fails here, before any call.
+    bool trace_rays(rvpt_ray_hit *records, size_t n, int hits);
+    // the same for n groups in device memory of the context's GPU (16-byte aligned): prim stays as the LIBRARY numbers it, as for trace_rays_device above
+    bool trace_rays_device(void *records, size_t n, int hits);
     // Path queries (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_PATHS; include/rvpt_hip.h: PATH QUERIES): every record comes in as a ray, an RNG state and a bounce
     // budget (org, seed, dir, max_bounces) and goes out as integrator_Kajiya's radiance along it and the segments the path traced, in place.  After
     // initialize(); no update() is needed.  Nothing is renumbered: radiance does not depend on the order of the triangles.

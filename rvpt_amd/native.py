@@ -27,6 +27,8 @@ BRUTE_MIXED_PACKETS = 0x200  # brute-force contexts: round 2's mixed-packet fram
 FORMAT_RGBA32F, FORMAT_RGBA8_UNORM = 0, 1
 FORMAT_RAY_HITS = 2  # RVPT_HIP_FORMAT_RAY_HITS: rvpt_hip_read answers ray queries, `dst` holds RAY_HIT_DTYPE records (Context.trace_rays)
 RAY_ANY_HIT = 0x1  # RVPT_HIP_RAY_ANY_HIT: a record's flag — stop at the first accepted triangle
+RAY_MAX_HITS = 8  # RVPT_HIP_RAY_MAX_HITS: the largest k of a k-nearest ray query
+
 NO_PRIM = 0xFFFFFFFF  # a record's prim after a miss
 # rvpt_ray_hit (48 B): org, tmax, dir, flags come in, t, prim, u, v go out
 RAY_HIT_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("flags", "<u4"), ("t", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4")])
@@ -42,6 +44,14 @@ def format_ray_paths_mode(mode) -> int:
     if not 0 <= int(mode) <= PATH_MODE_KAJIYA:
         raise NativeError(ERR_INVALID, f"path query: mode {int(mode)} is outside 0 .. 9; integrator_Hart and the modes that default to it are not part of the form")
     return 16 + int(mode)
+
+
+def FORMAT_RAY_HITS_NEAREST(k) -> int:
+    """RVPT_HIP_FORMAT_RAY_HITS_NEAREST(k), formats 33 .. 40: `dst` holds groups of k RAY_HIT_DTYPE records, the ray in the first, its k nearest hits out
+    (Context.trace_rays(..., hits=k)).  A k that is no int in 1 .. RAY_MAX_HITS raises before any call."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= RAY_MAX_HITS:
+        raise NativeError(ERR_INVALID, f"hits must be an int in 1 .. {RAY_MAX_HITS}, got {k!r}")
+    return 32 + int(k)
 PATH_MAX_BOUNCES = 1024  # RVPT_HIP_PATH_MAX_BOUNCES: a record with a larger bounce budget, or with none, is invalid (radiance 0, segments 0)
 # rvpt_ray_path (48 B): org, seed, dir, max_bounces come in, radiance and segments go out
 RAY_PATH_DTYPE = np.dtype([("org", "<f4", (3,)), ("seed", "<u4"), ("dir", "<f4", (3,)), ("max_bounces", "<u4"), ("radiance", "<f4", (3,)), ("segments", "<u4")])
@@ -690,7 +700,7 @@ class Context:
         """(pointer, bytes, object to keep alive) of a whole frame in a numpy array or a torch tensor — contiguous float32[h, w, 4] (FORMAT_RGBA32F) or
         uint8[h, w, 4] (FORMAT_RGBA8_UNORM); resolved the way _triangle_source resolves triangles: a tensor on this context's device is passed as device memory
         once the stream that last touched it has finished, and torch is imported only when a tensor is given.  Checked here, before the call."""
-        if fmt in (FORMAT_RAY_HITS, FORMAT_RAY_PATHS) or (isinstance(fmt, int) and 16 <= fmt <= 16 + PATH_MODE_KAJIYA):  # known formats, but of records and not of a frame
+        if fmt in (FORMAT_RAY_HITS, FORMAT_RAY_PATHS) or (isinstance(fmt, int) and (16 <= fmt <= 16 + PATH_MODE_KAJIYA or 33 <= fmt <= 32 + RAY_MAX_HITS)):  # known formats, but of records and not of a frame
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use trace_rays_into / trace_paths_into")
         if fmt == FORMAT_TRIANGLES:
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds the stored triangle rows, not a frame: use read_triangles / read_triangles_into")
@@ -733,10 +743,14 @@ class Context:
         del keep
         return dst
 
-    def trace_rays(self, org, dir, tmax=math.inf, any_hit=False) -> np.ndarray:
+    def trace_rays(self, org, dir, tmax=math.inf, any_hit=False, hits=None) -> np.ndarray:
         """Closest (any_hit: first accepted) hit of the rays org[n, 3] + t dir[n, 3], 0 < t < tmax, against the uploaded scene — include/rvpt_hip.h: RAY QUERIES
         has the order a query walks and the numbering of prim.  tmax and any_hit are scalars or one value per ray.  Returns RAY_HIT_DTYPE[n]: t, prim, u, v of
-        the hit, prim == NO_PRIM where there is none."""
+        the hit, prim == NO_PRIM where there is none.  hits=k (1 .. RAY_MAX_HITS) asks for the k nearest hits of every ray (K-NEAREST RAY QUERIES; any_hit:
+        the first k accepted) and returns RAY_HIT_DTYPE[n, k], record j of a row the j-th hit, prim == NO_PRIM from the first slot no hit fills; the ray is
+        repeated in every record's in fields."""
+        if hits is not None:
+            FORMAT_RAY_HITS_NEAREST(hits)  # (before anything else: a refusal needs no arrays)
         org = np.asarray(org, dtype=np.float32).reshape(-1, 3)
         dirv = np.asarray(dir, dtype=np.float32).reshape(-1, 3)
         if org.shape != dirv.shape:
@@ -745,13 +759,29 @@ class Context:
         rec["org"], rec["dir"] = org, dirv
         rec["tmax"] = np.asarray(tmax, dtype=np.float32)
         rec["flags"] = np.where(np.asarray(any_hit, dtype=bool), RAY_ANY_HIT, 0).astype(np.uint32)
+        if hits is not None:
+            return self.trace_rays_into(np.ascontiguousarray(np.repeat(rec[:, None], int(hits), axis=1)), hits=hits)
         return self.trace_rays_into(rec)
 
-    def trace_rays_into(self, records):
+    def trace_rays_into(self, records, hits=None):
         """rvpt_hip_read with FORMAT_RAY_HITS in the caller's memory: `records` is a contiguous RAY_HIT_DTYPE array, or a contiguous float32 torch tensor [n, 12]
         (48-byte records) on the host or on this context's device — resolved the way _frame_buffer resolves frames; device records never visit the host.  The
-        in fields stay as they are, the out fields are written.  Returns records."""
-        return self._query_into(records, FORMAT_RAY_HITS, RAY_HIT_DTYPE, "trace_rays_into", "RAY_HIT_DTYPE")
+        in fields stay as they are, the out fields are written.  Returns records.  hits=k (1 .. RAY_MAX_HITS): the call goes out with
+        FORMAT_RAY_HITS_NEAREST(k) and `records` holds n groups of k records — a RAY_HIT_DTYPE array shaped (n * k,) or (n, k), or a tensor [n * k, 12]; record
+        0 of a group carries the ray, the out quad of record j receives the j-th hit.  A record count that is no multiple of k raises before any call."""
+        if hits is None:
+            return self._query_into(records, FORMAT_RAY_HITS, RAY_HIT_DTYPE, "trace_rays_into", "RAY_HIT_DTYPE")
+        fmt = FORMAT_RAY_HITS_NEAREST(hits)
+        k = int(hits)
+        if isinstance(records, np.ndarray):
+            if records.ndim == 2 and records.shape[1] != k:
+                raise NativeError(ERR_INVALID, f"trace_rays_into: hits={k} needs RAY_HIT_DTYPE[n, {k}] or [n * {k}], got shape {tuple(records.shape)}")
+            count = records.size
+        else:
+            count = int(records.shape[0]) if hasattr(records, "data_ptr") and records.dim() == 2 else 0  # (_query_into refuses what is no tensor [n, 12])
+        if count % k:
+            raise NativeError(ERR_INVALID, f"trace_rays_into: {count} records are not a multiple of hits={k}: a ray takes a group of {k} records")
+        return self._query_into(records, fmt, RAY_HIT_DTYPE, "trace_rays_into", "RAY_HIT_DTYPE")
 
     def _query_into(self, records, fmt: int, dtype, what: str, dtype_name: str):
         is_tensor = not isinstance(records, np.ndarray) and hasattr(records, "data_ptr")

@@ -427,13 +427,14 @@ class RVPT:
             return self._ctx.read_into(out, fmt)
         return self._ctx.read(fmt)
 
-    def trace_rays(self, org, dir, tmax=float("inf"), any_hit=False) -> np.ndarray:
+    def trace_rays(self, org, dir, tmax=float("inf"), any_hit=False, hits=None) -> np.ndarray:
         """Ray queries against the scene as it is now (Context.trace_rays; include/rvpt_hip.h: RAY QUERIES): closest — any_hit: first accepted — hit of every ray
         org + t dir, 0 < t < tmax.  Returns native.RAY_HIT_DTYPE records; prim numbers the triangles in the order they were ADDED (native.NO_PRIM: a miss), as
-        update_triangles' indices do.  Needs initialize(), not update(): a query has no camera."""
+        update_triangles' indices do.  Needs initialize(), not update(): a query has no camera.  hits=k (1 .. native.RAY_MAX_HITS) returns records [n, k]: the
+        k nearest hits of every ray, nearest first (K-NEAREST RAY QUERIES), prim numbered the same way."""
         if self._ctx is None:
             raise RuntimeError("trace_rays before initialize()")
-        rec = self._ctx.trace_rays(org, dir, tmax, any_hit)
+        rec = self._ctx.trace_rays(org, dir, tmax, any_hit) if hits is None else self._ctx.trace_rays(org, dir, tmax, any_hit, hits=hits)
         if not self._device_built and rec.shape[0]:  # a host-built tree: the device numbers the leaf order it was given
             hit = rec["prim"] != native.NO_PRIM
             rec["prim"][hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[rec["prim"][hit]]
@@ -513,10 +514,15 @@ class RVPT:
         rec["prim"] = given.astype(np.uint32)
         return rec
 
-    def pick(self, x: int, y: int):
+    def pick(self, x: int, y: int, hits=None):
         """What is under pixel (x, y) of the current camera: (prim, t) of the closest hit along the pixel-centre ray, or None.  The ray is made HERE, on the host, from
         scene_camera.get_data() (camera.glsl:29-51 in double, rounded to float32 once) — not by the frame kernel's float32 arithmetic: t agrees with a frame's to
-        rounding, not to the bit.  Pinhole camera only."""
+        rounding, not to the bit.  Pinhole camera only.  hits=k (1 .. native.RAY_MAX_HITS) is the x-ray pick: the list of (prim, t) of the k nearest surfaces
+        along that ray, nearest first, shorter where the ray meets fewer and empty on a miss."""
+        if hits is not None:
+            native.FORMAT_RAY_HITS_NEAREST(hits)
+            if self._ctx is None:
+                raise RuntimeError("pick before initialize()")
         if self.scene_camera.mode != 0:
             raise ValueError("pick: only the pinhole camera (mode 0) has a pixel-centre ray made here")
         if not (0 <= int(x) < self.width and 0 <= int(y) < self.height):
@@ -526,6 +532,8 @@ class RVPT:
         cx, cy = (int(x) + 0.5) / self.width, 1.0 - (int(y) + 0.5) / self.height  # compute_pass.comp:151-156
         d = m[:3, :3] @ np.array([cam[16] * (2.0 * cx - 1.0), 2.0 * cy - 1.0, 1.0 / np.tan(0.5 * cam[17])])
         d /= np.linalg.norm(d)
+        if hits is not None:
+            return [(int(r["prim"]), float(r["t"])) for r in self.trace_rays(m[:3, 3], d, hits=hits)[0] if r["prim"] != native.NO_PRIM]
         rec = self.trace_rays(m[:3, 3], d)[0]
         return None if rec["prim"] == native.NO_PRIM else (int(rec["prim"]), float(rec["t"]))
 

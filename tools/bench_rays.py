@@ -9,7 +9,13 @@ usage: tools/bench_rays.py rates [default cornell terrain]     on the GPU box: r
        tools/bench_rays.py queries [scene]                     a few device-record queries and nothing else: the run to put under rocprofv3
        tools/bench_rays.py resources <parent tree>             where hipcc and a checkout of the parent commit are: VGPR, SGPR, scratch and static LDS of every frame
                                                                kernel there and here (tools/kernel_resources.py), and of the query kernels
-Each mode rewrites its own section of profiles/ray_queries.txt and leaves the other."""
+       tools/bench_rays.py nearest <label> [scenes]            k-nearest queries (FORMAT_RAY_HITS_NEAREST(k)) on the same 2 M camera rays from device records: k = 1, 2, 4
+                                                               and 8 beside format 2 in the same run — Grays/s, hits returned per second, and the ratio to k sequential
+                                                               format-2 calls.  <label> names the block the run writes ("this tree", "parent, before", ...); with
+                                                               RVPT_HIP_LIB naming a library that has no such format (the parent commit's) the block holds format 2
+                                                               alone, three passes, which is the yardstick for format 2's own rate
+Each mode rewrites its own section of profiles/ray_queries.txt and leaves the others; `nearest` rewrites the block of its label inside its section."""
+import os
 import statistics
 import sys
 import time
@@ -24,13 +30,34 @@ MARK = "==== kernel resources"
 W, H = 1920, 1080
 
 
+MARK_NEAREST = "==== k nearest hits"
+BLOCK = "---- block: "
+
+
 def write_section(text, resources):
     old = OUT.read_text() if OUT.exists() else ""
+    old, sep, nearest = old.partition(MARK_NEAREST)  # (the last section: kept as it is)
+    nearest = ("\n" + sep + nearest) if sep else ""
     head, _, tail = old.partition(MARK)
     if resources:
-        OUT.write_text(head.rstrip("\n") + ("\n\n" if head.strip() else "") + MARK + text)
+        OUT.write_text(head.rstrip("\n") + ("\n\n" if head.strip() else "") + MARK + text.rstrip("\n") + "\n" + nearest)
     else:
-        OUT.write_text(text.rstrip("\n") + "\n" + ("\n" + MARK + tail if tail else ""))
+        OUT.write_text(text.rstrip("\n") + "\n" + ("\n" + MARK + tail.rstrip("\n") + "\n" if tail else "") + nearest)
+
+
+def write_nearest_block(label, text):
+    """the block `label` of the k-nearest section replaced (or added behind the others); everything in front of the section stays"""
+    old = OUT.read_text() if OUT.exists() else ""
+    front, _, section = old.partition(MARK_NEAREST)
+    blocks = {}
+    for part in section.split(BLOCK)[1:]:
+        name, _, body = part.partition(" ----\n")
+        blocks[name] = body.rstrip("\n")
+    blocks[label] = text.rstrip("\n")
+    out = front.rstrip("\n") + "\n\n" + MARK_NEAREST + " (tools/bench_rays.py nearest <label>: one block per process, in the order they ran) ====\n"
+    for name, body in blocks.items():
+        out += "\n" + BLOCK + name + " ----\n" + body + "\n"
+    OUT.write_text(out)
 
 
 def scenes(names):
@@ -126,6 +153,59 @@ def rates(names):
     write_section(text, resources=False)
 
 
+def nearest(label, names):
+    import torch
+    from rvpt_amd import native
+    lib = os.environ.get("RVPT_HIP_LIB", "librvpt_hip.so (this tree's)")
+    n = W * H
+    lines = [f"library: {Path(lib).name}; {n} pixel-centre camera rays in pixel order, closest hit, tmax = inf, device records; wall clock around the call, 7 calls after 2",
+             "Grays/s counts rays; a k-nearest call takes n * k records.  `k x format 2` is k format-2 calls on the same records one after the other, timed together:",
+             "what a caller who re-traces pays at the least (the new origins are not even made).", ""]
+
+    def timed(fn, reps=7, warm=2):
+        for _ in range(warm):
+            fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts), min(ts), max(ts)
+
+    for name, tris, mats, nodes, cam in scenes(names):
+        lines.append(f"== {name}: {tris.shape[0]} triangles ==")
+        ctx = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BVH)
+        ctx.upload_scene(nodes, tris, mats)
+        rec = camera_records(cam)
+        dev = torch.from_numpy(rec.view(np.float32).reshape(-1, 12)).to("cuda:0")
+        for p in range(3):  # format 2's own rate, three passes: the figure that is compared with the parent commit's library
+            med, lo, hi = timed(lambda: ctx.trace_rays_into(dev))
+            lines.append(f"format 2, pass {p + 1}:            median {n / med / 1e9:7.3f}   min {n / hi / 1e9:7.3f}   max {n / lo / 1e9:7.3f}   Grays/s")
+        t2 = med
+        try:
+            ctx.trace_rays_into(dev[:8].clone(), hits=2)
+            has_form = True
+        except native.NativeError as e:
+            has_form = False
+            lines.append(f"no k-nearest form in this library ({str(e)[:60]}): format 2 alone")
+        for k in (1, 2, 4, 8) if has_form else ():
+            groups = np.zeros((n, k), dtype=native.RAY_HIT_DTYPE)
+            groups[:, 0] = rec
+            devk = torch.from_numpy(groups.view(np.float32).reshape(-1, 12)).to("cuda:0")
+            med, lo, hi = timed(lambda: ctx.trace_rays_into(devk, hits=k))
+            seq, _, _ = timed(lambda: [ctx.trace_rays_into(dev) for _ in range(k)], reps=5, warm=1)
+            got = devk.cpu().numpy().view(native.RAY_HIT_DTYPE).reshape(n, k)
+            held = int((got["prim"] != native.NO_PRIM).sum())
+            lines.append(f"k = {k}: median {n / med / 1e9:7.3f}   min {n / hi / 1e9:7.3f}   max {n / lo / 1e9:7.3f}   Grays/s   {held} hits returned = {held / med / 1e9:7.3f} Ghits/s   "
+                         f"{k} x format 2: {seq * 1e3:8.2f} ms against {med * 1e3:8.2f} ms = {seq / med:5.2f} x   (format 2 alone: {t2 * 1e3:.2f} ms)")
+            del devk, groups, got
+        ctx.close()
+        lines.append("")
+    text = "\n".join(lines)
+    print(text)
+    write_nearest_block(label, text)
+
+
 def queries(names):
     import torch
     from rvpt_amd import native
@@ -177,5 +257,8 @@ if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "rates"
     if mode == "resources":
         sys.exit(0 if resources(sys.argv[2]) else 1)
+    if mode == "nearest":
+        nearest(sys.argv[2], sys.argv[3:] or ["default", "cornell", "terrain"])
+        sys.exit(0)
     names = sys.argv[2:] or ["default", "cornell", "terrain"]
     rates(names) if mode == "rates" else queries(names)

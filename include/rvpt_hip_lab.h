@@ -5,7 +5,7 @@
  *   - diagnostics of the arithmetic specification and of the packet kernel's exact culls (rvpt_hip_selftest_*),
  *   - the host-side forms of data the kernels consume, GPU-free (rvpt_camera_rects, rvpt_bounce_rows, rvpt_claim_order, rvpt_bvh_wide_form),
  *   - the tuning knobs the sweeps of rounds 1-5 found flat (RVPT_HIP_BVH_WIDE, _WIDE_RESIDENT, _NO_RESIDENT, _NO_PACKED_HEADS, _CALLER_LAYOUT, _TOP_NODES,
- *     _STACK_LDS, _REFILL, _LEAF_BATCH, _CAM_MIN, _DETACH, _FORCE_STACK_LEVELS, RVPT_HIP_BRUTE_PACKETS, RVPT_HIP_PACKETS_LEAN_INSTANCE, RVPT_HIP_PACKETS_ROW_BOXES, _BLOCKS_PER_CU, _FIRST_UNITS, _CLAIM_UNITS,
+ *     _STACK_LDS, _REFILL, _LEAF_BATCH, _CAM_MIN, _DETACH, _FORCE_STACK_LEVELS, RVPT_HIP_BRUTE_PACKETS, RVPT_HIP_PACKETS_LEAN_INSTANCE, RVPT_HIP_PACKETS_ROW_BOXES, RVPT_HIP_PACKETS_ROW_RULE (read at upload_scene), _BLOCKS_PER_CU, _FIRST_UNITS, _CLAIM_UNITS,
  *     RVPT_HIP_TIMELINE): the release library reads none of them,
  *   - the kernels' internal checks (RVPT_HIP_DEBUG=1: a traversal-stack overflow is reported by rvpt_hip_wait).
  * rvpt_hip_build_flags() tells the two builds apart.  The release library reads: RVPT_HIP_QUIET, RVPT_HIP_DEBUG (refused without the checks),

@@ -235,6 +235,7 @@ struct rvpt_hip_ctx {
     float4 *d_row_boxes = nullptr;            // ... and every row's own boxes, two float4 per leaf, 32 / kLeafTris * vis_words leaves per row
     size_t row_boxes_cap = 0;                 // in float4
     bool have_row_boxes = false;              // made for the scene in d_prep
+    bool row_rule_tight = false;              // ... with the tight rule (rvpt_vis.h: kRowRuleTight; the laboratory build's RVPT_HIP_PACKETS_ROW_RULE=0: round 8's rule)
     uint32_t vis_words = 0;                   // 0: no table for this scene
     double scene_scale = 0.0;                 // largest |coordinate| + largest extent of the uploaded triangles: what float errors of positions scale with
     // screen rectangles of the triangles for the packet kernel's camera rounds (rvpt_rect.h), one buffer per launch slot: rewritten (camera_rects, on the
@@ -499,6 +500,7 @@ bool has_global_stack(Variant v) { return v == Variant::Bvh || v == Variant::Wid
 constexpr uint32_t kCullRects = 1u, kCullBounce = 2u, kCullBlockRounds = 4u, kCullLeafBoxes = 16u, kCullClaimOrder = 32u, kCullLeanInstance = 64u, kCullSkyList = 128u;
 constexpr uint32_t kCullRowBoxes = 256u;
 constexpr uint32_t kCullFrameRuns = 512u;  // ... and the listed launch in frame-run order with run headers (trace_brute_packets_aa1_culls_listed_runs)
+constexpr uint32_t kCullRowRuleTight = 1024u;  // ... and the row boxes it rode with were made by the tight rule (rvpt_vis.h: kRowRuleTight)
 
 struct Launch {
     Kernel kernel;
@@ -887,7 +889,8 @@ int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, i
     }
     l.cull_bits = (cull ? kCullRects : 0u) | (p.vis ? kCullBounce : 0u) | ((v == Variant::BrutePackets && p.first_units % 4u == 0u) ? kCullBlockRounds : 0u) |
                   (p.leaf_boxes ? kCullLeafBoxes : 0u) | (p.perm_groups != 0u ? kCullClaimOrder : 0u) | (lean ? kCullLeanInstance : 0u) | (l.listed ? kCullSkyList : 0u) |
-                  (p.row_boxes ? kCullRowBoxes : 0u) | ((l.listed && l.work.run_frames != 0u) ? kCullFrameRuns : 0u);
+                  (p.row_boxes ? kCullRowBoxes : 0u) | ((l.listed && l.work.run_frames != 0u) ? kCullFrameRuns : 0u) |
+                  ((p.row_boxes && ctx->row_rule_tight) ? kCullRowRuleTight : 0u);
     return 0;
 }
 
@@ -1124,11 +1127,16 @@ static int derive_bounce_state(rvpt_hip_ctx *ctx, bool bvh, const rvpt_triangle 
             // ... and the row boxes (rvpt_vis.h): every row's refined words and its own box per leaf, from the records and the leaf boxes just copied
             if ((rc = grow(ctx, ctx->d_row_bits, ctx->row_bits_cap, total, sizeof(uint32_t)))) return rc;
             if ((rc = grow(ctx, ctx->d_row_boxes, ctx->row_boxes_cap, static_cast<size_t>(2) * n * 2 * n_leaves, sizeof(float4)))) return rc;
+            bool tight = true;
+#if RVPT_HIP_LAB
+            if (const char *e = getenv("RVPT_HIP_PACKETS_ROW_RULE")) tight = atoi(e) > 0;  // read at every upload: 0 = the tables of round 8's rule (A/B, bit-exactness)
+#endif
             hipLaunchKernelGGL(rv::bounce_row_boxes, dim3(static_cast<uint32_t>((total + 63) / 64)), dim3(64), 0, ctx->stream, ctx->d_prep, n, scale, words, stride,
-                               reinterpret_cast<const float *>(ctx->d_leaf_boxes), ctx->d_row_bits, reinterpret_cast<float *>(ctx->d_row_boxes));
+                               reinterpret_cast<const float *>(ctx->d_leaf_boxes), ctx->d_row_bits, reinterpret_cast<float *>(ctx->d_row_boxes), tight ? 1u : 0u);
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             ctx->have_row_boxes = true;
+            ctx->row_rule_tight = tight;
         }
     }
     return 0;

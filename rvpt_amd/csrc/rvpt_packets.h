@@ -71,9 +71,10 @@ __global__ void sky_list(const FrameParams p, const uint32_t *__restrict__ sky_b
 // seen from side s (s = 0: the side A's normal cross(e0, e1) points to), by more than `margin`, and both triangles are well shaped; bits >= n are 0
 __global__ void bounce_visibility(const float4 *__restrict__ prep, uint32_t n, double margin, uint32_t words, uint32_t stride, uint32_t *__restrict__ out);
 // the row boxes of the same table (rvpt_vis.h: bounce_row_boxes_word): refined[(2 A + s) * stride + w] and the 32 / kLeafTris boxes of that word at
-// boxes[8 * ((2 A + s) * (32 / kLeafTris) * words + (32 / kLeafTris) * w)]; leaf_boxes: bounce_leaf_boxes' array padded to whole words; one thread per (row, word)
+// boxes[8 * ((2 A + s) * (32 / kLeafTris) * words + (32 / kLeafTris) * w)]; leaf_boxes: bounce_leaf_boxes' array padded to whole words; one thread per (row, word);
+// tight != 0: the tight rule (kRowRuleTight), 0: round 8's (kRowRuleShipped)
 __global__ void bounce_row_boxes(const float4 *__restrict__ prep, uint32_t n, double scale, uint32_t words, uint32_t stride, const float *__restrict__ leaf_boxes,
-                                 uint32_t *__restrict__ refined, float *__restrict__ boxes);
+                                 uint32_t *__restrict__ refined, float *__restrict__ boxes, uint32_t tight);
 #if RVPT_HIP_LAB
 // diagnostics (rvpt_hip_selftest_bounce_cull): every pixel x n_samples paths traced against EVERY triangle; on segments that leave a triangle, out[0] += pairs the
 // float test accepts with the interval wide open, out[1] += those whose triangle is NOT in the row of where the segment leaves from (must stay 0), out[2] += those whose

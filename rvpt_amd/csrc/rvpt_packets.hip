@@ -589,7 +589,7 @@ __global__ void bounce_visibility(const float4 *__restrict__ prep, uint32_t n, d
 }
 
 __global__ void bounce_row_boxes(const float4 *__restrict__ prep, uint32_t n, double scale, uint32_t words, uint32_t stride, const float *__restrict__ leaf_boxes,
-                                 uint32_t *__restrict__ refined, float *__restrict__ boxes)
+                                 uint32_t *__restrict__ refined, float *__restrict__ boxes, uint32_t tight)
 {
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= 2u * n * stride) return;
@@ -599,7 +599,8 @@ __global__ void bounce_row_boxes(const float4 *__restrict__ prep, uint32_t n, do
         return;
     }
     constexpr uint32_t kPerWord = 32u / kLeafTris;
-    refined[id] = bounce_row_boxes_word(reinterpret_cast<const float *>(prep), n, row, w, scale, leaf_boxes, boxes + 8u * (static_cast<size_t>(row) * kPerWord * words + kPerWord * w));
+    refined[id] = bounce_row_boxes_word_rule(tight ? kRowRuleTight : kRowRuleShipped, reinterpret_cast<const float *>(prep), n, row, w, scale, leaf_boxes,
+                                             boxes + 8u * (static_cast<size_t>(row) * kPerWord * words + kPerWord * w));
 }
 
 __global__ void camera_rects(const FrameParams p, uint2 *__restrict__ rects, float4 *__restrict__ records)

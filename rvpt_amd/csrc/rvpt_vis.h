@@ -157,15 +157,49 @@ constexpr double kBounceCameraScales = 64.0;     // ... which is: the camera (th
 // or whose refined bit is cleared: 0).
 constexpr double kRowSlackScales = 0x1p-14;
 
+// ---- the TIGHT rule of the row boxes ----------------------------------------------------------------------------------------------------------------------
+// The rule above spends eight times the slack its derivation asks for, and on the headline frame that slack is what the bounce rounds walk: the rays start at
+// eps = 0.005 over the leaving plane, INSIDE boxes widened by M = 0.0063, and the coplanar neighbours whose corners rise 0.002 - 0.004 over that plane stay in the
+// row (H0 = +0.0016).  The tight rule spends TWICE what the derivation asks for, term by term, and widens every member by what that member needs:
+//   H0(B) = eps - margin / 4 - 2^-14 E' - E_B                     (the headline: +0.0039)
+//   W_B   = 2.5 E_B + 2^-16 E'   around B's clipped polygon, per member, before the leaf's union (the leaf does not take one M)
+// H0.  The derivation above holds as written, and nothing in it is particular to the old constants: height(o) >= eps - 2^-13 scale - 2^-22 eps - 2^-23 E' (the
+//   accepted hit's position error under the launch-time premise of a camera within 64 scales, the unit normal's and the fma's rounding), the descent up to Y is
+//   <= 2^-16 E', so every point of the exact ray with t > 0 that matters has height >= eps - 2^-13 scale - 2^-15 E' (2^-16 + 2^-22 + 2^-23 < 2^-15), and the X of B
+//   that an accepted pair needs has height(X) >= eps - 2^-13 scale - 2^-15 E' - E_B.  margin / 4 = 2^-12 scale is twice the first term, 2^-14 E' twice the second;
+//   E_B is the bound itself (rvpt_rect.h), taken once as above.  No term was found that the derivation misses: the divisor is 4, the largest power of two that
+//   leaves a factor of two on the position error (8 would leave none).
+// W_B.  X lies in B's clipped polygon {height >= H0(B)} and |Y - X| <= E_B, so Y lies inside the polygon's bounds widened by E_B.  What the widening pays besides:
+//   the slab test's own error, <= 2^-21 (|b| + |o|) |inv| in t (leaf boxes, above), i.e. <= 2^-21 * 2 E' = 2^-20 E' in position along the axis — a sixteenth of the
+//   2^-16 E' term; and the rounding of the box to float (to nearest, not outward): <= 2^-24 of a coordinate <= 2^-24 E'.  Needed: E_B + 2^-20 E' + 2^-24 E'; spent:
+//   2.5 E_B + 2^-16 E', so E_B <= 0.4 W_B as the leaf boxes' proof has it, with 1.5 E_B and more than 7/8 of the 2^-16 E' left over.
+// Premises: A and B finite, non-degenerate, kappa >= 2^-6, a scene that has a scale — as above, with the same fallbacks (A fails: the shared leaf boxes and the
+//   table's words; B fails: its leaf's shared box in that row, and B's bit stays).  The premise E_B <= 0.4 M is NO LONGER NEEDED for a member's own widening — W_B
+//   is made from E_B, whatever it is.  The rule still sends a member beyond it to the shared box and caps W_B at M (where E_B <= 0.4 M, M is enough by the old
+//   rule's proof; the cap bites only for 0.4 M (1 - 2^-7) < E_B <= 0.4 M), for one reason only: with H0 no lower than the old rule's, every tight box then lies
+//   inside the old rule's box of the same (row, leaf) and every tight row inside the old row — which the tests check, and which makes the old rule's selftest
+//   and fuzz history evidence for the new one.
+// Checked: tests/test_row_boxes_tight.py (float64 restatement, GPU-free), tests/test_row_boxes_tight_gpu.py (selftest out[7], bit-exact frames against the old rule).
+struct RowRule {
+    double margin_div;    // H0 spends margin / margin_div
+    double slack_scales;  // ... and slack_scales * E'
+    bool per_member;      // the widening: true = W_B = kRowWidenEB * E_B + kRowWidenScales * E' (at most M) around every member's clipped part; false = one M around the leaf's union
+};
+constexpr double kRowWidenEB = 2.5, kRowWidenScales = 0x1p-16;
+constexpr RowRule kRowRuleShipped = {1.0, kRowSlackScales, false};  // (round 8; RVPT_HIP_PACKETS_ROW_RULE=0 in the laboratory build)
+constexpr RowRule kRowRuleTight = {4.0, kRowSlackScales, true};
+
 // One word w of the refined row `row` (returned) and the boxes of its 32 / kLeafTris leaves (boxes_out: 8 floats each — lo.xyz, hi.xyz, 0, 0).  prep, n, row, w:
 // bounce_row_word's; scale = bounce_scene_scale; leaf_boxes = bounce_leaf_boxes' array, padded to whole words (leaf 32 / kLeafTris * w + k at 8 floats each)
-RV_HD uint32_t bounce_row_boxes_word(const float *prep, const uint32_t n, const uint32_t row, const uint32_t w, const double scale, const float *leaf_boxes, float *boxes_out)
+RV_HD uint32_t bounce_row_boxes_word_rule(const RowRule rule, const float *prep, const uint32_t n, const uint32_t row, const uint32_t w, const double scale, const float *leaf_boxes,
+                                          float *boxes_out)
 {
     constexpr uint32_t kPerWord = 32u / kLeafTris;
     const double eps = static_cast<double>(kEpsilon);
     const double margin = kBounceMarginScales * scale;
     const double Es = scale + 2.0 * eps;
     const double M = kLeafBoxMarginScales * (scale + 2.0 * 0.005);  // bounce_group_boxes' M
+    const double Wleaf = rule.per_member ? 0.0 : M;                 // (x - 0.0 == x: one body serves both forms, and the old rule's output stays byte for byte)
     const uint32_t bits = bounce_row_word(prep, n, row, w, margin);
     const uint32_t A = row >> 1;
     const double side = (row & 1u) ? -1.0 : 1.0;
@@ -208,7 +242,9 @@ RV_HD uint32_t bounce_row_boxes_word(const float *prep, const uint32_t n, const 
                 shared = true;
                 continue;
             }
-            const double H0 = eps - margin - kRowSlackScales * Es - EB;
+            const double H0 = eps - margin / rule.margin_div - rule.slack_scales * Es - EB;
+            const double WB = kRowWidenEB * EB + kRowWidenScales * Es;
+            const double W = rule.per_member ? (WB < M ? WB : M) : 0.0;
             const bool up[3] = {h[0] >= H0, h[1] >= H0, h[2] >= H0};
             if (!(up[0] || up[1] || up[2])) {  // wholly below H0: no segment that leaves (A, s) is accepted by B
                 refined &= ~(1u << b);
@@ -218,12 +254,12 @@ RV_HD uint32_t bounce_row_boxes_word(const float *prep, const uint32_t n, const 
             for (int v = 0; v < 3; ++v) {
                 const int u = v == 2 ? 0 : v + 1;
                 if (up[v])
-                    for (int c = 0; c < 3; ++c) lo[c] = p[v][c] < lo[c] ? p[v][c] : lo[c], hi[c] = p[v][c] > hi[c] ? p[v][c] : hi[c];
+                    for (int c = 0; c < 3; ++c) lo[c] = p[v][c] - W < lo[c] ? p[v][c] - W : lo[c], hi[c] = p[v][c] + W > hi[c] ? p[v][c] + W : hi[c];
                 if (up[v] != up[u]) {  // the edge v -> u crosses the plane height = H0 (h[u] != h[v])
                     const double s = (H0 - h[v]) / (h[u] - h[v]);
                     for (int c = 0; c < 3; ++c) {
                         const double x = p[v][c] + s * (p[u][c] - p[v][c]);
-                        lo[c] = x < lo[c] ? x : lo[c], hi[c] = x > hi[c] ? x : hi[c];
+                        lo[c] = x - W < lo[c] ? x - W : lo[c], hi[c] = x + W > hi[c] ? x + W : hi[c];
                     }
                 }
             }
@@ -231,12 +267,18 @@ RV_HD uint32_t bounce_row_boxes_word(const float *prep, const uint32_t n, const 
         float *o = boxes_out + 8u * k;
         const float *sb = leaf_boxes + 8u * (kPerWord * w + k);
         for (int c = 0; c < 3; ++c) {
-            o[c] = shared ? sb[c] : (any ? static_cast<float>(lo[c] - M) : inf);
-            o[3 + c] = shared ? sb[3 + c] : (any ? static_cast<float>(hi[c] + M) : -inf);
+            o[c] = shared ? sb[c] : (any ? static_cast<float>(lo[c] - Wleaf) : inf);
+            o[3 + c] = shared ? sb[3 + c] : (any ? static_cast<float>(hi[c] + Wleaf) : -inf);
         }
         o[6] = o[7] = 0.0f;
     }
     return refined;
+}
+
+// the rule of round 8: {the whole margin, 2^-14 E', one M around the leaf's union}
+RV_HD uint32_t bounce_row_boxes_word(const float *prep, const uint32_t n, const uint32_t row, const uint32_t w, const double scale, const float *leaf_boxes, float *boxes_out)
+{
+    return bounce_row_boxes_word_rule(kRowRuleShipped, prep, n, row, w, scale, leaf_boxes, boxes_out);
 }
 
 }  // namespace rv

@@ -2,7 +2,7 @@
 // exactly as upload_scene's kernel evaluates them on the device (the same function).  No GPU, no library: tests/test_row_boxes.py compares the output with a
 // float64 restatement in numpy.
 //
-// usage: host_row_boxes <in> <out>
+// usage: host_row_boxes <in> <out> [rule]      rule: 0 (the default) = round 8's rule, 1 = the tight rule (rvpt_vis.h: kRowRuleShipped, kRowRuleTight)
 //   in : uint32 n, then n x 16 floats (reference Triangle records), then n x 16 floats (their prepared records)
 //   out: double scale, uint32 n, words, leaves per word, triangles per leaf; then (scale > 0 only) the table's rows [2 n][words], the refined rows [2 n][words],
 //        the shared leaf boxes [leaves per word * words][8] and the row boxes [2 n][leaves per word * words][8]
@@ -14,10 +14,12 @@
 
 int main(int argc, char **argv)
 {
-    if (argc != 3) {
-        std::fprintf(stderr, "usage: %s <in> <out>\n", argv[0]);
+    const bool rule_ok = argc == 3 || (argc == 4 && (argv[3][0] == '0' || argv[3][0] == '1') && argv[3][1] == '\0');
+    if (!rule_ok) {
+        std::fprintf(stderr, "usage: %s <in> <out> [rule: 0 | 1]\n", argv[0]);
         return 2;
     }
+    const rv::RowRule rule = (argc == 4 && argv[3][0] == '1') ? rv::kRowRuleTight : rv::kRowRuleShipped;
     std::FILE *in = std::fopen(argv[1], "rb");
     uint32_t n = 0;
     if (!in || std::fread(&n, sizeof n, 1, in) != 1 || n == 0 || n > 1024u) {
@@ -49,7 +51,7 @@ int main(int argc, char **argv)
             for (uint32_t w = 0; w < words; ++w) {
                 rows[static_cast<size_t>(row) * words + w] = rv::bounce_row_word(prep.data(), n, row, w, rv::kBounceMarginScales * scale);
                 refined[static_cast<size_t>(row) * words + w] =
-                    rv::bounce_row_boxes_word(prep.data(), n, row, w, scale, leaf.data(), boxes.data() + 8u * (static_cast<size_t>(row) * n_leaves + kPerWord * w));
+                    rv::bounce_row_boxes_word_rule(rule, prep.data(), n, row, w, scale, leaf.data(), boxes.data() + 8u * (static_cast<size_t>(row) * n_leaves + kPerWord * w));
             }
         ok = ok && std::fwrite(rows.data(), sizeof(uint32_t), rows.size(), out) == rows.size() && std::fwrite(refined.data(), sizeof(uint32_t), refined.size(), out) == refined.size() &&
              std::fwrite(leaf.data(), sizeof(float), leaf.size(), out) == leaf.size() && std::fwrite(boxes.data(), sizeof(float), boxes.size(), out) == boxes.size();

@@ -63,7 +63,8 @@ FORMAT_SURFACE_POINTS = 6  # RVPT_HIP_FORMAT_SURFACE_POINTS: rvpt_hip_read answe
 # rvpt_surface_point: 48 bytes, three float4 — prim, u, v as a query reported them (and a reserved word) in; the point of the stored mesh, its material word, its normal out
 SURFACE_POINT_DTYPE = np.dtype([("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("mat", "<u4"), ("normal", "<f4", (3,)), ("reserved", "<u4")])
 CULL_ROW_BOXES = 0x100  # Context.cull_info: the launch rode with the row boxes (rvpt_abi.hip: kCullRowBoxes)
-CULL_SKY_LIST = 0x80  # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
+CULL_ROW_RULE_TIGHT = 0x400  # Context.cull_info: ... made by the tight rule (rvpt_abi.hip: kCullRowRuleTight; rvpt_vis.h: kRowRuleTight)
+CULL_SKY_LIST = 0x80 # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
 CULL_FRAME_RUNS = 0x200  # Context.cull_info: ... in frame-run order, the camera set-up of a block made once per run (rvpt_abi.hip: kCullFrameRuns)
 TILE = 16
 TILE_SHIFT = 3  # RVPT_HIP_TILE_SHIFT: every row of the tile grid is rotated by this many more tiles than the one above (tile ownership)
@@ -985,7 +986,8 @@ class Context:
     def cull_info(self) -> int:
         """rvpt_hip_get_cull_info of the last launch: bit 0 screen rectangles, bit 1 bounce table, bit 2 camera rounds aligned to 16 x 4 blocks, bit 4 leaf boxes,
         bit 5 interleaved claim order, bit 6 the kernel instance without the uncull'd walks, bit 7 (CULL_SKY_LIST) the batched launch that claims only the blocks
-        that are not sky and blends the sky from the RNG, bit 8 (CULL_ROW_BOXES) the row boxes of bounce packets that leave one triangle, bit 9 (CULL_FRAME_RUNS) the listed launch in frame-run order."""
+        that are not sky and blends the sky from the RNG, bit 8 (CULL_ROW_BOXES) the row boxes of bounce packets that leave one triangle, bit 9 (CULL_FRAME_RUNS) the listed launch in frame-run order,
+        bit 10 (CULL_ROW_RULE_TIGHT) those row boxes were made by the tight rule (the laboratory build's RVPT_HIP_PACKETS_ROW_RULE=0 at upload_scene: round 8's)."""
         f = C.c_uint32(0)
         _check(self._L.rvpt_hip_get_cull_info(self._h, C.byref(f)), self._h, self._L)
         return f.value

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """GPU-free: what the culled bounce rounds of the packet kernel walk on the headline frame, as shipped before round 8 (union of the lanes' rows, shared leaf boxes)
-and with the ROW BOXES (rvpt_amd/csrc/rvpt_vis.h: a packet whose rays all leave one triangle on one side walks that row's refined words and its own boxes).
+and with the ROW BOXES (rvpt_amd/csrc/rvpt_vis.h: a packet whose rays all leave one triangle on one side walks that row's refined words and its own boxes),
+made by round 8's rule and by the tight rule.
 A numpy brute-force path tracer in float64 — default scene in BVH-leaf order, default camera, one frame, Lambert bounces with numpy's RNG: statistics, not the
 kernel's samples — packs the bounce rays 64 at a time in block order (16 x 16 tiles row-major, 16 x 4 blocks inside) and applies the library's own tables, written
 by the stand-alone host program rvpt_amd/bin/host_row_boxes (the function upload_scene's kernel runs).  The timeline build measures the same quantity on the GPU
@@ -27,12 +28,16 @@ tris = tris[order]
 prep = prepared_records(tris)
 n = len(tris)
 
-# ---- the library's tables, from the host program
-with tempfile.TemporaryDirectory() as d:
-    src, dst = Path(d) / "scene.bin", Path(d) / "table.bin"
-    src.write_bytes(np.uint32(n).tobytes() + np.ascontiguousarray(tris, np.float32).tobytes() + np.ascontiguousarray(prep, np.float32).tobytes())
-    subprocess.run([str(build.build_host() / "host_row_boxes"), str(src), str(dst)], check=True, capture_output=True)
-    raw = dst.read_bytes()
+# ---- the library's tables, from the host program: round 8's rule and the tight one (rvpt_vis.h: kRowRuleShipped, kRowRuleTight)
+def tables(rule):
+    with tempfile.TemporaryDirectory() as d:
+        src, dst = Path(d) / "scene.bin", Path(d) / "table.bin"
+        src.write_bytes(np.uint32(n).tobytes() + np.ascontiguousarray(tris, np.float32).tobytes() + np.ascontiguousarray(prep, np.float32).tobytes())
+        subprocess.run([str(build.build_host() / "host_row_boxes"), str(src), str(dst), str(rule)], check=True, capture_output=True)
+        return dst.read_bytes()
+
+
+raw = tables(0)
 scale = float(np.frombuffer(raw, np.float64, 1)[0])
 _, words, per_word, per = (int(x) for x in np.frombuffer(raw, np.uint32, 4, 8))
 L = per_word * words
@@ -41,15 +46,19 @@ rows = np.frombuffer(raw, np.uint32, 2 * n * words, off).reshape(2 * n, words)
 refined = np.frombuffer(raw, np.uint32, 2 * n * words, off + rows.nbytes).reshape(2 * n, words)
 leaf_boxes = np.frombuffer(raw, np.float32, 8 * L, off + 2 * rows.nbytes).reshape(L, 8).astype(np.float64)
 row_boxes = np.frombuffer(raw, np.float32, 2 * n * L * 8, off + 2 * rows.nbytes + 8 * L * 4).reshape(2 * n, L, 8).astype(np.float64)
+raw_tight = tables(1)
+refined_tight = np.frombuffer(raw_tight, np.uint32, 2 * n * words, off + rows.nbytes).reshape(2 * n, words)
+row_boxes_tight = np.frombuffer(raw_tight, np.float32, 2 * n * L * 8, off + 2 * rows.nbytes + 8 * L * 4).reshape(2 * n, L, 8).astype(np.float64)
 
 
 def unpack(r):  # [2 n, L * per] bits, padded to whole leaves
     return ((r[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(r.shape[0], -1).astype(bool)
 
 
-bits, fine = unpack(rows), unpack(refined)
+bits, fine, fine_tight = unpack(rows), unpack(refined), unpack(refined_tight)
 print(f"default scene, {n} triangles in BVH-leaf order, scale {scale:.4f}, leaves of {per}; {W} x {H}, one frame")
 print(f"table: {bits.sum() / (2 * n * n):.3f} of the bits set; refined rows: {fine.sum() / (2 * n * n):.3f}; row boxes that are empty: {np.isposinf(row_boxes[:, :(n + per - 1) // per, 0]).mean():.3f}")
+print(f"tight rule: refined rows: {fine_tight.sum() / (2 * n * n):.3f}; row boxes that are empty: {np.isposinf(row_boxes_tight[:, :(n + per - 1) // per, 0]).mean():.3f}")
 
 # ---- paths
 p = prep.astype(np.float64)
@@ -124,11 +133,13 @@ uniform = (rows_of == rows_of[:, :1]).all(1)
 distinct = np.array([len(np.unique(r)) for r in rows_of])
 near_leaf = np.zeros((n_packets, L), bool)
 near_row = np.zeros((n_packets, L), bool)
+near_tight = np.zeros((n_packets, L), bool)
 for s in range(0, n_packets, 512):  # (in slices: a row box per ray and leaf)
     e = min(n_packets, s + 512)
     r = slice(64 * s, 64 * e)
     near_leaf[s:e] = slab(O[r], INV[r], leaf_boxes).reshape(e - s, 64, L).any(1)
     near_row[s:e] = slab(O[r], INV[r], row_boxes[LV[r]]).reshape(e - s, 64, L).any(1)
+    near_tight[s:e] = slab(O[r], INV[r], row_boxes_tight[LV[r]]).reshape(e - s, 64, L).any(1)
 union = bits[rows_of].any(1)                               # [packets, L * per]
 own = fine[rows_of[:, 0]]                                  # the refined row of a uniform packet
 by_leaf = lambda x: x.reshape(n_packets, L, per)
@@ -136,6 +147,9 @@ shipped_tested = by_leaf(union).any(2)
 shipped_walked = (by_leaf(union) & (shipped_tested & near_leaf)[:, :, None]).sum((1, 2))
 row_tested = by_leaf(own).any(2)
 row_walked = (by_leaf(own) & (row_tested & near_row)[:, :, None]).sum((1, 2))
+own_t = fine_tight[rows_of[:, 0]]
+tight_tested = by_leaf(own_t).any(2)
+tight_walked = (by_leaf(own_t) & (tight_tested & near_tight)[:, :, None]).sum((1, 2))
 new_tested = np.where(uniform, row_tested.sum(1), shipped_tested.sum(1))
 new_walked = np.where(uniform, row_walked, shipped_walked)
 print(f"packets of 64 bounce rays: {n_packets}; one leaving row in every lane: {uniform.mean():.4f}; distinct rows per packet {distinct.mean():.3f}; rows in use {len(np.unique(LV))} of {2 * n}")
@@ -145,5 +159,7 @@ print(f"{'per bounce round':44s} {'row / union':>12s} {'boxes tested':>13s} {'tr
 print(f"{'as shipped (union of rows, leaf boxes)':44s} {union.sum(1).mean():12.2f} {shipped_tested.sum(1).mean():13.2f} {shipped_walked.mean():17.2f}")
 print(f"{'row boxes (uniform packets), else as shipped':44s} {np.where(uniform, own.sum(1), union.sum(1)).mean():12.2f} {new_tested.mean():13.2f} {new_walked.mean():17.2f}")
 print(f"{'  uniform packets alone':44s} {own[uniform].sum(1).mean():12.2f} {row_tested[uniform].sum(1).mean():13.2f} {row_walked[uniform].mean():17.2f}")
+print(f"{'tight rule (uniform packets), else as shipped':44s} {np.where(uniform, own_t.sum(1), union.sum(1)).mean():12.2f} {np.where(uniform, tight_tested.sum(1), shipped_tested.sum(1)).mean():13.2f} {np.where(uniform, tight_walked, shipped_walked).mean():17.2f}")
+print(f"{'  uniform packets alone':44s} {own_t[uniform].sum(1).mean():12.2f} {tight_tested[uniform].sum(1).mean():13.2f} {tight_walked[uniform].mean():17.2f}; rounds that walk nothing {(tight_walked[uniform] == 0).mean():.3f} (round 8's rule: {(row_walked[uniform] == 0).mean():.3f})")
 if (~uniform).any():
     print(f"{'  the other packets alone':44s} {union[~uniform].sum(1).mean():12.2f} {shipped_tested[~uniform].sum(1).mean():13.2f} {shipped_walked[~uniform].mean():17.2f}")

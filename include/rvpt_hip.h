@@ -83,7 +83,11 @@ extern "C" {
                                      format" error — is a SURFACE POINT read: `dst` holds rvpt_surface_point records, (prim, u, v) as a query reported them
                                      in, the point of the stored mesh, its material word and its normal out.  Still 8, no new symbol: rvpt_hip_read with
                                      a format RVPT_HIP_FORMAT_RAY_HITS_NEAREST(k) (33 .. 40) — until then the "unknown format" error — is a K-NEAREST RAY
-                                     QUERY: `dst` holds groups of k rvpt_ray_hit records, the ray in the first, the k nearest hits along it out */
+                                     QUERY: `dst` holds groups of k rvpt_ray_hit records, the ray in the first, the k nearest hits along it out.  Still 8, no
+                                     new symbol: the skin update's arguments under a count RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(permille) — until then the
+                                     "NULL scene array" error — are the GUARDED SKIN UPDATE: the skin update, the SAH cost of the skinned tree reported, and
+                                     past a limit a rebuild by the builder that made the tree, through which the rest pose follows its triangles and the
+                                     binding stays */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -477,7 +481,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  * - It moves nothing.  It is not "another form" in the pose update's snapshot rule: the rest pose stays.  The slots' prepared state stays, rvpt_hip_last_error
  *   is empty afterwards, and a frame after a bind is bit for bit the frame without it.  A second bind replaces the first.
  * - The binding is DROPPED by an ordinary full upload, by a build form the caller asks for, and whenever a call leaves the context without a scene.  It
- *   SURVIVES the plain, guarded, sparse, pose and guarded pose updates, their rebuilds included.
+ *   SURVIVES the plain, guarded, sparse, pose and guarded pose updates, their rebuilds included.  It survives the guarded skin update and its rebuild too.
  * - Weights are taken as given: they need not sum to 1, and non-finite weights are the caller's problem.
  *
  * SKIN UPDATE — linear blend skinning: every vertex of the mesh posed from the rest pose by its four weighted bone matrices, on the device:
@@ -507,8 +511,43 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx);
  *   brute-force context; the laboratory's caller-layout knob, with the answer the plain form gives.
  * - Frames in flight finish on the old geometry; `bones` may be freed on return; rvpt_hip_last_error is empty afterwards.  Every other form behaves and reports
  *   exactly as before.  There is NO GUARDED SKIN UPDATE: the tree is refitted, never costed or rebuilt, by this form; a caller whose skinned mesh has left its
- *   tree behind runs a guarded update or a build form.
- * Cost on one MI355X: profiles/skin_update.txt; DESIGN.md 5.18. */
+ *   tree behind runs a guarded update or a build form.  (That is this count's rule.  The GUARDED SKIN UPDATE below is this form under a count of its own, with
+ *   the tree costed behind it and rebuilt past a limit, and it keeps the binding and the rest pose.)
+ * Cost on one MI355X: profiles/skin_update.txt; DESIGN.md 5.18.
+ *
+ * GUARDED SKIN UPDATE — the skin update, then the cost of the skinned tree, and a rebuild once it has gone stale; the rest pose and the binding survive the rebuild:
+ *
+ *     rvpt_hip_upload_scene(ctx, (const rvpt_bvh_node *)bones, RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(permille), NULL, k, NULL, 0);      0 < k <= RVPT_HIP_SKIN_MAX_BONES
+ *
+ * permille is 0 (report only) or 1000 .. 65535, the guarded update's limit.  Any other value in the band is RVPT_HIP_ERR_INVALID ("guarded skin update: the
+ * limit is 0 (report only) or 1000 .. 65535 permille, got <n>") and leaves the stored scene, the rest pose and the binding untouched.  `bones` is the skin
+ * update's list: host memory or, on BVH contexts, device memory of the context's GPU.
+ * - BVH contexts.  Every refusal of the skin update comes first, in its words and its order.  Then the one refusal of this form: a limit on a tree that came
+ *   from an ordinary upload with the caller's own nodes is RVPT_HIP_ERR_INVALID — the library has no builder to name —, decided before anything is touched.
+ *   Report only (0) is legal there.
+ * - The skin update runs exactly as above: the snapshot if the context holds no rest pose, every vertex skinned from it, every box refitted by the plain
+ *   form's rule.  Then the TREE COST of the stored tree is computed as in the guarded update; every box is tight.  The base cost is the guarded update's.
+ * - With a limit, if cost > (permille / 1000) * base cost (in double) and the stored scene came from a build form, the library REBUILDS with that build form's
+ *   method from the skinned vertices beside the stored mat_id rows, carried back into the caller's order, and the materials as the caller last passed them.
+ *   What the context then holds — tree, permutation, level table, wide form, launch choice — is what
+ *   rvpt_hip_upload_scene(ctx, NULL, <that build count>, skinned_in_caller_order, n_tris, mats, n_mats) leaves, and the base cost becomes the new tree's.
+ * - THE REST POSE GOES WITH THE REBUILD, as in the guarded pose update: into the caller's order by the old permutation, back into stored order by the new one.
+ *   THE BINDING STAYS WHERE IT IS: it is kept in the caller's order and read through the stored permutation, so the new permutation is all it needs.  The
+ *   largest bound bone index and its position stay.  The next skin update — plain or guarded — poses every vertex from the same rest pose through the same
+ *   weights as before the rebuild, and the next pose update poses from that rest pose too.
+ * - A successful call of this form, like one of the plain skin form, keeps the rest pose and the binding, and the context remembers k matrices.  A rebuild that
+ *   fails follows the build form's rule: the context is left WITHOUT a scene, and the rest pose and the binding are dropped with it.
+ * - On success rvpt_hip_last_error holds ONE SENTENCE, one of
+ *       guarded skin update: cost <%.17g>, base cost <%.17g>, limit <permille> permille: refitted
+ *       guarded skin update: cost <%.17g>, base cost <%.17g>, limit <permille> permille: rebuilt (<lbvh|ploc|sah>), new base cost <%.17g>
+ *   where `cost` is that of the skinned tree, the one the decision was taken by, and the name is that of the tree the scene then holds (a PLOC rebuild that
+ *   fell back names lbvh; the next rebuild is a PLOC build again).  The wrappers parse this wording.
+ * - Brute-force contexts hold no tree: there the count is the plain skin update, and rvpt_hip_last_error is empty afterwards.
+ * - Frames in flight finish on the old geometry; `bones` may be freed on return.  Every other form, the plain skin update included, behaves and reports
+ *   exactly as before.
+ * Measured on one MI355X, 1 M triangles, 64 bones (profiles/guarded_skin.txt): the guard adds 0.045 ms to the 0.207 ms skin update; a call that
+ * rebuilds takes 2.2 / 3.5 / 17.0 ms (LBVH / PLOC / SAH); a fold of the bone grid by a tenth of the extent reports a ratio of 1.09, by a half 1.32.  The rate on
+ * the folded trees was not measured: no limit is recommended for a skinned mesh. */
 typedef struct rvpt_vertex_skin {    /* 32 bytes: the four influences of ONE vertex */
     uint32_t bone[4];                /* indices into the skin update's matrices, each < RVPT_HIP_SKIN_MAX_BONES */
     float    weight[4];
@@ -519,6 +558,7 @@ typedef struct rvpt_bone {           /* 48 bytes */
 #define RVPT_HIP_SKIN_MAX_BONES 1024u
 #define RVPT_HIP_NODES_BIND_SKIN ((size_t)-6)
 #define RVPT_HIP_NODES_UPDATE_SKIN ((size_t)-7)
+#define RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(permille) ((size_t)0 - (size_t)(0x300000u + (permille)))
 typedef struct rvpt_part_move {      /* 64 bytes */
     float    m[12];                  /* 3x4, row major: x' = m[0] x + m[1] y + m[2] z + m[3], y' from m[4..7], z' from m[8..11] */
     uint32_t first, count;           /* the triangles [first, first + count) */

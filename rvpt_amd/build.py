@@ -134,6 +134,7 @@ HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selft
                 "host_selftest_pose": ["host_selftest_pose.cpp", "rvpt_host.cpp"],
                 "host_selftest_pose_guard": ["host_selftest_pose_guard.cpp", "rvpt_host.cpp"],
                 "host_selftest_skin": ["host_selftest_skin.cpp", "rvpt_host.cpp"],
+                "host_selftest_skin_guard": ["host_selftest_skin_guard.cpp", "rvpt_host.cpp"],
                 "host_selftest_rays": ["host_selftest_rays.cpp", "rvpt_host.cpp"],
                 "host_selftest_multi_hit": ["host_selftest_multi_hit.cpp", "rvpt_host.cpp"],
                 "host_selftest_paths": ["host_selftest_paths.cpp", "rvpt_host.cpp"],
@@ -160,7 +161,7 @@ def _hip_host_flags() -> list:
 
 def build_host(force: bool = False) -> Path:
     """Compile the C++ host layer (rvpt_amd/host/: the mirror of the reference's class RVPT above the C ABI) with
-    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames`, `host_selftest_guard`, `host_selftest_sparse`, `host_selftest_pose`, `host_selftest_pose_guard`, `host_selftest_skin`, `host_selftest_rays`, `host_selftest_multi_hit`, `host_selftest_paths`, `host_selftest_path_modes`, `host_selftest_nearest` and `host_selftest_surface`."""
+    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames`, `host_selftest_guard`, `host_selftest_sparse`, `host_selftest_pose`, `host_selftest_pose_guard`, `host_selftest_skin`, `host_selftest_skin_guard`, `host_selftest_rays`, `host_selftest_multi_hit`, `host_selftest_paths`, `host_selftest_path_modes`, `host_selftest_nearest` and `host_selftest_surface`."""
     build_native()
     HOST_BIN_DIR.mkdir(exist_ok=True)
     srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h", _PKG / "csrc" / "rvpt_vis.h"]

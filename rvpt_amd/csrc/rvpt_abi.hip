@@ -171,7 +171,7 @@ struct rvpt_hip_ctx {
     unsigned char *d_sparse_stage = nullptr;
     size_t cap_sparse_stage = 0;
     // the POSE UPDATE of upload_scene (include/rvpt_hip.h): the REST POSE — the 48 vertex bytes of every stored triangle, in stored order, as the last call of
-    // any other form left them.  have_rest: the snapshot belongs to the stored scene; kept by the two pose forms (through a guarded rebuild too), dropped by every successful call of another form, taken again by the
+    // any other form left them.  have_rest: the snapshot belongs to the stored scene; kept by the two pose forms, the two skin forms and the bind (through a guarded rebuild too), dropped by every successful call of another form, taken again by the
     // next pose update.  BVH contexts keep it on the device (three quads per triangle), brute-force contexts on the host (twelve floats per triangle).
     float4 *d_rest = nullptr;
     size_t cap_rest = 0;
@@ -1860,29 +1860,12 @@ static int update_geometry_pose(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, 
     return pose_execute(ctx, moves, k, list);
 }
 
-// The GUARDED POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): the pose update, then the cost of the stored tree — the boxes off the listed paths as
-// they were, loose ones included —, then, with a limit, once the cost has grown past limit x base cost, a rebuild by the builder that made the stored tree
-// from the posed triangles carried back into the caller's order.  The rest pose goes with the rebuild: into the caller's order by the old permutation, back
-// into stored order by the new one, so that the next pose update poses from the same rest pose as before.  permille: 0 (report only) or 1000 .. 65535, checked
-// by the caller.  Brute-force contexts hold no tree: the plain pose form.
-static int update_geometry_pose_guarded(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats, uint32_t permille)
+// The rebuild tail of the guarded pose and the guarded skin update, behind their decision: the stored triangles and the rest pose into the caller's order by
+// the old permutation, the build by the builder that made the stored tree, the rest pose back into stored order by the new permutation, and the report.
+// `form`: "pose" or "skin", the word of the report.  d_skin is not touched: it is in the caller's order and is read through d_perm.
+static int rebuild_keeping_rest(rvpt_hip_ctx *ctx, const char *form, double cost, double base, uint32_t permille)
 {
-    // the pose form's own refusals come first, in its words and its order; then the one refusal of this form, before anything of the stored scene is touched
-    PoseList list;
-    if (int rc = pose_validate(ctx, moves, tris, k, mats, n_mats, &list)) return rc;
-    if (!list.bvh) return pose_execute(ctx, moves, k, list);
-    if (permille != 0 && ctx->built_by == rvpt_hip_ctx::kBuiltByCaller)
-        return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded pose update with a limit after an ordinary upload_scene: the tree is the caller's, the library has no builder to rebuild it by (report only, limit 0, is legal)");
-    if (int rc = pose_execute(ctx, moves, k, list)) return rc;
-    double cost = 0.0;
-    bool have = false;
-    if (int rc = device_tree_cost(ctx, &cost, &have)) return rc;
-    const double base = ctx->base_cost;
-    if (permille == 0 || !have || !ctx->have_cost || !ctx->have_perm || !(cost > static_cast<double>(permille) / 1000.0 * base)) {
-        fail(ctx, RVPT_HIP_OK, "guarded pose update: cost %.17g, base cost %.17g, limit %u permille: refitted", cost, base, permille);
-        return RVPT_HIP_OK;
-    }
-    // the rebuild, as the guarded update's: d_tris (posed vertices beside the stored mat_id rows, leaf order) into d_carry in the caller's order, and beside it
+    // the rebuild, as the guarded update's: d_tris (moved vertices beside the stored mat_id rows, leaf order) into d_carry in the caller's order, and beside it
     // the rest pose into d_rest_carry by the same permutation, before the build writes a new one
     const size_t n_tris = ctx->n_tris;
     const uint32_t n = static_cast<uint32_t>(n_tris);
@@ -1905,9 +1888,34 @@ static int update_geometry_pose_guarded(rvpt_hip_ctx *ctx, const rvpt_part_move 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->have_rest = true;
     static const char *const kNames[] = {"", "lbvh", "ploc", "sah"};
-    fail(ctx, RVPT_HIP_OK, "guarded pose update: cost %.17g, base cost %.17g, limit %u permille: rebuilt (%s), new base cost %.17g", cost, base, permille,
+    fail(ctx, RVPT_HIP_OK, "guarded %s update: cost %.17g, base cost %.17g, limit %u permille: rebuilt (%s), new base cost %.17g", form, cost, base, permille,
          kNames[fell_back ? rvpt_hip_ctx::kBuiltLbvh : built_by], ctx->base_cost);
     return RVPT_HIP_OK;
+}
+
+// The GUARDED POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): the pose update, then the cost of the stored tree — the boxes off the listed paths as
+// they were, loose ones included —, then, with a limit, once the cost has grown past limit x base cost, a rebuild by the builder that made the stored tree
+// from the posed triangles carried back into the caller's order.  The rest pose goes with the rebuild: into the caller's order by the old permutation, back
+// into stored order by the new one, so that the next pose update poses from the same rest pose as before.  permille: 0 (report only) or 1000 .. 65535, checked
+// by the caller.  Brute-force contexts hold no tree: the plain pose form.
+static int update_geometry_pose_guarded(rvpt_hip_ctx *ctx, const rvpt_part_move *moves, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats, uint32_t permille)
+{
+    // the pose form's own refusals come first, in its words and its order; then the one refusal of this form, before anything of the stored scene is touched
+    PoseList list;
+    if (int rc = pose_validate(ctx, moves, tris, k, mats, n_mats, &list)) return rc;
+    if (!list.bvh) return pose_execute(ctx, moves, k, list);
+    if (permille != 0 && ctx->built_by == rvpt_hip_ctx::kBuiltByCaller)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded pose update with a limit after an ordinary upload_scene: the tree is the caller's, the library has no builder to rebuild it by (report only, limit 0, is legal)");
+    if (int rc = pose_execute(ctx, moves, k, list)) return rc;
+    double cost = 0.0;
+    bool have = false;
+    if (int rc = device_tree_cost(ctx, &cost, &have)) return rc;
+    const double base = ctx->base_cost;
+    if (permille == 0 || !have || !ctx->have_cost || !ctx->have_perm || !(cost > static_cast<double>(permille) / 1000.0 * base)) {
+        fail(ctx, RVPT_HIP_OK, "guarded pose update: cost %.17g, base cost %.17g, limit %u permille: refitted", cost, base, permille);
+        return RVPT_HIP_OK;
+    }
+    return rebuild_keeping_rest(ctx, "pose", cost, base, permille);
 }
 
 // is `p` device memory, and of which GPU (-1: host memory)?
@@ -2008,7 +2016,14 @@ static void skin_vertex_host(const rvpt_bone *bones, const rvpt_vertex_skin &s, 
 // The SKIN UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): k matrices; every vertex of the stored scene is posed from the rest pose by the four weighted
 // matrices its bound record names.  BVH contexts: the snapshot if the context holds no rest pose, rv::skin_vertices over every vertex quad, then the plain
 // update form's tail (every box refitted).  Brute-force contexts skin on the host and run the plain form.  Everything is refused before anything is touched.
-static int update_geometry_skin(rvpt_hip_ctx *ctx, const rvpt_bone *bones, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats)
+// (Two halves, as the pose update's, so that the guarded skin form can put its own refusal between them: skin_validate touches nothing stored, skin_execute
+// refuses nothing a caller's arguments decide.)
+struct SkinList {
+    int dev = -1;  // the GPU whose memory holds the bones, -1: host memory
+    bool bvh = false;
+};
+
+static int skin_validate(rvpt_hip_ctx *ctx, const rvpt_bone *bones, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats, SkinList *list)
 {
     if (!ctx->have_scene) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update before any full upload_scene on this context: there is no scene to update");
     if (k == 0) return fail(ctx, RVPT_HIP_ERR_INVALID, "skin update without bones");
@@ -2034,6 +2049,15 @@ static int update_geometry_skin(rvpt_hip_ctx *ctx, const rvpt_bone *bones, const
 #else
         return fail(ctx, RVPT_HIP_ERR_UNSUPPORTED, "geometry update needs the level ranges of the tree's device layout, which this context does not hold");
 #endif
+    list->dev = dev, list->bvh = bvh;
+    return RVPT_HIP_OK;
+}
+
+static int skin_execute(rvpt_hip_ctx *ctx, const rvpt_bone *bones, size_t k, const SkinList &list)
+{
+    const size_t n_tris = ctx->n_tris;
+    const int dev = list.dev;
+    const bool bvh = list.bvh;
 
     if (!bvh) {  // the rest pose on the host, the skinned records through the plain form
         if (int rc0 = sync_all(ctx)) return rc0;
@@ -2083,6 +2107,38 @@ static int update_geometry_skin(rvpt_hip_ctx *ctx, const rvpt_bone *bones, const
     ctx->skin_bones = kk;
     ctx->err.clear();
     return RVPT_HIP_OK;
+}
+
+static int update_geometry_skin(rvpt_hip_ctx *ctx, const rvpt_bone *bones, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats)
+{
+    SkinList list;
+    if (int rc = skin_validate(ctx, bones, tris, k, mats, n_mats, &list)) return rc;
+    return skin_execute(ctx, bones, k, list);
+}
+
+// The GUARDED SKIN UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): the skin update — every box refitted —, then the cost of the stored tree, then, with a
+// limit, once the cost has grown past limit x base cost, the rebuild tail of the guarded pose update: the skinned triangles and the rest pose through the old
+// permutation into the caller's order, the build, the rest pose through the new permutation back.  The binding stays where it is, in the caller's order; the
+// next skin update reads it through the new permutation and poses from the same rest pose through the same weights.  permille: 0 (report only) or
+// 1000 .. 65535, checked by the caller.  Brute-force contexts hold no tree: the plain skin form.
+static int update_geometry_skin_guarded(rvpt_hip_ctx *ctx, const rvpt_bone *bones, const rvpt_triangle *tris, size_t k, const rvpt_material *mats, size_t n_mats, uint32_t permille)
+{
+    // the skin form's own refusals come first, in its words and its order; then the one refusal of this form, before anything of the stored scene is touched
+    SkinList list;
+    if (int rc = skin_validate(ctx, bones, tris, k, mats, n_mats, &list)) return rc;
+    if (!list.bvh) return skin_execute(ctx, bones, k, list);
+    if (permille != 0 && ctx->built_by == rvpt_hip_ctx::kBuiltByCaller)
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded skin update with a limit after an ordinary upload_scene: the tree is the caller's, the library has no builder to rebuild it by (report only, limit 0, is legal)");
+    if (int rc = skin_execute(ctx, bones, k, list)) return rc;
+    double cost = 0.0;
+    bool have = false;
+    if (int rc = device_tree_cost(ctx, &cost, &have)) return rc;
+    const double base = ctx->base_cost;
+    if (permille == 0 || !have || !ctx->have_cost || !ctx->have_perm || !(cost > static_cast<double>(permille) / 1000.0 * base)) {
+        fail(ctx, RVPT_HIP_OK, "guarded skin update: cost %.17g, base cost %.17g, limit %u permille: refitted", cost, base, permille);
+        return RVPT_HIP_OK;
+    }
+    return rebuild_keeping_rest(ctx, "skin", cost, base, permille);
 }
 
 // The GUARDED UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; BVH contexts): the update form, then the cost of the refitted tree, then — with a limit,
@@ -2138,6 +2194,16 @@ int rvpt_hip_upload_scene(rvpt_hip_ctx *ctx, const rvpt_bvh_node *nodes, size_t 
         if (permille != 0 && (permille < 1000u || permille > 65535u))
             return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded pose update: the limit is 0 (report only) or 1000 .. 65535 permille, got %zu", permille);
         const int rc = update_geometry_pose_guarded(ctx, reinterpret_cast<const rvpt_part_move *>(nodes), tris, n_tris, mats, n_mats, static_cast<uint32_t>(permille));
+        if (!ctx->have_scene) drop_skin(ctx);  // (a rebuild that failed)
+        return rc;
+    }
+    // the GUARDED SKIN UPDATE: the skin update's arguments and a count of the band RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(permille) lies in.  It keeps the rest pose and
+    // the binding, through a rebuild too; only a rebuild that failed, and so left no scene, has dropped them
+    if ((size_t)0 - n_nodes >= 0x300000u && (size_t)0 - n_nodes < 0x400000u) {
+        const size_t permille = (size_t)0 - n_nodes - 0x300000u;
+        if (permille != 0 && (permille < 1000u || permille > 65535u))
+            return fail(ctx, RVPT_HIP_ERR_INVALID, "guarded skin update: the limit is 0 (report only) or 1000 .. 65535 permille, got %zu", permille);
+        const int rc = update_geometry_skin_guarded(ctx, reinterpret_cast<const rvpt_bone *>(nodes), tris, n_tris, mats, n_mats, static_cast<uint32_t>(permille));
         if (!ctx->have_scene) drop_skin(ctx);  // (a rebuild that failed)
         return rc;
     }

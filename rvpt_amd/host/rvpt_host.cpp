@@ -406,7 +406,10 @@ bool RVPT::bind_skin(const rvpt_vertex_skin *skin, size_t n_tris)
 }
 
 // The skin form: `nodes` carries rvpt_bone records, the count is RVPT_HIP_NODES_UPDATE_SKIN, no triangles go down.
-bool RVPT::skin(const rvpt_bone *bones, size_t k)
+bool RVPT::skin(const rvpt_bone *bones, size_t k) { return skin_with(bones, k, RVPT_HIP_NODES_UPDATE_SKIN, "rvpt_hip_upload_scene (skin update)"); }
+
+// `count`: RVPT_HIP_NODES_UPDATE_SKIN or RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(permille)
+bool RVPT::skin_with(const rvpt_bone *bones, size_t k, size_t count, const char *what)
 {
     if (!ctx_) {
         error_ = "skin before initialize()";
@@ -426,7 +429,7 @@ bool RVPT::skin(const rvpt_bone *bones, size_t k)
                 error_ = "skin: skin[" + std::to_string(r) + "].bone[" + std::to_string(j) + "] = " + std::to_string(skin_[r].bone[j]) + " with " + std::to_string(k) + " bones";
                 return false;
             }
-    if (!check(backend_.upload_scene(ctx_, reinterpret_cast<const rvpt_bvh_node *>(bones), RVPT_HIP_NODES_UPDATE_SKIN, nullptr, k, nullptr, 0), "rvpt_hip_upload_scene (skin update)")) return false;
+    if (!check(backend_.upload_scene(ctx_, reinterpret_cast<const rvpt_bvh_node *>(bones), count, nullptr, k, nullptr, 0), what)) return false;
     if (!have_rest_) rest_ = triangles_, have_rest_ = true;
     for (size_t t = 0; t < triangles_.size(); ++t) {
         skin_vertex(bones, skin_[3 * t], rest_[t].vertex0, triangles_[t].vertex0);
@@ -441,7 +444,7 @@ bool RVPT::skin(const rvpt_bone *bones, size_t k)
     return true;
 }
 
-// The sentence rvpt_hip_last_error holds after a guarded update or a guarded pose update (include/rvpt_hip.h fixes both wordings: they differ in the prefix).
+// The sentence rvpt_hip_last_error holds after a guarded update, a guarded pose update or a guarded skin update (include/rvpt_hip.h fixes the wordings: they differ in the prefix).
 bool parse_update_report(const char *sentence, UpdateReport *report)
 {
     UpdateReport r;
@@ -450,6 +453,7 @@ bool parse_update_report(const char *sentence, UpdateReport *report)
     char tree[8] = {};
     if (!sentence) return false;
     if (std::strncmp(sentence, "guarded pose update: ", 21) == 0) sentence += 21;
+    else if (std::strncmp(sentence, "guarded skin update: ", 21) == 0) sentence += 21;
     else if (std::strncmp(sentence, "guarded update: ", 16) == 0) sentence += 16;
     else return false;
     if (std::sscanf(sentence, "cost %lg, base cost %lg, limit %u permille: %n", &r.cost, &r.base_cost, &permille, &used) < 3 || used == 0) return false;
@@ -504,6 +508,29 @@ bool RVPT::pose_parts(const rvpt_part_move *moves, size_t k, double rebuild_abov
     UpdateReport r;  // (a brute-force context holds no tree and reports nothing, an empty list sends nothing: the empty record)
     if (options_.bvh_traversal && k > 0 && !parse_update_report(backend_.last_error(ctx_), &r)) {
         error_ = "pose_parts: the guarded pose update's report could not be read";
+        return false;
+    }
+    // (a rebuild happens only after a device build, where bvh_nodes() is empty: there is no host copy of the tree to go wrong, as in update_triangles)
+    if (report) *report = r;
+    return true;
+}
+
+// The guarded skin form: the skin update under the count RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(permille), then the report.  The rest pose and the binding kept
+// here, in the order the triangles were added, stay through a rebuild, as the device's do.
+bool RVPT::skin(const rvpt_bone *bones, size_t k, double rebuild_above, UpdateReport *report)
+{
+    long permille = 0;  // infinity: report only
+    if (!std::isinf(rebuild_above) || rebuild_above < 0) {
+        permille = std::isnan(rebuild_above) ? -1 : std::lround(std::fmin(rebuild_above, 1e6) * 1000.0);
+        if (permille < 1000 || permille > 65535) {
+            error_ = "skin: rebuild_above is a factor in [1, 65.535] or infinity (report only)";
+            return false;
+        }
+    }
+    if (!skin_with(bones, k, RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(static_cast<size_t>(permille)), "rvpt_hip_upload_scene (guarded skin update)")) return false;
+    UpdateReport r;  // (a brute-force context holds no tree and reports nothing: the empty record)
+    if (options_.bvh_traversal && !triangles_.empty() && !parse_update_report(backend_.last_error(ctx_), &r)) {
+        error_ = "skin: the guarded skin update's report could not be read";
         return false;
     }
     // (a rebuild happens only after a device build, where bvh_nodes() is empty: there is no host copy of the tree to go wrong, as in update_triangles)

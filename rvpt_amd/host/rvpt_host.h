@@ -97,7 +97,7 @@ struct Backend {
     static const Backend &native();
 };
 
-// What a guarded geometry update or a guarded pose update reports (RVPT::update_triangles / RVPT::pose_parts with a limit), parsed from the one sentence rvpt_hip_last_error then holds
+// What a guarded geometry update, a guarded pose update or a guarded skin update reports (RVPT::update_triangles / RVPT::pose_parts / RVPT::skin with a limit), parsed from the one sentence rvpt_hip_last_error then holds
 struct UpdateReport {
     double cost = 0, base_cost = 0, ratio = 0;  // the refitted tree's cost, the cost of the tree as it was built, cost / base_cost (0 when the base is 0)
     bool rebuilt = false;
@@ -183,8 +183,14 @@ public:
     // Linear blend skinning — the skin update (RVPT_HIP_NODES_UPDATE_SKIN; include/rvpt_hip.h: SKIN UPDATE): k matrices pose EVERY vertex from the rest pose
     // pose_parts shares — the triangles as the last initialize() or update_triangles left them; two skin updates do not compose — and every box is refitted.
     // The host copies are skinned by skin_vertex (the same bits as the device), bvh_nodes() is refitted when next asked for; the next update() restarts the
-    // accumulation.  There is no guarded form.
+    // accumulation.  The guarded form is the overload below.
     bool skin(const rvpt_bone *bones, size_t k);
+    // The guarded form (RVPT_HIP_NODES_UPDATE_SKIN_GUARDED; include/rvpt_hip.h: GUARDED SKIN UPDATE): the same, then the SAH cost of the skinned tree from the
+    // device, and — `rebuild_above` a factor in [1, 65.535], rounded to thousandths — a rebuild by the device builder of initialize() once cost >
+    // rebuild_above x the base cost; infinity: report only.  The device carries its rest pose through the rebuild and keeps its binding, and the copies kept
+    // here stay, so later skins pose from the same rest pose through the same weights.  A limit needs Options::device_build.  Brute-force traversal: the
+    // plain skin, `report` comes back empty.
+    bool skin(const rvpt_bone *bones, size_t k, double rebuild_above, UpdateReport *report = nullptr);
 
     // RGBA32F (width*height*4 floats) or RGBA8 (width*height*4 bytes), row-major, top row first
     std::vector<float> read_frame();
@@ -254,6 +260,7 @@ private:
     bool check(int rc, const char *what);
     bool update_triangles_with(const std::vector<Triangle> &triangles, size_t count, const char *what);
     bool pose_parts_with(const rvpt_part_move *moves, size_t k, size_t count, const char *what);
+    bool skin_with(const rvpt_bone *bones, size_t k, size_t count, const char *what);
     uint32_t width_, height_;
     Options options_;
     const Backend &backend_;

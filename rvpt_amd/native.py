@@ -82,6 +82,7 @@ VERTEX_SKIN_DTYPE = np.dtype([("bone", "<u4", (4,)), ("weight", "<f4", (4,))])
 BONE_DTYPE = np.dtype([("m", "<f4", (12,))])
 NODES_UPDATE_GUARDED_BASE = 0x10000  # RVPT_HIP_NODES_UPDATE_GUARDED(permille) = (size_t)0 - (0x10000 + permille): the guarded update (Context.update_triangles(rebuild_above=))
 NODES_UPDATE_POSE_GUARDED_BASE = 0x200000  # RVPT_HIP_NODES_UPDATE_POSE_GUARDED(permille) = (size_t)0 - (0x200000 + permille): the guarded pose update (Context.pose_parts(rebuild_above=))
+NODES_UPDATE_SKIN_GUARDED_BASE = 0x300000  # RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(permille) = (size_t)0 - (0x300000 + permille): the guarded skin update (Context.skin(rebuild_above=))
 NODES_BUILD_PLOC = C.c_size_t(-2).value  # RVPT_HIP_NODES_BUILD_PLOC: the build form with a PLOC tree (Context.build_scene(method="ploc"))
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_SIZE, ERR_COMM = -1, -2, -3, -4, -5, -6
 
@@ -111,8 +112,13 @@ def nodes_update_pose_guarded(permille: int) -> int:
     return C.c_size_t(-(NODES_UPDATE_POSE_GUARDED_BASE + int(permille))).value
 
 
+def nodes_update_skin_guarded(permille: int) -> int:
+    """RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(permille) of include/rvpt_hip.h as the size_t the call takes"""
+    return C.c_size_t(-(NODES_UPDATE_SKIN_GUARDED_BASE + int(permille))).value
+
+
 def _guard_permille(rebuild_above, who: str) -> int:
-    """rebuild_above of the two guarded forms as the permille their counts carry: a float >= 1 rounded to thousandths, math.inf is 0 (report only)"""
+    """rebuild_above of the guarded forms as the permille their counts carry: a float >= 1 rounded to thousandths, math.inf is 0 (report only)"""
     limit = float(rebuild_above)
     permille = 0 if limit == math.inf else int(round(min(limit, 1e6) * 1000.0)) if limit == limit and limit > 0 else -1
     if permille != 0 and not 1000 <= permille <= 65535:
@@ -121,7 +127,7 @@ def _guard_permille(rebuild_above, who: str) -> int:
 
 
 class UpdateReport(NamedTuple):
-    """What a guarded update or a guarded pose update reports: the refitted tree's SAH cost, the cost of the tree as it was last built or uploaded, cost / base_cost (0.0 when the base is
+    """What a guarded update, a guarded pose update or a guarded skin update reports: the refitted tree's SAH cost, the cost of the tree as it was last built or uploaded, cost / base_cost (0.0 when the base is
     0), whether the library rebuilt, and then the builder's name ("lbvh", "ploc", "sah"; None after a refit)."""
     cost: float
     base_cost: float
@@ -130,16 +136,23 @@ class UpdateReport(NamedTuple):
     tree: Optional[str]
 
 
-_GUARD_SENTENCE = re.compile(r"guarded (?:pose )?update: cost (\S+), base cost (\S+), limit (\d+) permille: (?:refitted|rebuilt \((lbvh|ploc|sah)\), new base cost (\S+))\Z")
+_GUARD_SENTENCE = re.compile(r"guarded (?:pose |skin )?update: cost (\S+), base cost (\S+), limit (\d+) permille: (?:refitted|rebuilt \((lbvh|ploc|sah)\), new base cost (\S+))\Z")
 
 
 def parse_update_report(sentence: str) -> UpdateReport:
-    """The one sentence rvpt_hip_last_error holds after a guarded update or a guarded pose update (include/rvpt_hip.h fixes both wordings)"""
+    """The one sentence rvpt_hip_last_error holds after a guarded update, a guarded pose update or a guarded skin update (include/rvpt_hip.h fixes the wordings)"""
     m = _GUARD_SENTENCE.match(sentence)
     if m is None:
         raise NativeError(ERR_INVALID, f"update_triangles: not a guarded update's report: {sentence!r}")
     cost, base = float(m.group(1)), float(m.group(2))
     return UpdateReport(cost, base, cost / base if base > 0.0 else 0.0, m.group(4) is not None, m.group(4))
+
+
+def _report_of(ctx, rebuild_above):
+    """what a guarded form returns: None for the plain call and on a brute-force context, which holds no tree; the parsed sentence otherwise"""
+    if rebuild_above is None or (ctx.flags & (TRAVERSAL_BVH | TRAVERSAL_BVH_ORDERED)) == 0:
+        return None
+    return parse_update_report((ctx._L.rvpt_hip_last_error(ctx._h) or b"").decode())
 
 
 class SceneStateInfo(C.Structure):
@@ -614,27 +627,34 @@ class Context:
         _check(self._L.rvpt_hip_upload_scene(self._h, _ptr(rec), NODES_BIND_SKIN, None, rec.shape[0] // 3, None, 0), self._h, self._L)
         return None
 
-    def skin(self, bones) -> None:
+    def skin(self, bones, rebuild_above=None):
         """The SKIN UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h): linear blend skinning — every vertex is posed FROM THE REST POSE (the pose update's) by
         the four weighted matrices its bound record names, and every box of the tree is refitted as after update_triangles.  scene.skin_triangles is the same
         on the host, bit for bit.  bones: float32[k, 3, 4] or [k, 12], [k, 4, 4] with last rows 0 0 0 1, or — BVH contexts — a contiguous float32 torch tensor
-        [k, 3, 4] / [k, 12] on this context's device, which never visits the host.  Needs a bind_skin first and more bones than its largest index."""
+        [k, 3, 4] / [k, 12] on this context's device, which never visits the host.  Needs a bind_skin first and more bones than its largest index.
+
+        rebuild_above: None is the plain form and returns None.  A number is the GUARDED form (RVPT_HIP_NODES_UPDATE_SKIN_GUARDED): behind the skin the library
+        computes the tree's SAH cost on the device and, when it exceeds rebuild_above x the cost of the tree as it was built, rebuilds with the method of the
+        build_scene that made it; the rest pose follows the triangles through the rebuild and the binding stays, so later skins pose from the same rest pose
+        through the same weights.  A float >= 1 is rounded to thousandths (at most 65.535); math.inf only reports.  Returns an UpdateReport, whose `tree` names
+        the tree the scene holds after a rebuild; on a brute-force context, which holds no tree, the plain skin happens and None is returned."""
         from . import scene
+        count = NODES_UPDATE_SKIN if rebuild_above is None else nodes_update_skin_guarded(_guard_permille(rebuild_above, "skin"))
         if not isinstance(bones, np.ndarray) and hasattr(bones, "data_ptr"):
             import torch
             if bones.dtype != torch.float32 or tuple(bones.shape[1:]) not in ((3, 4), (12,)):
                 raise NativeError(ERR_INVALID, f"skin: a float32 tensor [k, 3, 4] or [k, 12] is needed, got {bones.dtype} {tuple(bones.shape)}")
             dev = self._device_tensor(bones, "skin", 12)
             if dev is not None:
-                _check(self._L.rvpt_hip_upload_scene(self._h, dev[0], NODES_UPDATE_SKIN, None, dev[1], None, 0), self._h, self._L)
-                return None
+                _check(self._L.rvpt_hip_upload_scene(self._h, dev[0], count, None, dev[1], None, 0), self._h, self._L)
+                return _report_of(self, rebuild_above)
             bones = bones.numpy()
         try:
             m = scene.bone_matrices(bones)
         except (ValueError, TypeError) as e:
             raise NativeError(ERR_INVALID, f"skin: {e}") from None
-        _check(self._L.rvpt_hip_upload_scene(self._h, _ptr(m), NODES_UPDATE_SKIN, None, m.shape[0], None, 0), self._h, self._L)
-        return None
+        _check(self._L.rvpt_hip_upload_scene(self._h, _ptr(m), count, None, m.shape[0], None, 0), self._h, self._L)
+        return _report_of(self, rebuild_above)
 
     def set_frame(self, settings: np.ndarray, camera: np.ndarray) -> None:
         settings = np.ascontiguousarray(settings)

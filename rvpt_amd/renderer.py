@@ -340,11 +340,15 @@ class RVPT:
             self._ctx.bind_skin(np.ascontiguousarray(rec.reshape(-1, 3)[np.asarray(self.primitive_indices, dtype=np.int64)]).reshape(-1))
         self._skin = rec.copy()
 
-    def skin(self, bones) -> None:
+    def skin(self, bones, rebuild_above=None):
         """Linear blend skinning — the SKIN UPDATE (Context.skin; include/rvpt_hip.h): `bones` (float32[k, 3, 4], [k, 12], or [k, 4, 4] with last rows 0 0 0 1) pose
         EVERY vertex from the REST POSE — pose_parts' rest pose: the triangles as the last initialize() or update_triangles left them; two skin updates do not
         compose — by the four weighted matrices bind_skin gave it; every box is refitted, on the device and in bvh_nodes.  scene.skin_triangles is the statement.
-        The next update() restarts the accumulation, as after update_triangles."""
+        The next update() restarts the accumulation, as after update_triangles.
+        rebuild_above: Context.skin's keyword — the GUARDED form: the skinned tree's SAH cost is reported (native.UpdateReport) and, past that factor of the cost of
+        the tree as built, the device rebuilds by the builder of initialize(), carries its rest pose along and keeps its binding; bvh_nodes, primitive_indices and
+        sorted_triangles are then those of a fresh build of the skinned triangles, made when asked for.  The rest copy and the binding kept here, in added order,
+        stay.  A limit needs build="device*"; math.inf only reports."""
         if self._ctx is None or self._n_triangles is None:
             raise RuntimeError("skin before initialize()")
         if self._skin is None:
@@ -357,15 +361,21 @@ class RVPT:
             skinned[:, 12:] = current[:, 12:]
         except (ValueError, TypeError) as e:
             raise native.NativeError(native.ERR_INVALID, f"skin: {e}") from None
-        self._ctx.skin(m)
+        report = self._ctx.skin(m) if rebuild_above is None else self._ctx.skin(m, rebuild_above=rebuild_above)
         self._rest_triangles = rest
         self.triangles = [skinned]
         if self._device_built:
             self._current_triangles = skinned
-        if self._built_from is None:  # there is a host statement to keep right: every box moves
+        if report is not None and report.rebuilt:
+            # the device holds a new tree and a new permutation: the host statement is that of a fresh build from the skinned triangles, made when asked for
+            self._built_from = skinned
+            self._bvh_nodes = self._primitive_indices = self._sorted_triangles = None
+            self._nodes_stale, self._stale_touched = False, None
+        elif self._built_from is None:  # there is a host statement to keep right: every box moves
             self._sorted_triangles = skinned[np.asarray(self._primitive_indices, dtype=np.int64)]
             self._nodes_stale, self._stale_touched = self._bvh_nodes is not None, None
         self._previous_key = None  # a new scene: nothing accumulated so far belongs to it
+        return report
 
     # -- lifecycle -----------------------------------------------------------------------------------------
     def initialize(self) -> bool:

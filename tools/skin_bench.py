@@ -5,9 +5,12 @@ whole-mesh pose update.  Candidates: the skin update from host bones and from de
 of the call, median of 20 after 3 warm-up rounds; the binding of a candidate's bone count is made outside the timed call).  Then the bind itself, from host and
 from device memory, and the kernel resources from the compiler's metadata.  -> stdout (profiles/skin_update.txt)
 Nothing here is a pass/fail bar: the two expectations of the header are printed beside the numbers.
-usage: tools/skin_bench.py [all|skin]     (skin: the skin updates alone, for a second library named by RVPT_HIP_LIB — the global-load form of the kernel,
-profiles/skin_update_exp_global_bones.patch — whose lines go beside the first run's)"""
-import os, statistics, sys, time
+usage: tools/skin_bench.py [all|skin|guard]     (skin: the skin updates alone, for a second library named by RVPT_HIP_LIB — the global-load form of the kernel,
+profiles/skin_update_exp_global_bones.patch — whose lines go beside the first run's; guard: the GUARDED SKIN UPDATE (Context.skin(rebuild_above=)) alone ->
+stdout (profiles/guarded_skin.txt): what the guard adds to a plain skin, both alternating in one loop on one context; what a guarded skin that rebuilds costs,
+per builder; and the ratio a bend of the bone grid reports.  Expected before the run: the guard adds about what it adds to a pose, 0.045 ms
+(profiles/guarded_pose.txt: the same two cost kernels and one 8-byte read), and a rebuild costs about the guarded pose's, 2.2 / 3.5 / 15.1 ms)"""
+import math, os, statistics, sys, time
 from pathlib import Path
 
 import numpy as np
@@ -73,6 +76,77 @@ import torch  # noqa: E402
 
 ctx = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BVH)
 ctx.build_scene(tris0, mats, method="sah")
+
+
+def bend(tris, k, amplitude, sign):
+    """the bones of `bones` with the middle column of the grid carried along z by `sign` x `amplitude`, its neighbours by half of that: the patch folds along a line"""
+    g = int(round(np.sqrt(k)))
+    out = bones(tris, k, 0)
+    for b in range(k):
+        d = abs(b % g - g // 2)
+        if d <= 1:
+            out[b, 2, 3] += np.float32(sign * amplitude * (1.0 if d == 0 else 0.5))
+    return out
+
+
+def guard_section():
+    k = 64
+    rec = weights(tris0, k)
+    d_rec = torch.from_numpy(rec.view(np.uint8).reshape(-1, 32).copy()).to("cuda:0")
+    ctx.bind_skin(d_rec)
+    gentle = [bones(tris0, k, f) for f in (0, 1)]
+    variants = {"plain skin, 64 bones, host array": lambda j: ctx.skin(gentle[j]),
+                "guarded skin, report only, the same bones": lambda j: ctx.skin(gentle[j], rebuild_above=math.inf),
+                "guarded skin, limit 1.1 (never reached), the same bones": lambda j: ctx.skin(gentle[j], rebuild_above=1.1)}
+    times = {name: [] for name in variants}
+    ratios = []
+    for it in range(23):  # the candidate and its yardstick alternate: whatever drifts, drifts for both
+        for name, fn in variants.items():
+            t0 = time.perf_counter()
+            rep = fn(it % 2)
+            if it >= 3:
+                times[name].append(time.perf_counter() - t0)
+            assert rep is None or not rep.rebuilt
+            if rep is not None:
+                ratios.append(rep.ratio)
+    print(f"\n== the guard's cost: {n} triangles, {k} bones on a grid with bilinear weights, SAH device build (wall clock of the call; alternating in one loop on one context) ==")
+    for name, ts in times.items():
+        print(f"{name:56s} {spread(ts)}")
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    plain = med["plain skin, 64 bones, host array"]
+    print(f"guarded (report only) - plain = {(med['guarded skin, report only, the same bones'] - plain) * 1e3:.3f} ms (expected: about the 0.045 ms of the guarded pose);   "
+          f"guarded / plain = {med['guarded skin, report only, the same bones'] / plain:.2f};   ratios reported by the gentle bones: {min(ratios):.4f} .. {max(ratios):.4f}")
+
+    print("\n== a guarded skin that rebuilds (limit 1.0; the middle column of the bone grid carried half the extent along z and against it in turn, each on the tree "
+          "built for the other; wall clock of the call; expected: about the guarded pose's 2.2 / 3.5 / 15.1 ms) ==")
+    folds = [bend(tris0, k, 0.5 * ext, s) for s in (1.0, -1.0)]
+    for method in ("lbvh", "ploc", "sah"):
+        built = ctx.build_scene(tris0, mats, method=method)
+        ctx.bind_skin(d_rec)
+        ts, kept = [], 0
+        for it in range(7):
+            t0 = time.perf_counter()
+            rep = ctx.skin(folds[it % 2], rebuild_above=1.0)
+            dt = time.perf_counter() - t0
+            if rep.rebuilt and it >= 1:
+                ts.append(dt)
+            kept += not rep.rebuilt
+        print(f"{method:5s} (the scene holds: {built:4s}) " + (spread(ts) if ts else "never rebuilt") + f"   calls that refitted: {kept} of 7")
+
+    print("\n== the ratio a bend of the bone grid reports (SAH device build of the rest pose, report only; the middle column of the 8 x 8 grid carried along z by the "
+          "given share of the extent, its two neighbours by half of that, over the gentle bones) ==")
+    for share in (0.01, 0.05, 0.1, 0.25, 0.5):
+        ctx.build_scene(tris0, mats, method="sah")
+        ctx.bind_skin(d_rec)
+        rep = ctx.skin(bend(tris0, k, share * ext, 1.0), rebuild_above=math.inf)
+        print(f"bend of {share:5.2f} x extent   cost {rep.cost:12.4f}   base {rep.base_cost:12.4f}   ratio {rep.ratio:8.4f}")
+
+
+if what == "guard":
+    guard_section()
+    ctx.close()
+    sys.exit(0)
+
 recs = {k: weights(tris0, k) for k in BONES}
 mats_h = {k: [bones(tris0, k, f) for f in (0, 1)] for k in BONES}
 mats_d = {k: [torch.from_numpy(m).to("cuda:0") for m in mats_h[k]] for k in BONES}

@@ -8,17 +8,20 @@ from pathlib import Path
 
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "librvpt_hip.so"
-SOURCES = [_PKG / "csrc" / n for n in ("rvpt_kernels.hip", "rvpt_packets.hip", "rvpt_bvh4.hip", "rvpt_abi.hip", "bvh_builder.cpp", "bvh_wide.cpp")]
-SOURCES.append(_PKG / "csrc" / "rvpt_refit.hip")  # the geometry update's kernels: no frame kernels, hence not among KERNEL_SOURCES below (kernel_sha stands)
-SOURCES.append(_PKG / "csrc" / "rvpt_build.hip")  # the device BVH build's kernels (upload_scene's build form): likewise outside KERNEL_SOURCES
-SOURCES.append(_PKG / "csrc" / "rvpt_ploc.hip")  # the PLOC build form's kernels: likewise
-SOURCES.append(_PKG / "csrc" / "rvpt_sah.hip")  # the SAH build form's kernels: likewise
-SOURCES.append(_PKG / "csrc" / "rvpt_frames.hip")  # rvpt_hip_read / write_accum on 4-byte aligned device memory: layout kernels, likewise
-SOURCES.append(_PKG / "csrc" / "rvpt_query.hip")  # ray queries (rvpt_hip_read with FORMAT_RAY_HITS): the walks without the path tracer, no frame kernels, likewise
-SOURCES.append(_PKG / "csrc" / "rvpt_paths.hip")  # path queries (rvpt_hip_read with FORMAT_RAY_PATHS and FORMAT_RAY_PATHS_MODE): those walks under shade() / shade_generic(), kernels of their own, likewise
-SOURCES.append(_PKG / "csrc" / "rvpt_nearest.hip")  # point queries (rvpt_hip_read with FORMAT_NEAREST_POINTS): a walk that prunes by distance, kernels of its own, likewise
-SOURCES.append(_PKG / "csrc" / "rvpt_surface.hip")  # the geometry read-back (rvpt_hip_read with FORMAT_TRIANGLES and FORMAT_SURFACE_POINTS): one record kernel, the row scatter launched from there, likewise
-HEADERS = [_PKG / "csrc" / "rvpt_surface.h", _PKG / "csrc" / "rvpt_nearest.h", _PKG / "csrc" / "rvpt_paths.h", _PKG / "csrc" / "rvpt_query.h", _PKG / "csrc" / "rvpt_frames.h", _PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
+SOURCES = [_PKG / "csrc" / n for n in (
+    "rvpt_kernels.hip", "rvpt_packets.hip", "rvpt_bvh4.hip", "rvpt_abi.hip", "bvh_builder.cpp", "bvh_wide.cpp",
+    "rvpt_scene.hip",  # every form of rvpt_hip_upload_scene: host code only, no kernels
+    "rvpt_refit.hip",  # the geometry update's kernels: no frame kernels, hence not among KERNEL_SOURCES below (kernel_sha stands)
+    "rvpt_build.hip",  # the device BVH build's kernels (upload_scene's build form): likewise outside KERNEL_SOURCES
+    "rvpt_ploc.hip",  # the PLOC build form's kernels: likewise
+    "rvpt_sah.hip",  # the SAH build form's kernels: likewise
+    "rvpt_frames.hip",  # rvpt_hip_read / write_accum on 4-byte aligned device memory: layout kernels, likewise
+    "rvpt_query.hip",  # ray queries (rvpt_hip_read with FORMAT_RAY_HITS): the walks without the path tracer, no frame kernels, likewise
+    "rvpt_paths.hip",  # path queries (rvpt_hip_read with FORMAT_RAY_PATHS and FORMAT_RAY_PATHS_MODE): those walks under shade() / shade_generic(), kernels of their own, likewise
+    "rvpt_nearest.hip",  # point queries (rvpt_hip_read with FORMAT_NEAREST_POINTS): a walk that prunes by distance, kernels of its own, likewise
+    "rvpt_surface.hip",  # the geometry read-back (rvpt_hip_read with FORMAT_TRIANGLES and FORMAT_SURFACE_POINTS): one record kernel, the row scatter launched from there, likewise
+)]
+HEADERS = [_PKG / "csrc" / "rvpt_ctx.h", _PKG / "csrc" / "rvpt_scene_forms.h", _PKG / "csrc" / "rvpt_surface.h", _PKG / "csrc" / "rvpt_nearest.h", _PKG / "csrc" / "rvpt_paths.h", _PKG / "csrc" / "rvpt_query.h", _PKG / "csrc" / "rvpt_frames.h", _PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
            _PKG / "csrc" / "rvpt_vis.h", _PKG.parent / "include" / "rvpt_hip.h", _PKG.parent / "include" / "rvpt_hip_lab.h"]
 
 # -ffp-contract=off: the arithmetic specification fixes where FMAs happen; applies to the
@@ -142,11 +145,12 @@ HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selft
                 "host_selftest_nearest": ["host_selftest_nearest.cpp", "rvpt_host.cpp"],
                 "host_selftest_surface": ["host_selftest_surface.cpp", "rvpt_host.cpp"],
                 "host_row_boxes": ["host_row_boxes.cpp"],  # (rvpt_vis.h alone: the row boxes' table for scenes given in files, tests/test_row_boxes.py)
-                "host_frame_runs": ["host_frame_runs.cpp"]}  # (rvpt_packets.h alone: the item map of listed launches in frame-run order, tests/test_frame_runs_host.py)
+                "host_frame_runs": ["host_frame_runs.cpp"],  # (rvpt_packets.h alone: the item map of listed launches in frame-run order, tests/test_frame_runs_host.py)
+                "host_scene_forms": ["host_scene_forms.cpp"]}  # (rvpt_scene_forms.h alone: which form of upload_scene a call is, tests/test_scene_forms_host.py)
 HOST_NEEDS_HIP = {"host_selftest_frames", "host_selftest_rays", "host_selftest_multi_hit", "host_selftest_paths", "host_selftest_path_modes", "host_selftest_nearest", "host_selftest_surface"}  # targets that allocate device memory themselves (its `--gpu` case): HIP's host API, still compiled by g++
 
 
-HOST_WITH_HIPCC = {"host_row_boxes", "host_frame_runs"}  # targets that include the kernels' host + device headers (csrc/): the host half of a HIP compilation, no device code, no library
+HOST_WITH_HIPCC = {"host_row_boxes", "host_frame_runs", "host_scene_forms"}  # targets that include the kernels' host + device headers (csrc/): the host half of a HIP compilation, no device code, no library
 
 
 def hipcc_host_cmd(sources, out, extra=()) -> list:
@@ -164,7 +168,7 @@ def build_host(force: bool = False) -> Path:
     g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames`, `host_selftest_guard`, `host_selftest_sparse`, `host_selftest_pose`, `host_selftest_pose_guard`, `host_selftest_skin`, `host_selftest_skin_guard`, `host_selftest_rays`, `host_selftest_multi_hit`, `host_selftest_paths`, `host_selftest_path_modes`, `host_selftest_nearest` and `host_selftest_surface`."""
     build_native()
     HOST_BIN_DIR.mkdir(exist_ok=True)
-    srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h", _PKG / "csrc" / "rvpt_vis.h"]
+    srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h", _PKG / "csrc" / "rvpt_vis.h", _PKG / "csrc" / "rvpt_scene_forms.h"]
     newest = max(p.stat().st_mtime for p in srcs + [LIB_PATH])
     for name, files in HOST_TARGETS.items():
         out = HOST_BIN_DIR / name

@@ -1,4 +1,4 @@
-// bvh_wide.h — the 4-wide regrouping of a binary BVH (bvh_wide.cpp), shared by the launcher (rvpt_abi.hip) and the exported rvpt_bvh_wide_form.
+// bvh_wide.h — the 4-wide regrouping of a binary BVH (bvh_wide.cpp), shared by the full upload (rvpt_scene.hip) and the exported rvpt_bvh_wide_form.
 #pragma once
 
 #include <cstddef>

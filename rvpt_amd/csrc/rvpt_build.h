@@ -1,4 +1,4 @@
-// rvpt_build.h — the device BVH build (rvpt_build.hip), launched by rvpt_hip_upload_scene's BUILD FORM (rvpt_abi.hip: build_scene_on_device): triangles in the
+// rvpt_build.h — the device BVH build (rvpt_build.hip), launched by rvpt_hip_upload_scene's BUILD FORM (rvpt_scene.hip: build_scene_on_device): triangles in the
 // caller's order in, the binary tree in its breadth-first device layout, its level table and its 4-wide form out.  Nothing derived from the triangles visits
 // the host except a few counters.
 //

@@ -217,7 +217,7 @@ __global__ void wide_pick(const float4 *__restrict__ nodes, uint32_t n_nodes, co
     cnt[j] = 0u;
     const uint32_t w = wbase + j, root = bin[j];
     // (a guard, not a result: a level that does not fit wide_cap rows is left partly written, and the host, which reads the same count from offs[count],
-    // fails the build before anything reads it — rvpt_abi.hip: build_scene_on_device)
+    // fails the build before anything reads it — rvpt_scene.hip: build_scene_on_device)
     if (w >= wide_cap || root >= n_nodes) return;
     const uint32_t f0 = load_node(nodes, root).first;
     if (f0 >= n_nodes - 1u) return;

@@ -1,4 +1,4 @@
-// rvpt_refit.h — the geometry update's kernels (rvpt_refit.hip), launched by rvpt_hip_upload_scene's update form (rvpt_abi.hip: update_geometry).
+// rvpt_refit.h — the geometry update's kernels (rvpt_refit.hip), launched by rvpt_hip_upload_scene's update form (rvpt_scene.hip: update_geometry).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,7 +21,7 @@ __global__ void tree_cost_finish(const double *__restrict__ partials, uint32_t n
 // the triangles of d_tris carried back into the caller's order for a guarded rebuild: out[perm[pos]] = tris[pos], grid = ceil(4 n / block) (one thread per quad)
 __global__ void carry_back_triangles(const float4 *__restrict__ tris, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ out);
 
-// The SPARSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; rvpt_abi.hip: update_geometry_sparse).  refit_level for the flagged nodes of a level alone ...
+// The SPARSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; rvpt_scene.hip: update_geometry_sparse).  refit_level for the flagged nodes of a level alone ...
 __global__ void refit_level_dirty(float4 *__restrict__ nodes, uint32_t begin, uint32_t end, uint32_t n_nodes, const float4 *__restrict__ tris, uint32_t n_tris,
                                   uint32_t *__restrict__ dirty);
 // ... the maps of a topology (both pre-filled with 0xFFFFFFFF; one thread per node) and the inverse of a build form's permutation (one thread per triangle) ...
@@ -37,20 +37,20 @@ __global__ void sparse_scatter(const float4 *__restrict__ src, const uint32_t *_
                                float4 *__restrict__ tris, const uint32_t *__restrict__ leaf_of, const uint32_t *__restrict__ parent, uint32_t n_nodes,
                                uint32_t *__restrict__ dirty);
 
-// The POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; rvpt_abi.hip: update_geometry_pose): one thread per listed triangle of a validated list, blocks
+// The POSE UPDATE of rvpt_hip_upload_scene (include/rvpt_hip.h; rvpt_scene.hip: pose_validate, pose_execute): one thread per listed triangle of a validated list, blocks
 // of 256.  rest: three quads per triangle in stored order; moves: k rvpt_part_move records as 16 words each; prefix: k + 1 exclusive sums of their counts,
 // prefix[k] = total; inv_perm may be null.  Writes the vertex rows of tris and flags the paths as sparse_scatter does.
 __global__ void pose_parts(const float4 *__restrict__ rest, const uint32_t *__restrict__ moves, const uint32_t *__restrict__ prefix, uint32_t k, uint32_t total,
                            uint32_t n_tris, const uint32_t *__restrict__ inv_perm, float4 *__restrict__ tris, const uint32_t *__restrict__ leaf_of,
                            const uint32_t *__restrict__ parent, uint32_t n_nodes, uint32_t *__restrict__ dirty);
 
-// The GUARDED POSE UPDATE (include/rvpt_hip.h; rvpt_abi.hip: update_geometry_pose_guarded): the rest pose through a rebuild.  Three quads per triangle on both
+// The GUARDED POSE UPDATE (include/rvpt_hip.h; rvpt_scene.hip: guarded_tail): the rest pose through a rebuild.  Three quads per triangle on both
 // sides, one thread per quad, grid = ceil(3 n / block): out[perm[pos]] = rest[pos] with the old permutation in front of the build ...
 __global__ void rest_to_caller_order(const float4 *__restrict__ rest, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ out);
 // ... and rest[pos] = in[perm[pos]] with the new one behind it
 __global__ void rest_to_stored_order(const float4 *__restrict__ in, const uint32_t *__restrict__ perm, uint32_t n, float4 *__restrict__ rest);
 
-// The SKIN UPDATE (include/rvpt_hip.h; rvpt_abi.hip: bind_skin, update_geometry_skin).  skin_check: the check of a bind from device memory, one thread per
+// The SKIN UPDATE (include/rvpt_hip.h; rvpt_scene.hip: bind_skin, skin_validate, skin_execute).  skin_check: the check of a bind from device memory, one thread per
 // 32-byte record, grid = ceil(n_records / block); words = {all ones, 0} before the launch, the smallest offence and the largest bone with its place after it ...
 __global__ void skin_check(const uint4 *__restrict__ skin, uint64_t n_records, uint32_t limit, unsigned long long *__restrict__ words);
 // ... and the skin: one thread per vertex quad of the rest pose at a time, ANY grid of kSkinBlock lanes (the work-groups stride over the 3 n quads; the host

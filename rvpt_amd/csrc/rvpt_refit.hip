@@ -81,7 +81,7 @@ __global__ void refit_wide_gather(float *__restrict__ wide, const uint32_t *__re
 //
 // RELIES ON the breadth-first device layout: the node array [0, n_nodes) holds the root at 0, the unused slot 1, and from 2 on the levels of the tree back to
 // back, so EVERY slot but 1 is a node the root reaches and a flat pass over the array is a pass over the tree.  Established by rvpt_hip_upload_scene
-// (rvpt_abi.hip), which copies a caller's tree into that layout node by reachable node — strays never arrive — and by build_scene_on_device, whose level
+// (rvpt_scene.hip), which copies a caller's tree into that layout node by reachable node — strays never arrive — and by build_scene_on_device, whose level
 // loops hand out the slots pair by pair; both pass n_nodes = the end of the last level.  Slot 1 is skipped here by its index, whatever it holds.
 //
 // No atomics, and a fixed shape of additions: lane i of a wave holds node base + i, the wave folds its 64 terms with __shfl_down (32, 16, .. 1), lane 0 of

@@ -112,7 +112,7 @@ def shrunk(tris, idx, factor=0.5):
 # ---- the device layout --------------------------------------------------------------------------------------------------------------------------------------
 
 def device_layout(nodes):
-    """upload_scene's relayout (rvpt_abi.hip): a FIFO from the root — root at 0, slot 1 zero, the children of every inner node taken from the queue at the next
+    """upload_scene's relayout (rvpt_scene.hip): a FIFO from the root — root at 0, slot 1 zero, the children of every inner node taken from the queue at the next
     free pair 2, 4, ..; nodes the root does not reach never arrive.  Returns (NODE records [len(nodes) + 1], levels uint32[h, 2] = [begin, end) per level)."""
     src = np.ascontiguousarray(nodes).view(NODE).reshape(-1)
     first, count = src["first"].tolist(), src["count"].tolist()
@@ -165,7 +165,7 @@ def levels_of(dev_nodes):
 
 
 def head_shift(n_device_nodes, n_tris, max_count):
-    """rvpt_abi.hip's rule: indices of the device layout and of the triangles below 2^shift, leaf sizes below 2^(32 - shift); 0: heads do not pack"""
+    """rvpt_scene.hip's rule: indices of the device layout and of the triangles below 2^shift, leaf sizes below 2^(32 - shift); 0: heads do not pack"""
     shift = 1
     while shift < 31 and (1 << shift) <= max(n_device_nodes, n_tris):
         shift += 1

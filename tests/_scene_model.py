@@ -41,7 +41,7 @@ SITUATIONS = ("a guarded plain rebuild while a binding and a rest pose are held,
               "a guarded pose rebuild, then a pose of an unlisted part",
               "a refusal directly after a rebuild",
               "a bind between two pose updates")
-# the refusals the generator draws: what, the pattern a message must match — each a piece of the header's wording or of rvpt_abi.hip's message text
+# the refusals the generator draws: what, the pattern a message must match — each a piece of the header's wording or of rvpt_abi.hip's and rvpt_scene.hip's message text
 REFUSALS = {
     "skin without a binding": "skin update before a bind",
     "skin with too few bones": "the binding names bone",

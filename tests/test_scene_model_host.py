@@ -1,5 +1,5 @@
 """tests/_scene_model.py held against what already pins the rules, without a GPU: its guarded pose form against tests/_guarded_pose.py's step, its forms
-against the examples include/rvpt_hip.h itself gives, its refusal patterns and its list of pairs no context can make against the header's and rvpt_abi.hip's
+against the examples include/rvpt_hip.h itself gives, its refusal patterns and its list of pairs no context can make against the header's, rvpt_abi.hip's and rvpt_scene.hip's
 text, and the generator against its two conditions, its variants, its coverage table (printed) and its own reproducibility."""
 import math
 import re
@@ -193,7 +193,7 @@ def header_text():
 
 def test_every_pattern_is_the_headers_or_the_librarys_wording():
     header = header_text()
-    abi = (ROOT / "rvpt_amd" / "csrc" / "rvpt_abi.hip").read_text()
+    abi = "".join((ROOT / "rvpt_amd" / "csrc" / name).read_text() for name in ("rvpt_abi.hip", "rvpt_scene.hip"))
     messages = " ".join(re.findall(r'"((?:[^"\\]|\\.)*)"', abi))
     model_source = (ROOT / "tests" / "_scene_model.py").read_text()
     patterns = set(sm.REFUSALS.values()) | set(re.findall(r'Refused\("([^"]+)"\)', model_source))

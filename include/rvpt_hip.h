@@ -87,7 +87,9 @@ extern "C" {
                                      new symbol: the skin update's arguments under a count RVPT_HIP_NODES_UPDATE_SKIN_GUARDED(permille) — until then the
                                      "NULL scene array" error — are the GUARDED SKIN UPDATE: the skin update, the SAH cost of the skinned tree reported, and
                                      past a limit a rebuild by the builder that made the tree, through which the rest pose follows its triangles and the
-                                     binding stays */
+                                     binding stays.  Still 8, no new symbol: rvpt_hip_read with a format RVPT_HIP_FORMAT_NEAREST_POINTS_K(k) (49 .. 56) —
+                                     until then the "unknown format" error — is a K-NEAREST POINT QUERY: `dst` holds groups of k rvpt_point_hit records,
+                                     the point in the first, the k nearest triangles of the mesh out */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -206,6 +208,9 @@ typedef struct rvpt_point_hit {
     float closest[3]; float d2;                            /* out: the nearest point of the mesh and its squared distance */
     uint32_t prim;    float u; float v; uint32_t region;   /* out: the triangle, the pair the region computed, 0 face, 1/2/3 vertex a/b/c, 4/5/6 edge ab/ac/bc */
 } rvpt_point_hit;
+
+#define RVPT_HIP_POINT_MAX_NEAREST 8u /* per call: the largest k of a k-nearest point query */
+#define RVPT_HIP_FORMAT_NEAREST_POINTS_K(k) (48 + (k))     /* k = 1 .. RVPT_HIP_POINT_MAX_NEAREST: formats 49 .. 56; dst: n groups of k rvpt_point_hit (K-NEAREST POINTS at rvpt_hip_read) */
 
 #define RVPT_HIP_FORMAT_TRIANGLES 5      /* dst: rvpt_triangle[n_tris], out: the stored rows in update order (TRIANGLES at rvpt_hip_read) */
 #define RVPT_HIP_FORMAT_SURFACE_POINTS 6 /* dst: rvpt_surface_point[dst_bytes / 48], in and out (SURFACE POINTS at rvpt_hip_read) */
@@ -757,6 +762,33 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  *   the frame counter, and rvpt_hip_last_error on success: a frame dispatched after a point query is bit for bit the frame dispatched without it.
  * - The answer is on the scene as the last update form left it: plain, guarded, sparse, pose or skin.
  * DESIGN.md 5.19 has the kernels and what was measured (profiles/nearest_points.txt).
+ *
+ * K-NEAREST POINTS — the k nearest triangles of the mesh to the caller's own points, in place:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_NEAREST_POINTS_K(k), records, n * k * sizeof(rvpt_point_hit));      k = 1 .. RVPT_HIP_POINT_MAX_NEAREST
+ *
+ * `dst` then holds n GROUPS of k consecutive rvpt_point_hit records.  Record 0 of a group carries the point and the bound (point, max_d2); the in fields of
+ * records 1 .. k-1 are ignored.  No in field of any record is ever written.  On return the out fields (closest, d2, prim, u, v, region) of record j hold the
+ * j-th entry of the group's answer.  The k belongs to the call, not to the record: a launch is uniform in k.  Formats 48 and 57 are the "unknown format" error.
+ * - THE ANSWER IS DEFINED WITHOUT REFERENCE TO ANY WALK, as a point query's is.  Every stored triangle i gets the candidate (d2_i, prim_i) of NEAREST POINTS,
+ *   by its PER-TRIANGLE ARITHMETIC, unchanged; a candidate whose d2 is NaN is never one.  The answer is the first k, in ascending lexicographic order of
+ *   (d2, prim), of all candidates that are smaller than (max_d2, 0xFFFFFFFF).  So d2 == max_d2 is accepted, among equal d2 the smaller reported prim comes
+ *   first, and when more than k candidates tie at the k-th distance the smaller numbers are the ones returned.
+ * - prim is numbered as a point query numbers it (THE NUMBERING OF prim above): the stored order after an upload, the caller's order after a build form.  The
+ *   answer is therefore the same after every builder.
+ * - A RADIUS QUERY.  A finite max_d2 makes the form one: the group holds EVERY triangle within the bound if its last slot is a miss, otherwise the k nearest of them.
+ * - MISSES AND INVALID RECORDS.  From the first slot no candidate fills, every slot is a miss: closest = 0, 0, 0, d2 = the bits of record 0's max_d2 as given,
+ *   prim = 0xFFFFFFFF, u = v = 0, region = 0.  A group whose record 0 is invalid by the rule of NEAREST POINTS gets k such slots, decided before any walk.  The
+ *   empty scene answers every group so.
+ * - With k = 1 the form is format 4 exactly: RVPT_HIP_FORMAT_NEAREST_POINTS_K(1) is format 4, the same kernels, the same bytes and the same messages.
+ * - Each stored triangle is taken to lie under one leaf, as in every tree the library's builders and rvpt_bvh_build make.  A caller's tree that lists a triangle
+ *   under two leaves may report it twice.
+ * - Everything else is a point query's rule: the call needs a scene and no rvpt_hip_set_frame; dst_bytes must be a multiple of 48 * k, else
+ *   RVPT_HIP_ERR_INVALID (the message gives k and the byte count); dst_bytes == 0 is a successful no-op; fewer than 2^32 records (n * k) per call; `dst` is host
+ *   memory or 16-byte aligned device memory of the context's GPU, another GPU's memory is an error naming both devices, and in every error case `dst` is
+ *   untouched; host records go through the staging buffer and only the out fields travel back; the call is LOCAL under a communicator, implies rvpt_hip_wait,
+ *   leaves untouched what a point query leaves untouched, and answers on the scene as the last update form left it.
+ * DESIGN.md 5.26 has the kernels and what was measured (profiles/nearest_points_k.txt).
  *
  * TRIANGLES — the whole mesh as it now stands:
  *

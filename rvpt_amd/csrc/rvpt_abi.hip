@@ -53,6 +53,7 @@ static_assert(sizeof(rvpt_material) == 48, "Material layout (structs.glsl:22-33)
 static_assert(sizeof(rvpt_render_settings) == 40, "RenderSettings std140 block (compute_pass.comp:28-40)");
 static_assert(sizeof(rvpt_camera_data) == 80, "Camera block (compute_pass.comp:44-49)");
 static_assert(RVPT_HIP_RAY_MAX_HITS == rv::kQueryMaxHits, "the k of a k-nearest ray query: the header's and the kernels'");
+static_assert(RVPT_HIP_POINT_MAX_NEAREST == rv::kNearestMaxK, "the k of a k-nearest point query: the header's and the kernels'");
 static_assert(sizeof(rvpt_ray_hit) == rv::kQueryRecordBytes && offsetof(rvpt_ray_hit, tmax) == 12 && offsetof(rvpt_ray_hit, dir) == 16 && offsetof(rvpt_ray_hit, flags) == 28 &&
                   offsetof(rvpt_ray_hit, t) == 32 && offsetof(rvpt_ray_hit, prim) == 36 && offsetof(rvpt_ray_hit, u) == 40 && offsetof(rvpt_ray_hit, v) == 44,
               "a ray query's record: three float4 (rvpt_query.hip)");
@@ -1460,7 +1461,8 @@ int rvpt_hip_gather(rvpt_hip_ctx *ctx, void *dst_dev_rgba32f)
 // `path_mode` (RecordKind::Paths only): the integrator of the call, 0 .. 9 — RVPT_HIP_FORMAT_RAY_PATHS is mode 9, RVPT_HIP_FORMAT_RAY_PATHS_MODE(m) is mode m.
 // `hits` (RecordKind::Rays only): 0 for RVPT_HIP_FORMAT_RAY_HITS and for RVPT_HIP_FORMAT_RAY_HITS_NEAREST(1), which is the same call; k for RVPT_HIP_FORMAT_RAY_HITS_NEAREST(k), k > 1 (K-NEAREST RAY QUERIES) — `dst` then holds groups of
 // k records, one ray each, and the plan and the launch count groups; everything else, the staging and the copy back of every record's out quad included, is
-// per record as before.
+// per record as before.  (RecordKind::Points: 0 for RVPT_HIP_FORMAT_NEAREST_POINTS and RVPT_HIP_FORMAT_NEAREST_POINTS_K(1), the same call; k for
+// RVPT_HIP_FORMAT_NEAREST_POINTS_K(k), k > 1 (K-NEAREST POINTS) — groups of k records, one point each, likewise.)
 enum class RecordKind { Rays, Paths, Points, Surface };
 static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const RecordKind kind, const uint32_t path_mode = rv::kPathModeKajiya, const uint32_t hits = 0)
 {
@@ -1468,6 +1470,9 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
     const char *what = surface ? "surface" : (points ? "point" : (paths ? "path" : "ray"));
     const char *record = surface ? "rvpt_surface_point" : (points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : "rvpt_ray_hit"));
     const size_t out_offset = surface ? offsetof(rvpt_surface_point, point) : (points ? offsetof(rvpt_point_hit, closest) : offsetof(rvpt_ray_hit, t));  // where a record's out fields begin
+    if (hits && points && dst_bytes % (sizeof(rvpt_point_hit) * hits))
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "point query with k = %u: dst_bytes %zu is not a multiple of the %zu bytes of a group of k rvpt_point_hit", hits, dst_bytes,
+                    sizeof(rvpt_point_hit) * hits);
     if (hits && dst_bytes % (sizeof(rvpt_ray_hit) * hits))
         return fail(ctx, RVPT_HIP_ERR_INVALID, "ray query with k = %u: dst_bytes %zu is not a multiple of the %zu bytes of a group of k rvpt_ray_hit", hits, dst_bytes,
                     sizeof(rvpt_ray_hit) * hits);
@@ -1497,10 +1502,10 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
     nearest.brute = !bvh;
     nearest.tris = ctx->d_tris, nearest.nodes = ctx->d_nodes, nearest.perm = scene.perm;
     nearest.n_tris = scene.n_tris, nearest.n_nodes = static_cast<uint32_t>(ctx->n_nodes), nearest.stack_levels = bvh_stack_levels(ctx);
-    const uint32_t groups_of = hits ? hits : 1u;  // records per ray
+    const uint32_t groups_of = hits ? hits : 1u;  // records per ray, or per point
     rv::QueryPlan plan{};
     if (points)
-        HIP_TRY(ctx, rv::nearest_plan(nearest, static_cast<uint32_t>(n), ctx->num_cus, &plan));
+        HIP_TRY(ctx, rv::nearest_plan(nearest, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
     else if (paths)
         HIP_TRY(ctx, rv::path_plan(path_scene, static_cast<uint32_t>(n), ctx->num_cus, path_mode, &plan));
     else if (!surface)  // (a surface read is one record per lane and no walk: no plan, no stack)
@@ -1529,7 +1534,7 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
         mesh.inv_perm = permuted ? ctx->d_surface_inv : nullptr, mesh.n_tris = scene.n_tris;
         HIP_TRY(ctx, rv::surface_launch(ctx->stream, mesh, records, static_cast<uint32_t>(n)));
     } else if (points)
-        HIP_TRY(ctx, rv::nearest_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
+        HIP_TRY(ctx, rv::nearest_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
     else if (paths)
         HIP_TRY(ctx, rv::path_launch(ctx->stream, path_scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n), path_mode));
     else
@@ -1579,6 +1584,9 @@ int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
     if (format == RVPT_HIP_FORMAT_RAY_HITS_NEAREST(1)) return query_records(ctx, dst, dst_bytes, RecordKind::Rays);  // k = 1 IS format 2, its messages included
     if (format > RVPT_HIP_FORMAT_RAY_HITS_NEAREST(1) && format <= static_cast<int>(RVPT_HIP_FORMAT_RAY_HITS_NEAREST(RVPT_HIP_RAY_MAX_HITS)))  // the k nearest hits of a ray; local as well
         return query_records(ctx, dst, dst_bytes, RecordKind::Rays, rv::kPathModeKajiya, static_cast<uint32_t>(format) - RVPT_HIP_FORMAT_RAY_HITS_NEAREST(0u));
+    if (format == RVPT_HIP_FORMAT_NEAREST_POINTS_K(1)) return query_records(ctx, dst, dst_bytes, RecordKind::Points);  // k = 1 IS format 4, its messages included
+    if (format > RVPT_HIP_FORMAT_NEAREST_POINTS_K(1) && format <= static_cast<int>(RVPT_HIP_FORMAT_NEAREST_POINTS_K(RVPT_HIP_POINT_MAX_NEAREST)))  // the k nearest triangles of a point; local as well
+        return query_records(ctx, dst, dst_bytes, RecordKind::Points, rv::kPathModeKajiya, static_cast<uint32_t>(format) - RVPT_HIP_FORMAT_NEAREST_POINTS_K(0u));
     if (format == RVPT_HIP_FORMAT_TRIANGLES) return read_triangles(ctx, dst, dst_bytes);  // local as well
     if (format == RVPT_HIP_FORMAT_SURFACE_POINTS) return query_records(ctx, dst, dst_bytes, RecordKind::Surface);
     if (format == RVPT_HIP_FORMAT_RAY_HITS || format == RVPT_HIP_FORMAT_RAY_PATHS || format == RVPT_HIP_FORMAT_NEAREST_POINTS)  // local even with a communicator: every rank holds the whole scene

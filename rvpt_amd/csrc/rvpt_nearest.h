@@ -12,6 +12,7 @@ namespace rv {
 
 constexpr uint32_t kNearestRecordBytes = 48;  // sizeof(rvpt_point_hit): three float4
 constexpr uint32_t kNearestTileTris = 512;    // triangle rows (three vertex quads each) per LDS tile of the brute-force kernel: 24 KiB
+constexpr uint32_t kNearestMaxK = 8;          // RVPT_HIP_POINT_MAX_NEAREST: the k of a k-nearest point query, held in register lists of 2, 4 or 8 slots
 
 // The scene a point query asks: the vertex rows every update form keeps current, and on BVH contexts the binary nodes with their refitted boxes
 struct NearestScene {
@@ -24,9 +25,11 @@ struct NearestScene {
 };
 
 // The launch shape for n records (QueryPlan's fields as for ray queries; top_nodes is 0): a persistent grid sized from occupancy for the tree walk, one
-// work-group per 256 records for the brute-force kernel.
-hipError_t nearest_plan(const NearestScene &scene, uint32_t n, int num_cus, QueryPlan *plan);
-// Answers records[0 .. n) in place on `stream`.  `scratch` as for query_launch: 64 words (the first is the claim counter, zeroed here), then plan.stack_words.
-hipError_t nearest_launch(hipStream_t stream, const NearestScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n);
+// work-group per 256 records for the brute-force kernel.  k > 1 (RVPT_HIP_FORMAT_NEAREST_POINTS_K(k)): n counts GROUPS of k records, one point each, and the
+// occupancy is that of the k-nearest instance the launch will use.
+hipError_t nearest_plan(const NearestScene &scene, uint32_t n, int num_cus, QueryPlan *plan, uint32_t k = 1);
+// Answers records[0 .. n) in place on `stream` — with k > 1 the n groups records[0 .. n * k), the plan made with the same k.  `scratch` as for query_launch:
+// 64 words (the first is the claim counter, zeroed here), then plan.stack_words.
+hipError_t nearest_launch(hipStream_t stream, const NearestScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n, uint32_t k = 1);
 
 }  // namespace rv

@@ -703,6 +703,26 @@ bool RVPT::closest_points_device(void *records, size_t n)
     }
     return check(backend_.read(ctx_, RVPT_HIP_FORMAT_NEAREST_POINTS, records, n * sizeof(rvpt_point_hit)), "rvpt_hip_read");
 }
+bool RVPT::closest_points(rvpt_point_hit *records, size_t n, int k)
+{
+    if (!closest_points_device(records, n, k)) return false;  // (the library classifies the pointer)
+    if (!device_built_)  // the library numbered the leaf order it was given: every slot of every group
+        for (size_t i = 0; i < n * static_cast<size_t>(k); ++i)
+            if (records[i].prim < order_.size()) records[i].prim = order_[records[i].prim];
+    return true;
+}
+bool RVPT::closest_points_device(void *records, size_t n, int k)
+{
+    if (!ctx_) {
+        error_ = "closest_points before initialize()";
+        return false;
+    }
+    if (k < 1 || k > static_cast<int>(RVPT_HIP_POINT_MAX_NEAREST)) {
+        error_ = "closest_points: k " + std::to_string(k) + " is outside 1 .. " + std::to_string(RVPT_HIP_POINT_MAX_NEAREST);
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_NEAREST_POINTS_K(k), records, n * static_cast<size_t>(k) * sizeof(rvpt_point_hit)), "rvpt_hip_read");
+}
 bool RVPT::read_triangles(std::vector<rvpt_triangle> &triangles)
 {
     if (!ctx_) {

@@ -230,6 +230,13 @@ public:
     bool closest_points(rvpt_point_hit *records, size_t n);
     // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host: prim then stays as the LIBRARY numbers it
     bool closest_points_device(void *records, size_t n);
+    // The k nearest triangles of every point (RVPT_HIP_FORMAT_NEAREST_POINTS_K(k); include/rvpt_hip.h: K-NEAREST POINTS): `records` holds n GROUPS of k
+    // consecutive records, n * k in all; record 0 of a group carries the point and the bound, the out fields of record j receive the j-th entry by (d2, prim)
+    // (prim 0xFFFFFFFF from the first slot no triangle fills).  prim of every slot is numbered as closest_points numbers it.  k outside
+    // 1 .. RVPT_HIP_POINT_MAX_NEAREST fails here, before any call.
+    bool closest_points(rvpt_point_hit *records, size_t n, int k);
+    // the same for n groups in device memory of the context's GPU (16-byte aligned): prim stays as the LIBRARY numbers it, as for closest_points_device above
+    bool closest_points_device(void *records, size_t n, int k);
     // The geometry read-back (rvpt_hip_read with RVPT_HIP_FORMAT_TRIANGLES; include/rvpt_hip.h: TRIANGLES): the stored rows of the mesh as the last update,
     // pose or skin form left them — all 64 bytes of each, nothing recomputed — in the order the triangles were ADDED (after a host build the leaf order the
     // library holds is undone here).  After initialize(); no update() is needed.

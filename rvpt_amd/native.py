@@ -58,6 +58,17 @@ RAY_PATH_DTYPE = np.dtype([("org", "<f4", (3,)), ("seed", "<u4"), ("dir", "<f4",
 FORMAT_NEAREST_POINTS = 4  # RVPT_HIP_FORMAT_NEAREST_POINTS: rvpt_hip_read answers point queries, `dst` holds POINT_HIT_DTYPE records (Context.closest_points)
 # rvpt_point_hit: 48 bytes, three float4 — a point and a SQUARED bound in; the nearest point of the mesh, its squared distance, the triangle, u, v and the region out
 POINT_HIT_DTYPE = np.dtype([("point", "<f4", (3,)), ("max_d2", "<f4"), ("closest", "<f4", (3,)), ("d2", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("region", "<u4")])
+POINT_MAX_NEAREST = 8  # RVPT_HIP_POINT_MAX_NEAREST: the largest k of a k-nearest point query
+
+
+def FORMAT_NEAREST_POINTS_K(k) -> int:
+    """RVPT_HIP_FORMAT_NEAREST_POINTS_K(k), formats 49 .. 56: `dst` holds groups of k POINT_HIT_DTYPE records, the point in the first, its k nearest triangles
+    out (Context.closest_points(..., k=k)).  A k that is no int in 1 .. POINT_MAX_NEAREST raises before any call."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= POINT_MAX_NEAREST:
+        raise NativeError(ERR_INVALID, f"k must be an int in 1 .. {POINT_MAX_NEAREST}, got {k!r}")
+    return 48 + int(k)
+
+
 FORMAT_TRIANGLES = 5  # RVPT_HIP_FORMAT_TRIANGLES: rvpt_hip_read returns the stored rvpt_triangle rows in update order (Context.read_triangles)
 FORMAT_SURFACE_POINTS = 6  # RVPT_HIP_FORMAT_SURFACE_POINTS: rvpt_hip_read answers surface records, `dst` holds SURFACE_POINT_DTYPE records (Context.surface_points)
 # rvpt_surface_point: 48 bytes, three float4 — prim, u, v as a query reported them (and a reserved word) in; the point of the stored mesh, its material word, its normal out
@@ -862,12 +873,16 @@ class Context:
             fmt = FORMAT_RAY_PATHS  # (the same kernels and bytes under either value: the form's first name is kept on the wire)
         return self._query_into(records, fmt, RAY_PATH_DTYPE, "trace_paths_into", "RAY_PATH_DTYPE")
 
-    def closest_points(self, points, max_dist=math.inf) -> np.ndarray:
+    def closest_points(self, points, max_dist=math.inf, k=None) -> np.ndarray:
         """The nearest point of the uploaded mesh to every point of points[n, 3] — include/rvpt_hip.h: NEAREST POINTS has the definition, the arithmetic and the
         numbering of prim.  max_dist, a scalar or one value per point, is a DISTANCE: it is squared here in float32 (max_dist * max_dist, one rounding) into the
         record's max_d2, the bound the library compares squared distances against; +inf searches without a bound, a negative or NaN max_dist makes the record
         invalid.  Returns POINT_HIT_DTYPE[n]: closest, d2 (squared: np.sqrt(rec["d2"]) is the distance), prim, u, v, region; prim == NO_PRIM where no triangle is
-        within the bound."""
+        within the bound.  k (1 .. POINT_MAX_NEAREST) asks for the k nearest triangles of every point (K-NEAREST POINTS: the first k candidates by (d2, prim))
+        and returns POINT_HIT_DTYPE[n, k], record j of a row the j-th entry, prim == NO_PRIM from the first slot no triangle fills; the point and the bound are
+        repeated in every record's in fields."""
+        if k is not None:
+            FORMAT_NEAREST_POINTS_K(k)  # (before anything else: a refusal needs no arrays)
         pts = np.asarray(points, dtype=np.float32)
         if pts.ndim == 0 or pts.size % 3 or (pts.ndim > 1 and pts.shape[-1] != 3):
             raise NativeError(ERR_INVALID, f"closest_points: points[n, 3] are needed, got shape {tuple(pts.shape)}")
@@ -879,13 +894,30 @@ class Context:
         rec["point"] = pts
         with np.errstate(all="ignore"):
             rec["max_d2"] = np.where(dist < 0, np.float32(-1), dist * dist)  # (a negative distance must not square into a valid bound)
+        if k is not None:
+            return self.closest_points_into(np.ascontiguousarray(np.repeat(rec[:, None], int(k), axis=1)), k=k)
         return self.closest_points_into(rec)
 
-    def closest_points_into(self, records):
+    def closest_points_into(self, records, k=None):
         """rvpt_hip_read with FORMAT_NEAREST_POINTS in the caller's memory: `records` is a contiguous POINT_HIT_DTYPE array, or a contiguous float32 torch tensor
         [n, 12] (48-byte records; prim and region are the bits of their floats) on the host or on this context's device, as for trace_rays_into.  The in fields
-        (point, max_d2 — a SQUARED distance) stay as they are, the out fields are written.  Returns records."""
-        return self._query_into(records, FORMAT_NEAREST_POINTS, POINT_HIT_DTYPE, "closest_points_into", "POINT_HIT_DTYPE")
+        (point, max_d2 — a SQUARED distance) stay as they are, the out fields are written.  Returns records.  k (1 .. POINT_MAX_NEAREST): the call goes out with
+        FORMAT_NEAREST_POINTS_K(k) and `records` holds n groups of k records — a POINT_HIT_DTYPE array shaped (n * k,) or (n, k), or a tensor [n * k, 12];
+        record 0 of a group carries the point and the bound, the out fields of record j receive the j-th entry.  A record count that is no multiple of k raises
+        before any call."""
+        if k is None:
+            return self._query_into(records, FORMAT_NEAREST_POINTS, POINT_HIT_DTYPE, "closest_points_into", "POINT_HIT_DTYPE")
+        fmt = FORMAT_NEAREST_POINTS_K(k)
+        k = int(k)
+        if isinstance(records, np.ndarray):
+            if records.ndim > 2 or (records.ndim == 2 and records.shape[1] != k):
+                raise NativeError(ERR_INVALID, f"closest_points_into: k={k} needs POINT_HIT_DTYPE[n, {k}] or [n * {k}], got shape {tuple(records.shape)}")
+            count = records.size
+        else:
+            count = int(records.shape[0]) if hasattr(records, "data_ptr") and records.dim() == 2 else 0  # (_query_into refuses what is no tensor [n, 12])
+        if count % k:
+            raise NativeError(ERR_INVALID, f"closest_points_into: {count} records are not a multiple of k={k}: a point takes a group of {k} records")
+        return self._query_into(records, fmt, POINT_HIT_DTYPE, "closest_points_into", "POINT_HIT_DTYPE")
 
     def read_triangles(self) -> np.ndarray:
         """rvpt_hip_read with FORMAT_TRIANGLES: the stored triangle rows as the last update form left them — all 64 bytes of each, nothing recomputed — as

@@ -468,14 +468,17 @@ class RVPT:
             max_bounces = int(self.render_settings.max_bounces)
         return self._ctx.trace_paths(org, dir, seed, max_bounces, mode=mode)
 
-    def closest_points(self, points, max_dist=float("inf")) -> np.ndarray:
+    def closest_points(self, points, max_dist=float("inf"), k=None) -> np.ndarray:
         """Point queries against the scene as it is now (Context.closest_points; include/rvpt_hip.h: NEAREST POINTS): the nearest point of the mesh to every
         point of points[n, 3] within max_dist (a distance; the records carry it squared).  Returns native.POINT_HIT_DTYPE records: closest, d2 (the SQUARED
         distance), u, v, region, and prim numbering the triangles in the order they were ADDED (native.NO_PRIM: nothing within the bound), as trace_rays does.
-        Over a host-built tree a tie between equal distances is broken on the stored number, before this renumbering.  Needs initialize(), not update()."""
+        Over a host-built tree a tie between equal distances is broken on the stored number, before this renumbering.  Needs initialize(), not update().  k (1 .. native.POINT_MAX_NEAREST) returns records [n, k]: the
+        k nearest triangles of every point, nearest first (K-NEAREST POINTS), prim of every filled slot numbered the same way."""
+        if k is not None:
+            native.FORMAT_NEAREST_POINTS_K(k)
         if self._ctx is None:
             raise RuntimeError("closest_points before initialize()")
-        rec = self._ctx.closest_points(points, max_dist)
+        rec = self._ctx.closest_points(points, max_dist) if k is None else self._ctx.closest_points(points, max_dist, k=k)
         if not self._device_built and rec.shape[0]:  # a host-built tree: the device numbers the leaf order it was given
             hit = rec["prim"] != native.NO_PRIM
             rec["prim"][hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[rec["prim"][hit]]

@@ -806,7 +806,54 @@ def closest_points(tris, points, max_d2=np.inf, chunk: int = 1 << 20) -> np.ndar
     return rec
 
 
-SURFACE_POINT_DTYPE = np.dtype([("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("mat", "<u4"), ("normal", "<f4", (3,)),
+POINT_MAX_NEAREST = 8  # == RVPT_HIP_POINT_MAX_NEAREST
+
+
+def closest_points_k(tris, points, k: int, max_d2=np.inf, chunk: int = 1 << 20) -> np.ndarray:
+    """The normative statement of a K-NEAREST POINT QUERY (include/rvpt_hip.h: K-NEAREST POINTS), by brute force: closest_points' candidates (d2_i, i), every
+    one of them, from closest_point_triangles; the answer of a point is the first k, in ascending lexicographic order of (d2, i), of the candidates below
+    (max_d2, 0xFFFFFFFF) — a stable sort by d2 of the accepted candidates in index order, a NaN d2 excluded, d2 == max_d2 accepted.  Arguments as for
+    closest_points; k = 1 .. POINT_MAX_NEAREST.  Returns POINT_HIT_DTYPE[m, k]: column j holds the j-th entry; from the first slot no candidate fills, and in
+    every slot of a point that closest_points calls invalid, the miss (closest 0, d2 = the bits of the point's max_d2, prim NO_PRIM, u = v = 0, region 0).
+    The in fields are filled in column 0 only (a query ignores the followers'), so column 0 is closest_points' answer, byte for byte."""
+    k = int(k)
+    if not 1 <= k <= POINT_MAX_NEAREST:
+        raise ValueError(f"k must be 1 .. {POINT_MAX_NEAREST}, got {k}")
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    pts = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    m = pts.shape[0]
+    rec = np.zeros((m, k), dtype=POINT_HIT_DTYPE)
+    rec["point"][:, 0] = pts
+    rec["max_d2"][:, 0] = np.asarray(max_d2, dtype=np.float32)
+    bound = rec["max_d2"][:, 0].copy()
+    rec["d2"], rec["prim"] = bound[:, None], NO_PRIM
+    with np.errstate(all="ignore"):
+        valid = np.isfinite(pts).all(axis=1) & (bound >= 0)
+    rows = np.flatnonzero(valid)
+    n = t.shape[0]
+    if n == 0 or rows.size == 0:
+        return rec
+    step = max(1, chunk // n)
+    take = min(k, n)
+    for lo in range(0, rows.size, step):
+        sel = rows[lo:lo + step]
+        q, d2, u, v, region = closest_point_triangles(pts[sel], t)
+        with np.errstate(all="ignore"):
+            ok = d2 <= bound[sel, None]  # (false for a NaN d2)
+        # a stable sort of the keys with the refused ones last: a key of +inf may be an accepted candidate (max_d2 = +inf), so the refused sort on a flag first
+        order = np.lexsort((d2, ~ok), axis=1)[:, :take]  # (lexsort is stable: equal (flag, d2) keep index order)
+        r = np.arange(sel.size)[:, None]
+        filled = ok[r, order]
+        out = rec[sel]
+        for name, src in (("closest", q), ("d2", d2), ("u", u), ("v", v), ("region", region)):
+            dst = out[name][:, :take]
+            dst[filled] = src[r, order][filled]
+        out["prim"][:, :take][filled] = order[filled].astype(np.uint32)
+        rec[sel] = out
+    return rec
+
+
+SURFACE_POINT_DTYPE =np.dtype([("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("mat", "<u4"), ("normal", "<f4", (3,)),
                                 ("reserved", "<u4")])  # rvpt_surface_point (== native.SURFACE_POINT_DTYPE)
 _LIBM_FMAF = None
 

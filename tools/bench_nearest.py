@@ -11,7 +11,12 @@ usage: tools/bench_nearest.py rates [default cornell terrain]   on the GPU box: 
        tools/bench_nearest.py queries [scene] [near|far]        a few device-record queries and nothing else: the run to put under rocprofv3
        tools/bench_nearest.py resources <parent tree>           where hipcc and a checkout of the parent commit are: VGPR, SGPR, scratch and static LDS of every
                                                                 kernel of every .hip file there and here (tools/kernel_resources.py), and of the new kernels
-Each mode rewrites its own section of profiles/nearest_points.txt and leaves the other."""
+       tools/bench_nearest.py --k <label> [scenes]              k-nearest point queries (FORMAT_NEAREST_POINTS_K(k)): Gpoints/s of 2^20 near points from device
+                                                                records at k = 1, 2, 4, 8 on the three scenes, beside format 4's own rate in three passes.  <label>
+                                                                names the block ("this tree", "parent"); with RVPT_HIP_LIB naming a library that has no such format
+                                                                (the parent commit's) the block holds format 4 alone.  Blocks are appended to
+                                                                profiles/nearest_points_k.txt.
+Each other mode rewrites its own section of profiles/nearest_points.txt and leaves the other."""
 import statistics
 import sys
 import time
@@ -141,6 +146,58 @@ def rates(names):
     write_section("\n".join(lines), resources=False)
 
 
+def rate_g(fn, n, reps=7, warm=2):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    r = [n / t / 1e9 for t in ts]
+    return statistics.median(r), min(r), max(r)
+
+
+def k_leg(label, names):
+    """Gpoints/s (points, that is groups, per second of wall clock around the call) at k = 1, 2, 4, 8, near points, device records"""
+    import os
+    import torch
+    from rvpt_amd import native
+    out = ROOT / "profiles" / "nearest_points_k.txt"
+    lines = [f"== {label}: tools/bench_nearest.py --k, library {Path(os.environ['RVPT_HIP_LIB']).name if os.environ.get('RVPT_HIP_LIB') else 'in-tree'} ==",
+             f"{N} points per call (near: a jittered grid through the scene's box), max_d2 = +inf, device records; Gpoints/s, median (min .. max) of 7 calls"]
+    done = 0
+    for name, tris, mats in scenes(names):
+        ctx = native.Context(64, 36, 0, 0, 1, native.TRAVERSAL_BVH)
+        how = upload(ctx, name, tris, mats, native)
+        rec = records_of(points(tris, "near"))
+        dev = torch.from_numpy(rec.view(np.float32).reshape(-1, 12)).to("cuda:0")
+        lines.append(f"{name}: {tris.shape[0]} triangles, {how}")
+        passes = [rate_g(lambda: ctx.closest_points_into(dev), N) for _ in range(3)]  # format 4's own rate, three passes: the figure compared across libraries
+        lines.append("  format 4      " + "   ".join(f"{m:7.4f} ({lo:7.4f} .. {hi:7.4f})" for m, lo, hi in passes))
+        plain = dev.cpu().numpy().view(native.POINT_HIT_DTYPE).reshape(-1)
+        for k in (1, 2, 4, 8):
+            groups = np.zeros((N, k), dtype=native.POINT_HIT_DTYPE)
+            groups[:, 0] = rec
+            gdev = torch.from_numpy(groups.view(np.float32).reshape(-1, 12)).to("cuda:0")
+            try:
+                m, lo, hi = rate_g(lambda: ctx.closest_points_into(gdev, k=k), N)
+            except native.NativeError as e:
+                lines.append(f"  k = {k}         this library has no such format ({e})")
+                break
+            got = gdev.cpu().numpy().view(native.POINT_HIT_DTYPE).reshape(N, k)
+            assert np.ascontiguousarray(got[:, 0]).tobytes() == plain.tobytes(), "slot 0 is not format 4's answer"
+            assert (got["d2"][:, 1:] >= got["d2"][:, :-1]).all()
+            lines.append(f"  k = {k}         {m:7.4f} ({lo:7.4f} .. {hi:7.4f})")
+            del gdev
+        ctx.close()
+        print("\n".join(lines[done:]), flush=True)
+        done = len(lines)
+    lines.append("")
+    with open(out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def queries(names, kind):
     import torch
     from rvpt_amd import native
@@ -197,6 +254,9 @@ def resources(parent):
 
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "rates"
+    if mode == "--k":
+        k_leg(sys.argv[2] if len(sys.argv) > 2 else "this tree", sys.argv[3:] or ["default", "cornell", "terrain"])
+        sys.exit(0)
     if mode == "resources":
         sys.exit(0 if resources(sys.argv[2]) else 1)
     args = sys.argv[2:]

@@ -89,7 +89,9 @@ extern "C" {
                                      past a limit a rebuild by the builder that made the tree, through which the rest pose follows its triangles and the
                                      binding stays.  Still 8, no new symbol: rvpt_hip_read with a format RVPT_HIP_FORMAT_NEAREST_POINTS_K(k) (49 .. 56) —
                                      until then the "unknown format" error — is a K-NEAREST POINT QUERY: `dst` holds groups of k rvpt_point_hit records,
-                                     the point in the first, the k nearest triangles of the mesh out */
+                                     the point in the first, the k nearest triangles of the mesh out.  Still 8, no new symbol: rvpt_hip_read with the
+                                     format RVPT_HIP_FORMAT_RAY_CROSSINGS (8) — until then the "unknown format" error — is a CROSSING QUERY: `dst` holds
+                                     rvpt_ray_crossings records, rays in, the counts of front and back hits along them and the first and last t out */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -188,6 +190,15 @@ typedef struct rvpt_ray_hit {
     float dir[3]; uint32_t flags;    /* in: 0 or RVPT_HIP_RAY_ANY_HIT; other bits reserved, ignored */
     float t; uint32_t prim; float u; float v;   /* out */
 } rvpt_ray_hit;
+
+#define RVPT_HIP_FORMAT_RAY_CROSSINGS 8  /* dst: rvpt_ray_crossings[dst_bytes / 48], in and out (RAY CROSSINGS at rvpt_hip_read) */
+
+/* One ray of a crossing query and its answer (48 B = three float4; the first two quads are an rvpt_ray_hit's). */
+typedef struct rvpt_ray_crossings {
+    float org[3]; float tmax;        /* in: as rvpt_ray_hit */
+    float dir[3]; uint32_t flags;    /* in: reserved, ignored — RVPT_HIP_RAY_ANY_HIT included */
+    uint32_t front; uint32_t back; float t_near; float t_far;   /* out */
+} rvpt_ray_crossings;
 
 #define RVPT_HIP_FORMAT_RAY_PATHS 3   /* dst: rvpt_ray_path[dst_bytes / 48], in and out (PATH QUERIES at rvpt_hip_read) */
 #define RVPT_HIP_PATH_MAX_BOUNCES 1024u /* per path: the largest bounce budget a record may ask for */
@@ -677,6 +688,38 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  *   call; `dst` is host memory or 16-byte aligned device memory of the context's GPU, another GPU's memory is an error naming both devices, and in every error
  *   case `dst` is untouched; the call is LOCAL under a communicator, implies rvpt_hip_wait, and leaves untouched what a ray query leaves untouched.
  * DESIGN.md 5.23 has the kernels and what was measured (profiles/ray_queries.txt).
+ *
+ * RAY CROSSINGS — how many surfaces the caller's own rays pass, by facing, and over what stretch, in place:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_RAY_CROSSINGS, records, n * sizeof(rvpt_ray_crossings));
+ *
+ * `dst` then holds n rvpt_ray_crossings records: each comes in as a ray (org, tmax, dir; flags is reserved and ignored, RVPT_HIP_RAY_ANY_HIT included) and goes
+ * out as (front, back, t_near, t_far).  The in fields are never written.
+ * - A VALID RAY is a ray query's: a non-finite component of org or dir, or a tmax that is NaN, zero or negative, is decided before any walk, and such a ray
+ *   is answered as a ray with no crossing.
+ * - THE SET A is every triangle test accepted by the walk of an any-hit k-nearest ray query with no limit on k.  The order is THE ORDER A QUERY WALKS above.
+ *   `bound` stays tmax from start to end: every box test and every triangle test uses the interval (0, tmax), and a triangle is accepted iff 0 < t < tmax,
+ *   0 < u, 0 < v and u + v < 1.  On brute-force contexts every stored triangle is tested; on BVH contexts the tested triangles are those under the leaves the
+ *   reference's walk reaches with that fixed interval.
+ * - A DOES NOT DEPEND ON THE VISITING ORDER, because the interval never changes: the answer is the same under RVPT_HIP_TRAVERSAL_BVH,
+ *   RVPT_HIP_TRAVERSAL_BVH_ORDERED and RVPT_HIP_BVH_PER_LANE.  Stacked duplicates count once each.  Each stored triangle is taken to lie under one leaf; a
+ *   caller's tree that lists a triangle under two leaves counts it twice.
+ * - FACING.  n is the stored unit normal of the accepted triangle, the 12 bytes SURFACE POINTS returns.  s = (dir.x*n.x + dir.y*n.y) + dir.z*n.z in binary32,
+ *   every operation rounded on its own, no FMA.  The hit is FRONT iff s < 0; every other hit is BACK (s > 0, s == 0, s NaN), hence front + back == |A|.  For a
+ *   closed mesh with outward normals, back - front is 1 from inside and 0 from outside along any ray that meets no edge exactly.
+ * - WHAT A RECORD HOLDS ON RETURN.  front and back are the two counts; t_near and t_far are the smallest and the largest accepted t (accepted t are finite, so
+ *   min and max are order-free).  If A is empty: front = back = 0, t_near = the bits of tmax as given (a NaN's payload included), t_far = +0.0.
+ * - WHAT IS NOT PROMISED.  On brute-force contexts t_near equals format 2's t.  On BVH contexts the closest-hit walk tests boxes against a shrinking interval,
+ *   and equality is not promised there; nor is it promised that a BVH context's A equals the brute-force context's A over the same triangles: a box test
+ *   may turn away a ray that its triangle's test would accept.
+ * - COST.  A crossing ray tests every triangle whose leaf its line enters inside (0, tmax): at most n_tris per ray, which a brute-force ray query already
+ *   costs.  A finite tmax is the caller's bound.
+ * - Everything else is a ray query's rule: the call needs a scene and no rvpt_hip_set_frame, the empty scene answers with no crossing; dst_bytes must be a
+ *   multiple of 48, else RVPT_HIP_ERR_INVALID; dst_bytes == 0 is a successful no-op; fewer than 2^32 records per call; `dst` is host memory or 16-byte aligned
+ *   device memory of the context's GPU, another GPU's memory is an error naming both devices, and in every error case `dst` is untouched; for host records
+ *   only the out quad travels back; the call is LOCAL under a communicator, implies rvpt_hip_wait, leaves untouched what a ray query leaves untouched, and
+ *   answers on the scene as the last update form left it.
+ * DESIGN.md 5.27 has the kernels and what was measured (profiles/ray_crossings.txt).
  *
  * PATH QUERIES — radiance along the caller's own rays, in place:
  *

@@ -1463,12 +1463,14 @@ int rvpt_hip_gather(rvpt_hip_ctx *ctx, void *dst_dev_rgba32f)
 // k records, one ray each, and the plan and the launch count groups; everything else, the staging and the copy back of every record's out quad included, is
 // per record as before.  (RecordKind::Points: 0 for RVPT_HIP_FORMAT_NEAREST_POINTS and RVPT_HIP_FORMAT_NEAREST_POINTS_K(1), the same call; k for
 // RVPT_HIP_FORMAT_NEAREST_POINTS_K(k), k > 1 (K-NEAREST POINTS) — groups of k records, one point each, likewise.)
-enum class RecordKind { Rays, Paths, Points, Surface };
+// RecordKind::Crossings (RVPT_HIP_FORMAT_RAY_CROSSINGS, RAY CROSSINGS): a ray query in everything but the kernels and the record's name.
+enum class RecordKind { Rays, Paths, Points, Surface, Crossings };
 static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const RecordKind kind, const uint32_t path_mode = rv::kPathModeKajiya, const uint32_t hits = 0)
 {
-    const bool paths = kind == RecordKind::Paths, points = kind == RecordKind::Points, surface = kind == RecordKind::Surface;
-    const char *what = surface ? "surface" : (points ? "point" : (paths ? "path" : "ray"));
-    const char *record = surface ? "rvpt_surface_point" : (points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : "rvpt_ray_hit"));
+    const bool paths = kind == RecordKind::Paths, points = kind == RecordKind::Points, surface = kind == RecordKind::Surface, crossings = kind == RecordKind::Crossings;
+    const char *what = surface ? "surface" : (points ? "point" : (paths ? "path" : (crossings ? "crossing" : "ray")));
+    const char *record = surface ? "rvpt_surface_point" : (points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : (crossings ? "rvpt_ray_crossings" : "rvpt_ray_hit")));
+    static_assert(sizeof(rvpt_ray_crossings) == sizeof(rvpt_ray_hit) && offsetof(rvpt_ray_crossings, front) == offsetof(rvpt_ray_hit, t), "a crossing record is laid out as a ray record");
     const size_t out_offset = surface ? offsetof(rvpt_surface_point, point) : (points ? offsetof(rvpt_point_hit, closest) : offsetof(rvpt_ray_hit, t));  // where a record's out fields begin
     if (hits && points && dst_bytes % (sizeof(rvpt_point_hit) * hits))
         return fail(ctx, RVPT_HIP_ERR_INVALID, "point query with k = %u: dst_bytes %zu is not a multiple of the %zu bytes of a group of k rvpt_point_hit", hits, dst_bytes,
@@ -1495,6 +1497,7 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
     scene.kind = !bvh ? rv::QueryKind::Brute : (ctx->n_wide > 0 && ctx->bvh_head_shift != 0 ? rv::QueryKind::Wide : rv::QueryKind::Binary);
     scene.prep = ctx->d_prep, scene.nodes = ctx->d_nodes, scene.wide = ctx->d_wide;
     scene.perm = ctx->have_perm ? ctx->d_perm : nullptr;
+    scene.unit_n = ctx->d_unit_n;
     scene.n_tris = static_cast<uint32_t>(ctx->n_tris), scene.n_wide = static_cast<uint32_t>(ctx->n_wide), scene.head_shift = ctx->bvh_head_shift;
     scene.stack_levels = scene.kind == rv::QueryKind::Wide ? ctx->wide_stack_levels : bvh_stack_levels(ctx);
     path_scene.mat_index = ctx->d_mat_index, path_scene.unit_n = ctx->d_unit_n, path_scene.mats = ctx->d_mats;
@@ -1508,6 +1511,8 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
         HIP_TRY(ctx, rv::nearest_plan(nearest, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
     else if (paths)
         HIP_TRY(ctx, rv::path_plan(path_scene, static_cast<uint32_t>(n), ctx->num_cus, path_mode, &plan));
+    else if (crossings)
+        HIP_TRY(ctx, rv::cross_plan(scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
     else if (!surface)  // (a surface read is one record per lane and no walk: no plan, no stack)
         HIP_TRY(ctx, rv::query_plan(scene, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
     if (int rc = rvpt_hip_wait(ctx)) return rc;  // every read implies it; frames in flight still read the scene, and the buffers below may be regrown
@@ -1537,6 +1542,8 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
         HIP_TRY(ctx, rv::nearest_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
     else if (paths)
         HIP_TRY(ctx, rv::path_launch(ctx->stream, path_scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n), path_mode));
+    else if (crossings)
+        HIP_TRY(ctx, rv::cross_launch(ctx->stream, scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
     else
         HIP_TRY(ctx, rv::query_launch(ctx->stream, scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
     if (!device_dst)  // only the out fields travel back: the in fields of a host record are never written either
@@ -1589,6 +1596,7 @@ int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
         return query_records(ctx, dst, dst_bytes, RecordKind::Points, rv::kPathModeKajiya, static_cast<uint32_t>(format) - RVPT_HIP_FORMAT_NEAREST_POINTS_K(0u));
     if (format == RVPT_HIP_FORMAT_TRIANGLES) return read_triangles(ctx, dst, dst_bytes);  // local as well
     if (format == RVPT_HIP_FORMAT_SURFACE_POINTS) return query_records(ctx, dst, dst_bytes, RecordKind::Surface);
+    if (format == RVPT_HIP_FORMAT_RAY_CROSSINGS) return query_records(ctx, dst, dst_bytes, RecordKind::Crossings);  // local as well
     if (format == RVPT_HIP_FORMAT_RAY_HITS || format == RVPT_HIP_FORMAT_RAY_PATHS || format == RVPT_HIP_FORMAT_NEAREST_POINTS)  // local even with a communicator: every rank holds the whole scene
         return query_records(ctx, dst, dst_bytes,
                              format == RVPT_HIP_FORMAT_NEAREST_POINTS ? RecordKind::Points : (format == RVPT_HIP_FORMAT_RAY_PATHS ? RecordKind::Paths : RecordKind::Rays));

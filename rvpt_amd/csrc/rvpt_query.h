@@ -27,6 +27,7 @@ struct QueryScene {
     const float4 *nodes;   // binary nodes, 2 float4 each (Wide: the root's box; Binary: the tree)
     const float4 *wide;    // Wide: 8 float4 per node
     const uint32_t *perm;  // non-null: prim = perm[stored index] (the caller's numbering after a build form)
+    const float4 *unit_n;  // n_tris: (normalize(n), 0) by stored index — read by crossing queries alone
     uint32_t n_tris, n_wide, head_shift;
     uint32_t stack_levels;  // slots a walk can hold at once (Wide: wide_stack_levels; Binary: the tree's height)
 };
@@ -46,5 +47,10 @@ hipError_t query_plan(const QueryScene &scene, uint32_t n, int num_cus, QueryPla
 // Answers records[0 .. n) in place on `stream` — with k > 1 the n groups records[0 .. n * k), the plan made with the same k.  `scratch` holds 64 words (the
 // first is the claim counter, zeroed here) followed by plan.stack_words words.
 hipError_t query_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n, uint32_t k = 1);
+
+// RAY CROSSINGS (RVPT_HIP_FORMAT_RAY_CROSSINGS): one rvpt_ray_crossings per ray, the same three kinds of walk with the interval fixed at tmax; the plan and
+// the scratch are a ray query's.  scene.unit_n must be set.
+hipError_t cross_plan(const QueryScene &scene, uint32_t n, int num_cus, QueryPlan *plan);
+hipError_t cross_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n);
 
 }  // namespace rv

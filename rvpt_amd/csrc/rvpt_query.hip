@@ -619,23 +619,278 @@ NearKernel near_kernel(const QueryKind kind, const uint32_t k)
 
 }  // namespace
 
-hipError_t query_plan(const QueryScene &scene, const uint32_t n, const int num_cus, QueryPlan *plan, const uint32_t k)
+// RAY CROSSINGS (include/rvpt_hip.h: RVPT_HIP_FORMAT_RAY_CROSSINGS): the three walks once more, reduced instead of listed.  The interval is (0, tmax) from
+// start to end, so the set of accepted tests is that of an any-hit k-nearest walk with no limit on k and does not depend on the visiting order; a lane keeps
+// two counts and the smallest and largest accepted t, and never leaves its walk early.
+namespace {
+
+struct CrossArgs {
+    QueryArgs q;
+    const float4 *unit_n;  // n_tris: (normalize(n), 0) by stored index, as SURFACE POINTS returns it
+};
+
+struct Crossings {
+    uint32_t front, back;
+    float t_near, t_far;  // +inf and +0 while nothing is accepted: an accepted t is in (0, tmax), finite and positive
+};
+
+// An accepted test counts by its facing: s = (d.x n.x + d.y n.y) + d.z n.z, every operation rounded on its own; FRONT iff s < 0, everything else (s NaN
+// included) BACK.  The normal is gathered only by the lanes that accept, and only when some lane does.
+__device__ __forceinline__ void accept_cross(const bool accept, const float tt, const uint32_t index, const f3 d, const float4 *unit_n, Crossings &c)
+{
+    if (ballot(accept) != 0) {
+        asm volatile("" ::: "memory");  // keep this a (wave-uniform) branch, as accept_hit does
+        if (accept) {
+            const float4 un = unit_n[index];
+            const float s = __fadd_rn(__fadd_rn(__fmul_rn(d.x, un.x), __fmul_rn(d.y, un.y)), __fmul_rn(d.z, un.z));
+            const bool front = s < 0.0f;
+            c.front += front ? 1u : 0u;
+            c.back += front ? 0u : 1u;
+            c.t_near = __builtin_fminf(c.t_near, tt);
+            c.t_far = __builtin_fmaxf(c.t_far, tt);
+        }
+    }
+}
+
+// test_leaf against the fixed interval: every triangle of the leaf, no early return
+__device__ __forceinline__ void test_leaf_cross(const v4f *prep, const uint32_t first, const uint32_t count, const QueryRay &q, const float4 *unit_n, Crossings &c)
+{
+    const float tmax = __uint_as_float(q.tmax_bits);
+    for (uint32_t i = first; i < first + count; ++i) {
+        const v4f *tp = prep + 4 * static_cast<size_t>(i);
+        const PrepTri t = unpack(tp[0], tp[1], tp[2], tp[3]);
+        const float tt = div_dots(dot(t.v0 - q.o, t.n), dot(q.d, t.n));
+        const f3 p0 = fma3(q.d, tt, q.o) - t.v0;
+        const float b0 = dot(p0, t.e0);
+        const float b1 = dot(p0, t.e1);
+        const float u = t.inv_det * fma_(t.a01, b1, t.a00 * b0);
+        const float v = t.inv_det * fma_(t.a11, b1, t.a01 * b0);
+        accept_cross((0.0f < tt) & (tt < tmax) & (0.0f < u) & (0.0f < v) & (u + v < 1.0f), tt, i, q.d, unit_n, c);
+    }
+}
+
+// query_run against the fixed interval (`active`: the ray is valid)
+__device__ __forceinline__ void cross_run(const v4f *src, const uint32_t index0, const uint32_t count, const QueryRay &q, const float4 *unit_n, const bool active,
+                                          Crossings &c)
+{
+    const float tmax = __uint_as_float(q.tmax_bits);
+    auto accept = [&](const OpenTest r, const uint32_t index) {
+        accept_cross((r.m > 0.0f) & (r.s < 1.0f) & (r.tt < tmax) & active, r.tt, index, q.d, unit_n, c);
+    };
+    uint32_t i = 0;
+    for (; i + 4 <= count; i += 4) {
+        OpenTest r[4];
+#pragma unroll
+        for (uint32_t s = 0; s < 4; ++s) {
+            const uint32_t j = i + s;
+            r[s] = test_triangle_open(unpack(src[4 * j + 0], src[4 * j + 1], src[4 * j + 2], src[4 * j + 3]), q.o, q.d);
+        }
+        asm volatile("" ::"v"(r[0].tt), "v"(r[0].m), "v"(r[0].s), "v"(r[1].tt), "v"(r[1].m), "v"(r[1].s), "v"(r[2].tt), "v"(r[2].m), "v"(r[2].s), "v"(r[3].tt),
+                     "v"(r[3].m), "v"(r[3].s));
+#pragma unroll
+        for (uint32_t s = 0; s < 4; ++s) accept(r[s], index0 + i + s);
+    }
+    for (; i < count; ++i) accept(test_triangle_open(unpack(src[4 * i + 0], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]), q.o, q.d), index0 + i);
+}
+
+// A record's out quad: the counts, t_near and t_far; with nothing accepted (0, 0, the bits of tmax as given, +0)
+__device__ __forceinline__ void store_crossings(float4 *records, const size_t r, const QueryRay &q, const Crossings &c)
+{
+    const bool none = (c.front | c.back) == 0u;
+    records[3 * r + 2] = make_float4(__uint_as_float(c.front), __uint_as_float(c.back), none ? __uint_as_float(q.tmax_bits) : c.t_near, c.t_far);
+}
+
+}  // namespace
+
+// query_bvh4 with the interval fixed at tmax: the stacked entry distances are still compared against it at the pop
+__global__ __launch_bounds__(kBlock) void cross_bvh4(const CrossArgs ca)
+{
+    const QueryArgs &a = ca.q;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const uint32_t lds_levels = a.lds_levels;
+    float4 *lds_root = reinterpret_cast<float4 *>(lds_stack + 2u * lds_levels * kBlock);
+    float4 *lds_top = lds_root + 2;
+    const uint32_t top_nodes = a.top_nodes;
+    if (threadIdx.x < 2u) lds_root[threadIdx.x] = a.nodes[threadIdx.x];
+    for (uint32_t i = threadIdx.x; i < 8u * top_nodes; i += kBlock) lds_top[i] = a.wide[i];
+    __syncthreads();
+    const v4f *prep = reinterpret_cast<const v4f *>(a.prep);
+    const uint32_t top_level = a.stack_levels - 1u;
+    const uint32_t head_shift = a.head_shift;
+    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
+    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
+    const uint32_t lane = lane_id();
+
+    for (;;) {
+        const uint32_t run = claim_run(a.counter, lane);
+        if (run >= a.n_runs) break;
+        const size_t r = static_cast<size_t>(run) * 64u + lane;
+        const bool live = r < a.n;
+        const QueryRay q = load_ray(a.records, r, live);
+        const float tmax = __uint_as_float(q.tmax_bits);
+        Crossings c{0u, 0u, kInf, 0.0f};
+        uint32_t sp = 0, cur = 0, leaf_first = 0, leaf_count = 0;
+        const f3 inv = mk(1.0f / q.d.x, 1.0f / q.d.y, 1.0f / q.d.z);
+        bool walking = q.valid;
+        {
+            float entry;
+            walking = walking && slab_entry(q.o, inv, lds_root[0], lds_root[1], tmax, entry);
+        }
+        auto enter = [&](const uint32_t head) {
+            const uint32_t first = head & ((1u << head_shift) - 1u), count = head >> head_shift;
+            cur = first;
+            leaf_first = first;
+            leaf_count = count;
+        };
+        auto push = [&](const float entry, const uint32_t head) {
+            const uint32_t at = min(sp, top_level);  // (the clamp keeps a wrong size inside the memory, as in query_bvh4)
+            if (at < lds_levels) {
+                lds_stack[(2u * at + 0u) * kBlock + threadIdx.x] = __float_as_uint(entry);
+                lds_stack[(2u * at + 1u) * kBlock + threadIdx.x] = head;
+            } else {
+                ovf[(2u * (at - lds_levels) + 0u) * ovf_stride] = __float_as_uint(entry);
+                ovf[(2u * (at - lds_levels) + 1u) * ovf_stride] = head;
+            }
+            sp = at + 1u;
+        };
+        while (ballot(walking) != 0) {
+            bool need_pop = false;
+            if (walking && leaf_count == 0) {
+                const float4 *node = cur < top_nodes ? lds_top + 8u * cur : a.wide + 8u * static_cast<size_t>(cur);
+                const float4 minx = node[0], maxx = node[1], miny = node[2], maxy = node[3], minz = node[4], maxz = node[5], hq = node[6];
+                const uint32_t hd0 = __float_as_uint(hq.x), hd1 = __float_as_uint(hq.y), hd2 = __float_as_uint(hq.z), hd3 = __float_as_uint(hq.w);
+                float e0, e1, e2, e3;
+                const bool h0 = slab_child(q.o, inv, minx.x, maxx.x, miny.x, maxy.x, minz.x, maxz.x, tmax, e0);
+                const bool h1 = slab_child(q.o, inv, minx.y, maxx.y, miny.y, maxy.y, minz.y, maxz.y, tmax, e1);
+                const bool h2 = slab_child(q.o, inv, minx.z, maxx.z, miny.z, maxy.z, minz.z, maxz.z, tmax, e2) && hd2 != kWideEmpty;
+                const bool h3 = slab_child(q.o, inv, minx.w, maxx.w, miny.w, maxy.w, minz.w, maxz.w, tmax, e3) && hd3 != kWideEmpty;
+                if (h3 && (h0 || h1 || h2)) push(e3, hd3);
+                if (h2 && (h0 || h1)) push(e2, hd2);
+                if (h1 && h0) push(e1, hd1);
+                if (h0 || h1 || h2 || h3)
+                    enter(h0 ? hd0 : (h1 ? hd1 : (h2 ? hd2 : hd3)));
+                else
+                    need_pop = true;
+            }
+            if (walking && leaf_count > 0) {
+                test_leaf_cross(prep, leaf_first, leaf_count, q, ca.unit_n, c);
+                leaf_count = 0;
+                need_pop = true;
+            }
+            if (walking && need_pop) {
+                bool found = false;
+                while (sp > 0 && !found) {
+                    sp -= 1;
+                    uint32_t entry_bits, cand;
+                    if (sp < lds_levels) {
+                        entry_bits = lds_stack[(2u * sp + 0u) * kBlock + threadIdx.x];
+                        cand = lds_stack[(2u * sp + 1u) * kBlock + threadIdx.x];
+                    } else {
+                        entry_bits = ovf[(2u * (sp - lds_levels) + 0u) * ovf_stride];
+                        cand = ovf[(2u * (sp - lds_levels) + 1u) * ovf_stride];
+                    }
+                    if (tmax >= __uint_as_float(entry_bits)) {  // the box test at the visit: the interval is the one the child was stacked under
+                        enter(cand);
+                        found = true;
+                    }
+                }
+                walking = found;
+            }
+        }
+        if (live) store_crossings(a.records, r, q, c);
+    }
+}
+
+// query_bvh2 with the interval fixed at tmax
+__global__ __launch_bounds__(kBlock) void cross_bvh2(const CrossArgs ca)
+{
+    const QueryArgs &a = ca.q;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const uint32_t lds_levels = a.lds_levels;
+    const v4f *prep = reinterpret_cast<const v4f *>(a.prep);
+    const uint32_t top_level = a.stack_levels - 1u;
+    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
+    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
+    const uint32_t lane = lane_id();
+
+    for (;;) {
+        const uint32_t run = claim_run(a.counter, lane);
+        if (run >= a.n_runs) break;
+        const size_t r = static_cast<size_t>(run) * 64u + lane;
+        const bool live = r < a.n;
+        const QueryRay q = load_ray(a.records, r, live);
+        const float tmax = __uint_as_float(q.tmax_bits);
+        Crossings c{0u, 0u, kInf, 0.0f};
+        uint32_t sp = 0, cur = 0;
+        const f3 inv = mk(1.0f / q.d.x, 1.0f / q.d.y, 1.0f / q.d.z);
+        bool walking = q.valid;
+        while (ballot(walking) != 0) {
+            if (walking) {
+                const float4 n0 = a.nodes[2u * static_cast<size_t>(cur)], n1 = a.nodes[2u * static_cast<size_t>(cur) + 1u];
+                const uint32_t first = __float_as_uint(n0.x), count = __float_as_uint(n0.y);
+                bool pop = true;
+                float entry;
+                if (slab_entry(q.o, inv, n0, n1, tmax, entry)) {
+                    if (count > 0) {
+                        test_leaf_cross(prep, first, count, q, ca.unit_n, c);
+                    } else {
+                        const uint32_t at = min(sp, top_level);  // (the clamp as in query_bvh4)
+                        if (at < lds_levels)
+                            lds_stack[at * kBlock + threadIdx.x] = first + 1u;
+                        else
+                            ovf[(at - lds_levels) * ovf_stride] = first + 1u;
+                        sp = at + 1u;
+                        cur = first;
+                        pop = false;
+                    }
+                }
+                if (pop) {
+                    if (sp == 0) {
+                        walking = false;
+                    } else {
+                        sp -= 1;
+                        cur = sp < lds_levels ? lds_stack[sp * kBlock + threadIdx.x] : ovf[(sp - lds_levels) * ovf_stride];
+                    }
+                }
+            }
+        }
+        if (live) store_crossings(a.records, r, q, c);
+    }
+}
+
+// query_brute with the interval fixed at tmax: a work-group runs over every tile unless none of its rays is valid
+__global__ __launch_bounds__(kBlock) void cross_brute(const CrossArgs ca)
+{
+    const QueryArgs &a = ca.q;
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tile[];
+    const size_t r = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const bool live = r < a.n;
+    const QueryRay q = load_ray(a.records, r, live);
+    Crossings c{0u, 0u, kInf, 0.0f};
+    const bool active = q.valid;
+    if (__syncthreads_or(active ? 1 : 0) != 0) {
+        for (uint32_t base = 0; base < a.n_tris; base += kQueryTileTris) {
+            const uint32_t count = min(kQueryTileTris, a.n_tris - base);
+            if (base != 0) __syncthreads();  // the last tile has been read by every wave
+            for (uint32_t i = threadIdx.x; i < 4u * count; i += kBlock) lds_tile[i] = a.prep[4u * static_cast<size_t>(base) + i];
+            __syncthreads();
+            if (ballot(active) != 0) cross_run(reinterpret_cast<const v4f *>(lds_tile), base, count, q, ca.unit_n, active, c);
+        }
+    }
+    if (live) store_crossings(a.records, r, q, c);
+}
+
+namespace {
+
+// The persistent grid and the split of the stack for a tree walk by `kernel` (whose occupancy sizes the grid)
+hipError_t plan_walk(const QueryScene &scene, const uint32_t n, const int num_cus, const void *kernel, QueryPlan *plan)
 {
     QueryPlan p{};
-    if (scene.kind == QueryKind::Brute) {
-        p.grid = std::max<uint32_t>(1u, static_cast<uint32_t>((static_cast<uint64_t>(n) + kBlock - 1u) / kBlock));
-        p.lds_bytes = static_cast<size_t>(kQueryTileTris) * 64u;
-        *plan = p;
-        return hipSuccess;
-    }
     const uint32_t levels = std::max<uint32_t>(1u, scene.stack_levels);
     p.lds_levels = std::min(levels, kQueryLdsLevels);
     p.top_nodes = scene.kind == QueryKind::Wide ? std::min(scene.n_wide, kQueryTopNodes) : 0u;
     p.lds_bytes = static_cast<size_t>(p.lds_levels) * kBlock * 2u * sizeof(uint32_t) + 2u * sizeof(float4) + static_cast<size_t>(p.top_nodes) * 128u;
     int per_cu = 0;
-    // (the occupancy of the instance that is launched: a k-nearest instance holds its list in registers and may fit fewer waves)
-    const void *kernel = k > 1u ? reinterpret_cast<const void *>(near_kernel(scene.kind, k))
-                                : (scene.kind == QueryKind::Wide ? reinterpret_cast<const void *>(query_bvh4) : reinterpret_cast<const void *>(query_bvh2));
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, p.lds_bytes);
     if (e != hipSuccess) return e;
     const uint64_t runs = (static_cast<uint64_t>(n) + 63u) / 64u;
@@ -648,10 +903,16 @@ hipError_t query_plan(const QueryScene &scene, const uint32_t n, const int num_c
     return hipSuccess;
 }
 
-hipError_t query_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, const uint32_t n, const uint32_t k)
+QueryPlan plan_brute(const uint32_t n)
 {
-    if (n == 0) return hipSuccess;
-    if (k == 0 || k > kQueryMaxHits) return hipErrorInvalidValue;
+    QueryPlan p{};
+    p.grid = std::max<uint32_t>(1u, static_cast<uint32_t>((static_cast<uint64_t>(n) + kBlock - 1u) / kBlock));
+    p.lds_bytes = static_cast<size_t>(kQueryTileTris) * 64u;
+    return p;
+}
+
+QueryArgs query_args(const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, const uint32_t n)
+{
     QueryArgs a{};
     a.prep = scene.prep, a.nodes = scene.nodes, a.wide = scene.wide, a.perm = scene.perm;
     a.records = static_cast<float4 *>(records);
@@ -662,6 +923,55 @@ hipError_t query_launch(hipStream_t stream, const QueryScene &scene, const Query
     a.n_tris = scene.n_tris, a.head_shift = scene.head_shift;
     a.stack_levels = std::max<uint32_t>(1u, scene.stack_levels);
     a.lds_levels = plan.lds_levels, a.top_nodes = plan.top_nodes;
+    return a;
+}
+
+}  // namespace
+
+hipError_t cross_plan(const QueryScene &scene, const uint32_t n, const int num_cus, QueryPlan *plan)
+{
+    if (scene.kind == QueryKind::Brute) {
+        *plan = plan_brute(n);
+        return hipSuccess;
+    }
+    return plan_walk(scene, n, num_cus, scene.kind == QueryKind::Wide ? reinterpret_cast<const void *>(cross_bvh4) : reinterpret_cast<const void *>(cross_bvh2), plan);
+}
+
+hipError_t cross_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, const uint32_t n)
+{
+    if (n == 0) return hipSuccess;
+    if (scene.n_tris > 0 && !scene.unit_n) return hipErrorInvalidValue;
+    const CrossArgs ca{query_args(scene, plan, scratch, records, n), scene.unit_n};
+    if (scene.kind == QueryKind::Brute) {
+        hipLaunchKernelGGL(cross_brute, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, ca);
+        return hipGetLastError();
+    }
+    const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    if (scene.kind == QueryKind::Wide)
+        hipLaunchKernelGGL(cross_bvh4, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, ca);
+    else
+        hipLaunchKernelGGL(cross_bvh2, dim3(plan.grid), dim3(kBlock), plan.lds_bytes, stream, ca);
+    return hipGetLastError();
+}
+
+hipError_t query_plan(const QueryScene &scene, const uint32_t n, const int num_cus, QueryPlan *plan, const uint32_t k)
+{
+    if (scene.kind == QueryKind::Brute) {
+        *plan = plan_brute(n);
+        return hipSuccess;
+    }
+    // (the occupancy of the instance that is launched: a k-nearest instance holds its list in registers and may fit fewer waves)
+    const void *kernel = k > 1u ? reinterpret_cast<const void *>(near_kernel(scene.kind, k))
+                                : (scene.kind == QueryKind::Wide ? reinterpret_cast<const void *>(query_bvh4) : reinterpret_cast<const void *>(query_bvh2));
+    return plan_walk(scene, n, num_cus, kernel, plan);
+}
+
+hipError_t query_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, const uint32_t n, const uint32_t k)
+{
+    if (n == 0) return hipSuccess;
+    if (k == 0 || k > kQueryMaxHits) return hipErrorInvalidValue;
+    const QueryArgs a = query_args(scene, plan, scratch, records, n);
     if (k > 1u) {  // n groups of k records; k = 1 is format 2 itself, through the kernels below
         if (scene.kind != QueryKind::Brute) {
             const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(uint32_t), stream);

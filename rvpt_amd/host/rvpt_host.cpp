@@ -654,6 +654,15 @@ bool RVPT::trace_rays_device(void *records, size_t n, int hits)
     }
     return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_HITS_NEAREST(hits), records, n * static_cast<size_t>(hits) * sizeof(rvpt_ray_hit)), "rvpt_hip_read");
 }
+bool RVPT::count_crossings(rvpt_ray_crossings *records, size_t n) { return count_crossings_device(records, n); }  // (the library classifies the pointer)
+bool RVPT::count_crossings_device(void *records, size_t n)
+{
+    if (!ctx_) {
+        error_ = "count_crossings before initialize()";
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_RAY_CROSSINGS, records, n * sizeof(rvpt_ray_crossings)), "rvpt_hip_read");
+}
 bool RVPT::trace_paths(std::vector<rvpt_ray_path> &records)
 {
     if (!ctx_) {

@@ -212,6 +212,12 @@ public:
     bool trace_rays(rvpt_ray_hit *records, size_t n, int hits);
     // the same for n groups in device memory of the context's GPU (16-byte aligned): prim stays as the LIBRARY numbers it, as for trace_rays_device above
     bool trace_rays_device(void *records, size_t n, int hits);
+    // Crossing queries (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_CROSSINGS; include/rvpt_hip.h: RAY CROSSINGS): every record comes in as a ray (org, tmax, dir) and
+    // goes out as the counts of the triangles it passes facing it and facing away, and the smallest and largest such t (front, back, t_near, t_far), in place.
+    // After initialize(); no update() is needed.  Nothing is renumbered: the answer names no triangle.
+    bool count_crossings(rvpt_ray_crossings *records, size_t n);
+    // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host
+    bool count_crossings_device(void *records, size_t n);
     // Path queries (rvpt_hip_read with RVPT_HIP_FORMAT_RAY_PATHS; include/rvpt_hip.h: PATH QUERIES): every record comes in as a ray, an RNG state and a bounce
     // budget (org, seed, dir, max_bounces) and goes out as integrator_Kajiya's radiance along it and the segments the path traced, in place.  After
     // initialize(); no update() is needed.  Nothing is renumbered: radiance does not depend on the order of the triangles.

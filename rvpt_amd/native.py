@@ -32,6 +32,9 @@ RAY_MAX_HITS = 8  # RVPT_HIP_RAY_MAX_HITS: the largest k of a k-nearest ray quer
 NO_PRIM = 0xFFFFFFFF  # a record's prim after a miss
 # rvpt_ray_hit (48 B): org, tmax, dir, flags come in, t, prim, u, v go out
 RAY_HIT_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("flags", "<u4"), ("t", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4")])
+FORMAT_RAY_CROSSINGS = 8  # RVPT_HIP_FORMAT_RAY_CROSSINGS: rvpt_hip_read answers crossing queries, `dst` holds RAY_CROSSINGS_DTYPE records (Context.count_crossings)
+# rvpt_ray_crossings (48 B): org, tmax, dir, flags come in as for a ray query (flags is ignored), front, back, t_near, t_far go out
+RAY_CROSSINGS_DTYPE = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("flags", "<u4"), ("front", "<u4"), ("back", "<u4"), ("t_near", "<f4"), ("t_far", "<f4")])
 FORMAT_RAY_PATHS = 3  # RVPT_HIP_FORMAT_RAY_PATHS: rvpt_hip_read answers path queries, `dst` holds RAY_PATH_DTYPE records (Context.trace_paths)
 PATH_MODE_KAJIYA = 9  # the render mode of integrator_Kajiya: format_ray_paths_mode(9) is FORMAT_RAY_PATHS' own kernels and bytes
 
@@ -734,6 +737,8 @@ class Context:
         once the stream that last touched it has finished, and torch is imported only when a tensor is given.  Checked here, before the call."""
         if fmt in (FORMAT_RAY_HITS, FORMAT_RAY_PATHS) or (isinstance(fmt, int) and (16 <= fmt <= 16 + PATH_MODE_KAJIYA or 33 <= fmt <= 32 + RAY_MAX_HITS)):  # known formats, but of records and not of a frame
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use trace_rays_into / trace_paths_into")
+        if fmt == FORMAT_RAY_CROSSINGS:
+            raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use count_crossings_into")
         if fmt == FORMAT_TRIANGLES:
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds the stored triangle rows, not a frame: use read_triangles / read_triangles_into")
         if fmt == FORMAT_SURFACE_POINTS:
@@ -814,6 +819,27 @@ class Context:
         if count % k:
             raise NativeError(ERR_INVALID, f"trace_rays_into: {count} records are not a multiple of hits={k}: a ray takes a group of {k} records")
         return self._query_into(records, fmt, RAY_HIT_DTYPE, "trace_rays_into", "RAY_HIT_DTYPE")
+
+    def count_crossings(self, org, dir, tmax=math.inf) -> np.ndarray:
+        """Front and back hit counts of the rays org[n, 3] + t dir[n, 3], 0 < t < tmax, against the uploaded scene — include/rvpt_hip.h: RAY CROSSINGS has the
+        set that is counted and the facing rule.  tmax is a scalar or one value per ray.  Returns RAY_CROSSINGS_DTYPE[n]: front, back, and the smallest and
+        largest accepted t; with no crossing front = back = 0, t_near = tmax and t_far = 0."""
+        org = np.asarray(org, dtype=np.float32).reshape(-1, 3)
+        dirv = np.asarray(dir, dtype=np.float32).reshape(-1, 3)
+        if org.shape != dirv.shape:
+            raise NativeError(ERR_INVALID, f"count_crossings: {org.shape[0]} origins, {dirv.shape[0]} directions")
+        tmax = np.asarray(tmax, dtype=np.float32)
+        if tmax.ndim > 1 or (tmax.ndim == 1 and tmax.shape[0] != org.shape[0]):
+            raise NativeError(ERR_INVALID, f"count_crossings: {org.shape[0]} rays, tmax of shape {tuple(tmax.shape)}")
+        rec = np.zeros(org.shape[0], dtype=RAY_CROSSINGS_DTYPE)
+        rec["org"], rec["dir"], rec["tmax"] = org, dirv, tmax
+        return self.count_crossings_into(rec)
+
+    def count_crossings_into(self, records):
+        """rvpt_hip_read with FORMAT_RAY_CROSSINGS in the caller's memory: `records` is a contiguous RAY_CROSSINGS_DTYPE array, or a contiguous float32 torch
+        tensor [n, 12] (48-byte records; front and back are the bits of their floats) on the host or on this context's device, as for trace_rays_into.  The in
+        fields stay as they are, the out fields are written.  Returns records."""
+        return self._query_into(records, FORMAT_RAY_CROSSINGS, RAY_CROSSINGS_DTYPE, "count_crossings_into", "RAY_CROSSINGS_DTYPE")
 
     def _query_into(self, records, fmt: int, dtype, what: str, dtype_name: str):
         is_tensor = not isinstance(records, np.ndarray) and hasattr(records, "data_ptr")

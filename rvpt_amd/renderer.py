@@ -89,6 +89,33 @@ def launch_sizes(frames: int, batch: int, in_flight: int = 3) -> list[int]:
     return [base + 1] * extra + [base] * (n - extra)
 
 
+# the directions of RVPT.inside's three rays: none axis-aligned, none in a coordinate plane (they need not be unit)
+INSIDE_DIRECTIONS = ((0.5377, 0.6197, 0.5717), (-0.6421, 0.3061, 0.7029), (0.2113, -0.8391, 0.5013))
+
+
+def crossing_rays(points):
+    """(org[3n, 3], dir[3n, 3]) float32: the rays RVPT.inside asks, ray 3 i + j leaving point i along INSIDE_DIRECTIONS[j]"""
+    points = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    return np.repeat(points, 3, axis=0), np.tile(np.asarray(INSIDE_DIRECTIONS, dtype=np.float32), (points.shape[0], 1))
+
+
+def inside_from_crossings(front, back, rule="winding") -> np.ndarray:
+    """RVPT.inside's vote over the counts of crossing_rays' 3 n rays: bool[n], true where at least two of a point's three rays say inside"""
+    if rule not in ("winding", "parity"):
+        raise ValueError(f"inside: rule must be 'winding' or 'parity', got {rule!r}")
+    front, back = np.asarray(front, dtype=np.int64).reshape(-1, 3), np.asarray(back, dtype=np.int64).reshape(-1, 3)
+    says = (back - front > 0) if rule == "winding" else ((front + back) % 2 == 1)
+    return says.sum(axis=1) >= 2
+
+
+def signed_distance_from(d2, prim, inside) -> np.ndarray:
+    """RVPT.signed_distance from a point query's d2 and prim and RVPT.inside's answer: float32, +inf where the point query missed"""
+    with np.errstate(invalid="ignore"):
+        d = np.sqrt(np.asarray(d2, dtype=np.float32))
+    d = np.where(np.asarray(inside, dtype=bool), -d, d).astype(np.float32)
+    return np.where(np.asarray(prim) == native.NO_PRIM, np.float32(np.inf), d).astype(np.float32)
+
+
 class RVPT:
     def __init__(self, width: int, height: int, device: int = 0, traversal: str = "brute", tile_rank: int = 0,
                  tile_world: int = 1, flags: int = 0, build: str = "host"):
@@ -483,6 +510,36 @@ class RVPT:
             hit = rec["prim"] != native.NO_PRIM
             rec["prim"][hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[rec["prim"][hit]]
         return rec
+
+    def count_crossings(self, org, dir, tmax=float("inf")) -> np.ndarray:
+        """Crossing queries against the scene as it is now (Context.count_crossings; include/rvpt_hip.h: RAY CROSSINGS): for every ray org + t dir, 0 < t < tmax,
+        how many triangles it passes facing it (front) and facing away (back), and the smallest and largest such t.  Returns native.RAY_CROSSINGS_DTYPE records;
+        with no crossing front = back = 0, t_near = tmax, t_far = 0.  The answer names no triangle, so it is the same after every builder.  Needs initialize(),
+        not update()."""
+        if self._ctx is None:
+            raise RuntimeError("count_crossings before initialize()")
+        return self._ctx.count_crossings(org, dir, tmax)
+
+    def inside(self, points, rule="winding") -> np.ndarray:
+        """bool[n]: whether each point of points[n, 3] lies inside the mesh as it is now.  Three rays leave every point along the three fixed directions
+        INSIDE_DIRECTIONS = (0.5377, 0.6197, 0.5717), (-0.6421, 0.3061, 0.7029), (0.2113, -0.8391, 0.5013) — none axis-aligned, none in a coordinate plane —
+        and each ray votes by its crossing counts (count_crossings, tmax = inf):
+          rule="winding": inside iff back - front > 0.  Assumes a closed mesh whose normals point outward; nested and overlapping shells add up.
+          rule="parity":  inside iff front + back is odd.  Assumes a closed mesh; the winding of its triangles does not matter.
+        A point is inside iff at least two of its three rays say so.  The result is a VOTE, not a definition: a ray that meets an edge or a vertex exactly may
+        count it twice or not at all, which is why there are three; on a mesh that is not closed the answer depends on the directions.  A point with a
+        non-finite coordinate is outside.  Needs initialize(), not update()."""
+        inside_from_crossings((), (), rule)  # (a wrong rule raises before any call)
+        org, dirv = crossing_rays(points)
+        rec = self.count_crossings(org, dirv)
+        return inside_from_crossings(rec["front"], rec["back"], rule)
+
+    def signed_distance(self, points) -> np.ndarray:
+        """float32[n]: the distance from each point to the mesh as it is now — sqrt of closest_points' d2 — negative where inside(points) (the winding rule, with
+        what it assumes) says inside; +inf where the point query misses (a non-finite point, the empty scene).  Needs initialize(), not update()."""
+        points = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+        rec = self.closest_points(points)
+        return signed_distance_from(rec["d2"], rec["prim"], self.inside(points))
 
     def read_triangles(self, out=None):
         """The mesh as it now stands on the device (Context.read_triangles; include/rvpt_hip.h: TRIANGLES): float32[n, 16], the stored bytes of every triangle

@@ -14,6 +14,11 @@ usage: tools/bench_rays.py rates [default cornell terrain]     on the GPU box: r
                                                                format-2 calls.  <label> names the block the run writes ("this tree", "parent, before", ...); with
                                                                RVPT_HIP_LIB naming a library that has no such format (the parent commit's) the block holds format 2
                                                                alone, three passes, which is the yardstick for format 2's own rate
+       tools/bench_rays.py --crossings <label> [scenes]        crossing queries (FORMAT_RAY_CROSSINGS) on the same 2 M camera rays from device records: format 2 in three passes
+                                                               and any-hit hits=8 as yardsticks of the same run, format 8 with tmax = inf and with tmax = one scene extent,
+                                                               the mean front + back per ray, and how many rays a brute-force context of the same triangles counts
+                                                               differently.  With RVPT_HIP_LIB naming a library that has no such format (the parent commit's) the block
+                                                               holds the yardsticks alone.  Writes the block of its label into profiles/ray_crossings.txt
 Each mode rewrites its own section of profiles/ray_queries.txt and leaves the others; `nearest` rewrites the block of its label inside its section."""
 import os
 import statistics
@@ -206,6 +211,102 @@ def nearest(label, names):
     write_nearest_block(label, text)
 
 
+OUT_CROSSINGS = ROOT / "profiles" / "ray_crossings.txt"
+MARK_CROSSINGS = "==== measured"
+
+
+def write_crossings_block(label, text):
+    """the block `label` of profiles/ray_crossings.txt's measured section replaced (or added behind the others); everything in front of the section stays"""
+    old = OUT_CROSSINGS.read_text() if OUT_CROSSINGS.exists() else ""
+    front, _, section = old.partition(MARK_CROSSINGS)
+    blocks = {}
+    for part in section.split(BLOCK)[1:]:
+        name, _, body = part.partition(" ----\n")
+        blocks[name] = body.rstrip("\n")
+    blocks[label] = text.rstrip("\n")
+    out = front.rstrip("\n") + "\n\n" + MARK_CROSSINGS + " (tools/bench_rays.py --crossings <label>: one block per process, in the order they ran) ====\n"
+    for name, body in blocks.items():
+        out += "\n" + BLOCK + name + " ----\n" + body + "\n"
+    OUT_CROSSINGS.write_text(out)
+
+
+def crossings(label, names):
+    import torch
+    from rvpt_amd import native
+    lib = os.environ.get("RVPT_HIP_LIB", "librvpt_hip.so (this tree's)")
+    n = W * H
+    lines = [f"library: {Path(lib).name}; {n} pixel-centre camera rays in pixel order, device records; wall clock around the call; every figure is the median (min .. max)",
+             "of 7 calls after 2, in Grays/s", ""]
+
+    def timed(fn, reps=7, warm=2):
+        for _ in range(warm):
+            fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts), min(ts), max(ts)
+
+    def figure(t):
+        med, lo, hi = t
+        return f"{n / med / 1e9:7.3f} ({n / hi / 1e9:7.3f} .. {n / lo / 1e9:7.3f})"
+
+    for name, tris, mats, nodes, cam in scenes(names):
+        ext = float(np.ptp(tris.reshape(-1, 4, 4)[:, :3, :3].reshape(-1, 3), axis=0).max())
+        lines.append(f"== {name}: {tris.shape[0]} triangles, extent {ext:.2f} ==")
+        ctx = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BVH)
+        ctx.upload_scene(nodes, tris, mats)
+        rec = camera_records(cam)
+        dev = torch.from_numpy(rec.view(np.float32).reshape(-1, 12)).to("cuda:0")
+        for p in range(3):  # format 2's own rate, three passes: the figure that is compared with the parent commit's library
+            t2 = timed(lambda: ctx.trace_rays_into(dev))
+            lines.append(f"format 2, pass {p + 1}:                      {figure(t2)}")
+        groups = np.zeros((n, 8), dtype=native.RAY_HIT_DTYPE)
+        groups[:, 0] = camera_records(cam, flags=native.RAY_ANY_HIT)
+        dev8 = torch.from_numpy(groups.view(np.float32).reshape(-1, 12)).to("cuda:0")
+        t8 = timed(lambda: ctx.trace_rays_into(dev8, hits=8))
+        lines.append(f"any hit, hits=8:                       {figure(t8)}")
+        del dev8, groups
+        if not hasattr(native, "FORMAT_RAY_CROSSINGS"):
+            has_form = False
+        else:
+            try:
+                ctx.count_crossings_into(dev[:8].clone())
+                has_form = True
+            except native.NativeError as e:
+                has_form = False
+                lines.append(f"no crossing form in this library ({str(e)[:60]}): the yardsticks alone")
+        if has_form:
+            tc = timed(lambda: ctx.count_crossings_into(dev))
+            got = dev.cpu().numpy().view(native.RAY_CROSSINGS_DTYPE).reshape(-1)
+            total = got["front"].astype(np.int64) + got["back"]
+            lines.append(f"format 8, tmax = inf:                  {figure(tc)}   = {t2[0] / tc[0]:5.2f} x format 2's rate, {t8[0] / tc[0]:5.2f} x any-hit hits=8's")
+            lines.append(f"    front + back per ray: mean {total.mean():.3f}, max {int(total.max())}; rays with a crossing: {int((total > 0).sum())}")
+            cut = camera_records(cam, tmax=np.float32(ext))
+            devc = torch.from_numpy(cut.view(np.float32).reshape(-1, 12)).to("cuda:0")
+            tf = timed(lambda: ctx.count_crossings_into(devc))
+            gotc = devc.cpu().numpy().view(native.RAY_CROSSINGS_DTYPE).reshape(-1)
+            lines.append(f"format 8, tmax = extent = {ext:7.2f}:      {figure(tf)}   = {t2[0] / tf[0]:5.2f} x format 2's rate; front + back per ray: mean "
+                         f"{(gotc['front'].astype(np.int64) + gotc['back']).mean():.3f}")
+            # the same triangles on a brute-force context: how many rays get other counts (recorded, not asserted; as many rays as 2e10 triangle tests allow)
+            stride = max(1, int(np.ceil(n * float(tris.shape[0]) / 2e10)))
+            some = np.ascontiguousarray(rec[::stride])
+            brute = native.Context(W, H, 0, 0, 1, native.TRAVERSAL_BRUTE)
+            brute.upload_scene(None, tris, mats)
+            b = brute.count_crossings_into(some.view(native.RAY_CROSSINGS_DTYPE).copy())
+            brute.close()
+            g = got[::stride]
+            differ = int(((b["front"] != g["front"]) | (b["back"] != g["back"])).sum())
+            lines.append(f"    BVH context against a brute-force context of the same triangles, every {stride}th ray ({some.shape[0]} rays): {differ} rays with other counts")
+            del devc
+        ctx.close()
+        lines.append("")
+    text = "\n".join(lines)
+    print(text)
+    write_crossings_block(label, text)
+
+
 def queries(names):
     import torch
     from rvpt_amd import native
@@ -257,6 +358,9 @@ if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "rates"
     if mode == "resources":
         sys.exit(0 if resources(sys.argv[2]) else 1)
+    if mode in ("--crossings", "crossings"):
+        crossings(sys.argv[2], sys.argv[3:] or ["default", "cornell", "terrain"])
+        sys.exit(0)
     if mode == "nearest":
         nearest(sys.argv[2], sys.argv[3:] or ["default", "cornell", "terrain"])
         sys.exit(0)

@@ -91,7 +91,11 @@ extern "C" {
                                      until then the "unknown format" error — is a K-NEAREST POINT QUERY: `dst` holds groups of k rvpt_point_hit records,
                                      the point in the first, the k nearest triangles of the mesh out.  Still 8, no new symbol: rvpt_hip_read with the
                                      format RVPT_HIP_FORMAT_RAY_CROSSINGS (8) — until then the "unknown format" error — is a CROSSING QUERY: `dst` holds
-                                     rvpt_ray_crossings records, rays in, the counts of front and back hits along them and the first and last t out */
+                                     rvpt_ray_crossings records, rays in, the counts of front and back hits along them and the first and last t out.
+                                     Still 8, no new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_BOX_OVERLAPS (9) or a format
+                                     RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k) (65 .. 68) — until then the "unknown format" error — is a BOX QUERY: `dst` holds
+                                     groups of k rvpt_box_overlap records, a closed box in the first, the count of the triangles that meet it and the
+                                     smallest of their numbers out */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -222,6 +226,18 @@ typedef struct rvpt_point_hit {
 
 #define RVPT_HIP_POINT_MAX_NEAREST 8u /* per call: the largest k of a k-nearest point query */
 #define RVPT_HIP_FORMAT_NEAREST_POINTS_K(k) (48 + (k))     /* k = 1 .. RVPT_HIP_POINT_MAX_NEAREST: formats 49 .. 56; dst: n groups of k rvpt_point_hit (K-NEAREST POINTS at rvpt_hip_read) */
+
+#define RVPT_HIP_FORMAT_BOX_OVERLAPS 9   /* dst: rvpt_box_overlap[dst_bytes / 48], in and out (BOX OVERLAPS at rvpt_hip_read) */
+
+/* One box of a query and its answer (48 B = three float4; no reference counterpart: the reference asks its scene nothing but its camera's paths). */
+typedef struct rvpt_box_overlap {
+    float lo[3]; uint32_t prim_from;     /* in: the box is [lo, hi] per axis, closed; only triangles whose reported number is >= prim_from take part */
+    float hi[3]; uint32_t flags;         /* in: flags reserved, ignored */
+    uint32_t count; uint32_t prim[3];    /* out: how many triangles meet the box; the smallest of their numbers, ascending, 0xFFFFFFFF past the last */
+} rvpt_box_overlap;
+
+#define RVPT_HIP_BOX_MAX_GROUP 4u /* per call: the largest k of a box query's groups */
+#define RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k) (64 + (k))       /* k = 1 .. RVPT_HIP_BOX_MAX_GROUP: formats 65 .. 68; dst: n groups of k rvpt_box_overlap listing 4k - 1 numbers (BOX OVERLAPS at rvpt_hip_read) */
 
 #define RVPT_HIP_FORMAT_TRIANGLES 5      /* dst: rvpt_triangle[n_tris], out: the stored rows in update order (TRIANGLES at rvpt_hip_read) */
 #define RVPT_HIP_FORMAT_SURFACE_POINTS 6 /* dst: rvpt_surface_point[dst_bytes / 48], in and out (SURFACE POINTS at rvpt_hip_read) */
@@ -832,6 +848,48 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  *   untouched; host records go through the staging buffer and only the out fields travel back; the call is LOCAL under a communicator, implies rvpt_hip_wait,
  *   leaves untouched what a point query leaves untouched, and answers on the scene as the last update form left it.
  * DESIGN.md 5.26 has the kernels and what was measured (profiles/nearest_points_k.txt).
+ *
+ * BOX OVERLAPS — how many triangles of the mesh meet the caller's own boxes, and which, in place:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_BOX_OVERLAPS, records, n * sizeof(rvpt_box_overlap));
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k), records, n * k * sizeof(rvpt_box_overlap));         k = 1 .. RVPT_HIP_BOX_MAX_GROUP
+ *
+ * The region form of a query: the broad phase of a collision against the mesh as it is posed or skinned on the device, and the cell test of a conservative
+ * (surface) voxelisation.  A record carries a closed box [lo, hi] and a first number prim_from in, and the count and the smallest numbers out.  With
+ * RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k), `dst` holds n GROUPS of k consecutive records: record 0 of a group carries the box; the in quads (the first 32 bytes) of
+ * records 1 .. k-1 are ignored and never written; the out quad of record j >= 1 is four more prim slots.  A group therefore lists up to S = 4k - 1 numbers:
+ * 3, 7, 11 or 15.  The k belongs to the call, not to the record.  RVPT_HIP_FORMAT_BOX_OVERLAPS_K(1) is format 9 itself: the same kernels, bytes and messages.
+ * Formats 64 and 69 are the "unknown format" error.
+ * - THE ANSWER IS DEFINED WITHOUT REFERENCE TO ANY WALK, as a point query's is.  A is the set of stored triangles that pass THE TEST below and whose reported
+ *   number is >= prim_from.  The reported number is a point query's (THE NUMBERING OF prim above): the stored order after an upload, the caller's order after
+ *   a build form.  count = |A|.  The prim slots hold the S smallest reported numbers of A in ascending order; from the first slot that A does not fill, every
+ *   slot is 0xFFFFFFFF.  The answer is therefore the same on every kind of context, after every builder and on every tree.
+ * - PAGING.  If count > S, call again with prim_from = the last listed number + 1: a caller enumerates A in ceil(|A| / S) calls, and count of each call is
+ *   what is still to come, the listed ones included.
+ * - Each stored triangle is taken to lie under one leaf, as in every tree the library's builders and rvpt_bvh_build make.  A caller's tree that lists a triangle
+ *   under two leaves may count it twice.
+ * - THE TEST is the separating-axis test of a triangle against a box, 13 axes, in binary32: every product, sum and difference is rounded on its own, no FMA.
+ *   Every comparison is a rejection, so a NaN rejects nothing: "min(x, y, z) > r" below stands for x > r and y > r and z > r, "max(x, y, z) < r" likewise.
+ *   a, b, c are vert0..2 of the stored row.  A triangle with any non-finite vertex component is never in A.
+ *   1. Boxes.  Per axis k, reject if min(a_k, b_k, c_k) > hi_k or max(a_k, b_k, c_k) < lo_k.  Comparisons only.
+ *   2. Set-up.  ctr = lo*0.5 + hi*0.5 and h = hi - ctr; v0 = a - ctr, v1 = b - ctr, v2 = c - ctr; e0 = b - a, e1 = c - b, e2 = a - c.
+ *   3. Plane.  n = cross(b - a, c - a) with cross(x, y) = (x1*y2 - x2*y1, x2*y0 - x0*y2, x0*y1 - x1*y0), and dot(x, y) = (x0*y0 + x1*y1) + x2*y2.  Per axis,
+ *      vmin_k = n_k > 0 ? -h_k - v0_k : h_k - v0_k, and vmax_k is the other choice.  Reject if dot(n, vmin) > 0.  Reject if dot(n, vmax) < 0.
+ *   4. Nine edge axes.  For each edge e_i, i = 0, 1, 2, and each axis j = x, y, z, in that nesting order, with k1 = (j + 1) % 3 and k2 = (j + 2) % 3:
+ *      p_m = e_i[k1]*v_m[k2] - e_i[k2]*v_m[k1] for m = 0, 1, 2; r = h[k1]*|e_i[k2]| + h[k2]*|e_i[k1]|; reject if min(p0, p1, p2) > r or max(p0, p1, p2) < -r.
+ *   The triangle is in A iff nothing rejected.  Touching counts.  A zero-area triangle gets what this arithmetic gives: the segment test for a == b, the box
+ *   test alone for a == b == c.
+ * - WHAT IS NOT PROMISED.  The test is the ROUNDED form of the separating-axis test: a triangle within rounding of a box face may fall on either side of it.
+ *   Where every operation above is exact — small integers, say — the answer is the exact one.
+ * - INVALID RECORDS.  A record 0 is invalid if a component of lo or hi is non-finite, or if lo_k > hi_k on some axis; lo == hi is legal, a point or a plane
+ *   probe.  Invalidity is decided before any walk: count = 0 and every slot 0xFFFFFFFF.  The empty scene answers every record the same way.
+ * - Everything else is a point query's rule: the call needs a scene and no rvpt_hip_set_frame; dst_bytes must be a multiple of 48 * k, else
+ *   RVPT_HIP_ERR_INVALID (with k > 1 the message gives k and the byte count); dst_bytes == 0 is a successful no-op; fewer than 2^32 records (n * k) per call;
+ *   `dst` is host memory or 16-byte aligned device memory of the context's GPU, another GPU's memory is an error naming both devices, and in every error case
+ *   `dst` is untouched; host records go through the staging buffer and only the out quads travel back; the call is LOCAL under a communicator, implies
+ *   rvpt_hip_wait, leaves untouched what a point query leaves untouched — a frame dispatched afterwards is bit for bit the frame dispatched without it — and
+ *   answers on the scene as the last update form left it: plain, guarded, sparse, pose or skin.
+ * DESIGN.md 5.28 has the kernels, why a walk that prunes by step 1 returns exactly A, and what was measured (profiles/box_overlaps.txt).
  *
  * TRIANGLES — the whole mesh as it now stands:
  *

@@ -35,6 +35,7 @@
 #include "rvpt_build.h"
 #include "rvpt_query.h"
 #include "rvpt_nearest.h"
+#include "rvpt_box.h"
 #include "rvpt_surface.h"
 #include "rvpt_paths.h"
 #include "rvpt_packets.h"
@@ -54,6 +55,10 @@ static_assert(sizeof(rvpt_render_settings) == 40, "RenderSettings std140 block (
 static_assert(sizeof(rvpt_camera_data) == 80, "Camera block (compute_pass.comp:44-49)");
 static_assert(RVPT_HIP_RAY_MAX_HITS == rv::kQueryMaxHits, "the k of a k-nearest ray query: the header's and the kernels'");
 static_assert(RVPT_HIP_POINT_MAX_NEAREST == rv::kNearestMaxK, "the k of a k-nearest point query: the header's and the kernels'");
+static_assert(RVPT_HIP_BOX_MAX_GROUP == rv::kBoxMaxGroup, "the k of a box query's group: the header's and the kernels'");
+static_assert(sizeof(rvpt_box_overlap) == rv::kBoxRecordBytes && offsetof(rvpt_box_overlap, prim_from) == 12 && offsetof(rvpt_box_overlap, hi) == 16 &&
+                  offsetof(rvpt_box_overlap, flags) == 28 && offsetof(rvpt_box_overlap, count) == 32 && offsetof(rvpt_box_overlap, prim) == 36,
+              "a box query's record: three float4 (rvpt_box.hip)");
 static_assert(sizeof(rvpt_ray_hit) == rv::kQueryRecordBytes && offsetof(rvpt_ray_hit, tmax) == 12 && offsetof(rvpt_ray_hit, dir) == 16 && offsetof(rvpt_ray_hit, flags) == 28 &&
                   offsetof(rvpt_ray_hit, t) == 32 && offsetof(rvpt_ray_hit, prim) == 36 && offsetof(rvpt_ray_hit, u) == 40 && offsetof(rvpt_ray_hit, v) == 44,
               "a ray query's record: three float4 (rvpt_query.hip)");
@@ -1464,14 +1469,21 @@ int rvpt_hip_gather(rvpt_hip_ctx *ctx, void *dst_dev_rgba32f)
 // per record as before.  (RecordKind::Points: 0 for RVPT_HIP_FORMAT_NEAREST_POINTS and RVPT_HIP_FORMAT_NEAREST_POINTS_K(1), the same call; k for
 // RVPT_HIP_FORMAT_NEAREST_POINTS_K(k), k > 1 (K-NEAREST POINTS) — groups of k records, one point each, likewise.)
 // RecordKind::Crossings (RVPT_HIP_FORMAT_RAY_CROSSINGS, RAY CROSSINGS): a ray query in everything but the kernels and the record's name.
-enum class RecordKind { Rays, Paths, Points, Surface, Crossings };
+// RecordKind::Boxes (RVPT_HIP_FORMAT_BOX_OVERLAPS, BOX OVERLAPS): a point query's scene under the kernels of rvpt_box.hip; `hits` is 0 for format 9 and for
+// RVPT_HIP_FORMAT_BOX_OVERLAPS_K(1), the same call, and k for RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k), k > 1 — groups of k records, one box each; only the third quad
+// of a record is out.
+enum class RecordKind { Rays, Paths, Points, Surface, Crossings, Boxes };
 static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const RecordKind kind, const uint32_t path_mode = rv::kPathModeKajiya, const uint32_t hits = 0)
 {
     const bool paths = kind == RecordKind::Paths, points = kind == RecordKind::Points, surface = kind == RecordKind::Surface, crossings = kind == RecordKind::Crossings;
-    const char *what = surface ? "surface" : (points ? "point" : (paths ? "path" : (crossings ? "crossing" : "ray")));
-    const char *record = surface ? "rvpt_surface_point" : (points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : (crossings ? "rvpt_ray_crossings" : "rvpt_ray_hit")));
+    const bool boxes = kind == RecordKind::Boxes;
+    const char *what = boxes ? "box" : surface ? "surface" : (points ? "point" : (paths ? "path" : (crossings ? "crossing" : "ray")));
+    const char *record = boxes ? "rvpt_box_overlap" : surface ? "rvpt_surface_point" : (points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : (crossings ? "rvpt_ray_crossings" : "rvpt_ray_hit")));
     static_assert(sizeof(rvpt_ray_crossings) == sizeof(rvpt_ray_hit) && offsetof(rvpt_ray_crossings, front) == offsetof(rvpt_ray_hit, t), "a crossing record is laid out as a ray record");
     const size_t out_offset = surface ? offsetof(rvpt_surface_point, point) : (points ? offsetof(rvpt_point_hit, closest) : offsetof(rvpt_ray_hit, t));  // where a record's out fields begin
+    if (hits && boxes && dst_bytes % (sizeof(rvpt_box_overlap) * hits))
+        return fail(ctx, RVPT_HIP_ERR_INVALID, "box query with k = %u: dst_bytes %zu is not a multiple of the %zu bytes of a group of k rvpt_box_overlap", hits, dst_bytes,
+                    sizeof(rvpt_box_overlap) * hits);
     if (hits && points && dst_bytes % (sizeof(rvpt_point_hit) * hits))
         return fail(ctx, RVPT_HIP_ERR_INVALID, "point query with k = %u: dst_bytes %zu is not a multiple of the %zu bytes of a group of k rvpt_point_hit", hits, dst_bytes,
                     sizeof(rvpt_point_hit) * hits);
@@ -1505,9 +1517,11 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
     nearest.brute = !bvh;
     nearest.tris = ctx->d_tris, nearest.nodes = ctx->d_nodes, nearest.perm = scene.perm;
     nearest.n_tris = scene.n_tris, nearest.n_nodes = static_cast<uint32_t>(ctx->n_nodes), nearest.stack_levels = bvh_stack_levels(ctx);
-    const uint32_t groups_of = hits ? hits : 1u;  // records per ray, or per point
+    const uint32_t groups_of = hits ? hits : 1u;  // records per ray, per point or per box
     rv::QueryPlan plan{};
-    if (points)
+    if (boxes)
+        HIP_TRY(ctx, rv::box_plan(nearest, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
+    else if (points)
         HIP_TRY(ctx, rv::nearest_plan(nearest, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
     else if (paths)
         HIP_TRY(ctx, rv::path_plan(path_scene, static_cast<uint32_t>(n), ctx->num_cus, path_mode, &plan));
@@ -1538,7 +1552,9 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
         mesh.tris = ctx->d_tris, mesh.unit_n = ctx->d_unit_n, mesh.mat_index = ctx->d_mat_index;
         mesh.inv_perm = permuted ? ctx->d_surface_inv : nullptr, mesh.n_tris = scene.n_tris;
         HIP_TRY(ctx, rv::surface_launch(ctx->stream, mesh, records, static_cast<uint32_t>(n)));
-    } else if (points)
+    } else if (boxes)
+        HIP_TRY(ctx, rv::box_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
+    else if (points)
         HIP_TRY(ctx, rv::nearest_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
     else if (paths)
         HIP_TRY(ctx, rv::path_launch(ctx->stream, path_scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n), path_mode));
@@ -1597,6 +1613,9 @@ int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
     if (format == RVPT_HIP_FORMAT_TRIANGLES) return read_triangles(ctx, dst, dst_bytes);  // local as well
     if (format == RVPT_HIP_FORMAT_SURFACE_POINTS) return query_records(ctx, dst, dst_bytes, RecordKind::Surface);
     if (format == RVPT_HIP_FORMAT_RAY_CROSSINGS) return query_records(ctx, dst, dst_bytes, RecordKind::Crossings);  // local as well
+    if (format == RVPT_HIP_FORMAT_BOX_OVERLAPS || format == RVPT_HIP_FORMAT_BOX_OVERLAPS_K(1)) return query_records(ctx, dst, dst_bytes, RecordKind::Boxes);  // k = 1 IS format 9, its messages included; local as well
+    if (format > RVPT_HIP_FORMAT_BOX_OVERLAPS_K(1) && format <= static_cast<int>(RVPT_HIP_FORMAT_BOX_OVERLAPS_K(RVPT_HIP_BOX_MAX_GROUP)))  // the longer lists of a box query; local as well
+        return query_records(ctx, dst, dst_bytes, RecordKind::Boxes, rv::kPathModeKajiya, static_cast<uint32_t>(format) - RVPT_HIP_FORMAT_BOX_OVERLAPS_K(0u));
     if (format == RVPT_HIP_FORMAT_RAY_HITS || format == RVPT_HIP_FORMAT_RAY_PATHS || format == RVPT_HIP_FORMAT_NEAREST_POINTS)  // local even with a communicator: every rank holds the whole scene
         return query_records(ctx, dst, dst_bytes,
                              format == RVPT_HIP_FORMAT_NEAREST_POINTS ? RecordKind::Points : (format == RVPT_HIP_FORMAT_RAY_PATHS ? RecordKind::Paths : RecordKind::Rays));

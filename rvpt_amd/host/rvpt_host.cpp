@@ -732,6 +732,30 @@ bool RVPT::closest_points_device(void *records, size_t n, int k)
     }
     return check(backend_.read(ctx_, RVPT_HIP_FORMAT_NEAREST_POINTS_K(k), records, n * static_cast<size_t>(k) * sizeof(rvpt_point_hit)), "rvpt_hip_read");
 }
+bool RVPT::box_overlaps(rvpt_box_overlap *records, size_t n, int k)
+{
+    if (!box_overlaps_device(records, n, k)) return false;  // (the library classifies the pointer)
+    if (!device_built_)  // the library numbered the leaf order it was given: every slot of every group, the count of record 0 left alone
+        for (size_t i = 0; i < n * static_cast<size_t>(k); ++i) {
+            uint32_t *quad = reinterpret_cast<uint32_t *>(&records[i]) + 8;  // the out quad: (count, three numbers) in record 0, four numbers in a follower
+            for (int w = i % static_cast<size_t>(k) == 0 ? 1 : 0; w < 4; ++w)
+                if (quad[w] < order_.size()) quad[w] = order_[quad[w]];
+        }
+    return true;
+}
+bool RVPT::box_overlaps_device(void *records, size_t n, int k)
+{
+    if (!ctx_) {
+        error_ = "box_overlaps before initialize()";
+        return false;
+    }
+    if (k < 1 || k > static_cast<int>(RVPT_HIP_BOX_MAX_GROUP)) {
+        error_ = "box_overlaps: k " + std::to_string(k) + " is outside 1 .. " + std::to_string(RVPT_HIP_BOX_MAX_GROUP);
+        return false;
+    }
+    return check(backend_.read(ctx_, k == 1 ? RVPT_HIP_FORMAT_BOX_OVERLAPS : RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k), records, n * static_cast<size_t>(k) * sizeof(rvpt_box_overlap)),
+                 "rvpt_hip_read");
+}
 bool RVPT::read_triangles(std::vector<rvpt_triangle> &triangles)
 {
     if (!ctx_) {

@@ -243,6 +243,14 @@ public:
     bool closest_points(rvpt_point_hit *records, size_t n, int k);
     // the same for n groups in device memory of the context's GPU (16-byte aligned): prim stays as the LIBRARY numbers it, as for closest_points_device above
     bool closest_points_device(void *records, size_t n, int k);
+    // Box queries (rvpt_hip_read with RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k); include/rvpt_hip.h: BOX OVERLAPS): `records` holds n GROUPS of k consecutive records,
+    // n * k in all; record 0 of a group carries the closed box and prim_from, and receives the count of the triangles that meet the box; the 4k - 1 smallest of
+    // their numbers fill record 0's prim and the out quads of records 1 .. k - 1 (0xFFFFFFFF past the last).  Every listed number is renumbered to the order the
+    // triangles were ADDED, as closest_points does; after a host build the library orders, cuts and compares with prim_from by the STORED number, before that
+    // renumbering.  k outside 1 .. RVPT_HIP_BOX_MAX_GROUP fails here, before any call.  After initialize(); no update() is needed.
+    bool box_overlaps(rvpt_box_overlap *records, size_t n, int k = 1);
+    // the same for n groups in device memory of the context's GPU (16-byte aligned), which never visit the host: the numbers stay as the LIBRARY numbers them
+    bool box_overlaps_device(void *records, size_t n, int k = 1);
     // The geometry read-back (rvpt_hip_read with RVPT_HIP_FORMAT_TRIANGLES; include/rvpt_hip.h: TRIANGLES): the stored rows of the mesh as the last update,
     // pose or skin form left them — all 64 bytes of each, nothing recomputed — in the order the triangles were ADDED (after a host build the leaf order the
     // library holds is undone here).  After initialize(); no update() is needed.

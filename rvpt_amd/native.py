@@ -72,6 +72,27 @@ def FORMAT_NEAREST_POINTS_K(k) -> int:
     return 48 + int(k)
 
 
+FORMAT_BOX_OVERLAPS = 9  # RVPT_HIP_FORMAT_BOX_OVERLAPS: rvpt_hip_read answers box queries, `dst` holds BOX_OVERLAP_DTYPE records (Context.box_overlaps)
+# rvpt_box_overlap: 48 bytes, three float4 — a closed box [lo, hi] and the first number that takes part in; the count of the triangles that meet it and the smallest of their numbers out
+BOX_OVERLAP_DTYPE = np.dtype([("lo", "<f4", (3,)), ("prim_from", "<u4"), ("hi", "<f4", (3,)), ("flags", "<u4"), ("count", "<u4"), ("prim", "<u4", (3,))])
+BOX_MAX_GROUP = 4  # RVPT_HIP_BOX_MAX_GROUP: the largest k of a box query's groups, which list 4k - 1 numbers
+
+
+def FORMAT_BOX_OVERLAPS_K(k) -> int:
+    """RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k), formats 65 .. 68: `dst` holds groups of k BOX_OVERLAP_DTYPE records, the box in the first, count and 4k - 1 numbers
+    out (Context.box_overlaps(..., k=k)); k = 1 is FORMAT_BOX_OVERLAPS' own kernels and bytes.  A k that is no int in 1 .. BOX_MAX_GROUP raises before any call."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= BOX_MAX_GROUP:
+        raise NativeError(ERR_INVALID, f"k must be an int in 1 .. {BOX_MAX_GROUP}, got {k!r}")
+    return 64 + int(k)
+
+
+def box_overlap_lists(records, k=1):
+    """(count[n], numbers[n, 4k - 1]) of answered box records (BOX_OVERLAP_DTYPE, n groups of k, flat or [n, k]): the lists of a group side by side"""
+    g = np.ascontiguousarray(records).reshape(-1, int(k))
+    quads = g.view(np.uint32).reshape(g.shape[0], int(k), 12)[:, :, 8:].reshape(g.shape[0], 4 * int(k))
+    return quads[:, 0].copy(), quads[:, 1:].copy()
+
+
 FORMAT_TRIANGLES = 5  # RVPT_HIP_FORMAT_TRIANGLES: rvpt_hip_read returns the stored rvpt_triangle rows in update order (Context.read_triangles)
 FORMAT_SURFACE_POINTS = 6  # RVPT_HIP_FORMAT_SURFACE_POINTS: rvpt_hip_read answers surface records, `dst` holds SURFACE_POINT_DTYPE records (Context.surface_points)
 # rvpt_surface_point: 48 bytes, three float4 — prim, u, v as a query reported them (and a reserved word) in; the point of the stored mesh, its material word, its normal out
@@ -739,6 +760,8 @@ class Context:
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use trace_rays_into / trace_paths_into")
         if fmt == FORMAT_RAY_CROSSINGS:
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use count_crossings_into")
+        if fmt == FORMAT_BOX_OVERLAPS or (isinstance(fmt, int) and 65 <= fmt <= 64 + BOX_MAX_GROUP):
+            raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use box_overlaps_into")
         if fmt == FORMAT_TRIANGLES:
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds the stored triangle rows, not a frame: use read_triangles / read_triangles_into")
         if fmt == FORMAT_SURFACE_POINTS:
@@ -944,6 +967,42 @@ class Context:
         if count % k:
             raise NativeError(ERR_INVALID, f"closest_points_into: {count} records are not a multiple of k={k}: a point takes a group of {k} records")
         return self._query_into(records, fmt, POINT_HIT_DTYPE, "closest_points_into", "POINT_HIT_DTYPE")
+
+    def box_overlaps(self, lo, hi, prim_from=0, k=1) -> np.ndarray:
+        """How many triangles of the uploaded mesh meet each of the closed boxes [lo[n, 3], hi[n, 3]], and which — include/rvpt_hip.h: BOX OVERLAPS has the
+        set, the test and the numbering of prim.  prim_from, a scalar or one value per box, leaves out every triangle whose number is below it (paging: ask
+        again with the last listed number + 1).  Returns BOX_OVERLAP_DTYPE[n, k]: rec["count"][:, 0] is the count; the 4k - 1 smallest numbers, ascending and
+        NO_PRIM past the last, are rec["prim"][:, 0] followed by the out quads of records 1 .. k - 1 (box_overlap_lists puts them side by side)."""
+        FORMAT_BOX_OVERLAPS_K(k)  # (before anything else: a refusal needs no arrays)
+        lo, hi = np.asarray(lo, dtype=np.float32), np.asarray(hi, dtype=np.float32)
+        if lo.ndim == 0 or lo.size % 3 or lo.shape != hi.shape or (lo.ndim > 1 and lo.shape[-1] != 3):
+            raise NativeError(ERR_INVALID, f"box_overlaps: lo[n, 3] and hi[n, 3] are needed, got shapes {tuple(lo.shape)} and {tuple(hi.shape)}")
+        lo, hi = lo.reshape(-1, 3), hi.reshape(-1, 3)
+        first = np.asarray(prim_from, dtype=np.uint32)
+        if first.ndim > 1 or (first.ndim == 1 and first.shape[0] != lo.shape[0]):
+            raise NativeError(ERR_INVALID, f"box_overlaps: {lo.shape[0]} boxes, prim_from of shape {tuple(first.shape)}")
+        rec = np.zeros((lo.shape[0], int(k)), dtype=BOX_OVERLAP_DTYPE)
+        rec["lo"][:, 0], rec["hi"][:, 0], rec["prim_from"][:, 0] = lo, hi, first
+        return self.box_overlaps_into(rec, k=k)
+
+    def box_overlaps_into(self, records, k=1):
+        """rvpt_hip_read with FORMAT_BOX_OVERLAPS (k = 1) or FORMAT_BOX_OVERLAPS_K(k) in the caller's memory: `records` holds n groups of k records — a contiguous
+        BOX_OVERLAP_DTYPE array shaped (n * k,) or (n, k), or a contiguous float32 torch tensor [n * k, 12] (48-byte records; prim_from, count and the numbers are
+        the bits of their floats) on the host or on this context's device, as for trace_rays_into.  Record 0 of a group carries the box; every in quad stays as it
+        is, the out quads are written.  Returns records.  A record count that is no multiple of k raises before any call."""
+        fmt = FORMAT_BOX_OVERLAPS_K(k)
+        k = int(k)
+        if k == 1:
+            fmt = FORMAT_BOX_OVERLAPS  # (the same kernels and bytes under either value: the form's first name is kept on the wire)
+        if isinstance(records, np.ndarray):
+            if records.ndim > 2 or (records.ndim == 2 and records.shape[1] != k):
+                raise NativeError(ERR_INVALID, f"box_overlaps_into: k={k} needs BOX_OVERLAP_DTYPE[n, {k}] or [n * {k}], got shape {tuple(records.shape)}")
+            count = records.size
+        else:
+            count = int(records.shape[0]) if hasattr(records, "data_ptr") and records.dim() == 2 else 0  # (_query_into refuses what is no tensor [n, 12])
+        if count % k:
+            raise NativeError(ERR_INVALID, f"box_overlaps_into: {count} records are not a multiple of k={k}: a box takes a group of {k} records")
+        return self._query_into(records, fmt, BOX_OVERLAP_DTYPE, "box_overlaps_into", "BOX_OVERLAP_DTYPE")
 
     def read_triangles(self) -> np.ndarray:
         """rvpt_hip_read with FORMAT_TRIANGLES: the stored triangle rows as the last update form left them — all 64 bytes of each, nothing recomputed — as

@@ -93,6 +93,19 @@ def launch_sizes(frames: int, batch: int, in_flight: int = 3) -> list[int]:
 INSIDE_DIRECTIONS = ((0.5377, 0.6197, 0.5717), (-0.6421, 0.3061, 0.7029), (0.2113, -0.8391, 0.5013))
 
 
+def voxel_boxes(origin, cell, shape):
+    """(lo, hi), float32[nx * ny * nz, 3] each: the closed cells of RVPT.voxelize's grid in C order of (i, j, k).  Along every axis cell i is
+    [origin + i * cell, origin + (i + 1) * cell] in float32, one product and one sum, so neighbours share their face exactly; cell is a scalar or one edge
+    per axis."""
+    origin = np.broadcast_to(np.asarray(origin, dtype=np.float32), (3,))
+    cell = np.broadcast_to(np.asarray(cell, dtype=np.float32), (3,))
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or min(shape) < 0:
+        raise ValueError(f"voxel_boxes: a shape (nx, ny, nz) is needed, got {shape}")
+    index = np.stack(np.meshgrid(*[np.arange(s, dtype=np.float32) for s in shape], indexing="ij"), axis=-1).reshape(-1, 3)
+    return origin + index * cell, origin + (index + np.float32(1)) * cell
+
+
 def crossing_rays(points):
     """(org[3n, 3], dir[3n, 3]) float32: the rays RVPT.inside asks, ray 3 i + j leaving point i along INSIDE_DIRECTIONS[j]"""
     points = np.asarray(points, dtype=np.float32).reshape(-1, 3)
@@ -519,6 +532,54 @@ class RVPT:
         if self._ctx is None:
             raise RuntimeError("count_crossings before initialize()")
         return self._ctx.count_crossings(org, dir, tmax)
+
+    def box_overlaps(self, lo, hi, prim_from=0, k=1) -> np.ndarray:
+        """Box queries against the scene as it is now (Context.box_overlaps; include/rvpt_hip.h: BOX OVERLAPS): how many triangles meet each closed box
+        [lo[n, 3], hi[n, 3]] and the 4k - 1 smallest of their numbers.  Returns native.BOX_OVERLAP_DTYPE[n, k] (native.box_overlap_lists reads a group's count
+        and list).  The listed numbers name the triangles in the order they were ADDED, as trace_rays does; over a host-built tree the library orders, cuts and
+        compares with prim_from by the STORED number, before this renumbering, so there a list is not ascending and prim_from is a stored number — overlapping()
+        pages for the caller and returns whole, sorted lists.  Needs initialize(), not update()."""
+        if self._ctx is None:
+            raise RuntimeError("box_overlaps before initialize()")
+        rec = self._ctx.box_overlaps(lo, hi, prim_from, k)
+        if not self._device_built and rec.shape[0]:  # a host-built tree: the device numbers the leaf order it was given
+            quads = rec.view(np.uint32).reshape(rec.shape[0], int(k), 12)[:, :, 8:]
+            hit = quads != native.NO_PRIM
+            hit[:, 0, 0] = False  # (a group's first word is its count, not a number)
+            quads[hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[quads[hit]]
+        return rec
+
+    def overlapping(self, lo, hi) -> list:
+        """For every closed box [lo[n, 3], hi[n, 3]] the numbers of ALL triangles that meet it (BOX OVERLAPS: the set A with prim_from = 0), ascending, in the
+        order the triangles were ADDED: a list of n uint32 arrays.  Pages with the longest groups (15 numbers a call) and prim_from = the last listed number + 1
+        until every box has count numbers in hand; only the boxes that still have some to come are asked again.  Needs initialize(), not update()."""
+        if self._ctx is None:
+            raise RuntimeError("overlapping before initialize()")
+        lo, hi = np.asarray(lo, dtype=np.float32).reshape(-1, 3), np.asarray(hi, dtype=np.float32).reshape(-1, 3)
+        k = native.BOX_MAX_GROUP
+        parts = [[] for _ in range(lo.shape[0])]
+        ask, first = np.arange(lo.shape[0]), np.zeros(lo.shape[0], dtype=np.uint32)
+        while ask.size:
+            count, numbers = native.box_overlap_lists(self._ctx.box_overlaps(lo[ask], hi[ask], first, k), k)
+            for row, box in enumerate(ask):
+                parts[box].append(numbers[row][numbers[row] != native.NO_PRIM])
+            more = count > numbers.shape[1]  # the list is full and there is more to come
+            ask, first = ask[more], (numbers[more, -1] + np.uint32(1)).astype(np.uint32)
+        out = [np.concatenate(p) if p else np.zeros(0, np.uint32) for p in parts]
+        if not self._device_built and self._n_triangles:  # a host-built tree: stored numbers -> the order the triangles were added
+            added = np.asarray(self.primitive_indices, dtype=np.uint32)
+            out = [np.sort(added[o]) for o in out]
+        return out
+
+    def voxelize(self, origin, cell, shape) -> np.ndarray:
+        """bool[nx, ny, nz]: the conservative SURFACE voxelisation of the mesh as it now stands — cell (i, j, k) of the grid voxel_boxes(origin, cell, shape)
+        is set iff a box query counts at least one triangle meeting the closed cell, so a sliver between two cell centres still marks its cells (inside() only
+        classifies points).  One box per cell, one call.  Needs initialize(), not update()."""
+        if self._ctx is None:
+            raise RuntimeError("voxelize before initialize()")
+        lo, hi = voxel_boxes(origin, cell, shape)
+        rec = self._ctx.box_overlaps(lo, hi)
+        return (rec["count"][:, 0] > 0).reshape(tuple(int(s) for s in shape))
 
     def inside(self, points, rule="winding") -> np.ndarray:
         """bool[n]: whether each point of points[n, 3] lies inside the mesh as it is now.  Three rays leave every point along the three fixed directions

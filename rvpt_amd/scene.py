@@ -853,6 +853,89 @@ def closest_points_k(tris, points, k: int, max_d2=np.inf, chunk: int = 1 << 20) 
     return rec
 
 
+BOX_OVERLAP_DTYPE = np.dtype([("lo", "<f4", (3,)), ("prim_from", "<u4"), ("hi", "<f4", (3,)), ("flags", "<u4"), ("count", "<u4"),
+                              ("prim", "<u4", (3,))])  # rvpt_box_overlap (== native.BOX_OVERLAP_DTYPE)
+BOX_MAX_GROUP = 4  # == RVPT_HIP_BOX_MAX_GROUP
+
+
+def triangle_box_overlaps(tris, lo, hi) -> np.ndarray:
+    """THE TEST of a BOX QUERY (include/rvpt_hip.h: BOX OVERLAPS), vectorised: which triangles of `tris` (float32[n, 16] rows, or [n, 3, 3] vertices) meet the
+    closed boxes [lo, hi] (float32[3] or [m, 3] each).  The rounded separating-axis test over 13 axes, every operation in np.float32 and rounded on its own (numpy
+    never fuses); every comparison is a rejection — "min(p) > r" is written as all three above r — so a NaN rejects nothing; a triangle with a non-finite vertex
+    component never passes.  The boxes are taken as they are: whether a record is valid is box_overlaps' business.  Returns bool[m, n] (bool[n] for one box)."""
+    t = np.asarray(tris, dtype=np.float32)
+    verts = t.reshape(-1, 4, 4)[:, :3, :3] if t.ndim == 2 and t.shape[1] == 16 else t.reshape(-1, 3, 3)
+    lo, hi = np.asarray(lo, dtype=np.float32), np.asarray(hi, dtype=np.float32)
+    single = lo.ndim == 1
+    lo, hi = lo.reshape(-1, 1, 3), hi.reshape(-1, 1, 3)  # [m, 1, 3] against [n, 3]
+    a, b, c = verts[:, 0], verts[:, 1], verts[:, 2]
+    half = np.float32(0.5)
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(verts).all(axis=(1, 2))
+        # 1. boxes: comparisons only
+        apart = (((a > hi) & (b > hi) & (c > hi)) | ((a < lo) & (b < lo) & (c < lo))).any(axis=-1)
+        # 2. set-up
+        ctr = lo * half + hi * half
+        h = hi - ctr
+        v = [a - ctr, b - ctr, c - ctr]
+        e = [b - a, c - b, a - c]
+        # 3. the plane
+        x, y = b - a, c - a
+        n = np.stack([x[:, 1] * y[:, 2] - x[:, 2] * y[:, 1], x[:, 2] * y[:, 0] - x[:, 0] * y[:, 2], x[:, 0] * y[:, 1] - x[:, 1] * y[:, 0]], axis=-1)
+        up = n > 0
+        vmin, vmax = np.where(up, -h - v[0], h - v[0]), np.where(up, h - v[0], -h - v[0])
+        n_ = np.broadcast_to(n, vmin.shape)
+        apart = apart | (_dot_rounded(n_, vmin) > 0) | (_dot_rounded(n_, vmax) < 0)
+        # 4. the nine edge axes
+        for ei in e:
+            for j in range(3):
+                k1, k2 = (j + 1) % 3, (j + 2) % 3
+                p = [ei[:, k1] * vm[..., k2] - ei[:, k2] * vm[..., k1] for vm in v]
+                r = h[..., k1] * np.abs(ei[:, k2]) + h[..., k2] * np.abs(ei[:, k1])
+                assert p[0].dtype == np.float32 and r.dtype == np.float32
+                apart = apart | ((p[0] > r) & (p[1] > r) & (p[2] > r)) | ((p[0] < -r) & (p[1] < -r) & (p[2] < -r))
+    meets = finite & ~apart
+    return meets[0] if single else meets
+
+
+def box_overlaps(tris, records, k: int = 1, perm=None, chunk: int = 1 << 22) -> np.ndarray:
+    """The normative statement of a BOX QUERY (include/rvpt_hip.h: BOX OVERLAPS), by brute force.  `records` holds n groups of k BOX_OVERLAP_DTYPE records (flat
+    or [n, k]); record 0 of a group carries the box and prim_from.  A is every triangle of `tris` (float32[m, 16], stored order) that passes
+    triangle_box_overlaps and whose reported number — its index, or perm[index] with a permutation — is >= prim_from; count = |A| goes to record 0's count, the
+    4k - 1 smallest reported numbers, ascending, to the prim slots of record 0 and then to the whole out quads of records 1 .. k - 1, 0xFFFFFFFF from the first
+    slot A does not fill.  A record 0 with a non-finite corner or lo > hi on some axis, and every record of the empty scene, gets count 0 and every slot
+    0xFFFFFFFF.  Returns a copy of `records`, same shape, with the out quads written and every in quad — the followers' included — as it came."""
+    k = int(k)
+    if not 1 <= k <= BOX_MAX_GROUP:
+        raise ValueError(f"k must be 1 .. {BOX_MAX_GROUP}, got {k}")
+    rec = np.asarray(records)
+    if rec.dtype != BOX_OVERLAP_DTYPE or rec.size % k:
+        raise ValueError(f"box_overlaps: BOX_OVERLAP_DTYPE records in groups of {k} are needed, got {rec.dtype} x {rec.size}")
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    out = np.ascontiguousarray(rec).copy()
+    g = out.reshape(-1, k)
+    n, m, slots = g.shape[0], t.shape[0], 4 * k - 1
+    number = np.arange(m, dtype=np.uint32) if perm is None else np.asarray(perm, dtype=np.uint32).reshape(m)
+    lo, hi, prim_from = g["lo"][:, 0], g["hi"][:, 0], g["prim_from"][:, 0]
+    with np.errstate(all="ignore"):
+        valid = np.isfinite(lo).all(axis=1) & np.isfinite(hi).all(axis=1) & (lo <= hi).all(axis=1)
+    quads = np.full((n, 4 * k), NO_PRIM, dtype=np.uint32)
+    quads[:, 0] = 0
+    rows = np.flatnonzero(valid)
+    order = np.argsort(number, kind="stable")
+    step = max(1, chunk // max(m, 1))
+    for at in range(0, rows.size if m else 0, step):
+        sel = rows[at:at + step]
+        member = triangle_box_overlaps(t, lo[sel], hi[sel]) & (number[None, :] >= prim_from[sel, None])
+        quads[sel, 0] = member.sum(axis=1)
+        by_number = member[:, order]  # columns in ascending reported number
+        for row, box in enumerate(sel):
+            listed = number[order[np.flatnonzero(by_number[row])[:slots]]]
+            quads[box, 1:1 + listed.size] = listed
+    out.view(np.uint32).reshape(n, k, 12)[:, :, 8:] = quads.reshape(n, k, 4)
+    return out
+
+
 SURFACE_POINT_DTYPE =np.dtype([("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("mat", "<u4"), ("normal", "<f4", (3,)),
                                 ("reserved", "<u4")])  # rvpt_surface_point (== native.SURFACE_POINT_DTYPE)
 _LIBM_FMAF = None

@@ -1015,7 +1015,8 @@ int rvpt_hip_get_launch_info(rvpt_hip_ctx *ctx, uint32_t *grid_blocks, uint32_t 
  * a cull compiled out: fewer registers to keep alive), bit 7 = the batched launch that claims only the blocks that are not sky, bit 8 = the row boxes of bounce
  * packets whose rays leave one triangle (with the leaf boxes; RVPT_HIP_PACKETS_BOX_CULL=0 switches both off), bit 9 = that batched launch
  * (of 16 frames or more) runs each block's frames back to back in groups of 16 and makes the block's camera set-up once per run, bit 10 = the row boxes
- * of bit 8 were made by the tight rule (rvpt_amd/csrc/rvpt_vis.h; always, in this library: the laboratory build can make round 8's tables instead).  0 for
+ * of bit 8 were made by the tight rule (rvpt_amd/csrc/rvpt_vis.h; always, in this library: the laboratory build can make round 8's tables instead), bit 11 =
+ * those packets ride with finite row caps: a round whose rays all rise above their row's cap walks nothing (rvpt_vis.h; always, in this library).  0 for
  * every other kernel.  The image never depends on these; tools/fuzz_culls.py records them. */
 int rvpt_hip_get_cull_info(rvpt_hip_ctx *ctx, uint32_t *flags);
 

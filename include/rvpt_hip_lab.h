@@ -5,7 +5,7 @@
  *   - diagnostics of the arithmetic specification and of the packet kernel's exact culls (rvpt_hip_selftest_*),
  *   - the host-side forms of data the kernels consume, GPU-free (rvpt_camera_rects, rvpt_bounce_rows, rvpt_claim_order, rvpt_bvh_wide_form),
  *   - the tuning knobs the sweeps of rounds 1-5 found flat (RVPT_HIP_BVH_WIDE, _WIDE_RESIDENT, _NO_RESIDENT, _NO_PACKED_HEADS, _CALLER_LAYOUT, _TOP_NODES,
- *     _STACK_LDS, _REFILL, _LEAF_BATCH, _CAM_MIN, _DETACH, _FORCE_STACK_LEVELS, RVPT_HIP_BRUTE_PACKETS, RVPT_HIP_PACKETS_LEAN_INSTANCE, RVPT_HIP_PACKETS_ROW_BOXES, RVPT_HIP_PACKETS_ROW_RULE (read at upload_scene), _BLOCKS_PER_CU, _FIRST_UNITS, _CLAIM_UNITS,
+ *     _STACK_LDS, _REFILL, _LEAF_BATCH, _CAM_MIN, _DETACH, _FORCE_STACK_LEVELS, RVPT_HIP_BRUTE_PACKETS, RVPT_HIP_PACKETS_LEAN_INSTANCE, RVPT_HIP_PACKETS_ROW_BOXES, RVPT_HIP_PACKETS_ROW_RULE and RVPT_HIP_PACKETS_ROW_CAPS (read at upload_scene), _BLOCKS_PER_CU, _FIRST_UNITS, _CLAIM_UNITS,
  *     RVPT_HIP_TIMELINE): the release library reads none of them,
  *   - the kernels' internal checks (RVPT_HIP_DEBUG=1: a traversal-stack overflow is reported by rvpt_hip_wait).
  * rvpt_hip_build_flags() tells the two builds apart.  The release library reads: RVPT_HIP_QUIET, RVPT_HIP_DEBUG (refused without the checks),
@@ -55,7 +55,8 @@ int rvpt_hip_selftest_pretest(int device_id, const float *a, const float *den, c
  * (rvpt_amd/csrc/rvpt_vis.h; RVPT_HIP_PACKETS_BOX_CULL=0 switches them off): out[4] = accepted pairs whose ray fails the slab test of the triangle's leaf box (the
  * claim: 0), out[5] / out[6] = (segment, leaf box) pairs tested / passed; the row boxes of packets that leave one triangle (rvpt_vis.h; off with the leaf boxes, or alone with
  * RVPT_HIP_PACKETS_ROW_BOXES=0 in this build): out[7] = accepted pairs whose bit is cleared in the refined row of where the segment leaves from or whose ray fails
- * the slab test of that row's box of the triangle's leaf (the claim: 0). */
+ * the slab test of that row's box of the triangle's leaf, or whose segment the row cap of where it leaves from declares out of reach (rvpt_vis.h: the row caps;
+ * RVPT_HIP_PACKETS_ROW_CAPS=0 at upload_scene makes every cap +inf) (the claim: 0). */
 int rvpt_hip_selftest_bounce_cull(rvpt_hip_ctx *ctx, uint32_t n_samples, uint64_t out[8]);
 /* selftest_fast_div (ABI 6, host only, no GPU): q[i] = x[i] / divisor through the multiply-high form the frame kernels use to turn a claimed work index into
  * (frame, tile, pixel) (rvpt_kernels.h: FastDiv) — must equal the integer quotient for every x and every divisor >= 1. */

@@ -149,12 +149,13 @@ HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selft
                 "host_selftest_nearest": ["host_selftest_nearest.cpp", "rvpt_host.cpp"],
                 "host_selftest_surface": ["host_selftest_surface.cpp", "rvpt_host.cpp"],
                 "host_row_boxes": ["host_row_boxes.cpp"],  # (rvpt_vis.h alone: the row boxes' table for scenes given in files, tests/test_row_boxes.py)
+                "host_row_caps": ["host_row_caps.cpp"],  # (rvpt_vis.h alone: the row caps' table for scenes given in files, tests/test_row_caps.py)
                 "host_frame_runs": ["host_frame_runs.cpp"],  # (rvpt_packets.h alone: the item map of listed launches in frame-run order, tests/test_frame_runs_host.py)
                 "host_scene_forms": ["host_scene_forms.cpp"]}  # (rvpt_scene_forms.h alone: which form of upload_scene a call is, tests/test_scene_forms_host.py)
 HOST_NEEDS_HIP = {"host_selftest_frames", "host_selftest_box", "host_selftest_rays", "host_selftest_multi_hit", "host_selftest_nearest_k", "host_selftest_crossings", "host_selftest_paths", "host_selftest_path_modes", "host_selftest_nearest", "host_selftest_surface"}  # targets that allocate device memory themselves (its `--gpu` case): HIP's host API, still compiled by g++
 
 
-HOST_WITH_HIPCC = {"host_row_boxes", "host_frame_runs", "host_scene_forms"}  # targets that include the kernels' host + device headers (csrc/): the host half of a HIP compilation, no device code, no library
+HOST_WITH_HIPCC = {"host_row_boxes", "host_row_caps", "host_frame_runs", "host_scene_forms"}  # targets that include the kernels' host + device headers (csrc/): the host half of a HIP compilation, no device code, no library
 
 
 def hipcc_host_cmd(sources, out, extra=()) -> list:

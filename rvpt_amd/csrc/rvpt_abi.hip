@@ -275,6 +275,7 @@ bool has_global_stack(Variant v) { return v == Variant::Bvh || v == Variant::Wid
 constexpr uint32_t kCullRects = 1u, kCullBounce = 2u, kCullBlockRounds = 4u, kCullLeafBoxes = 16u, kCullClaimOrder = 32u, kCullLeanInstance = 64u, kCullSkyList = 128u;
 constexpr uint32_t kCullRowBoxes = 256u;
 constexpr uint32_t kCullFrameRuns = 512u;  // ... and the listed launch in frame-run order with run headers (trace_brute_packets_aa1_culls_listed_runs)
+constexpr uint32_t kCullRowCaps = 2048u;  // ... and with finite row caps: uniform rounds whose rays all rise above their row's cap walk nothing (rvpt_vis.h: the row caps)
 constexpr uint32_t kCullRowRuleTight = 1024u;  // ... and the row boxes it rode with were made by the tight rule (rvpt_vis.h: kRowRuleTight)
 
 struct Launch {
@@ -567,7 +568,7 @@ int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, i
             p.vis_words = ctx->vis_words;
             p.vis_stride = (ctx->vis_words + 3u) & ~3u;
             if (k.packets_box_cull && ctx->d_leaf_boxes) p.leaf_boxes = ctx->d_leaf_boxes;
-            if (p.leaf_boxes && k.packets_row_boxes && ctx->have_row_boxes) p.row_bits = ctx->d_row_bits, p.row_boxes = ctx->d_row_boxes;
+            if (p.leaf_boxes && k.packets_row_boxes && ctx->have_row_boxes) p.row_bits = ctx->d_row_bits, p.row_boxes = ctx->d_row_boxes, p.row_caps = ctx->d_row_caps;
         }
     }
     if (bvh && k.force_stack_levels > 0) {  // tests: a stack smaller than the tree needs — the kernels clamp and report (RVPT_HIP_DEBUG)
@@ -663,7 +664,7 @@ int choose_launch(rvpt_hip_ctx *ctx, rv::FrameParams &p, bool lone, int slots, i
     l.cull_bits = (cull ? kCullRects : 0u) | (p.vis ? kCullBounce : 0u) | ((v == Variant::BrutePackets && p.first_units % 4u == 0u) ? kCullBlockRounds : 0u) |
                   (p.leaf_boxes ? kCullLeafBoxes : 0u) | (p.perm_groups != 0u ? kCullClaimOrder : 0u) | (lean ? kCullLeanInstance : 0u) | (l.listed ? kCullSkyList : 0u) |
                   (p.row_boxes ? kCullRowBoxes : 0u) | ((l.listed && l.work.run_frames != 0u) ? kCullFrameRuns : 0u) |
-                  ((p.row_boxes && ctx->row_rule_tight) ? kCullRowRuleTight : 0u);
+                  ((p.row_boxes && ctx->row_rule_tight) ? kCullRowRuleTight : 0u) | ((p.row_boxes && ctx->row_caps_on) ? kCullRowCaps : 0u);
     return 0;
 }
 
@@ -801,6 +802,7 @@ void rvpt_hip_destroy(rvpt_hip_ctx *ctx)
     if (ctx->d_leaf_boxes) (void)hipFree(ctx->d_leaf_boxes);
     if (ctx->d_row_bits) (void)hipFree(ctx->d_row_bits);
     if (ctx->d_row_boxes) (void)hipFree(ctx->d_row_boxes);
+    if (ctx->d_row_caps) (void)hipFree(ctx->d_row_caps);
     if (ctx->d_gather) (void)hipFree(ctx->d_gather);
     if (ctx->d_barrier) (void)hipFree(ctx->d_barrier);
     if (ctx->d_quant) (void)hipFree(ctx->d_quant);
@@ -1831,7 +1833,7 @@ int rvpt_hip_selftest_bounce_cull(rvpt_hip_ctx *ctx, uint32_t n_samples, uint64_
     p.vis_words = ctx->vis_words;
     p.vis_stride = (ctx->vis_words + 3u) & ~3u;
     p.leaf_boxes = ctx->d_leaf_boxes;
-    if (ctx->have_row_boxes) p.row_bits = ctx->d_row_bits, p.row_boxes = ctx->d_row_boxes;
+    if (ctx->have_row_boxes) p.row_bits = ctx->d_row_bits, p.row_boxes = ctx->d_row_boxes, p.row_caps = ctx->d_row_caps;
     unsigned long long *d_out = nullptr;
     unsigned long long h_out[6] = {};
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&d_out), 6 * sizeof(unsigned long long)));

@@ -174,7 +174,10 @@ struct rvpt_hip_ctx {
     size_t row_bits_cap = 0;                  // in words
     float4 *d_row_boxes = nullptr;            // ... and every row's own boxes, two float4 per leaf, 32 / kLeafTris * vis_words leaves per row
     size_t row_boxes_cap = 0;                 // in float4
-    bool have_row_boxes = false;              // made for the scene in d_prep
+    float4 *d_row_caps = nullptr;             // ... and every row's cap (rvpt_vis.h: the row caps), one float4 per row, made behind the row boxes
+    size_t row_caps_cap = 0;                  // in float4
+    bool row_caps_on = false;                 // ... with finite caps (the laboratory build's RVPT_HIP_PACKETS_ROW_CAPS=0: every K = +inf, no round skips)
+    bool have_row_boxes = false;              // made for the scene in d_prep (row boxes and row caps)
     bool row_rule_tight = false;              // ... with the tight rule (rvpt_vis.h: kRowRuleTight; the laboratory build's RVPT_HIP_PACKETS_ROW_RULE=0: round 8's rule)
     uint32_t vis_words = 0;                   // 0: no table for this scene
     double scene_scale = 0.0;                 // largest |coordinate| + largest extent of the uploaded triangles: what float errors of positions scale with

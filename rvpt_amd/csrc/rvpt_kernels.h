@@ -153,6 +153,8 @@ struct FrameParams {
     const uint32_t *row_bits; // packet kernel (with leaf_boxes): the REFINED rows — vis' layout and stride; bit B of row 2 A + s = B is in the row and has a part above H0 over
                               // A's plane on side s (rvpt_vis.h: bounce_row_boxes_word) — read with scalar loads by packets whose rays all leave one triangle.  nullptr = off
     const float4 *row_boxes;  // ... and that row's own boxes, two float4 per leaf as leaf_boxes, 32 / kLeafTris * vis_words leaves per row: the parts above H0 only
+    const float4 *row_caps;   // ... and the row caps, one float4 per row (set whenever row_boxes is): (the leaving triangle's float unit normal turned to the leaving side, K) — a
+                              // ray with dot(d, normal) > 0 and dot^2 > K |d|^2 reaches no member of the row (rvpt_vis.h: bounce_row_caps_row); K = +inf: no cap
     uint32_t bvh_cam_min;     // camera packets (trace_bvh4_resident): at least this many lanes must start a camera ray at once to walk as a packet
     uint32_t bvh_detach;      // ... and the lanes of a node leave the packet (go on per lane) when at most this many of them are in it
     // work distribution plan (units of kUnit work indices, see WavePool): wave w owns units

@@ -75,11 +75,16 @@ __global__ void bounce_visibility(const float4 *__restrict__ prep, uint32_t n, d
 // tight != 0: the tight rule (kRowRuleTight), 0: round 8's (kRowRuleShipped)
 __global__ void bounce_row_boxes(const float4 *__restrict__ prep, uint32_t n, double scale, uint32_t words, uint32_t stride, const float *__restrict__ leaf_boxes,
                                  uint32_t *__restrict__ refined, float *__restrict__ boxes, uint32_t tight);
+// the row caps of the same table (rvpt_vis.h: bounce_row_caps_row): caps[2 A + s] = (unit_n[A] turned to side s, K_row); enabled == 0: every K = +inf (no round skips);
+// one thread per row
+__global__ void bounce_row_caps(const float4 *__restrict__ prep, const float4 *__restrict__ unit_n, uint32_t n, double scale, uint32_t words, uint32_t enabled,
+                                float4 *__restrict__ caps);
 #if RVPT_HIP_LAB
 // diagnostics (rvpt_hip_selftest_bounce_cull): every pixel x n_samples paths traced against EVERY triangle; on segments that leave a triangle, out[0] += pairs the
 // float test accepts with the interval wide open, out[1] += those whose triangle is NOT in the row of where the segment leaves from (must stay 0), out[2] += those whose
 // ray fails the slab test of the triangle's leaf box (must stay 0), out[3] / out[4] += (ray, leaf box) pairs tested / passed, out[5] += those whose bit is cleared in
-// the refined row of where the segment leaves from or whose ray fails the slab test of that row's box of the triangle's leaf (row boxes; must stay 0)
+// the refined row of where the segment leaves from, whose ray fails the slab test of that row's box of the triangle's leaf, or whose segment the row cap of where it
+// leaves from declares out of reach (row boxes and row caps; must stay 0)
 __global__ void selftest_bounce_cull(const FrameParams p, uint32_t n_samples, unsigned long long *__restrict__ out);
 // diagnostics (rvpt_hip_selftest_camera_rects): every pixel of the image x n_samples jittered camera rays x every triangle through the float test with
 // an open interval; out[0] += accepted pairs, out[1] += accepted pairs whose block lies OUTSIDE the triangle's rectangle (must stay 0),

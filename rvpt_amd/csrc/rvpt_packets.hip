@@ -167,7 +167,7 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
     uint64_t hdr_todo[3] = {0, 0, 0};
     // optional timeline (RVPT_HIP_TIMELINE): [0] start [1] pool dry [2] end (100 MHz wall clock) [3] camera rounds | bounce rounds << 32 [4] split rounds | lane-rounds << 32
     unsigned long long t_start = 0, t_dry = 0;
-    uint32_t n_cam = 0, n_bounce = 0, n_split = 0, lane_rounds = 0, n_listed = 0, n_uniform = 0;  // [5] triangles walked by the culled bounce rounds | those of them that took the row boxes << 32
+    uint32_t n_cam = 0, n_bounce = 0, n_split = 0, lane_rounds = 0, n_listed = 0, n_uniform = 0, n_skipped = 0;  // [5] triangles walked by the culled bounce rounds | those of them that took the row boxes << 32
     uint32_t n_after_dry = 0, lanes_after_dry = 0;  // [6] rounds | lane-rounds << 32 after the pool ran dry for this wave; [7] the wave's last camera round (clock)
     unsigned long long t_last_cam = 0;
     if (RV_PACKETS_TIMELINE && p.timeline) t_start = wall_clock64();
@@ -385,7 +385,6 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
             const bool boxes = CULLS || p.leaf_boxes != nullptr;
             typedef const __attribute__((address_space(4))) float *ConstFloats;
             const ConstFloats leaf_boxes_k = (ConstFloats)(reinterpret_cast<uintptr_t>(p.leaf_boxes));
-            const LeafRay lr = leaf_ray(L.o, L.d);
             const bool vote_all = has && leave == 0xFFFFFFFFu;
             const bool own_row = has && leave != 0xFFFFFFFFu;
             constexpr uint32_t kPerWord = 32u / kLeafTris, kMask = (1u << kLeafTris) - 1u;
@@ -404,57 +403,73 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
             const ConstRowWords row_bits_k = (ConstRowWords)(reinterpret_cast<uintptr_t>(p.row_bits)) + static_cast<size_t>(uni ? uni_row : 0u) * p.vis_stride;
             const ConstFloats boxes_k = uni ? (ConstFloats)(reinterpret_cast<uintptr_t>(p.row_boxes)) + static_cast<size_t>(uni_row) * (8u * kPerWord * p.vis_words) : leaf_boxes_k;
             if (RV_PACKETS_TIMELINE && p.timeline) n_uniform += uni ? 1u : 0u;
-            // What a bounce round WAITS for (the per-phase clocks of tools/packets_timeline.py: the culls took a quarter of a wave's time, more than the triangle tests they
-            // leave): a row word per 32 triangles and a box per leaf, each a load the next step depended on.  So: FOUR words of the lane's row in one 16-byte load (rows
-            // are 16-byte aligned, a multiple of four words apart, zero padded: vis_stride), the four wave-wide ORs back to back, and a word's boxes in ONE scalar request
-            // (contiguous: 32 B x kPerWord) before any of them is tested.
-            for (uint32_t w0 = 0; w0 < p.vis_words; w0 += 4u) {
-                uint32_t m[4];
-                if (uni) {  // (wave-uniform) four words of the refined row: one scalar request (rows are 16-byte aligned, zero padded)
+            // The ROW CAPS (rvpt_vis.h): row_caps[row] = (the float unit normal of the leaving triangle turned to the leaving side, K).  A lane whose direction rises
+            // over the leaving plane with sin^2 of the elevation above K is out of reach of every member of its row; when every ray of a uniform round is, the round
+            // walks nothing — no reciprocals, no row words, no boxes — and goes to shade with the miss the walk would have found.  One scalar request, some ten VALU.
+            bool skip = false;
+            if (uni) {
+                typedef const __attribute__((address_space(4))) v4f *ConstCaps;
+                const v4f cap = ((ConstCaps)(reinterpret_cast<uintptr_t>(p.row_caps)))[uni_row];
+                const float c = dot(L.d, mk(cap.x, cap.y, cap.z)), dd = dot(L.d, L.d);
+                const bool low = !(c > 0.0f && c * c > cap.w * dd);  // (NaN: low)
+                skip = ballot(has && low) == 0;
+                if (RV_PACKETS_TIMELINE && p.timeline) n_skipped += skip ? 1u : 0u;
+            }
+            if (!skip) {
+                const LeafRay lr = leaf_ray(L.o, L.d);
+                // What a bounce round WAITS for (the per-phase clocks of tools/packets_timeline.py: the culls took a quarter of a wave's time, more than the triangle tests they
+                // leave): a row word per 32 triangles and a box per leaf, each a load the next step depended on.  So: FOUR words of the lane's row in one 16-byte load (rows
+                // are 16-byte aligned, a multiple of four words apart, zero padded: vis_stride), the four wave-wide ORs back to back, and a word's boxes in ONE scalar request
+                // (contiguous: 32 B x kPerWord) before any of them is tested.
+                for (uint32_t w0 = 0; w0 < p.vis_words; w0 += 4u) {
+                    uint32_t m[4];
+                    if (uni) {  // (wave-uniform) four words of the refined row: one scalar request (rows are 16-byte aligned, zero padded)
 #pragma unroll
-                    for (uint32_t j = 0; j < 4u; ++j) m[j] = row_bits_k[w0 + j];
-                } else {
-                    uint4 r = make_uint4(0u, 0u, 0u, 0u);
-                    if (own_row) r = *reinterpret_cast<const uint4 *>(row + w0);
-                    if (vote_all) r = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-                    // (all four even where the scene has fewer words — 143 triangles are five: four and one —: four independent DPP chains overlap, three branches
-                    // around them measured 3 % slower)
-                    m[0] = wave_or(r.x), m[1] = wave_or(r.y), m[2] = wave_or(r.z), m[3] = wave_or(r.w);
-                }
-                RV_PHASE(4)
+                        for (uint32_t j = 0; j < 4u; ++j) m[j] = row_bits_k[w0 + j];
+                    } else {
+                        uint4 r = make_uint4(0u, 0u, 0u, 0u);
+                        if (own_row) r = *reinterpret_cast<const uint4 *>(row + w0);
+                        if (vote_all) r = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+                        // (all four even where the scene has fewer words — 143 triangles are five: four and one —: four independent DPP chains overlap, three branches
+                        // around them measured 3 % slower)
+                        m[0] = wave_or(r.x), m[1] = wave_or(r.y), m[2] = wave_or(r.z), m[3] = wave_or(r.w);
+                    }
+                    RV_PHASE(4)
 #pragma unroll
-                for (uint32_t j = 0; j < 4u; ++j) {
-                    const uint32_t w = w0 + j;
-                    if (w >= p.vis_words) break;
-                    uint32_t todo = m[j];
-                    if (w + 1u == p.vis_words && (p.n_tris & 31u) != 0u) todo &= (1u << (p.n_tris & 31u)) - 1u;
-                    if (todo == 0u) continue;  // (wave-uniform)
-                    if (boxes) {
-                        // (through the constant address space: a wave-uniform address there is a SCALAR load from the scalar cache, boxes in SGPRs; as an ordinary global
-                        // pointer the compiler makes it a vector load behind the kernel's own stores)
+                    for (uint32_t j = 0; j < 4u; ++j) {
+                        const uint32_t w = w0 + j;
+                        if (w >= p.vis_words) break;
+                        uint32_t todo = m[j];
+                        if (w + 1u == p.vis_words && (p.n_tris & 31u) != 0u) todo &= (1u << (p.n_tris & 31u)) - 1u;
+                        if (todo == 0u) continue;  // (wave-uniform)
+                        if (boxes) {
+                            // (through the constant address space: a wave-uniform address there is a SCALAR load from the scalar cache, boxes in SGPRs; as an ordinary global
+                            // pointer the compiler makes it a vector load behind the kernel's own stores)
 #pragma unroll
-                        for (uint32_t k0 = 0; k0 < kPerWord; k0 += RV_BOX_BATCH) {
-                            if (((todo >> (kLeafTris * k0)) & kBatchMask) == 0u) continue;  // (wave-uniform)
-                            const ConstFloats b = boxes_k + 8u * (kPerWord * w + k0);
-                            float bb[8u * RV_BOX_BATCH];
+                            for (uint32_t k0 = 0; k0 < kPerWord; k0 += RV_BOX_BATCH) {
+                                if (((todo >> (kLeafTris * k0)) & kBatchMask) == 0u) continue;  // (wave-uniform)
+                                const ConstFloats b = boxes_k + 8u * (kPerWord * w + k0);
+                                float bb[8u * RV_BOX_BATCH];
 #pragma unroll
-                            for (uint32_t i = 0; i < 8u * RV_BOX_BATCH; ++i) bb[i] = ((i & 7u) < 6u) ? b[i] : 0.0f;
+                                for (uint32_t i = 0; i < 8u * RV_BOX_BATCH; ++i) bb[i] = ((i & 7u) < 6u) ? b[i] : 0.0f;
 #pragma unroll
-                            for (uint32_t k = k0; k < k0 + RV_BOX_BATCH; ++k) {
-                                if (((todo >> (kLeafTris * k)) & kMask) == 0u) continue;  // (wave-uniform)
-                                const uint32_t o8 = 8u * (k - k0);
-                                const float4 b0 = make_float4(bb[o8 + 0u], bb[o8 + 1u], bb[o8 + 2u], bb[o8 + 3u]), b1 = make_float4(bb[o8 + 4u], bb[o8 + 5u], 0.0f, 0.0f);
-                                const bool near = has && (vote_all || leaf_slab(lr, b0, b1));
-                                if (ballot(near) == 0) todo &= ~(kMask << (kLeafTris * k));
+                                for (uint32_t k = k0; k < k0 + RV_BOX_BATCH; ++k) {
+                                    if (((todo >> (kLeafTris * k)) & kMask) == 0u) continue;  // (wave-uniform)
+                                    const uint32_t o8 = 8u * (k - k0);
+                                    const float4 b0 = make_float4(bb[o8 + 0u], bb[o8 + 1u], bb[o8 + 2u], bb[o8 + 3u]), b1 = make_float4(bb[o8 + 4u], bb[o8 + 5u], 0.0f, 0.0f);
+                                    const bool near = has && (vote_all || leaf_slab(lr, b0, b1));
+                                    if (ballot(near) == 0) todo &= ~(kMask << (kLeafTris * k));
+                                }
                             }
                         }
+                        if (RV_PACKETS_TIMELINE && p.timeline) n_listed += static_cast<uint32_t>(__builtin_popcount(todo));
+                        RV_PHASE(4)
+                        if (has) intersect_listed(src, 32u * w, todo, L.o, L.d, closest, hit);
+                        RV_PHASE(5)
                     }
-                    if (RV_PACKETS_TIMELINE && p.timeline) n_listed += static_cast<uint32_t>(__builtin_popcount(todo));
-                    RV_PHASE(4)
-                    if (has) intersect_listed(src, 32u * w, todo, L.o, L.d, closest, hit);
-                    RV_PHASE(5)
                 }
             }
+            RV_PHASE(4)
         } else if (!CULLS && has) {
             if (camera_round)
                 intersect_run_camera(src, cam_records, 0u, p.n_tris, L.o, L.d, closest, hit);
@@ -497,6 +512,7 @@ __device__ __forceinline__ void packets_body(const FrameParams &p, const ListedW
     if (RV_PACKETS_TIMELINE && p.timeline && lane == 0) {
         unsigned long long *w = p.timeline + 8ull * p.n_waves + 8ull * wave_id;  // (second half of the rows)
         for (int k = 0; k < 8; ++k) w[k] = ph[k];
+        w[7] |= static_cast<unsigned long long>(n_skipped) << 32;  // ... and beside the last of them, the uniform bounce rounds that the row caps skipped
         unsigned long long *t = p.timeline + 8ull * wave_id;
         t[0] = t_start;
         t[1] = t_dry;
@@ -601,6 +617,20 @@ __global__ void bounce_row_boxes(const float4 *__restrict__ prep, uint32_t n, do
     constexpr uint32_t kPerWord = 32u / kLeafTris;
     refined[id] = bounce_row_boxes_word_rule(tight ? kRowRuleTight : kRowRuleShipped, reinterpret_cast<const float *>(prep), n, row, w, scale, leaf_boxes,
                                              boxes + 8u * (static_cast<size_t>(row) * kPerWord * words + kPerWord * w));
+}
+
+__global__ void bounce_row_caps(const float4 *__restrict__ prep, const float4 *__restrict__ unit_n, uint32_t n, double scale, uint32_t words, uint32_t enabled,
+                                float4 *__restrict__ caps)
+{
+    const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= 2u * n) return;
+    const float4 un = unit_n[row >> 1];
+    const float u[3] = {un.x, un.y, un.z};
+    const float side = (row & 1u) ? -1.0f : 1.0f;
+    float K = __builtin_inff();  // no cap: the round never skips
+    if (enabled && bounce_row_cap_normal_ok(reinterpret_cast<const float *>(prep), row >> 1, u))
+        K = bounce_row_caps_row(reinterpret_cast<const float *>(prep), n, row, words, scale, nullptr);
+    caps[row] = make_float4(side * un.x, side * un.y, side * un.z, K);
 }
 
 __global__ void camera_rects(const FrameParams p, uint2 *__restrict__ rects, float4 *__restrict__ records)
@@ -709,7 +739,11 @@ __global__ void selftest_bounce_cull(const FrameParams p, uint32_t n_samples, un
                             const uint32_t refined = p.row_bits[static_cast<size_t>(leave) * p.vis_stride + (j >> 5)];
                             const size_t box = static_cast<size_t>(leave) * (32u / kLeafTris) * p.vis_words + j / kLeafTris;
                             const bool in = ((refined >> (j & 31u)) & 1u) != 0u && leaf_slab(lr, p.row_boxes[2u * box + 0u], p.row_boxes[2u * box + 1u]);
-                            outside_row_box += in ? 0u : 1u;
+                            // ... and the row cap of where the segment leaves from does not declare the segment out of reach (the frame kernel's compare)
+                            const float4 cap = p.row_caps[leave];
+                            const float cn = dot(L.d, mk(cap.x, cap.y, cap.z)), dd = dot(L.d, L.d);
+                            const bool reach = !(cn > 0.0f && cn * cn > cap.w * dd);
+                            outside_row_box += (in && reach) ? 0u : 1u;
                         }
                     }
                     if (leave != 0xFFFFFFFFu && p.leaf_boxes != nullptr && (j % kLeafTris) == 0u) {  // how selective the boxes are, per ray

@@ -70,9 +70,18 @@ static int derive_bounce_state(rvpt_hip_ctx *ctx, bool bvh, const rvpt_triangle 
             hipLaunchKernelGGL(rv::bounce_row_boxes, dim3(static_cast<uint32_t>((total + 63) / 64)), dim3(64), 0, ctx->stream, ctx->d_prep, n, scale, words, stride,
                                reinterpret_cast<const float *>(ctx->d_leaf_boxes), ctx->d_row_bits, reinterpret_cast<float *>(ctx->d_row_boxes), tight ? 1u : 0u);
             HIP_TRY(ctx, hipGetLastError());
+            // ... and the row caps behind them (rvpt_vis.h), from the records and the hit normals
+            if ((rc = grow(ctx, ctx->d_row_caps, ctx->row_caps_cap, static_cast<size_t>(2) * n, sizeof(float4)))) return rc;
+            bool caps = true;
+#if RVPT_HIP_LAB
+            if (const char *e = getenv("RVPT_HIP_PACKETS_ROW_CAPS")) caps = atoi(e) > 0;  // read at every upload: 0 = every cap +inf, no round skips (A/B, bit-exactness)
+#endif
+            hipLaunchKernelGGL(rv::bounce_row_caps, dim3((2u * n + 63u) / 64u), dim3(64), 0, ctx->stream, ctx->d_prep, ctx->d_unit_n, n, scale, words, caps ? 1u : 0u, ctx->d_row_caps);
+            HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             ctx->have_row_boxes = true;
             ctx->row_rule_tight = tight;
+            ctx->row_caps_on = caps;
         }
     }
     return 0;

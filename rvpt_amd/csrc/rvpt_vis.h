@@ -281,4 +281,173 @@ RV_HD uint32_t bounce_row_boxes_word(const float *prep, const uint32_t n, const 
     return bounce_row_boxes_word_rule(kRowRuleShipped, prep, n, row, w, scale, leaf_boxes, boxes_out);
 }
 
+// ---- the ROW CAPS of the bounce rounds -------------------------------------------------------------------------------------------------------------------
+// What is left in the tight rows are mostly A's near-coplanar neighbours, a few degrees off A's plane.  To reach one a ray must leave A at a LOW ELEVATION, and a
+// Lambert direction seldom does: P(sin elevation < s) = s^2.  So every row 2 A + s gets one number K, an upper bound of sin^2 of the elevation over A's plane at
+// which a segment that leaves (A, s) can still be accepted by ANY member of the row, and a packet whose rays all leave (A, s) above it walks nothing at all.
+//
+// The cap.  n^ = A's exact unit normal turned to side s, height h(x) = dot(x - v0_A, n^) as above, eps, margin, E', E_B as above.  A segment whose `leave` names
+//   (A, s) starts at o with h(o) >= h_o = eps - 2^-13 scale - 2^-15 E', and every point of the exact ray with t > 0 that matters has height >= h_o (the row boxes'
+//   derivation: it needs `leave`'s premise that the ray does not descend by more than 2^-18 |d|).  The float test accepts (ray, B) only when a point Y = o + t d,
+//   t > 0, of the exact ray lies within E_B of a point X of B; so h(X) >= h_o - E_B and h(X) >= H0(B) (the tight rule's): X lies in
+//     P_B = B clipped at height >= max(H0(B), h_o - E_B)          (empty: no segment is accepted, cap 0).
+//   Rise:  t dot(d, n^) = h(Y) - h(o) <= h(X) + E_B - h_o.
+//   Run:   o projects within rho_A of triangle A.  o = fma3(N', +-eps, pos); pos is the float position of the accepted hit on A: the exact ray's point lies within
+//     E_A of a point of A (the float test's bound (33 eps / kappa_A)(t + S), rvpt_rect.h; the segment that hit A may be a camera ray, whose origin lies up to 64
+//     scales out under the launch-time premise: t |d| <= 113 scales, S <= 390 scales + the edges, so E_A = (33 eps / kappa_A)(512 E' + |e0|_1 + |e1|_1)), pos
+//     within 2^-13 scale of that point (the position error the table budgets under the same premise), the fma rounds coordinates <= E' (sqrt(3) 2^-24 E'), and eps N' leaves n^'s line by <= 2^-21 eps.  Projection onto A's
+//     plane is 1-Lipschitz:  rho_A = E_A + 2^-12 scale + 2^-20 E'  (twice the position term, more than eight times the others).  For an edge line k of A (through
+//     a_k, outward in-plane unit normal m_k, s_k(x) = dot(x - a_k, m_k) <= 0 on A):  s_k(o) <= rho_A, s_k(Y) >= s_k(X) - E_B, so
+//     t dot(d, m_k) >= s_k(X) - E_B - rho_A.
+//   Where that is > 0 at every vertex of P_B (edge k SEPARATES A from P_B), dot(d, n^) / dot(d, m_k) <= (h(X) + E_B - h_o) / (s_k(X) - E_B - rho_A), a ratio of two
+//   affine functions with a positive denominator over a convex polygon: largest at a vertex.  tan cap_B = min over separating k of max over the vertices; no such
+//   edge, or A or B failing a premise: +inf.  The premises are the row boxes' — finite, non-degenerate, kappa >= 2^-6, a scene that has a scale — without E_B <= 0.4 M:
+//   every step above takes E_B as it is, and the clip that counts, h_o - E_B, is proved here and not taken from the row (a member the tight rule keeps only because
+//   its E_B is large is clipped at its own, lower, height).  dot(d, m_k) <= sqrt(|d|^2 - dot(d, n^)^2), hence for an accepted pair
+//     dot(d, n^) <= 0   or   dot(d, n^)^2 <= sin^2(cap_B) |d|^2,          sin^2 = tan^2 / (1 + tan^2).
+// The float evaluation (rvpt_packets.hip): c = dot(d, sN') in float, sN' the float unit normal the table holds, dd = dot(d, d); a lane is OUT OF REACH when
+//   c > 0 && c * c > K * dd.  |sN' - n^| <= 2^-21 (bounce_row_cap_normal_ok checks it in double against the very floats, else K = +inf), the dot's three products
+//   and two sums carry <= 3 * 2^-24 |d| |N'|: |c - dot(d, n^)| <= 2^-20 |d|.  dd and the two products of the compare carry 2^-22 and 2^-24 relative.  So the compare
+//   implies dot(d, n^) > (sqrt(K) (1 - 2^-21) - 2^-20) |d|, which is >= sin(cap) |d| for sqrt(K) = max(sin(cap) (1 + 2^-20) + 2^-19, 2^-18); K goes up by 2^-22
+//   more before it is rounded to float (to nearest: 2^-24).  The floor keeps every lane with c <= 2^-18 |d| on the walk (what a descent by rounding looks like);
+//   |d|^2 >= 2^-16 for every direction `leave` vouches for, so neither product underflows; K = +inf says "no cap", and a NaN anywhere makes the compare false.
+// K_row = the largest K of the row's members, K_leaf the same per leaf of kLeafTris triangles.  The caps name no box and no refined bit: they hold for the table's
+// row (a member the tight rule drops has an empty P_B), whichever rule made the boxes.
+// Checked: tests/test_row_caps.py (float64 restatement, brute-force soundness, simulated paths; GPU-free), tests/test_row_caps_gpu.py (bit-exact frames against
+// K = +inf; rvpt_hip_selftest_bounce_cull out[7] counts accepted pairs the row cap declares out of reach: 0).
+constexpr double kRowCapFloor = 0x1p-18;  // of sqrt(K)
+
+RV_HD float bounce_row_cap_k(const double tan_cap)
+{
+    if (!(tan_cap < 1e300)) return __builtin_inff();  // (+inf or NaN: no cap)
+    const double s = tan_cap / __builtin_sqrt(1.0 + tan_cap * tan_cap);
+    double r = s * (1.0 + 0x1p-20) + 0x1p-19;
+    r = r > kRowCapFloor ? r : kRowCapFloor;
+    return static_cast<float>(r * r * (1.0 + 0x1p-22));
+}
+
+// is the float unit normal un (FrameParams::unit_n of A, not yet turned to the side) within 2^-21 of the exact one of A's record?
+RV_HD bool bounce_row_cap_normal_ok(const float *prep, const uint32_t A, const float *un)
+{
+    const float *a = prep + 16u * A;
+    const double an[3] = {a[3], a[4], a[5]};
+    const double nn = __builtin_sqrt(an[0] * an[0] + an[1] * an[1] + an[2] * an[2]);
+    double d2 = 0.0;
+    for (int c = 0; c < 3; ++c) d2 += (an[c] / nn - un[c]) * (an[c] / nn - un[c]);
+    return d2 <= 0x1p-42;  // (NaN: false)
+}
+
+// K_row of row 2 A + s (returned) and, where k_leaf is given, K_leaf of its 32 / kLeafTris * words leaves.  prep, n, scale: bounce_row_boxes_word_rule's
+RV_HD float bounce_row_caps_row(const float *prep, const uint32_t n, const uint32_t row, const uint32_t words, const double scale, float *k_leaf)
+{
+    constexpr uint32_t kPerWord = 32u / kLeafTris;
+    const double eps = static_cast<double>(kEpsilon);
+    const double margin = kBounceMarginScales * scale;
+    const double Es = scale + 2.0 * eps;
+    const double inf = static_cast<double>(__builtin_inff());
+    const uint32_t A = row >> 1;
+    const double side = (row & 1u) ? -1.0 : 1.0;
+    const float *a = prep + 16u * A;
+    const double av0[3] = {a[0], a[1], a[2]}, an[3] = {a[3], a[4], a[5]}, ae0[3] = {a[6], a[7], a[8]}, ae1[3] = {a[9], a[10], a[11]};
+    const double nn = __builtin_sqrt(an[0] * an[0] + an[1] * an[1] + an[2] * an[2]);
+    auto abs1 = [](const double *x) { return __builtin_fabs(x[0]) + __builtin_fabs(x[1]) + __builtin_fabs(x[2]); };
+    bool a_ok;
+    double rhoA;
+    {
+        const double a00 = ae1[0] * ae1[0] + ae1[1] * ae1[1] + ae1[2] * ae1[2], a11 = ae0[0] * ae0[0] + ae0[1] * ae0[1] + ae0[2] * ae0[2];
+        const double a01 = ae0[0] * ae1[0] + ae0[1] * ae1[1] + ae0[2] * ae1[2];
+        a_ok = (a00 * a11 - a01 * a01) >= 0x1p-6 * (a00 * a11) && a00 * a11 > 0.0 && nn > 0.0 && margin > 0.0;
+        for (int k = 0; k < 3; ++k) a_ok = a_ok && (av0[k] - av0[k] == 0.0) && (an[k] - an[k] == 0.0);
+        const double kappaA = (a00 * a11 - a01 * a01) / (a00 * a11);
+        const double EA = (33.0 * 0x1p-24 / kappaA) * (512.0 * Es + abs1(ae0) + abs1(ae1));  // (the segment that hit A may have come from the camera)
+        rhoA = EA + 0x1p-12 * scale + 0x1p-20 * Es;
+        a_ok = a_ok && (rhoA - rhoA == 0.0);
+    }
+    const double h_o = eps - 0x1p-13 * scale - 0x1p-15 * Es;
+    // A's three edge lines: a point a_k and the outward in-plane unit normal m_k
+    double ea[3][3], em[3][3];
+    for (int k = 0; k < 3; ++k) {
+        double pa[3], pb[3], pc[3];
+        for (int c = 0; c < 3; ++c) {
+            const double v[3] = {av0[c], av0[c] + ae0[c], av0[c] + ae1[c]};
+            pa[c] = v[k], pb[c] = v[k == 2 ? 0 : k + 1], pc[c] = v[k == 0 ? 2 : k - 1];
+        }
+        const double e[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]};
+        double m[3] = {e[1] * an[2] - e[2] * an[1], e[2] * an[0] - e[0] * an[2], e[0] * an[1] - e[1] * an[0]};
+        const double len = __builtin_sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+        a_ok = a_ok && len > 0.0 && (len - len == 0.0);
+        const double inward = (pc[0] - pa[0]) * m[0] + (pc[1] - pa[1]) * m[1] + (pc[2] - pa[2]) * m[2];
+        for (int c = 0; c < 3; ++c) ea[k][c] = pa[c], em[k][c] = (inward > 0.0 ? -m[c] : m[c]) / len;
+    }
+    double row_tan = 0.0;
+    for (uint32_t w = 0; w < words; ++w) {
+        const uint32_t bits = bounce_row_word(prep, n, row, w, margin);
+        for (uint32_t k = 0; k < kPerWord; ++k) {
+            double leaf_tan = 0.0;
+            for (uint32_t b = kLeafTris * k; b < kLeafTris * (k + 1u); ++b) {
+                const uint32_t B = 32u * w + b;
+                if (B >= n) break;
+                if (((bits >> b) & 1u) == 0u) continue;
+                if (!a_ok) {
+                    leaf_tan = inf;
+                    continue;
+                }
+                const float *q = prep + 16u * B;
+                const double v0[3] = {q[0], q[1], q[2]}, e0[3] = {q[6], q[7], q[8]}, e1[3] = {q[9], q[10], q[11]};
+                const double a00 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2], a11 = e0[0] * e0[0] + e0[1] * e0[1] + e0[2] * e0[2];
+                const double a01 = e0[0] * e1[0] + e0[1] * e1[1] + e0[2] * e1[2];
+                const double kappa = (a00 * a11 - a01 * a01) / (a00 * a11);
+                const double EB = (33.0 * 0x1p-24 / kappa) * (10.0 * Es + abs1(e0) + abs1(e1));
+                double p[3][3], h[3];
+                bool b_ok = kappa >= 0x1p-6 && a00 * a11 > 0.0 && (EB - EB == 0.0);  // (the row boxes' premises but E_B <= 0.4 M, which nothing here needs; NaN: false)
+                for (int v = 0; v < 3; ++v) {
+                    for (int c = 0; c < 3; ++c) p[v][c] = v0[c] + (v == 1 ? e0[c] : (v == 2 ? e1[c] : 0.0));
+                    h[v] = side * ((p[v][0] - av0[0]) * an[0] + (p[v][1] - av0[1]) * an[1] + (p[v][2] - av0[2]) * an[2]) / nn;
+                    b_ok = b_ok && (h[v] - h[v] == 0.0) && (p[v][0] - p[v][0] == 0.0) && (p[v][1] - p[v][1] == 0.0) && (p[v][2] - p[v][2] == 0.0);
+                }
+                if (!b_ok) {
+                    leaf_tan = inf;
+                    continue;
+                }
+                const double H0 = eps - margin / kRowRuleTight.margin_div - kRowRuleTight.slack_scales * Es - EB;
+                const double Hc = H0 > h_o - EB ? H0 : h_o - EB;
+                // the vertices of P_B: the corners at height >= Hc and the points where an edge crosses it
+                double x[6][3], xh[6];
+                int nx = 0;
+                const bool up[3] = {h[0] >= Hc, h[1] >= Hc, h[2] >= Hc};
+                for (int v = 0; v < 3; ++v) {
+                    const int u = v == 2 ? 0 : v + 1;
+                    if (up[v]) {
+                        for (int c = 0; c < 3; ++c) x[nx][c] = p[v][c];
+                        xh[nx++] = h[v];
+                    }
+                    if (up[v] != up[u]) {
+                        const double s = (Hc - h[v]) / (h[u] - h[v]);
+                        for (int c = 0; c < 3; ++c) x[nx][c] = p[v][c] + s * (p[u][c] - p[v][c]);
+                        xh[nx++] = Hc;
+                    }
+                }
+                if (nx == 0) continue;  // empty: cap 0
+                double cap = inf;
+                for (int e = 0; e < 3; ++e) {
+                    bool separates = true;
+                    double worst = 0.0;
+                    for (int i = 0; i < nx; ++i) {
+                        const double den = (x[i][0] - ea[e][0]) * em[e][0] + (x[i][1] - ea[e][1]) * em[e][1] + (x[i][2] - ea[e][2]) * em[e][2] - EB - rhoA;
+                        const double num = xh[i] + EB - h_o;
+                        separates = separates && den > 0.0;  // (NaN: false)
+                        const double r = (num > 0.0 ? num : 0.0) / den;
+                        worst = r > worst ? r : worst;
+                    }
+                    if (separates && worst < cap) cap = worst;
+                }
+                leaf_tan = cap > leaf_tan ? cap : leaf_tan;
+            }
+            if (k_leaf) k_leaf[kPerWord * w + k] = bounce_row_cap_k(leaf_tan);
+            row_tan = leaf_tan > row_tan ? leaf_tan : row_tan;
+        }
+    }
+    return bounce_row_cap_k(row_tan);
+}
+
 }  // namespace rv

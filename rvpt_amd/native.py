@@ -99,6 +99,7 @@ FORMAT_SURFACE_POINTS = 6  # RVPT_HIP_FORMAT_SURFACE_POINTS: rvpt_hip_read answe
 SURFACE_POINT_DTYPE = np.dtype([("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("mat", "<u4"), ("normal", "<f4", (3,)), ("reserved", "<u4")])
 CULL_ROW_BOXES = 0x100  # Context.cull_info: the launch rode with the row boxes (rvpt_abi.hip: kCullRowBoxes)
 CULL_ROW_RULE_TIGHT = 0x400  # Context.cull_info: ... made by the tight rule (rvpt_abi.hip: kCullRowRuleTight; rvpt_vis.h: kRowRuleTight)
+CULL_ROW_CAPS = 0x800  # Context.cull_info: ... and with finite row caps, which let uniform rounds skip their walk (rvpt_abi.hip: kCullRowCaps; rvpt_vis.h: the row caps)
 CULL_SKY_LIST = 0x80 # Context.cull_info: the launch took the listed path (rvpt_abi.hip: kCullSkyList)
 CULL_FRAME_RUNS = 0x200  # Context.cull_info: ... in frame-run order, the camera set-up of a block made once per run (rvpt_abi.hip: kCullFrameRuns)
 TILE = 16

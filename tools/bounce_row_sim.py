@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU-free: what the culled bounce rounds of the packet kernel walk on the headline frame, as shipped before round 8 (union of the lanes' rows, shared leaf boxes)
 and with the ROW BOXES (rvpt_amd/csrc/rvpt_vis.h: a packet whose rays all leave one triangle on one side walks that row's refined words and its own boxes),
-made by round 8's rule and by the tight rule.
+made by round 8's rule and by the tight rule, and with the ROW CAPS on top of the tight rule (uniform packets whose rays all rise above their row's cap walk nothing).
 A numpy brute-force path tracer in float64 — default scene in BVH-leaf order, default camera, one frame, Lambert bounces with numpy's RNG: statistics, not the
 kernel's samples — packs the bounce rays 64 at a time in block order (16 x 16 tiles row-major, 16 x 4 blocks inside) and applies the library's own tables, written
 by the stand-alone host program rvpt_amd/bin/host_row_boxes (the function upload_scene's kernel runs).  The timeline build measures the same quantity on the GPU
@@ -163,3 +163,26 @@ print(f"{'tight rule (uniform packets), else as shipped':44s} {np.where(uniform,
 print(f"{'  uniform packets alone':44s} {own_t[uniform].sum(1).mean():12.2f} {tight_tested[uniform].sum(1).mean():13.2f} {tight_walked[uniform].mean():17.2f}; rounds that walk nothing {(tight_walked[uniform] == 0).mean():.3f} (round 8's rule: {(row_walked[uniform] == 0).mean():.3f})")
 if (~uniform).any():
     print(f"{'  the other packets alone':44s} {union[~uniform].sum(1).mean():12.2f} {shipped_tested[~uniform].sum(1).mean():13.2f} {shipped_walked[~uniform].mean():17.2f}")
+
+# ---- the ROW CAPS (rvpt_vis.h: bounce_row_caps_row, from the host program rvpt_amd/bin/host_row_caps): a uniform packet whose rays all rise above their row's cap walks nothing
+with tempfile.TemporaryDirectory() as d_:
+    src, dst = Path(d_) / "scene.bin", Path(d_) / "caps.bin"
+    src.write_bytes(np.uint32(n).tobytes() + np.ascontiguousarray(tris, np.float32).tobytes() + np.ascontiguousarray(prep, np.float32).tobytes())
+    subprocess.run([str(build.build_host() / "host_row_caps"), str(src), str(dst)], check=True, capture_output=True)
+    caps = np.frombuffer(dst.read_bytes(), np.float32, 8 * n, 24).reshape(2 * n, 4)
+d32, n32 = D.astype(np.float32), caps[LV, :3]
+c32 = (d32[:, 0] * n32[:, 0] + d32[:, 1] * n32[:, 1]) + d32[:, 2] * n32[:, 2]
+dd32 = (d32[:, 0] * d32[:, 0] + d32[:, 1] * d32[:, 1]) + d32[:, 2] * d32[:, 2]
+with np.errstate(invalid="ignore", over="ignore"):
+    out_of_reach = (c32 > 0) & (c32 * c32 > caps[LV, 3] * dd32)  # the kernel's compare, in float32
+skip = uniform & out_of_reach.reshape(n_packets, 64).all(1)
+caps_tested = np.where(skip, 0, np.where(uniform, tight_tested.sum(1), shipped_tested.sum(1)))
+caps_walked = np.where(skip, 0, np.where(uniform, tight_walked, shipped_walked))
+print(f"{'tight rule + row caps, else as shipped':44s} {'':12s} {caps_tested.mean():13.2f} {caps_walked.mean():17.2f}")
+print(f"{'  uniform packets alone':44s} {'':12s} {caps_tested[uniform].mean():13.2f} {caps_walked[uniform].mean():17.2f}; rounds the caps skip {skip.sum() / max(1, uniform.sum()):.3f} of the uniform ones, "
+      f"{skip.mean():.3f} of all; of the skipped, rounds the tight boxes would have walked something in: {(tight_walked[skip] > 0).mean() if skip.any() else 0:.3f}")
+print(f"rows with a finite cap: {np.isfinite(caps[:, 3]).sum()} of {2 * n}; rays out of reach of their row: {out_of_reach.mean():.4f}")
+share = np.bincount(LV, minlength=2 * n) / len(LV)
+for r in np.argsort(share)[::-1][:8]:
+    in_row = rows_of[:, 0] == r
+    print(f"  row {r:4d}: {share[r]:.3f} of the rays, sin cap {np.sqrt(caps[r, 3]):.4f}; its uniform packets that skip: {skip[uniform & in_row].mean() if (uniform & in_row).any() else 0:.3f}")

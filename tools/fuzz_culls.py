@@ -222,7 +222,10 @@ def launches(case):
     return [(f, 1, case["cams"][1 if (case["moving"] and f >= 1) else 0]) for f in range(case["frames"])]
 
 
-def render_gpu(case, cull, bounce_cull, box_cull=True, interleave=None):
+def render_gpu(case, cull, bounce_cull, box_cull=True, interleave=None, caps=True):
+    os.environ.pop("RVPT_HIP_PACKETS_ROW_CAPS", None)
+    if not caps:  # the row caps of the bounce rounds (rvpt_vis.h) all +inf: a knob of the laboratory build, read at upload_scene — the same kernel, which never skips a round
+        os.environ["RVPT_HIP_PACKETS_ROW_CAPS"] = "0"
     if interleave is None:
         os.environ.pop("RVPT_HIP_PACKETS_INTERLEAVE", None)
     else:  # the claim order of the packet kernel (round 6): 0 = tile-linear, g = groups of g blocks dealt from all over the frame (launches below four frames), -g = every launch
@@ -230,7 +233,7 @@ def render_gpu(case, cull, bounce_cull, box_cull=True, interleave=None):
     os.environ["RVPT_HIP_PACKETS_CULL"] = "1" if cull else "0"
     os.environ["RVPT_HIP_PACKETS_BOUNCE_CULL"] = "1" if bounce_cull else "0"
     os.environ["RVPT_HIP_PACKETS_BOX_CULL"] = "1" if box_cull else "0"
-    ctx = native.Context(case["W"], case["H"], 0, 0, 1, native.COUNT_SEGMENTS, lab=False)  # the SHIPPED kernels (the release library reads these two knobs for exactly this A/B)
+    ctx = native.Context(case["W"], case["H"], 0, 0, 1, native.COUNT_SEGMENTS, lab=not caps)  # the SHIPPED kernels (the release library reads these two knobs for exactly this A/B)
     try:
         ctx.upload_scene(None, case["tris"], case["mats"])
         info = 0
@@ -243,6 +246,7 @@ def render_gpu(case, cull, bounce_cull, box_cull=True, interleave=None):
         seg = ctx.stats()[0]
     finally:
         ctx.close()
+        os.environ.pop("RVPT_HIP_PACKETS_ROW_CAPS", None)
     return img, seg, info
 
 
@@ -297,6 +301,9 @@ def run_case(case, oracle_budget):
         if not same_bits(img, img2) or seg != seg2:
             problems.append(f"interleave={order}: {int((img.view(np.uint32) != img2.view(np.uint32)).any(axis=2).sum())} pixels differ, segments {seg2} vs {seg}")
     os.environ.pop("RVPT_HIP_PACKETS_INTERLEAVE", None)
+    img2, seg2, _ = render_gpu(case, True, True, True, caps=False)  # no round skips on its row cap: the same bits
+    if not same_bits(img, img2) or seg != seg2:
+        problems.append(f"row_caps=0: {int((img.view(np.uint32) != img2.view(np.uint32)).any(axis=2).sum())} pixels differ, segments {seg2} vs {seg}")
     rect, bounce = selftests(case)
     if rect[1] != 0:
         problems.append(f"camera rectangles exclude {int(rect[1])} accepted pairs of {int(rect[0])}")
@@ -306,7 +313,7 @@ def run_case(case, oracle_budget):
     if bounce[4] != 0 and guard_on:
         problems.append(f"leaf boxes exclude {int(bounce[4])} accepted pairs of {int(bounce[0])}")
     if bounce[7] != 0 and guard_on:
-        problems.append(f"row boxes exclude {int(bounce[7])} accepted pairs of {int(bounce[0])}")
+        problems.append(f"row boxes or row caps exclude {int(bounce[7])} accepted pairs of {int(bounce[0])}")
     cost = case["W"] * case["H"] * len(case["tris"]) * case["aa"] * case["frames"]
     checked = False
     if cost <= oracle_budget:

@@ -36,7 +36,9 @@ grid, r_lds = r.context.launch_info()[:2]
 r.shutdown()
 whole = np.fromfile(out / "packets_timeline.bin", dtype=np.uint64).reshape(-1, 8)
 raw = whole[: grid * 4]
-phases = whole[len(whole) // 2: len(whole) // 2 + grid * 4].astype(np.float64)  # second half of the rows: shader clocks per phase (rvpt_packets.hip: RV_PHASE)
+second = whole[len(whole) // 2: len(whole) // 2 + grid * 4]  # second half of the rows: shader clocks per phase in the low words (rvpt_packets.hip: RV_PHASE)
+phases = (second & 0xFFFFFFFF).astype(np.float64)
+skipped = (second[:, 7] >> 32).astype(np.int64)  # ... and, beside the last of them, the uniform bounce rounds that the row caps skipped (rvpt_vis.h: the row caps)
 t0, dry, t1 = raw[:, 0].astype(np.int64), raw[:, 1].astype(np.int64), raw[:, 2].astype(np.int64)
 base = t0.min()
 us = lambda x: (x - base) / 100.0
@@ -50,6 +52,7 @@ cam = (raw[:, 3] & 0xFFFFFFFF).astype(np.int64); bnc = (raw[:, 3] >> 32).astype(
 print(f"  per wave: camera rounds {cam.mean():.1f} (min {cam.min()} max {cam.max()}), bounce rounds {bnc.mean():.1f} (min {bnc.min()} max {bnc.max()}), split rounds {spl.mean():.2f}, lanes per round {lr.sum() / max(1, (cam + bnc).sum()):.1f}")
 walked, uni = (raw[:, 5] & 0xFFFFFFFF).astype(np.int64), (raw[:, 5] >> 32).astype(np.int64)
 print(f"  triangles walked per bounce round (after the row or the union of rows and the boxes): {walked.sum() / max(1, bnc.sum()):.2f} of {tris.shape[0]}; bounce rounds that took the row boxes (one leaving triangle): {uni.sum()} of {bnc.sum()} = {uni.sum() / max(1, bnc.sum()):.3f}")
+print(f"  of those, rounds the row caps skipped (every ray out of reach of its row: no words, no boxes, no reciprocals): {skipped.sum()} = {skipped.sum() / max(1, uni.sum()):.3f}")
 busy = (t1 - t0).astype(np.float64) / 100.0
 print(f"  wave busy time: mean {busy.mean():.1f} us, min {busy.min():.1f}, max {busy.max():.1f}; idle share of the span {1 - busy.mean() / us(t1.max()):.3f}")
 if phases.sum() > 0:

@@ -16,6 +16,7 @@ import numpy as np
 
 import _device_state as ds
 import _guarded_pose as gp
+import _guarded_skin as gs
 import _skin
 from rvpt_amd import native, scene
 
@@ -28,25 +29,40 @@ MAX_SEQUENCES = 24
 REDRAWS = 8
 MARGIN = 1e-6  # the least distance of cost / (limit x base) from 1 a guarded step may have: a thousand times test_guarded_update.REL
 
-# the eleven successful forms whose ordered pairs the walk covers ...
-FORMS = ("upload", "build", "plain", "guarded-refit", "guarded-rebuild", "sparse", "pose", "pose-guarded-refit", "pose-guarded-rebuild", "bind", "skin")
+# the thirteen successful forms whose ordered pairs the walk covers ...
+FORMS = ("upload", "build", "plain", "guarded-refit", "guarded-rebuild", "sparse", "pose", "pose-guarded-refit", "pose-guarded-rebuild", "bind", "skin",
+         "skin-guarded-refit", "skin-guarded-rebuild")
+REBUILDS = ("guarded-rebuild", "pose-guarded-rebuild", "skin-guarded-rebuild")
 # ... and the pairs no context can make, each with the sentence of include/rvpt_hip.h that rules it out
 UNMAKEABLE = {
     ("upload", "guarded-rebuild"): "After an ordinary upload with the caller's own nodes the library has no builder to name: a limit there is RVPT_HIP_ERR_INVALID",
     ("upload", "pose-guarded-rebuild"): "from an ordinary upload with the caller's own nodes is RVPT_HIP_ERR_INVALID",
     ("upload", "skin"): "The binding is DROPPED by an ordinary full upload, by a build form the caller asks for",
     ("build", "skin"): "The binding is DROPPED by an ordinary full upload, by a build form the caller asks for",
+    # the guarded skin update is the skin update first: "Every refusal of the skin update comes first", and without a binding that is "skin update before a bind"
+    ("upload", "skin-guarded-refit"): "The binding is DROPPED by an ordinary full upload, by a build form the caller asks for",
+    ("build", "skin-guarded-refit"): "The binding is DROPPED by an ordinary full upload, by a build form the caller asks for",
+    ("upload", "skin-guarded-rebuild"): "The binding is DROPPED by an ordinary full upload, by a build form the caller asks for",  # (and no builder to name)
+    ("build", "skin-guarded-rebuild"): "The binding is DROPPED by an ordinary full upload, by a build form the caller asks for",
 }
 SITUATIONS = ("a guarded plain rebuild while a binding and a rest pose are held, then a skin update",
               "a guarded pose rebuild, then a pose of an unlisted part",
-              "a refusal directly after a rebuild",
-              "a bind between two pose updates")
+              "a refusal directly after a guarded plain rebuild",
+              "a bind between two pose updates",
+              "a refusal directly after a guarded pose rebuild",
+              "a refusal directly after a guarded skin rebuild",
+              "a guarded skin rebuild, then a sparse update",
+              "a guarded skin rebuild, then a pose of some parts",
+              "a guarded skin rebuild, then a plain skin update with the same bones",
+              "a guarded plain rebuild between two guarded skin steps")
 # the refusals the generator draws: what, the pattern a message must match — each a piece of the header's wording or of rvpt_abi.hip's and rvpt_scene.hip's message text
 REFUSALS = {
     "skin without a binding": "skin update before a bind",
     "skin with too few bones": "the binding names bone",
     "a limit on a caller's tree": "guarded update with a limit after an ordinary upload_scene",
     "a limit on a caller's tree (pose)": "guarded pose update with a limit after an ordinary upload_scene",
+    "a limit on a caller's tree (skin)": "guarded skin update with a limit after an ordinary upload_scene",
+    "a guarded skin update with a limit on a caller's tree, without a binding": "skin update before a bind",  # the skin update's refusals come first
     "two pose ranges share a triangle": "share triangle",
     "an index twice in a sparse list": "occurs more than once in the list",
     "a plain update of another n_tris": "the uploaded scene has",
@@ -319,18 +335,41 @@ class Model:
         self.max_bone = int(rec["bone"].max()) if rec.size else 0
         return None
 
-    def skin(self, bones):
+    def _check_bones(self, bones):
         m = scene.bone_matrices(bones)
         if self.binding is None:
             raise Refused(REFUSALS["skin without a binding"])
         if m.shape[0] <= self.max_bone:
             raise Refused(REFUSALS["skin with too few bones"])
+        return m
+
+    def _skin(self, m):
         if self.rest is None:
             self.rest = self.current
         self.current = scene.skin_triangles(self.rest, self.binding, m)  # every triangle, from the rest pose, which it keeps
         if self.bvh:
             self._refit()  # "every box is then refitted by the PLAIN form's rule"
+
+    def skin(self, bones):
+        self._skin(self._check_bones(bones))
         return None
+
+    def skin_guarded(self, bones, limit):
+        permille = gp.permille_of(limit)
+        m = self._check_bones(bones)  # "every refusal of the skin update comes first, in its words and its order"
+        if not self.bvh:  # "there the count is the plain skin update"
+            self._skin(m)
+            return None
+        if permille != 0 and self.built_by is None:  # "then the one refusal of this form"; "report only (0) is legal there"
+            raise Refused(REFUSALS["a limit on a caller's tree (skin)"])
+        self._skin(m)
+        cost, base = scene.tree_cost(self.nodes), self.base_cost
+        if permille == 0 or not cost > permille / 1000.0 * base:
+            return Report(cost, base, False, None, None)
+        rest = self.rest
+        self._rebuild()  # THE REST POSE GOES WITH THE REBUILD, THE BINDING STAYS WHERE IT IS: in update order both are the same arrays, and max_bone stays
+        self.rest = rest
+        return Report(cost, base, True, self.tree, self.base_cost)  # (the tree the scene then holds: a PLOC rebuild that fell back names lbvh)
 
     # ---- the read-back ---------------------------------------------------------------------------------------------------------------------------------------
 
@@ -538,12 +577,25 @@ class _Draw:
         rows = scene.wobble(self.m.current, self.phase(), 0.03 * extent(self.m.current))[idx]
         return idx.astype(np.int64), np.ascontiguousarray(rows)
 
-    def binding(self):
-        return _skin.weights(self.m.current if self.m.rest is None else self.m.rest, int(self.rng.choice([1, 3, 16, 64])))
+    def binding(self, many=False):
+        """many: enough bones that a block of them can be carried away from its neighbours (tests/_guarded_skin.py: carried_bones)"""
+        return _skin.weights(self.m.current if self.m.rest is None else self.m.rest, int(self.rng.choice([16, 64] if many else [1, 3, 16, 64])))
 
     def bones(self, k=None):
         rows = self.m.current if self.m.rest is None else self.m.rest
         return _skin.bones(rows, self.m.max_bone + 1 if k is None else k, self.phase())
+
+    def carrying(self, attempt):
+        """tests/_guarded_skin.py's carrying set for the bones bound: gentle rotations, the blocks of carried_bones translated along an axis — another axis,
+        sign and length with every attempt, as carried_triangles varies its motion"""
+        rows = self.m.current if self.m.rest is None else self.m.rest
+        k = self.m.max_bone + 1
+        axis = gs.axes_by_extent(rows)[(attempt + int(self.rng.randint(3))) % 3]
+        out = gs.carrying(rows, k, axis, self.phase())
+        factor = (1.0 + attempt // 3) * (1.0 if self.rng.rand() < 0.5 else -1.0)
+        for b in gs.carried_bones(k):
+            out[b, axis, 3] += np.float32((factor - 1.0) * 0.5 * extent(rows))
+        return out
 
     def caller_tree(self, loose):
         """the caller's own tree over the triangles as they stand: (nodes, triangles in leaf order)"""
@@ -574,9 +626,11 @@ def _clear_of_limit(report, limit):
 def _available(model, prev_listed):
     kinds = ["pose", "pose-guarded-refit", "bind", "plain", "guarded-refit", "sparse", "upload", "build"]
     if model.binding is not None:
-        kinds.append("skin")
+        kinds += ["skin", "skin-guarded-refit"]
     if model.bvh and model.built_by is not None:
         kinds += ["guarded-rebuild", "pose-guarded-rebuild"]
+        if model.binding is not None:
+            kinds.append("skin-guarded-rebuild")
     return kinds
 
 
@@ -588,6 +642,7 @@ def _refusals_available(model):
         out.append("skin with too few bones")
     if model.bvh and model.built_by is None:
         out += ["a limit on a caller's tree", "a limit on a caller's tree (pose)"]
+        out.append("a limit on a caller's tree (skin)" if model.binding is not None else "a guarded skin update with a limit on a caller's tree, without a binding")
     return out
 
 
@@ -601,6 +656,10 @@ def _draw_refusal(draw, what):
         return "update_guarded", (draw.wobbled(), 1.0 + int(rng.randint(0, 500)) / 1000.0)
     if what == "a limit on a caller's tree (pose)":
         return "pose_guarded", (draw.moves(), 1.0 + int(rng.randint(0, 500)) / 1000.0)
+    if what == "a limit on a caller's tree (skin)":
+        return "skin_guarded", (draw.bones(), 1.0 + int(rng.randint(0, 500)) / 1000.0)
+    if what == "a guarded skin update with a limit on a caller's tree, without a binding":
+        return "skin_guarded", (_skin.bones(m.current, 3, draw.phase()), 1.0 + int(rng.randint(0, 500)) / 1000.0)
     if what == "two pose ranges share a triangle":
         rec = draw.moves()
         first, count = int(rec["first"][-1]), int(rec["count"][-1])
@@ -618,7 +677,7 @@ def _draw_refusal(draw, what):
     return "bind", (draw.binding()[:-3].copy(),)
 
 
-DEVICE_FORMS = ("build", "update", "update_guarded", "update_sparse", "bind", "skin")  # where the header allows device memory; a pose list is host memory
+DEVICE_FORMS = ("build", "update", "update_guarded", "update_sparse", "bind", "skin", "skin_guarded")  # where the header allows device memory; a pose list is host memory
 
 
 def _draw_kind(draw, kind, prev_listed, attempt):
@@ -635,6 +694,8 @@ def _draw_kind(draw, kind, prev_listed, attempt):
         return "update_sparse", draw.sparse()
     if kind == "bind":
         return "bind", (draw.binding(),)
+    if kind == "bind-many":
+        return "bind", (draw.binding(many=True),)
     if kind == "skin":
         return "skin", (draw.bones(),)
     if kind == "pose":
@@ -643,6 +704,11 @@ def _draw_kind(draw, kind, prev_listed, attempt):
     if kind.startswith("pose-guarded"):
         args = (draw.moves(carry=rebuild, attempt=attempt),)
         form = "pose_guarded"
+    elif kind.startswith("skin-guarded"):
+        if rebuild and one_bone(m.binding):
+            return None  # one bone carries the whole mesh along: no tree gets worse by that
+        args = (draw.carrying(attempt) if rebuild else draw.bones(),)
+        form = "skin_guarded"
     else:
         args = (draw.carried_triangles(attempt) if rebuild else draw.wobbled(),)
         form = "update_guarded"
@@ -654,6 +720,25 @@ def _draw_kind(draw, kind, prev_listed, attempt):
     return (form, args + (limit,)) if limit is not None else None
 
 
+def one_bone(binding) -> bool:
+    """every influence that counts names the same bone: the skin update is then one pose of the whole mesh"""
+    return np.unique(binding["bone"][binding["weight"] != 0]).size <= 1
+
+
+def rebuild_conditions(before, after):
+    """what a skin-guarded-rebuild step of the suite must be for a wrong device to show, as a list of what fails: the rebuild changes the permutation (or the
+    rest pose carried by the old one would still fit), the rest pose is not the skinned pose (or carrying the wrong one would not show), and the binding is
+    not one pose of the whole mesh (or a binding read through the wrong permutation would skin alike)"""
+    out = []
+    if np.array_equal(before.perm, after.perm):
+        out.append("the permutation stays")
+    if after.rest.tobytes() == after.current.tobytes():
+        out.append("the rest pose is the skinned pose")
+    if one_bone(after.binding):
+        out.append("the binding names one bone")
+    return out
+
+
 def kind_of(step_form, report, pattern=None):
     if step_form in ("upload", "build", "bind", "skin", "pose"):
         return step_form
@@ -661,11 +746,17 @@ def kind_of(step_form, report, pattern=None):
         return "plain"
     if step_form == "update_sparse":
         return "sparse"
-    prefix = "guarded" if step_form == "update_guarded" else "pose-guarded"
+    prefix = {"update_guarded": "guarded", "pose_guarded": "pose-guarded", "skin_guarded": "skin-guarded"}[step_form]
     return f"{prefix}-{'rebuild' if report is not None and report.rebuilt else 'refit'}"
 
 
-SCRIPT = ("bind", "skin", "guarded-rebuild", "skin", "pose-guarded-rebuild", "pose-unlisted", "bind", "pose", "guarded-rebuild", "refusal")  # the four named situations
+# the named situations, in one walk: what a token makes beyond its kind is said in ALIAS
+SCRIPT = ("bind-many", "skin", "guarded-rebuild", "skin", "pose-guarded-rebuild", "pose-unlisted", "bind-many", "pose", "skin-guarded-rebuild", "sparse",
+          "skin-guarded-rebuild", "refusal", "skin-guarded-rebuild", "pose", "skin-guarded-rebuild", "skin-same", "skin-guarded-refit", "guarded-rebuild",
+          "skin-guarded-refit", "guarded-rebuild", "refusal", "pose-guarded-rebuild", "refusal")
+ALIAS = {"bind-many": "bind",       # a bind of 16 or 64 bones
+         "pose-unlisted": "pose",   # a pose that avoids the parts the guarded pose rebuild before it listed
+         "skin-same": "skin"}       # the plain skin update with the bones of the guarded skin update before it
 
 
 class Coverage:
@@ -710,8 +801,16 @@ def situations_in(steps):
             found.add(SITUATIONS[0])
         if s.kind == "pose-guarded-rebuild" and nxt.form in ("pose", "pose_guarded") and not nxt.refusal and not np.intersect1d(ranges_of(s), ranges_of(nxt)).size:
             found.add(SITUATIONS[1])
-        if s.kind in ("guarded-rebuild", "pose-guarded-rebuild") and nxt.refusal:
-            found.add(SITUATIONS[2])
+        if s.kind in REBUILDS and nxt.refusal:
+            found.add(SITUATIONS[{"guarded-rebuild": 2, "pose-guarded-rebuild": 4, "skin-guarded-rebuild": 5}[s.kind]])
+        if s.kind == "skin-guarded-rebuild" and nxt.kind == "sparse":
+            found.add(SITUATIONS[6])
+        if s.kind == "skin-guarded-rebuild" and nxt.kind == "pose":
+            found.add(SITUATIONS[7])
+        if s.kind == "skin-guarded-rebuild" and nxt.kind == "skin" and np.asarray(nxt.args[0]).tobytes() == np.asarray(s.args[0]).tobytes():
+            found.add(SITUATIONS[8])
+        if s.kind == "guarded-rebuild" and i > 0 and steps[i - 1].kind.startswith("skin-guarded") and nxt.kind.startswith("skin-guarded"):
+            found.add(SITUATIONS[9])
         if s.kind == "bind" and i > 0 and steps[i - 1].kind.startswith("pose") and nxt.kind.startswith("pose") and not nxt.refusal:
             found.add(SITUATIONS[3])
     return found
@@ -743,7 +842,8 @@ def sequence(seed, source, n_steps, coverage=None):
     while len(steps) < n_steps:
         prev = steps[-1]
         wanted = script.pop(0) if script else None
-        want_refusal = wanted == "refusal" or (wanted is None and len(steps) > 1 and not prev.refusal and rng.rand() < 1.0 / 8.0)
+        rare = min(refusals[o] for o in _refusals_available(model)) < 2  # a refusal met less than twice can be made here: three times as likely
+        want_refusal = wanted == "refusal" or (wanted is None and len(steps) > 1 and not prev.refusal and rng.rand() < (3.0 if rare else 1.0) / 8.0)
         held = (model.binding is not None, model.rest is not None)
         if want_refusal:
             options = _refusals_available(model)
@@ -761,9 +861,7 @@ def sequence(seed, source, n_steps, coverage=None):
             steps.append(step)
             continue
         options = _available(model, prev_listed)
-        if wanted == "pose-unlisted":
-            ranked = ["pose"]
-        elif wanted is not None:
+        if wanted is not None:
             ranked = [wanted]
         else:
             def score(k):
@@ -773,11 +871,15 @@ def sequence(seed, source, n_steps, coverage=None):
             ranked = sorted(options, key=score, reverse=True)
         ranked += [k for k in ("plain", "sparse") if k not in ranked]  # (what is left where a wanted form cannot be made: always makeable)
         step = None
-        for kind in ranked:
+        for token in ranked:
+            kind = ALIAS.get(token, token)
             if kind not in options:
                 continue
             for attempt in range(REDRAWS + 1):
-                drawn = _draw_kind(draw, kind, prev_listed if kind == "pose" and prev.kind == "pose-guarded-rebuild" else None, attempt)
+                if token == "skin-same":
+                    drawn = ("skin", (prev.args[0],)) if prev.form == "skin_guarded" else None
+                else:
+                    drawn = _draw_kind(draw, token if token == "bind-many" else kind, prev_listed if kind == "pose" and prev.kind == "pose-guarded-rebuild" else None, attempt)
                 if drawn is None:
                     continue
                 form, args = drawn
@@ -786,6 +888,8 @@ def sequence(seed, source, n_steps, coverage=None):
                 if kind_of(form, report) != kind or not ds.no_zero_coordinate(trial.current):
                     continue
                 if report is not None and not _clear_of_limit(report, args[-1]):
+                    continue
+                if kind == "skin-guarded-rebuild" and rebuild_conditions(model, trial):
                     continue
                 step = Step(form, args, bool(model.bvh and form in DEVICE_FORMS and rng.rand() < 0.4), kind, None, held)
                 break
@@ -812,7 +916,8 @@ class Spec(NamedTuple):
 SUITE = (Spec(1, "upload", "lab"), Spec(2, "upload-loose", "lab"), Spec(3, "lbvh", "lab"), Spec(4, "ploc", "lab"), Spec(5, "sah", "lab"), Spec(6, "lbvh", "lab"),
          Spec(7, "ploc", "lab"), Spec(8, "sah", "lab"), Spec(9, "upload", "lab"), Spec(10, "upload-loose", "lab"), Spec(11, "lbvh", "lab-ordered"),
          Spec(12, "sah", "lab-ordered"), Spec(13, "brute", "lab"), Spec(14, "brute", "lab"), Spec(15, "lbvh", "release"), Spec(16, "ploc", "release"),
-         Spec(17, "sah", "release"))
+         Spec(17, "sah", "release"), Spec(18, "upload", "lab"), Spec(19, "ploc", "lab"),
+         Spec(20, "lbvh", "lab"))
 _GENERATED = []
 _COVERAGE = []
 
@@ -836,3 +941,32 @@ def suite():
     """([(Spec, [Step])] of SUITE, the coverage of its BVH sequences)"""
     sequence_of(len(SUITE) - 1)
     return list(_GENERATED), _COVERAGE[0]
+
+
+# ---- steps that once differed from the model ---------------------------------------------------------------------------------------------------------------------
+
+class Regression(NamedTuple):
+    """step `step` of sequence(seed, source, step + 1), what it caught, and what that step must be: a predicate over (steps, index), held on the CPU by
+    tests/test_scene_model_host.py, so that a change of the generator cannot quietly make the replay a test of something else"""
+    seed: int
+    source: str
+    step: int
+    what: str
+    holds: object
+
+
+def _sparse_refusal_with_a_device_list_after(kinds, source=None):
+    def holds(steps, index):
+        step, before = steps[index], steps[index - 1]
+        return (index > 0 and step.kind == "refusal: an index twice in a sparse list" and step.on_device and before.kind in kinds
+                and (source is None or (steps[0].form == "build" and steps[0].args[0] == source)))
+    return holds
+
+
+REGRESSION = (
+    Regression(2, "ploc", 23, "a sparse update refused for an index that occurs twice, its list in device memory, directly after a rebuild: the library had made the "
+               "inverse permutation for the validation kernels and kept its flag (have_inv_perm False -> True across a refusal); the flag now comes back",
+               _sparse_refusal_with_a_device_list_after(REBUILDS, "ploc")),
+    Regression(7, "sah", 12, "the same refusal directly after a guarded skin update that rebuilt, which discards the inverse permutation on a path of its own",
+               _sparse_refusal_with_a_device_list_after(("skin-guarded-rebuild",))),
+)

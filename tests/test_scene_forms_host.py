@@ -149,6 +149,7 @@ def held_model():
         "update": lambda x: x.update(tris), "update-guarded": lambda x: x.update_guarded(tris, None), "update-sparse": lambda x: x.update_sparse([5], tris[:1]),
         "pose": lambda x: x.pose(move), "pose-guarded": lambda x: x.pose_guarded(move, None),
         "bind-skin": lambda x: x.bind(_skin.weights(tris, 2)), "skin": lambda x: x.skin(_skin.bones(tris, 3)),
+        "skin-guarded": lambda x: x.skin_guarded(_skin.bones(tris, 3), None),
     }
     return m, calls
 
@@ -163,7 +164,7 @@ def test_the_keep_columns_are_the_models_rules(decoder):
     held, model_calls = held_model()
     for form in FORMS:
         m = held.copy()
-        model_calls["skin" if form == "skin-guarded" else form](m)  # (the model has no guarded skin method: the header gives that form the skin update's two rules)
+        model_calls[form](m)
         assert rows[form][0] == (m.binding is not None), form  # keeps_binding
         assert rows[form][1] == (m.rest is not None), form     # keeps_rest
     # the guard's two columns: the pose and skin guards carry the rest pose through a rebuild and name the tree the scene then holds, the plain guard the builder

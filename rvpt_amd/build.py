@@ -22,7 +22,7 @@ SOURCES = [_PKG / "csrc" / n for n in (
     "rvpt_box.hip",  # box queries (rvpt_hip_read with FORMAT_BOX_OVERLAPS and FORMAT_BOX_OVERLAPS_K): a walk that prunes by six comparisons, kernels of its own, likewise
     "rvpt_surface.hip",  # the geometry read-back (rvpt_hip_read with FORMAT_TRIANGLES and FORMAT_SURFACE_POINTS): one record kernel, the row scatter launched from there, likewise
 )]
-HEADERS = [_PKG / "csrc" / "rvpt_ctx.h", _PKG / "csrc" / "rvpt_box.h", _PKG / "csrc" / "rvpt_scene_forms.h", _PKG / "csrc" / "rvpt_surface.h", _PKG / "csrc" / "rvpt_nearest.h", _PKG / "csrc" / "rvpt_paths.h", _PKG / "csrc" / "rvpt_query.h", _PKG / "csrc" / "rvpt_frames.h", _PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
+HEADERS = [_PKG / "csrc" / "rvpt_ctx.h", _PKG / "csrc" / "rvpt_box.h", _PKG / "csrc" / "rvpt_scene_forms.h", _PKG / "csrc" / "rvpt_surface.h", _PKG / "csrc" / "rvpt_nearest.h", _PKG / "csrc" / "rvpt_paths.h", _PKG / "csrc" / "rvpt_query.h", _PKG / "csrc" / "rvpt_walk.h", _PKG / "csrc" / "rvpt_frames.h", _PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
            _PKG / "csrc" / "rvpt_vis.h", _PKG.parent / "include" / "rvpt_hip.h", _PKG.parent / "include" / "rvpt_hip_lab.h"]
 
 # -ffp-contract=off: the arithmetic specification fixes where FMAs happen; applies to the

@@ -1520,6 +1520,7 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
     nearest.tris = ctx->d_tris, nearest.nodes = ctx->d_nodes, nearest.perm = scene.perm;
     nearest.n_tris = scene.n_tris, nearest.n_nodes = static_cast<uint32_t>(ctx->n_nodes), nearest.stack_levels = bvh_stack_levels(ctx);
     const uint32_t groups_of = hits ? hits : 1u;  // records per ray, per point or per box
+    const rv::QueryForm ray_form = crossings ? rv::QueryForm::Crossings : rv::QueryForm::Hits;
     rv::QueryPlan plan{};
     if (boxes)
         HIP_TRY(ctx, rv::box_plan(nearest, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
@@ -1527,10 +1528,8 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
         HIP_TRY(ctx, rv::nearest_plan(nearest, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
     else if (paths)
         HIP_TRY(ctx, rv::path_plan(path_scene, static_cast<uint32_t>(n), ctx->num_cus, path_mode, &plan));
-    else if (crossings)
-        HIP_TRY(ctx, rv::cross_plan(scene, static_cast<uint32_t>(n), ctx->num_cus, &plan));
     else if (!surface)  // (a surface read is one record per lane and no walk: no plan, no stack)
-        HIP_TRY(ctx, rv::query_plan(scene, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
+        HIP_TRY(ctx, rv::query_plan(scene, ray_form, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
     if (int rc = rvpt_hip_wait(ctx)) return rc;  // every read implies it; frames in flight still read the scene, and the buffers below may be regrown
     if (int rc = grow(ctx, ctx->d_query_scratch, ctx->cap_query_scratch, 64u + plan.stack_words, sizeof(uint32_t))) return rc;
     void *records = dst;
@@ -1560,10 +1559,8 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
         HIP_TRY(ctx, rv::nearest_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
     else if (paths)
         HIP_TRY(ctx, rv::path_launch(ctx->stream, path_scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n), path_mode));
-    else if (crossings)
-        HIP_TRY(ctx, rv::cross_launch(ctx->stream, scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
     else
-        HIP_TRY(ctx, rv::query_launch(ctx->stream, scene, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
+        HIP_TRY(ctx, rv::query_launch(ctx->stream, scene, ray_form, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
     if (!device_dst)  // only the out fields travel back: the in fields of a host record are never written either
         HIP_TRY(ctx, hipMemcpy2DAsync(static_cast<unsigned char *>(dst) + out_offset, sizeof(rvpt_ray_hit), ctx->d_query_stage + out_offset, sizeof(rvpt_ray_hit),
                                       sizeof(rvpt_ray_hit) - out_offset, n, hipMemcpyDeviceToHost, ctx->stream));

@@ -25,6 +25,7 @@
 
 #include "rvpt_device.h"
 #include "rvpt_box.h"
+#include "rvpt_walk.h"
 
 namespace rv {
 
@@ -123,14 +124,6 @@ __device__ __forceinline__ void store_group(float4 *records, const size_t group,
                 make_float4(__uint_as_float(w[4 * j]), __uint_as_float(w[4 * j + 1]), __uint_as_float(w[4 * j + 2]), __uint_as_float(w[4 * j + 3]));
 }
 
-// the next run of 64 groups for this wave (wave-uniform)
-__device__ __forceinline__ uint32_t claim_run(uint32_t *counter, const uint32_t lane)
-{
-    uint32_t run = 0;
-    if (lane == 0) run = atomicAdd(counter, 1u);
-    return __builtin_amdgcn_readlane(run, 0);
-}
-
 // a binary node's box (bounds = {minx,maxx,miny,maxy,minz,maxz}: n0.zw = x, n1.xy = y, n1.zw = z) against the lane's
 __device__ __forceinline__ bool node_apart(const BoxProbe &q, const float4 n0, const float4 n1)
 {
@@ -139,17 +132,13 @@ __device__ __forceinline__ bool node_apart(const BoxProbe &q, const float4 n0, c
 
 }  // namespace
 
-// LDS: [stack: lds_levels x kBlock words] — a slot is a node index; the global part likewise.
+// LDS: [stack: lds_levels x kBlock words] — a slot is a node index, WalkStack<1> of rvpt_walk.h; the global part likewise.
 template <int CAP>
 __global__ __launch_bounds__(kBlock) void box_bvh2(const BoxArgs a)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
     const uint32_t k = a.k;
-    const uint32_t lds_levels = a.lds_levels;
-    const uint32_t top_level = a.stack_levels - 1u;
+    const WalkStack<1> stack(a.lds_levels, a.stack_levels, a.stack_overflow);
     const uint32_t n_nodes = a.n_nodes, n_tris = a.n_tris;
-    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
-    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
     const uint32_t lane = lane_id();
 
     for (;;) {
@@ -174,14 +163,7 @@ __global__ __launch_bounds__(kBlock) void box_bvh2(const BoxArgs a)
                 } else if (first < n_nodes && first + 1u < n_nodes) {  // both children inside the node buffer (first + 1 may wrap: then first fails)
                     const float4 *kids = a.nodes + 2u * static_cast<size_t>(first);
                     const bool vl = !node_apart(g.q, kids[0], kids[1]), vr = !node_apart(g.q, kids[2], kids[3]);
-                    if (vl && vr) {
-                        const uint32_t at = min(sp, top_level);  // (the tree's height bounds the pushes of a root-to-leaf path; the clamp keeps a wrong size inside the memory)
-                        if (at < lds_levels)
-                            lds_stack[at * kBlock + threadIdx.x] = first + 1u;
-                        else
-                            ovf[(at - lds_levels) * ovf_stride] = first + 1u;
-                        sp = at + 1u;
-                    }
+                    if (vl && vr) stack.push(sp, first + 1u);  // (the tree's height bounds the pushes of a root-to-leaf path)
                     if (vl || vr) {
                         cur = vl ? first : first + 1u;
                         pop = false;
@@ -190,8 +172,7 @@ __global__ __launch_bounds__(kBlock) void box_bvh2(const BoxArgs a)
                 if (pop) {
                     bool found = false;
                     while (sp > 0 && !found) {
-                        sp -= 1;
-                        const uint32_t node = sp < lds_levels ? lds_stack[sp * kBlock + threadIdx.x] : ovf[(sp - lds_levels) * ovf_stride];
+                        const uint32_t node = stack.pop(sp);
                         if (node < n_nodes) {
                             cur = node;
                             found = true;

@@ -30,6 +30,7 @@
 
 #include "rvpt_device.h"
 #include "rvpt_nearest.h"
+#include "rvpt_walk.h"
 
 namespace rv {
 
@@ -156,14 +157,6 @@ __device__ __forceinline__ void store_point(float4 *records, const size_t r, con
     records[3 * r + 2] = out2;
 }
 
-// the next run of 64 records for this wave (wave-uniform)
-__device__ __forceinline__ uint32_t claim_run(uint32_t *counter, const uint32_t lane)
-{
-    uint32_t run = 0;
-    if (lane == 0) run = atomicAdd(counter, 1u);
-    return __builtin_amdgcn_readlane(run, 0);
-}
-
 // K-NEAREST POINTS.  n, n_runs of NearestArgs count GROUPS of k records: record 0 of a group carries the point, record j receives the j-th entry.
 struct NearestKArgs {
     NearestArgs q;
@@ -248,15 +241,11 @@ __device__ __forceinline__ void store_points(float4 *records, const size_t group
 
 }  // namespace
 
-// LDS: [stack: lds_levels x 2 words x kBlock] — a slot is (box_d2 bits, node index), query_bvh4's two-word layout; the global part likewise.
+// LDS: [stack: lds_levels x 2 words x kBlock] — a slot is (box_d2 bits, node index), WalkStack<2> of rvpt_walk.h; the global part likewise.
 __global__ __launch_bounds__(kBlock) void nearest_bvh2(const NearestArgs a)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
-    const uint32_t lds_levels = a.lds_levels;
-    const uint32_t top_level = a.stack_levels - 1u;
+    const WalkStack<2> stack(a.lds_levels, a.stack_levels, a.stack_overflow);
     const uint32_t n_nodes = a.n_nodes, n_tris = a.n_tris;
-    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
-    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
     const uint32_t lane = lane_id();
 
     for (;;) {
@@ -283,17 +272,9 @@ __global__ __launch_bounds__(kBlock) void nearest_bvh2(const NearestArgs a)
                     const bool vl = dl <= best, vr = dr <= best;
                     const bool left_first = dl <= dr || !vr;
                     if (vl && vr) {
-                        const uint32_t at = min(sp, top_level);  // (the tree's height bounds the pushes of a root-to-leaf path; the clamp keeps a wrong size inside the memory)
                         const float far_d = left_first ? dr : dl;
                         const uint32_t far_node = left_first ? first + 1u : first;
-                        if (at < lds_levels) {
-                            lds_stack[(2u * at + 0u) * kBlock + threadIdx.x] = __float_as_uint(far_d);
-                            lds_stack[(2u * at + 1u) * kBlock + threadIdx.x] = far_node;
-                        } else {
-                            ovf[(2u * (at - lds_levels) + 0u) * ovf_stride] = __float_as_uint(far_d);
-                            ovf[(2u * (at - lds_levels) + 1u) * ovf_stride] = far_node;
-                        }
-                        sp = at + 1u;
+                        stack.push(sp, __float_as_uint(far_d), far_node);  // (the tree's height bounds the pushes of a root-to-leaf path)
                     }
                     if (vl || vr) {
                         cur = (vl && left_first) ? first : first + 1u;
@@ -303,15 +284,8 @@ __global__ __launch_bounds__(kBlock) void nearest_bvh2(const NearestArgs a)
                 if (pop) {
                     bool found = false;
                     while (sp > 0 && !found) {
-                        sp -= 1;
                         uint32_t d_bits, node;
-                        if (sp < lds_levels) {
-                            d_bits = lds_stack[(2u * sp + 0u) * kBlock + threadIdx.x];
-                            node = lds_stack[(2u * sp + 1u) * kBlock + threadIdx.x];
-                        } else {
-                            d_bits = ovf[(2u * (sp - lds_levels) + 0u) * ovf_stride];
-                            node = ovf[(2u * (sp - lds_levels) + 1u) * ovf_stride];
-                        }
+                        stack.pop(sp, d_bits, node);
                         if (__uint_as_float(d_bits) <= best && node < n_nodes) {  // best may have shrunk since the push
                             cur = node;
                             found = true;
@@ -354,12 +328,8 @@ __global__ __launch_bounds__(kBlock) void nearest_bvh2_k(const NearestKArgs ka)
 {
     const NearestArgs &a = ka.q;
     const uint32_t k = ka.k;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
-    const uint32_t lds_levels = a.lds_levels;
-    const uint32_t top_level = a.stack_levels - 1u;
+    const WalkStack<2> stack(a.lds_levels, a.stack_levels, a.stack_overflow);
     const uint32_t n_nodes = a.n_nodes, n_tris = a.n_tris;
-    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
-    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
     const uint32_t lane = lane_id();
 
     for (;;) {
@@ -388,17 +358,9 @@ __global__ __launch_bounds__(kBlock) void nearest_bvh2_k(const NearestKArgs ka)
                     const bool vl = dl <= h.bound, vr = dr <= h.bound;
                     const bool left_first = dl <= dr || !vr;
                     if (vl && vr) {
-                        const uint32_t at = min(sp, top_level);  // (the tree's height bounds the pushes of a root-to-leaf path; the clamp keeps a wrong size inside the memory)
                         const float far_d = left_first ? dr : dl;
                         const uint32_t far_node = left_first ? first + 1u : first;
-                        if (at < lds_levels) {
-                            lds_stack[(2u * at + 0u) * kBlock + threadIdx.x] = __float_as_uint(far_d);
-                            lds_stack[(2u * at + 1u) * kBlock + threadIdx.x] = far_node;
-                        } else {
-                            ovf[(2u * (at - lds_levels) + 0u) * ovf_stride] = __float_as_uint(far_d);
-                            ovf[(2u * (at - lds_levels) + 1u) * ovf_stride] = far_node;
-                        }
-                        sp = at + 1u;
+                        stack.push(sp, __float_as_uint(far_d), far_node);  // (the tree's height bounds the pushes of a root-to-leaf path)
                     }
                     if (vl || vr) {
                         cur = (vl && left_first) ? first : first + 1u;
@@ -408,15 +370,8 @@ __global__ __launch_bounds__(kBlock) void nearest_bvh2_k(const NearestKArgs ka)
                 if (pop) {
                     bool found = false;
                     while (sp > 0 && !found) {
-                        sp -= 1;
                         uint32_t d_bits, node;
-                        if (sp < lds_levels) {
-                            d_bits = lds_stack[(2u * sp + 0u) * kBlock + threadIdx.x];
-                            node = lds_stack[(2u * sp + 1u) * kBlock + threadIdx.x];
-                        } else {
-                            d_bits = ovf[(2u * (sp - lds_levels) + 0u) * ovf_stride];
-                            node = ovf[(2u * (sp - lds_levels) + 1u) * ovf_stride];
-                        }
+                        stack.pop(sp, d_bits, node);
                         if (__uint_as_float(d_bits) <= h.bound && node < n_nodes) {  // bound may have shrunk since the push
                             cur = node;
                             found = true;

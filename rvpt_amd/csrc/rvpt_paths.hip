@@ -22,6 +22,7 @@
 
 #include "rvpt_device.h"
 #include "rvpt_paths.h"
+#include "rvpt_walk.h"
 
 namespace rv {
 
@@ -153,27 +154,15 @@ enum { S_IDLE = 0, S_TRAV = 1, S_HIT = 2 };  // no segment / a segment whose wal
 
 }  // namespace
 
-// query_bvh4's walk (rvpt_bvh4.hip's per-lane walk: slab_entry at the root, four slab_child tests per wide node, on with the first child that passes, the others
-// stacked, the last first, with their entry distances and packed heads, popped with closest >= entry) under the frame kernel's loop: lanes whose walk has ended
-// wait in S_HIT until kPathRefill of them do, then shade, regenerate and start the next walk together; reached leaves are parked and run in batches.
-// LDS: [stack: lds_levels x 2 words x kBlock][root: 2 float4][top_nodes wide nodes]
+// The 4-wide walk of rvpt_walk.h (walk_bvh4's: its order, its stack and its LDS layout are stated there) under the frame kernel's loop: lanes whose walk has
+// ended wait in S_HIT until kPathRefill of them do, then shade, regenerate and start the next walk together; reached leaves are parked and run in batches.
 template <int FORM>
 __global__ __launch_bounds__(kBlock) void path_bvh4(const PathArgs a)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
-    const uint32_t lds_levels = a.lds_levels;
-    float4 *lds_root = reinterpret_cast<float4 *>(lds_stack + 2u * lds_levels * kBlock);
-    float4 *lds_top = lds_root + 2;
-    const uint32_t top_nodes = a.top_nodes;
-    if (threadIdx.x < 2u) lds_root[threadIdx.x] = a.nodes[threadIdx.x];
-    for (uint32_t i = threadIdx.x; i < 8u * top_nodes; i += kBlock) lds_top[i] = a.wide[i];
-    __syncthreads();
+    const WideTree tree(a.lds_levels, a.nodes, a.wide, a.top_nodes, a.head_shift);
+    const WalkStack<2> stack(a.lds_levels, a.stack_levels, a.stack_overflow);
     const v4f *prep = reinterpret_cast<const v4f *>(a.prep);
     const ShadeSrc shade_src{a.prep, a.mat_index, a.mats, a.unit_n};
-    const uint32_t top_level = a.stack_levels - 1u;
-    const uint32_t head_shift = a.head_shift;
-    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
-    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
     const uint32_t lane = lane_id();
 
     RunPool pool;
@@ -181,25 +170,9 @@ __global__ __launch_bounds__(kBlock) void path_bvh4(const PathArgs a)
     int state = S_IDLE;
     bool walking = false;
     float closest = kInf;
-    uint32_t hit = kNoPrim, sp = 0, cur = 0, leaf_first = 0, leaf_count = 0;
+    uint32_t hit = kNoPrim, sp = 0;
+    WideAt at;
     f3 inv = mk(0.0f, 0.0f, 0.0f);
-    auto enter = [&](const uint32_t head) {  // head = first | count << head_shift (leaf, count > 0) or a wide node index (count 0)
-        const uint32_t first = head & ((1u << head_shift) - 1u), count = head >> head_shift;
-        cur = first;
-        leaf_first = first;
-        leaf_count = count;
-    };
-    auto push = [&](const float entry, const uint32_t head) {
-        const uint32_t at = min(sp, top_level);  // the host sized the stack from the wide tree: sp never passes top_level; the clamp keeps a wrong size inside the memory
-        if (at < lds_levels) {
-            lds_stack[(2u * at + 0u) * kBlock + threadIdx.x] = __float_as_uint(entry);
-            lds_stack[(2u * at + 1u) * kBlock + threadIdx.x] = head;
-        } else {
-            ovf[(2u * (at - lds_levels) + 0u) * ovf_stride] = __float_as_uint(entry);
-            ovf[(2u * (at - lds_levels) + 1u) * ovf_stride] = head;
-        }
-        sp = at + 1u;
-    };
 
     for (;;) {
         // ---- refill: every lane that is not walking shades the segment it finished, takes a record if its path ended, and starts its next walk
@@ -213,9 +186,9 @@ __global__ __launch_bounds__(kBlock) void path_bvh4(const PathArgs a)
                 inv = mk(1.0f / P.L.d.x, 1.0f / P.L.d.y, 1.0f / P.L.d.z);
                 sp = 0;
                 float entry;
-                if (slab_entry(P.L.o, inv, lds_root[0], lds_root[1], closest, entry)) {
-                    cur = 0;  // the wide root
-                    leaf_count = 0;
+                if (slab_entry(P.L.o, inv, tree.lds_root[0], tree.lds_root[1], closest, entry)) {
+                    at.cur = 0;  // the wide root
+                    at.leaf_count = 0;
                     walking = true;
                 } else {
                     state = S_HIT;
@@ -228,55 +201,21 @@ __global__ __launch_bounds__(kBlock) void path_bvh4(const PathArgs a)
         // ---- traverse: every iteration each walking lane handles one wide node; leaves are parked and run in batches
         for (uint32_t steps = 0;; ++steps) {
             bool need_pop = false;
-            if (state == S_TRAV && leaf_count == 0) {
-                const float4 *node = cur < top_nodes ? lds_top + 8u * cur : a.wide + 8u * static_cast<size_t>(cur);
-                const float4 minx = node[0], maxx = node[1], miny = node[2], maxy = node[3], minz = node[4], maxz = node[5], hq = node[6];
-                const uint32_t hd0 = __float_as_uint(hq.x), hd1 = __float_as_uint(hq.y), hd2 = __float_as_uint(hq.z), hd3 = __float_as_uint(hq.w);
-                float e0, e1, e2, e3;
-                const bool h0 = slab_child(P.L.o, inv, minx.x, maxx.x, miny.x, maxy.x, minz.x, maxz.x, closest, e0);  // (a wide node has at least two children)
-                const bool h1 = slab_child(P.L.o, inv, minx.y, maxx.y, miny.y, maxy.y, minz.y, maxz.y, closest, e1);
-                const bool h2 = slab_child(P.L.o, inv, minx.z, maxx.z, miny.z, maxy.z, minz.z, maxz.z, closest, e2) && hd2 != kWideEmpty;
-                const bool h3 = slab_child(P.L.o, inv, minx.w, maxx.w, miny.w, maxy.w, minz.w, maxz.w, closest, e3) && hd3 != kWideEmpty;
-                if (h3 && (h0 || h1 || h2)) push(e3, hd3);
-                if (h2 && (h0 || h1)) push(e2, hd2);
-                if (h1 && h0) push(e1, hd1);
-                if (h0 || h1 || h2 || h3)
-                    enter(h0 ? hd0 : (h1 ? hd1 : (h2 ? hd2 : hd3)));
-                else
-                    need_pop = true;
-            }
-            const uint32_t at_leaf = static_cast<uint32_t>(__builtin_popcountll(ballot(leaf_count > 0)));
-            const uint32_t at_inner = static_cast<uint32_t>(__builtin_popcountll(ballot(state == S_TRAV && leaf_count == 0)));
+            if (state == S_TRAV && at.leaf_count == 0) wide_step(tree, P.L.o, inv, closest, stack, sp, at, need_pop);
+            const uint32_t at_leaf = static_cast<uint32_t>(__builtin_popcountll(ballot(at.leaf_count > 0)));
+            const uint32_t at_inner = static_cast<uint32_t>(__builtin_popcountll(ballot(state == S_TRAV && at.leaf_count == 0)));
             const bool run_leaves = at_leaf > 0 && (at_inner == 0 || at_leaf >= kPathLeafBatch);
-            if (run_leaves && leaf_count > 0) {
-                for (uint32_t i = leaf_first; i < leaf_first + leaf_count; ++i) {
+            if (run_leaves && at.leaf_count > 0) {
+                for (uint32_t i = at.leaf_first; i < at.leaf_first + at.leaf_count; ++i) {
                     const v4f *tp = prep + 4 * static_cast<size_t>(i);
                     test_triangle(unpack(tp[0], tp[1], tp[2], tp[3]), P.L.o, P.L.d, i, closest, hit);
                 }
-                leaf_count = 0;
+                at.leaf_count = 0;
                 need_pop = true;
             }
-            if (need_pop) {
-                bool found = false;
-                while (sp > 0 && !found) {
-                    sp -= 1;
-                    uint32_t entry_bits, cand;
-                    if (sp < lds_levels) {
-                        entry_bits = lds_stack[(2u * sp + 0u) * kBlock + threadIdx.x];
-                        cand = lds_stack[(2u * sp + 1u) * kBlock + threadIdx.x];
-                    } else {
-                        entry_bits = ovf[(2u * (sp - lds_levels) + 0u) * ovf_stride];
-                        cand = ovf[(2u * (sp - lds_levels) + 1u) * ovf_stride];
-                    }
-                    if (closest >= __uint_as_float(entry_bits)) {  // the reference's box test at the visit (rvpt_bvh4.hip's header comment)
-                        enter(cand);
-                        found = true;
-                    }
-                }
-                if (!found) {
-                    state = S_HIT;
-                    walking = false;
-                }
+            if (need_pop && !wide_pop(tree, closest, stack, sp, at)) {
+                state = S_HIT;
+                walking = false;
             }
             if (ballot(state == S_TRAV) == 0) break;
             const uint32_t waiting = static_cast<uint32_t>(__builtin_popcountll(ballot(state == S_HIT)));
@@ -285,18 +224,14 @@ __global__ __launch_bounds__(kBlock) void path_bvh4(const PathArgs a)
     }
 }
 
-// query_bvh2's walk — intersect_bvh as the reference writes it, over the binary nodes: pop a node, test its box against the interval of that moment, a leaf's
+// walk_bvh2's walk (rvpt_query.hip) — intersect_bvh as the reference writes it, over the binary nodes: pop a node, test its box against the interval of that moment, a leaf's
 // triangles in order, an inner node's right child stacked and its left child next — under the same loop.  One word per stack slot (the node index).
 template <int FORM>
 __global__ __launch_bounds__(kBlock) void path_bvh2(const PathArgs a)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
-    const uint32_t lds_levels = a.lds_levels;
+    const WalkStack<1> stack(a.lds_levels, a.stack_levels, a.stack_overflow);
     const v4f *prep = reinterpret_cast<const v4f *>(a.prep);
     const ShadeSrc shade_src{a.prep, a.mat_index, a.mats, a.unit_n};
-    const uint32_t top_level = a.stack_levels - 1u;
-    uint32_t *const ovf = a.stack_overflow + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x);
-    const size_t ovf_stride = static_cast<size_t>(gridDim.x) * kBlock;
     const uint32_t lane = lane_id();
 
     RunPool pool;
@@ -337,12 +272,7 @@ __global__ __launch_bounds__(kBlock) void path_bvh2(const PathArgs a)
                             test_triangle(unpack(tp[0], tp[1], tp[2], tp[3]), P.L.o, P.L.d, i, closest, hit);
                         }
                     } else {
-                        const uint32_t at = min(sp, top_level);  // (the tree's height bounds the pushes of a root-to-leaf path; the clamp as in path_bvh4)
-                        if (at < lds_levels)
-                            lds_stack[at * kBlock + threadIdx.x] = first + 1u;
-                        else
-                            ovf[(at - lds_levels) * ovf_stride] = first + 1u;
-                        sp = at + 1u;
+                        stack.push(sp, first + 1u);  // (the tree's height bounds the pushes of a root-to-leaf path)
                         cur = first;
                         pop = false;
                     }
@@ -352,8 +282,7 @@ __global__ __launch_bounds__(kBlock) void path_bvh2(const PathArgs a)
                         state = S_HIT;
                         walking = false;
                     } else {
-                        sp -= 1;
-                        cur = sp < lds_levels ? lds_stack[sp * kBlock + threadIdx.x] : ovf[(sp - lds_levels) * ovf_stride];
+                        cur = stack.pop(sp);
                     }
                 }
             }
@@ -365,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void path_bvh2(const PathArgs a)
 }
 
 // Brute force, in work-group-synchronous ROUNDS: at a round's start every lane without a path takes a record (each wave deals its own runs); then the prepared
-// triangles stream through LDS in tiles of kQueryTileTris, as query_brute streams them, and every lane that holds a path runs its current segment over each
+// triangles stream through LDS in tiles of kQueryTileTris, as walk_brute streams them, and every lane that holds a path runs its current segment over each
 // tile in index order; then it shades.  The work-group leaves when a round starts with no path in any of its lanes.  No culls: the packet kernel's rest on a
 // camera and a block of pixels.
 template <int FORM>

@@ -40,17 +40,16 @@ struct QueryPlan {
     size_t stack_words;    // uint32 words of the global part of the stack (0: none); the launch also needs one claim word, which precedes them
 };
 
-// The launch shape for n records: a persistent grid sized from occupancy for the tree walks (the overflow stack is bounded by the grid, not by n), one
-// work-group per 256 records for the brute-force kernel.  k > 1 (RVPT_HIP_FORMAT_RAY_HITS_NEAREST(k)): n counts GROUPS of k records, one ray each, and the
-// occupancy is that of the k-nearest instance the launch will use.
-hipError_t query_plan(const QueryScene &scene, uint32_t n, int num_cus, QueryPlan *plan, uint32_t k = 1);
-// Answers records[0 .. n) in place on `stream` — with k > 1 the n groups records[0 .. n * k), the plan made with the same k.  `scratch` holds 64 words (the
-// first is the claim counter, zeroed here) followed by plan.stack_words words.
-hipError_t query_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n, uint32_t k = 1);
+// What a ray query gathers along its walk: Hits — the closest or any hit (RVPT_HIP_FORMAT_RAY_HITS), with k > 1 the k nearest hits
+// (RVPT_HIP_FORMAT_RAY_HITS_NEAREST(k)) —, or Crossings — one rvpt_ray_crossings per ray (RVPT_HIP_FORMAT_RAY_CROSSINGS; k is 1, scene.unit_n must be set).
+enum class QueryForm : uint32_t { Hits = 0, Crossings = 1 };
 
-// RAY CROSSINGS (RVPT_HIP_FORMAT_RAY_CROSSINGS): one rvpt_ray_crossings per ray, the same three kinds of walk with the interval fixed at tmax; the plan and
-// the scratch are a ray query's.  scene.unit_n must be set.
-hipError_t cross_plan(const QueryScene &scene, uint32_t n, int num_cus, QueryPlan *plan);
-hipError_t cross_launch(hipStream_t stream, const QueryScene &scene, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n);
+// The launch shape for n records: a persistent grid sized from occupancy for the tree walks (the overflow stack is bounded by the grid, not by n), one
+// work-group per 256 records for the brute-force kernel.  k > 1: n counts GROUPS of k records, one ray each.  The occupancy is that of the instance the
+// launch will use.
+hipError_t query_plan(const QueryScene &scene, QueryForm form, uint32_t n, int num_cus, QueryPlan *plan, uint32_t k = 1);
+// Answers records[0 .. n) in place on `stream` — with k > 1 the n groups records[0 .. n * k), the plan made with the same form and k.  `scratch` holds 64 words
+// (the first is the claim counter, zeroed here) followed by plan.stack_words words.
+hipError_t query_launch(hipStream_t stream, const QueryScene &scene, QueryForm form, const QueryPlan &plan, uint32_t *scratch, void *records, uint32_t n, uint32_t k = 1);
 
 }  // namespace rv

@@ -224,7 +224,7 @@ def test_a_deep_tree(native, oracle):
 
 
 def test_the_binary_walk(native, oracle, default_scene, whole_set, monkeypatch):
-    """The laboratory build with the caller-layout knob holds no wide form: cross_bvh2 on 600 records of the whole set"""
+    """The laboratory build with the caller-layout knob holds no wide form: walk_bvh2<Crossings> on 600 records of the whole set"""
     monkeypatch.setenv("RVPT_HIP_BVH_CALLER_LAYOUT", "1")
     records, want = whole_set[0]
     ctx = context(native, native.TRAVERSAL_BVH, default_scene, lab=True)

@@ -179,7 +179,7 @@ def chain_scene():
 
 
 def test_the_binary_walk(native, oracle, default_scene, sweep, monkeypatch):
-    """The laboratory build with the caller-layout knob holds no wide form: query_bvh2's k-nearest instances on the default scene and, past the 8 LDS levels,
+    """The laboratory build with the caller-layout knob holds no wide form: walk_bvh2<Nearest<CAP>>, every CAP, on the default scene and, past the 8 LDS levels,
     on the 48-level mirrored chain, at k = 3 and 8"""
     monkeypatch.setenv("RVPT_HIP_BVH_CALLER_LAYOUT", "1")
     ctx = context(native, native.TRAVERSAL_BVH, default_scene, lab=True)

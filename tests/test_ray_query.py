@@ -141,7 +141,7 @@ def test_the_overflow_stack(native, oracle, shape, loose):
 
 
 def test_no_wide_form(native, default_scene, ray_set, monkeypatch):
-    """Case 3.  The laboratory build with the caller-layout knob holds no wide form: query_bvh2 gives case 1's bytes."""
+    """Case 3.  The laboratory build with the caller-layout knob holds no wide form: walk_bvh2<Closest> gives case 1's bytes."""
     records, want = ray_set
     monkeypatch.setenv("RVPT_HIP_BVH_CALLER_LAYOUT", "1")
     got, state = ask(native, native.TRAVERSAL_BVH, default_scene, records, lab=True)

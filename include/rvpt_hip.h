@@ -95,7 +95,10 @@ extern "C" {
                                      Still 8, no new symbol: rvpt_hip_read with the format RVPT_HIP_FORMAT_BOX_OVERLAPS (9) or a format
                                      RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k) (65 .. 68) — until then the "unknown format" error — is a BOX QUERY: `dst` holds
                                      groups of k rvpt_box_overlap records, a closed box in the first, the count of the triangles that meet it and the
-                                     smallest of their numbers out */
+                                     smallest of their numbers out.  Still 8, no new symbol: rvpt_hip_read with the format
+                                     RVPT_HIP_FORMAT_SPHERE_SWEEPS (10) — until then the "unknown format" error — is a SPHERE SWEEP: `dst` holds
+                                     rvpt_sphere_sweep records, a sphere and the motion of its centre in, the time of its first contact with the mesh,
+                                     the triangle and the barycentric pair out */
 
 /* ---- POD layouts: byte-identical to the reference's GPU buffers ------------------ */
 
@@ -238,6 +241,15 @@ typedef struct rvpt_box_overlap {
 
 #define RVPT_HIP_BOX_MAX_GROUP 4u /* per call: the largest k of a box query's groups */
 #define RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k) (64 + (k))       /* k = 1 .. RVPT_HIP_BOX_MAX_GROUP: formats 65 .. 68; dst: n groups of k rvpt_box_overlap listing 4k - 1 numbers (BOX OVERLAPS at rvpt_hip_read) */
+
+#define RVPT_HIP_FORMAT_SPHERE_SWEEPS 10 /* dst: rvpt_sphere_sweep[dst_bytes / 48], in and out (SPHERE SWEEPS at rvpt_hip_read) */
+
+/* One moving sphere of a query and its first contact (48 B = three float4; no reference counterpart: the reference asks its scene nothing but its camera's paths). */
+typedef struct rvpt_sphere_sweep {
+    float org[3]; float radius;                 /* in: the centre at t = 0; radius >= 0 */
+    float dir[3]; float tmax;                   /* in: the centre is org + t*dir, t in [0, tmax] (closed; +inf allowed); dir need not be unit */
+    float t; uint32_t prim; float u; float v;   /* out: laid out as the out quad of an rvpt_ray_hit */
+} rvpt_sphere_sweep;
 
 #define RVPT_HIP_FORMAT_TRIANGLES 5      /* dst: rvpt_triangle[n_tris], out: the stored rows in update order (TRIANGLES at rvpt_hip_read) */
 #define RVPT_HIP_FORMAT_SURFACE_POINTS 6 /* dst: rvpt_surface_point[dst_bytes / 48], in and out (SURFACE POINTS at rvpt_hip_read) */
@@ -890,6 +902,64 @@ int rvpt_hip_wait_for(rvpt_hip_ctx *ctx, uint64_t timeout_ns);
  *   rvpt_hip_wait, leaves untouched what a point query leaves untouched — a frame dispatched afterwards is bit for bit the frame dispatched without it — and
  *   answers on the scene as the last update form left it: plain, guarded, sparse, pose or skin.
  * DESIGN.md 5.28 has the kernels, why a walk that prunes by step 1 returns exactly A, and what was measured (profiles/box_overlaps.txt).
+ *
+ * SPHERE SWEEPS — when and where the caller's own moving spheres first touch the mesh, in place:
+ *
+ *     rvpt_hip_read(ctx, RVPT_HIP_FORMAT_SPHERE_SWEEPS, records, n * sizeof(rvpt_sphere_sweep));
+ *
+ * The sweep form of a query: a character controller's step, a camera boom, a projectile with a size, an object dropped onto the mesh as it is posed or skinned
+ * on the device.  `dst` then holds n rvpt_sphere_sweep records: each comes in as a sphere and the motion of its centre (org, radius, dir, tmax) — the centre is
+ * org + t*dir for t in [0, tmax], closed; dir need not be a unit vector, so t is in units of dir — and goes out as the first contact (t, prim, u, v), laid out
+ * as the out quad of an rvpt_ray_hit.  The in quads are never written.
+ * - THE ANSWER IS DEFINED WITHOUT REFERENCE TO ANY WALK, as a point query's is.  Every stored triangle i gets a candidate (t_i, prim_i), or none, by the
+ *   arithmetic below; the answer is the lexicographically smallest candidate.  A NaN never wins (no candidate's t is one), and among equal t the smaller
+ *   reported prim wins.  The numbering of prim is a ray query's (THE NUMBERING OF prim above): the stored order after an ordinary upload, the caller's order
+ *   after a build form.  The answer is therefore the same on every kind of context, after every builder and on every tree.
+ * - PER-TRIANGLE ARITHMETIC.  binary32 throughout; every product, sum, quotient and square root is rounded on its own, no FMA; the square root is the
+ *   correctly rounded one.  a, b, c = vert0..2 of the stored row; p = org, d = dir, r = radius, T = tmax; dot(x,y) = (x0*y0 + x1*y1) + x2*y2 and
+ *   cross(x,y) = (x1*y2 - x2*y1, x2*y0 - x0*y2, x0*y1 - x1*y0).  Per record, once: inv_k = 1/d_k on every axis with d_k != 0, rr = r*r, A = dot(d,d).
+ *   Every "max" and "min" below that moves a time is the select written next to it, so that a NaN moves nothing and a zero keeps its sign.
+ *   1. OWN BOX.  lo, hi are the exact min / max of a, b, c per axis (fminf / fmaxf; the vertices are finite).  A triangle with a non-finite vertex component
+ *      takes no part.  The box is inflated by one rounded operation per side, L = lo - r and H = hi + r.  t_in = 0 and t_out = T; then per axis k:
+ *        d_k == 0:  reject if p_k < L_k or p_k > H_k — two comparisons, no arithmetic;
+ *        otherwise: t1 = (L_k - p_k)*inv_k, t2 = (H_k - p_k)*inv_k; (near, far) = d_k > 0 ? (t1, t2) : (t2, t1);
+ *                   t_in = near > t_in ? near : t_in;   t_out = far < t_out ? far : t_out.
+ *      Reject unless t_in <= t_out and t_in < +inf.  A NaN among near and far — 0 * inf from a denormal d_k, or, where the same test runs on a node of a tree,
+ *      a node's side that is a NaN — passes neither select and rejects nothing.
+ *   2. CONTACT TIME t_tri: the smallest time over seven features, each a number in [0, T] or nothing.  The ROOT of (c0, b0, a0) is
+ *      t = c0 / (sqrt(b0*b0 - a0*c0) - b0), taken iff c0 > 0, b0 < 0, a0 > 0, b0*b0 - a0*c0 >= 0, and 0 <= t <= T: the smaller root of a0*t*t + 2*b0*t + c0
+ *      for a centre that starts outside and approaches, in the form without cancellation.
+ *      For each pair (x0, x1) = (a, b), (b, c), (c, a), with m = p - x0, e = x1 - x0, B = dot(m,d), C = dot(m,m) - rr:
+ *        the VERTEX x0:     C <= 0 gives 0; otherwise the ROOT of (C, B, A);
+ *        the EDGE x0 -> x1: ee = dot(e,e), md = dot(m,e), nd = dot(d,e); ca = ee*A - nd*nd, cb = ee*B - nd*md, cc = ee*C - md*md (the ray against the infinite
+ *                           cylinder, reduced).  Nothing if ee == 0.  cc <= 0 with 0 <= md <= ee (an initial overlap) gives 0; otherwise the ROOT of
+ *                           (cc, cb, ca), accepted only where the contact projects into the edge: s = md + t*nd, 0 <= s <= ee.
+ *      The FACE: n = cross(b - a, c - a), nn = dot(n,n); nothing if nn is not > 0.  h = dot(p - a, n), rn = r*sqrt(nn), hs = |h|, dn = dot(d,n),
+ *        dns = h > 0 ? dn : -dn.  hs <= rn gives the time 0; otherwise, iff hs > rn and dns < 0, the time t = (rn - hs)/dns — the plane pushed out by r*|n|
+ *        towards the centre's side — taken iff 0 <= t <= T.  The time is accepted iff closest_point(a, b, c, p + d*t) of NEAREST POINTS — one product and one sum
+ *        per component for the centre, then the regions in their order — decides region 0, the face.
+ *      Together the seven are the Minkowski sum of the triangle and the ball: a sphere that already overlaps the triangle reports 0.
+ *   3. REPORTED TIME.  t_i = t_in > t_tri ? t_in : t_tri, a candidate iff t_tri exists and t_i < +inf.  It is the record's t.  (u, v) is the pair
+ *      closest_point(a, b, c, p + d*t_i) computes, before its clamp.  The out quad therefore pipes into an rvpt_surface_point as a point hit's last quad does:
+ *      SURFACE POINTS gives the contact point and the stored normal.
+ *   4. dir = 0, 0, 0 is a valid record: every axis takes the two comparisons, no ROOT exists (A = 0), and only the candidates at t = 0 remain.
+ * - WHY STEP 1 IS THERE: it makes pruning exact, as the clamp does for NEAREST POINTS.  The box of every node above a triangle contains its finite vertices:
+ *   node.lo <= lo and node.hi >= hi.  Rounding is monotone, so the inflated node box contains the inflated own box IN FLOATS, and every operation of step 1 is
+ *   monotone in L and H.  THE LEMMA: run on the node's box, step 1 passes whenever it passes on the own box, and t_in(node) <= t_in(own) <= t_i.  A walk that
+ *   skips a node iff its step 1 rejects or t_in(node) > best — strictly: at equality a smaller prim may still lie below — returns the definition's bytes on any
+ *   tree whose boxes contain their vertices, the caller's loose boxes included, in any visiting order (DESIGN.md 5.30 has the proof).
+ * - A ZERO-AREA TRIANGLE gets what this arithmetic gives: its face is skipped (nn is 0), its edges and vertices still answer.
+ * - WHAT IS NOT PROMISED.  t is the ROUNDED contact time: near a graze the discriminant's cancellation decides between a contact and a miss, and t_in may lift
+ *   t above t_tri by the rounding of the own box's slab test.  DESIGN.md 5.30 has the measured distance between the sphere at t and the triangle.
+ * - INVALID RECORDS AND MISSES.  A record is invalid if a component of org or dir is non-finite, if radius is NaN, negative or infinite, or if tmax is NaN
+ *   or < 0 (-0.0 is 0); that is decided before any walk.  Invalid records and misses go out as t = the bits of tmax as given, prim = 0xFFFFFFFF, u = v = 0.
+ * - Everything else is a point query's rule: the call needs a scene — before any full upload it is RVPT_HIP_ERR_INVALID; the empty scene answers every record
+ *   with a miss — and no rvpt_hip_set_frame; dst_bytes must be a multiple of 48, else RVPT_HIP_ERR_INVALID; dst_bytes == 0 is a successful no-op; fewer than
+ *   2^32 records per call; `dst` is host memory or 16-byte aligned device memory of the context's GPU, another GPU's memory is an error naming both devices,
+ *   and in every error case `dst` is untouched; host records go through the staging buffer and only the out quad travels back; the call is LOCAL under a
+ *   communicator, implies rvpt_hip_wait, leaves untouched what a point query leaves untouched — a frame dispatched afterwards is bit for bit the frame
+ *   dispatched without it — and answers on the scene as the last update form left it: plain, guarded, sparse, pose or skin.
+ * DESIGN.md 5.30 has the kernels, the lemma's proof and what was measured (profiles/sphere_sweeps.txt).
  *
  * TRIANGLES — the whole mesh as it now stands:
  *

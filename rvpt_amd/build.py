@@ -20,9 +20,10 @@ SOURCES = [_PKG / "csrc" / n for n in (
     "rvpt_paths.hip",  # path queries (rvpt_hip_read with FORMAT_RAY_PATHS and FORMAT_RAY_PATHS_MODE): those walks under shade() / shade_generic(), kernels of their own, likewise
     "rvpt_nearest.hip",  # point queries (rvpt_hip_read with FORMAT_NEAREST_POINTS): a walk that prunes by distance, kernels of its own, likewise
     "rvpt_box.hip",  # box queries (rvpt_hip_read with FORMAT_BOX_OVERLAPS and FORMAT_BOX_OVERLAPS_K): a walk that prunes by six comparisons, kernels of its own, likewise
+    "rvpt_sweep.hip",  # sphere sweeps (rvpt_hip_read with FORMAT_SPHERE_SWEEPS): a walk that prunes by the entry time into the inflated boxes, kernels of its own, likewise
     "rvpt_surface.hip",  # the geometry read-back (rvpt_hip_read with FORMAT_TRIANGLES and FORMAT_SURFACE_POINTS): one record kernel, the row scatter launched from there, likewise
 )]
-HEADERS = [_PKG / "csrc" / "rvpt_ctx.h", _PKG / "csrc" / "rvpt_box.h", _PKG / "csrc" / "rvpt_scene_forms.h", _PKG / "csrc" / "rvpt_surface.h", _PKG / "csrc" / "rvpt_nearest.h", _PKG / "csrc" / "rvpt_paths.h", _PKG / "csrc" / "rvpt_query.h", _PKG / "csrc" / "rvpt_walk.h", _PKG / "csrc" / "rvpt_frames.h", _PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
+HEADERS = [_PKG / "csrc" / "rvpt_ctx.h", _PKG / "csrc" / "rvpt_box.h", _PKG / "csrc" / "rvpt_sweep.h", _PKG / "csrc" / "rvpt_scene_forms.h", _PKG / "csrc" / "rvpt_surface.h", _PKG / "csrc" / "rvpt_nearest.h", _PKG / "csrc" / "rvpt_paths.h", _PKG / "csrc" / "rvpt_query.h", _PKG / "csrc" / "rvpt_walk.h", _PKG / "csrc" / "rvpt_frames.h", _PKG / "csrc" / "rvpt_build.h", _PKG / "csrc" / "rvpt_refit.h", _PKG / "csrc" / "bvh_wide.h", _PKG / "csrc" / "rvpt_kernels.h", _PKG / "csrc" / "rvpt_packets.h", _PKG / "csrc" / "rvpt_early_out.h", _PKG / "csrc" / "rvpt_device.h", _PKG / "csrc" / "rvpt_math.h", _PKG / "csrc" / "rvpt_rect.h",
            _PKG / "csrc" / "rvpt_vis.h", _PKG.parent / "include" / "rvpt_hip.h", _PKG.parent / "include" / "rvpt_hip_lab.h"]
 
 # -ffp-contract=off: the arithmetic specification fixes where FMAs happen; applies to the
@@ -143,6 +144,7 @@ HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selft
                 "host_selftest_multi_hit": ["host_selftest_multi_hit.cpp", "rvpt_host.cpp"],
                 "host_selftest_nearest_k": ["host_selftest_nearest_k.cpp", "rvpt_host.cpp"],
                 "host_selftest_box": ["host_selftest_box.cpp", "rvpt_host.cpp"],
+                "host_selftest_sweep": ["host_selftest_sweep.cpp", "rvpt_host.cpp"],
                 "host_selftest_crossings": ["host_selftest_crossings.cpp", "rvpt_host.cpp"],
                 "host_selftest_paths": ["host_selftest_paths.cpp", "rvpt_host.cpp"],
                 "host_selftest_path_modes": ["host_selftest_path_modes.cpp", "rvpt_host.cpp"],
@@ -151,11 +153,12 @@ HOST_TARGETS = {"rvpt_render": ["render_main.cpp", "rvpt_host.cpp"], "host_selft
                 "host_row_boxes": ["host_row_boxes.cpp"],  # (rvpt_vis.h alone: the row boxes' table for scenes given in files, tests/test_row_boxes.py)
                 "host_row_caps": ["host_row_caps.cpp"],  # (rvpt_vis.h alone: the row caps' table for scenes given in files, tests/test_row_caps.py)
                 "host_frame_runs": ["host_frame_runs.cpp"],  # (rvpt_packets.h alone: the item map of listed launches in frame-run order, tests/test_frame_runs_host.py)
+                "host_sweep_table": ["host_sweep_table.cpp"],  # (rvpt_sweep.h alone: a sphere sweep's per-triangle arithmetic for records given in files, tests/test_sweep_host.py)
                 "host_scene_forms": ["host_scene_forms.cpp"]}  # (rvpt_scene_forms.h alone: which form of upload_scene a call is, tests/test_scene_forms_host.py)
-HOST_NEEDS_HIP = {"host_selftest_frames", "host_selftest_box", "host_selftest_rays", "host_selftest_multi_hit", "host_selftest_nearest_k", "host_selftest_crossings", "host_selftest_paths", "host_selftest_path_modes", "host_selftest_nearest", "host_selftest_surface"}  # targets that allocate device memory themselves (its `--gpu` case): HIP's host API, still compiled by g++
+HOST_NEEDS_HIP = {"host_selftest_frames", "host_selftest_box", "host_selftest_sweep", "host_selftest_rays", "host_selftest_multi_hit", "host_selftest_nearest_k", "host_selftest_crossings", "host_selftest_paths", "host_selftest_path_modes", "host_selftest_nearest", "host_selftest_surface"}  # targets that allocate device memory themselves (its `--gpu` case): HIP's host API, still compiled by g++
 
 
-HOST_WITH_HIPCC = {"host_row_boxes", "host_row_caps", "host_frame_runs", "host_scene_forms"}  # targets that include the kernels' host + device headers (csrc/): the host half of a HIP compilation, no device code, no library
+HOST_WITH_HIPCC = {"host_row_boxes", "host_sweep_table", "host_row_caps", "host_frame_runs", "host_scene_forms"}  # targets that include the kernels' host + device headers (csrc/): the host half of a HIP compilation, no device code, no library
 
 
 def hipcc_host_cmd(sources, out, extra=()) -> list:
@@ -170,10 +173,10 @@ def _hip_host_flags() -> list:
 
 def build_host(force: bool = False) -> Path:
     """Compile the C++ host layer (rvpt_amd/host/: the mirror of the reference's class RVPT above the C ABI) with
-    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames`, `host_selftest_guard`, `host_selftest_sparse`, `host_selftest_pose`, `host_selftest_pose_guard`, `host_selftest_skin`, `host_selftest_skin_guard`, `host_selftest_rays`, `host_selftest_multi_hit`, `host_selftest_nearest_k`, `host_selftest_box`, `host_selftest_paths`, `host_selftest_path_modes`, `host_selftest_nearest` and `host_selftest_surface`."""
+    g++ and link it against the in-tree librvpt_hip.so: the headless CLI `rvpt_render` and the GPU-free `host_selftest`, `host_selftest_build`, `host_selftest_build_ploc`, `host_selftest_build_sah`, `host_selftest_frames`, `host_selftest_guard`, `host_selftest_sparse`, `host_selftest_pose`, `host_selftest_pose_guard`, `host_selftest_skin`, `host_selftest_skin_guard`, `host_selftest_rays`, `host_selftest_multi_hit`, `host_selftest_nearest_k`, `host_selftest_box`, `host_selftest_sweep`, `host_selftest_paths`, `host_selftest_path_modes`, `host_selftest_nearest` and `host_selftest_surface`."""
     build_native()
     HOST_BIN_DIR.mkdir(exist_ok=True)
-    srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h", _PKG / "csrc" / "rvpt_vis.h", _PKG / "csrc" / "rvpt_scene_forms.h"]
+    srcs = list(HOST_DIR.glob("*.cpp")) + list(HOST_DIR.glob("*.h")) + [_PKG.parent / "include" / "rvpt_hip.h", _PKG / "csrc" / "rvpt_vis.h", _PKG / "csrc" / "rvpt_scene_forms.h", _PKG / "csrc" / "rvpt_sweep.h", _PKG / "csrc" / "rvpt_nearest.h"]
     newest = max(p.stat().st_mtime for p in srcs + [LIB_PATH])
     for name, files in HOST_TARGETS.items():
         out = HOST_BIN_DIR / name

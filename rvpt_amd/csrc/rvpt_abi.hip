@@ -36,6 +36,7 @@
 #include "rvpt_query.h"
 #include "rvpt_nearest.h"
 #include "rvpt_box.h"
+#include "rvpt_sweep.h"
 #include "rvpt_surface.h"
 #include "rvpt_paths.h"
 #include "rvpt_packets.h"
@@ -59,6 +60,10 @@ static_assert(RVPT_HIP_BOX_MAX_GROUP == rv::kBoxMaxGroup, "the k of a box query'
 static_assert(sizeof(rvpt_box_overlap) == rv::kBoxRecordBytes && offsetof(rvpt_box_overlap, prim_from) == 12 && offsetof(rvpt_box_overlap, hi) == 16 &&
                   offsetof(rvpt_box_overlap, flags) == 28 && offsetof(rvpt_box_overlap, count) == 32 && offsetof(rvpt_box_overlap, prim) == 36,
               "a box query's record: three float4 (rvpt_box.hip)");
+static_assert(sizeof(rvpt_sphere_sweep) == rv::kSweepRecordBytes && sizeof(rvpt_sphere_sweep) == sizeof(rvpt_ray_hit) && offsetof(rvpt_sphere_sweep, radius) == 12 &&
+                  offsetof(rvpt_sphere_sweep, dir) == 16 && offsetof(rvpt_sphere_sweep, tmax) == 28 && offsetof(rvpt_sphere_sweep, t) == 32 && offsetof(rvpt_sphere_sweep, prim) == 36 &&
+                  offsetof(rvpt_sphere_sweep, u) == 40 && offsetof(rvpt_sphere_sweep, v) == 44,
+              "a sphere sweep's record: three float4 (rvpt_sweep.hip), its out quad laid out as a ray record's, and it shares query_records");
 static_assert(sizeof(rvpt_ray_hit) == rv::kQueryRecordBytes && offsetof(rvpt_ray_hit, tmax) == 12 && offsetof(rvpt_ray_hit, dir) == 16 && offsetof(rvpt_ray_hit, flags) == 28 &&
                   offsetof(rvpt_ray_hit, t) == 32 && offsetof(rvpt_ray_hit, prim) == 36 && offsetof(rvpt_ray_hit, u) == 40 && offsetof(rvpt_ray_hit, v) == 44,
               "a ray query's record: three float4 (rvpt_query.hip)");
@@ -1474,13 +1479,14 @@ int rvpt_hip_gather(rvpt_hip_ctx *ctx, void *dst_dev_rgba32f)
 // RecordKind::Boxes (RVPT_HIP_FORMAT_BOX_OVERLAPS, BOX OVERLAPS): a point query's scene under the kernels of rvpt_box.hip; `hits` is 0 for format 9 and for
 // RVPT_HIP_FORMAT_BOX_OVERLAPS_K(1), the same call, and k for RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k), k > 1 — groups of k records, one box each; only the third quad
 // of a record is out.
-enum class RecordKind { Rays, Paths, Points, Surface, Crossings, Boxes };
+// RecordKind::Sweeps (RVPT_HIP_FORMAT_SPHERE_SWEEPS, SPHERE SWEEPS): a point query's scene under the kernels of rvpt_sweep.hip; the third quad of a record is out.
+enum class RecordKind { Rays, Paths, Points, Surface, Crossings, Boxes, Sweeps };
 static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const RecordKind kind, const uint32_t path_mode = rv::kPathModeKajiya, const uint32_t hits = 0)
 {
     const bool paths = kind == RecordKind::Paths, points = kind == RecordKind::Points, surface = kind == RecordKind::Surface, crossings = kind == RecordKind::Crossings;
-    const bool boxes = kind == RecordKind::Boxes;
-    const char *what = boxes ? "box" : surface ? "surface" : (points ? "point" : (paths ? "path" : (crossings ? "crossing" : "ray")));
-    const char *record = boxes ? "rvpt_box_overlap" : surface ? "rvpt_surface_point" : (points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : (crossings ? "rvpt_ray_crossings" : "rvpt_ray_hit")));
+    const bool boxes = kind == RecordKind::Boxes, sweeps = kind == RecordKind::Sweeps;
+    const char *what = sweeps ? "sweep" : boxes ? "box" : surface ? "surface" : (points ? "point" : (paths ? "path" : (crossings ? "crossing" : "ray")));
+    const char *record = sweeps ? "rvpt_sphere_sweep" : boxes ? "rvpt_box_overlap" : surface ? "rvpt_surface_point" : (points ? "rvpt_point_hit" : (paths ? "rvpt_ray_path" : (crossings ? "rvpt_ray_crossings" : "rvpt_ray_hit")));
     static_assert(sizeof(rvpt_ray_crossings) == sizeof(rvpt_ray_hit) && offsetof(rvpt_ray_crossings, front) == offsetof(rvpt_ray_hit, t), "a crossing record is laid out as a ray record");
     const size_t out_offset = surface ? offsetof(rvpt_surface_point, point) : (points ? offsetof(rvpt_point_hit, closest) : offsetof(rvpt_ray_hit, t));  // where a record's out fields begin
     if (hits && boxes && dst_bytes % (sizeof(rvpt_box_overlap) * hits))
@@ -1522,7 +1528,9 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
     const uint32_t groups_of = hits ? hits : 1u;  // records per ray, per point or per box
     const rv::QueryForm ray_form = crossings ? rv::QueryForm::Crossings : rv::QueryForm::Hits;
     rv::QueryPlan plan{};
-    if (boxes)
+    if (sweeps)
+        HIP_TRY(ctx, rv::sweep_plan(nearest, static_cast<uint32_t>(n), ctx->num_cus, &plan));
+    else if (boxes)
         HIP_TRY(ctx, rv::box_plan(nearest, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
     else if (points)
         HIP_TRY(ctx, rv::nearest_plan(nearest, static_cast<uint32_t>(n / groups_of), ctx->num_cus, &plan, groups_of));
@@ -1553,7 +1561,9 @@ static int query_records(rvpt_hip_ctx *ctx, void *dst, size_t dst_bytes, const R
         mesh.tris = ctx->d_tris, mesh.unit_n = ctx->d_unit_n, mesh.mat_index = ctx->d_mat_index;
         mesh.inv_perm = permuted ? ctx->d_surface_inv : nullptr, mesh.n_tris = scene.n_tris;
         HIP_TRY(ctx, rv::surface_launch(ctx->stream, mesh, records, static_cast<uint32_t>(n)));
-    } else if (boxes)
+    } else if (sweeps)
+        HIP_TRY(ctx, rv::sweep_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n)));
+    else if (boxes)
         HIP_TRY(ctx, rv::box_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
     else if (points)
         HIP_TRY(ctx, rv::nearest_launch(ctx->stream, nearest, plan, ctx->d_query_scratch, records, static_cast<uint32_t>(n / groups_of), groups_of));
@@ -1615,6 +1625,7 @@ int rvpt_hip_read(rvpt_hip_ctx *ctx, int format, void *dst, size_t dst_bytes)
     if (format == RVPT_HIP_FORMAT_BOX_OVERLAPS || format == RVPT_HIP_FORMAT_BOX_OVERLAPS_K(1)) return query_records(ctx, dst, dst_bytes, RecordKind::Boxes);  // k = 1 IS format 9, its messages included; local as well
     if (format > RVPT_HIP_FORMAT_BOX_OVERLAPS_K(1) && format <= static_cast<int>(RVPT_HIP_FORMAT_BOX_OVERLAPS_K(RVPT_HIP_BOX_MAX_GROUP)))  // the longer lists of a box query; local as well
         return query_records(ctx, dst, dst_bytes, RecordKind::Boxes, rv::kPathModeKajiya, static_cast<uint32_t>(format) - RVPT_HIP_FORMAT_BOX_OVERLAPS_K(0u));
+    if (format == RVPT_HIP_FORMAT_SPHERE_SWEEPS) return query_records(ctx, dst, dst_bytes, RecordKind::Sweeps);  // local as well
     if (format == RVPT_HIP_FORMAT_RAY_HITS || format == RVPT_HIP_FORMAT_RAY_PATHS || format == RVPT_HIP_FORMAT_NEAREST_POINTS)  // local even with a communicator: every rank holds the whole scene
         return query_records(ctx, dst, dst_bytes,
                              format == RVPT_HIP_FORMAT_NEAREST_POINTS ? RecordKind::Points : (format == RVPT_HIP_FORMAT_RAY_PATHS ? RecordKind::Paths : RecordKind::Rays));

@@ -54,55 +54,9 @@ struct NearestPoint {
     bool valid;
 };
 
-struct Closest {
-    f3 q;
-    float d2, u, v;
-    uint32_t region;
-};
-
 __device__ __forceinline__ bool finite_(const float x) { return __builtin_fabsf(x) < kInf; }  // false for NaN and +-inf
 
-// (x0*y0 + x1*y1) + x2*y2, three products and two sums, each rounded (rv::dot of rvpt_math.h is the FUSED one: not used here)
-__device__ __forceinline__ float dot_rounded(const f3 a, const f3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-// the IEEE quotient; a quotient whose divisor is 0 is taken as 0
-__device__ __forceinline__ float quotient(const float num, const float den) { return den == 0.0f ? 0.0f : num / den; }
-__device__ __forceinline__ float clamp_keep_nan(const float q, const float lo, const float hi) { return q < lo ? lo : (q > hi ? hi : q); }
-
-// The candidate of one triangle (a, b, c) for the point p: Ericson's point-triangle test, its regions tested in the specified order — written as selects over
-// the seven predicates, which picks the first that holds exactly as the chain of ifs does — then q = (a + ab*u) + ac*v clamped into the triangle's own box.
-// Two quotients at most (the face's u and v); every other region has one or none, and their operands are selected before the divide.
-__device__ __forceinline__ Closest closest_point(const f3 a, const f3 b, const f3 c, const f3 p)
-{
-    const f3 ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c;
-    const float d1 = dot_rounded(ab, ap), d2 = dot_rounded(ac, ap), d3 = dot_rounded(ab, bp), d4 = dot_rounded(ac, bp), d5 = dot_rounded(ab, cp), d6 = dot_rounded(ac, cp);
-    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-    const float e1 = d4 - d3, e2 = d5 - d6;
-    const bool r1 = d1 <= 0.0f && d2 <= 0.0f;
-    const bool r2 = d3 >= 0.0f && d4 <= d3;
-    const bool r4 = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
-    const bool r3 = d6 >= 0.0f && d5 <= d6;
-    const bool r5 = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
-    const bool r6 = va <= 0.0f && e1 >= 0.0f && e2 >= 0.0f;
-    const uint32_t region = r1 ? 1u : (r2 ? 2u : (r4 ? 4u : (r3 ? 3u : (r5 ? 5u : (r6 ? 6u : 0u)))));
-    const float s = (va + vb) + vc;
-    const float num_a = region == 4u ? d1 : (region == 5u ? d2 : (region == 6u ? e1 : vb));
-    const float den_a = region == 4u ? d1 - d3 : (region == 5u ? d2 - d6 : (region == 6u ? e1 + e2 : s));
-    const bool one = region >= 4u || region == 0u;  // the regions with a quotient
-    const float qa = quotient(one ? num_a : 0.0f, one ? den_a : 1.0f);
-    const float qb = quotient(region == 0u ? vc : 0.0f, region == 0u ? s : 1.0f);
-    Closest r;
-    r.region = region;
-    r.u = region == 2u ? 1.0f : (region == 4u ? qa : (region == 6u ? 1.0f - qa : (region == 0u ? qa : 0.0f)));
-    r.v = region == 3u ? 1.0f : (region == 5u ? qa : (region == 6u ? qa : (region == 0u ? qb : 0.0f)));
-    const f3 raw = (a + ab * r.u) + ac * r.v;
-    const f3 lo = mk(__builtin_fminf(__builtin_fminf(a.x, b.x), c.x), __builtin_fminf(__builtin_fminf(a.y, b.y), c.y), __builtin_fminf(__builtin_fminf(a.z, b.z), c.z));
-    const f3 hi = mk(__builtin_fmaxf(__builtin_fmaxf(a.x, b.x), c.x), __builtin_fmaxf(__builtin_fmaxf(a.y, b.y), c.y), __builtin_fmaxf(__builtin_fmaxf(a.z, b.z), c.z));
-    r.q = mk(clamp_keep_nan(raw.x, lo.x, hi.x), clamp_keep_nan(raw.y, lo.y, hi.y), clamp_keep_nan(raw.z, lo.z, hi.z));
-    const f3 d = p - r.q;
-    r.d2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
-    return r;
-}
-
+// (closest_point() itself is rvpt_nearest.h's: the sphere sweeps of rvpt_sweep.h call it too)
 __device__ __forceinline__ Closest closest_point_row(const float4 *row, const f3 p)
 {
     const float4 a = row[0], b = row[1], c = row[2];

@@ -756,6 +756,22 @@ bool RVPT::box_overlaps_device(void *records, size_t n, int k)
     return check(backend_.read(ctx_, k == 1 ? RVPT_HIP_FORMAT_BOX_OVERLAPS : RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k), records, n * static_cast<size_t>(k) * sizeof(rvpt_box_overlap)),
                  "rvpt_hip_read");
 }
+bool RVPT::sweep_spheres(rvpt_sphere_sweep *records, size_t n)
+{
+    if (!sweep_spheres_device(records, n)) return false;  // (the library classifies the pointer)
+    if (!device_built_)  // the library numbered the leaf order it was given
+        for (size_t k = 0; k < n; ++k)
+            if (records[k].prim < order_.size()) records[k].prim = order_[records[k].prim];
+    return true;
+}
+bool RVPT::sweep_spheres_device(void *records, size_t n)
+{
+    if (!ctx_) {
+        error_ = "sweep_spheres before initialize()";
+        return false;
+    }
+    return check(backend_.read(ctx_, RVPT_HIP_FORMAT_SPHERE_SWEEPS, records, n * sizeof(rvpt_sphere_sweep)), "rvpt_hip_read");
+}
 bool RVPT::read_triangles(std::vector<rvpt_triangle> &triangles)
 {
     if (!ctx_) {

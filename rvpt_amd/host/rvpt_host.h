@@ -251,6 +251,13 @@ public:
     bool box_overlaps(rvpt_box_overlap *records, size_t n, int k = 1);
     // the same for n groups in device memory of the context's GPU (16-byte aligned), which never visit the host: the numbers stay as the LIBRARY numbers them
     bool box_overlaps_device(void *records, size_t n, int k = 1);
+    // Sphere sweeps (rvpt_hip_read with RVPT_HIP_FORMAT_SPHERE_SWEEPS; include/rvpt_hip.h: SPHERE SWEEPS): every record comes in as a sphere and the motion of
+    // its centre (org, radius, dir, tmax) and goes out as its first contact with the mesh (t, prim, u, v), in place; (prim, u, v) pipes into surface_points.
+    // prim numbers the triangles in the order they were ADDED, as trace_rays does (after a host build a tie between equal times is broken on the library's
+    // stored number, before this renumbering).  After initialize(); no update() is needed.
+    bool sweep_spheres(rvpt_sphere_sweep *records, size_t n);
+    // the same for `n` records in device memory of the context's GPU (16-byte aligned), which never visit the host: prim then stays as the LIBRARY numbers it
+    bool sweep_spheres_device(void *records, size_t n);
     // The geometry read-back (rvpt_hip_read with RVPT_HIP_FORMAT_TRIANGLES; include/rvpt_hip.h: TRIANGLES): the stored rows of the mesh as the last update,
     // pose or skin form left them — all 64 bytes of each, nothing recomputed — in the order the triangles were ADDED (after a host build the leaf order the
     // library holds is undone here).  After initialize(); no update() is needed.

@@ -78,6 +78,11 @@ BOX_OVERLAP_DTYPE = np.dtype([("lo", "<f4", (3,)), ("prim_from", "<u4"), ("hi", 
 BOX_MAX_GROUP = 4  # RVPT_HIP_BOX_MAX_GROUP: the largest k of a box query's groups, which list 4k - 1 numbers
 
 
+FORMAT_SPHERE_SWEEPS = 10  # RVPT_HIP_FORMAT_SPHERE_SWEEPS: rvpt_hip_read answers sphere sweeps, `dst` holds SPHERE_SWEEP_DTYPE records (Context.sweep_spheres)
+# rvpt_sphere_sweep (== scene.SPHERE_SWEEP_DTYPE): the out quad is laid out as RAY_HIT_DTYPE's
+SPHERE_SWEEP_DTYPE = np.dtype([("org", "<f4", (3,)), ("radius", "<f4"), ("dir", "<f4", (3,)), ("tmax", "<f4"), ("t", "<f4"), ("prim", "<u4"), ("u", "<f4"), ("v", "<f4")])
+
+
 def FORMAT_BOX_OVERLAPS_K(k) -> int:
     """RVPT_HIP_FORMAT_BOX_OVERLAPS_K(k), formats 65 .. 68: `dst` holds groups of k BOX_OVERLAP_DTYPE records, the box in the first, count and 4k - 1 numbers
     out (Context.box_overlaps(..., k=k)); k = 1 is FORMAT_BOX_OVERLAPS' own kernels and bytes.  A k that is no int in 1 .. BOX_MAX_GROUP raises before any call."""
@@ -763,6 +768,8 @@ class Context:
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use count_crossings_into")
         if fmt == FORMAT_BOX_OVERLAPS or (isinstance(fmt, int) and 65 <= fmt <= 64 + BOX_MAX_GROUP):
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use box_overlaps_into")
+        if fmt == FORMAT_SPHERE_SWEEPS:
+            raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds query records, not a frame: use sweep_spheres_into")
         if fmt == FORMAT_TRIANGLES:
             raise NativeError(ERR_INVALID, f"{what}: format {fmt} holds the stored triangle rows, not a frame: use read_triangles / read_triangles_into")
         if fmt == FORMAT_SURFACE_POINTS:
@@ -1004,6 +1011,32 @@ class Context:
         if count % k:
             raise NativeError(ERR_INVALID, f"box_overlaps_into: {count} records are not a multiple of k={k}: a box takes a group of {k} records")
         return self._query_into(records, fmt, BOX_OVERLAP_DTYPE, "box_overlaps_into", "BOX_OVERLAP_DTYPE")
+
+    def sweep_spheres(self, org, dir, radius, tmax=math.inf) -> np.ndarray:
+        """When and where the spheres of radius `radius` whose centres move along org[n, 3] + t dir[n, 3], t in [0, tmax], first touch the uploaded mesh —
+        include/rvpt_hip.h: SPHERE SWEEPS has the definition, the arithmetic and the numbering of prim.  radius and tmax are scalars or one value per sphere;
+        dir need not be unit (t is in its units), and dir = 0 asks whether the sphere overlaps the mesh where it stands.  Returns SPHERE_SWEEP_DTYPE[n]: t, prim,
+        and the pair (u, v) of the point of that triangle nearest to the centre at t, which Context.surface_points turns into the contact point and the stored
+        normal; prim == NO_PRIM (and t = tmax) where nothing is touched or the record is invalid."""
+        org = np.asarray(org, dtype=np.float32)
+        dirv = np.asarray(dir, dtype=np.float32)
+        if org.ndim == 0 or org.size % 3 or org.shape != dirv.shape or (org.ndim > 1 and org.shape[-1] != 3):
+            raise NativeError(ERR_INVALID, f"sweep_spheres: org[n, 3] and dir[n, 3] are needed, got shapes {tuple(org.shape)} and {tuple(dirv.shape)}")
+        org, dirv = org.reshape(-1, 3), dirv.reshape(-1, 3)
+        rec = np.zeros(org.shape[0], dtype=SPHERE_SWEEP_DTYPE)
+        rec["org"], rec["dir"] = org, dirv
+        for name, value in (("radius", radius), ("tmax", tmax)):
+            value = np.asarray(value, dtype=np.float32)
+            if value.ndim > 1 or (value.ndim == 1 and value.shape[0] != org.shape[0]):
+                raise NativeError(ERR_INVALID, f"sweep_spheres: {org.shape[0]} spheres, {name} of shape {tuple(value.shape)}")
+            rec[name] = value
+        return self.sweep_spheres_into(rec)
+
+    def sweep_spheres_into(self, records):
+        """rvpt_hip_read with FORMAT_SPHERE_SWEEPS in the caller's memory: `records` is a contiguous SPHERE_SWEEP_DTYPE array, or a contiguous float32 torch
+        tensor [n, 12] (48-byte records; prim is the bits of its float) on the host or on this context's device, as for trace_rays_into.  The in quads (org,
+        radius, dir, tmax) stay as they are, the out quad is written.  Returns records."""
+        return self._query_into(records, FORMAT_SPHERE_SWEEPS, SPHERE_SWEEP_DTYPE, "sweep_spheres_into", "SPHERE_SWEEP_DTYPE")
 
     def read_triangles(self) -> np.ndarray:
         """rvpt_hip_read with FORMAT_TRIANGLES: the stored triangle rows as the last update form left them — all 64 bytes of each, nothing recomputed — as

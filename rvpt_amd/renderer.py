@@ -549,6 +549,23 @@ class RVPT:
             quads[hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[quads[hit]]
         return rec
 
+    def sweep_spheres(self, org, dir, radius, tmax=float("inf"), contacts=False):
+        """Sphere sweeps against the scene as it is now (Context.sweep_spheres; include/rvpt_hip.h: SPHERE SWEEPS): when and where the spheres of radius
+        `radius` whose centres move along org[n, 3] + t dir[n, 3], t in [0, tmax], first touch the mesh.  Returns native.SPHERE_SWEEP_DTYPE records: t (in units
+        of dir; 0 for a sphere that already overlaps), u, v, and prim numbering the triangles in the order they were ADDED (native.NO_PRIM: nothing touched, t =
+        tmax), as trace_rays does.  Over a host-built tree a tie between equal times is broken on the stored number, before this renumbering.  contacts=True
+        pipes the answer through surface_points and returns (records, native.SURFACE_POINT_DTYPE records): the contact point on the triangle, the stored unit
+        normal and the material word of every hit, zeros and mat NO_PRIM beside a miss.  Needs initialize(), not update()."""
+        if self._ctx is None:
+            raise RuntimeError("sweep_spheres before initialize()")
+        rec = self._ctx.sweep_spheres(org, dir, radius, tmax)
+        if not self._device_built and rec.shape[0]:  # a host-built tree: the device numbers the leaf order it was given
+            hit = rec["prim"] != native.NO_PRIM
+            rec["prim"][hit] = np.asarray(self.primitive_indices, dtype=np.uint32)[rec["prim"][hit]]
+        if not contacts:
+            return rec
+        return rec, self.surface_points(rec["prim"], rec["u"], rec["v"])
+
     def overlapping(self, lo, hi) -> list:
         """For every closed box [lo[n, 3], hi[n, 3]] the numbers of ALL triangles that meet it (BOX OVERLAPS: the set A with prim_from = 0), ascending, in the
         order the triangles were ADDED: a list of n uint32 arrays.  Pages with the longest groups (15 numbers a call) and prim_from = the last listed number + 1

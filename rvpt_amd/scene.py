@@ -730,7 +730,14 @@ def closest_point_triangles(p, tris):
     verts = t.reshape(-1, 4, 4)[:, :3, :3] if t.ndim == 2 and t.shape[1] == 16 else t.reshape(-1, 3, 3)
     p = np.asarray(p, dtype=np.float32)
     single = p.ndim == 1
-    pp = p.reshape(-1, 1, 3)  # [m, 1, 3] against [n, 3]
+    q, dist2, u, v, region = _closest_point_pairs(p.reshape(-1, 1, 3), verts)  # [m, 1, 3] against [n, 3]
+    if single:
+        return q[0], dist2[0], u[0], v[0], region[0]
+    return q, dist2, u, v, region
+
+
+def _closest_point_pairs(pp, verts):
+    """closest_point_triangles' arithmetic for points pp[m, 1 or n, 3] against the vertices verts[n, 3, 3]: one point per row, or one per (row, triangle) pair."""
     a, b, c = verts[:, 0], verts[:, 1], verts[:, 2]
     one, zero = np.float32(1), np.float32(0)
     with np.errstate(all="ignore"):
@@ -754,8 +761,6 @@ def closest_point_triangles(p, tris):
         d = pp - q
         dist2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
     assert q.dtype == np.float32 and dist2.dtype == np.float32
-    if single:
-        return q[0], dist2[0], u[0], v[0], region[0]
     return q, dist2, u, v, region
 
 
@@ -934,6 +939,176 @@ def box_overlaps(tris, records, k: int = 1, perm=None, chunk: int = 1 << 22) -> 
             quads[box, 1:1 + listed.size] = listed
     out.view(np.uint32).reshape(n, k, 12)[:, :, 8:] = quads.reshape(n, k, 4)
     return out
+
+
+SPHERE_SWEEP_DTYPE = np.dtype([("org", "<f4", (3,)), ("radius", "<f4"), ("dir", "<f4", (3,)), ("tmax", "<f4"), ("t", "<f4"), ("prim", "<u4"), ("u", "<f4"),
+                               ("v", "<f4")])  # rvpt_sphere_sweep (== native.SPHERE_SWEEP_DTYPE)
+SWEEP_FEATURES = ("face", "vertex a", "vertex b", "vertex c", "edge ab", "edge bc", "edge ca")  # the columns of sweep_feature_times
+
+
+def sweep_slab(p, d, r, tmax, lo, hi):
+    """Step 1 of a SPHERE SWEEP (include/rvpt_hip.h: SPHERE SWEEPS): the centre's path p + t*d, t in [0, tmax], against the box [lo, hi] inflated by one rounded
+    operation per side, L = lo - r and H = hi + r.  p, d, lo, hi [..., 3], r and tmax [...], broadcast against each other; float32 throughout.  Per axis with
+    d == 0 the two comparisons p < L, p > H reject and nothing else happens; otherwise inv = 1/d, t1 = (L - p)*inv, t2 = (H - p)*inv, near and far are t1 and t2
+    by the sign of d, and t_in = near > t_in ? near : t_in from 0, t_out = far < t_out ? far : t_out from tmax — selects, so that a NaN changes nothing.  Passes
+    iff nothing rejected, t_in <= t_out and t_in < +inf.  Every operation is monotone in lo and hi, which is the pruning lemma.  Returns (passes, t_in)."""
+    f32 = np.float32
+    p, d, lo, hi = (np.asarray(x, dtype=f32) for x in (p, d, lo, hi))
+    r, tmax = np.asarray(r, dtype=f32), np.asarray(tmax, dtype=f32)
+    with np.errstate(all="ignore"):
+        low, high = lo - r[..., None], hi + r[..., None]
+        zero = d == 0
+        inv = f32(1) / np.where(zero, f32(1), d)
+        t1, t2 = (low - p) * inv, (high - p) * inv
+        near, far = np.where(d > 0, t1, t2), np.where(d > 0, t2, t1)
+        outside = (zero & ((p < low) | (p > high))).any(axis=-1)
+        shape = np.broadcast(outside, tmax).shape
+        t_in, t_out = np.zeros(shape, dtype=f32), np.broadcast_to(tmax, shape).astype(f32)
+        for k in range(3):
+            nk, fk = np.where(zero[..., k], f32(-np.inf), near[..., k]), np.where(zero[..., k], f32(np.inf), far[..., k])
+            t_in = np.where(nk > t_in, nk, t_in)
+            t_out = np.where(fk < t_out, fk, t_out)
+        passes = ~outside & (t_in <= t_out) & (t_in < f32(np.inf))
+    assert t_in.dtype == f32
+    return passes, t_in
+
+
+def _cross_rounded(x, y):
+    return np.stack([x[..., 1] * y[..., 2] - x[..., 2] * y[..., 1], x[..., 2] * y[..., 0] - x[..., 0] * y[..., 2], x[..., 0] * y[..., 1] - x[..., 1] * y[..., 0]], axis=-1)
+
+
+def sweep_feature_times(p, d, r, tmax, verts):
+    """Step 2 of a SPHERE SWEEP: the contact time of each of the seven features of every triangle verts[n, 3, 3] for the records p, d [m, 3], r, tmax [m],
+    float32 [m, n, 7] in the order of SWEEP_FEATURES, +inf where a feature has none.  Every accepted time is a number in [0, tmax]."""
+    f32 = np.float32
+    inf, zero = f32(np.inf), f32(0)
+    pp, dd = p[:, None, :], d[:, None, :]
+    rr, big_t = (r * r)[:, None], tmax[:, None]
+    a, b, c = verts[:, 0], verts[:, 1], verts[:, 2]
+    shape = (p.shape[0], verts.shape[0])
+    out = np.full(shape + (7,), inf, dtype=f32)
+    big_a = np.broadcast_to(_dot_rounded(dd, dd), shape)
+
+    def root(c0, b0, a0, gate):  # the smaller root of a0*t*t + 2*b0*t + c0 as c0 / (sqrt(b0*b0 - a0*c0) - b0), where the centre starts outside and approaches
+        disc = b0 * b0 - a0 * c0
+        ok = gate & (c0 > 0) & (b0 < 0) & (a0 > 0) & (disc >= 0)
+        t = c0 / np.where(ok, np.sqrt(np.where(ok, disc, zero)) - b0, f32(1))
+        return t, ok & (t >= 0) & (t <= big_t)
+
+    for k, (x0, x1) in enumerate(((a, b), (b, c), (c, a))):
+        m = pp - x0
+        dm = np.broadcast_to(dd, m.shape)
+        big_b, big_c = _dot_rounded(m, dm), _dot_rounded(m, m) - rr
+        t, ok = root(big_c, big_b, big_a, True)
+        out[..., 1 + k] = np.where(big_c <= 0, zero, np.where(ok, t, inf))
+        e = np.broadcast_to(x1 - x0, m.shape)
+        ee, md, nd = _dot_rounded(e, e), _dot_rounded(m, e), _dot_rounded(dm, e)
+        ca, cb, cc = ee * big_a - nd * nd, ee * big_b - nd * md, ee * big_c - md * md
+        t, ok = root(cc, cb, ca, ee > 0)
+        s = md + t * nd
+        ok = ok & (s >= 0) & (s <= ee)
+        inside = (ee > 0) & (cc <= 0) & (md >= 0) & (md <= ee)
+        out[..., 4 + k] = np.where(inside, zero, np.where(ok, t, inf))
+    n = _cross_rounded(b - a, c - a)
+    nn = _dot_rounded(n, n)
+    m = pp - a
+    h = _dot_rounded(m, np.broadcast_to(n, m.shape))
+    rn = r[:, None] * np.sqrt(nn)
+    hs, dn = np.abs(h), _dot_rounded(np.broadcast_to(dd, m.shape), np.broadcast_to(n, m.shape))
+    dns = np.where(h > 0, dn, -dn)
+    within = hs <= rn
+    moving = ~within & (hs > rn) & (dns < 0)
+    t = np.where(within, zero, (rn - hs) / np.where(moving, dns, f32(1)))
+    ok = (nn > 0) & (within | (moving & (t >= 0) & (t <= big_t)))
+    t = np.where(ok, t, zero)
+    centre = pp + dd * t[..., None]
+    region = _closest_point_pairs(centre, verts)[4]
+    out[..., 0] = np.where(ok & (region == 0), t, inf)
+    assert out.dtype == f32
+    return out
+
+
+def sweep_sphere_triangles(org, direction, radius, tmax, tris):
+    """The per-triangle arithmetic of a SPHERE SWEEP (include/rvpt_hip.h: SPHERE SWEEPS), vectorised: the candidate of every triangle of `tris` (float32[n, 16]
+    rows, or [n, 3, 3] vertices) for one record (org[3], direction[3], radius, tmax) or for m of them ([m, 3], [m, 3], [m], [m]).  float32 throughout, every
+    product, sum, quotient and square root rounded on its own, in the header's order: the own box's slab test (sweep_slab) gives t_in, the seven features
+    (sweep_feature_times) give t_tri as their smallest time, t = t_in > t_tri ? t_in : t_tri, and (u, v) are closest_point_triangles' pair for the centre
+    org + direction*t.  A triangle with a non-finite vertex component has no candidate.  The record is taken as it is: whether it is valid is sphere_sweeps'
+    business.  Returns (has[..., n] bool, t[..., n], u[..., n], v[..., n], feature[..., n] int — the index into SWEEP_FEATURES of the first feature at t_tri)."""
+    f32 = np.float32
+    t_ = np.asarray(tris, dtype=f32)
+    verts = t_.reshape(-1, 4, 4)[:, :3, :3] if t_.ndim == 2 and t_.shape[1] == 16 else t_.reshape(-1, 3, 3)
+    p, d = np.asarray(org, dtype=f32), np.asarray(direction, dtype=f32)
+    single = p.ndim == 1
+    p, d = p.reshape(-1, 3), d.reshape(-1, 3)
+    r = np.broadcast_to(np.asarray(radius, dtype=f32), p.shape[:1]).astype(f32)
+    big_t = np.broadcast_to(np.asarray(tmax, dtype=f32), p.shape[:1]).astype(f32)
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(verts).all(axis=(1, 2))
+        lo, hi = np.fmin(np.fmin(verts[:, 0], verts[:, 1]), verts[:, 2]), np.fmax(np.fmax(verts[:, 0], verts[:, 1]), verts[:, 2])
+        passes, t_in = sweep_slab(p[:, None, :], d[:, None, :], r[:, None], big_t[:, None], lo, hi)
+        times = sweep_feature_times(p, d, r, big_t, verts)
+        t_tri = times.min(axis=-1)
+        feature = times.argmin(axis=-1)
+        t = np.where(t_in > t_tri, t_in, t_tri)
+        has = finite & passes & (t < f32(np.inf))
+        t = np.where(has, t, f32(0))
+        centre = p[:, None, :] + d[:, None, :] * t[..., None]
+        u, v = _closest_point_pairs(centre, verts)[2:4]
+    assert t.dtype == f32 and u.dtype == f32
+    if single:
+        return has[0], t[0], u[0], v[0], feature[0]
+    return has, t, u, v, feature
+
+
+def sweep_records(org, direction, radius, tmax=np.inf) -> np.ndarray:
+    """SPHERE_SWEEP_DTYPE[m] with the in quads filled (radius and tmax a scalar or one per record) and the out quad zero."""
+    p = np.asarray(org, dtype=np.float32).reshape(-1, 3)
+    rec = np.zeros(p.shape[0], dtype=SPHERE_SWEEP_DTYPE)
+    rec["org"], rec["dir"] = p, np.asarray(direction, dtype=np.float32).reshape(-1, 3)
+    rec["radius"], rec["tmax"] = np.asarray(radius, dtype=np.float32), np.asarray(tmax, dtype=np.float32)
+    return rec
+
+
+def sweep_valid(records) -> np.ndarray:
+    """Which records of a SPHERE SWEEP are valid: org and dir finite, radius a finite number >= 0, tmax a number >= 0 (+inf allowed; -0.0 is 0)."""
+    rec = np.asarray(records)
+    with np.errstate(all="ignore"):
+        return np.isfinite(rec["org"]).all(axis=1) & np.isfinite(rec["dir"]).all(axis=1) & np.isfinite(rec["radius"]) & (rec["radius"] >= 0) & (rec["tmax"] >= 0)
+
+
+def sphere_sweeps(tris, records, perm=None, chunk: int = 1 << 18, features=None) -> np.ndarray:
+    """The normative statement of a SPHERE SWEEP (include/rvpt_hip.h: SPHERE SWEEPS), by brute force: every triangle's candidate (t_i, prim_i) from
+    sweep_sphere_triangles, the answer the lexicographically smallest one — among equal t the smaller reported number, which is the index, or perm[index] with
+    a permutation.  `tris` (float32[n, 16]) in stored order; `records` SPHERE_SWEEP_DTYPE[m].  An invalid record (sweep_valid) and a miss go out as t = the bits
+    of tmax, prim NO_PRIM, u = v = 0.  Returns a copy of `records` with the out quads written and the in quads as they came.  `features`, an int array [m], is
+    filled with the deciding feature of each hit (the index into SWEEP_FEATURES) and -1 elsewhere."""
+    rec = np.asarray(records)
+    if rec.dtype != SPHERE_SWEEP_DTYPE:
+        raise ValueError(f"sphere_sweeps: SPHERE_SWEEP_DTYPE records are needed, got {rec.dtype}")
+    out = np.ascontiguousarray(rec).copy().reshape(-1)
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    n = t.shape[0]
+    number = np.arange(n, dtype=np.uint32) if perm is None else np.asarray(perm, dtype=np.uint32).reshape(n)
+    out["t"], out["prim"], out["u"], out["v"] = out["tmax"], NO_PRIM, 0, 0
+    if features is not None:
+        features[...] = -1
+    rows = np.flatnonzero(sweep_valid(out))
+    step = max(1, chunk // max(n, 1))
+    for at in range(0, rows.size if n else 0, step):
+        sel = rows[at:at + step]
+        has, tt, u, v, feature = sweep_sphere_triangles(out["org"][sel], out["dir"][sel], out["radius"][sel], out["tmax"][sel], t)
+        key = np.where(has, tt, np.float32(np.inf))
+        best = has & (key == key.min(axis=1, keepdims=True))
+        hit = best.any(axis=1)
+        i = np.argmin(np.where(best, number[None, :].astype(np.int64), np.int64(1) << 40), axis=1)  # the smallest reported number among equal t
+        k = np.arange(sel.size)
+        got = out[sel]
+        got["t"][hit], got["prim"][hit], got["u"][hit], got["v"][hit] = tt[k, i][hit], number[i][hit], u[k, i][hit], v[k, i][hit]
+        out[sel] = got
+        if features is not None:
+            features[sel] = np.where(hit, feature[k, i], -1)
+    return out.reshape(rec.shape)
 
 
 SURFACE_POINT_DTYPE =np.dtype([("prim", "<u4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("point", "<f4", (3,)), ("mat", "<u4"), ("normal", "<f4", (3,)),
